@@ -52,6 +52,10 @@ and, at N = 1, one sub-record per remaining BASELINE.json config and claim:
   cfg4, general_values   as before.
 `--only NAME[,NAME]` runs just those sub-records (profiling); `--krylov gmres` times
 GMRES(--restart) with its Gram-Schmidt passes counted in `iteration.bytes`.
+`--dump-outputs DIR` writes what the headline's last timed step computed, for comparing two
+builds output for output: DIR/x.npy (float64), the solution a caller of the solve receives --
+all of it up to DUMP_MAX rows, else a fixed seeded sample of DUMP_MAX rows (dump_sample); for
+an SpMV-only workload DIR/y.npy, y = S b of the operator the timed launches apply.
 """
 import argparse
 import ctypes
@@ -77,6 +81,8 @@ WORKLOADS = {
     "lap3d": "lap3d:nx=400,ny=400,nz=400",
     "powerlaw": "powerlaw:n=8000000,gamma=1.585350372615855,max=4096,seed=20240607",
 }
+DUMP_MAX = 1 << 22      # entries per dumped vector: 32 MB of float64, under the 64 MB a dump may take
+DUMP_SEED = 20240607
 
 
 def parse():
@@ -143,7 +149,15 @@ def parse():
     p.add_argument("--verify", type=int, default=1,
                    help="1 = a solve counts only once ||b - S x|| <= tol ||b|| holds for the residual "
                         "recomputed from x (correction solves inside the timed region if needed)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy "
+                        "(x of the solve; y = S b for an SpMV-only workload), sampled beyond %d rows" % DUMP_MAX)
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.only:
+        p.error("--dump-outputs writes the headline's outputs; --only runs no headline")
+    return a
 
 
 def read_file_matrix(path):
@@ -350,9 +364,39 @@ def gmres_bytes(n, sp, m, steps):
     return tot
 
 
-def run_workload(a, c, workload, steps, warmup, cpu_leg):
+def dump_sample(n):
+    """Rows of a length-n output that --dump-outputs writes, ascending: all of them up to DUMP_MAX,
+    else one row in each of DUMP_MAX equal strata at an offset drawn from DUMP_SEED -- the same
+    rows for the same n on every run and every build."""
+    import numpy as np
+    if n <= DUMP_MAX:
+        return np.arange(n, dtype=np.int64)
+    lo = np.arange(DUMP_MAX, dtype=np.int64) * n // DUMP_MAX
+    hi = np.arange(1, DUMP_MAX + 1, dtype=np.int64) * n // DUMP_MAX
+    return lo + (np.random.default_rng(DUMP_SEED).random(DUMP_MAX) * (hi - lo)).astype(np.int64)
+
+
+def dump_outputs(c, out_dir, name, d_v, r0, n):
+    """Write the dump_sample(n) rows of a distributed length-n vector (this rank holds d_v = rows
+    [r0, r0 + len(d_v))) to out_dir/name.npy as float64, from rank 0."""
+    import numpy as np
+    idx = dump_sample(n)
+    mine = np.nonzero((idx >= r0) & (idx < r0 + d_v.numel()))[0]
+    v = torch.zeros(len(idx), dtype=torch.float64, device=d_v.device)
+    v[torch.from_numpy(mine).to(d_v.device)] = d_v[torch.from_numpy(idx[mine] - r0).to(d_v.device)]
+    if c.dist_on:   # every row sits on exactly one rank: the sum over ranks is the sample
+        v = v.to(c.cdev)
+        dist.all_reduce(v)
+    if c.rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, name + ".npy"), v.cpu().numpy())
+        print("dump: %s (%d of %d rows) -> %s" % (name, len(idx), n, out_dir), file=sys.stderr, flush=True)
+
+
+def run_workload(a, c, workload, steps, warmup, cpu_leg, dump=""):
     """Build the operator (this rank's rows), warm up, time EXACTLY `steps` solves
-    between barriers; returns the record (rank 0's view, times = max over ranks)."""
+    between barriers; returns the record (rank 0's view, times = max over ranks).
+    `dump`: directory that receives what the last timed step computed (dump_outputs)."""
     rank, world = c.rank, c.world
     t_setup = time.perf_counter()
     spmv_only = False
@@ -447,6 +491,12 @@ def run_workload(a, c, workload, steps, warmup, cpu_leg):
         # config 5: SpMV throughput only (the operator is unsymmetric)
         ms = solver.time_spmv(warmup * 10, steps * 20)
         barrier()
+        if dump:
+            # the timed launches hand nothing back: the same operator applied to b, the one input a caller has
+            d_y = torch.empty_like(d_x)
+            solver.spmv_dev(d_b, d_y)
+            dump_outputs(c, dump, "y", d_y, r0, n)
+            del d_y
         gbps = bytes_spmv / ms / 1e6
         rec = {"metric": "fp64_csr_spmv_GBps", "value": gbps * world, "unit": "GB/s",
                "n_gpus": world, "steps": steps * 20, "warmup": warmup * 10,
@@ -490,6 +540,8 @@ def run_workload(a, c, workload, steps, warmup, cpu_leg):
         sys.exit("solve did not converge (status %d after %d iterations): no valid number"
                  % (res.status, res.iters))
     its = iters // max(steps, 1)
+    if dump:
+        dump_outputs(c, dump, "x", d_x, r0, n)
 
     # ---- outside the timed region: ||b - S x|| / ||b|| recomputed from x, by torch ----
     d_y = torch.empty_like(d_x)
@@ -741,7 +793,7 @@ def main():
                 line[k] = f(a, c)
         print(json.dumps(line), flush=True)
         return
-    line = run_workload(a, c, a.workload, a.steps, a.warmup, cpu_leg=True)
+    line = run_workload(a, c, a.workload, a.steps, a.warmup, cpu_leg=True, dump=a.dump_outputs)
     spec = WORKLOADS.get(a.workload, a.workload)
     if a.cfg4 and line["metric"] == "cg_solves_per_sec" and not spec.startswith("lap3d"):
         r4 = run_workload(a, c, "lap3d", a.cfg4_steps, 1, cpu_leg=False)

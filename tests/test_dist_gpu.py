@@ -87,21 +87,26 @@ def test_multi_process_gmres(tmp_path):
     assert np.linalg.norm(x - xo) / np.linalg.norm(xo) <= 1e-8
 
 
-def test_bench_two_ranks_on_one_gpu():
+def test_bench_two_ranks_on_one_gpu(tmp_path):
     """bench.py's N > 1 branch end to end (gloo for torch.distributed, the test
-    double for the library's collectives): same iteration count as N = 1."""
-    common = ["--workload", "lap2d:nx=700,ny=500", "--tol", "1e-8", "--steps", "2", "--warmup", "1",
+    double for the library's collectives): same iteration count as N = 1.  Both
+    lines dump x (--dump-outputs): the whole solution, in the caller's row order,
+    gathered over the ranks for N = 2."""
+    import scipy.sparse as sps
+    spec = "lap2d:nx=700,ny=500"
+    common = ["--workload", spec, "--tol", "1e-8", "--steps", "2", "--warmup", "1",
               "--cpu-seconds", "0", "--cfg4", "0"]
     env = _env()
     env["LSB_BENCH_BACKEND"] = "gloo"
     env["LSB_BENCH_ONE_GPU"] = "1"
-    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common,
+    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common
+                        + ["--dump-outputs", str(tmp_path / "one")],
                         capture_output=True, text=True, timeout=600)
     assert r1.returncode == 0, r1.stderr[-2000:]
     one = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29655", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2"] + common
+           "--gpus", "2"] + common + ["--dump-outputs", str(tmp_path / "two")]
     r2 = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r2.returncode == 0, (r2.stdout[-1500:], r2.stderr[-3000:])
     lines = [l for l in r2.stdout.splitlines() if l.startswith("{")]
@@ -116,6 +121,13 @@ def test_bench_two_ranks_on_one_gpu():
     assert one["per_rank"] is None and len(pr["rows"]) == 2 and sum(pr["rows"]) == 350000
     assert sum(pr["nnz"]) == two["config"]["nnz"] and 0 < pr["iteration_us"]["min"] <= pr["iteration_us"]["max"]
     assert 0 <= pr["spmv_us"]["min"] <= pr["spmv_us"]["max"]
+    A = la.lsbench_matrix_synth(spec)
+    S = sps.csr_matrix((A.vals, A.cols.astype(np.int64), A.offs.astype(np.int64)), shape=(A.nrows, A.nrows))
+    b = O.rhs(A.nrows)
+    for d in ("one", "two"):
+        x = np.load(tmp_path / d / "x.npy")
+        assert x.dtype == np.float64 and x.shape == (350000,)
+        assert np.linalg.norm(b - S @ x) / np.linalg.norm(b) <= 1e-8 * (1 + 1e-6), d
 
 
 @pytest.mark.parametrize("ngpus,comm,matrix", [

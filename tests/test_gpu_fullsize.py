@@ -188,20 +188,24 @@ def test_lap3d_64m_rows(hip):
         assert abs(rp.relres - rel1) <= 1e-9 * rel1
 
 
-def test_bench_line_contract():
+def test_bench_line_contract(tmp_path):
     """`python bench.py` end to end at full size: ONE JSON line with the contract's keys, the
     roofline and cpu_baseline objects, a solve that is converged on the residual recomputed from
     x -- and a sub-record for every other BASELINE.json config (cfg2, cfg4, cfg5; general_values)
-    plus csr_kernel, the SpMV figure that follows SURVEY 8(d) to the letter."""
+    plus csr_kernel, the SpMV figure that follows SURVEY 8(d) to the letter.  --dump-outputs
+    writes the headline's x as its fixed sample of DUMP_MAX rows."""
     import json
     import os
     import subprocess
     import sys
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
-                        "--cpu-seconds", "3", "--cfg4-steps", "1"], capture_output=True, text=True,
-                       timeout=900)
+                        "--cpu-seconds", "3", "--cfg4-steps", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
+    x = np.load(tmp_path / "x.npy")
+    assert sorted(os.listdir(tmp_path)) == ["x.npy"] and x.dtype == np.float64 and x.shape == (1 << 22,)
+    assert np.isfinite(x).all() and x.max() > 0
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])

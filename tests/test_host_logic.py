@@ -955,3 +955,24 @@ def test_bench_quotes_pmc_traffic_only_for_what_it_was_measured_on(tmp_path, mon
     one = bench.gmres_bytes(n, sp, 30, 1)
     assert one == 24 * n + 8 * n * 4 + 32 * n + sp + 2 * 8 * n * 2 + 2 * 8 * n * 3
     assert bench.gmres_bytes(n, sp, 30, 31) - bench.gmres_bytes(n, sp, 30, 30) == one + 16 * n + sp + 8 * n * (1 - 30) + 8 * n * 30 - 8 * n
+
+
+def test_bench_dump_sample_is_fixed_and_fits_the_budget(monkeypatch):
+    """bench.py --dump-outputs: an output of up to DUMP_MAX rows is written whole; a longer one as
+    DUMP_MAX distinct rows in ascending order, one per equal stratum, the same on every call -- so
+    two builds' dumps of the same workload compare row for row -- and at most 64 MB of float64."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    K = bench.DUMP_MAX
+    assert 8 * K <= 64 << 20
+    assert np.array_equal(bench.dump_sample(350000), np.arange(350000))
+    assert np.array_equal(bench.dump_sample(K), np.arange(K))
+    for n in (K + 1, 9998244, 64000000):
+        idx = bench.dump_sample(n)
+        assert len(idx) == K and idx[0] >= 0 and idx[-1] < n and (np.diff(idx) > 0).all()
+        stratum = np.arange(K, dtype=np.int64)
+        assert ((stratum * n // K <= idx) & (idx < (stratum + 1) * n // K)).all()
+        assert np.array_equal(idx, bench.dump_sample(n))
