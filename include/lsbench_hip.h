@@ -497,8 +497,25 @@ int lsb_tmpl_check(const struct lsb_sell *S, const struct lsb_sell_vc *V, const 
  * mask}; the items run z-group after z-group (at most kmax planes each, as equal as they come),
  * positions ascending, and XCD k takes [xbeg[k], xbeg[k+1]): a contiguous run with an eighth of the
  * slices -- a band of planes.
- * Lossless: the same operands and products in the same order as k_spmv_tmpl / k_spmv_sell16. */
+ * Lossless: the same operands and products in the same order as k_spmv_tmpl / k_spmv_sell16.
+ * WALK DIRECTION: a column re-reads the plane below its first slice and the plane above its last, and
+ * the column next to it in z owns that plane.  Walked upward both, column g asks for its bottom halo at
+ * step 0 and column g - 1 for the same plane at its last step: by then the L2 has turned over.  Where a
+ * z-group's neighbours are dealt into the same turn of the workgroups (2 period <= the items an XCD
+ * takes per turn, LSB_TMPL_COL_TURN), the z-groups of odd index walk DOWNWARD: two neighbouring columns
+ * then touch their shared planes at the same step.  down[i / 32] bit i % 32 = item i is walked from its
+ * top slice down (= the parity of its z-group, for columns of >= 3 slices: the PCG kernels take shorter
+ * items slice by slice, upward, and the SpMV forms the same dot partials as they do); down = NULL: every
+ * item upward.  The items themselves
+ * are the same either way; the device plan carries the bits behind the items (LSB_TMPL_COL_DOWN). */
 #define LSB_TMPL_COL_MAX 16
+/* the resident grid of the two-launch PCG kernels (lsb_k_pcg_col_px / _r) and the items an XCD takes per turn
+ * of it (4 waves per workgroup, 8 XCDs) -- what the walk directions are planned against */
+#define LSB_TMPL_COL_GRID(nfar) ((nfar) >= 2 ? 768u : 1280u)
+#define LSB_TMPL_COL_TURN(nfar) (4u * LSB_TMPL_COL_GRID(nfar) / 8u)
+/* the device plan: xbeg[9] at [0, 9), [LSB_TMPL_COL_DOWN] = the offset in words of the direction bits
+ * (0: none), the items from word 16, the bits behind them */
+#define LSB_TMPL_COL_DOWN 9
 #define LSB_TMPL_COL_LOCKSTEP 0x80000000u /* bit 31 of an item's slice count: the four items of a workgroup's
                                              turn are columns of one length (a barrier per plane keeps them in step) */
 struct lsb_tmpl_cols {
@@ -509,6 +526,7 @@ struct lsb_tmpl_cols {
   unsigned long long in_cols;   /* slices inside columns (the rest are single items) */
   int centre0;                  /* every column's centre slot has base 0 (the diagonal): where the fused
                                    dot is with the gathered vector itself, the centre pair is its operand */
+  unsigned *down;               /* (nitem + 31) / 32 words: bit i = item i walks downward; NULL: none does */
 };
 /* NULL where the layout has no such columns (period < 8, no shaped template with plane-reaching
  * far slots) or fewer than 3/4 of the slices fall inside columns. */
@@ -521,7 +539,8 @@ void lsb_tmpl_cols_free(struct lsb_tmpl_cols *C);
 /* The rules k_spmv_tmpl_col relies on, as host assertions (run at every upload): every slice in
  * [s_lo, s_hi) in exactly one item, none outside; a column's slices s + k period share the item's template -- shaped,
  * constant or masked slots only, outermost far slots one plane away -- and its mask words bit
- * for bit.  0 or a rule number with the rule in `why`. */
+ * for bit; with direction bits, only where the deal allows them and every item's bit the parity of its
+ * z-group (0 for items of fewer than 3 slices).  0 or a rule number with the rule in `why`. */
 int lsb_tmpl_cols_check(const struct lsb_sell_tmpls *T, const struct lsb_tmpl_cols *C, char *why, size_t whylen);
 /* mean |col - (row + row_begin)| over a sample of the rows */
 double lsb_csr_mean_scatter(const struct csr *A, unsigned row_begin);

@@ -118,7 +118,8 @@ class TmplCols(C.Structure):
     """struct lsb_tmpl_cols."""
     _fields_ = [("nitem", C.c_uint), ("kmax", C.c_uint), ("period", C.c_uint), ("s_lo", C.c_uint), ("s_hi", C.c_uint),
                 ("xbeg", C.c_uint * 9),
-                ("item", C.POINTER(C.c_uint)), ("in_cols", C.c_ulonglong), ("centre0", C.c_int)]
+                ("item", C.POINTER(C.c_uint)), ("in_cols", C.c_ulonglong), ("centre0", C.c_int),
+                ("down", C.POINTER(C.c_uint))]
 
 
 class Binned(C.Structure):

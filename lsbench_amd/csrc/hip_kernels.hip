@@ -1652,13 +1652,14 @@ template <int NF> struct col_tmpl { // the column's template, in scalar register
   int bc, bl[NF > 1 ? NF - 1 : 1], bh[NF > 1 ? NF - 1 : 1];
   double k0, kl[NF > 1 ? NF - 1 : 1], kc, kh[NF > 1 ? NF - 1 : 1], kL;
 };
-// gu = global row of lane 0's first row in this step's slice; lrow = its local row
+// gu = global row of lane 0's first row in this step's slice; lrow = its local row; D = rows from a plane to the one
+// ahead of it in the walk (+ a plane upward, - a plane downward)
 template <int NF, int DOT>
 __device__ __forceinline__ void col_issue(col_ops<NF> &o, sell_d2u &cnext, const col_tmpl<NF> &T, const double *__restrict__ x,
-                                          const double *__restrict__ xdot, long long gu, unsigned lrow, unsigned P,
+                                          const double *__restrict__ xdot, long long gu, unsigned lrow, long long D,
                                           unsigned xlen, unsigned lane, bool with_next) {
   if (with_next)
-    cnext = *(const sell_d2u *)(x + (gu + T.bc + (long long)P) + 2 * lane);
+    cnext = *(const sell_d2u *)(x + (gu + T.bc + D) + 2 * lane);
 #pragma unroll
   for (int k = 0; k < NF - 1; k++) {
     o.lo[k] = *(const sell_d2u *)(x + (gu + T.bl[k]) + 2 * lane);
@@ -1702,7 +1703,17 @@ __device__ __forceinline__ void col_compute(const col_ops<NF> &o, const sell_d2u
     dot = fma(a0, o.xd.x, dot), dot = fma(a1, o.xd.y, dot);
 }
 
-#define LSB_COL_HEAD 16 // unsigneds in front of the items: xbeg[NXCD + 1]
+#define LSB_COL_HEAD 16 // unsigneds in front of the items: xbeg[NXCD + 1], [LSB_TMPL_COL_DOWN] the direction bits' offset
+// The walk direction of a column (include/lsbench_hip.h): item `it` walks from its top slice DOWNWARD where the plan
+// has direction bits and its bit is set.  A downward walk is the upward one mirrored: it starts at the column's top
+// plane with the plane above it as the one "behind", and the plane ahead is the one below.  Every row's products keep
+// their order -- plane below first, plane above last -- only the roles of the three registers of centre pairs turn
+// round: y, q, p' and x are the same bits either way; a dot's per-lane terms come in the reverse plane order.
+// The direction is wave-uniform: what a step selects between (the planes behind and ahead) is a v_cndmask per
+// register, no branch.
+__device__ __forceinline__ bool col_walks_down(const unsigned *__restrict__ plan, unsigned dofs, unsigned it) {
+  return dofs && ((plan[dofs + (it >> 5)] >> (it & 31u)) & 1u);
+}
 // (a loaded dot operand is four more registers per step in flight: five workgroups per CU instead of six
 // rather than spills -- the walk runs best from three or four anyway)
 template <int NF, int DOT>
@@ -1719,6 +1730,7 @@ __global__ __launch_bounds__(WG, DOT == 2 ? 5 : 6) void k_spmv_tmpl_col(
   const unsigned gx = gridDim.x / NXCD, xcd = blockIdx.x % NXCD, slot = blockIdx.x / NXCD;
   const unsigned i0 = plan[xcd], i1 = plan[xcd + 1];
   const u4v *__restrict__ items = (const u4v *)(plan + LSB_COL_HEAD);
+  const unsigned dofs = plan[LSB_TMPL_COL_DOWN];
   const int stopped = st ? st->status : 0; // tested behind the first loads
   const unsigned P = period * LSB_SELL_ROWS; // rows of a plane
   double dot = 0.0;
@@ -1744,14 +1756,6 @@ __global__ __launch_bounds__(WG, DOT == 2 ? 5 : 6) void k_spmv_tmpl_col(
         C.kl[k] = T->cst[1 + k], C.kh[k] = T->cst[NF + 3 + k];
       }
       const int side_k[2] = {T->kidx[NF], T->kidx[NF + 2]}, side_kd[2] = {T->kind[NF], T->kind[NF + 2]};
-      long long gu = (long long)s * LSB_SELL_ROWS + row_begin;
-      unsigned lrow = s * LSB_SELL_ROWS;
-      // prologue: the operands of step 0 -- the plane below, the centre, the plane above
-      col_ops<NF> cur, nxt;
-      sell_d2u cm = *(const sell_d2u *)(x + (gu + C.bc - (long long)P) + 2 * lane);
-      sell_d2u c0 = *(const sell_d2u *)(x + (gu + C.bc) + 2 * lane);
-      sell_d2u cp, cn;
-      col_issue<NF, DOT>(cur, cp, C, x, xdot, gu, lrow, P, xlen, lane, true);
       // the column's masks (wave-uniform, scalar loads beside the gathers) and side values, once
       unsigned long long mk[2][2] = {{0ull, 0ull}, {0ull, 0ull}};
 #pragma unroll
@@ -1760,38 +1764,52 @@ __global__ __launch_bounds__(WG, DOT == 2 ? 5 : 6) void k_spmv_tmpl_col(
           const unsigned long long *mp = mask + 2 * ((size_t)mb + (unsigned)side_k[side]);
           mk[side][0] = mp[0], mk[side][1] = mp[1];
         }
+      const bool down = col_walks_down(plan, dofs, it); // wave-uniform
+      const unsigned s0 = down ? s + (K - 1) * period : s; // the plane of step 0
+      const long long D = down ? -(long long)P : (long long)P;
+      const unsigned Du = (unsigned)D;
+      long long gu = (long long)s0 * LSB_SELL_ROWS + row_begin;
+      unsigned lrow = s0 * LSB_SELL_ROWS;
+      // prologue: the operands of step 0 -- the plane behind, the centre, the plane ahead
+      col_ops<NF> cur, nxt;
+      sell_d2u cb = *(const sell_d2u *)(x + (gu + C.bc - D) + 2 * lane);
+      sell_d2u c0 = *(const sell_d2u *)(x + (gu + C.bc) + 2 * lane);
+      sell_d2u ca, cn;
+      col_issue<NF, DOT>(cur, ca, C, x, xdot, gu, lrow, D, xlen, lane, true);
       double vm0 = T->cst[NF], vm1 = vm0, vp0 = T->cst[NF + 2], vp1 = vp0;
       if (side_k[0] >= 0 || side_k[1] >= 0)
         tmpl_side_values(T, NF, 0u, lane, side_k, side_kd, mk, vals, f32, vm0, vm1, vp0, vp1);
       if (stopped)
         return;
       // step 0 (K >= 2: there is a next one), steps 1 .. K-2, step K-1
-      col_issue<NF, DOT>(nxt, cn, C, x, xdot, gu + (long long)P, lrow + P, P, xlen, lane, true);
+      col_issue<NF, DOT>(nxt, cn, C, x, xdot, gu + D, lrow + Du, D, xlen, lane, true);
       double a0, a1;
-      col_compute<NF, DOT>(cur, cm, c0, cp, C, vm0, vm1, vp0, vp1, lane, a0, a1, dot);
-      cm = c0, c0 = cp, cp = cn, cur = nxt;
+      col_compute<NF, DOT>(cur, down ? ca : cb, c0, down ? cb : ca, C, vm0, vm1, vp0, vp1, lane, a0, a1, dot);
+      cb = c0, c0 = ca, ca = cn, cur = nxt;
       for (unsigned k = 1; k + 1 < K; k++) {
-        gu += (long long)P, lrow += P;
+        gu += D, lrow += Du;
         if (lockstep)
           __builtin_amdgcn_s_barrier();
-        col_issue<NF, DOT>(nxt, cn, C, x, xdot, gu + (long long)P, lrow + P, P, xlen, lane, true);
+        col_issue<NF, DOT>(nxt, cn, C, x, xdot, gu + D, lrow + Du, D, xlen, lane, true);
         {
           const sell_d2v o = {a0, a1};
-          *(sell_d2v *)(y + (lrow - P) + 2 * lane) = o;
+          *(sell_d2v *)(y + (lrow - Du) + 2 * lane) = o;
         }
-        col_compute<NF, DOT>(cur, cm, c0, cp, C, vm0, vm1, vp0, vp1, lane, a0, a1, dot);
-        cm = c0, c0 = cp, cp = cn, cur = nxt;
+        col_compute<NF, DOT>(cur, down ? ca : cb, c0, down ? cb : ca, C, vm0, vm1, vp0, vp1, lane, a0, a1, dot);
+        cb = c0, c0 = ca, ca = cn, cur = nxt;
       }
-      gu += (long long)P, lrow += P;
+      gu += D, lrow += Du;
       {
         const sell_d2v o = {a0, a1};
-        *(sell_d2v *)(y + (lrow - P) + 2 * lane) = o;
+        *(sell_d2v *)(y + (lrow - Du) + 2 * lane) = o;
       }
-      col_compute<NF, DOT>(cur, cm, c0, cp, C, vm0, vm1, vp0, vp1, lane, a0, a1, dot);
+      col_compute<NF, DOT>(cur, down ? ca : cb, c0, down ? cb : ca, C, vm0, vm1, vp0, vp1, lane, a0, a1, dot);
       {
         const sell_d2v o = {a0, a1};
         *(sell_d2v *)(y + lrow + 2 * lane) = o;
       }
+      if (stopped)
+        return;
     } else { // one slice, slot by slot off the slot records (k_spmv_tmpl's way for a slice without a template)
       const unsigned row = s * LSB_SELL_ROWS + 2 * lane;
       const int grow = (int)(row + row_begin);
@@ -1890,23 +1908,23 @@ template <int NF> struct colp_m {
 struct colp_out { // results of a step
   sell_d2v q, x, p;
 };
-// gu: global row of lane 0's first row of the step's slice (one shard: = its local row)
+// gu: global row of lane 0's first row of the step's slice (one shard: = its local row); D: rows to the plane ahead
 template <int NF, bool WITH_X, int NT>
 __device__ __forceinline__ void colp_issue_c(colp_c<NF> &o, const col_tmpl<NF> &T, const double *__restrict__ r,
                                              const double *__restrict__ pold, const double *__restrict__ x,
-                                             const double *pstale, long long gu, unsigned P, unsigned xlen,
+                                             const double *pstale, long long gu, long long D, unsigned xlen,
                                              unsigned lane) {
-  const long long ga = gu + T.bc + (long long)P; // the plane ahead
+  const long long ga = gu + T.bc + D; // the plane ahead
   o.rn = *(const sell_d2u *)(r + ga + 2 * lane);
   o.pn = *(const sell_d2u *)(pold + ga + 2 * lane);
   if (WITH_X) { // x and the stale direction are touched once per launch: nontemporal (NT & 1) keeps them out of the
                 // way of the r / p lines the neighbouring columns gather again
     if (NT & 1) {
-      o.xn = __builtin_nontemporal_load((const sell_d2v *)(x + (gu + (long long)P) + 2 * lane));
-      o.sn = __builtin_nontemporal_load((const sell_d2v *)(pstale + (gu + (long long)P) + 2 * lane));
+      o.xn = __builtin_nontemporal_load((const sell_d2v *)(x + (gu + D) + 2 * lane));
+      o.sn = __builtin_nontemporal_load((const sell_d2v *)(pstale + (gu + D) + 2 * lane));
     } else {
-      o.xn = *(const sell_d2v *)(x + (gu + (long long)P) + 2 * lane);
-      o.sn = *(const sell_d2v *)(pstale + (gu + (long long)P) + 2 * lane);
+      o.xn = *(const sell_d2v *)(x + (gu + D) + 2 * lane);
+      o.sn = *(const sell_d2v *)(pstale + (gu + D) + 2 * lane);
     }
   }
   long long el = gu + T.bc - 1, er = gu + T.bc + (long long)LSB_SELL_ROWS; // wave-uniform, clamped (see col_issue)
@@ -1925,13 +1943,14 @@ __device__ __forceinline__ void colp_issue_m(colp_m<NF> &o, const col_tmpl<NF> &
     o.phi[k] = *(const sell_d2u *)(pold + (gu + T.bh[k]) + 2 * lane);
   }
 }
-// one step: q of the centre plane from (below, centre, above) = (pm, p0, p' of the plane ahead); OWNED: the
-// plane ahead is the column's own -- its x is updated and it and p' go to `out`
+// one step: q of the centre plane from p' of the plane behind (pb), the centre (p0) and the plane ahead (pp, formed
+// here) -- below, centre, above = pb, p0, pp upward (down false), pp, p0, pb downward; OWNED: the plane ahead is the
+// column's own -- its x is updated and it and p' go to `out`
 // XUPD: this launch applies the two pending x updates (alpha of the iteration before with its direction p, alpha2 of
 // the one before that with the stale direction)
 template <int NF, bool OWNED, bool XUPD>
-__device__ __forceinline__ void colp_compute(const colp_c<NF> &o, const colp_m<NF> &m, const sell_d2u &pm,
-                                             const sell_d2u &p0, sell_d2u &pp, const col_tmpl<NF> &T, double vm0,
+__device__ __forceinline__ void colp_compute(const colp_c<NF> &o, const colp_m<NF> &m, const sell_d2u &pb,
+                                             const sell_d2u &p0, sell_d2u &pp, bool down, const col_tmpl<NF> &T, double vm0,
                                              double vm1, double vp0, double vp1, double beta, double alpha, double alpha2,
                                              double dc, unsigned lane, colp_out &out, double &dot) {
   pp.x = pnew_of(dc, o.rn.x, beta, o.pn.x), pp.y = pnew_of(dc, o.rn.y, beta, o.pn.y);
@@ -1947,6 +1966,7 @@ __device__ __forceinline__ void colp_compute(const colp_c<NF> &o, const colp_m<N
     up = edge;
   if (lane == 63)
     dn = edge;
+  const sell_d2u &pm = down ? pp : pb, &pu = down ? pb : pp; // the planes below and above
   double a0 = fma(T.k0, pm.x, 0.0), a1 = fma(T.k0, pm.y, 0.0);
 #pragma unroll
   for (int k = 0; k < NF - 1; k++) {
@@ -1961,7 +1981,7 @@ __device__ __forceinline__ void colp_compute(const colp_c<NF> &o, const colp_m<N
     const double h0 = pnew_of(dc, m.rhi[k].x, beta, m.phi[k].x), h1 = pnew_of(dc, m.rhi[k].y, beta, m.phi[k].y);
     a0 = fma(T.kh[k], h0, a0), a1 = fma(T.kh[k], h1, a1);
   }
-  a0 = fma(T.kL, pp.x, a0), a1 = fma(T.kL, pp.y, a1);
+  a0 = fma(T.kL, pu.x, a0), a1 = fma(T.kL, pu.y, a1);
   out.q.x = a0, out.q.y = a1;
   dot = fma(a0, p0.x, dot), dot = fma(a1, p0.y, dot);
 }
@@ -2027,8 +2047,8 @@ __device__ __forceinline__ void colp_single(unsigned s, unsigned n, unsigned lan
       COLP_ST(q + (LROW) + 2 * lane, (OUT).q, 2);                                              \
     if (WITH_XP) {                                                                             \
       if (XUPD)                                                                                \
-        COLP_ST(x + ((LROW) + P) + 2 * lane, (OUT).x, 1);                                      \
-      COLP_ST(pnew + ((LROW) + P) + 2 * lane, (OUT).p, 2);                                     \
+        COLP_ST(x + ((LROW) + Du) + 2 * lane, (OUT).x, 1);                                     \
+      COLP_ST(pnew + ((LROW) + Du) + 2 * lane, (OUT).p, 2);                                    \
     }                                                                                          \
   } while (0)
 
@@ -2040,7 +2060,8 @@ __device__ __forceinline__ void colp_single(unsigned s, unsigned n, unsigned lan
 // to still holds (each lane reads its own rows' p'' just before it overwrites them; nobody else reads that
 // buffer in this launch).  Launches of odd run index leave x alone: x is read and written half as often.
 template <int NF, int NT, bool XUPD>
-__global__ __launch_bounds__(WG, NF == 2 ? 3 : 4) void k_pcg_col_px(
+// (launch bounds: the resident grid of lsb_k_pcg_col_px, LSB_TMPL_COL_GRID -- three and five workgroups per CU)
+__global__ __launch_bounds__(WG, NF == 2 ? 3 : 5) void k_pcg_col_px(
     const unsigned *__restrict__ plan, unsigned period, unsigned n, const unsigned *__restrict__ sptr,
     const unsigned long long *__restrict__ mask, const lsb_sell_tmpl *__restrict__ td, const int *__restrict__ sbase,
     const double *__restrict__ vals, const double *__restrict__ vconst, const double *__restrict__ r,
@@ -2080,6 +2101,7 @@ __global__ __launch_bounds__(WG, NF == 2 ? 3 : 4) void k_pcg_col_px(
     return;
   const double beta = rz_new / rz_old;
   const u4v *__restrict__ items = (const u4v *)(plan + LSB_COL_HEAD);
+  const unsigned dofs = plan[LSB_TMPL_COL_DOWN];
   const unsigned P = period * LSB_SELL_ROWS;
   double dot = 0.0;
   for (unsigned g = slot; i0 + 4 * g < i1; g += gx) {
@@ -2101,21 +2123,25 @@ __global__ __launch_bounds__(WG, NF == 2 ? 3 : 4) void k_pcg_col_px(
         C.kl[k] = T->cst[1 + k], C.kh[k] = T->cst[NF + 3 + k];
       }
       const int side_k[2] = {T->kidx[NF], T->kidx[NF + 2]}, side_kd[2] = {T->kind[NF], T->kind[NF + 2]};
-      long long gu = (long long)s * LSB_SELL_ROWS;
-      unsigned lrow = s * LSB_SELL_ROWS;
-      // prologue: r, p of the plane below (another column's) and of the first plane with its x; step 0's loads
+      const bool down = col_walks_down(plan, dofs, it); // wave-uniform
+      const unsigned s0 = down ? s + (K - 1) * period : s; // the plane of step 0
+      const long long D = down ? -(long long)P : (long long)P;
+      const unsigned Du = (unsigned)D;
+      long long gu = (long long)s0 * LSB_SELL_ROWS;
+      unsigned lrow = s0 * LSB_SELL_ROWS;
+      // prologue: r, p of the plane behind (another column's) and of the first plane with its x; step 0's loads
       const long long gc = gu + C.bc;
-      const sell_d2u rb = *(const sell_d2u *)(r + (gc - (long long)P) + 2 * lane);
-      const sell_d2u pb = *(const sell_d2u *)(pold + (gc - (long long)P) + 2 * lane);
+      const sell_d2u rb = *(const sell_d2u *)(r + (gc - D) + 2 * lane);
+      const sell_d2u pb = *(const sell_d2u *)(pold + (gc - D) + 2 * lane);
       const sell_d2u r0 = *(const sell_d2u *)(r + gc + 2 * lane), o0 = *(const sell_d2u *)(pold + gc + 2 * lane);
-      sell_d2v x0 = {0.0, 0.0}, s0 = {0.0, 0.0};
+      sell_d2v x0 = {0.0, 0.0}, s0v = {0.0, 0.0};
       if (XUPD) // (a compile-time branch: no join in front of the loads)
-        x0 = *(const sell_d2v *)(x + lrow + 2 * lane), s0 = *(const sell_d2v *)(pnew + lrow + 2 * lane);
+        x0 = *(const sell_d2v *)(x + lrow + 2 * lane), s0v = *(const sell_d2v *)(pnew + lrow + 2 * lane);
       colp_c<NF> c0, c1;
       colp_m<NF> m0, m1, m2;
-      colp_issue_c<NF, XUPD, NT>(c0, C, r, pold, x, pnew, gu, P, n, lane);
+      colp_issue_c<NF, XUPD, NT>(c0, C, r, pold, x, pnew, gu, D, n, lane);
       colp_issue_m<NF>(m0, C, r, pold, gu, lane);
-      colp_issue_m<NF>(m1, C, r, pold, gu + (long long)P, lane);
+      colp_issue_m<NF>(m1, C, r, pold, gu + D, lane);
       unsigned long long mk[2][2] = {{0ull, 0ull}, {0ull, 0ull}};
 #pragma unroll
       for (int side = 0; side < 2; side++)
@@ -2126,34 +2152,34 @@ __global__ __launch_bounds__(WG, NF == 2 ? 3 : 4) void k_pcg_col_px(
       double vm0 = T->cst[NF], vm1 = vm0, vp0 = T->cst[NF + 2], vp1 = vp0;
       if (side_k[0] >= 0 || side_k[1] >= 0)
         tmpl_side_values(T, NF, 0u, lane, side_k, side_kd, mk, vals, 0, vm0, vm1, vp0, vp1);
-      sell_d2u pm, p0, pp;
+      sell_d2u pm, p0, pp; // p' of the plane behind, the centre, the plane ahead
       pm.x = pnew_of(dc, rb.x, beta, pb.x), pm.y = pnew_of(dc, rb.y, beta, pb.y);
       p0.x = pnew_of(dc, r0.x, beta, o0.x), p0.y = pnew_of(dc, r0.y, beta, o0.y);
       // A step issues the NEXT step's loads, waits for its own (older) and stores its results right away: the stores
       // are younger than the loads the next step waits for, so they are never waited for either (vmcnt counts
       // loads and stores in one order) -- no parking of results across a step.
       colp_out res;
-      res.x.x = (x0.x + alpha2 * s0.x) + alpha * o0.x, res.x.y = (x0.y + alpha2 * s0.y) + alpha * o0.y;
+      res.x.x = (x0.x + alpha2 * s0v.x) + alpha * o0.x, res.x.y = (x0.y + alpha2 * s0v.y) + alpha * o0.y;
       res.p.x = p0.x, res.p.y = p0.y;
       res.q = res.p; // (not stored)
-      COLP_STORE(res, lrow - P, false, true); // the first plane's x and p'
+      COLP_STORE(res, lrow - Du, false, true); // the first plane's x and p'
       // steps 0 .. K-3 (K >= 3): the plane after next is the column's own
       for (unsigned k = 0; k + 2 < K; k++) {
-        colp_issue_c<NF, XUPD, NT>(c1, C, r, pold, x, pnew, gu + (long long)P, P, n, lane);
-        colp_issue_m<NF>(m2, C, r, pold, gu + 2 * (long long)P, lane);
-        colp_compute<NF, true, XUPD>(c0, m0, pm, p0, pp, C, vm0, vm1, vp0, vp1, beta, alpha, alpha2, dc, lane, res, dot);
+        colp_issue_c<NF, XUPD, NT>(c1, C, r, pold, x, pnew, gu + D, D, n, lane);
+        colp_issue_m<NF>(m2, C, r, pold, gu + 2 * D, lane);
+        colp_compute<NF, true, XUPD>(c0, m0, pm, p0, pp, down, C, vm0, vm1, vp0, vp1, beta, alpha, alpha2, dc, lane, res, dot);
         COLP_STORE(res, lrow, false, true);
         pm = p0, p0 = pp, c0 = c1, m0 = m1, m1 = m2;
-        gu += (long long)P, lrow += P;
+        gu += D, lrow += Du;
       }
-      // step K-2: the plane after next is the one above the column (no x, no +-line operands to ask for)
-      colp_issue_c<NF, false, NT>(c1, C, r, pold, x, pnew, gu + (long long)P, P, n, lane);
-      colp_compute<NF, true, XUPD>(c0, m0, pm, p0, pp, C, vm0, vm1, vp0, vp1, beta, alpha, alpha2, dc, lane, res, dot);
+      // step K-2: the plane after next lies beyond the column's end (no x, no +-line operands to ask for)
+      colp_issue_c<NF, false, NT>(c1, C, r, pold, x, pnew, gu + D, D, n, lane);
+      colp_compute<NF, true, XUPD>(c0, m0, pm, p0, pp, down, C, vm0, vm1, vp0, vp1, beta, alpha, alpha2, dc, lane, res, dot);
       COLP_STORE(res, lrow, false, true);
       pm = p0, p0 = pp, c0 = c1, m0 = m1;
-      gu += (long long)P, lrow += P;
+      gu += D, lrow += Du;
       // step K-1: nothing to load; the plane ahead is not the column's
-      colp_compute<NF, false, XUPD>(c0, m0, pm, p0, pp, C, vm0, vm1, vp0, vp1, beta, alpha, alpha2, dc, lane, res, dot);
+      colp_compute<NF, false, XUPD>(c0, m0, pm, p0, pp, down, C, vm0, vm1, vp0, vp1, beta, alpha, alpha2, dc, lane, res, dot);
       COLP_STORE(res, lrow, false, false);
     } else {
       for (unsigned k = 0; k < K; k++)
@@ -2212,6 +2238,7 @@ __global__ __launch_bounds__(WG, 5) void k_pcg_col_r(
     st->pq = pq, st->alpha[1] = st->alpha[0], st->alpha[0] = alpha, st->xpend = (xtwo ? 3 : 1) + pbuf;
   }
   const u4v *__restrict__ items = (const u4v *)(plan + LSB_COL_HEAD);
+  const unsigned dofs = plan[LSB_TMPL_COL_DOWN];
   const unsigned P = period * LSB_SELL_ROWS;
   double acc[2] = {0.0, 0.0}, nodot = 0.0;
 #define COLR_FINISH(A0, A1, RV, LROW)                                                          \
@@ -2243,13 +2270,17 @@ __global__ __launch_bounds__(WG, 5) void k_pcg_col_r(
         C.kl[k] = T->cst[1 + k], C.kh[k] = T->cst[NF + 3 + k];
       }
       const int side_k[2] = {T->kidx[NF], T->kidx[NF + 2]}, side_kd[2] = {T->kind[NF], T->kind[NF + 2]};
-      long long gu = (long long)s * LSB_SELL_ROWS;
-      unsigned lrow = s * LSB_SELL_ROWS;
+      const bool down = col_walks_down(plan, dofs, it); // wave-uniform
+      const unsigned s0 = down ? s + (K - 1) * period : s; // the plane of step 0
+      const long long D = down ? -(long long)P : (long long)P;
+      const unsigned Du = (unsigned)D;
+      long long gu = (long long)s0 * LSB_SELL_ROWS;
+      unsigned lrow = s0 * LSB_SELL_ROWS;
       col_ops<NF> cur, nxt;
-      sell_d2u cm = *(const sell_d2u *)(p + (gu + C.bc - (long long)P) + 2 * lane);
+      sell_d2u cb = *(const sell_d2u *)(p + (gu + C.bc - D) + 2 * lane);
       sell_d2u c0 = *(const sell_d2u *)(p + (gu + C.bc) + 2 * lane);
-      sell_d2u cp, cn;
-      col_issue<NF, 2>(cur, cp, C, p, r, gu, lrow, P, n, lane, true); // (the "dot operand" slot carries r's pair)
+      sell_d2u ca, cn;
+      col_issue<NF, 2>(cur, ca, C, p, r, gu, lrow, D, n, lane, true); // (the "dot operand" slot carries r's pair)
       unsigned long long mk[2][2] = {{0ull, 0ull}, {0ull, 0ull}};
 #pragma unroll
       for (int side = 0; side < 2; side++)
@@ -2261,15 +2292,15 @@ __global__ __launch_bounds__(WG, 5) void k_pcg_col_r(
       if (side_k[0] >= 0 || side_k[1] >= 0)
         tmpl_side_values(T, NF, 0u, lane, side_k, side_kd, mk, vals, 0, vm0, vm1, vp0, vp1);
       for (unsigned k = 0; k + 1 < K; k++) {
-        col_issue<NF, 2>(nxt, cn, C, p, r, gu + (long long)P, lrow + P, P, n, lane, true);
+        col_issue<NF, 2>(nxt, cn, C, p, r, gu + D, lrow + Du, D, n, lane, true);
         double a0, a1;
-        col_compute<NF, 0>(cur, cm, c0, cp, C, vm0, vm1, vp0, vp1, lane, a0, a1, nodot);
+        col_compute<NF, 0>(cur, down ? ca : cb, c0, down ? cb : ca, C, vm0, vm1, vp0, vp1, lane, a0, a1, nodot);
         COLR_FINISH(a0, a1, cur.xd, lrow);
-        cm = c0, c0 = cp, cp = cn, cur = nxt;
-        gu += (long long)P, lrow += P;
+        cb = c0, c0 = ca, ca = cn, cur = nxt;
+        gu += D, lrow += Du;
       }
       double a0, a1;
-      col_compute<NF, 0>(cur, cm, c0, cp, C, vm0, vm1, vp0, vp1, lane, a0, a1, nodot);
+      col_compute<NF, 0>(cur, down ? ca : cb, c0, down ? cb : ca, C, vm0, vm1, vp0, vp1, lane, a0, a1, nodot);
       COLR_FINISH(a0, a1, cur.xd, lrow);
     } else {
       for (unsigned k = 0; k < K; k++) { // one slice, slot by slot off the slot records
@@ -3013,8 +3044,10 @@ void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, 
                       unsigned *npartials, struct lsb_pcg_state *st, int parity, const double *parts2,
                       unsigned nparts2, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  /* every workgroup resident: three per CU with two far slots per side (142 VGPRs), five with one (96) */
-  const unsigned res = nfar == 2 ? 768u : 1280u;
+  /* every workgroup resident: three per CU with two far slots per side (<= 168 VGPRs), five with one (<= 96, what
+   * the kernel's launch bounds hold it to: with x it needed 102 and only four were resident, the grid's last fifth
+   * ran as a second wave).  The plan's walk directions are dealt against this grid (LSB_TMPL_COL_TURN) */
+  const unsigned res = LSB_TMPL_COL_GRID(nfar);
   const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, nitem, 0, grid_cap && grid_cap < res ? grid_cap : res);
   if (npartials)
     *npartials = g;
@@ -3045,6 +3078,7 @@ void lsb_k_pcg_col_r(unsigned grid_cap, unsigned period, const unsigned *plan, u
                      struct lsb_pcg_state *st, int parity, int pbuf, int xtwo, const double *pq_parts, unsigned npq,
                      double *partials2, unsigned *npartials, void *stream) {
   hipStream_t s = (hipStream_t)stream;
+  /* five workgroups per CU (launch bounds): the grid of lsb_k_pcg_col_px with one far slot per side */
   const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, nitem, 0, grid_cap && grid_cap < 1280u ? grid_cap : 1280u);
   *npartials = g;
   if (period < NXCD || !plan)

@@ -405,10 +405,16 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
                 char why[256];
                 if (lsb_tmpl_cols_check(TT, CC, why, sizeof why))
                   errx(EXIT_FAILURE, "hip_cdna4: z-column plan breaks a rule its kernel relies on: %s", why);
-                unsigned *plan = lsb_calloc(unsigned, 16 + 4 * ((size_t)CC->nitem + 1));
+                /* xbeg, the items, the walk directions behind them (include/lsbench_hip.h) */
+                const size_t nw = 16 + 4 * ((size_t)CC->nitem + 1), nd = CC->down ? ((size_t)CC->nitem + 31) / 32 : 0;
+                unsigned *plan = lsb_calloc(unsigned, nw + nd);
                 memcpy(plan, CC->xbeg, sizeof CC->xbeg);
                 memcpy(plan + 16, CC->item, 4 * (size_t)CC->nitem * sizeof(unsigned));
-                unsigned *d = (unsigned *)dev_upload(plan, (16 + 4 * ((size_t)CC->nitem + 1)) * sizeof(unsigned));
+                if (nd) {
+                  plan[LSB_TMPL_COL_DOWN] = (unsigned)nw;
+                  memcpy(plan + nw, CC->down, nd * sizeof(unsigned));
+                }
+                unsigned *d = (unsigned *)dev_upload(plan, (nw + nd) * sizeof(unsigned));
                 LSB_CHK_HIP(hipStreamSynchronize(g_stream));
                 free(plan);
                 if (w == 0) {
@@ -1102,11 +1108,17 @@ void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
         /* the z-column walk of a 3-D stencil (k_spmv_tmpl_col): one new plane per step */
         /* (fewer resident workgroups than the other flavours: 3-4 per CU measured 232-233 us on the
          * 64 M-row 7-point operator, 5 / 6 / 8 per CU 246 / 246 / 253, profiles/r04_col.txt) */
+        /* (no more workgroups than the two-launch iteration's grid, LSB_TMPL_COL_GRID: a run's first p.q comes
+         * from this SpMV, the others from k_pcg_col_px -- on one grid they are the same partial sums, and a solve
+         * repeats bit for bit however it is cut into runs) */
         if (s->d_colplan) {
           if (o->spmv_grid <= 0) {
+            const unsigned gcol = LSB_TMPL_COL_GRID(s->tmpl_nfar);
             CAND(LSB_SPMV_SELL, f | LSB_SP_COL, 768, 0);
-            CAND(LSB_SPMV_SELL, f | LSB_SP_COL, 1024, 0);
-            CAND(LSB_SPMV_SELL, f | LSB_SP_COL, 1536, 0);
+            if (gcol > 768) {
+              CAND(LSB_SPMV_SELL, f | LSB_SP_COL, 1024, 0);
+              CAND(LSB_SPMV_SELL, f | LSB_SP_COL, gcol, 0);
+            }
           } else
             CAND(LSB_SPMV_SELL, f | LSB_SP_COL, grid0, 0);
         }

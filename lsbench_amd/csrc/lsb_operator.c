@@ -1577,6 +1577,10 @@ struct lsb_tmpl_cols *lsb_sell_tmpl_columns_range(const struct lsb_sell_tmpls *T
    * line of 25 slices: the launch ran 28 % longer than on a grid of 64-slice lines, profiles/r04_pad.txt.) */
   const unsigned ngroups = (nplanes + kmax - 1) / kmax;
   const unsigned long long ncell = (unsigned long long)ngroups * period, total = s_hi - s_lo;
+  /* walk directions (include/lsbench_hip.h): z-groups of odd index downward, where a z-group and its neighbours
+   * go through the chip in one turn -- a 2-D grid of 25-slice lines, not a 3-D one of 1250-slice planes */
+  if (2ull * period <= LSB_TMPL_COL_TURN(T->nfar))
+    C->down = lsb_calloc(unsigned, ((size_t)ns + 1 + 31) / 32);
   unsigned ni = 0, xk = 0;
   unsigned long long seen = 0; /* slices of the cells emitted so far */
   C->xbeg[0] = 0;
@@ -1601,6 +1605,10 @@ struct lsb_tmpl_cols *lsb_sell_tmpl_columns_range(const struct lsb_sell_tmpls *T
                col_member(T, (unsigned)(s + (unsigned long long)run * period), period) &&
                col_same(T, (unsigned)s, (unsigned)(s + (unsigned long long)run * period)))
           run++;
+      /* (columns of >= 3 slices only: those of two, and single slices, the PCG kernels take slice by slice in
+       * ascending order, and the SpMV that forms a run's first p.q must add its terms in the same order) */
+      if (C->down && (zg & 1u) && run >= 3)
+        C->down[ni / 32] |= 1u << (ni % 32);
       unsigned *it = C->item + 4 * (size_t)ni++;
       it[0] = (unsigned)s, it[1] = run, it[2] = T->tid[s], it[3] = T->vbase[2 * (size_t)s + 1];
       if (run >= 2) {
@@ -1652,9 +1660,12 @@ int lsb_tmpl_cols_check(const struct lsb_sell_tmpls *T, const struct lsb_tmpl_co
   for (unsigned k = 0; k < LSB_COL_XCDS; k++)
     if (C->xbeg[k] > C->xbeg[k + 1])
       CC_FAIL(3, "item ranges of the XCDs not ascending at %u", k);
+  if (C->down && 2ull * period > LSB_TMPL_COL_TURN(T->nfar))
+    CC_FAIL(13, "walk directions on z-groups of %u cells, %u items per XCD and turn", period, LSB_TMPL_COL_TURN(T->nfar));
   seen = (unsigned char *)calloc((size_t)ns + 1, 1);
   if (!seen)
     CC_FAIL(4, "out of memory");
+  const unsigned nplanes = (ns + period - 1) / period, ngroups = (nplanes + C->kmax - 1) / C->kmax;
   for (unsigned i = 0; i < C->nitem; i++) {
     const unsigned *it = C->item + 4 * (size_t)i;
     const unsigned s = it[0], run = it[1] & ~LSB_TMPL_COL_LOCKSTEP;
@@ -1683,6 +1694,11 @@ int lsb_tmpl_cols_check(const struct lsb_sell_tmpls *T, const struct lsb_tmpl_co
     if (run >= 2 && (it[2] != T->tid[s] || it[3] != T->vbase[2 * (size_t)s + 1]))
       CC_FAIL(8, "item %u: template %u / first mask %u, its first slice has %u / %u", i, it[2], it[3], T->tid[s],
               T->vbase[2 * (size_t)s + 1]);
+    if (C->down) { /* the z-group of plane z: the last zg with nplanes * zg / ngroups <= z */
+      const unsigned zg = (unsigned)(((unsigned long long)(s / period + 1) * ngroups - 1) / nplanes);
+      if (((C->down[i / 32] >> (i % 32)) & 1u) != ((zg & 1u) && run >= 3))
+        CC_FAIL(13, "item %u: %u slices walk %s in z-group %u", i, run, ((zg & 1u) && run >= 3) ? "upward" : "downward", zg);
+    }
   }
   for (unsigned s = C->s_lo; s < C->s_hi; s++)
     if (!seen[s])
@@ -1695,7 +1711,7 @@ int lsb_tmpl_cols_check(const struct lsb_sell_tmpls *T, const struct lsb_tmpl_co
 void lsb_tmpl_cols_free(struct lsb_tmpl_cols *C) {
   if (!C)
     return;
-  free(C->item), free(C);
+  free(C->item), free(C->down), free(C);
 }
 
 void lsb_sell_tmpls_free(struct lsb_sell_tmpls *T) {
