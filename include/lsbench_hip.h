@@ -108,7 +108,7 @@ enum { LSB_PRECOND_JACOBI = 0, LSB_PRECOND_NONE = 1,
                                        per block, blocks inverted at setup (the
                                        block form of src/ginkgo.cpp:57-58's
                                        Jacobi preconditioner)                 */
-       LSB_PRECOND_FSAI = 5 };        /* factorised sparse approximate inverse,
+       LSB_PRECOND_FSAI = 5,          /* factorised sparse approximate inverse,
                                        M^-1 = G^T G with G on the pattern of tril(S^k),
                                        k = opts.fsai_power: the expensive part (one small
                                        dense SPD solve per row, on the device) happens
@@ -117,6 +117,11 @@ enum { LSB_PRECOND_JACOBI = 0, LSB_PRECOND_NONE = 1,
                                        in csr_init (src/cholmod-impl.h:25-26) and times
                                        only solves (:59-62); an application is two SpMVs,
                                        no triangular solve, no reduction        */
+       LSB_PRECOND_AMG = 6 };         /* smoothed-aggregation algebraic multigrid: one
+                                       symmetric V-cycle with l1-Jacobi smoothing, the
+                                       hierarchy built on the host at solver creation
+                                       (lsb_amg_setup), applied by hip_amg.hip; one
+                                       shard, classic PCG                      */
 enum { LSB_KRYLOV_PCG = 0,    /* preconditioned CG (symmetric operators)    */
        LSB_KRYLOV_GMRES = 1,  /* restarted GMRES(m), right-preconditioned,
                                  for LSB_OP_RAW / unsymmetric operators;
@@ -211,6 +216,16 @@ struct lsb_hip_opts {
                         -1 = timed per solver at creation (tune_blas1_nt); else a mask
                         (bit 0 x, 1 p and q, 2 r in k_pcg_update_xr; 3 r, 4 p in
                         k_pcg_update_p; 5 k_cg1_update; 1 = all)              [-1] */
+  /* LSB_PRECOND_AMG (lsb_amg.c, hip_amg.hip) */
+  double amg_theta;  /* strength threshold: j strong for i when
+                        |a_ij| >= theta sqrt(|a_ii a_jj|)                 [0.08] */
+  int amg_sweeps;    /* l1-Jacobi sweeps before and after the coarse correction  [1] */
+  int amg_coarse;    /* coarsening stops at this many rows (dense coarse solve) [256] */
+  int amg_max_levels; /* levels at most, the coarsest included               [20] */
+  int amg_tail_rows; /* levels of at most this many rows, and the coarse solve, run
+                        in ONE launch of one workgroup (k_amg_tail); 0 = off, a launch
+                        per step: measured faster at every size tried (one workgroup
+                        is latency-bound; profiles/r05_amg.txt)                 [0] */
 };
 enum { LSB_PREC_FP64 = 0, LSB_PREC_MIXED = 1 };
 
@@ -382,6 +397,26 @@ struct lsb_fsai_pattern {
 #define LSB_FSAI_CAP 128
 struct lsb_fsai_pattern *lsb_csr_fsai_pattern(const struct csr *S, int power, unsigned cap);
 void lsb_fsai_pattern_free(struct lsb_fsai_pattern *P);
+/* Smoothed-aggregation AMG hierarchy (LSB_PRECOND_AMG), pure host logic (lsb_amg.c, rules
+ * there).  lv[0].A = S as a 0-based CSR with sorted columns; level l < nlev - 1 has P
+ * (n x n_next) and R = P^T; the coarsest level lv[nlev - 1] has neither and is solved by
+ * coarse_inv (nc x nc, row-major, symmetric).  Every level's rows have sorted columns.  An
+ * operator that is not SPD (a diagonal <= 0 on some level, a coarse pivot <= 0) makes it exit
+ * with a "positive definite" message. */
+struct lsb_amg_level {
+  unsigned n;
+  struct csr *A, *P, *R;
+};
+struct lsb_amg_hier {
+  unsigned nlev;
+  struct lsb_amg_level *lv;
+  unsigned nc;
+  double *coarse_inv;
+};
+struct lsb_amg_hier *lsb_amg_setup(const struct csr *S, double theta, unsigned coarse, unsigned max_levels);
+/* the aggregates of one level (malloc'ed, n entries; -1 = not aggregated), *naggr of them */
+int *lsb_amg_aggregate(const struct csr *A, double theta, unsigned *naggr);
+void lsb_amg_free(struct lsb_amg_hier *h);
 /* Sliced-ELL copy of a CSR for LSB_SPMV_SELL: rows in slices of LSB_SELL_ROWS,
  * every slice padded to its longest row and stored column-major (entry j of
  * row 128s+i at sptr[s] + 128j + i), so that a wavefront's lane l reads the
@@ -602,6 +637,14 @@ int lsb_hip_solver_solve_dev(lsb_hip_solver *s, const double *d_b, double *d_x,
 /* y_local = Op * x: d_x holds this rank's rows (length n_local); remote
  * entries are exchanged first when the solver is distributed. */
 int lsb_hip_solver_spmv_dev(lsb_hip_solver *s, const double *d_x, double *d_y);
+/* z = M^-1 r once, the preconditioner the solver was made with (LSB_PRECOND_AMG: one V-cycle),
+ * on the solver's stream; device buffers of length n_local in the caller's numbering.  2 for a
+ * preconditioner that is not applied as a vector of its own (the diagonal ones: see
+ * lsb_hip_solver_jacobi_sweep_dev). */
+int lsb_hip_solver_precond_dev(lsb_hip_solver *s, const double *d_r, double *d_z);
+/* LSB_PRECOND_AMG: levels of the hierarchy, the coarsest included, and how many of them (with
+ * the coarse solve) run in the one-launch tail; 2 for another preconditioner. */
+int lsb_hip_solver_amg_info(lsb_hip_solver *s, unsigned *levels, unsigned *tail_levels);
 /* Time `reps` back-to-back launches of the solver's SpMV kernel with HIP
  * events on the solver's stream (after `warm` untimed ones); *ms_avg = mean
  * milliseconds per launch.  No exchange, local shard 0. */

@@ -21,6 +21,7 @@ UNIQUE_ID_BYTES = 128
 SOLVER_HIP = 6
 OP_CHOLMOD_UPPER, OP_RAW = 0, 1
 PRECOND_JACOBI, PRECOND_NONE, PRECOND_L1JACOBI, PRECOND_CHEBYSHEV, PRECOND_BLOCKJACOBI, PRECOND_FSAI = 0, 1, 2, 3, 4, 5
+PRECOND_AMG = 6
 KRYLOV_PCG, KRYLOV_GMRES, KRYLOV_PCG1, KRYLOV_AUTO = 0, 1, 2, 3
 SPMV_AUTO, SPMV_ADAPTIVE, SPMV_SUBWAVE, SPMV_SCALAR, SPMV_PANEL, SPMV_SELL, SPMV_BINNED, SPMV_TWOPHASE = 0, 1, 2, 3, 4, 5, 6, 7
 SELL_ROWS = 128
@@ -61,7 +62,9 @@ class Opts(C.Structure):
                 ("restart", C.c_int), ("verbose", C.c_int),
                 ("ngpus", C.c_int), ("verify", C.c_int), ("cheb_degree", C.c_int),
                 ("block_size", C.c_int), ("precision", C.c_int), ("persistent", C.c_int),
-                ("comm_deadline_s", C.c_double), ("fsai_power", C.c_int), ("blas1_nt", C.c_int)]
+                ("comm_deadline_s", C.c_double), ("fsai_power", C.c_int), ("blas1_nt", C.c_int),
+                ("amg_theta", C.c_double), ("amg_sweeps", C.c_int), ("amg_coarse", C.c_int),
+                ("amg_max_levels", C.c_int), ("amg_tail_rows", C.c_int)]
 
 
 class Result(C.Structure):
@@ -98,6 +101,18 @@ class FsaiPattern(C.Structure):
     """struct lsb_fsai_pattern."""
     _fields_ = [("n", C.c_uint), ("cap", C.c_uint), ("nnz", C.c_ulonglong), ("offs", C.POINTER(C.c_uint)),
                 ("cols", C.POINTER(C.c_uint))]
+
+
+class AmgLevel(C.Structure):
+    """struct lsb_amg_level."""
+    _fields_ = [("n", C.c_uint), ("A", C.POINTER(CsrStruct)), ("P", C.POINTER(CsrStruct)),
+                ("R", C.POINTER(CsrStruct))]
+
+
+class AmgHier(C.Structure):
+    """struct lsb_amg_hier."""
+    _fields_ = [("nlev", C.c_uint), ("lv", C.POINTER(AmgLevel)), ("nc", C.c_uint),
+                ("coarse_inv", C.POINTER(C.c_double))]
 
 
 class SellTmpl(C.Structure):
@@ -197,6 +212,9 @@ SIGNATURES = {
     "lsb_sell_vc_free": (None, [C.POINTER(SellVc)]),
     "lsb_csr_fsai_pattern": (C.POINTER(FsaiPattern), [_csrp, _i, _u]),
     "lsb_fsai_pattern_free": (None, [C.POINTER(FsaiPattern)]),
+    "lsb_amg_setup": (C.POINTER(AmgHier), [_csrp, _d, _u, _u]),
+    "lsb_amg_aggregate": (C.POINTER(C.c_int), [_csrp, _d, C.POINTER(_u)]),
+    "lsb_amg_free": (None, [C.POINTER(AmgHier)]),
     "lsb_sell16_templates": (C.POINTER(SellTmpls), [C.POINTER(Sell), C.POINTER(SellVc)]),
     "lsb_sell_tmpls_free": (None, [C.POINTER(SellTmpls)]),
     "lsb_tmpl_check": (_i, [C.POINTER(Sell), C.POINTER(SellVc), C.POINTER(SellTmpls), _u, _u, _u, _i,
@@ -217,6 +235,8 @@ SIGNATURES = {
     "lsb_hip_solver_solve": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
     "lsb_hip_solver_solve_dev": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
     "lsb_hip_solver_spmv_dev": (_i, [_vp, _vp, _vp]),
+    "lsb_hip_solver_precond_dev": (_i, [_vp, _vp, _vp]),
+    "lsb_hip_solver_amg_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u)]),
     "lsb_hip_solver_time_spmv": (_i, [_vp, _i, _i, C.POINTER(_d)]),
     "lsb_hip_solver_jacobi_sweep_dev": (_i, [_vp, _d, _vp, _vp]),
     "lsb_hip_solver_nrows_local": (_u, [_vp]),

@@ -276,6 +276,17 @@ class Solver:
     def spmv_dev(self, d_x, d_y):
         L.check(L.load().lsb_hip_solver_spmv_dev(self._h, _ptr(d_x), _ptr(d_y)), "spmv_dev")
 
+    def precond_dev(self, d_r, d_z):
+        """z = M^-1 r once with the solver's preconditioner (device buffers, n_local each)."""
+        L.check(L.load().lsb_hip_solver_precond_dev(self._h, _ptr(d_r), _ptr(d_z)), "precond_dev")
+
+    @property
+    def amg_info(self):
+        """(levels, levels in the one-launch tail) of an AMG-preconditioned solver."""
+        lv, tl = C.c_uint(), C.c_uint()
+        L.check(L.load().lsb_hip_solver_amg_info(self._h, C.byref(lv), C.byref(tl)), "amg_info")
+        return lv.value, tl.value
+
     def time_spmv(self, warm=5, reps=50):
         ms = C.c_double()
         L.check(L.load().lsb_hip_solver_time_spmv(self._h, warm, reps, C.byref(ms)),

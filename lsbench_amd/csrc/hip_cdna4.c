@@ -92,6 +92,11 @@ void lsb_hip_opts_default(struct lsb_hip_opts *o) {
   o->comm_deadline_s = 120.0;
   o->fsai_power = 3;
   o->blas1_nt = -1;
+  o->amg_theta = 0.08;
+  o->amg_sweeps = 1;
+  o->amg_coarse = 256;
+  o->amg_max_levels = 20;
+  o->amg_tail_rows = 0; /* measured: one workgroup is latency-bound, a launch per step is faster (profiles/r05_amg.txt) */
 }
 
 /* ONE typed table for everything a caller may set by name: the command line of a host
@@ -107,7 +112,7 @@ static const struct optchoice CH_OPERATOR[] = {{"upper", LSB_OP_CHOLMOD_UPPER}, 
 static const struct optchoice CH_PRECOND[] = {{"jacobi", LSB_PRECOND_JACOBI},   {"none", LSB_PRECOND_NONE},
                                               {"l1", LSB_PRECOND_L1JACOBI},     {"cheb", LSB_PRECOND_CHEBYSHEV},
                                               {"bj", LSB_PRECOND_BLOCKJACOBI},  {"fsai", LSB_PRECOND_FSAI},
-                                              {NULL, 0}};
+                                              {"amg", LSB_PRECOND_AMG},         {NULL, 0}};
 static const struct optchoice CH_COMM[] = {{"auto", LSB_COMM_AUTO}, {"rccl", LSB_COMM_RCCL}, {"p2p", LSB_COMM_P2P}, {NULL, 0}};
 static const struct optchoice CH_KRYLOV[] = {{"cg", LSB_KRYLOV_PCG},     {"pcg", LSB_KRYLOV_PCG}, /* (alias) */
                                              {"cg1", LSB_KRYLOV_PCG1},   {"pcg1", LSB_KRYLOV_PCG1},
@@ -146,6 +151,11 @@ static const struct optdef {
     OPT("comm-deadline-s", OT_DBL, comm_deadline_s, NULL),
     OPT("fsai-power", OT_INT, fsai_power, NULL),
     OPT("blas1-nt", OT_INT, blas1_nt, NULL),
+    OPT("amg-theta", OT_DBL, amg_theta, NULL),
+    OPT("amg-sweeps", OT_INT, amg_sweeps, NULL),
+    OPT("amg-coarse", OT_INT, amg_coarse, NULL),
+    OPT("amg-max-levels", OT_INT, amg_max_levels, NULL),
+    OPT("amg-tail-rows", OT_INT, amg_tail_rows, NULL),
 };
 #undef OPT
 #define NOPTS (sizeof OPTS / sizeof OPTS[0])

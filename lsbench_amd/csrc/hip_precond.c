@@ -11,7 +11,169 @@
 
 int generic_precond(const lsb_hip_solver *sv) {
   return sv->o.precond == LSB_PRECOND_CHEBYSHEV || sv->o.precond == LSB_PRECOND_BLOCKJACOBI ||
-         sv->o.precond == LSB_PRECOND_FSAI;
+         sv->o.precond == LSB_PRECOND_FSAI || sv->o.precond == LSB_PRECOND_AMG;
+}
+
+/* ---- AMG: hierarchy on the host (lsb_amg.c), V-cycle on the device (hip_amg.hip) ------------ */
+static void *amg_keep(struct amg_dev *a, void *p) {
+  a->mem[a->nmem++] = p;
+  return p;
+}
+
+/* lanes per row from the mean row length, as fsai_upload_csr picks them */
+static struct lsb_amg_mat amg_upload_mat(struct amg_dev *a, const struct csr *M) {
+  struct lsb_amg_mat m;
+  const unsigned n = M->nrows;
+  const unsigned long long nnz = M->offs[n];
+  if (nnz > 0x7fffffffull)
+    errx(EXIT_FAILURE, "hip_cdna4: an AMG operator has %llu entries, more than 2^31 - 1", nnz);
+  m.rows = n;
+  m.offs = (const int *)amg_keep(a, dev_upload(M->offs, ((size_t)n + 1) * sizeof(unsigned)));
+  m.cols = (const int *)amg_keep(a, dev_upload(M->cols, (size_t)(nnz ? nnz : 1) * sizeof(unsigned)));
+  m.vals = (const double *)amg_keep(a, dev_upload(M->vals, (size_t)(nnz ? nnz : 1) * sizeof(double)));
+  const unsigned mean = n ? (unsigned)((nnz + n - 1) / n) : 1;
+  const unsigned L = pow2_ceil(mean ? mean : 1);
+  m.lanes = L < 2 ? 2 : (L > 64 ? 64 : L);
+  return m;
+}
+
+static void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const double *vals,
+                              const struct lsb_hip_opts *o) {
+  if (s->row_begin != 0 || s->n != s->n_glob)
+    errx(EXIT_FAILURE, "hip_cdna4: --precond amg runs on one shard (the hierarchy couples all rows); use it "
+                       "without --ngpus / --nvirt");
+  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_PCG1)
+    errx(EXIT_FAILURE, "hip_cdna4: --precond amg runs under classic PCG (--krylov cg or auto), not %s",
+         o->krylov == LSB_KRYLOV_GMRES ? "gmres" : "cg1");
+  const double t0 = wall_seconds();
+  const unsigned n = s->n;
+  struct csr view = {n, 0, (unsigned *)offs, (unsigned *)cols, (double *)vals};
+  const unsigned coarse = o->amg_coarse < 1 ? 1u : (unsigned)o->amg_coarse;
+  const unsigned maxlev = o->amg_max_levels < 1 ? 1u : (o->amg_max_levels > 64 ? 64u : (unsigned)o->amg_max_levels);
+  struct lsb_amg_hier *h = lsb_amg_setup(&view, o->amg_theta, coarse, maxlev);
+  if (!h)
+    errx(EXIT_FAILURE, "hip_cdna4: cannot build the AMG hierarchy");
+  struct amg_dev *a = lsb_calloc(struct amg_dev, 1);
+  a->nlev = h->nlev, a->nc = h->nc;
+  a->nu = o->amg_sweeps < 1 ? 1u : (o->amg_sweeps > 16 ? 16u : (unsigned)o->amg_sweeps);
+  a->mem = lsb_calloc(void *, 12 * (size_t)h->nlev + 4);
+  a->lv = lsb_calloc(struct lsb_amg_lvdev, h->nlev);
+  a->tail = h->nlev;
+  for (unsigned l = 0; l < h->nlev; l++)
+    if (o->amg_tail_rows > 0 && h->lv[l].n <= (unsigned)o->amg_tail_rows) {
+      a->tail = l;
+      break;
+    }
+  unsigned long long nnz0 = 0, nnzall = 0;
+  for (unsigned l = 0; l < h->nlev; l++) {
+    const struct lsb_amg_level *L = &h->lv[l];
+    struct lsb_amg_lvdev *v = &a->lv[l];
+    v->n = L->n;
+    v->A = amg_upload_mat(a, L->A);
+    if (L->P) {
+      v->P = amg_upload_mat(a, L->P);
+      v->R = amg_upload_mat(a, L->R);
+    }
+    double *minv = (double *)malloc((size_t)(L->n ? L->n : 1) * sizeof(double));
+    for (unsigned i = 0; i < L->n; i++) {
+      double sum = 0.0;
+      for (unsigned e = L->A->offs[i]; e < L->A->offs[i + 1]; e++)
+        sum += fabs(L->A->vals[e]);
+      minv[i] = 1.0 / sum; /* > 0: lsb_amg_setup refused a diagonal <= 0 */
+    }
+    v->minv = (const double *)amg_keep(a, dev_upload(minv, (size_t)(L->n ? L->n : 1) * sizeof(double)));
+    LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+    free(minv);
+    if (l > 0) { /* level 0: the caller's r and z; its two other vectors come out of the slab (precond_setup) */
+      double *buf = (double *)amg_keep(a, lsb_hip_malloc(4 * (size_t)L->n * sizeof(double)));
+      LSB_CHK_HIP(hipMemsetAsync(buf, 0, 4 * (size_t)L->n * sizeof(double), g_stream));
+      v->b = buf, v->out = buf + L->n, v->tmp = buf + 2 * (size_t)L->n, v->r = buf + 3 * (size_t)L->n;
+    }
+    nnzall += L->A->offs[L->n];
+    if (l == 0)
+      nnz0 = L->A->offs[L->n];
+  }
+  a->d_cinv = (double *)amg_keep(a, dev_upload(h->coarse_inv, (size_t)h->nc * h->nc * sizeof(double)));
+  {
+    const unsigned L = pow2_ceil(h->nc ? h->nc : 1);
+    a->clanes = L < 2 ? 2 : (L > 64 ? 64 : L);
+  }
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  a->setup_s = wall_seconds() - t0;
+  if (o->verbose) {
+    for (unsigned l = 0; l < h->nlev; l++) {
+      const struct lsb_amg_level *L = &h->lv[l];
+      fprintf(stderr, "hip_cdna4: AMG level %u: %u rows, %u entries, %u lanes (A)", l, L->n, L->A->offs[L->n],
+              a->lv[l].A.lanes);
+      if (L->P)
+        fprintf(stderr, ", %u / %u lanes (P / R)\n", a->lv[l].P.lanes, a->lv[l].R.lanes);
+      else
+        fprintf(stderr, ", dense coarse inverse, %u lanes\n", a->clanes);
+    }
+    fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u of %u levels in the one-launch tail, %u sweep%s, "
+                    "set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev - a->tail, h->nlev, a->nu,
+            a->nu > 1 ? "s" : "", a->setup_s);
+  }
+  lsb_amg_free(h);
+  s->amg = a;
+}
+
+/* level 0's second smoothing buffer and residual, out of the vector slab; the descriptors to the device */
+static void amg_finish_setup(struct shard *s) {
+  struct amg_dev *a = s->amg;
+  a->lv[0].tmp = shard_vec(s, s->n), a->lv[0].r = shard_vec(s, s->n);
+  LSB_CHK_HIP(hipMemsetAsync(a->lv[0].tmp, 0, (size_t)s->n * sizeof(double), g_stream));
+  LSB_CHK_HIP(hipMemsetAsync(a->lv[0].r, 0, (size_t)s->n * sizeof(double), g_stream));
+  a->d_lv = (struct lsb_amg_lvdev *)amg_keep(a, dev_upload(a->lv, (size_t)a->nlev * sizeof(struct lsb_amg_lvdev)));
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+}
+
+/* z = one V-cycle on r; the launches of levels above the tail, the tail (or the coarse solve) */
+static void amg_vcycle(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st) {
+  const struct amg_dev *a = s->amg;
+  const unsigned nu = a->nu, top = a->tail < a->nlev ? a->tail : a->nlev - 1;
+  for (unsigned l = 0; l < top; l++) {
+    const struct lsb_amg_lvdev *v = &a->lv[l];
+    const double *b = l ? v->b : d_r;
+    double *out = l ? v->out : d_z, *cur = v->tmp, *oth = out;
+    lsb_k_amg_first(v->n, b, v->minv, cur, st, g_stream);
+    for (unsigned k = 1; k < nu; k++) {
+      lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
+      double *w = cur;
+      cur = oth, oth = w;
+    }
+    lsb_k_amg_csr(LSB_AMG_RESID, &v->A, cur, b, v->minv, v->r, st, g_stream);
+    lsb_k_amg_csr(LSB_AMG_SPMV, &v->R, v->r, NULL, NULL, a->lv[l + 1].b, st, g_stream);
+  }
+  if (a->tail < a->nlev)
+    lsb_k_amg_tail(a->d_lv, a->tail, a->nlev, nu, a->d_cinv, a->nc, a->clanes, d_r, d_z, st, g_stream);
+  else {
+    const unsigned c = a->nlev - 1;
+    lsb_k_amg_dense(a->nc, a->clanes, a->d_cinv, c ? a->lv[c].b : d_r, c ? a->lv[c].out : d_z, st, g_stream);
+  }
+  for (unsigned l = top; l-- > 0;) {
+    const struct lsb_amg_lvdev *v = &a->lv[l];
+    const double *b = l ? v->b : d_r;
+    double *out = l ? v->out : d_z;
+    double *cur = (nu - 1) % 2 ? out : v->tmp, *oth = (nu - 1) % 2 ? v->tmp : out;
+    lsb_k_amg_csr(LSB_AMG_ADDP, &v->P, a->lv[l + 1].out, NULL, NULL, cur, st, g_stream);
+    for (unsigned k = 0; k < nu; k++) { /* 2 nu - 1 out-of-place sweeps in all: the last one writes `out` */
+      lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
+      double *w = cur;
+      cur = oth, oth = w;
+    }
+  }
+}
+
+static void amg_free(struct shard *s) {
+  struct amg_dev *a = s->amg;
+  if (!a)
+    return;
+  for (unsigned k = 0; k < a->nmem; k++)
+    lsb_hip_free(a->mem[k]);
+  shard_vec_free(s, a->lv[0].tmp), shard_vec_free(s, a->lv[0].r);
+  free(a->mem), free(a->lv), free(a);
+  s->amg = NULL;
 }
 
 /* ---- FSAI: G on the pattern of tril(S^k), rows by batched dense solves on the device ------- */
@@ -133,6 +295,8 @@ void precond_shard_blocks(struct shard *s, const int *offs, const int *cols, con
                           const struct lsb_hip_opts *o) {
   if (o->precond == LSB_PRECOND_FSAI)
     precond_shard_fsai(s, offs, cols, vals, o);
+  if (o->precond == LSB_PRECOND_AMG)
+    precond_shard_amg(s, offs, cols, vals, o);
   if (o->precond != LSB_PRECOND_BLOCKJACOBI)
     return;
   unsigned bs = o->block_size < 1 ? 1u : (unsigned)o->block_size;
@@ -246,6 +410,8 @@ void precond_setup(lsb_hip_solver *sv) {
     s->d_z = sv->o.precond == LSB_PRECOND_CHEBYSHEV ? s->d_zfull + s->row_begin : s->d_zfull;
     if (sv->o.precond == LSB_PRECOND_CHEBYSHEV)
       s->d_chd = shard_vec(s, s->n);
+    if (sv->o.precond == LSB_PRECOND_AMG)
+      amg_finish_setup(s);
   }
   if (sv->o.precond != LSB_PRECOND_CHEBYSHEV)
     return;
@@ -337,6 +503,11 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
     fsai_spmv(s, &s->fs_gt, s->d_fst, s->d_z, s->d_st);
     return;
   }
+  if (sv->o.precond == LSB_PRECOND_AMG) { /* z = one V-cycle */
+    struct shard *s = &sv->sh[0];
+    amg_vcycle(s, s->d_r, s->d_z, s->d_st);
+    return;
+  }
   if (sv->o.precond == LSB_PRECOND_BLOCKJACOBI) {
     for (int i = 0; i < sv->nshard; i++) {
       struct shard *s = &sv->sh[i];
@@ -400,4 +571,50 @@ void precond_free_shard(struct shard *s) {
   lsb_hip_free(s->d_binv), lsb_hip_free(s->d_bjpart), shard_vec_free(s, s->d_zfull), shard_vec_free(s, s->d_chd);
   shard_vec_free(s, s->d_zfull2);
   fsai_free_csr(&s->fs_g), fsai_free_csr(&s->fs_gt), shard_vec_free(s, s->d_fst), shard_vec_free(s, s->d_r1);
+  amg_free(s);
+}
+
+/* z = M^-1 r once, outside a solve: r goes where the solve keeps it, the state is set running (the
+ * launches are gated on it), z comes back from the preconditioner's own vector */
+int lsb_hip_solver_precond_dev(lsb_hip_solver *sv, const double *d_r, double *d_z) {
+  if (!lsb_initialized)
+    return 1;
+  if (!sv || !d_r || !d_z || !generic_precond(sv))
+    return 2;
+  const double *rin = d_r;
+  if (sv->d_perm) { /* re-ordered / line-padded operator: the solver's own numbering */
+    lsb_k_perm_gather(sv->n_here, sv->d_perm, d_r, sv->d_bp, g_stream);
+    rin = sv->d_bp;
+  }
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    LSB_CHK_HIP(hipMemcpyAsync(s->d_r, rin + (s->row_begin - sv->row_first), (size_t)s->n * sizeof(double),
+                               hipMemcpyDeviceToDevice, g_stream));
+    LSB_CHK_HIP(hipMemsetAsync(&s->d_st->status, 0, sizeof(int), g_stream));
+  }
+  precond_apply(sv, 0);
+  double *zout = sv->d_perm ? sv->d_xp : d_z;
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    LSB_CHK_HIP(hipMemcpyAsync(zout + (s->row_begin - sv->row_first), s->d_z, (size_t)s->n * sizeof(double),
+                               hipMemcpyDeviceToDevice, g_stream));
+  }
+  if (sv->d_perm)
+    lsb_k_perm_scatter(sv->n_here, sv->d_perm, sv->d_xp, d_z, g_stream);
+  drain_stream(sv, "lsb_hip_solver_precond_dev");
+  check_aux_status(sv, "lsb_hip_solver_precond_dev");
+  return 0;
+}
+
+int lsb_hip_solver_amg_info(lsb_hip_solver *sv, unsigned *levels, unsigned *tail_levels) {
+  if (!lsb_initialized)
+    return 1;
+  if (!sv || sv->o.precond != LSB_PRECOND_AMG || !sv->sh[0].amg)
+    return 2;
+  const struct amg_dev *a = sv->sh[0].amg;
+  if (levels)
+    *levels = a->nlev;
+  if (tail_levels)
+    *tail_levels = a->nlev - a->tail;
+  return 0;
 }

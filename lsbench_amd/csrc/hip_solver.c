@@ -481,6 +481,9 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
       cnt += (size_t)n;                                        /* z */
     else if (o->precond == LSB_PRECOND_FSAI)
       cnt += 4 * (size_t)n;                                    /* z, t = G r, the second r / p buffers */
+    else if (o->precond == LSB_PRECOND_AMG)
+      cnt += 3 * (size_t)n;                                    /* z, the fine level's second smoothing
+                                                                  buffer and its residual */
     /* ... where the vectors are of the Infinity Cache's scale or below (n <= 20 M rows): that is where
      * their relative placement decides which lines fight for the same sets.  Vectors that fit no cache
      * gain nothing from it and measured 5 % SLOWER out of one allocation (64 M-row 7-point operator:
@@ -647,6 +650,10 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
     warnx("hip_cdna4: mixed precision is an iterative refinement around CG; GMRES runs in fp64");
     o.precision = LSB_PREC_FP64;
   }
+  if (o.precision == LSB_PREC_MIXED && o.precond == LSB_PRECOND_AMG) {
+    warnx("hip_cdna4: --precond amg runs in fp64");
+    o.precision = LSB_PREC_FP64;
+  }
   /* the operator, 0-based, both triangles */
   struct csr *S = o.op_mode == LSB_OP_CHOLMOD_UPPER ? lsb_csr_symmetrize_upper(A)
                                                     : lsb_csr_copy_base0(A);
@@ -734,7 +741,7 @@ lsb_hip_solver *lsb_hip_solver_create_dist(const struct csr *A_rows,
     o = *o_in;
   else
     lsb_hip_get_opts(&o);
-  if (o.precision == LSB_PREC_MIXED && o.krylov == LSB_KRYLOV_GMRES)
+  if (o.precision == LSB_PREC_MIXED && (o.krylov == LSB_KRYLOV_GMRES || o.precond == LSB_PRECOND_AMG))
     o.precision = LSB_PREC_FP64; /* as in lsb_hip_solver_create */
   const int P = lsb_hip_comm_size(), me = lsb_hip_comm_rank();
   lsb_hip_solver *sv = solver_alloc(1, &o);

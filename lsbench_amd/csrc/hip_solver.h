@@ -150,6 +150,15 @@ struct shard {
   double *d_fst;     /* t = G r */
   double *d_r1;      /* the three-launch iteration's second residual buffer */
   unsigned fs_maxrow; /* longest row of the pattern */
+  /* AMG (LSB_PRECOND_AMG): the hierarchy on the device, z = one V-cycle (hip_amg.hip) */
+  struct amg_dev {
+    unsigned nlev, tail, nu, nc, clanes; /* tail: first level of the one-launch tail (nlev: none) */
+    struct lsb_amg_lvdev *lv, *d_lv;     /* descriptors: host copy, device copy */
+    double *d_cinv;                      /* nc x nc coarse inverse */
+    void **mem;                          /* every allocation of the hierarchy */
+    unsigned nmem;
+    double setup_s;
+  } *amg;
   /* binned form (LSB_SPMV_BINNED), built for scattered operators only */
   unsigned bn, bcap;   /* bins (0 = not built), entries per chunk */
   unsigned *h_binchunk; /* bn+1: first chunk of each bin (host) */
@@ -307,8 +316,7 @@ LSB_INTERNAL void precond_shard_blocks(struct shard *s, const int *offs, const i
                                        const double *vals, const struct lsb_hip_opts *o);
 LSB_INTERNAL void precond_setup(lsb_hip_solver *sv);
 LSB_INTERNAL void precond_apply(lsb_hip_solver *sv, int after_update);
-LSB_INTERNAL void precond_free_shard(struct shard *s);
-/* hip_gmres_drv.c */
+LSB_INTERNAL void precond_free_shard(struct shard *s);/* hip_gmres_drv.c */
 LSB_INTERNAL int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
                                  struct lsb_hip_result *res);
 

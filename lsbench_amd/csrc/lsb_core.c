@@ -80,12 +80,15 @@ static void usage(const char *prog) {
   printf("  --nvirt <P>          (hip) P row-range shards on one device (test)\n");
   printf("  --krylov <cg|cg1|auto|gmres> (hip) cg1 = single-reduction CG, gmres for --operator raw\n");
   printf("  --restart <M>        (hip) GMRES restart length, 1..32, default 30\n");
-  printf("  --precond <jacobi|l1|none|cheb|bj|fsai> (hip) diag(S); diag(sum_j |S_ij|); none; Chebyshev\n");
+  printf("  --precond <jacobi|l1|none|cheb|bj|fsai|amg> (hip) diag(S); diag(sum_j |S_ij|); none; Chebyshev\n");
   printf("                       polynomial in D^-1 S (--cheb-degree M, default 4); block-Jacobi with\n");
   printf("                       dense inverted blocks of --block-size B rows (default 8; B >= n = a\n");
   printf("                       cached dense inverse, for operators of a few thousand rows); fsai =\n");
   printf("                       factorised sparse approximate inverse G^T G on the pattern of\n");
-  printf("                       tril(S^k), k = --fsai-power (default 3), set up once on the device\n");
+  printf("                       tril(S^k), k = --fsai-power (default 3), set up once on the device;\n");
+  printf("                       amg = smoothed-aggregation AMG, one V-cycle with l1-Jacobi sweeps\n");
+  printf("                       (--amg-theta T, --amg-sweeps NU, --amg-coarse ROWS, --amg-max-levels L,\n");
+  printf("                       --amg-tail-rows ROWS: levels run in one launch), one shard, cg only\n");
   printf("  --ngpus <N>          (hip) row-partition the operator over N GPUs of this node\n");
   printf("                       (0 = all visible), driven from this one process\n");
   printf("  --reorder            (hip) solve the RCM-permuted operator (any --ordering\n");
@@ -107,6 +110,9 @@ struct lsbench *lsbench_init(int argc, char *argv[]) {
       {"cheb-degree", required_argument, 0, 80}, {"block-size", required_argument, 0, 80},
       {"fsai-power", required_argument, 0, 80}, {"comm", required_argument, 0, 80},
       {"verify", required_argument, 0, 80},
+      {"amg-theta", required_argument, 0, 80}, {"amg-sweeps", required_argument, 0, 80},
+      {"amg-coarse", required_argument, 0, 80}, {"amg-max-levels", required_argument, 0, 80},
+      {"amg-tail-rows", required_argument, 0, 80},
       {0, 0, 0, 0}};
 
   /* zero-filled => solver 0 (CUSOLVER), ordering 0 (RCM), FP64: the

@@ -296,6 +296,37 @@ void lsb_p2p_test_setvals(double *d_v, int me, unsigned round, void *stream);
 void lsb_p2p_test_checkvals(const double *d_v, int R, unsigned round, unsigned *d_bad,
                             void *stream);
 
+/* ---- smoothed-aggregation AMG V-cycle (hip_amg.hip; set-up lsb_amg.c, hip_precond.c) ----
+ * One level as the kernels see it.  A CSR of the level: int offsets and columns (all < 2^31),
+ * `lanes` per row (2..64, from the mean row length), `rows` of them. */
+struct lsb_amg_mat {
+  const int *offs, *cols;
+  const double *vals;
+  unsigned rows, lanes;
+};
+struct lsb_amg_lvdev {
+  unsigned n, pad_;
+  struct lsb_amg_mat A, P, R; /* P: n rows, R: the next level's n rows (none on the coarsest) */
+  const double *minv;         /* 1 / sum_j |a_ij|: the l1-Jacobi smoother */
+  double *b, *out;            /* the level's right-hand side and correction (level 0: the caller's) */
+  double *tmp, *r;            /* the other smoothing buffer, the residual */
+};
+enum { LSB_AMG_SWEEP = 1, /* y = x + M^-1 (b - A x), out of place                 */
+       LSB_AMG_RESID = 2, /* r = b - A x                                           */
+       LSB_AMG_SPMV = 3,  /* y = M x for a rectangular M (the restriction R r)      */
+       LSB_AMG_ADDP = 4 };/* x += P e, in place (row i reads x_i only)              */
+void lsb_k_amg_first(unsigned n, const double *b, const double *minv, double *x,
+                     const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg_csr(int mode, const struct lsb_amg_mat *m, const double *xin, const double *b, const double *minv,
+                   double *y, const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg_dense(unsigned nc, unsigned lanes, const double *cinv, const double *b, double *out,
+                     const struct lsb_pcg_state *st, void *stream);
+/* levels t .. nlev - 1 of the V-cycle and the coarse solve in one launch of one 1024-thread
+ * workgroup; lv = the device copy of all levels' descriptors; b0 / out0 stand in for level 0's */
+void lsb_k_amg_tail(const struct lsb_amg_lvdev *lv, unsigned t, unsigned nlev, unsigned nu, const double *cinv,
+                    unsigned nc, unsigned clanes, const double *b0, double *out0, const struct lsb_pcg_state *st,
+                    void *stream);
+
 /* ---- backend internals shared between hip_cdna4.c and hip_comm.c -------- */
 void *lsb_hip_stream(void);
 int lsb_hip_is_initialized(void);
