@@ -134,11 +134,9 @@ void allreduce_pq(lsb_hip_solver *sv, unsigned cnt, int with2) {
 int can_overlap(const lsb_hip_solver *sv) {
   if (!sv->multi || !sv->o.overlap)
     return 0;
-  for (int i = 0; i < sv->nshard; i++) {
-    const struct shard *s = &sv->sh[i];
-    if (!(s->variant == LSB_SPMV_ADAPTIVE && s->ov_ok) && !(s->variant == LSB_SPMV_SELL && s->ov_sok))
+  for (int i = 0; i < sv->nshard; i++)
+    if (!shard_split(&sv->sh[i], NULL).ok)
       return 0;
-  }
   /* auto: the split SpMV costs 2 launches (direct path) or 2 launches and two cross-stream events
    * (RCCL) -- 18-25 us per iteration on one device -- and can only win what a halo transfer takes,
    * which no rule of thumb knows: both forms are TIMED on the real communicator at creation
@@ -161,10 +159,8 @@ void overlap_setup(lsb_hip_solver *sv) {
   if (!sv->multi || sv->o.overlap >= 0 || sv->o.krylov == LSB_KRYLOV_GMRES || getenv("LSBENCH_HIP_NO_OVERLAP_TUNE"))
     return;
   unsigned can = 1; /* the split needs the prefix / interior / suffix shape on every shard of every rank */
-  for (int i = 0; i < sv->nshard; i++) {
-    const struct shard *s = &sv->sh[i];
-    can &= (s->variant == LSB_SPMV_ADAPTIVE && s->ov_ok) || (s->variant == LSB_SPMV_SELL && s->ov_sok);
-  }
+  for (int i = 0; i < sv->nshard; i++)
+    can &= shard_split(&sv->sh[i], NULL).ok;
   const int P = sv->dist ? lsb_hip_comm_size() : 1;
   unsigned *all = lsb_calloc(unsigned, 2 * (size_t)P), mine[2] = {can, 0};
   if (sv->dist)
@@ -216,31 +212,29 @@ void overlap_setup(lsb_hip_solver *sv) {
   lsb_hip_free(d_b), lsb_hip_free(d_x);
 }
 
-/* part 0: the rows that need no halo; 1 / 2: the ones before / after them */
-void spmv_range(struct shard *s, int part, double *y, double *partials, unsigned *np,
-                       const struct lsb_pcg_state *st) {
-  *np = 0;
-  if (s->variant == LSB_SPMV_SELL) {
-    const unsigned b0 = part == 0 ? s->ov_s1 : part == 1 ? 0 : s->ov_s2;
-    const unsigned b1 = part == 0 ? s->ov_s2 : part == 1 ? s->ov_s1 : s->nslice;
-    if (b1 > b0)
-      sell_launch(s, b0, b1 - b0, s->d_pfull, y, s->d_pfull + s->row_begin, partials, np, st);
-    return;
-  }
-  const unsigned b0 = part == 0 ? s->ov_b1 : part == 1 ? 0 : s->ov_b2;
-  const unsigned b1 = part == 0 ? s->ov_b2 : part == 1 ? s->ov_b1 : s->nblk;
-  if (b1 > b0)
-    lsb_k_spmv(LSB_SPMV_ADAPTIVE, s->n, s->d_offs, s->d_cols, s->d_vals, s->d_rowblk + b0,
-               s->d_blklanes + b0, b1 - b0, s->lanes, s->sp_flags, s->sp_grid, s->d_pfull, y,
-               s->d_pfull + s->row_begin, partials, np, st, NULL, &s->tail, g_stream);
+/* units [*b0, *b0 + count) of the split SpMV's part (row blocks or slices, shard_split): part 0 the ones
+ * that need no halo; 1 / 2 the ones before / after them */
+static unsigned range_len(const struct shard *s, int part, unsigned *b0) {
+  unsigned cnt;
+  const struct halo_split sp = shard_split(s, &cnt);
+  const unsigned b1 = part == 0 ? sp.last : part == 1 ? sp.first : cnt;
+  *b0 = part == 0 ? sp.first : part == 1 ? 0 : sp.last;
+  return b1 > *b0 ? b1 - *b0 : 0;
 }
 
-/* rows of the split SpMV's part (see spmv_range) */
-static unsigned range_len(const struct shard *s, int part) {
-  const unsigned a = s->variant == LSB_SPMV_SELL ? s->ov_s1 : s->ov_b1;
-  const unsigned b = s->variant == LSB_SPMV_SELL ? s->ov_s2 : s->ov_b2;
-  const unsigned e = s->variant == LSB_SPMV_SELL ? s->nslice : s->nblk;
-  return part == 0 ? (b > a ? b - a : 0) : part == 1 ? a : (e > b ? e - b : 0);
+void spmv_range(struct shard *s, int part, double *y, double *partials, unsigned *np,
+                       const struct lsb_pcg_state *st) {
+  unsigned b0;
+  const unsigned nb = range_len(s, part, &b0);
+  *np = 0;
+  if (!nb)
+    return;
+  if (s->variant == LSB_SPMV_SELL)
+    sell_launch(s, b0, nb, s->d_pfull, y, s->d_pfull + s->row_begin, partials, np, st);
+  else
+    lsb_k_spmv(LSB_SPMV_ADAPTIVE, s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->csr.rowblk + b0,
+               s->csr.blklanes + b0, nb, s->lanes, s->sp_flags, s->sp_grid, s->d_pfull, y,
+               s->d_pfull + s->row_begin, partials, np, st, NULL, &s->tail, g_stream);
 }
 
 /* The all-reduce of {w.u; the sweep's r.u, r.r} folded into neighbouring
@@ -317,10 +311,10 @@ void exchange_and_spmv(lsb_hip_solver *sv, int sample) {
   }
   if (sample >= 0)
     LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample], g_stream));
-  unsigned na, nb, nc;
+  unsigned na, nb, nc, b0;
   for (int i = 0; i < sv->nshard; i++) {                         /* interior: no halo     */
     struct shard *s = &sv->sh[i];
-    if (fold && !range_len(s, 1) && !range_len(s, 2))
+    if (fold && !range_len(s, 1, &b0) && !range_len(s, 2, &b0))
       arm_tail(sv, i, 0);
     spmv_range(s, 0, s->d_q, s->d_parts_pq, &na, s->d_st);
     s->tail.counter = NULL;
@@ -333,11 +327,11 @@ void exchange_and_spmv(lsb_hip_solver *sv, int sample) {
     LSB_CHK_HIP(hipStreamWaitEvent(g_stream, sv->ev_halo, 0));
   for (int i = 0; i < sv->nshard; i++) {                         /* boundary rows         */
     struct shard *s = &sv->sh[i];
-    if (fold && range_len(s, 1) && !range_len(s, 2))
+    if (fold && range_len(s, 1, &b0) && !range_len(s, 2, &b0))
       arm_tail(sv, i, s->npq);
     spmv_range(s, 1, s->d_q, s->d_parts_pq + s->npq, &nb, s->d_st);
     s->tail.counter = NULL;
-    if (fold && range_len(s, 2))
+    if (fold && range_len(s, 2, &b0))
       arm_tail(sv, i, s->npq + nb);
     spmv_range(s, 2, s->d_q, s->d_parts_pq + s->npq + nb, &nc, s->d_st);
     s->tail.counter = NULL;

@@ -2828,12 +2828,9 @@ void lsb_k_spmv_sell(unsigned flags, unsigned grid_cap, unsigned period, const u
 
 /* The constant-slot layout through slice templates (k_spmv_tmpl).  vals: the kept value slots
  * (fp32 when flags & LSB_SP_F32; the templates' constants are then fp32-rounded by the caller). */
-void lsb_k_spmv_tmpl(unsigned flags, unsigned grid_cap, unsigned period, const unsigned *sptr, unsigned s0,
-                     unsigned ns, unsigned n, unsigned row_begin, unsigned xlen, const unsigned *srec,
-                     const unsigned long long *mask, const struct lsb_sell_tmpl *td,
-                     unsigned nfar, const int *sbase, const void *vals,
-                     const double *vconst, const double *x, double *y, const double *xdot,
-                     double *partials, unsigned *npartials, const struct lsb_pcg_state *st,
+void lsb_k_spmv_tmpl(unsigned flags, unsigned grid_cap, unsigned period, const struct lsb_sell16_dev *c, unsigned s0,
+                     unsigned ns, unsigned n, unsigned row_begin, unsigned xlen, const double *x, double *y,
+                     const double *xdot, double *partials, unsigned *npartials, const struct lsb_pcg_state *st,
                      const struct lsb_ar_tail *tail_in, const struct lsb_cheb_epi *epi_in, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const lsb_ar_tail tail = tail_for(tail_in, partials);
@@ -2850,35 +2847,34 @@ void lsb_k_spmv_tmpl(unsigned flags, unsigned grid_cap, unsigned period, const u
   if (period && (period < NXCD || ns < period))
     period = 0;
   const int f32 = (flags & LSB_SP_F32) != 0, dot_is_x = xdot && xdot == x + row_begin;
+#define LSB_TMPL_ARGS                                                                                           \
+  c->sptr, s0, ns, period, n, row_begin, xlen, (const u4v *)c->tmpl.srec, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals, \
+      f32, c->vconst, x, y, xdot, dot_is_x, partials, st, tail, epi
 #define LSB_TMPL(NF)                                                                                 \
   do {                                                                                               \
     if (epi.zout)                                                                                    \
-      k_spmv_tmpl<NF, true><<<g, WG, 0, s>>>(sptr, s0, ns, period, n, row_begin, xlen, (const u4v *)srec, mask, td, sbase, vals, f32, \
-                                             vconst, x, y, xdot, dot_is_x, partials, st, tail, epi);   \
+      k_spmv_tmpl<NF, true><<<g, WG, 0, s>>>(LSB_TMPL_ARGS);                                         \
     else if (flags & LSB_SP_DEFER)                                                                   \
-      k_spmv_tmpl<NF, false, true><<<g, WG, 0, s>>>(sptr, s0, ns, period, n, row_begin, xlen, (const u4v *)srec, mask, td, sbase, vals, f32, \
-                                                    vconst, x, y, xdot, dot_is_x, partials, st, tail, epi); \
+      k_spmv_tmpl<NF, false, true><<<g, WG, 0, s>>>(LSB_TMPL_ARGS);                                  \
     else                                                                                             \
-      k_spmv_tmpl<NF, false><<<g, WG, 0, s>>>(sptr, s0, ns, period, n, row_begin, xlen, (const u4v *)srec, mask, td, sbase, vals, f32, \
-                                              vconst, x, y, xdot, dot_is_x, partials, st, tail, epi);  \
+      k_spmv_tmpl<NF, false><<<g, WG, 0, s>>>(LSB_TMPL_ARGS);                                        \
   } while (0)
-  switch (nfar) {
+  switch (c->tmpl.nfar) {
   case 0: LSB_TMPL(0); break;
   case 1: LSB_TMPL(1); break;
   case 2: LSB_TMPL(2); break;
-  default: errx(EXIT_FAILURE, "lsb_k_spmv_tmpl: %u far slots per side", nfar);
+  default: errx(EXIT_FAILURE, "lsb_k_spmv_tmpl: %u far slots per side", c->tmpl.nfar);
   }
 #undef LSB_TMPL
+#undef LSB_TMPL_ARGS
 }
 
 /* The template layout walked in z-columns (k_spmv_tmpl_col): plan = xbeg[NXCD + 1], padding to 16
  * unsigneds, then nitem 16-byte items (lsb_sell_tmpl_columns).  Whole launches only (every slice of
  * the shard is in exactly one item). */
 void lsb_k_spmv_tmpl_col(unsigned flags, unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem,
-                         int centre0, unsigned n, unsigned row_begin, unsigned xlen, const unsigned *sptr,
-                         const unsigned long long *mask, const struct lsb_sell_tmpl *td, unsigned nfar,
-                         const int *sbase, const void *vals, const double *vconst, const double *x, double *y,
-                         const double *xdot, double *partials, unsigned *npartials,
+                         int centre0, unsigned n, unsigned row_begin, unsigned xlen, const struct lsb_sell16_dev *c,
+                         const double *x, double *y, const double *xdot, double *partials, unsigned *npartials,
                          const struct lsb_pcg_state *st, const struct lsb_ar_tail *tail_in, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const lsb_ar_tail tail = tail_for(tail_in, partials);
@@ -2893,8 +2889,8 @@ void lsb_k_spmv_tmpl_col(unsigned flags, unsigned grid_cap, unsigned period, con
   // the plan builder says so in lsb_tmpl_cols.centre0)
   const int dot = !partials || !xdot ? 0 : (xdot == x + row_begin && centre0) ? 1 : 2;
 #define LSB_COL(NF, D)                                                                                \
-  k_spmv_tmpl_col<NF, D><<<g, WG, 0, s>>>(plan, period, n, row_begin, xlen, sptr, mask, td, sbase, vals, f32, vconst, x, y, \
-                                          xdot, partials, st, tail)
+  k_spmv_tmpl_col<NF, D><<<g, WG, 0, s>>>(plan, period, n, row_begin, xlen, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, \
+                                          c->vals, f32, c->vconst, x, y, xdot, partials, st, tail)
 #define LSB_COLD(NF)                                                                                  \
   do {                                                                                                \
     if (dot == 0)                                                                                     \
@@ -2904,10 +2900,10 @@ void lsb_k_spmv_tmpl_col(unsigned flags, unsigned grid_cap, unsigned period, con
     else                                                                                              \
       LSB_COL(NF, 2);                                                                                 \
   } while (0)
-  switch (nfar) {
+  switch (c->tmpl.nfar) {
   case 1: LSB_COLD(1); break;
   case 2: LSB_COLD(2); break;
-  default: errx(EXIT_FAILURE, "lsb_k_spmv_tmpl_col: %u far slots per side", nfar);
+  default: errx(EXIT_FAILURE, "lsb_k_spmv_tmpl_col: %u far slots per side", c->tmpl.nfar);
   }
 #undef LSB_COLD
 #undef LSB_COL
@@ -3038,12 +3034,11 @@ void lsb_k_pcg_update_xr(unsigned n, const double *p, const double *q,
 }
 
 void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem, unsigned n,
-                      const unsigned *sptr, const unsigned long long *mask, const struct lsb_sell_tmpl *td,
-                      unsigned nfar, const int *sbase, const double *vals, const double *vconst, const double *r,
-                      const double *pold, double *pnew, double *x, int xupd, double dc, double *partials,
-                      unsigned *npartials, struct lsb_pcg_state *st, int parity, const double *parts2,
-                      unsigned nparts2, void *stream) {
+                      const struct lsb_sell16_dev *c, const double *r, const double *pold, double *pnew, double *x,
+                      int xupd, double dc, double *partials, unsigned *npartials, struct lsb_pcg_state *st, int parity,
+                      const double *parts2, unsigned nparts2, void *stream) {
   hipStream_t s = (hipStream_t)stream;
+  const unsigned nfar = c->tmpl.nfar;
   /* every workgroup resident: three per CU with two far slots per side (<= 168 VGPRs), five with one (<= 96, what
    * the kernel's launch bounds hold it to: with x it needed 102 and only four were resident, the grid's last fifth
    * ran as a second wave).  The plan's walk directions are dealt against this grid (LSB_TMPL_COL_TURN) */
@@ -3055,14 +3050,15 @@ void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, 
     errx(EXIT_FAILURE, "lsb_k_pcg_col_px: no column plan (period %u) or one direction buffer", period);
   /* x, p' and q streamed nontemporally (NT = 3; measured against 0 / 1 / 2 on config 4: 950.5 / 950.3 / 905.7 /
    * 894.1 us per iteration, profiles/r04_px.txt) */
+#define LSB_PX_ARGS                                                                                   \
+  plan, period, n, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals, c->vconst, r, pold, pnew, x, dc, partials, st, \
+      parity, parts2, nparts2
 #define LSB_PX(NF)                                                                                    \
   do {                                                                                                \
     if (xupd)                                                                                         \
-      k_pcg_col_px<NF, 3, true><<<g, WG, 0, s>>>(plan, period, n, sptr, mask, td, sbase, vals, vconst, r, pold, pnew, x, dc, \
-                                                 partials, st, parity, parts2, nparts2);              \
+      k_pcg_col_px<NF, 3, true><<<g, WG, 0, s>>>(LSB_PX_ARGS);                                        \
     else                                                                                              \
-      k_pcg_col_px<NF, 3, false><<<g, WG, 0, s>>>(plan, period, n, sptr, mask, td, sbase, vals, vconst, r, pold, pnew, x, \
-                                                  dc, partials, st, parity, parts2, nparts2);         \
+      k_pcg_col_px<NF, 3, false><<<g, WG, 0, s>>>(LSB_PX_ARGS);                                       \
   } while (0)
   switch (nfar) {
   case 1: LSB_PX(1); break;
@@ -3070,30 +3066,28 @@ void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, 
   default: errx(EXIT_FAILURE, "lsb_k_pcg_col_px: %u far slots per side", nfar);
   }
 #undef LSB_PX
+#undef LSB_PX_ARGS
 }
 
 void lsb_k_pcg_col_r(unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem, unsigned n,
-                     const unsigned *sptr, const unsigned long long *mask, const struct lsb_sell_tmpl *td, unsigned nfar,
-                     const int *sbase, const double *vals, const double *vconst, const double *p, double *r, double dc,
-                     struct lsb_pcg_state *st, int parity, int pbuf, int xtwo, const double *pq_parts, unsigned npq,
-                     double *partials2, unsigned *npartials, void *stream) {
+                     const struct lsb_sell16_dev *c, const double *p, double *r, double dc, struct lsb_pcg_state *st,
+                     int parity, int pbuf, int xtwo, const double *pq_parts, unsigned npq, double *partials2,
+                     unsigned *npartials, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   /* five workgroups per CU (launch bounds): the grid of lsb_k_pcg_col_px with one far slot per side */
   const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, nitem, 0, grid_cap && grid_cap < 1280u ? grid_cap : 1280u);
   *npartials = g;
   if (period < NXCD || !plan)
     errx(EXIT_FAILURE, "lsb_k_pcg_col_r: no column plan (period %u)", period);
-  switch (nfar) {
-  case 1:
-    k_pcg_col_r<1><<<g, WG, 0, s>>>(plan, period, n, sptr, mask, td, sbase, vals, vconst, p, r, dc, st, parity, pbuf,
-                                    xtwo, pq_parts, npq, partials2);
-    break;
-  case 2:
-    k_pcg_col_r<2><<<g, WG, 0, s>>>(plan, period, n, sptr, mask, td, sbase, vals, vconst, p, r, dc, st, parity, pbuf,
-                                    xtwo, pq_parts, npq, partials2);
-    break;
-  default: errx(EXIT_FAILURE, "lsb_k_pcg_col_r: %u far slots per side", nfar);
+#define LSB_R_ARGS                                                                                                \
+  plan, period, n, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals, c->vconst, p, r, dc, st, parity, pbuf, xtwo, \
+      pq_parts, npq, partials2
+  switch (c->tmpl.nfar) {
+  case 1: k_pcg_col_r<1><<<g, WG, 0, s>>>(LSB_R_ARGS); break;
+  case 2: k_pcg_col_r<2><<<g, WG, 0, s>>>(LSB_R_ARGS); break;
+  default: errx(EXIT_FAILURE, "lsb_k_pcg_col_r: %u far slots per side", c->tmpl.nfar);
   }
+#undef LSB_R_ARGS
 }
 
 void lsb_k_pcg_xfix(unsigned n, const double *p0, const double *p1, double *x, const struct lsb_pcg_state *st,

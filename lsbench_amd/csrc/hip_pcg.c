@@ -108,7 +108,7 @@ static void fsai_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int p
     sv->pcur = 0, sv->rcur = 0;
     spmv_shard(s, pb[0], s->d_q, pb[0], s->d_parts_pq, &s->npq, s->d_st);
   } else {
-    lsb_k_spmv_subwave_p(s->n, s->d_offs, s->d_cols, s->d_vals, s->lanes, s->d_z, NULL, 1.0, pb[sv->pcur],
+    lsb_k_spmv_subwave_p(s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->lanes, s->d_z, NULL, 1.0, pb[sv->pcur],
                          pb[sv->pcur ^ 1], s->d_q, s->d_parts_pq, &s->npq, s->d_st, parity ^ 1, s->d_parts2,
                          s->np2, g_stream);
     sv->pcur ^= 1;
@@ -184,8 +184,7 @@ int lsb_fuse_p_kind(const lsb_hip_solver *sv) {
    * half of the first sweep ride in the next SpMV launch, the r half forms S p again instead of reading a
    * stored q, x is updated every second iteration with two directions at once (k_pcg_col_px + k_pcg_col_r: 60
    * instead of 88 bytes per row and iteration) */
-  if (s->variant == LSB_SPMV_SELL && (s->sp_flags & LSB_SP_COL) && (s->sp_flags & LSB_SP_TMPL) && s->d_colplan &&
-      s->d_srec && s->dinv_uniform && s->tmpl_nfar >= 1 && s->tmpl_nfar <= 2 && s->row_begin == 0 &&
+  if (s->sell_form == SELL_COL && s->dinv_uniform && s->c16.tmpl.nfar >= 1 && s->c16.tmpl.nfar <= 2 && s->row_begin == 0 &&
       s->n == s->n_glob && sv->o.precond == LSB_PRECOND_JACOBI && !no_fuse_px)
     return 2; /* (event-timed too: the sample brackets the launch that carries the SpMV) */
   /* (not while SpMV launches are being event-timed: the fused launch has no SpMV of its own to
@@ -234,8 +233,7 @@ static void fused_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int 
       sv->pcur = 0;
       spmv_shard(s, buf[0], s->d_q, buf[0], s->d_parts_pq, &s->npq, s->d_st);
     } else {
-      lsb_k_pcg_col_px(s->sp_grid, s->col_period, s->d_colplan, s->col_items, s->n, s->d_sptr16, s->d_tmask,
-                       s->d_tmpl, s->tmpl_nfar, s->d_sbase, s->d_svals16, s->d_svconst, s->d_r, buf[sv->pcur],
+      lsb_k_pcg_col_px(s->sp_grid, s->col.period, s->col.plan, s->col.items, s->n, &s->c16, s->d_r, buf[sv->pcur],
                        buf[sv->pcur ^ 1], d_x, /* x updated by the run's even iterations, two steps at once */ parity == 0,
                        s->dinv_const, s->d_parts_pq,
                        &s->npq, s->d_st, parity ^ 1, s->d_parts2, np2, g_stream);
@@ -247,8 +245,8 @@ static void fused_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int 
       LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 3], g_stream));
     }
     /* r -= alpha S p with S p formed again out of p (k_pcg_col_r): q never travels */
-    lsb_k_pcg_col_r(s->sp_grid, s->col_period, s->d_colplan, s->col_items, s->n, s->d_sptr16, s->d_tmask, s->d_tmpl,
-                    s->tmpl_nfar, s->d_sbase, s->d_svals16, s->d_svconst, buf[sv->pcur], s->d_r, s->dinv_const, s->d_st,
+    lsb_k_pcg_col_r(s->sp_grid, s->col.period, s->col.plan, s->col.items, s->n, &s->c16, buf[sv->pcur], s->d_r,
+                    s->dinv_const, s->d_st,
                     parity, sv->pcur, /* x is two updates behind after an odd iteration */ parity != 0, s->d_parts_pq, s->npq,
                     s->d_parts2, &s->np2, g_stream);
     if (pos & 2) { /* last of the run: the pending x update, then the direction back into the gather vector */
@@ -262,7 +260,7 @@ static void fused_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int 
     sv->pcur = 0;
     spmv_shard(s, buf[0], s->d_q, buf[0], s->d_parts_pq, &s->npq, s->d_st);
   } else { /* beta, stop test and p = D^-1 r + beta p of the previous iteration, then S p */
-    lsb_k_spmv_subwave_p(s->n, s->d_offs, s->d_cols, s->d_vals, s->lanes, s->d_r, DINV(s),
+    lsb_k_spmv_subwave_p(s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->lanes, s->d_r, DINV(s),
                          buf[sv->pcur], buf[sv->pcur ^ 1], s->d_q, s->d_parts_pq, &s->npq, s->d_st,
                          parity ^ 1, s->d_parts2, np2, g_stream);
     sv->pcur ^= 1;
@@ -705,8 +703,8 @@ static int persist_run(lsb_hip_solver *sv, const double *d_b, double *d_x, doubl
       hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0)
     khz = 100000, (void)hipGetLastError();
   LSB_CHK_HIP(hipMemsetAsync(sv->ps.d_shared, 0, 64, g_stream));
-  return lsb_k_pcg_persist(s->n, sv->ps.G, sv->ps.stride, sv->ps.d_wgrow, s->d_offs, s->d_cols,
-                           s->d_vals, s->d_dinv, d_b, d_x, sv->ps.d_ug, sv->ps.d_shared, s->d_st, tol,
+  return lsb_k_pcg_persist(s->n, sv->ps.G, sv->ps.stride, sv->ps.d_wgrow, s->csr.offs, s->csr.cols,
+                           s->csr.vals, s->d_dinv, d_b, d_x, sv->ps.d_ug, sv->ps.d_shared, s->d_st, tol,
                            maxit, sv->ps.lanes, 2000ll * khz, g_stream);
 }
 
@@ -738,7 +736,7 @@ void persist_setup(lsb_hip_solver *sv) {
   /* rows to workgroups: contiguous, balanced by non-zeros */
   int *offs = (int *)malloc(((size_t)s->n + 1) * sizeof(int));
   unsigned *row = (unsigned *)malloc(((size_t)G + 1) * sizeof(unsigned));
-  LSB_CHK_HIP(hipMemcpy(offs, s->d_offs, ((size_t)s->n + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  LSB_CHK_HIP(hipMemcpy(offs, s->csr.offs, ((size_t)s->n + 1) * sizeof(int), hipMemcpyDeviceToHost));
   int ok = 1;
   row[0] = 0;
   for (unsigned g = 1, r = 0; g <= G; g++) {

@@ -251,9 +251,9 @@ static void precond_shard_fsai(struct shard *s, const int *offs, const int *cols
   double *d_g = (double *)lsb_hip_malloc((size_t)(P->nnz ? P->nnz : 1) * sizeof(double));
   int *d_bad = (int *)lsb_hip_malloc(sizeof(int)), bad = 0;
   LSB_CHK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), g_stream));
-  lsb_k_fsai_rows(d_small, nsmall, 32, s->d_offs, s->d_cols, s->d_vals, s->row_begin, d_poffs, d_pcols, d_g, d_bad,
+  lsb_k_fsai_rows(d_small, nsmall, 32, s->csr.offs, s->csr.cols, s->csr.vals, s->row_begin, d_poffs, d_pcols, d_g, d_bad,
                   g_stream);
-  lsb_k_fsai_rows(d_big, nbig, LSB_FSAI_CAP, s->d_offs, s->d_cols, s->d_vals, s->row_begin, d_poffs, d_pcols, d_g,
+  lsb_k_fsai_rows(d_big, nbig, LSB_FSAI_CAP, s->csr.offs, s->csr.cols, s->csr.vals, s->row_begin, d_poffs, d_pcols, d_g,
                   d_bad, g_stream);
   double *g = (double *)malloc((size_t)(P->nnz ? P->nnz : 1) * sizeof(double));
   LSB_CHK_HIP(hipMemcpyAsync(g, d_g, (size_t)P->nnz * sizeof(double), hipMemcpyDeviceToHost, g_stream));
@@ -474,11 +474,8 @@ void precond_setup(lsb_hip_solver *sv) {
   {
     const char *e = getenv("LSBENCH_HIP_CHEB_FUSE");
     sv->cheb_fused = !(e && atoi(e) == 0);
-    for (int i = 0; i < sv->nshard; i++) {
-      const struct shard *s = &sv->sh[i];
-      sv->cheb_fused &= s->variant == LSB_SPMV_SELL && (s->sp_flags & LSB_SP_C16) && s->d_scodes &&
-                        !(s->row_begin & 1u);
-    }
+    for (int i = 0; i < sv->nshard; i++)
+      sv->cheb_fused &= sv->sh[i].sell_form >= SELL_16 && !(sv->sh[i].row_begin & 1u);
     for (int i = 0; i < sv->nshard && sv->cheb_fused; i++) {
       struct shard *s = &sv->sh[i];
       s->d_zfull2 = shard_vec(s, sv->n_glob);
@@ -538,7 +535,7 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
         s->epi.r = s->d_r, s->epi.dinv = s->dinv_uniform ? NULL : s->d_dinv, s->epi.dc = s->dinv_const;
         s->epi.a = sv->cheb_a[k], s->epi.b = sv->cheb_b[k], s->epi.d = s->d_chd;
         s->epi.zout = ((k & 1) ? s->d_zfull : s->d_zfull2) + s->row_begin;
-        sell_launch(s, 0, s->nslice, s->d_pfull, NULL, NULL, NULL, NULL, s->d_st);
+        sell_launch(s, 0, s->sell.nslice, s->d_pfull, NULL, NULL, NULL, NULL, s->d_st);
         s->epi.zout = NULL;
       }
       for (int i = 0; i < sv->nshard; i++)

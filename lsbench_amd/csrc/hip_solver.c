@@ -25,13 +25,13 @@ void choose_spmv(struct shard *s, const struct lsb_hip_opts *o) {
    * and wins 3.2 vs 5.7 us per launch on tests/xn3b_A_18.txt. */
   if (v == LSB_SPMV_AUTO)
     v = s->nnz <= 500000ull ? LSB_SPMV_SUBWAVE : LSB_SPMV_ADAPTIVE;
-  if (v == LSB_SPMV_PANEL && !s->pn)
+  if (v == LSB_SPMV_PANEL && !s->panel.n)
     v = LSB_SPMV_ADAPTIVE; /* the operator did not qualify for panels */
-  if (v == LSB_SPMV_BINNED && !s->bn)
+  if (v == LSB_SPMV_BINNED && !s->bins.n)
     v = LSB_SPMV_ADAPTIVE;
-  if (v == LSB_SPMV_TWOPHASE && !s->tp_bins)
+  if (v == LSB_SPMV_TWOPHASE && !s->tp.bins)
     v = LSB_SPMV_ADAPTIVE;
-  if (v == LSB_SPMV_SELL && !s->d_sptr)
+  if (v == LSB_SPMV_SELL && !s->sell.sptr)
     v = LSB_SPMV_ADAPTIVE; /* no sliced-ELL copy (32-bit offsets exceeded) */
   s->variant = v;
   unsigned L = pow2_ceil(mean ? mean : 1);
@@ -40,62 +40,6 @@ void choose_spmv(struct shard *s, const struct lsb_hip_opts *o) {
   if (L > 64)
     L = 64;
   s->lanes = L;
-}
-
-
-/* Column-panel form of the shard (lsb_csr_panelize) + its row blocks, one run
- * of blocks per panel so that a launch never crosses a panel. */
-static void shard_build_panels(struct shard *s, const struct csr *view, unsigned width) {
-  struct lsb_panel_csr *P = lsb_csr_panelize(view, width);
-  const unsigned np = P->npanels;
-  s->h_pblk = lsb_calloc(unsigned, (size_t)np + 1);
-  size_t cap = (size_t)P->offs[P->npairs] / LSB_BLOCK_NNZ * 2 + 4 * (size_t)np + 16, nb = 0;
-  unsigned *rball = (unsigned *)malloc((cap + 1) * sizeof(unsigned));
-  unsigned char *lanes = (unsigned char *)malloc(cap + 1);
-  for (unsigned p = 0; p < np; p++) {
-    const unsigned b0 = P->pair_begin[p], cnt = P->pair_begin[p + 1] - b0;
-    s->h_pblk[p] = (unsigned)nb;
-    if (cnt == 0)
-      continue;
-    struct csr sub = {cnt, 0, P->offs + b0, NULL, NULL};
-    unsigned *rb = NULL;
-    const unsigned k = lsb_csr_row_blocks(&sub, LSB_BLOCK_NNZ, &rb);
-    if (nb + k + 1 > cap)
-      errx(EXIT_FAILURE, "hip_cdna4: panel row-block estimate too small");
-    lsb_csr_block_lanes(&sub, rb, k, lanes + nb);
-    for (unsigned i = 0; i <= k; i++)
-      rball[nb + i] = rb[i] + b0; /* the last entry is the next panel's first */
-    nb += k;
-    free(rb);
-  }
-  s->h_pblk[np] = (unsigned)nb;
-  rball[nb] = P->npairs;
-  s->pn = np;
-  s->pd_offs = (int *)dev_upload(P->offs, ((size_t)P->npairs + 1) * sizeof(int));
-  s->pd_cols = (int *)dev_upload(P->cols, (size_t)P->offs[P->npairs] * sizeof(int));
-  s->pd_vals = (double *)dev_upload(P->vals, (size_t)P->offs[P->npairs] * sizeof(double));
-  s->pd_rowmap = (int *)dev_upload(P->pair_row, (size_t)P->npairs * sizeof(int));
-  s->pd_rowblk = (int *)dev_upload(rball, (nb + 1) * sizeof(int));
-  s->pd_blklanes = (unsigned char *)dev_upload(lanes, nb ? nb : 1);
-  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-  free(rball), free(lanes);
-  lsb_panel_csr_free(P);
-}
-
-/* Binned form of the shard (lsb_csr_binize), uploaded as it is. */
-static void shard_build_bins(struct shard *s, const struct csr *view, unsigned width) {
-  struct lsb_binned *B = lsb_csr_binize(view, width);
-  if (!B)
-    return;
-  s->bn = B->nbins, s->bcap = B->chunk_cap;
-  s->h_binchunk = (unsigned *)malloc(((size_t)B->nbins + 1) * sizeof(unsigned));
-  memcpy(s->h_binchunk, B->bin_chunk, ((size_t)B->nbins + 1) * sizeof(unsigned));
-  s->bd_chunk = (unsigned *)dev_upload(B->chunk_begin, ((size_t)B->nchunks + 1) * sizeof(unsigned));
-  s->bd_rows = (unsigned *)dev_upload(B->rows, (size_t)B->nnz * sizeof(unsigned));
-  s->bd_cols = (unsigned *)dev_upload(B->cols, (size_t)B->nnz * sizeof(unsigned));
-  s->bd_vals = (double *)dev_upload(B->vals, (size_t)B->nnz * sizeof(double));
-  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-  lsb_binned_free(B);
 }
 
 /* fp32 copy of a value array on the device; *exact &= "no value changed" */
@@ -117,8 +61,121 @@ static float *upload_f32(const double *v, size_t cnt, int *exact) {
   return d;
 }
 
+/* Which units of the shard's rows G (local offsets, global columns) touch columns owned by other shards?
+ * Unit k is rows [ub[k], ub[k+1]) (row blocks) or, with ub = NULL, rows [k h, (k+1) h) (slices).  Under
+ * row-range partitioning of a banded operator they are a prefix and a suffix. */
+static struct halo_split halo_split(const struct shard *s, const struct csr *G, const unsigned *ub, unsigned h,
+                                    unsigned count) {
+  const unsigned *offs = G->offs, *cols = G->cols, row_end = s->row_begin + s->n;
+  unsigned char *ext = (unsigned char *)calloc(count ? count : 1, 1);
+  for (unsigned k = 0; k < count; k++)
+    for (unsigned r = ub ? ub[k] : k * h; r < (ub ? ub[k + 1] : (k + 1) * h) && r < s->n && !ext[k]; r++)
+      if (offs[r + 1] > offs[r] && (cols[offs[r]] < s->row_begin || cols[offs[r + 1] - 1] >= row_end))
+        ext[k] = 1;
+  struct halo_split sp = {0, count, 1};
+  while (sp.first < count && ext[sp.first])
+    sp.first++;
+  while (sp.last > sp.first && ext[sp.last - 1])
+    sp.last--;
+  for (unsigned k = sp.first; k < sp.last; k++)
+    sp.ok &= !ext[k];
+  sp.ok = sp.ok && sp.last > sp.first;
+  free(ext);
+  return sp;
+}
+
+/* The CSR arrays (and their fp32 copy under mixed precision) + the adaptive kernel's row blocks. */
+static void csr_build(struct shard *s, const struct csr *G) {
+  struct shard_csr *c = &s->csr;
+  c->offs = (int *)dev_upload(G->offs, ((size_t)s->n + 1) * sizeof(int));
+  c->cols = (int *)dev_upload(G->cols, (size_t)s->nnz * sizeof(int));
+  c->vals = (double *)dev_upload(G->vals, (size_t)s->nnz * sizeof(double));
+  if (s->mixed)
+    c->vals32 = upload_f32(G->vals, (size_t)s->nnz, &s->exact32);
+  unsigned *rb = NULL;
+  c->nblk = lsb_csr_row_blocks(G, LSB_BLOCK_NNZ, &rb);
+  c->rowblk = (int *)dev_upload(rb, ((size_t)c->nblk + 1) * sizeof(int));
+  unsigned char *lanes = (unsigned char *)malloc((size_t)c->nblk + 1);
+  lsb_csr_block_lanes(G, rb, c->nblk, lanes);
+  c->blklanes = (unsigned char *)dev_upload(lanes, (size_t)c->nblk);
+  c->split = halo_split(s, G, rb, 0, c->nblk);
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  free(rb), free(lanes);
+}
+static void csr_free(struct shard_csr *c) {
+  lsb_hip_free(c->offs), lsb_hip_free(c->cols), lsb_hip_free(c->vals), lsb_hip_free(c->vals32);
+  lsb_hip_free(c->rowblk), lsb_hip_free(c->blklanes);
+  memset(c, 0, sizeof *c);
+}
+
+/* Column-panel form of the shard (lsb_csr_panelize) + its row blocks, one run
+ * of blocks per panel so that a launch never crosses a panel. */
+static void panel_build(struct shard_panel *pl, const struct csr *view, unsigned width) {
+  struct lsb_panel_csr *P = lsb_csr_panelize(view, width);
+  const unsigned np = P->npanels;
+  pl->blk = lsb_calloc(unsigned, (size_t)np + 1);
+  size_t cap = (size_t)P->offs[P->npairs] / LSB_BLOCK_NNZ * 2 + 4 * (size_t)np + 16, nb = 0;
+  unsigned *rball = (unsigned *)malloc((cap + 1) * sizeof(unsigned));
+  unsigned char *lanes = (unsigned char *)malloc(cap + 1);
+  for (unsigned p = 0; p < np; p++) {
+    const unsigned b0 = P->pair_begin[p], cnt = P->pair_begin[p + 1] - b0;
+    pl->blk[p] = (unsigned)nb;
+    if (cnt == 0)
+      continue;
+    struct csr sub = {cnt, 0, P->offs + b0, NULL, NULL};
+    unsigned *rb = NULL;
+    const unsigned k = lsb_csr_row_blocks(&sub, LSB_BLOCK_NNZ, &rb);
+    if (nb + k + 1 > cap)
+      errx(EXIT_FAILURE, "hip_cdna4: panel row-block estimate too small");
+    lsb_csr_block_lanes(&sub, rb, k, lanes + nb);
+    for (unsigned i = 0; i <= k; i++)
+      rball[nb + i] = rb[i] + b0; /* the last entry is the next panel's first */
+    nb += k;
+    free(rb);
+  }
+  pl->blk[np] = (unsigned)nb;
+  rball[nb] = P->npairs;
+  pl->n = np;
+  pl->offs = (int *)dev_upload(P->offs, ((size_t)P->npairs + 1) * sizeof(int));
+  pl->cols = (int *)dev_upload(P->cols, (size_t)P->offs[P->npairs] * sizeof(int));
+  pl->vals = (double *)dev_upload(P->vals, (size_t)P->offs[P->npairs] * sizeof(double));
+  pl->rowmap = (int *)dev_upload(P->pair_row, (size_t)P->npairs * sizeof(int));
+  pl->rowblk = (int *)dev_upload(rball, (nb + 1) * sizeof(int));
+  pl->blklanes = (unsigned char *)dev_upload(lanes, nb ? nb : 1);
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  free(rball), free(lanes);
+  lsb_panel_csr_free(P);
+}
+static void panel_free(struct shard_panel *pl) {
+  free(pl->blk);
+  lsb_hip_free(pl->offs), lsb_hip_free(pl->cols), lsb_hip_free(pl->vals);
+  lsb_hip_free(pl->rowmap), lsb_hip_free(pl->rowblk), lsb_hip_free(pl->blklanes);
+  memset(pl, 0, sizeof *pl);
+}
+
+/* Binned form of the shard (lsb_csr_binize), uploaded as it is. */
+static void bins_build(struct shard_bins *b, const struct csr *view, unsigned width) {
+  struct lsb_binned *B = lsb_csr_binize(view, width);
+  if (!B)
+    return;
+  b->n = B->nbins, b->cap = B->chunk_cap;
+  b->chunk_h = (unsigned *)malloc(((size_t)B->nbins + 1) * sizeof(unsigned));
+  memcpy(b->chunk_h, B->bin_chunk, ((size_t)B->nbins + 1) * sizeof(unsigned));
+  b->chunk = (unsigned *)dev_upload(B->chunk_begin, ((size_t)B->nchunks + 1) * sizeof(unsigned));
+  b->rows = (unsigned *)dev_upload(B->rows, (size_t)B->nnz * sizeof(unsigned));
+  b->cols = (unsigned *)dev_upload(B->cols, (size_t)B->nnz * sizeof(unsigned));
+  b->vals = (double *)dev_upload(B->vals, (size_t)B->nnz * sizeof(double));
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  lsb_binned_free(B);
+}
+static void bins_free(struct shard_bins *b) {
+  free(b->chunk_h);
+  lsb_hip_free(b->chunk), lsb_hip_free(b->rows), lsb_hip_free(b->cols), lsb_hip_free(b->vals);
+  memset(b, 0, sizeof *b);
+}
+
 /* Two-phase form of the shard (lsb_csr_pbize), uploaded as it is. */
-static void shard_build_twophase(struct shard *s, const struct csr *view, unsigned n_glob) {
+static void tp_build(struct shard_tp *t, const struct csr *view, unsigned n_glob) {
   struct lsb_pb *P = lsb_csr_pbize(view);
   if (!P)
     return;
@@ -127,23 +184,249 @@ static void shard_build_twophase(struct shard *s, const struct csr *view, unsign
     if (lsb_pb_check(P, P->nnz + 2, P->nnz + 2, 0, why, sizeof why))
       errx(EXIT_FAILURE, "hip_cdna4: two-phase layout breaks a bound its kernels rely on: %s", why);
   }
-  s->tp_items = P->nitems, s->tp_bins = P->nbins, s->tp_col_lo = P->ncols_lo, s->tp_xlen = n_glob;
-  s->tp_cols = P->cols, s->tp_rows = P->rows;
-  s->tp_item = (unsigned *)dev_upload(P->item, (size_t)P->nitems * 3 * sizeof(unsigned));
-  s->tp_binptr = (unsigned *)dev_upload(P->bin_ptr, ((size_t)P->nbins + 1) * sizeof(unsigned));
-  s->tp_first = (unsigned *)dev_upload(P->grp_first, (size_t)(P->nent / 64 + 1) * sizeof(unsigned));
-  s->tp_mask = (unsigned long long *)dev_upload(P->grp_mask, (size_t)(P->nent / 64 + 1) * sizeof(unsigned long long));
-  s->tp_delta = (unsigned *)dev_upload(P->delta, ((size_t)P->npieces + 1) * sizeof(unsigned));
-  s->tp_colw = (unsigned short *)dev_upload(P->colw, (size_t)P->nent * sizeof(unsigned short));
+  t->items = P->nitems, t->bins = P->nbins, t->col_lo = P->ncols_lo, t->xlen = n_glob;
+  t->cols = P->cols, t->rows = P->rows;
+  t->item = (unsigned *)dev_upload(P->item, (size_t)P->nitems * 3 * sizeof(unsigned));
+  t->binptr = (unsigned *)dev_upload(P->bin_ptr, ((size_t)P->nbins + 1) * sizeof(unsigned));
+  t->first = (unsigned *)dev_upload(P->grp_first, (size_t)(P->nent / 64 + 1) * sizeof(unsigned));
+  t->mask = (unsigned long long *)dev_upload(P->grp_mask, (size_t)(P->nent / 64 + 1) * sizeof(unsigned long long));
+  t->delta = (unsigned *)dev_upload(P->delta, ((size_t)P->npieces + 1) * sizeof(unsigned));
+  t->colw = (unsigned short *)dev_upload(P->colw, (size_t)P->nent * sizeof(unsigned short));
   /* (+2: phase 2 loads slots in pairs, on clamped indices) */
-  s->tp_roww = (unsigned short *)lsb_hip_malloc(((size_t)P->nnz + 2) * sizeof(unsigned short));
-  LSB_CHK_HIP(hipMemcpy(s->tp_roww, P->roww, (size_t)P->nnz * sizeof(unsigned short), hipMemcpyHostToDevice));
-  s->tp_vals = (double *)dev_upload(P->vals, (size_t)P->nent * sizeof(double));
-  s->tp_prod = (double *)lsb_hip_malloc(((size_t)P->nnz + 2) * sizeof(double));
-  LSB_CHK_HIP(hipMemsetAsync(s->tp_prod, 0, ((size_t)P->nnz + 2) * sizeof(double), g_stream));
-  s->tp_binparts = (double *)lsb_hip_malloc((size_t)lsb_k_twophase_groups(P->nbins) * sizeof(double));
+  t->roww = (unsigned short *)lsb_hip_malloc(((size_t)P->nnz + 2) * sizeof(unsigned short));
+  LSB_CHK_HIP(hipMemcpy(t->roww, P->roww, (size_t)P->nnz * sizeof(unsigned short), hipMemcpyHostToDevice));
+  t->vals = (double *)dev_upload(P->vals, (size_t)P->nent * sizeof(double));
+  t->prod = (double *)lsb_hip_malloc(((size_t)P->nnz + 2) * sizeof(double));
+  LSB_CHK_HIP(hipMemsetAsync(t->prod, 0, ((size_t)P->nnz + 2) * sizeof(double), g_stream));
+  t->binparts = (double *)lsb_hip_malloc((size_t)lsb_k_twophase_groups(P->nbins) * sizeof(double));
   LSB_CHK_HIP(hipStreamSynchronize(g_stream));
   lsb_pb_free(P);
+}
+static void tp_free(struct shard_tp *t) {
+  lsb_hip_free(t->item), lsb_hip_free(t->binptr), lsb_hip_free(t->first), lsb_hip_free(t->mask);
+  lsb_hip_free(t->delta), lsb_hip_free(t->colw), lsb_hip_free(t->roww), lsb_hip_free(t->vals);
+  lsb_hip_free(t->prod), lsb_hip_free(t->binparts);
+  memset(t, 0, sizeof *t);
+}
+
+/* Near-uniform row lengths (stencils, meshes): the sliced-ELL copy with 32-bit columns, its slice geometry
+ * and the periods a 3-D stencil offers; tune_spmv() keeps whichever kernel is faster on this shard. */
+static void sell_build(struct shard *s, const struct csr *G, const struct lsb_hip_opts *o) {
+  const int forced = o->spmv_variant == LSB_SPMV_SELL;
+  const unsigned long long stored = (forced || s->nnz >= 4000000ull) ? lsb_csr_sell_stored(G) : 0;
+  struct lsb_sell *E = NULL;
+  if (stored && (forced || (o->spmv_variant == LSB_SPMV_AUTO && stored <= s->nnz + s->nnz / 8)))
+    E = lsb_csr_sellize(G);
+  if (!E)
+    return;
+  /* 3-D stencil?  the largest |col - row| a multiple of the slice height and the slices whole planes:
+   * candidate period of the XCD dealing */
+  unsigned bw = 0;
+  for (unsigned i = 0; i < s->n; i++)
+    if (G->offs[i + 1] > G->offs[i]) {
+      const long long g = (long long)s->row_begin + i;
+      const long long a = g - G->cols[G->offs[i]], b = (long long)G->cols[G->offs[i + 1] - 1] - g;
+      if (a > (long long)bw)
+        bw = (unsigned)a;
+      if (b > (long long)bw)
+        bw = (unsigned)b;
+    }
+  if (bw % LSB_SELL_ROWS == 0 && E->nslice >= 2 * (bw / LSB_SELL_ROWS)) {
+    if (bw >= 64 * LSB_SELL_ROWS)
+      s->sell.period = bw / LSB_SELL_ROWS;
+    /* ... and of the z-column walk, which only needs a slice for every XCD in a plane (a line-padded
+     * 2-D grid: its "planes" are grid lines of a few dozen slices) */
+    if (bw >= NXCD_HOST * LSB_SELL_ROWS)
+      s->col.period = bw / LSB_SELL_ROWS;
+  }
+  struct shard_sell *e = &s->sell;
+  e->nslice = E->nslice;
+  e->bytes = (unsigned long long)E->stored * (s->mixed ? 8 : 12) + ((unsigned long long)E->nslice + 1) * 4;
+  e->sptr = (unsigned *)dev_upload(E->sptr, ((size_t)E->nslice + 1) * sizeof(unsigned));
+  e->cols = (int *)dev_upload(E->cols, ((size_t)E->stored + LSB_SELL_ROWS) * sizeof(int));
+  e->vals = s->mixed ? (double *)upload_f32(E->vals, (size_t)E->stored + LSB_SELL_ROWS, NULL)
+                     : (double *)dev_upload(E->vals, ((size_t)E->stored + LSB_SELL_ROWS) * sizeof(double));
+  e->split = halo_split(s, G, NULL, LSB_SELL_ROWS, E->nslice);
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  lsb_sell_free(E);
+}
+/* the 32-bit copy's arrays; the slice geometry stays (the 16-bit copy runs on it) */
+static void sell32_free(struct shard_sell *e) {
+  lsb_hip_free(e->sptr), lsb_hip_free(e->cols), lsb_hip_free(e->vals);
+  e->sptr = NULL, e->cols = NULL, e->vals = NULL, e->bytes = 0;
+}
+
+/* 10 instead of 12 bytes per entry where every slot of every slice is one diagonal band (stencils, banded
+ * meshes): the 16-bit copy.  Slots whose 128 values are one number keep it once (lsb_sell16_value_slots):
+ * on a constant-coefficient stencil that is every slot away from the grid's faces; taken where it drops at
+ * least an eighth of the value slots.  Returns the host copy and in *vc its constant slots (the templates
+ * are built on them; *vc stays NULL without), NULL where the copy is not built. */
+static struct lsb_sell *c16_build(struct shard *s, const struct csr *G, struct lsb_sell_vc **vc) {
+  struct lsb_sell16_dev *c = &s->c16;
+  struct lsb_sell *H = getenv("LSBENCH_HIP_NO_C16") ? NULL : lsb_csr_sellize16(G, s->row_begin);
+  if (H && H->stored > s->nnz + s->nnz / 8)
+    lsb_sell_free(H), H = NULL;
+  if (!H)
+    return NULL;
+  c->sptr = (unsigned *)dev_upload(H->sptr, ((size_t)H->nslice + 1) * sizeof(unsigned));
+  c->codes = (short *)dev_upload(H->codes, ((size_t)H->ncode_slots + 1) * LSB_SELL_ROWS * sizeof(short));
+  /* every slice the same number of slots?  then the kernel needs no look at sptr */
+  c->ulen = H->nslice ? (H->sptr[1] - H->sptr[0]) / LSB_SELL_ROWS : 0;
+  for (unsigned k = 0; k < H->nslice && c->ulen; k++)
+    if ((H->sptr[k + 1] - H->sptr[k]) / LSB_SELL_ROWS != c->ulen)
+      c->ulen = 0;
+  struct lsb_sell_vc *V = getenv("LSBENCH_HIP_NO_VCONST") ? NULL : lsb_sell16_value_slots(H);
+  if (V && (unsigned long long)V->nval_slots * 8 > V->nslots * 7)
+    lsb_sell_vc_free(V), V = NULL;
+  if (V) {
+    const size_t nv = ((size_t)V->nval_slots + 1) * LSB_SELL_ROWS;
+    c->sbase = (int *)dev_upload(V->slots, 4 * ((size_t)V->nslots + 1) * sizeof(int));
+    c->vconst = (double *)dev_upload(V->vconst, ((size_t)V->nslots + 1) * sizeof(double));
+    c->vals = s->mixed ? (double *)upload_f32(V->vals, nv, NULL) : (double *)dev_upload(V->vals, nv * sizeof(double));
+    c->vslots = V->nval_slots, c->slots = (unsigned)V->nslots;
+    c->bytes = (unsigned long long)V->nslots * 24; /* slot record + the slot's constant */
+  } else {
+    c->sbase = (int *)dev_upload(H->sbase, 2 * ((size_t)H->stored / LSB_SELL_ROWS + 1) * sizeof(int));
+    c->vals = s->mixed ? (double *)upload_f32(H->vals, (size_t)H->stored + LSB_SELL_ROWS, NULL)
+                       : (double *)dev_upload(H->vals, ((size_t)H->stored + LSB_SELL_ROWS) * sizeof(double));
+    c->vslots = c->slots = (unsigned)(H->stored / LSB_SELL_ROWS);
+    c->bytes = (unsigned long long)c->slots * 8;
+  }
+  /* what one launch streams besides x and y: slot records (and constants), the code arrays, the kept
+   * values, the slice offsets where it looks */
+  c->bytes += (unsigned long long)H->ncode_slots * LSB_SELL_ROWS * sizeof(short) +
+              (unsigned long long)c->vslots * LSB_SELL_ROWS * (s->mixed ? 4 : 8) +
+              (c->ulen ? 0ull : ((unsigned long long)H->nslice + 1) * 4);
+  *vc = V;
+  return H;
+}
+static void tmpl_free(struct lsb_tmpl_dev *t) {
+  lsb_hip_free(t->srec), lsb_hip_free(t->td), lsb_hip_free(t->mask);
+  memset(t, 0, sizeof *t);
+}
+static void c16_free(struct lsb_sell16_dev *c) {
+  lsb_hip_free(c->sptr), lsb_hip_free(c->codes), lsb_hip_free(c->sbase), lsb_hip_free(c->vals);
+  lsb_hip_free(c->vconst), tmpl_free(&c->tmpl);
+  memset(c, 0, sizeof *c);
+}
+
+/* Slices of the constant-slot layout with identical constant records share a template (a structured grid
+ * has a handful): a 16-byte record per slice instead of 24 per slot, and the three inner diagonals from one
+ * gather (k_spmv_tmpl).  Returns the host templates (NULL: none) for the z-column plan. */
+static struct lsb_sell_tmpls *tmpl_build(struct shard *s, struct lsb_sell *H, struct lsb_sell_vc *V) {
+  struct lsb_tmpl_dev *t = &s->c16.tmpl;
+  struct lsb_sell_tmpls *TT = getenv("LSBENCH_HIP_NO_TMPL") ? NULL : lsb_sell16_templates(H, V);
+  { /* the bounds the constant-slot and template kernels rely on (unguarded 16-byte gathers,
+     * value-slot / mask / template indices), against this shard's rows and gather vector */
+    char why[256];
+    if (lsb_tmpl_check(H, V, TT, s->row_begin, s->n, s->n_glob, 0, why, sizeof why))
+      errx(EXIT_FAILURE, "hip_cdna4: sliced-ELL layout breaks a bound its kernels rely on: %s", why);
+  }
+  if (!TT)
+    return NULL;
+  if (s->mixed) /* fp32 matrix values: the constants as the fp32 kernels see them */
+    for (unsigned k = 0; k < TT->ntmpl; k++)
+      for (int j = 0; j < TT->t[k].nslots; j++)
+        TT->t[k].cst[j] = (double)(float)TT->t[k].cst[j];
+  /* per slice ONE 16-byte record {template id, first kept value slot, first mask, 0}: a single scalar load in
+   * the kernel */
+  unsigned *rec = lsb_calloc(unsigned, 4 * ((size_t)TT->nslice + 1));
+  for (unsigned k = 0; k < TT->nslice; k++)
+    rec[4 * (size_t)k] = TT->tid[k], rec[4 * (size_t)k + 1] = TT->vbase[2 * (size_t)k],
+                   rec[4 * (size_t)k + 2] = TT->vbase[2 * (size_t)k + 1];
+  t->srec = (unsigned *)dev_upload(rec, 4 * ((size_t)TT->nslice + 1) * sizeof(unsigned));
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  free(rec);
+  t->mask = (unsigned long long *)dev_upload(TT->mask, 2 * ((size_t)TT->nmask + 1) * sizeof(unsigned long long));
+  t->td = (struct lsb_sell_tmpl *)dev_upload(TT->t, (size_t)TT->ntmpl * sizeof(struct lsb_sell_tmpl));
+  t->nfar = TT->nfar;
+  /* what a launch streams with templates: 16 bytes per slice, the templates, and for the
+   * slices without one their slot records, constants and two offsets */
+  t->bytes = 16ull * TT->nslice + (unsigned long long)TT->ntmpl * sizeof(struct lsb_sell_tmpl) + 16ull * TT->nmask +
+             TT->kept_read * LSB_SELL_ROWS * (s->mixed ? 4ull : 8ull); /* the values it still reads */
+  for (unsigned k = 0; k < H->nslice; k++)
+    if (TT->tid[k] == 255)
+      t->bytes += (unsigned long long)(H->sptr[k + 1] - H->sptr[k]) / LSB_SELL_ROWS * 24 + 8;
+  return TT;
+}
+
+/* 3-D stencil with planes of whole slices: the z-column plan of the template layout (k_spmv_tmpl_col) */
+static void col_build(struct shard *s, const struct lsb_sell *H, const struct lsb_sell_vc *V,
+                      const struct lsb_sell_tmpls *TT) {
+  struct shard_col *c = &s->col;
+  if (!c->period || getenv("LSBENCH_HIP_NO_COL"))
+    return;
+  const char *ek = getenv("LSBENCH_HIP_COL_K");
+  /* columns of up to 16 slices: every plane of x is then read 18 / 16 times (64 M-row 7-point
+   * operator: 222 us against 233 us with columns of 8, profiles/r04_col.txt) */
+  /* ... where that still leaves every wave several columns to walk: with a dozen thousand
+   * waves resident a 10 M-row operator (78 k slices) has 1.2 columns of 16 per wave -- columns of 6 */
+  /* (measured through the two-launch iteration, profiles/r04_px.txt: a 10 M-row 5-point grid of
+   * whole-slice lines 120.9 / 128.3 / 130.0 us per iteration with columns of 4 / 6 / 12 -- one far
+   * slot per side, nothing but streams: the shorter the column the more of them per wave; a
+   * 50-plane slab of the 7-point grid 130.1 / 122.6 / 116.6 us -- two far slots: every plane
+   * re-read costs two vectors and their +-line operands) */
+  /* (final form of the iteration, config 3 padded: 111.0 / 110.0 / 108.6 / 115.8 / 116.7 us with columns
+   * of 3 / 4 / 5 / 6 / 8) */
+  unsigned kauto = TT->nfar >= 2 ? TT->nslice / 5120u : TT->nslice / 15000u;
+  kauto = kauto < 4u ? 4u : kauto > 16u ? 16u : kauto;
+  const unsigned kmax = ek ? (unsigned)atoi(ek) : kauto;
+  /* [0]: every slice of the shard; [1]: the slices that need no halo, where the shard has
+   * such a range (the interior launch of the split SpMV; the boundary launches go
+   * through k_spmv_tmpl) */
+  for (int w = 0; w < 2; w++) {
+    if (w == 1 && !(c->plan && s->sell.split.ok && (s->sell.split.first > 0 || s->sell.split.last < TT->nslice)))
+      break;
+    struct lsb_tmpl_cols *CC = w == 0 ? lsb_sell_tmpl_columns(TT, c->period, kmax)
+                                      : lsb_sell_tmpl_columns_range(TT, c->period, kmax, s->sell.split.first,
+                                                                    s->sell.split.last);
+    if (!CC)
+      break;
+    char why[256];
+    if (lsb_tmpl_cols_check(TT, CC, why, sizeof why))
+      errx(EXIT_FAILURE, "hip_cdna4: z-column plan breaks a rule its kernel relies on: %s", why);
+    /* xbeg, the items, the walk directions behind them (include/lsbench_hip.h) */
+    const size_t nw = 16 + 4 * ((size_t)CC->nitem + 1), nd = CC->down ? ((size_t)CC->nitem + 31) / 32 : 0;
+    unsigned *plan = lsb_calloc(unsigned, nw + nd);
+    memcpy(plan, CC->xbeg, sizeof CC->xbeg);
+    memcpy(plan + 16, CC->item, 4 * (size_t)CC->nitem * sizeof(unsigned));
+    if (nd) {
+      plan[LSB_TMPL_COL_DOWN] = (unsigned)nw;
+      memcpy(plan + nw, CC->down, nd * sizeof(unsigned));
+    }
+    unsigned *d = (unsigned *)dev_upload(plan, (nw + nd) * sizeof(unsigned));
+    LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+    free(plan);
+    if (w == 0) {
+      c->plan = d, c->items = CC->nitem, c->centre0 = CC->centre0, c->slices = CC->in_cols;
+      /* what a launch of the z-column walk streams besides x and y: a 16-byte item per
+       * column or single slice, the templates, a column's masks once, and for the single
+       * slices their slot records, constants and kept values */
+      c->bytes = 16ull * CC->nitem + (unsigned long long)TT->ntmpl * sizeof(struct lsb_sell_tmpl);
+      for (unsigned q = 0; q < CC->nitem; q++) {
+        const unsigned sl = CC->item[4 * (size_t)q], run = CC->item[4 * (size_t)q + 1] & ~LSB_TMPL_COL_LOCKSTEP;
+        if (run >= 2) {
+          const struct lsb_sell_tmpl *t = &TT->t[TT->tid[sl]];
+          for (int j = 0; j < t->nslots; j++)
+            c->bytes += t->kind[j] == 2 ? 16ull : 0ull;
+        } else {
+          const unsigned q0 = H->sptr[sl] / LSB_SELL_ROWS, len = (H->sptr[sl + 1] - H->sptr[sl]) / LSB_SELL_ROWS;
+          c->bytes += 24ull * len + 8;
+          for (unsigned j = 0; j < len; j++)
+            if (V->slots[4 * ((size_t)q0 + j) + 2] >= 0)
+              c->bytes += LSB_SELL_ROWS * (s->mixed ? 4ull : 8ull);
+        }
+      }
+    } else {
+      c->plan_in = d, c->items_in = CC->nitem;
+      c->centre0 &= CC->centre0;
+    }
+    lsb_tmpl_cols_free(CC);
+  }
+}
+static void col_free(struct shard_col *c) {
+  lsb_hip_free(c->plan), lsb_hip_free(c->plan_in);
+  memset(c, 0, sizeof *c);
 }
 
 /* count doubles out of the shard's vector slab (256-byte aligned), or a hipMalloc of their own */
@@ -190,286 +473,42 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
   s->col_lo = lo, s->col_hi = hi;
   if ((unsigned long long)s->nnz > 0x7FFFFFFFull || n_glob > 0x7FFFFFFFu)
     errx(EXIT_FAILURE, "shard too large for int32 device indices");
-  s->d_offs = (int *)dev_upload(offs, ((size_t)n + 1) * sizeof(int));
-  s->d_cols = (int *)dev_upload(cols, (size_t)s->nnz * sizeof(int));
-  s->d_vals = (double *)dev_upload(S->vals + j0, (size_t)s->nnz * sizeof(double));
   s->mixed = o->precision == LSB_PREC_MIXED, s->exact32 = 1;
-  if (s->mixed)
-    s->d_vals32 = upload_f32(S->vals + j0, (size_t)s->nnz, &s->exact32);
-  /* row blocks of the adaptive kernel, on the local offsets */
-  struct csr view = {n, 0, (unsigned *)offs, NULL, NULL};
-  unsigned *rb = NULL;
-  s->nblk = lsb_csr_row_blocks(&view, LSB_BLOCK_NNZ, &rb);
-  s->d_rowblk = (int *)dev_upload(rb, ((size_t)s->nblk + 1) * sizeof(int));
-  unsigned char *lanes = (unsigned char *)malloc((size_t)s->nblk + 1);
-  lsb_csr_block_lanes(&view, rb, s->nblk, lanes);
-  s->d_blklanes = (unsigned char *)dev_upload(lanes, (size_t)s->nblk);
-  /* Which row blocks touch columns owned by other shards?  Under row-range
-   * partitioning of a banded operator they are a prefix and a suffix; the
-   * blocks in between can start before the halo has arrived. */
-  {
-    const int row_end = (int)(row_begin + n);
-    unsigned b1 = 0, b2 = s->nblk;
-    int ok = 1;
-    unsigned char *ext = (unsigned char *)calloc(s->nblk ? s->nblk : 1, 1);
-    for (unsigned k = 0; k < s->nblk; k++)
-      for (unsigned r = rb[k]; r < rb[k + 1] && !ext[k]; r++)
-        if (offs[r + 1] > offs[r] &&
-            (cols[offs[r]] < (int)row_begin || cols[offs[r + 1] - 1] >= row_end))
-          ext[k] = 1;
-    while (b1 < s->nblk && ext[b1])
-      b1++;
-    while (b2 > b1 && ext[b2 - 1])
-      b2--;
-    for (unsigned k = b1; k < b2; k++)
-      ok &= !ext[k];
-    free(ext);
-    s->ov_ok = ok && b2 > b1, s->ov_b1 = b1, s->ov_b2 = b2;
-  }
-  /* Scattered rows (mean |col-row| in the millions, x far beyond L2): also
-   * build the column-panel form; tune_spmv() keeps whichever is faster. */
-  {
-    struct csr gview = {n, 0, (unsigned *)offs, (unsigned *)cols, (double *)(S->vals + j0)};
-    const char *e = getenv("LSBENCH_HIP_PANEL_COLS");
-    /* window of x one bin / panel gathers from: 4 MiB = an XCD's whole L2.  Measured
-     * on the 8 M-row power-law operator (binned form): 1 MiB 3.71 ms, 2 MiB 3.05,
-     * 3 MiB 2.85, 4 MiB 2.80, 8 MiB 3.21 -- fewer passes over y win until the
-     * window no longer fits */
-    const unsigned width = e ? (unsigned)strtoul(e, NULL, 10) : 524288u;
-    const int forced = o->spmv_variant == LSB_SPMV_PANEL;
-    const int scattered = s->nnz > 4000000ull && (double)(hi - lo) * 8.0 > 16.0e6 &&
-                          lsb_csr_mean_scatter(&gview, row_begin) > 1.0e6;
-    if (width && forced) /* (no longer built on its own accord: superseded by the binned form) */
-      shard_build_panels(s, &gview, width);
-    if (width && (o->spmv_variant == LSB_SPMV_BINNED ||
-                  (o->spmv_variant == LSB_SPMV_AUTO && scattered)))
-      shard_build_bins(s, &gview, width);
-    /* the two-phase form: 1.59 ms against the binned form's 2.79 ms on the 8 M-row
-     * power-law operator; the timing pass decides per shard */
-    if (o->spmv_variant == LSB_SPMV_TWOPHASE ||
-        (o->spmv_variant == LSB_SPMV_AUTO && scattered))
-      shard_build_twophase(s, &gview, n_glob);
-  }
-  /* Near-uniform row lengths (stencils, meshes): also keep a sliced-ELL copy;
-   * tune_spmv() keeps whichever kernel is faster on this shard. */
-  {
-    struct csr gview = {n, 0, (unsigned *)offs, (unsigned *)cols, (double *)(S->vals + j0)};
-    const int forced = o->spmv_variant == LSB_SPMV_SELL;
-    const unsigned long long stored = (forced || s->nnz >= 4000000ull) ? lsb_csr_sell_stored(&gview) : 0;
-    struct lsb_sell *E = NULL;
-    if (stored && (forced || (o->spmv_variant == LSB_SPMV_AUTO && stored <= s->nnz + s->nnz / 8)))
-      E = lsb_csr_sellize(&gview);
-    if (E) {
-      /* 3-D stencil?  the largest |col - row| a multiple of the slice height and
-       * the slices whole planes: candidate period of the XCD dealing */
-      {
-        unsigned bw = 0;
-        for (unsigned i = 0; i < n; i++)
-          if (offs[i + 1] > offs[i]) {
-            const long long g = (long long)row_begin + i;
-            const long long a = g - cols[offs[i]], b = (long long)cols[offs[i + 1] - 1] - g;
-            if (a > (long long)bw)
-              bw = (unsigned)a;
-            if (b > (long long)bw)
-              bw = (unsigned)b;
-          }
-        if (bw >= 64 * LSB_SELL_ROWS && bw % LSB_SELL_ROWS == 0 && E->nslice >= 2 * (bw / LSB_SELL_ROWS))
-          s->sell_period = bw / LSB_SELL_ROWS;
-        /* ... and of the z-column walk, which only needs a slice for every XCD in a plane (a line-padded
-         * 2-D grid: its "planes" are grid lines of a few dozen slices) */
-        if (bw >= NXCD_HOST * LSB_SELL_ROWS && bw % LSB_SELL_ROWS == 0 && E->nslice >= 2 * (bw / LSB_SELL_ROWS))
-          s->col_period = bw / LSB_SELL_ROWS;
-      }
-      s->nslice = E->nslice;
-      s->sell32_bytes = (unsigned long long)E->stored * (s->mixed ? 8 : 12) + ((unsigned long long)E->nslice + 1) * 4;
-      s->d_sptr = (unsigned *)dev_upload(E->sptr, ((size_t)E->nslice + 1) * sizeof(unsigned));
-      s->d_scols = (int *)dev_upload(E->cols, ((size_t)E->stored + LSB_SELL_ROWS) * sizeof(int));
-      s->d_svals = s->mixed ? (double *)upload_f32(E->vals, (size_t)E->stored + LSB_SELL_ROWS, NULL)
-                            : (double *)dev_upload(E->vals, ((size_t)E->stored + LSB_SELL_ROWS) * sizeof(double));
-      const int row_end = (int)(row_begin + n);
-      unsigned s1 = 0, s2 = E->nslice;
-      int ok = 1;
-      unsigned char *ext = (unsigned char *)calloc(E->nslice ? E->nslice : 1, 1);
-      for (unsigned k = 0; k < E->nslice; k++)
-        for (unsigned r = k * LSB_SELL_ROWS; r < n && r < (k + 1) * LSB_SELL_ROWS && !ext[k]; r++)
-          if (offs[r + 1] > offs[r] &&
-              (cols[offs[r]] < (int)row_begin || cols[offs[r + 1] - 1] >= row_end))
-            ext[k] = 1;
-      while (s1 < E->nslice && ext[s1])
-        s1++;
-      while (s2 > s1 && ext[s2 - 1])
-        s2--;
-      for (unsigned k = s1; k < s2; k++)
-        ok &= !ext[k];
-      free(ext);
-      s->ov_sok = ok && s2 > s1, s->ov_s1 = s1, s->ov_s2 = s2;
-      LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-      lsb_sell_free(E);
-      /* 10 instead of 12 bytes per entry where every slot of every slice is
-       * one diagonal band (stencils, banded meshes) */
-      struct lsb_sell *H = getenv("LSBENCH_HIP_NO_C16") ? NULL : lsb_csr_sellize16(&gview, row_begin);
-      if (H && H->stored > s->nnz + s->nnz / 8) {
-        lsb_sell_free(H);
-        H = NULL;
-      }
-      if (H) {
-        s->d_sptr16 = (unsigned *)dev_upload(H->sptr, ((size_t)H->nslice + 1) * sizeof(unsigned));
-        s->d_scodes = (short *)dev_upload(H->codes, ((size_t)H->ncode_slots + 1) * LSB_SELL_ROWS * sizeof(short));
-        /* slots whose 128 values are one number keep it once (lsb_sell16_value_slots): on a
-         * constant-coefficient stencil that is every slot away from the grid's faces.  Taken
-         * where it drops at least an eighth of the value slots. */
-        { /* every slice the same number of slots?  then the kernel needs no look at sptr */
-          unsigned ul = H->nslice ? (H->sptr[1] - H->sptr[0]) / LSB_SELL_ROWS : 0;
-          for (unsigned k = 0; k < H->nslice && ul; k++)
-            if ((H->sptr[k + 1] - H->sptr[k]) / LSB_SELL_ROWS != ul)
-              ul = 0;
-          s->sell_ulen = ul;
-        }
-        struct lsb_sell_vc *V = getenv("LSBENCH_HIP_NO_VCONST") ? NULL : lsb_sell16_value_slots(H);
-        if (V && (unsigned long long)V->nval_slots * 8 > V->nslots * 7) {
-          lsb_sell_vc_free(V);
-          V = NULL;
-        }
-        if (V) {
-          const size_t nv = ((size_t)V->nval_slots + 1) * LSB_SELL_ROWS;
-          s->d_sbase = (int *)dev_upload(V->slots, 4 * ((size_t)V->nslots + 1) * sizeof(int));
-          s->d_svconst = (double *)dev_upload(V->vconst, ((size_t)V->nslots + 1) * sizeof(double));
-          s->d_svals16 = s->mixed ? (double *)upload_f32(V->vals, nv, NULL)
-                                  : (double *)dev_upload(V->vals, nv * sizeof(double));
-          s->sell_vslots = V->nval_slots, s->sell_slots = (unsigned)V->nslots;
-          s->sell16_bytes = (unsigned long long)V->nslots * 24; /* slot record + the slot's constant */
-          /* slices with identical constant records share a template (a structured grid has a
-           * handful): a 16-byte record per slice instead of 24 per slot, and the three inner diagonals
-           * from one gather (k_spmv_tmpl) */
-          struct lsb_sell_tmpls *TT = getenv("LSBENCH_HIP_NO_TMPL") ? NULL : lsb_sell16_templates(H, V);
-          { /* the bounds the constant-slot and template kernels rely on (unguarded 16-byte gathers,
-             * value-slot / mask / template indices), against this shard's rows and gather vector */
-            char why[256];
-            if (lsb_tmpl_check(H, V, TT, row_begin, n, n_glob, 0, why, sizeof why))
-              errx(EXIT_FAILURE, "hip_cdna4: sliced-ELL layout breaks a bound its kernels rely on: %s", why);
-          }
-          if (TT) {
-            if (s->mixed) /* fp32 matrix values: the constants as the fp32 kernels see them */
-              for (unsigned t = 0; t < TT->ntmpl; t++)
-                for (int j = 0; j < TT->t[t].nslots; j++)
-                  TT->t[t].cst[j] = (double)(float)TT->t[t].cst[j];
-            { /* per slice ONE 16-byte record {template id, first kept value slot, first mask, 0}: a
-               * single scalar load in the kernel */
-              unsigned *rec = lsb_calloc(unsigned, 4 * ((size_t)TT->nslice + 1));
-              for (unsigned k = 0; k < TT->nslice; k++)
-                rec[4 * (size_t)k] = TT->tid[k], rec[4 * (size_t)k + 1] = TT->vbase[2 * (size_t)k],
-                               rec[4 * (size_t)k + 2] = TT->vbase[2 * (size_t)k + 1];
-              s->d_srec = (unsigned *)dev_upload(rec, 4 * ((size_t)TT->nslice + 1) * sizeof(unsigned));
-              LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-              free(rec);
-            }
-            s->d_tmask = (unsigned long long *)dev_upload(TT->mask, 2 * ((size_t)TT->nmask + 1) * sizeof(unsigned long long));
-            s->d_tmpl = (struct lsb_sell_tmpl *)dev_upload(TT->t, (size_t)TT->ntmpl * sizeof(struct lsb_sell_tmpl));
-            s->tmpl_nfar = TT->nfar, s->tmpl_count = TT->ntmpl;
-            s->tmpl_pure = TT->covered, s->tmpl_shaped = TT->shaped;
-            /* what a launch streams with templates: 16 bytes per slice, the templates, and for the
-             * slices without one their slot records, constants and two offsets */
-            s->tmpl_bytes = 16ull * TT->nslice + (unsigned long long)TT->ntmpl * sizeof(struct lsb_sell_tmpl) +
-                            16ull * TT->nmask +
-                            TT->kept_read * LSB_SELL_ROWS * (s->mixed ? 4ull : 8ull); /* the values it still reads */
-            for (unsigned k = 0; k < H->nslice; k++)
-              if (TT->tid[k] == 255)
-                s->tmpl_bytes += (unsigned long long)(H->sptr[k + 1] - H->sptr[k]) / LSB_SELL_ROWS * 24 + 8;
-            /* 3-D stencil with planes of whole slices: the z-column plan (k_spmv_tmpl_col) */
-            if (s->col_period && !getenv("LSBENCH_HIP_NO_COL")) {
-              const char *ek = getenv("LSBENCH_HIP_COL_K");
-              /* columns of up to 16 slices: every plane of x is then read 18 / 16 times (64 M-row 7-point
-               * operator: 222 us against 233 us with columns of 8, profiles/r04_col.txt) */
-              /* ... where that still leaves every wave several columns to walk: with a dozen thousand
-               * waves resident a 10 M-row operator (78 k slices) has 1.2 columns of 16 per wave -- columns of 6 */
-              /* (measured through the two-launch iteration, profiles/r04_px.txt: a 10 M-row 5-point grid of
-               * whole-slice lines 120.9 / 128.3 / 130.0 us per iteration with columns of 4 / 6 / 12 -- one far
-               * slot per side, nothing but streams: the shorter the column the more of them per wave; a
-               * 50-plane slab of the 7-point grid 130.1 / 122.6 / 116.6 us -- two far slots: every plane
-               * re-read costs two vectors and their +-line operands) */
-              /* (final form of the iteration, config 3 padded: 111.0 / 110.0 / 108.6 / 115.8 / 116.7 us with columns
-               * of 3 / 4 / 5 / 6 / 8) */
-              unsigned kauto = TT->nfar >= 2 ? TT->nslice / 5120u : TT->nslice / 15000u;
-              kauto = kauto < 4u ? 4u : kauto > 16u ? 16u : kauto;
-              const unsigned kmax = ek ? (unsigned)atoi(ek) : kauto;
-              /* [0]: every slice of the shard; [1]: the slices that need no halo, where the shard has
-               * such a range (the interior launch of the split SpMV; the boundary launches go
-               * through k_spmv_tmpl) */
-              for (int w = 0; w < 2; w++) {
-                if (w == 1 && !(s->d_colplan && s->ov_sok && (s->ov_s1 > 0 || s->ov_s2 < TT->nslice)))
-                  break;
-                struct lsb_tmpl_cols *CC = w == 0 ? lsb_sell_tmpl_columns(TT, s->col_period, kmax)
-                                                  : lsb_sell_tmpl_columns_range(TT, s->col_period, kmax, s->ov_s1, s->ov_s2);
-                if (!CC)
-                  break;
-                char why[256];
-                if (lsb_tmpl_cols_check(TT, CC, why, sizeof why))
-                  errx(EXIT_FAILURE, "hip_cdna4: z-column plan breaks a rule its kernel relies on: %s", why);
-                /* xbeg, the items, the walk directions behind them (include/lsbench_hip.h) */
-                const size_t nw = 16 + 4 * ((size_t)CC->nitem + 1), nd = CC->down ? ((size_t)CC->nitem + 31) / 32 : 0;
-                unsigned *plan = lsb_calloc(unsigned, nw + nd);
-                memcpy(plan, CC->xbeg, sizeof CC->xbeg);
-                memcpy(plan + 16, CC->item, 4 * (size_t)CC->nitem * sizeof(unsigned));
-                if (nd) {
-                  plan[LSB_TMPL_COL_DOWN] = (unsigned)nw;
-                  memcpy(plan + nw, CC->down, nd * sizeof(unsigned));
-                }
-                unsigned *d = (unsigned *)dev_upload(plan, (nw + nd) * sizeof(unsigned));
-                LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-                free(plan);
-                if (w == 0) {
-                  s->d_colplan = d, s->col_items = CC->nitem, s->col_kmax = CC->kmax, s->col_centre0 = CC->centre0;
-                  s->col_slices = CC->in_cols;
-                  /* what a launch of the z-column walk streams besides x and y: a 16-byte item per
-                   * column or single slice, the templates, a column's masks once, and for the single
-                   * slices their slot records, constants and kept values */
-                  s->col_bytes = 16ull * CC->nitem + (unsigned long long)TT->ntmpl * sizeof(struct lsb_sell_tmpl);
-                  for (unsigned q = 0; q < CC->nitem; q++) {
-                    const unsigned sl = CC->item[4 * (size_t)q], run = CC->item[4 * (size_t)q + 1] & ~LSB_TMPL_COL_LOCKSTEP;
-                    if (run >= 2) {
-                      const struct lsb_sell_tmpl *t = &TT->t[TT->tid[sl]];
-                      for (int j = 0; j < t->nslots; j++)
-                        s->col_bytes += t->kind[j] == 2 ? 16ull : 0ull;
-                    } else {
-                      const unsigned q0 = H->sptr[sl] / LSB_SELL_ROWS, len = (H->sptr[sl + 1] - H->sptr[sl]) / LSB_SELL_ROWS;
-                      s->col_bytes += 24ull * len + 8;
-                      for (unsigned j = 0; j < len; j++)
-                        if (V->slots[4 * ((size_t)q0 + j) + 2] >= 0)
-                          s->col_bytes += LSB_SELL_ROWS * (s->mixed ? 4ull : 8ull);
-                    }
-                  }
-                } else {
-                  s->d_colplan_in = d, s->col_items_in = CC->nitem;
-                  s->col_centre0 &= CC->centre0;
-                }
-                lsb_tmpl_cols_free(CC);
-              }
-            }
-            LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-            lsb_sell_tmpls_free(TT);
-          }
-        } else {
-          s->d_sbase = (int *)dev_upload(H->sbase, 2 * ((size_t)H->stored / LSB_SELL_ROWS + 1) * sizeof(int));
-          s->d_svals16 = s->mixed ? (double *)upload_f32(H->vals, (size_t)H->stored + LSB_SELL_ROWS, NULL)
-                                  : (double *)dev_upload(H->vals, ((size_t)H->stored + LSB_SELL_ROWS) * sizeof(double));
-          s->sell_vslots = s->sell_slots = (unsigned)(H->stored / LSB_SELL_ROWS);
-          s->sell16_bytes = (unsigned long long)s->sell_slots * 8;
-        }
-        /* what one launch of the 16-bit form streams besides x and y: slot records (and
-         * constants), the code arrays, the kept values, the slice offsets where it looks */
-        s->sell16_bytes += (unsigned long long)H->ncode_slots * LSB_SELL_ROWS * sizeof(short) +
-                           (unsigned long long)s->sell_vslots * LSB_SELL_ROWS * (s->mixed ? 4 : 8) +
-                           (s->sell_ulen ? 0ull : ((unsigned long long)H->nslice + 1) * 4);
-
-        LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-        lsb_sell_vc_free(V);
-        lsb_sell_free(H);
-      }
-    }
+  /* the shard's rows: local offsets, global columns */
+  struct csr G = {n, 0, (unsigned *)offs, (unsigned *)cols, (double *)(S->vals + j0)};
+  csr_build(s, &G);
+  /* Scattered rows (mean |col-row| in the millions, x far beyond L2): also build the binned and
+   * two-phase forms; tune_spmv() keeps whichever is faster. */
+  const char *e = getenv("LSBENCH_HIP_PANEL_COLS");
+  /* window of x one bin / panel gathers from: 4 MiB = an XCD's whole L2.  Measured
+   * on the 8 M-row power-law operator (binned form): 1 MiB 3.71 ms, 2 MiB 3.05,
+   * 3 MiB 2.85, 4 MiB 2.80, 8 MiB 3.21 -- fewer passes over y win until the
+   * window no longer fits */
+  const unsigned width = e ? (unsigned)strtoul(e, NULL, 10) : 524288u;
+  const int scattered = s->nnz > 4000000ull && (double)(hi - lo) * 8.0 > 16.0e6 &&
+                        lsb_csr_mean_scatter(&G, row_begin) > 1.0e6;
+  if (width && o->spmv_variant == LSB_SPMV_PANEL) /* (no longer built on its own accord: superseded by the binned form) */
+    panel_build(&s->panel, &G, width);
+  if (width && (o->spmv_variant == LSB_SPMV_BINNED || (o->spmv_variant == LSB_SPMV_AUTO && scattered)))
+    bins_build(&s->bins, &G, width);
+  /* the two-phase form: 1.59 ms against the binned form's 2.79 ms on the 8 M-row
+   * power-law operator; the timing pass decides per shard */
+  if (o->spmv_variant == LSB_SPMV_TWOPHASE || (o->spmv_variant == LSB_SPMV_AUTO && scattered))
+    tp_build(&s->tp, &G, n_glob);
+  /* sliced-ELL: the 32-bit copy, on it the 16-bit one, its templates, their z-column plan */
+  sell_build(s, &G, o);
+  if (s->sell.sptr) {
+    struct lsb_sell_vc *V = NULL;
+    struct lsb_sell *H = c16_build(s, &G, &V);
+    struct lsb_sell_tmpls *TT = V ? tmpl_build(s, H, V) : NULL;
+    if (TT)
+      col_build(s, H, V, TT);
+    LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+    lsb_sell_tmpls_free(TT), lsb_sell_vc_free(V), lsb_sell_free(H);
   }
   precond_shard_blocks(s, offs, cols, S->vals + j0, o); /* block-Jacobi: dense diagonal blocks */
   LSB_CHK_HIP(hipStreamSynchronize(g_stream)); /* host staging is freed next */
-  free(rb), free(offs), free(cols), free(lanes);
+  free(offs), free(cols);
 
   { /* the vector slab: everything this configuration's iteration streams, in one allocation */
     size_t cnt = 3 * (size_t)n + n_glob;                       /* r, q, the diagonal; the gather vector */
@@ -515,9 +554,9 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
     int *d_nz = (int *)lsb_hip_malloc(sizeof(int)), nz = 0;
     LSB_CHK_HIP(hipMemsetAsync(d_nz, 0, sizeof(int), g_stream));
     if (o->precond == LSB_PRECOND_L1JACOBI)
-      lsb_k_l1_setup(n, s->d_offs, s->d_vals, s->d_dinv, d_nz, g_stream);
+      lsb_k_l1_setup(n, s->csr.offs, s->csr.vals, s->d_dinv, d_nz, g_stream);
     else
-      lsb_k_jacobi_setup(n, row_begin, s->d_offs, s->d_cols, s->d_vals, s->d_dinv, d_nz,
+      lsb_k_jacobi_setup(n, row_begin, s->csr.offs, s->csr.cols, s->csr.vals, s->d_dinv, d_nz,
                          g_stream);
     LSB_CHK_HIP(hipMemcpyAsync(&nz, d_nz, sizeof(int), hipMemcpyDeviceToHost, g_stream));
     LSB_CHK_HIP(hipStreamSynchronize(g_stream));
@@ -549,26 +588,12 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
 }
 
 void shard_free(struct shard *s) {
-  lsb_hip_free(s->d_offs), lsb_hip_free(s->d_cols), lsb_hip_free(s->d_vals), lsb_hip_free(s->d_vals32);
-  lsb_hip_free(s->d_rowblk), lsb_hip_free(s->d_blklanes);
+  csr_free(&s->csr), panel_free(&s->panel), bins_free(&s->bins), tp_free(&s->tp);
+  sell32_free(&s->sell), c16_free(&s->c16), col_free(&s->col);
   shard_vec_free(s, s->d_dinv), shard_vec_free(s, s->d_r);
   shard_vec_free(s, s->d_q), shard_vec_free(s, s->d_pfull), lsb_hip_free(s->d_parts_pq);
   shard_vec_free(s, s->d_p1), shard_vec_free(s, s->d_s1);
   lsb_hip_free(s->d_parts2), lsb_hip_free(s->d_st), lsb_hip_free(s->d_st_aux);
-  lsb_hip_free(s->pd_offs), lsb_hip_free(s->pd_cols), lsb_hip_free(s->pd_vals);
-  lsb_hip_free(s->pd_rowmap), lsb_hip_free(s->pd_rowblk), lsb_hip_free(s->pd_blklanes);
-  lsb_hip_free(s->d_sptr), lsb_hip_free(s->d_scols), lsb_hip_free(s->d_svals);
-  lsb_hip_free(s->d_sptr16), lsb_hip_free(s->d_scodes), lsb_hip_free(s->d_sbase);
-  lsb_hip_free(s->d_svals16), lsb_hip_free(s->d_svconst);
-  lsb_hip_free(s->d_srec), lsb_hip_free(s->d_tmpl), lsb_hip_free(s->d_tmask), lsb_hip_free(s->d_colplan), lsb_hip_free(s->d_colplan_in);
-  free(s->h_pblk);
-  lsb_hip_free(s->bd_chunk), lsb_hip_free(s->bd_rows), lsb_hip_free(s->bd_cols);
-  lsb_hip_free(s->bd_vals);
-  free(s->h_binchunk);
-  lsb_hip_free(s->tp_item), lsb_hip_free(s->tp_binptr), lsb_hip_free(s->tp_first);
-  lsb_hip_free(s->tp_mask), lsb_hip_free(s->tp_delta);
-  lsb_hip_free(s->tp_colw), lsb_hip_free(s->tp_roww), lsb_hip_free(s->tp_vals);
-  lsb_hip_free(s->tp_prod), lsb_hip_free(s->tp_binparts);
   precond_free_shard(s);
   lsb_hip_free(s->d_slab); /* behind everything that may point into it */
   s->d_slab = NULL;
@@ -856,21 +881,19 @@ unsigned long long lsb_hip_solver_nnz_local(const lsb_hip_solver *s) {
     z += s->sh[i].nnz;
   return z;
 }
-unsigned lsb_hip_solver_nblocks(const lsb_hip_solver *s) { return s->sh[0].nblk; }
+unsigned lsb_hip_solver_nblocks(const lsb_hip_solver *s) { return s->sh[0].csr.nblk; }
 int lsb_hip_solver_spmv_variant(const lsb_hip_solver *s) { return s->sh[0].variant; }
 unsigned lsb_hip_solver_spmv_flags(const lsb_hip_solver *s) { return s->sh[0].sp_flags; }
 unsigned lsb_hip_solver_spmv_grid(const lsb_hip_solver *s) { return s->sh[0].sp_grid; }
 unsigned lsb_hip_solver_spmv_period(const lsb_hip_solver *s) { return s->sh[0].sp_period; }
-unsigned long long lsb_hip_solver_spmv_col_slices(const lsb_hip_solver *s) {
-  return s->sh[0].d_colplan ? s->sh[0].col_slices : 0ull;
-}
+unsigned long long lsb_hip_solver_spmv_col_slices(const lsb_hip_solver *s) { return s->sh[0].col.slices; }
 void lsb_hip_solver_sell_value_slots(const lsb_hip_solver *s, unsigned *kept, unsigned *total) {
   const struct shard *h = &s->sh[0];
-  const int on = h->variant == LSB_SPMV_SELL && (h->sp_flags & LSB_SP_C16) && h->d_scodes;
+  const int on = h->sell_form >= SELL_16;
   if (kept)
-    *kept = on ? h->sell_vslots : 0;
+    *kept = on ? h->c16.vslots : 0;
   if (total)
-    *total = on ? h->sell_slots : 0;
+    *total = on ? h->c16.slots : 0;
 }
 void lsb_hip_solver_comm_plan(const lsb_hip_solver *s, unsigned long long plan[8]) {
   const struct shard *h = &s->sh[0];
@@ -902,16 +925,11 @@ int lsb_hip_solver_fused_p(const lsb_hip_solver *s) { return lsb_fuse_p_kind(s);
 int lsb_hip_solver_blas1_nt(const lsb_hip_solver *s) { return s->nt_mask; }
 unsigned long long lsb_hip_solver_spmv_layout_bytes(const lsb_hip_solver *s) {
   const struct shard *h = &s->sh[0];
-  unsigned long long m = 12ull * h->nnz + 4ull * ((unsigned long long)h->n + 1); /* the CSR arrays */
-  if (h->variant == LSB_SPMV_SELL)
-    m = (h->sp_flags & LSB_SP_C16) && h->d_scodes
-            ? ((h->sp_flags & LSB_SP_TMPL) && h->d_srec
-                   ? ((h->sp_flags & LSB_SP_COL) && h->d_colplan ? h->col_bytes : h->tmpl_bytes)
-                   : h->sell16_bytes)
-            : h->sell32_bytes;
-  else if (h->variant == LSB_SPMV_TWOPHASE || h->variant == LSB_SPMV_BINNED)
+  if (h->variant == LSB_SPMV_TWOPHASE || h->variant == LSB_SPMV_BINNED)
     return 0; /* more than one pass over intermediate data: no single-pass figure */
-  return m + 16ull * h->n; /* + x read once, y written once */
+  const unsigned long long m[] = {12ull * h->nnz + 4ull * ((unsigned long long)h->n + 1), /* the CSR arrays */
+                                  h->sell.bytes, h->c16.bytes, h->c16.tmpl.bytes, h->col.bytes}; /* by sell_form */
+  return m[h->sell_form] + 16ull * h->n; /* + x read once, y written once */
 }
 int lsb_hip_solver_overlaps(const lsb_hip_solver *s) { return can_overlap(s); }
 int lsb_hip_solver_comm(const lsb_hip_solver *s, double *p2p_us, double *rccl_us) {
@@ -927,76 +945,74 @@ void sell_launch(struct shard *s, unsigned s0, unsigned ns, const double *xfull,
                         const double *xdot, double *partials, unsigned *np,
                         const struct lsb_pcg_state *st) {
   const unsigned f32 = s->mixed ? LSB_SP_F32 : 0u; /* the value arrays hold floats then */
+  const struct shard_col *c = &s->col;
   /* whole launches of a shard with a z-column plan (a Chebyshev epilogue and the split interior /
    * boundary launches go through k_spmv_tmpl) */
-  const int col_all = s->d_colplan && s0 == 0 && ns == s->nslice;
-  const int col_in = s->d_colplan_in && s0 == s->ov_s1 && ns == s->ov_s2 - s->ov_s1;
-  if ((s->sp_flags & LSB_SP_C16) && (s->sp_flags & LSB_SP_TMPL) && (s->sp_flags & LSB_SP_COL) && (col_all || col_in) &&
-      s->d_srec && s->d_scodes && !s->epi.zout)
-    lsb_k_spmv_tmpl_col(s->sp_flags | f32, s->sp_grid, s->col_period, col_all ? s->d_colplan : s->d_colplan_in,
-                        col_all ? s->col_items : s->col_items_in, s->col_centre0, s->n,
-                        s->row_begin, s->n_glob, s->d_sptr16, s->d_tmask, s->d_tmpl, s->tmpl_nfar, s->d_sbase,
-                        s->d_svals16, s->d_svconst, xfull, y, xdot, partials, np, st, &s->tail, g_stream);
-  else if ((s->sp_flags & LSB_SP_C16) && (s->sp_flags & LSB_SP_TMPL) && s->d_srec && s->d_scodes)
+  const int col_all = s0 == 0 && ns == s->sell.nslice;
+  const int col_in = c->plan_in && s0 == s->sell.split.first && ns == s->sell.split.last - s->sell.split.first;
+  if (s->sell_form == SELL_COL && (col_all || col_in) && !s->epi.zout)
+    lsb_k_spmv_tmpl_col(s->sp_flags | f32, s->sp_grid, c->period, col_all ? c->plan : c->plan_in,
+                        col_all ? c->items : c->items_in, c->centre0, s->n, s->row_begin, s->n_glob, &s->c16, xfull,
+                        y, xdot, partials, np, st, &s->tail, g_stream);
+  else if (s->sell_form >= SELL_TMPL)
     /* (a z-column flavour's grid was timed for the walk -- 3-4 workgroups per CU; the launches that go through
      * k_spmv_tmpl instead -- Chebyshev epilogue, boundary parts of a split SpMV -- take that kernel's own 6 per CU:
      * config 3 with Chebyshev(16) 941 -> 811 ms per solve) */
-    lsb_k_spmv_tmpl(s->sp_flags | f32, (s->sp_flags & LSB_SP_COL) ? 1536u : s->sp_grid, s->sp_period, s->d_sptr16, s0, ns, s->n, s->row_begin, s->n_glob,
-                    s->d_srec, s->d_tmask, s->d_tmpl, s->tmpl_nfar, s->d_sbase, s->d_svals16, s->d_svconst, xfull, y, xdot, partials, np, st,
-                    &s->tail, &s->epi, g_stream);
-  else if ((s->sp_flags & LSB_SP_C16) && s->d_scodes)
-    lsb_k_spmv_sell(s->sp_flags | f32, s->sp_grid, s->sp_period, s->d_sptr16, s0, ns, s->n, s->row_begin, s->n_glob, s->d_scodes,
-                    s->d_sbase, s->d_svals16, s->d_svconst, s->sell_ulen, xfull, y, xdot, partials, np, st, &s->tail, &s->epi,
-                    g_stream);
+    lsb_k_spmv_tmpl(s->sp_flags | f32, (s->sp_flags & LSB_SP_COL) ? 1536u : s->sp_grid, s->sp_period, &s->c16, s0, ns,
+                    s->n, s->row_begin, s->n_glob, xfull, y, xdot, partials, np, st, &s->tail, &s->epi, g_stream);
+  else if (s->sell_form == SELL_16)
+    lsb_k_spmv_sell(s->sp_flags | f32, s->sp_grid, s->sp_period, s->c16.sptr, s0, ns, s->n, s->row_begin, s->n_glob,
+                    s->c16.codes, s->c16.sbase, s->c16.vals, s->c16.vconst, s->c16.ulen, xfull, y, xdot, partials, np,
+                    st, &s->tail, &s->epi, g_stream);
   else
-    lsb_k_spmv_sell((s->sp_flags & ~LSB_SP_C16) | f32, s->sp_grid, s->sp_period, s->d_sptr, s0, ns, s->n, s->row_begin, s->n_glob,
-                    s->d_scols, NULL, s->d_svals, NULL, 0, xfull, y, xdot, partials, np, st, &s->tail, NULL, g_stream);
+    lsb_k_spmv_sell((s->sp_flags & ~LSB_SP_C16) | f32, s->sp_grid, s->sp_period, s->sell.sptr, s0, ns, s->n,
+                    s->row_begin, s->n_glob, s->sell.cols, NULL, s->sell.vals, NULL, 0, xfull, y, xdot, partials, np,
+                    st, &s->tail, NULL, g_stream);
 }
 
 void spmv_shard(struct shard *s, const double *xfull, double *y,
                        const double *xdot, double *partials, unsigned *np,
                        const struct lsb_pcg_state *st) {
-  if (s->variant == LSB_SPMV_PANEL) {
-    /* y = 0, then one launch per column panel accumulates into it: inside a
-     * launch every XCD gathers from the same 2 MiB slice of x, out of its L2 */
+  if (s->variant == LSB_SPMV_PANEL || s->variant == LSB_SPMV_BINNED) {
+    /* y = 0, then one launch per column panel / bin (= per L2-sized window of x) accumulates into it: inside
+     * a launch every XCD gathers from the same slice of x, out of its L2 */
+    const struct shard_panel *pl = &s->panel;
+    const struct shard_bins *bn = &s->bins;
     LSB_CHK_HIP(hipMemsetAsync(y, 0, (size_t)s->n * sizeof(double), g_stream));
-    for (unsigned p = 0; p < s->pn; p++) {
-      const unsigned b0 = s->h_pblk[p], nb = s->h_pblk[p + 1] - b0;
+    for (unsigned p = 0; s->variant == LSB_SPMV_PANEL && p < pl->n; p++) {
+      const unsigned b0 = pl->blk[p], nb = pl->blk[p + 1] - b0;
       if (nb)
-        lsb_k_spmv(LSB_SPMV_ADAPTIVE, s->n, s->pd_offs, s->pd_cols, s->pd_vals,
-                   s->pd_rowblk + b0, s->pd_blklanes + b0, nb, s->lanes, s->sp_flags,
-                   s->sp_grid, xfull, y, NULL, NULL, NULL, st, s->pd_rowmap, NULL, g_stream);
+        lsb_k_spmv(LSB_SPMV_ADAPTIVE, s->n, pl->offs, pl->cols, pl->vals, pl->rowblk + b0, pl->blklanes + b0, nb,
+                   s->lanes, s->sp_flags, s->sp_grid, xfull, y, NULL, NULL, NULL, st, pl->rowmap, NULL, g_stream);
     }
+    for (unsigned b = 0; s->variant == LSB_SPMV_BINNED && b < bn->n; b++)
+      lsb_k_spmv_binned(s->sp_flags, bn->cap, bn->chunk, bn->chunk_h[b], bn->chunk_h[b + 1] - bn->chunk_h[b],
+                        bn->rows, bn->cols, bn->vals, xfull, y, st, g_stream);
     if (partials)
       lsb_k_dot(s->n, y, xdot, partials, np, g_stream);
     return;
   }
   if (s->variant == LSB_SPMV_SELL) {
-    sell_launch(s, 0, s->nslice, xfull, y, xdot, partials, np, st);
+    sell_launch(s, 0, s->sell.nslice, xfull, y, xdot, partials, np, st);
     return;
   }
   if (s->variant == LSB_SPMV_TWOPHASE) {
-    lsb_k_spmv_twophase(s->tp_items, s->tp_item, s->tp_vals, s->tp_colw, s->tp_first, s->tp_mask,
-                        s->tp_delta, s->tp_roww, s->tp_col_lo, s->tp_cols, s->tp_rows, s->tp_bins,
-                        s->tp_binptr, s->tp_prod, s->n, xfull, s->tp_xlen, y, xdot, partials, np,
-                        s->tp_binparts, st, g_stream);
-    return;
-  }
-  if (s->variant == LSB_SPMV_BINNED) {
-    /* y = 0, then one launch per bin (= per L2-sized window of x) adds to it */
-    LSB_CHK_HIP(hipMemsetAsync(y, 0, (size_t)s->n * sizeof(double), g_stream));
-    for (unsigned b = 0; b < s->bn; b++)
-      lsb_k_spmv_binned(s->sp_flags, s->bcap, s->bd_chunk, s->h_binchunk[b],
-                        s->h_binchunk[b + 1] - s->h_binchunk[b], s->bd_rows, s->bd_cols, s->bd_vals,
-                        xfull, y, st, g_stream);
-    if (partials)
-      lsb_k_dot(s->n, y, xdot, partials, np, g_stream);
+    const struct shard_tp *t = &s->tp;
+    lsb_k_spmv_twophase(t->items, t->item, t->vals, t->colw, t->first, t->mask, t->delta, t->roww, t->col_lo,
+                        t->cols, t->rows, t->bins, t->binptr, t->prod, s->n, xfull, t->xlen, y, xdot, partials, np,
+                        t->binparts, st, g_stream);
     return;
   }
   const int f32 = s->mixed && (s->variant == LSB_SPMV_ADAPTIVE || s->variant == LSB_SPMV_SUBWAVE);
-  lsb_k_spmv(s->variant, s->n, s->d_offs, s->d_cols, f32 ? (const double *)s->d_vals32 : s->d_vals,
-             s->d_rowblk, s->d_blklanes, s->nblk, s->lanes, s->sp_flags | (f32 ? LSB_SP_F32 : 0u),
+  lsb_k_spmv(s->variant, s->n, s->csr.offs, s->csr.cols, f32 ? (const double *)s->csr.vals32 : s->csr.vals,
+             s->csr.rowblk, s->csr.blklanes, s->csr.nblk, s->lanes, s->sp_flags | (f32 ? LSB_SP_F32 : 0u),
              s->sp_grid, xfull, y, xdot, partials, np, st, NULL, &s->tail, g_stream);
+}
+
+struct halo_split shard_split(const struct shard *s, unsigned *count) {
+  if (count)
+    *count = s->variant == LSB_SPMV_SELL ? s->sell.nslice : s->csr.nblk;
+  return s->variant == LSB_SPMV_SELL ? s->sell.split : s->variant == LSB_SPMV_ADAPTIVE ? s->csr.split : (struct halo_split){0};
 }
 
 void spmv_shard_exact(struct shard *s, const double *xfull, double *y, const double *xdot,
@@ -1007,8 +1023,18 @@ void spmv_shard_exact(struct shard *s, const double *xfull, double *y, const dou
   }
   /* the CSR arrays always stay: row-blocked kernel (sub-wavefront for small operators) */
   const int v = s->nnz <= 500000ull ? LSB_SPMV_SUBWAVE : LSB_SPMV_ADAPTIVE;
-  lsb_k_spmv(v, s->n, s->d_offs, s->d_cols, s->d_vals, s->d_rowblk, s->d_blklanes, s->nblk, s->lanes,
+  lsb_k_spmv(v, s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->csr.rowblk, s->csr.blklanes, s->csr.nblk, s->lanes,
              LSB_SP_PREFETCH | LSB_SP_NT, 0, xfull, y, xdot, partials, np, st, NULL, NULL, g_stream);
+}
+
+/* the sliced-ELL kernel the shard's variant and flags select among the copies it has */
+static int sell_form(const struct shard *s) {
+  const unsigned f = s->sp_flags;
+  return s->variant != LSB_SPMV_SELL               ? SELL_NONE
+         : !(f & LSB_SP_C16) || !s->c16.codes      ? SELL_32
+         : !(f & LSB_SP_TMPL) || !s->c16.tmpl.srec ? SELL_16
+         : (f & LSB_SP_COL) && s->col.plan         ? SELL_COL
+                                                   : SELL_TMPL;
 }
 
 /*
@@ -1025,25 +1051,8 @@ void spmv_shard_exact(struct shard *s, const double *xfull, double *y, const dou
  * survives next to the matrix stream (64 M-row 7-point: plain loads).  The
  * copies that lose are freed.
  */
-void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
+static void time_spmv(lsb_hip_solver *sv, struct shard *s) {
   const struct lsb_hip_opts *o = &sv->o;
-  s->sp_flags = LSB_SP_PREFETCH | LSB_SP_NT;
-  s->sp_grid = o->spmv_grid > 0 ? (unsigned)o->spmv_grid : LSB_MAX_PARTIALS;
-  if (getenv("LSBENCH_HIP_FORCE_PERIOD")) /* tests: the plane-periodic dealing on small operators */
-    s->sp_period = s->sell_period;
-  if (o->spmv_tune >= 0) {
-    s->sp_flags = (unsigned)o->spmv_tune & (31u | LSB_SP_TMPL | LSB_SP_DEFER | LSB_SP_COL); /* bit 2: 16-bit codes, where that copy exists;
-                                                   bits 3, 4: binned form's gather flavour; bit 6: slice
-                                                   templates, where the constant-slot layout has them */
-    return;
-  }
-  if (s->variant == LSB_SPMV_SELL && !s->d_sptr)
-    s->variant = LSB_SPMV_ADAPTIVE; /* the operator did not qualify for the copy */
-  if ((s->variant != LSB_SPMV_ADAPTIVE && s->variant != LSB_SPMV_PANEL &&
-       s->variant != LSB_SPMV_SELL && s->variant != LSB_SPMV_BINNED &&
-       s->variant != LSB_SPMV_TWOPHASE) ||
-      s->nnz < 4000000ull)
-    return; /* small operators are launch-latency bound: nothing to tune */
   float best = 1e30f;
   unsigned bf = s->sp_flags, np;
   int bv = s->variant;
@@ -1069,12 +1078,12 @@ void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
   if (any || s->variant == LSB_SPMV_ADAPTIVE)
     for (unsigned f = 0; f < 4; f++)
       CAND(LSB_SPMV_ADAPTIVE, f, grid0, 0);
-  if (s->pn && (any || s->variant == LSB_SPMV_PANEL))
+  if (s->panel.n && (any || s->variant == LSB_SPMV_PANEL))
     for (unsigned f = 0; f < 4; f++)
       CAND(LSB_SPMV_PANEL, f, grid0, 0);
-  if (s->tp_bins && (any || s->variant == LSB_SPMV_TWOPHASE))
+  if (s->tp.bins && (any || s->variant == LSB_SPMV_TWOPHASE))
     CAND(LSB_SPMV_TWOPHASE, 0, grid0, 0);
-  if (s->bn && (any || s->variant == LSB_SPMV_BINNED)) {
+  if (s->bins.n && (any || s->variant == LSB_SPMV_BINNED)) {
     /* stream loads {nontemporal, plain}; the gather of x stays a plain load: L1-
      * bypassing (sc1) gathers measured the same, nontemporal ones 1.7x slower
      * (flags 8 / 16, kept for experiments through opts.spmv_tune) */
@@ -1082,35 +1091,35 @@ void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
     for (unsigned k = 0; k < sizeof bf / sizeof bf[0]; k++)
       CAND(LSB_SPMV_BINNED, bf[k], grid0, 0);
   }
-  const int periodic = s->sell_period != 0;
-  if (s->d_sptr && (any || s->variant == LSB_SPMV_SELL))
-    for (unsigned c16 = 0; c16 <= (s->d_scodes ? LSB_SP_C16 : 0u); c16 += LSB_SP_C16) {
+  const unsigned period = s->sell.period;
+  if (s->sell.sptr && (any || s->variant == LSB_SPMV_SELL))
+    for (unsigned c16 = 0; c16 <= (s->c16.codes ? LSB_SP_C16 : 0u); c16 += LSB_SP_C16) {
       CAND(LSB_SPMV_SELL, c16 | LSB_SP_NT, grid0, 0);
       CAND(LSB_SPMV_SELL, c16, grid0, 0);
       if (o->spmv_grid <= 0)
         CAND(LSB_SPMV_SELL, c16 | LSB_SP_NT, 1536, 0);
-      if (periodic) { /* every XCD an eighth of every plane */
-        CAND(LSB_SPMV_SELL, c16 | LSB_SP_NT, grid0, s->sell_period);
-        CAND(LSB_SPMV_SELL, c16, grid0, s->sell_period);
+      if (period) { /* every XCD an eighth of every plane */
+        CAND(LSB_SPMV_SELL, c16 | LSB_SP_NT, grid0, period);
+        CAND(LSB_SPMV_SELL, c16, grid0, period);
       }
-      if (c16 && s->d_srec) { /* slice templates (no stream to load nontemporally: NT only marks the
+      if (c16 && s->c16.tmpl.srec) { /* slice templates (no stream to load nontemporally: NT only marks the
                                  flavour as "solve-like" for the 3 % rule below) */
         const unsigned f = c16 | LSB_SP_NT | LSB_SP_TMPL;
         CAND(LSB_SPMV_SELL, f, grid0, 0);
         if (o->spmv_grid <= 0)
           CAND(LSB_SPMV_SELL, f, 1536, 0);
-        if (periodic) {
-          CAND(LSB_SPMV_SELL, f, grid0, s->sell_period);
+        if (period) {
+          CAND(LSB_SPMV_SELL, f, grid0, period);
           if (o->spmv_grid <= 0)
-            CAND(LSB_SPMV_SELL, f, 1536, s->sell_period);
+            CAND(LSB_SPMV_SELL, f, 1536, period);
         }
         /* the same with y parked in LDS and stored one turn later (k_spmv_tmpl<.., DEFER>): pays where
          * the vectors come out of HBM, costs ~2 us where they sit in the Infinity Cache */
-        if (s->tmpl_nfar >= 1 && s->nnz >= 16000000ull) {
+        if (s->c16.tmpl.nfar >= 1 && s->nnz >= 16000000ull) {
           const unsigned fd = f | LSB_SP_DEFER, gd = o->spmv_grid <= 0 ? 1536u : grid0;
           CAND(LSB_SPMV_SELL, fd, gd, 0);
-          if (periodic)
-            CAND(LSB_SPMV_SELL, fd, gd, s->sell_period);
+          if (period)
+            CAND(LSB_SPMV_SELL, fd, gd, period);
         }
         /* the z-column walk of a 3-D stencil (k_spmv_tmpl_col): one new plane per step */
         /* (fewer resident workgroups than the other flavours: 3-4 per CU measured 232-233 us on the
@@ -1118,9 +1127,9 @@ void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
         /* (no more workgroups than the two-launch iteration's grid, LSB_TMPL_COL_GRID: a run's first p.q comes
          * from this SpMV, the others from k_pcg_col_px -- on one grid they are the same partial sums, and a solve
          * repeats bit for bit however it is cut into runs) */
-        if (s->d_colplan) {
+        if (s->col.plan) {
           if (o->spmv_grid <= 0) {
-            const unsigned gcol = LSB_TMPL_COL_GRID(s->tmpl_nfar);
+            const unsigned gcol = LSB_TMPL_COL_GRID(s->c16.tmpl.nfar);
             CAND(LSB_SPMV_SELL, f | LSB_SP_COL, 768, 0);
             if (gcol > 768) {
               CAND(LSB_SPMV_SELL, f | LSB_SP_COL, 1024, 0);
@@ -1134,6 +1143,7 @@ void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
 #undef CAND
   for (int ci = 0; ci < ncand; ci++) {
     s->variant = cand[ci].v, s->sp_flags = cand[ci].f, s->sp_grid = cand[ci].g, s->sp_period = cand[ci].p;
+    s->sell_form = sell_form(s);
     spmv_shard(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &np, NULL);
     LSB_CHK_HIP(hipEventRecord(sv->ev_t0, g_stream));
     const int reps = 5;
@@ -1157,7 +1167,7 @@ void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
     /* the z-column walk is also what the two-launch iteration runs on (k_pcg_col_px + k_pcg_col_r: 8 vector passes
      * instead of 11): where that form will apply -- one shard, Jacobi with a constant diagonal, classic PCG, fp64 --
      * a flavour without it has to beat the walk by 15 % as an SpMV to be worth the three launches */
-    if ((s->sp_flags & LSB_SP_COL) && s->d_colplan && sv->nshard == 1 && !sv->dist && !sv->multi && s->dinv_uniform &&
+    if (s->sell_form == SELL_COL && sv->nshard == 1 && !sv->dist && !sv->multi && s->dinv_uniform &&
         !s->mixed && o->precond == LSB_PRECOND_JACOBI && (o->krylov == LSB_KRYLOV_PCG || o->krylov == LSB_KRYLOV_AUTO) &&
         !sv->env_no_fuse_px)
       ms *= 0.85f;
@@ -1168,40 +1178,40 @@ void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
   s->sp_period = bp;
   s->variant = bv;
   s->sp_flags = bf;
-  /* the copies that lost are not kept */
-  if (any && bv != LSB_SPMV_TWOPHASE && s->tp_bins) {
-    lsb_hip_free(s->tp_item), lsb_hip_free(s->tp_binptr), lsb_hip_free(s->tp_first);
-    lsb_hip_free(s->tp_mask), lsb_hip_free(s->tp_delta);
-    lsb_hip_free(s->tp_colw), lsb_hip_free(s->tp_roww), lsb_hip_free(s->tp_vals);
-    lsb_hip_free(s->tp_prod), lsb_hip_free(s->tp_binparts);
-    s->tp_item = s->tp_binptr = s->tp_first = s->tp_delta = NULL, s->tp_mask = NULL;
-    s->tp_colw = s->tp_roww = NULL;
-    s->tp_vals = s->tp_prod = s->tp_binparts = NULL, s->tp_bins = 0;
-  }
-  if (any && bv != LSB_SPMV_BINNED && s->bn) {
-    lsb_hip_free(s->bd_chunk), lsb_hip_free(s->bd_rows), lsb_hip_free(s->bd_cols);
-    lsb_hip_free(s->bd_vals);
-    s->bd_chunk = s->bd_rows = s->bd_cols = NULL, s->bd_vals = NULL, s->bn = 0;
-  }
-  if (!(bv == LSB_SPMV_SELL && (bf & LSB_SP_C16))) {
-    lsb_hip_free(s->d_sptr16), lsb_hip_free(s->d_scodes), lsb_hip_free(s->d_sbase);
-    lsb_hip_free(s->d_svals16), lsb_hip_free(s->d_svconst);
-    s->d_sptr16 = NULL, s->d_scodes = NULL, s->d_sbase = NULL, s->d_svals16 = NULL, s->d_svconst = NULL;
-  }
-  if (!(bv == LSB_SPMV_SELL && (bf & LSB_SP_TMPL))) {
-    lsb_hip_free(s->d_srec), lsb_hip_free(s->d_tmpl), lsb_hip_free(s->d_tmask);
-    s->d_srec = NULL, s->d_tmpl = NULL, s->d_tmask = NULL;
-  }
-  if (!(bv == LSB_SPMV_SELL && (bf & LSB_SP_COL))) {
-    lsb_hip_free(s->d_colplan), lsb_hip_free(s->d_colplan_in);
-    s->d_colplan = s->d_colplan_in = NULL;
-  }
-  if (any && !(bv == LSB_SPMV_SELL && !(bf & LSB_SP_C16))) {
-    lsb_hip_free(s->d_scols), lsb_hip_free(s->d_svals);
-    s->d_scols = NULL, s->d_svals = NULL;
-    if (bv != LSB_SPMV_SELL)
-      lsb_hip_free(s->d_sptr), s->d_sptr = NULL;
-  }
+  /* the copies that lost are not kept: the two-phase, binned and 32-bit ones where the form was left to this
+   * pass, the 16-bit parts whenever they were not chosen */
+  const int sell = bv == LSB_SPMV_SELL;
+  if (any && bv != LSB_SPMV_TWOPHASE)
+    tp_free(&s->tp);
+  if (any && bv != LSB_SPMV_BINNED)
+    bins_free(&s->bins);
+  if (!(sell && (bf & LSB_SP_TMPL)))
+    tmpl_free(&s->c16.tmpl);
+  if (!(sell && (bf & LSB_SP_C16)))
+    c16_free(&s->c16);
+  if (!(sell && (bf & LSB_SP_COL)))
+    col_free(&s->col);
+  if (any && !(sell && !(bf & LSB_SP_C16)))
+    sell32_free(&s->sell);
+}
+
+/* The SpMV flavour of the shard: opts.spmv_tune as given, else the timing pass; then the sliced-ELL kernel
+ * it resolves to. */
+void tune_spmv(lsb_hip_solver *sv, struct shard *s) {
+  const struct lsb_hip_opts *o = &sv->o;
+  s->sp_flags = LSB_SP_PREFETCH | LSB_SP_NT;
+  s->sp_grid = o->spmv_grid > 0 ? (unsigned)o->spmv_grid : LSB_MAX_PARTIALS;
+  if (getenv("LSBENCH_HIP_FORCE_PERIOD")) /* tests: the plane-periodic dealing on small operators */
+    s->sp_period = s->sell.period;
+  if (o->spmv_tune >= 0)
+    s->sp_flags = (unsigned)o->spmv_tune & (31u | LSB_SP_TMPL | LSB_SP_DEFER | LSB_SP_COL); /* bit 2: 16-bit codes, where that copy exists;
+                                                   bits 3, 4: binned form's gather flavour; bit 6: slice
+                                                   templates, where the constant-slot layout has them */
+  else if ((s->variant == LSB_SPMV_ADAPTIVE || s->variant == LSB_SPMV_PANEL || s->variant == LSB_SPMV_SELL ||
+            s->variant == LSB_SPMV_BINNED || s->variant == LSB_SPMV_TWOPHASE) &&
+           s->nnz >= 4000000ull) /* (small operators are launch-latency bound: nothing to tune) */
+    time_spmv(sv, s);
+  s->sell_form = sell_form(s);
 }
 
 /* y = Op x for the rows of this process */

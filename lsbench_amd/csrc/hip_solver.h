@@ -3,7 +3,8 @@
  * backend:
  *   hip_cdna4.c      backend entry points (init / finalize / bench), options,
  *                    device memory helpers, kernel-level C-ABI
- *   hip_solver.c     shards: upload, kernel forms, timing pass, create / destroy
+ *   hip_solver.c     shards: one builder and one free per SpMV layout, upload, kernel forms,
+ *                    timing pass, create / destroy
  *   hip_dist.c       what sharded solves add: exchange, all-reduce, overlap,
  *                    the direct xGMI path's set-up
  *   hip_pcg.c        PCG / single-reduction PCG iteration and the host loop
@@ -46,6 +47,16 @@ LSB_INTERNAL int bench_multi(double *x, struct csr *A, const double *r, const st
 #define MAX_SAMPLES 64
 #define LSB_NGRAPH 4 /* cached hipGraphs: whole-solve + continuation chunk, solve proper + correction */
 
+/* Rows that reference other shards' columns sit in units [0,first) and [last,count) of a layout (row
+ * blocks, slices); the units in between can start before the halo has arrived (ok = 0: not separable) */
+struct halo_split {
+  unsigned first, last;
+  int ok;
+};
+/* the sliced-ELL kernel a shard's SpMV runs (tune_spmv resolves it from the variant, the flags and the
+ * copies that exist; sell_launch, the getters, the fused PCG and Chebyshev forms read it) */
+enum { SELL_NONE, SELL_32, SELL_16, SELL_TMPL, SELL_COL };
+
 struct shard {
   /* ONE allocation for the vectors the iteration streams (r, q, the gather vector, the Jacobi
    * diagonal, the single-reduction form's p / s, the preconditioners' z vectors): their placement
@@ -59,13 +70,70 @@ struct shard {
   size_t slab_cap, slab_used;
   unsigned row_begin, n;
   unsigned long long nnz;
-  int *d_offs, *d_cols, *d_rowblk;
-  unsigned char *d_blklanes;
-  unsigned sp_flags, sp_grid; /* adaptive-SpMV flavour, picked by tune_spmv() */
-  unsigned col_period;             /* slices per plane of the z-column plan (a period of at least 8 slices) */
-  unsigned sp_period, sell_period; /* sliced-ELL: slices per plane the XCD dealing follows (0 =
-                                      contiguous eighths); candidate found at upload */
-  double *d_vals, *d_dinv, *d_r, *d_q, *d_pfull;
+  unsigned n_glob; /* columns of the operator = length of the gather vector */
+  unsigned col_lo, col_hi; /* column hull referenced by the shard's rows */
+  int variant, sell_form; /* LSB_SPMV_*; the sliced-ELL kernel it resolves to (SELL_*) */
+  unsigned lanes;
+  /* SpMV flavour, grid and (sliced-ELL) slices per plane the XCD dealing follows (0 = contiguous eighths),
+   * picked by tune_spmv() */
+  unsigned sp_flags, sp_grid, sp_period;
+  /* opts.precision = LSB_PREC_MIXED: the SpMV forms stream fp32 values (the sliced-ELL value arrays then
+   * HOLD floats; csr.vals32 is the CSR's copy); csr.vals stays fp64 for the residual of the refinement.
+   * exact32: rounding changed nothing */
+  int mixed, exact32;
+  /* The SpMV layouts: one struct, one builder and one free each (hip_solver.c).  The CSR is always
+   * there; the others are built where the operator qualifies, and tune_spmv() frees the ones that lose. */
+  struct shard_csr { /* CSR + the row blocks of the adaptive kernel */
+    int *offs, *cols, *rowblk;
+    unsigned char *blklanes;
+    double *vals;
+    float *vals32;
+    unsigned nblk;
+    struct halo_split split; /* in row blocks */
+  } csr;
+  struct shard_panel { /* column-panel form (LSB_SPMV_PANEL), built when asked for */
+    unsigned n;     /* panels, 0 = not built */
+    unsigned *blk;  /* host, n+1: first row block of each panel */
+    int *offs, *cols, *rowmap, *rowblk;
+    unsigned char *blklanes;
+    double *vals;
+  } panel;
+  struct shard_bins { /* binned form (LSB_SPMV_BINNED), built for scattered operators only */
+    unsigned n, cap; /* bins (0 = not built), entries per chunk */
+    unsigned *chunk_h; /* host, n+1: first chunk of each bin */
+    unsigned *chunk, *rows, *cols;
+    double *vals;
+  } bins;
+  struct shard_tp { /* two-phase form (LSB_SPMV_TWOPHASE), built for scattered operators only */
+    unsigned items, bins, col_lo, xlen, cols, rows; /* bins = 0: not built */
+    unsigned *item, *binptr, *first, *delta;
+    unsigned long long *mask;
+    unsigned short *colw, *roww;
+    double *vals, *prod, *binparts;
+  } tp;
+  /* sliced-ELL (LSB_SPMV_SELL), built when padding stays under 1/8: the slice geometry every copy shares
+   * and the 32-bit copy */
+  struct shard_sell {
+    unsigned nslice;
+    unsigned period;         /* candidate period of the XCD dealing, found at upload (0: none) */
+    struct halo_split split; /* in slices */
+    unsigned *sptr;
+    int *cols;
+    double *vals;
+    unsigned long long bytes; /* matrix-side bytes one launch streams */
+  } sell;
+  struct lsb_sell16_dev c16; /* its 16-bit-code form (LSB_SP_C16) and the templates (LSB_SP_TMPL) */
+  /* z-column plan of the template layout (lsb_sell_tmpl_columns; LSB_SP_COL): xbeg[9], padding to 16
+   * unsigneds, 16-byte items */
+  struct shard_col {
+    unsigned period;           /* slices per plane (a period of at least 8 slices; 0: no plan) */
+    unsigned *plan, *plan_in;  /* all slices; the interior range of the split SpMV */
+    unsigned items, items_in;
+    int centre0;
+    unsigned long long slices; /* slices inside columns */
+    unsigned long long bytes;  /* matrix-side bytes one launch of the walk streams */
+  } col;
+  double *d_dinv, *d_r, *d_q, *d_pfull;
   double *d_p1, *d_s1; /* single-reduction CG: p and s = S p (pfull then holds u) */
   unsigned npq, np2;   /* partial counts of the SpMV / sweep launches */
   const double *ar2_parts; /* sweep partials the next all-reduce folds in */
@@ -75,43 +143,8 @@ struct shard {
   double *d_zfull2;        /* its second gather vector: z' of step k is step k+1's z */
   struct lsb_ar_tail tail; /* counter != NULL: the next SpMV launch of this shard carries the
                               all-reduce's contribute phase (exchange_and_spmv arms and clears it) */
-  /* rows that reference other shards' columns sit in row blocks [0,ov_b1) and
-   * [ov_b2,nblk); the blocks in between need no halo (0,0 = not separable) */
-  unsigned ov_b1, ov_b2;
-  int ov_ok;
-  /* sliced-ELL copy (LSB_SPMV_SELL), built when padding stays under 1/8; the
-   * same prefix/interior/suffix split in slices */
-  unsigned *d_sptr;
-  int *d_scols;
-  double *d_svals;
-  unsigned nslice, ov_s1, ov_s2;
-  int ov_sok;
-  /* ... and its 16-bit-code form (LSB_SP_C16 in sp_flags), own slice offsets */
   int dinv_uniform;   /* all entries of dinv equal dinv_const */
   double dinv_const;
-  unsigned *d_sptr16;
-  short *d_scodes;
-  int *d_sbase;
-  double *d_svals16;
-  double *d_svconst;       /* != NULL: the constant-slot layout (lsb_sell16_value_slots): d_sbase holds 4
-                              ints per slot, d_svals16 only the sell_vslots slots that keep their values */
-  unsigned sell_vslots, sell_slots;
-  unsigned long long sell16_bytes, sell32_bytes; /* matrix-side bytes one launch of the form streams */
-  /* slice templates of the constant-slot layout (lsb_sell16_templates; LSB_SP_TMPL in sp_flags) */
-  unsigned *d_srec; /* per slice {template id (255: none), first kept value slot, first mask, 0} */
-  unsigned long long *d_tmask;
-  unsigned n_glob; /* columns of the operator = length of the gather vector */
-  struct lsb_sell_tmpl *d_tmpl;
-  unsigned tmpl_nfar, tmpl_count;
-  unsigned long long tmpl_pure, tmpl_shaped, tmpl_bytes;
-  /* z-column plan of the template layout (lsb_sell_tmpl_columns; LSB_SP_COL in sp_flags): xbeg[9],
-   * padding to 16 unsigneds, 16-byte items */
-  unsigned *d_colplan, *d_colplan_in; /* all slices; the interior range [ov_s1, ov_s2) of the split SpMV */
-  unsigned col_items, col_items_in, col_kmax;
-  int col_centre0;
-  unsigned long long col_slices; /* slices inside columns */
-  unsigned long long col_bytes;  /* matrix-side bytes one launch of the z-column walk streams */
-  unsigned sell_ulen;      /* != 0: every slice of the 16-bit copy has this many slots */
   double *d_parts_pq, *d_parts2;
   double *d_scal; /* [0] p.q   [1] r.z'  [2] r.r   (multi-shard path) */
   struct lsb_pcg_state *d_st;
@@ -119,20 +152,6 @@ struct shard {
    * SpMV entry point, the first all-reduce of a solve): a time-out of the direct
    * xGMI path is recorded here and reported by the host (check_aux_status) */
   struct lsb_pcg_state *d_st_aux;
-  unsigned nblk, lanes;
-  int variant;
-  unsigned col_lo, col_hi; /* column hull referenced by the shard's rows */
-  /* column-panel form (LSB_SPMV_PANEL), built for scattered operators only */
-  unsigned pn;       /* panels, 0 = not built */
-  unsigned *h_pblk;  /* pn+1: first row block of each panel */
-  int *pd_offs, *pd_cols, *pd_rowmap, *pd_rowblk;
-  unsigned char *pd_blklanes;
-  double *pd_vals;
-  /* opts.precision = LSB_PREC_MIXED: the SpMV forms stream fp32 values (the sliced-
-   * ELL value arrays then HOLD floats; d_vals32 is the CSR's copy); d_vals stays
-   * fp64 for the residual of the refinement.  exact32: rounding changed nothing */
-  int mixed, exact32;
-  float *d_vals32;
   /* preconditioners that produce z = M^-1 r as a vector (hip_precond.c) */
   double *d_zfull, *d_z; /* z: a gather vector of its own (Chebyshev), or n doubles */
   double *d_chd;         /* Chebyshev: the recurrence's direction vector */
@@ -159,17 +178,6 @@ struct shard {
     unsigned nmem;
     double setup_s;
   } *amg;
-  /* binned form (LSB_SPMV_BINNED), built for scattered operators only */
-  unsigned bn, bcap;   /* bins (0 = not built), entries per chunk */
-  unsigned *h_binchunk; /* bn+1: first chunk of each bin (host) */
-  unsigned *bd_chunk, *bd_rows, *bd_cols;
-  double *bd_vals;
-  /* two-phase form (LSB_SPMV_TWOPHASE), built for scattered operators only */
-  unsigned tp_items, tp_bins, tp_col_lo, tp_xlen, tp_cols, tp_rows; /* tp_bins = 0: not built */
-  unsigned *tp_item, *tp_binptr, *tp_first, *tp_delta;
-  unsigned long long *tp_mask;
-  unsigned short *tp_colw, *tp_roww;
-  double *tp_vals, *tp_prod, *tp_binparts;
   struct lsb_xfer *recv, *send;
   int nrecv, nsend;
 };
@@ -290,6 +298,8 @@ LSB_INTERNAL void spmv_shard(struct shard *s, const double *xfull, double *y, co
 LSB_INTERNAL void spmv_shard_exact(struct shard *s, const double *xfull, double *y, const double *xdot,
                                    double *partials, unsigned *np, const struct lsb_pcg_state *st);
 LSB_INTERNAL void tune_spmv(lsb_hip_solver *sv, struct shard *s);
+/* the halo split of the layout the shard's SpMV runs on and its unit count (ok = 0: the form has none) */
+LSB_INTERNAL struct halo_split shard_split(const struct shard *s, unsigned *count);
 /* hip_dist.c */
 LSB_INTERNAL void p2p_setup(lsb_hip_solver *sv);
 LSB_INTERNAL void overlap_setup(lsb_hip_solver *sv);

@@ -120,35 +120,47 @@ void lsb_k_spmv_sell(unsigned flags, unsigned grid_cap, unsigned period, const u
                      const struct lsb_cheb_epi *epi, void *stream);
 #define LSB_SP_TMPL 64u /* 16-bit sliced-ELL with constant slots: slice templates (k_spmv_tmpl) */
 #define LSB_SP_DEFER 128u /* k_spmv_tmpl: a turn's y is parked in LDS and stored by the wave's next turn */
-void lsb_k_spmv_tmpl(unsigned flags, unsigned grid_cap, unsigned period, const unsigned *sptr, unsigned s0,
-                     unsigned ns, unsigned n, unsigned row_begin, unsigned xlen, const unsigned *srec,
-                     const unsigned long long *mask, const struct lsb_sell_tmpl *td,
-                     unsigned nfar, const int *sbase, const void *vals,
-                     const double *vconst, const double *x, double *y, const double *xdot,
-                     double *partials, unsigned *npartials, const struct lsb_pcg_state *st,
+/* A shard's 16-bit sliced-ELL copy on the device (lsb_csr_sellize16) with its constant slots
+ * (lsb_sell16_value_slots) and slice templates (lsb_sell16_templates): the operands the template
+ * launchers below unpack */
+struct lsb_sell16_dev {
+  unsigned *sptr;
+  short *codes;
+  int *sbase;
+  double *vals;   /* the kept value slots (floats under LSB_SP_F32) */
+  double *vconst; /* != NULL: the constant-slot layout -- sbase holds 4 ints per slot, vals only the
+                     vslots slots that keep their values */
+  unsigned vslots, slots, ulen; /* ulen != 0: every slice has this many slots */
+  unsigned long long bytes; /* matrix-side bytes one launch streams */
+  struct lsb_tmpl_dev { /* srec != NULL: the templates (LSB_SP_TMPL) */
+    unsigned *srec; /* per slice {template id (255: none), first kept value slot, first mask, 0} */
+    unsigned long long *mask;
+    struct lsb_sell_tmpl *td;
+    unsigned nfar;
+    unsigned long long bytes;
+  } tmpl;
+};
+void lsb_k_spmv_tmpl(unsigned flags, unsigned grid_cap, unsigned period, const struct lsb_sell16_dev *c, unsigned s0,
+                     unsigned ns, unsigned n, unsigned row_begin, unsigned xlen, const double *x, double *y,
+                     const double *xdot, double *partials, unsigned *npartials, const struct lsb_pcg_state *st,
                      const struct lsb_ar_tail *tail, const struct lsb_cheb_epi *epi, void *stream);
 /* the classic PCG iteration in two launches on a z-column plan (hip_kernels.hip: k_pcg_col_px) */
 void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem, unsigned n,
-                      const unsigned *sptr, const unsigned long long *mask, const struct lsb_sell_tmpl *td,
-                      unsigned nfar, const int *sbase, const double *vals, const double *vconst, const double *r,
-                      const double *pold, double *pnew, double *x, int xupd, double dc, double *partials,
-                      unsigned *npartials, struct lsb_pcg_state *st, int parity, const double *parts2,
-                      unsigned nparts2, void *stream);
+                      const struct lsb_sell16_dev *c, const double *r, const double *pold, double *pnew, double *x,
+                      int xupd, double dc, double *partials, unsigned *npartials, struct lsb_pcg_state *st, int parity,
+                      const double *parts2, unsigned nparts2, void *stream);
 /* the r half: alpha, r -= alpha S p with S p formed again out of p (q is never stored), partials of (r.z', r.r) */
 void lsb_k_pcg_col_r(unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem, unsigned n,
-                     const unsigned *sptr, const unsigned long long *mask, const struct lsb_sell_tmpl *td, unsigned nfar,
-                     const int *sbase, const double *vals, const double *vconst, const double *p, double *r, double dc,
-                     struct lsb_pcg_state *st, int parity, int pbuf, int xtwo, const double *pq_parts, unsigned npq,
-                     double *partials2, unsigned *npartials, void *stream);
+                     const struct lsb_sell16_dev *c, const double *p, double *r, double dc, struct lsb_pcg_state *st,
+                     int parity, int pbuf, int xtwo, const double *pq_parts, unsigned npq, double *partials2,
+                     unsigned *npartials, void *stream);
 void lsb_k_pcg_xfix(unsigned n, const double *p0, const double *p1, double *x, const struct lsb_pcg_state *st,
                     void *stream);
 #define LSB_SP_COL 256u /* k_spmv_tmpl_col: the template layout walked in z-columns (whole launches of a
                            shard that has a column plan; implies LSB_SP_TMPL) */
 void lsb_k_spmv_tmpl_col(unsigned flags, unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem,
-                         int centre0, unsigned n, unsigned row_begin, unsigned xlen, const unsigned *sptr,
-                         const unsigned long long *mask, const struct lsb_sell_tmpl *td, unsigned nfar,
-                         const int *sbase, const void *vals, const double *vconst, const double *x, double *y,
-                         const double *xdot, double *partials, unsigned *npartials,
+                         int centre0, unsigned n, unsigned row_begin, unsigned xlen, const struct lsb_sell16_dev *c,
+                         const double *x, double *y, const double *xdot, double *partials, unsigned *npartials,
                          const struct lsb_pcg_state *st, const struct lsb_ar_tail *tail, void *stream);
 void lsb_k_spmv_binned(unsigned flags, unsigned chunk_cap, const unsigned *chunk_begin, unsigned c0,
                        unsigned nchunk, const unsigned *rows, const unsigned *cols, const double *vals,
