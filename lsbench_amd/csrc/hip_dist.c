@@ -286,17 +286,14 @@ void exchange_and_spmv(lsb_hip_solver *sv, int sample) {
     exchange_p(sv, 1);
     for (int i = 0; i < sv->nshard; i++) {
       struct shard *s = &sv->sh[i];
-      if (i == 0 && sample >= 0)
-        LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample], g_stream));
+      if (i == 0)
+        sample_open(sv, sample);
       if (fold)
         arm_tail(sv, i, 0);
       spmv_shard(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &s->npq, s->d_st);
       s->tail.counter = NULL;
-      if (i == 0 && sample >= 0) {
-        LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 1], g_stream));
-        LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 2], g_stream));
-        LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 3], g_stream));
-      }
+      if (i == 0)
+        sample_close(sv, sample);
     }
     return;
   }
@@ -309,8 +306,7 @@ void exchange_and_spmv(lsb_hip_solver *sv, int sample) {
     exchange_on(sv, comm_stream());
     LSB_CHK_HIP(hipEventRecord(sv->ev_halo, comm_stream()));    /* the halo has landed   */
   }
-  if (sample >= 0)
-    LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample], g_stream));
+  sample_open(sv, sample);
   unsigned na, nb, nc, b0;
   for (int i = 0; i < sv->nshard; i++) {                         /* interior: no halo     */
     struct shard *s = &sv->sh[i];
@@ -337,11 +333,7 @@ void exchange_and_spmv(lsb_hip_solver *sv, int sample) {
     s->tail.counter = NULL;
     s->npq += nb + nc;
   }
-  if (sample >= 0) {
-    LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 1], g_stream));
-    LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 2], g_stream));
-    LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 3], g_stream));
-  }
+  sample_close(sv, sample);
 }
 
 /*

@@ -1,7 +1,7 @@
 /*
- * Jacobi-PCG on the device-resident state: what one iteration enqueues
- * (classic three-launch form and the single-reduction form), and the host loop
- * around it ("Host loop").
+ * Jacobi-PCG on the device-resident state: the iteration forms a solver may run (one is chosen at
+ * creation, pcg_choose_form), what each enqueues per iteration, and the host loop around them
+ * ("Host loop").
  */
 #define _GNU_SOURCE
 #include "hip_solver.h"
@@ -13,33 +13,155 @@
 /* ------------------------------------------------------------------------ */
 /* PCG                                                                       */
 /* ------------------------------------------------------------------------ */
-static int use_cg1(const lsb_hip_solver *sv);
-static int fuse_p(const lsb_hip_solver *sv);
-static void cg1_enqueue_init(lsb_hip_solver *sv, const double *d_b, double *d_x);
-static void cg1_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sample);
-
-/* ---- PCG with z = M^-1 r as a vector (Chebyshev, block-Jacobi) -------------
- * The classic recurrences through the same sweeps: k_pcg_update_xr with a unit
- * "diagonal" (its own r.r partial sums are superseded), the preconditioner's
- * launches, k_dot2 for (r.z, r.r), k_pcg_update_p with z in the place of r. */
-static void gen_dot_and_reduce(lsb_hip_solver *sv, int gated, unsigned *np2_out) {
-  unsigned np2 = 0;
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    lsb_k_dot2(s->n, s->d_r, s->d_z, s->d_parts2, &np2, gated ? s->d_st : NULL, g_stream);
-    if (sv->multi)
-      lsb_k_reduce_final(s->d_parts2, np2, 2, s->d_scal + 1, 0, gated ? s->d_st : NULL, g_stream);
-  }
-  if (sv->multi)
-    allreduce_scal(sv, 1, 2, gated);
-  *np2_out = np2;
+/* Which PCG iteration the solver runs (enum pcg_form), tried in this order:
+ *   FSAI3    FSAI on a launch-bound operator (S, G and G^T all sub-wavefront), one shard, fp64
+ *   GENERIC  any other vector preconditioner (Chebyshev, block-Jacobi, FSAI, AMG)
+ *   CG1      opts.krylov = cg1, or auto across shards
+ *   COL      one shard, fp64, Jacobi with one constant diagonal, on the z-column plan
+ *   SUBWAVE  one shard, fp64, the sub-wavefront SpMV
+ *   CLASSIC  the rest
+ * Called once, by solver_finish_setup: after precond_setup (FSAI3 looks at G and G^T), before the set-up
+ * passes that run solves (p2p_setup, overlap_setup, persist_setup).  That is the choice each enqueued
+ * iteration used to make again: of its inputs only opts.sample_spmv changes after creation -- overlap_setup
+ * zeroes it for its timing solves, on multi-shard solvers only, where neither form that reads it (FSAI3,
+ * SUBWAVE) can apply.  The switches that turn the fused forms off for the tests that compare them
+ * (LSBENCH_HIP_NO_FSAI_FUSE, _NO_FUSE_P, _NO_FUSE_PX) are read here alone. */
+enum pcg_form pcg_choose_form(const lsb_hip_solver *sv) {
+  const struct shard *s = &sv->sh[0];
+  const struct lsb_hip_opts *o = &sv->o;
+  if (o->krylov == LSB_KRYLOV_GMRES)
+    return PCG_NONE;
+  if (o->precond == LSB_PRECOND_FSAI && !sv->multi && !s->mixed && s->variant == LSB_SPMV_SUBWAVE &&
+      s->fs_g.variant == LSB_SPMV_SUBWAVE && s->fs_gt.variant == LSB_SPMV_SUBWAVE && o->sample_spmv <= 0 &&
+      o->krylov != LSB_KRYLOV_PCG1 && !getenv("LSBENCH_HIP_NO_FSAI_FUSE"))
+    return PCG_FSAI3;
+  if (generic_precond(sv))
+    return PCG_GENERIC;
+  /* single reduction, measured on one GPU: no gain for small operators (tests/xn3b_A_18.txt: 390 vs
+   * 400 solves/s, the fused sweep is as long as the two it replaces) and +6 % time
+   * on the 10M-row operator where the diagonal is a vector (96 n vs 88 n bytes; round 3, general
+   * values: 251 against 236-241 us per iteration); what it saves there is a collective.
+   * With ONE constant diagonal (u = c r never stored) it moves the classic form's 72 n in two
+   * launches instead of three; since its sweep loads the gather vector the plain way
+   * (k_cg1_update, round 3: the SpMV behind it 40 -> 24 us on config 3) it is level with the
+   * classic form on one GPU -- config 3 through bench.py 136.8-138.0 against 136.0-139.8 us per
+   * iteration, config 4 1186-1188 against 1182-1191 (tools/gpu_krylov_ab.sh) -- so one shard
+   * keeps the classic form, the reference's algorithm as written. */
+  if (o->krylov == LSB_KRYLOV_PCG1 || (o->krylov == LSB_KRYLOV_AUTO && sv->multi))
+    return PCG_CG1;
+  if (sv->multi || s->mixed || getenv("LSBENCH_HIP_NO_FUSE_P"))
+    return PCG_CLASSIC;
+  if (s->sell_form == SELL_COL && s->dinv_uniform && s->c16.tmpl.nfar >= 1 && s->c16.tmpl.nfar <= 2 &&
+      s->row_begin == 0 && s->n == s->n_glob && o->precond == LSB_PRECOND_JACOBI && !getenv("LSBENCH_HIP_NO_FUSE_PX"))
+    return PCG_COL; /* (event-timed too: the sample brackets the launch that carries the SpMV) */
+  /* (not while SpMV launches are being event-timed: the fused launch has no SpMV of its own to
+   * bracket, and solve_core reads the sample events) */
+  return s->variant == LSB_SPMV_SUBWAVE && o->sample_spmv <= 0 ? PCG_SUBWAVE : PCG_CLASSIC;
 }
 
-static void gen_enqueue_init(lsb_hip_solver *sv, const double *d_b, double *d_x) {
-  unsigned np2 = 0;
+/* The vectors a form needs besides the shard's own, out of its slab where they fit (shard_vec): the second
+ * direction buffer of SUBWAVE, COL and FSAI3, FSAI3's second residual, CG1's p and s.  Where they land sets
+ * the iteration's speed (tune_blas1_nt), so they are taken when they always were: FSAI's by precond_setup
+ * for every FSAI solver, whichever form it runs (the slab counts them), the others by the first init. */
+void form_vecs(lsb_hip_solver *sv, enum pcg_form f) {
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    if (!s->d_p1 && (f == PCG_SUBWAVE || f == PCG_COL || f == PCG_CG1 || f == PCG_FSAI3))
+      s->d_p1 = shard_vec(s, s->n);
+    if (!s->d_s1 && f == PCG_CG1)
+      s->d_s1 = shard_vec(s, s->n);
+    if (!s->d_r1 && f == PCG_FSAI3)
+      s->d_r1 = shard_vec(s, s->n);
+  }
+}
+
+void sample_open(lsb_hip_solver *sv, int k) {
+  if (k >= 0)
+    LSB_CHK_HIP(hipEventRecord(sv->ev[4 * k], g_stream));
+}
+
+/* e1 closes the SpMV interval; e2,e3 bracket NOTHING: their distance is
+ * what one event marker costs in this very spot of the stream, and is
+ * subtracted from e0->e1 (an event pair around a kernel otherwise reads
+ * ~9 us longer than the kernel's duration in a rocprofv3 trace). */
+void sample_close(lsb_hip_solver *sv, int k) {
+  for (int e = 1; e < 4 && k >= 0; e++)
+    LSB_CHK_HIP(hipEventRecord(sv->ev[4 * k + e], g_stream));
+}
+
+/* q = S p and p.q on every shard: behind the exchange and through the all-reduce where there are several */
+static void spmv_pq(lsb_hip_solver *sv, int sample) {
+  if (sv->multi) {
+    exchange_and_spmv(sv, sample);
+    allreduce_pq(sv, 1, 0);
+    return;
+  }
+  struct shard *s = &sv->sh[0];
+  sample_open(sv, sample);
+  spmv_shard(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &s->npq, s->d_st);
+  sample_close(sv, sample);
+}
+
+/* the s->np2 partial sums of (r.z, r.r) in every shard's d_parts2, summed over the shards into d_scal[1..2]
+ * where there are several; gated: on the state of the running solve */
+static void reduce_rz(lsb_hip_solver *sv, int gated) {
+  if (!sv->multi)
+    return;
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    lsb_k_reduce_final(s->d_parts2, s->np2, 2, s->d_scal + 1, 0, gated ? s->d_st : NULL, g_stream);
+  }
+  allreduce_scal(sv, 1, 2, gated);
+}
+
+/* how every init ends: (r.z, r.r) starts the run's state (not gated: the device state still holds the
+ * previous solve's status) */
+static void init_state(lsb_hip_solver *sv) {
+  reduce_rz(sv, 0);
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    lsb_k_pcg_init_state(s->d_st, sv->multi ? s->d_scal + 1 : s->d_parts2, sv->multi ? 1u : s->np2, sv->tol_run,
+                         (int)sv->o.maxit, g_stream);
+  }
+}
+
+/* ---- classic form, and the init of the two that fuse it (SUBWAVE, COL) ---- */
+static void classic_enqueue_init(lsb_hip_solver *sv, const double *d_b, double *d_x) {
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
     const size_t o = s->row_begin - sv->row_first;
+    lsb_k_pcg_init(s->n, d_b + o, DINV(s), d_x + o, s->d_r, s->d_pfull + s->row_begin, s->d_parts2, &s->np2,
+                   g_stream);
+  }
+  init_state(sv);
+}
+
+static void classic_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sample) {
+  spmv_pq(sv, sample);
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    const size_t o = s->row_begin - sv->row_first;
+    lsb_k_pcg_update_xr(s->n, s->d_pfull + s->row_begin, s->d_q, DINV(s), d_x + o, s->d_r, s->d_st, parity,
+                        sv->multi ? s->d_scal : s->d_parts_pq, sv->multi ? 1u : s->npq, s->d_parts2, &s->np2,
+                        g_stream);
+  }
+  reduce_rz(sv, 1);
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    lsb_k_pcg_update_p(s->n, s->d_r, DINV(s), s->d_pfull + s->row_begin, s->d_pfull + s->row_begin, s->d_st,
+                       parity, sv->multi ? s->d_scal + 1 : s->d_parts2, sv->multi ? 1u : s->np2, g_stream);
+  }
+}
+
+/* ---- GENERIC: PCG with z = M^-1 r as a vector (Chebyshev, block-Jacobi, FSAI, AMG) -------------
+ * The classic recurrences through the same sweeps: k_pcg_update_xr with a unit
+ * "diagonal" (its own r.r partial sums are superseded), the preconditioner's
+ * launches, k_dot2 for (r.z, r.r), k_pcg_update_p with z in the place of r. */
+static void gen_enqueue_init(lsb_hip_solver *sv, const double *d_b, double *d_x) {
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    const size_t o = s->row_begin - sv->row_first;
+    unsigned np2 = 0; /* (superseded by k_dot2's below) */
     /* x = 0, r = b (p = b for the moment) */
     lsb_k_pcg_init(s->n, d_b + o, NULL, 1.0, d_x + o, s->d_r, s->d_pfull + s->row_begin,
                    s->d_parts2, &np2, g_stream);
@@ -51,56 +173,41 @@ static void gen_enqueue_init(lsb_hip_solver *sv, const double *d_b, double *d_x)
     struct shard *s = &sv->sh[i];
     LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + s->row_begin, s->d_z, (size_t)s->n * sizeof(double),
                                hipMemcpyDeviceToDevice, g_stream)); /* p = z */
+    lsb_k_dot2(s->n, s->d_r, s->d_z, s->d_parts2, &s->np2, NULL, g_stream); /* (b.z, b.b) */
   }
-  gen_dot_and_reduce(sv, 0, &np2); /* (b.z, b.b) */
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    lsb_k_pcg_init_state(s->d_st, sv->multi ? s->d_scal + 1 : s->d_parts2, sv->multi ? 1u : np2,
-                         sv->tol_run, (int)sv->o.maxit, g_stream);
-  }
+  init_state(sv);
 }
 
 static void gen_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sample) {
-  unsigned npq = 0, np2 = 0;
-  if (sv->multi) {
-    exchange_and_spmv(sv, sample);
-    allreduce_pq(sv, 1, 0);
-  } else {
-    struct shard *s = &sv->sh[0];
-    if (sample >= 0)
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample], g_stream));
-    spmv_shard(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &npq, s->d_st);
-    if (sample >= 0) {
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 1], g_stream));
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 2], g_stream));
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 3], g_stream));
-    }
-  }
-  sv->nspmv++;
+  spmv_pq(sv, sample);
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
     const size_t o = s->row_begin - sv->row_first;
     lsb_k_pcg_update_xr(s->n, s->d_pfull + s->row_begin, s->d_q, NULL, 1.0, d_x + o, s->d_r, s->d_st,
-                        parity, sv->multi ? s->d_scal : s->d_parts_pq, sv->multi ? 1u : npq,
-                        s->d_parts2, &np2, g_stream);
-    s->np2 = np2;
+                        parity, sv->multi ? s->d_scal : s->d_parts_pq, sv->multi ? 1u : s->npq,
+                        s->d_parts2, &s->np2, g_stream);
   }
   precond_apply(sv, 1);
-  gen_dot_and_reduce(sv, 1, &np2);
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    lsb_k_dot2(s->n, s->d_r, s->d_z, s->d_parts2, &s->np2, s->d_st, g_stream);
+  }
+  reduce_rz(sv, 1);
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
     lsb_k_pcg_update_p(s->n, s->d_z, NULL, 1.0, s->d_pfull + s->row_begin, s->d_pfull + s->row_begin,
                        s->d_st, parity, sv->multi ? s->d_scal + 1 : s->d_parts2,
-                       sv->multi ? 1u : np2, g_stream);
+                       sv->multi ? 1u : s->np2, g_stream);
   }
 }
 
-/* FSAI-PCG of a launch-bound operator in three launches per iteration (hip_fsai.hip):
+/* ---- FSAI3: FSAI-PCG of a launch-bound operator in three launches per iteration (hip_fsai.hip):
  *   A  beta, stop test, p = z + beta p in the gather of S's rows, q = S p, p.q   (k_spmv_subwave_p)
  *   B  alpha, x += alpha p, r' = r - alpha q in the gather of G's rows, t = G r'  (k_fsai_xr_gr)
  *   C  z = G^T t, partial sums of (r'.z, r'.r')                                   (k_fsai_gt_dots)
  * p and r alternate between two buffers each; the last iteration of an enqueued run closes
- * with the stand-alone direction sweep and leaves r in the shard's own residual vector. */
+ * with the stand-alone direction sweep and leaves r in the shard's own residual vector.
+ * (Its init is GENERIC's.) */
 static void fsai_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int pos) {
   struct shard *s = &sv->sh[0];
   double *pb[2] = {s->d_pfull, s->d_p1}, *rb[2] = {s->d_r, s->d_r1};
@@ -113,7 +220,6 @@ static void fsai_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int p
                          s->np2, g_stream);
     sv->pcur ^= 1;
   }
-  sv->nspmv++;
   lsb_k_fsai_xr_gr(s->n, s->fs_g.offs, s->fs_g.cols, s->fs_g.vals, s->fs_g.lanes, pb[sv->pcur], s->d_q, d_x,
                    rb[sv->rcur], rb[sv->rcur ^ 1], s->d_fst, s->d_st, parity, s->d_parts_pq, s->npq, g_stream);
   sv->rcur ^= 1;
@@ -128,141 +234,28 @@ static void fsai_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int p
   }
 }
 
-static void pcg_enqueue_init(lsb_hip_solver *sv, const double *d_b, double *d_x) {
-  if (generic_precond(sv)) {
-    gen_enqueue_init(sv, d_b, d_x);
-    return;
-  }
-  if (use_cg1(sv)) {
-    cg1_enqueue_init(sv, d_b, d_x);
-    return;
-  }
-  unsigned np2 = 0;
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    const size_t o = s->row_begin - sv->row_first;
-    lsb_k_pcg_init(s->n, d_b + o, DINV(s), d_x + o, s->d_r, s->d_pfull + s->row_begin,
-                   s->d_parts2, &np2, g_stream);
-    if (!s->d_p1 && fuse_p(sv)) /* second direction buffer of the two-launch iteration */
-      s->d_p1 = shard_vec(s, s->n);
-    if (sv->multi)
-      lsb_k_reduce_final(s->d_parts2, np2, 2, s->d_scal + 1, 0, NULL, g_stream);
-  }
-  if (sv->multi) {
-    allreduce_scal(sv, 1, 2, 0); /* the device state still holds the previous solve's status */
-  }
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    if (sv->multi)
-      lsb_k_pcg_init_state(s->d_st, s->d_scal + 1, 1, sv->tol_run, (int)sv->o.maxit, g_stream);
-    else
-      lsb_k_pcg_init_state(s->d_st, s->d_parts2, np2, sv->tol_run, (int)sv->o.maxit, g_stream);
-  }
-}
-
-/* Launch-bound operators (one shard, sub-wavefront SpMV, classic form): the
- * direction update rides in the NEXT iteration's SpMV (k_spmv_subwave_p), two
+/* ---- SUBWAVE: launch-bound operators (one shard, sub-wavefront SpMV, classic form) -------------
+ * The direction update rides in the NEXT iteration's SpMV (k_spmv_subwave_p), two
  * launches per iteration; the two direction buffers alternate.  Only the last
  * iteration of an enqueued run closes with the stand-alone update, which also
- * brings the direction back into the gather vector. */
-/* 1 = the direction update rides in the next SpMV launch (the sub-wavefront form of launch-bound
- * operators).  The same fold was built for the slice-template form of a structured grid
+ * brings the direction back into the gather vector.
+ * The same fold was built for the slice-template form of a structured grid
  * (k_spmv_tmpl_p, round 3: the direction update's own pass over r and p disappears, 880 -> 800 MB
  * per iteration on the 10 M-row 5-point operator), measured -- 81.4 us where k_spmv_tmpl +
  * k_pcg_update_p take 40.4 + 40.4 (rocprofv3 means inside the solve, gpurun_out/r3_fuse3): no
  * gain, both SpMV-shaped launches run at 4.0 TB/s inside the solve -- and taken out again when
  * its 7-point instantiation turned out not to be repeatable run to run once the masked slots
  * came in (gpurun_out/r3_mask, tools/gpu_tmpl_diag3.py): DESIGN.md section 4. */
-int lsb_fuse_p_kind(const lsb_hip_solver *sv) {
-  /* (asked for every iteration that is enqueued: the two environment switches were looked at when the solver
-   * was made) */
-  const int no_fuse_p = sv->env_no_fuse_p, no_fuse_px = sv->env_no_fuse_px;
-  if (sv->multi || use_cg1(sv) || generic_precond(sv) || sv->sh[0].mixed || no_fuse_p)
-    return 0;
-  const struct shard *s = &sv->sh[0];
-  /* 2 = the z-column form of a 3-D stencil with a constant diagonal: direction update AND the x
-   * half of the first sweep ride in the next SpMV launch, the r half forms S p again instead of reading a
-   * stored q, x is updated every second iteration with two directions at once (k_pcg_col_px + k_pcg_col_r: 60
-   * instead of 88 bytes per row and iteration) */
-  if (s->sell_form == SELL_COL && s->dinv_uniform && s->c16.tmpl.nfar >= 1 && s->c16.tmpl.nfar <= 2 && s->row_begin == 0 &&
-      s->n == s->n_glob && sv->o.precond == LSB_PRECOND_JACOBI && !no_fuse_px)
-    return 2; /* (event-timed too: the sample brackets the launch that carries the SpMV) */
-  /* (not while SpMV launches are being event-timed: the fused launch has no SpMV of its own to
-   * bracket, and solve_core reads the sample events) */
-  return s->variant == LSB_SPMV_SUBWAVE && sv->o.sample_spmv <= 0;
-}
-static int fuse_p(const lsb_hip_solver *sv) { return lsb_fuse_p_kind(sv) != 0; }
-
-/* Bytes ONE iteration of the Krylov loop must move on shard 0: the SpMV's layout bytes
- * (lsb_hip_solver_spmv_layout_bytes) + every vector pass of the sweeps behind it.  Classic PCG:
- * k_pcg_update_xr reads x p q r and writes x r, k_pcg_update_p reads r p and writes p -- 9 passes,
- * + 2 reads of the inverse diagonal where it is a vector; the single-reduction form: 9 passes with
- * a constant diagonal (u = dc r never stored), else 11 + the diagonal.  0 where the iteration is
- * something else (GMRES, a polynomial / block / FSAI preconditioner, the one-launch and
- * two-launch forms of small operators, fp32 values, the multi-pass SpMV forms). */
-unsigned long long lsb_hip_solver_iteration_bytes(const lsb_hip_solver *sv) {
-  const struct shard *s = &sv->sh[0];
-  const unsigned long long sp = lsb_hip_solver_spmv_layout_bytes(sv), n8 = 8ull * s->n;
-  if (!sp || sv->o.krylov == LSB_KRYLOV_GMRES || generic_precond(sv) || s->mixed || sv->ps.use ||
-      lsb_fuse_p_kind(sv) == 1)
-    return 0;
-  if (lsb_fuse_p_kind(sv) == 2) /* k_pcg_col_px: r p x in, p' x out; k_pcg_col_r: p' r in, r out; the layout's
-                                   matrix-side bytes (sp less its x-in / y-out) in both */
-    return 2 * (sp - 2 * n8) + 15 * n8 / 2; /* (x and the stale direction only every second iteration: 6 and 3 passes) */
-  const unsigned vec = s->dinv_uniform ? 0u : 1u;
-  if (use_cg1(sv))
-    return sp + n8 * (sv->cg1_implicit ? 9u : 11u + vec);
-  return sp + n8 * (9u + 2u * vec);
-}
-
-static void fused_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int pos, int sample) {
+static void subwave_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int pos) {
   struct shard *s = &sv->sh[0];
   double *buf[2] = {s->d_pfull, s->d_p1};
-  unsigned np2 = s->np2;
-  if (lsb_fuse_p_kind(sv) == 2) {
-    /* z-column form: [S p | p' = dc r + beta p, x += alpha p, p'.(S p')] then [r -= alpha S p']; the x update of an
-     * iteration rides in the NEXT iteration's first launch, the run's last one is applied by k_pcg_xfix */
-    /* sampling: the launch that carries the SpMV, bracketed as pcg_enqueue_iter brackets a plain one; a run's
-     * first iteration (a plain SpMV launch) is marked in samp_skip and left out by pcg_run -- the figure is
-     * k_pcg_col_px's alone */
-    if (sample >= 0)
-      sv->samp_skip[sample] = (pos & 1) != 0;
-    if (sample >= 0 && !(pos & 1))
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample], g_stream));
-    if (pos & 1) { /* first of the run: the direction is in the gather vector, x is up to date */
-      sv->pcur = 0;
-      spmv_shard(s, buf[0], s->d_q, buf[0], s->d_parts_pq, &s->npq, s->d_st);
-    } else {
-      lsb_k_pcg_col_px(s->sp_grid, s->col.period, s->col.plan, s->col.items, s->n, &s->c16, s->d_r, buf[sv->pcur],
-                       buf[sv->pcur ^ 1], d_x, /* x updated by the run's even iterations, two steps at once */ parity == 0,
-                       s->dinv_const, s->d_parts_pq,
-                       &s->npq, s->d_st, parity ^ 1, s->d_parts2, np2, g_stream);
-      sv->pcur ^= 1;
-    }
-    if (sample >= 0 && !(pos & 1)) {
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 1], g_stream));
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 2], g_stream));
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 3], g_stream));
-    }
-    /* r -= alpha S p with S p formed again out of p (k_pcg_col_r): q never travels */
-    lsb_k_pcg_col_r(s->sp_grid, s->col.period, s->col.plan, s->col.items, s->n, &s->c16, buf[sv->pcur], s->d_r,
-                    s->dinv_const, s->d_st,
-                    parity, sv->pcur, /* x is two updates behind after an odd iteration */ parity != 0, s->d_parts_pq, s->npq,
-                    s->d_parts2, &s->np2, g_stream);
-    if (pos & 2) { /* last of the run: the pending x update, then the direction back into the gather vector */
-      lsb_k_pcg_xfix(s->n, buf[0], buf[1], d_x, s->d_st, g_stream);
-      lsb_k_pcg_update_p(s->n, s->d_r, DINV(s), buf[sv->pcur], buf[0], s->d_st, parity, s->d_parts2, s->np2,
-                         g_stream);
-    }
-    return;
-  }
   if (pos & 1) { /* first of the run: the direction is in the gather vector */
     sv->pcur = 0;
     spmv_shard(s, buf[0], s->d_q, buf[0], s->d_parts_pq, &s->npq, s->d_st);
   } else { /* beta, stop test and p = D^-1 r + beta p of the previous iteration, then S p */
     lsb_k_spmv_subwave_p(s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->lanes, s->d_r, DINV(s),
                          buf[sv->pcur], buf[sv->pcur ^ 1], s->d_q, s->d_parts_pq, &s->npq, s->d_st,
-                         parity ^ 1, s->d_parts2, np2, g_stream);
+                         parity ^ 1, s->d_parts2, s->np2, g_stream);
     sv->pcur ^= 1;
   }
   lsb_k_pcg_update_xr(s->n, buf[sv->pcur], s->d_q, DINV(s), d_x, s->d_r, s->d_st, parity,
@@ -272,100 +265,49 @@ static void fused_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int 
                        s->np2, g_stream);
 }
 
-/* One PCG iteration, enqueued.  sample >= 0: bracket the SpMV of shard 0 with
- * events 4*sample .. 4*sample+3.  pos: bit 0 = first, bit 1 = last iteration of
- * the run being enqueued. */
-static void pcg_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sample, int pos) {
-  if (fsai_three_launches(sv)) {
-    fsai_enqueue_iter(sv, d_x, parity, pos);
-    return;
+/* ---- COL: the z-column form of a 3-D stencil with a constant diagonal ----------------------------
+ * [S p | p' = dc r + beta p, x += alpha p, p'.(S p')] then [r -= alpha S p']: direction update AND the x half
+ * of the first sweep ride in the next SpMV launch, the r half forms S p again instead of reading a stored q,
+ * x is updated every second iteration with two directions at once (k_pcg_col_px + k_pcg_col_r: 60 instead of
+ * 88 bytes per row and iteration); the run's last pending x update is applied by k_pcg_xfix.  x goes in and
+ * out as 16-byte vectors: pcg_run gives an x that is not 16-byte aligned to the classic form.
+ * Sampling: the launch that carries the SpMV, bracketed as the classic form brackets a plain one; a run's
+ * first iteration (a plain SpMV launch) is marked in samp_skip and left out by pcg_run -- the figure is
+ * k_pcg_col_px's alone. */
+static void col_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int pos, int sample) {
+  struct shard *s = &sv->sh[0];
+  double *buf[2] = {s->d_pfull, s->d_p1};
+  if (sample >= 0)
+    sv->samp_skip[sample] = (pos & 1) != 0;
+  if (pos & 1) { /* first of the run: the direction is in the gather vector, x is up to date */
+    sv->pcur = 0;
+    spmv_shard(s, buf[0], s->d_q, buf[0], s->d_parts_pq, &s->npq, s->d_st);
+  } else {
+    sample_open(sv, sample);
+    lsb_k_pcg_col_px(s->sp_grid, s->col.period, s->col.plan, s->col.items, s->n, &s->c16, s->d_r, buf[sv->pcur],
+                     buf[sv->pcur ^ 1], d_x, /* x updated by the run's even iterations, two steps at once */ parity == 0,
+                     s->dinv_const, s->d_parts_pq, &s->npq, s->d_st, parity ^ 1, s->d_parts2, s->np2, g_stream);
+    sample_close(sv, sample);
+    sv->pcur ^= 1;
   }
-  if (generic_precond(sv)) {
-    gen_enqueue_iter(sv, d_x, parity, sample);
-    return;
-  }
-  if (use_cg1(sv)) {
-    cg1_enqueue_iter(sv, d_x, parity, sample);
-    return;
-  }
-  if (fuse_p(sv)) {
-    fused_enqueue_iter(sv, d_x, parity, pos, sample);
-    return;
-  }
-  unsigned npq = 0, np2 = 0;
-  if (sv->multi) {
-    exchange_and_spmv(sv, sample);
-    allreduce_pq(sv, 1, 0);
-  }
-  for (int i = 0; i < sv->nshard && !sv->multi; i++) {
-    struct shard *s = &sv->sh[i];
-    if (i == 0 && sample >= 0)
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample], g_stream));
-    spmv_shard(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &npq, s->d_st);
-    if (i == 0 && sample >= 0)
-    {
-      /* e1 closes the SpMV interval; e2,e3 bracket NOTHING: their distance is
-       * what one event marker costs in this very spot of the stream, and is
-       * subtracted from e0->e1 (an event pair around a kernel otherwise reads
-       * ~9 us longer than the kernel's duration in a rocprofv3 trace). */
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 1], g_stream));
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 2], g_stream));
-      LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 3], g_stream));
-    }
-  }
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    const size_t o = s->row_begin - sv->row_first;
-    lsb_k_pcg_update_xr(s->n, s->d_pfull + s->row_begin, s->d_q, DINV(s), d_x + o, s->d_r,
-                        s->d_st, parity, sv->multi ? s->d_scal : s->d_parts_pq,
-                        sv->multi ? 1u : npq, s->d_parts2, &np2, g_stream);
-    if (sv->multi)
-      lsb_k_reduce_final(s->d_parts2, np2, 2, s->d_scal + 1, 0, s->d_st, g_stream);
-  }
-  if (sv->multi)
-    allreduce_scal(sv, 1, 2, 1);
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    lsb_k_pcg_update_p(s->n, s->d_r, DINV(s), s->d_pfull + s->row_begin,
-                       s->d_pfull + s->row_begin, s->d_st, parity,
-                       sv->multi ? s->d_scal + 1 : s->d_parts2, sv->multi ? 1u : np2,
+  /* r -= alpha S p with S p formed again out of p (k_pcg_col_r): q never travels */
+  lsb_k_pcg_col_r(s->sp_grid, s->col.period, s->col.plan, s->col.items, s->n, &s->c16, buf[sv->pcur], s->d_r,
+                  s->dinv_const, s->d_st,
+                  parity, sv->pcur, /* x is two updates behind after an odd iteration */ parity != 0, s->d_parts_pq, s->npq,
+                  s->d_parts2, &s->np2, g_stream);
+  if (pos & 2) { /* last of the run: the pending x update, then the direction back into the gather vector */
+    lsb_k_pcg_xfix(s->n, buf[0], buf[1], d_x, s->d_st, g_stream);
+    lsb_k_pcg_update_p(s->n, s->d_r, DINV(s), buf[sv->pcur], buf[0], s->d_st, parity, s->d_parts2, s->np2,
                        g_stream);
   }
 }
 
-/* ---- single-reduction CG (LSB_KRYLOV_PCG1): see k_cg1_update -------------- */
-static int use_cg1(const lsb_hip_solver *sv) {
-  if (generic_precond(sv)) /* z = M^-1 r as a vector: the classic form, see gen_enqueue_iter */
-    return 0;
-  if (sv->o.krylov == LSB_KRYLOV_PCG1)
-    return 1;
-  if (sv->o.krylov != LSB_KRYLOV_AUTO)
-    return 0;
-  /* measured on one GPU: no gain for small operators (tests/xn3b_A_18.txt: 390 vs
-   * 400 solves/s, the fused sweep is as long as the two it replaces) and +6 % time
-   * on the 10M-row operator where the diagonal is a vector (96 n vs 88 n bytes; round 3, general
-   * values: 251 against 236-241 us per iteration); what it saves there is a collective.
-   * With ONE constant diagonal (u = c r never stored) it moves the classic form's 72 n in two
-   * launches instead of three; since its sweep loads the gather vector the plain way
-   * (k_cg1_update, round 3: the SpMV behind it 40 -> 24 us on config 3) it is level with the
-   * classic form on one GPU -- config 3 through bench.py 136.8-138.0 against 136.0-139.8 us per
-   * iteration, config 4 1186-1188 against 1182-1191 (tools/gpu_krylov_ab.sh) -- so one shard
-   * keeps the classic form, the reference's algorithm as written. */
-  return sv->multi;
-}
-int lsb_hip_solver_single_reduction(const lsb_hip_solver *sv) {
-  return sv->o.krylov != LSB_KRYLOV_GMRES && use_cg1(sv);
-}
-
+/* ---- CG1: single-reduction CG (LSB_KRYLOV_PCG1), see k_cg1_update -------------- */
 static void cg1_enqueue_init(lsb_hip_solver *sv, const double *d_b, double *d_x) {
   sv->ar_fold = can_fold_allreduce(sv), sv->ar_pending = 0, sv->fold_next = 0;
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
     const size_t o = s->row_begin - sv->row_first, bytes = (size_t)s->n * sizeof(double);
-    if (!s->d_p1) {
-      s->d_p1 = shard_vec(s, s->n);
-      s->d_s1 = shard_vec(s, s->n);
-    }
     /* x = 0, r = b, u = D^-1 b (into the gather vector), partials (r.u, b.b);
      * implicit u (constant diagonal): r itself goes into the gather vector and
      * u = c b lands in a scratch nobody reads */
@@ -377,28 +319,9 @@ static void cg1_enqueue_init(lsb_hip_solver *sv, const double *d_b, double *d_x)
                      s->d_parts2, &s->np2, g_stream);
     LSB_CHK_HIP(hipMemsetAsync(s->d_p1, 0, bytes, g_stream));
     LSB_CHK_HIP(hipMemsetAsync(s->d_s1, 0, bytes, g_stream));
-    if (sv->multi)
-      lsb_k_reduce_final(s->d_parts2, s->np2, 2, s->d_scal + 1, 0, NULL, g_stream);
   }
-  if (sv->multi) {
-    allreduce_scal(sv, 1, 2, 0); /* the device state still holds the previous solve's status */
-  }
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    if (sv->multi)
-      lsb_k_pcg_init_state(s->d_st, s->d_scal + 1, 1, sv->tol_run, (int)sv->o.maxit, g_stream);
-    else
-      lsb_k_pcg_init_state(s->d_st, s->d_parts2, s->np2, sv->tol_run, (int)sv->o.maxit, g_stream);
-  }
-  if (sv->multi)
-    exchange_and_spmv(sv, -1); /* w = S u, partials w.u */
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    if (!sv->multi)
-      spmv_shard(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &s->npq, s->d_st);
-  }
-  if (sv->multi)
-    allreduce_pq(sv, 1, 0);
+  init_state(sv);
+  spmv_pq(sv, -1); /* w = S u, partials w.u */
 }
 
 static void cg1_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sample) {
@@ -424,20 +347,11 @@ static void cg1_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sa
   if (sv->multi) {
     sv->fold_next = sv->ar_fold == 2;
     exchange_and_spmv(sv, sample);
-  }
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    if (!sv->multi) {
-      if (sample >= 0)
-        LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample], g_stream));
-      spmv_shard(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &s->npq,
-                 s->d_st);
-      if (sample >= 0) {
-        LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 1], g_stream));
-        LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 2], g_stream));
-        LSB_CHK_HIP(hipEventRecord(sv->ev[4 * sample + 3], g_stream));
-      }
-    }
+  } else {
+    struct shard *s = &sv->sh[0];
+    sample_open(sv, sample);
+    spmv_shard(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &s->npq, s->d_st);
+    sample_close(sv, sample);
   }
   /* w.u, r.u, r.r in ONE collective -- over the direct path sent by a launch that waits
    * for nobody (or by the SpMV's last workgroup) and collected by the next k_cg1_update */
@@ -449,6 +363,74 @@ static void cg1_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sa
     allreduce_pq(sv, 3, 1);
 }
 
+/* ---- one dispatch ---- */
+static void pcg_enqueue_init(lsb_hip_solver *sv, enum pcg_form form, const double *d_b, double *d_x) {
+  form_vecs(sv, sv->form);
+  switch (form) {
+  case PCG_CG1:
+    cg1_enqueue_init(sv, d_b, d_x);
+    break;
+  case PCG_GENERIC:
+  case PCG_FSAI3:
+    gen_enqueue_init(sv, d_b, d_x);
+    break;
+  default: /* CLASSIC, SUBWAVE, COL */
+    classic_enqueue_init(sv, d_b, d_x);
+  }
+}
+
+/* One PCG iteration, enqueued.  sample >= 0: bracket the SpMV of shard 0 with
+ * events 4*sample .. 4*sample+3.  pos: bit 0 = first, bit 1 = last iteration of
+ * the run being enqueued. */
+static void pcg_enqueue_iter(lsb_hip_solver *sv, enum pcg_form form, double *d_x, int parity, int sample, int pos) {
+  switch (form) {
+  case PCG_FSAI3:
+    fsai_enqueue_iter(sv, d_x, parity, pos);
+    break;
+  case PCG_GENERIC:
+    gen_enqueue_iter(sv, d_x, parity, sample);
+    break;
+  case PCG_CG1:
+    cg1_enqueue_iter(sv, d_x, parity, sample);
+    break;
+  case PCG_SUBWAVE:
+    subwave_enqueue_iter(sv, d_x, parity, pos);
+    break;
+  case PCG_COL:
+    col_enqueue_iter(sv, d_x, parity, pos, sample);
+    break;
+  default: /* CLASSIC */
+    classic_enqueue_iter(sv, d_x, parity, sample);
+  }
+}
+
+/* Bytes ONE iteration of the Krylov loop must move on shard 0: the SpMV's layout bytes
+ * (lsb_hip_solver_spmv_layout_bytes) + every vector pass of the sweeps behind it.  Classic PCG:
+ * k_pcg_update_xr reads x p q r and writes x r, k_pcg_update_p reads r p and writes p -- 9 passes,
+ * + 2 reads of the inverse diagonal where it is a vector; the single-reduction form: 9 passes with
+ * a constant diagonal (u = dc r never stored), else 11 + the diagonal.  0 where the iteration is
+ * something else (GMRES, a polynomial / block / FSAI preconditioner, the one-launch and
+ * two-launch forms of small operators, fp32 values, the multi-pass SpMV forms). */
+unsigned long long lsb_hip_solver_iteration_bytes(const lsb_hip_solver *sv) {
+  const struct shard *s = &sv->sh[0];
+  const unsigned long long sp = lsb_hip_solver_spmv_layout_bytes(sv), n8 = 8ull * s->n;
+  const unsigned vec = s->dinv_uniform ? 0u : 1u;
+  if (!sp || s->mixed || sv->ps.use)
+    return 0;
+  switch (sv->form) {
+  case PCG_CLASSIC:
+    return sp + n8 * (9u + 2u * vec);
+  case PCG_CG1:
+    return sp + n8 * (sv->cg1_implicit ? 9u : 11u + vec);
+  case PCG_COL: /* k_pcg_col_px: r p x in, p' x out; k_pcg_col_r: p' r in, r out; the layout's matrix-side bytes
+                   (sp less its x-in / y-out) in both */
+    return 2 * (sp - 2 * n8) + 15 * n8 / 2; /* (x and the stale direction only every second iteration: 6 and 3 passes) */
+  default:
+    return 0;
+  }
+}
+
+int lsb_hip_solver_single_reduction(const lsb_hip_solver *sv) { return sv->form == PCG_CG1; }
 static int auto_chunk(const lsb_hip_solver *sv) {
   /* aim at ~0.3 ms of device work per chunk (at least 8 iterations): the poll
    * is pipelined one chunk ahead, so small chunks cost nothing while running
@@ -601,8 +583,9 @@ void tune_blas1_nt(lsb_hip_solver *sv) {
 }
 
 /* hipGraph of `iters` PCG iterations writing to d_x; two cached entries (the
- * hinted whole-solve graph and the small continuation chunk). */
-static hipGraphExec_t get_graph(lsb_hip_solver *sv, int iters, double *d_x) {
+ * hinted whole-solve graph and the small continuation chunk).  The form a run takes
+ * depends on the solver and d_x alone: the key holds it. */
+static hipGraphExec_t get_graph(lsb_hip_solver *sv, enum pcg_form form, int iters, double *d_x) {
   for (int i = 0; i < LSB_NGRAPH; i++)
     if (sv->gcache[i].exec && sv->gcache[i].iters == iters && sv->gcache[i].x == d_x)
       return sv->gcache[i].exec;
@@ -613,7 +596,7 @@ static hipGraphExec_t get_graph(lsb_hip_solver *sv, int iters, double *d_x) {
   hipGraph_t g;
   LSB_CHK_HIP(hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal));
   for (int i = 0; i < iters; i++)
-    pcg_enqueue_iter(sv, d_x, i & 1, -1, (i == 0) | ((i == iters - 1) << 1));
+    pcg_enqueue_iter(sv, form, d_x, i & 1, -1, (i == 0) | ((i == iters - 1) << 1));
   LSB_CHK_HIP(hipStreamEndCapture(g_stream, &g));
   LSB_CHK_HIP(hipGraphInstantiate(&sv->gcache[slot].exec, g, NULL, NULL, 0));
   LSB_CHK_HIP(hipGraphDestroy(g));
@@ -810,6 +793,8 @@ static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct ls
   const int sampling = sv->o.sample_spmv > 0;
   memset(sv->samp_skip, 0, sizeof sv->samp_skip);
   const int use_graph = sv->o.use_graph && !sv->multi && !sampling;
+  /* k_pcg_col_px loads and stores x as 16-byte vectors: any other x runs the classic form */
+  const enum pcg_form form = sv->form == PCG_COL && ((uintptr_t)d_x & 15) ? PCG_CLASSIC : sv->form;
   int nsamp = 0;
   unsigned done_iters = 0;
   struct lsb_pcg_state *hst = sv->h_st; /* two pinned slots */
@@ -842,14 +827,14 @@ static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct ls
   do {                                                                         \
     const int cnt_ = (count);                                                  \
     if (use_graph) {                                                           \
-      LSB_CHK_HIP(hipGraphLaunch(get_graph(sv, cnt_, d_x), g_stream));         \
+      LSB_CHK_HIP(hipGraphLaunch(get_graph(sv, form, cnt_, d_x), g_stream));   \
     } else {                                                                   \
       for (int i_ = 0; i_ < cnt_; i_++) {                                      \
         int smp_ = -1;                                                         \
         if (sampling && nsamp < MAX_SAMPLES &&                                 \
             ((done_iters + (unsigned)i_) % (unsigned)sv->o.sample_spmv) == 0)  \
           smp_ = nsamp++;                                                      \
-        pcg_enqueue_iter(sv, d_x, i_ & 1, smp_, (i_ == 0) | ((i_ == cnt_ - 1) << 1)); \
+        pcg_enqueue_iter(sv, form, d_x, i_ & 1, smp_, (i_ == 0) | ((i_ == cnt_ - 1) << 1)); \
       }                                                                        \
     }                                                                          \
     done_iters += (unsigned)cnt_;                                              \
@@ -862,7 +847,7 @@ static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct ls
     LSB_CHK_HIP(hipEventRecord(sv->ev_poll[slot], g_stream));                  \
   } while (0)
 
-  pcg_enqueue_init(sv, d_b, d_x);
+  pcg_enqueue_init(sv, form, d_b, d_x);
   int fin = -1; /* slot holding the final state */
   if (*hint > 0) {
     /* graphs beyond ~1k iterations cost more to build than they save */
@@ -1030,7 +1015,7 @@ int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
   r.seconds = wall_seconds() - t0;
   {
     const unsigned m = sv->o.precond == LSB_PRECOND_CHEBYSHEV ? (unsigned)sv->cheb_m : 0u;
-    r.spmvs = r.iters * (1u + m) + (1u + r.corrections) * (m + (use_cg1(sv) || sv->ps.use ? 1u : 0u)) +
+    r.spmvs = r.iters * (1u + m) + (1u + r.corrections) * (m + (sv->form == PCG_CG1 || sv->ps.use ? 1u : 0u)) +
               (r.true_relres >= 0.0 ? 1u + r.corrections : 0u);
   }
   if (res)

@@ -383,24 +383,11 @@ static void op_apply(lsb_hip_solver *sv, int which_z, double *const *y, int gate
 #define CHEB_SAFETY 1.1
 #define CHEB_RATIO 30.0
 
-/* FSAI on a launch-bound operator (everything sub-wavefront kernels, one shard): the iteration
- * runs in three launches (hip_fsai.hip, hip_pcg.c) */
-int fsai_three_launches(const lsb_hip_solver *sv) {
-  const struct shard *s = &sv->sh[0];
-  return sv->o.precond == LSB_PRECOND_FSAI && !sv->multi && !s->mixed && s->variant == LSB_SPMV_SUBWAVE &&
-         s->fs_g.variant == LSB_SPMV_SUBWAVE && s->fs_gt.variant == LSB_SPMV_SUBWAVE && sv->o.sample_spmv <= 0 &&
-         sv->o.krylov != LSB_KRYLOV_PCG1 && !getenv("LSBENCH_HIP_NO_FSAI_FUSE");
-}
-
 void precond_setup(lsb_hip_solver *sv) {
   if (!generic_precond(sv))
     return;
-  if (sv->o.precond == LSB_PRECOND_FSAI) { /* buffers of the three-launch iteration */
-    struct shard *s = &sv->sh[0];
-    if (!s->d_p1)
-      s->d_p1 = shard_vec(s, s->n);
-    s->d_r1 = shard_vec(s, s->n);
-  }
+  if (sv->o.precond == LSB_PRECOND_FSAI) /* buffers of the three-launch iteration */
+    form_vecs(sv, PCG_FSAI3);
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
     /* z lives in a gather vector of its own: Chebyshev multiplies it by S */
@@ -540,7 +527,6 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
       }
       for (int i = 0; i < sv->nshard; i++)
         sv->sh[i].d_pfull = keep[i];
-      sv->nspmv++;
     }
     return;
   }
@@ -555,7 +541,6 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
     w[i] = sv->sh[i].d_q;
   for (int k = 0; k < sv->cheb_m; k++) {
     op_apply(sv, 1, w, 1);
-    sv->nspmv++;
     for (int i = 0; i < sv->nshard; i++) {
       struct shard *s = &sv->sh[i];
       lsb_k_cheb_step(s->n, s->d_r, s->d_q, DINV(s), sv->cheb_a[k], sv->cheb_b[k], s->d_chd, s->d_z,
@@ -567,7 +552,7 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
 void precond_free_shard(struct shard *s) {
   lsb_hip_free(s->d_binv), lsb_hip_free(s->d_bjpart), shard_vec_free(s, s->d_zfull), shard_vec_free(s, s->d_chd);
   shard_vec_free(s, s->d_zfull2);
-  fsai_free_csr(&s->fs_g), fsai_free_csr(&s->fs_gt), shard_vec_free(s, s->d_fst), shard_vec_free(s, s->d_r1);
+  fsai_free_csr(&s->fs_g), fsai_free_csr(&s->fs_gt), shard_vec_free(s, s->d_fst);
   amg_free(s);
 }
 

@@ -592,7 +592,7 @@ void shard_free(struct shard *s) {
   sell32_free(&s->sell), c16_free(&s->c16), col_free(&s->col);
   shard_vec_free(s, s->d_dinv), shard_vec_free(s, s->d_r);
   shard_vec_free(s, s->d_q), shard_vec_free(s, s->d_pfull), lsb_hip_free(s->d_parts_pq);
-  shard_vec_free(s, s->d_p1), shard_vec_free(s, s->d_s1);
+  shard_vec_free(s, s->d_p1), shard_vec_free(s, s->d_s1), shard_vec_free(s, s->d_r1);
   lsb_hip_free(s->d_parts2), lsb_hip_free(s->d_st), lsb_hip_free(s->d_st_aux);
   precond_free_shard(s);
   lsb_hip_free(s->d_slab); /* behind everything that may point into it */
@@ -612,7 +612,6 @@ lsb_hip_solver *solver_alloc(int nshard, const struct lsb_hip_opts *o) {
   sv->sh = lsb_calloc(struct shard, nshard);
   sv->o = *o;
   LSB_CHK_HIP(hipHostMalloc((void **)&sv->h_st, 2 * sizeof(struct lsb_pcg_state), 0));
-  sv->env_no_fuse_p = getenv("LSBENCH_HIP_NO_FUSE_P") != NULL, sv->env_no_fuse_px = getenv("LSBENCH_HIP_NO_FUSE_PX") != NULL;
   return sv;
 }
 
@@ -656,6 +655,7 @@ void solver_finish_setup(lsb_hip_solver *sv) {
   }
   tune_blas1_nt(sv);
   precond_setup(sv);
+  sv->form = pcg_choose_form(sv);
   sv->overlap_on = -1;
   p2p_setup(sv);
   overlap_setup(sv);
@@ -921,7 +921,7 @@ int lsb_hip_solver_overlap(const lsb_hip_solver *s, double us[2]) {
     us[0] = s->overlap_us[0], us[1] = s->overlap_us[1];
   return can_overlap(s);
 }
-int lsb_hip_solver_fused_p(const lsb_hip_solver *s) { return lsb_fuse_p_kind(s); }
+int lsb_hip_solver_fused_p(const lsb_hip_solver *s) { return s->form == PCG_COL ? 2 : s->form == PCG_SUBWAVE; }
 int lsb_hip_solver_blas1_nt(const lsb_hip_solver *s) { return s->nt_mask; }
 unsigned long long lsb_hip_solver_spmv_layout_bytes(const lsb_hip_solver *s) {
   const struct shard *h = &s->sh[0];
@@ -1165,11 +1165,9 @@ static void time_spmv(lsb_hip_solver *sv, struct shard *s) {
     if (!(s->sp_flags & LSB_SP_NT))
       ms *= 1.03f;
     /* the z-column walk is also what the two-launch iteration runs on (k_pcg_col_px + k_pcg_col_r: 8 vector passes
-     * instead of 11): where that form will apply -- one shard, Jacobi with a constant diagonal, classic PCG, fp64 --
-     * a flavour without it has to beat the walk by 15 % as an SpMV to be worth the three launches */
-    if (s->sell_form == SELL_COL && sv->nshard == 1 && !sv->dist && !sv->multi && s->dinv_uniform &&
-        !s->mixed && o->precond == LSB_PRECOND_JACOBI && (o->krylov == LSB_KRYLOV_PCG || o->krylov == LSB_KRYLOV_AUTO) &&
-        !sv->env_no_fuse_px)
+     * instead of 11): where that form will apply (pcg_choose_form: one shard, Jacobi with a constant diagonal,
+     * classic PCG, fp64) a flavour without it has to beat the walk by 15 % as an SpMV to be worth the three launches */
+    if (pcg_choose_form(sv) == PCG_COL)
       ms *= 0.85f;
     if (ms < best)
       best = ms, bf = s->sp_flags, bv = s->variant, bg = s->sp_grid, bp = s->sp_period;

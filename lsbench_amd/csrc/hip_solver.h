@@ -7,7 +7,7 @@
  *                    timing pass, create / destroy
  *   hip_dist.c       what sharded solves add: exchange, all-reduce, overlap,
  *                    the direct xGMI path's set-up
- *   hip_pcg.c        PCG / single-reduction PCG iteration and the host loop
+ *   hip_pcg.c        PCG iteration forms (one chosen per solver) and the host loop
  *   hip_gmres_drv.c  GMRES(m) driver
  * Nothing here is part of the C-ABI (include/lsbench_hip.h).
  */
@@ -56,6 +56,16 @@ struct halo_split {
 /* the sliced-ELL kernel a shard's SpMV runs (tune_spmv resolves it from the variant, the flags and the
  * copies that exist; sell_launch, the getters, the fused PCG and Chebyshev forms read it) */
 enum { SELL_NONE, SELL_32, SELL_16, SELL_TMPL, SELL_COL };
+/* the PCG iteration a solver runs (pcg_choose_form picks it once, at creation; hip_pcg.c) */
+enum pcg_form {
+  PCG_NONE,    /* GMRES: no PCG iteration */
+  PCG_CLASSIC, /* SpMV, k_pcg_update_xr, k_pcg_update_p (one shard or many) */
+  PCG_SUBWAVE, /* k_spmv_subwave_p + k_pcg_update_xr: the direction update rides in the next SpMV */
+  PCG_COL,     /* k_pcg_col_px + k_pcg_col_r on the z-column plan (+ k_pcg_xfix at a run's end) */
+  PCG_CG1,     /* single reduction: k_cg1_update + SpMV */
+  PCG_GENERIC, /* the classic sweeps around precond_apply (z = M^-1 r as a vector) */
+  PCG_FSAI3,   /* FSAI in three launches: k_spmv_subwave_p, k_fsai_xr_gr, k_fsai_gt_dots */
+};
 
 struct shard {
   /* ONE allocation for the vectors the iteration streams (r, q, the gather vector, the Jacobi
@@ -134,7 +144,9 @@ struct shard {
     unsigned long long bytes;  /* matrix-side bytes one launch of the walk streams */
   } col;
   double *d_dinv, *d_r, *d_q, *d_pfull;
-  double *d_p1, *d_s1; /* single-reduction CG: p and s = S p (pfull then holds u) */
+  /* the forms' own vectors (form_vecs): the second direction buffer of the fused and FSAI-3 forms, or the
+   * single-reduction form's p (pfull then holds u); its s = S p */
+  double *d_p1, *d_s1;
   unsigned npq, np2;   /* partial counts of the SpMV / sweep launches */
   const double *ar2_parts; /* sweep partials the next all-reduce folds in */
   unsigned ar2_n, ar2_width;
@@ -167,7 +179,7 @@ struct shard {
     unsigned long long nnz;
   } fs_g, fs_gt;
   double *d_fst;     /* t = G r */
-  double *d_r1;      /* the three-launch iteration's second residual buffer */
+  double *d_r1;      /* the three-launch iteration's second residual buffer (form_vecs) */
   unsigned fs_maxrow; /* longest row of the pattern */
   /* AMG (LSB_PRECOND_AMG): the hierarchy on the device, z = one V-cycle (hip_amg.hip) */
   struct amg_dev {
@@ -238,13 +250,12 @@ struct lsb_hip_solver {
   /* single-reduction PCG without the vector u = D^-1 r: every shard of every
    * rank has the same constant Jacobi diagonal (k_cg1_update<UI>) */
   int cg1_implicit;
+  enum pcg_form form; /* the PCG iteration this solver runs (pcg_choose_form) */
   int pcur, rcur; /* launch-bound fused paths: which direction / residual buffer is current */
-  int env_no_fuse_p, env_no_fuse_px; /* LSBENCH_HIP_NO_FUSE_P / _NO_FUSE_PX at creation (tests compare the forms) */
   int nt_mask;    /* which operands of the BLAS-1 sweeps are loaded nontemporal (tune_blas1_nt) */
 #define LSB_CHEB_MAX 32
   int cheb_m, cheb_fused; /* fused: the steps ride in the SpMV's epilogue (one shard, 16-bit sliced-ELL) */
   double cheb_lmin, cheb_lmax, cheb_c0, cheb_a[LSB_CHEB_MAX], cheb_b[LSB_CHEB_MAX];
-  unsigned nspmv; /* SpMV launches (per shard) of the solve being enqueued */
   /* launch-bound operators: the whole solve as one persistent launch (hip_persist.hip) */
   struct {
     int ok, use;          /* qualifies / chosen */
@@ -274,7 +285,6 @@ void lsb_k_fsai_xr_gr(unsigned n, const int *goffs, const int *gcols, const doub
 void lsb_k_fsai_gt_dots(unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
                         const double *t, double *z, const double *r, double *partials2, unsigned *npartials,
                         const struct lsb_pcg_state *st, void *stream);
-LSB_INTERNAL int fsai_three_launches(const lsb_hip_solver *sv);
 /* hip_cdna4.c */
 LSB_INTERNAL double wall_seconds(void);
 /* Leave the process from a state in which a stream of this process may never drain (a hung
@@ -314,7 +324,11 @@ LSB_INTERNAL void allreduce_pq_contribute(lsb_hip_solver *sv);
 LSB_INTERNAL void exchange_and_spmv(lsb_hip_solver *sv, int sample);
 LSB_INTERNAL double true_resid2(lsb_hip_solver *sv, const double *d_b, const double *d_x);
 /* hip_pcg.c */
-LSB_INTERNAL int lsb_fuse_p_kind(const lsb_hip_solver *sv);
+LSB_INTERNAL enum pcg_form pcg_choose_form(const lsb_hip_solver *sv);
+LSB_INTERNAL void form_vecs(lsb_hip_solver *sv, enum pcg_form f);
+/* sample k >= 0: events 4k, 4k+1 around shard 0's SpMV (and the bare pair 4k+2, 4k+3); k < 0: nothing */
+LSB_INTERNAL void sample_open(lsb_hip_solver *sv, int k);
+LSB_INTERNAL void sample_close(lsb_hip_solver *sv, int k);
 LSB_INTERNAL void tune_blas1_nt(lsb_hip_solver *sv);
 LSB_INTERNAL void drop_graphs(lsb_hip_solver *sv);
 LSB_INTERNAL void persist_setup(lsb_hip_solver *sv);

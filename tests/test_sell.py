@@ -278,7 +278,9 @@ def test_two_launch_column_iteration(hip, monkeypatch, spec, kmax):
     iteration's bookkeeping), launches and hipGraph replay, second solves on the first one's hint
     -- and every solve bit for bit run to run; converged solves against the oracle's PCG.  7-point
     grids (two far slots per side: the +-line operands formed a second time) and 5-point grids whose
-    lines are whole slices (one far slot: everything out of registers)."""
+    lines are whole slices (one far slot: everything out of registers).  k_pcg_col_px moves x as 16-byte
+    vectors: an x only 8-byte aligned (solve_dev into a tensor slice) runs the three-launch form."""
+    import torch
     monkeypatch.setenv("LSBENCH_HIP_COL_K", str(kmax))
     A = hip.lsbench_matrix_synth(spec)
     b = O.rhs(A.nrows)
@@ -302,6 +304,18 @@ def test_two_launch_column_iteration(hip, monkeypatch, spec, kmax):
             if maxit != 20000:
                 assert r.iters == maxit
             out[(fused, graph, maxit)] = (x, int(r.iters), r.relres)
+    monkeypatch.delenv("LSBENCH_HIP_NO_FUSE_PX")
+    d_b = torch.from_numpy(b).to("cuda:0")
+    for graph in (0, 1):
+        s = hip.Solver(A, hip.default_opts(op_mode=hip.OP_RAW, spmv_variant=hip.SPMV_SELL, tol=1e-10,
+                                           spmv_tune=6 | 64 | 256, use_graph=graph))
+        d_x = torch.full((A.nrows + 1,), float("nan"), dtype=torch.float64, device="cuda:0")[1:]
+        assert s.fused_p == 2 and d_x.data_ptr() % 16 == 8
+        r = s.solve_dev(d_b, d_x)
+        s.destroy()
+        ref = out[(0, graph, 20000)]
+        assert r.status == hip.STATUS_CONVERGED and r.iters == ref[1]
+        assert np.linalg.norm(d_x.cpu().numpy() - ref[0]) <= 1e-9 * np.linalg.norm(ref[0])
     for (fused, graph, maxit), (x, it, rel) in out.items():
         ref = out[(0, 0, maxit)] if (0, 0, maxit) in out else out[(0, 1, maxit)]
         assert abs(it - ref[1]) <= (1 if maxit == 20000 else 0), (fused, graph, maxit)
