@@ -548,6 +548,8 @@ int lsb_tmpl_check(const struct lsb_sell *S, const struct lsb_sell_vc *V, const 
  * of it (4 waves per workgroup, 8 XCDs) -- what the walk directions are planned against */
 #define LSB_TMPL_COL_GRID(nfar) ((nfar) >= 2 ? 768u : 1280u)
 #define LSB_TMPL_COL_TURN(nfar) (4u * LSB_TMPL_COL_GRID(nfar) / 8u)
+/* the sliced-ELL, template and z-column SpMV launchers' grid where none is asked for */
+#define LSB_SELL_GRID 1536u
 /* the device plan: xbeg[9] at [0, 9), [LSB_TMPL_COL_DOWN] = the offset in words of the direction bits
  * (0: none), the items from word 16, the bits behind them */
 #define LSB_TMPL_COL_DOWN 9

@@ -1,5 +1,5 @@
 // Device side of the direct-xGMI all-reduce (hip_p2p.hip), shared with the
-// kernels it can be folded into (hip_kernels.hip): the CONTRIBUTE phase --
+// kernels it can be folded into (hip_kernels.hip, hip_sweeps.hip): the CONTRIBUTE phase --
 // reduce this rank's partial sums in a fixed order, store the 1-3 results into
 // slot [epoch & 1][rank] of every peer's mailbox -- runs either in
 // k_p2p_allreduce or as the tail of the SpMV launch that wrote the partial

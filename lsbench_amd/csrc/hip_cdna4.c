@@ -9,7 +9,7 @@
  * back, CSV record -- with a Jacobi-preconditioned CG (the Krylov+Jacobi
  * semantics of src/ginkgo.cpp:55-69,91-99: x reset to the initial guess
  * before every trial, reset not timed ... here the reset is fused into the
- * first sweep) made of the hand-written kernels in hip_kernels.hip instead of
+ * first sweep) made of the hand-written kernels in hip_kernels.hip and hip_sweeps.hip instead of
  * a vendor library call.
  *
  * The operator is what the reference's CHOLMOD path factorises,

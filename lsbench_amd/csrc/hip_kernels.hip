@@ -1,4 +1,4 @@
-// gfx950 (MI355X, CDNA4) kernels of the lsbench HIP backend + their C-ABI
+// gfx950 (MI355X, CDNA4) SpMV kernels of the lsbench HIP backend + their C-ABI
 // launchers ("the shim").  Host code (hip_cdna4.c, plain C) never sees a
 // kernel symbol, only the extern "C" lsb_k_* functions at the bottom.
 //
@@ -6,25 +6,16 @@
 // backend hands its CSR to a third-party library; the
 // nearest call site is the Krylov+Jacobi apply of src/ginkgo.cpp:55-69,91-99.
 // Kernel inventory = SURVEY.md section 8 (a2):
-//   a2-1  spmv (adaptive row-blocked / sub-wavefront / scalar), fused p.q
-//   a2-2  dot, nrm2           two-stage, fixed-order => run-to-run identical
-//   a2-3  axpy, xpay          scalars read from HBM, no host sync
-//   a2-4  jacobi setup/apply/sweep
-//   a2-5  fused PCG sweeps    (x,r update + r.z + r.r) and (p update)
+//   a2-1  spmv (adaptive row-blocked / sub-wavefront / scalar / sliced-ELL /
+//         slice templates / z-columns / binned), fused p.q; the two-launch PCG
+//         iteration's kernels, which walk the same z-columns
+//   a2-2 .. a2-5  (dot, axpy, Jacobi, the fused PCG sweeps): hip_sweeps.hip
 //
 // Everything here is HBM-bandwidth bound (0.125 flop/B for a 5-point row):
 // 64-wide wavefronts, coalesced 8-16 B/lane streams, LDS staging of the
 // per-non-zero products, XCD-contiguous work assignment so that the x-vector
 // window a row block gathers from is re-used out of one XCD's L2.  No MFMA.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-
-#include "hip_ar.h"
-#include "lsb_impl.h"
-
-#include "hip_wg.h"
-static_assert(WG == AR_WG, "the folded all-reduce phases assume this workgroup size");
+#include "hip_kcommon.h"
 
 // End of an SpMV launch with the fused dot: the workgroup's partial sum goes to
 // partials[blockIdx.x]; with a tail (sharded solve over the direct xGMI path)
@@ -254,9 +245,6 @@ __global__ __launch_bounds__(WG) void k_spmv_subwave(
 // the fly for every gathered column (three gathers of vectors that sit in L2)
 // and stored, for the rows of this workgroup, into the OTHER direction buffer.
 // At a few thousand rows a launch costs more than all of that.
-__device__ __forceinline__ double pnew_of(double d, double r, double beta, double p) {
-  return __fma_rn(beta, p, d * r);
-}
 template <int L>
 __global__ __launch_bounds__(WG) void k_spmv_subwave_p(
     unsigned n, unsigned rows_per_wg, const int *__restrict__ offs,
@@ -346,652 +334,6 @@ __global__ __launch_bounds__(WG) void k_spmv_scalar(
       partials[w] = d[0];
   }
 }
-
-// --------------------------------------------------------------------------
-// a2-2  second stage of every reduction: one workgroup, fixed order.
-// out[k] = sum over records of parts[i*width+k]   (sqrt'ed for nrm2)
-// --------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void k_reduce_final(
-    const double *__restrict__ parts, unsigned nparts, unsigned width,
-    double *__restrict__ out, int take_sqrt,
-    const lsb_pcg_state *__restrict__ st) {
-  if (st && st->status)
-    return;
-  __shared__ double sred[4];
-  for (unsigned k = 0; k < width; k++) {
-    double v[1] = {0.0};
-    for (unsigned i = threadIdx.x; i < nparts; i += WG)
-      v[0] += parts[(size_t)i * width + k];
-    wg_sum<1>(v, sred);
-    if (threadIdx.x == 0)
-      out[k] = take_sqrt ? sqrt(v[0]) : v[0];
-  }
-}
-
-// two of those in one launch (the RCCL path of the single-reduction iteration
-// needs the SpMV's and the sweep's partial sums reduced before ONE all-reduce)
-__global__ __launch_bounds__(WG) void k_reduce_final2(
-    const double *__restrict__ pa, unsigned na, unsigned wa, double *__restrict__ outa,
-    const double *__restrict__ pb, unsigned nb, unsigned wb, double *__restrict__ outb,
-    const lsb_pcg_state *__restrict__ st) {
-  if (st && st->status)
-    return;
-  __shared__ double sred[4];
-  for (unsigned k = 0; k < wa + wb; k++) {
-    const bool a = k < wa;
-    const double *p = a ? pa : pb;
-    const unsigned n = a ? na : nb, w = a ? wa : wb, c = a ? k : k - wa;
-    double v[1] = {0.0};
-    for (unsigned i = threadIdx.x; i < n; i += WG)
-      v[0] += p[(size_t)i * w + c];
-    wg_sum<1>(v, sred);
-    if (threadIdx.x == 0)
-      (a ? outa : outb)[c] = v[0];
-  }
-}
-
-// first stage of dot / nrm2 (b == a gives sum a_i^2)
-__global__ __launch_bounds__(WG) void k_dot(unsigned n,
-                                            const double *__restrict__ a,
-                                            const double *__restrict__ b,
-                                            double *__restrict__ partials) {
-  __shared__ double sred[4];
-  double v[1] = {0.0};
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * WG)
-    v[0] += a[i] * b[i];
-  wg_sum<1>(v, sred);
-  if (threadIdx.x == 0)
-    partials[blockIdx.x] = v[0];
-}
-
-// --------------------------------------------------------------------------
-// a2-3  axpy / xpay with the scalar in HBM
-// --------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void k_axpy(unsigned n,
-                                             const double *__restrict__ alpha,
-                                             const double *__restrict__ x,
-                                             double *__restrict__ y) {
-  const double a = alpha[0];
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * WG)
-    y[i] += a * x[i];
-}
-
-__global__ __launch_bounds__(WG) void k_xpay(unsigned n,
-                                             const double *__restrict__ beta,
-                                             const double *__restrict__ x,
-                                             double *__restrict__ y) {
-  const double b = beta[0];
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * WG)
-    y[i] = x[i] + b * y[i];
-}
-
-// --------------------------------------------------------------------------
-// a2-4  Jacobi
-// --------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void k_jacobi_setup(
-    unsigned n, unsigned row_begin, const int *__restrict__ offs,
-    const int *__restrict__ cols, const double *__restrict__ vals,
-    double *__restrict__ dinv, int *__restrict__ nzero) {
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * WG) {
-    const int want = (int)(i + row_begin);
-    double d = 0.0;
-    for (int j = offs[i]; j < offs[i + 1]; j++)
-      if (cols[j] == want)
-        d = vals[j];
-    if (d != 0.0) {
-      dinv[i] = 1.0 / d;
-    } else {
-      dinv[i] = 0.0;
-      atomicAdd(nzero, 1);
-    }
-  }
-}
-
-// l1-Jacobi: dinv[i] = 1 / sum_j |S_ij| (the whole row, also its entries in
-// other shards' columns: independent of the partition)
-__global__ __launch_bounds__(WG) void k_l1_setup(unsigned n, const int *__restrict__ offs,
-                                                 const double *__restrict__ vals,
-                                                 double *__restrict__ dinv,
-                                                 int *__restrict__ nzero) {
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * WG) {
-    double d = 0.0;
-    for (int j = offs[i]; j < offs[i + 1]; j++)
-      d += fabs(vals[j]);
-    if (d != 0.0) {
-      dinv[i] = 1.0 / d;
-    } else {
-      dinv[i] = 0.0;
-      atomicAdd(nzero, 1);
-    }
-  }
-}
-
-__global__ __launch_bounds__(WG) void k_jacobi_apply(
-    unsigned n, const double *__restrict__ dinv, const double *__restrict__ r,
-    double *__restrict__ z) {
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * WG)
-    z[i] = dinv[i] * r[i];
-}
-
-// x <- x + w * dinv .* (b - ax)      (ax = Op x from a preceding SpMV)
-__global__ __launch_bounds__(WG) void k_jacobi_sweep(
-    unsigned n, double w, const double *__restrict__ dinv,
-    const double *__restrict__ b, const double *__restrict__ ax,
-    double *__restrict__ x) {
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * WG)
-    x[i] += w * dinv[i] * (b[i] - ax[i]);
-}
-
-// dst[i] = src[perm[i]]  /  dst[perm[i]] = src[i]   (reordering, perm[new] = old)
-__global__ __launch_bounds__(WG) void k_perm_gather(unsigned n, const int *__restrict__ perm,
-                                                    const double *__restrict__ src,
-                                                    double *__restrict__ dst) {
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG) {
-    const int j = perm[i]; // -1: a pad row of a line-padded grid (lsb_csr_pad_lines)
-    dst[i] = j >= 0 ? src[j] : 0.0;
-  }
-}
-
-__global__ __launch_bounds__(WG) void k_perm_scatter(unsigned n, const int *__restrict__ perm,
-                                                     const double *__restrict__ src,
-                                                     double *__restrict__ dst) {
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG) {
-    const int j = perm[i];
-    if (j >= 0)
-      dst[j] = src[i];
-  }
-}
-
-__global__ __launch_bounds__(WG) void k_fill_index(unsigned n, unsigned first,
-                                                   double *__restrict__ v) {
-  for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * WG)
-    v[i] = (double)(i + first);
-}
-
-// --------------------------------------------------------------------------
-// a2-5  fused PCG sweeps.  Vector loads are 16 B/lane (double2) when every
-// operand is 16-B aligned, 8 B/lane otherwise (a shard that starts on an odd
-// row); the tail element, if any, is handled by the last thread.
-// --------------------------------------------------------------------------
-
-// x = 0, r = b, p = dinv.*b ; partials (r.z, b.b)
-template <bool V2>
-__global__ __launch_bounds__(WG) void k_pcg_init(
-    unsigned n, const double *__restrict__ b, const double *__restrict__ dinv, double dc,
-    double *__restrict__ x, double *__restrict__ r, double *__restrict__ p,
-    double *__restrict__ partials2) {
-  __shared__ double sred[8];
-  double acc[2] = {0.0, 0.0};
-  const size_t gtid = (size_t)blockIdx.x * WG + threadIdx.x;
-  const size_t gsz = (size_t)gridDim.x * WG;
-  if (V2) {
-    const size_t n2 = n / 2;
-    const double2 *b2 = (const double2 *)b, *d2 = (const double2 *)dinv;
-    double2 *x2 = (double2 *)x, *r2 = (double2 *)r, *p2 = (double2 *)p;
-    for (size_t i = gtid; i < n2; i += gsz) {
-      const double2 bv = b2[i], dv = dinv ? d2[i] : double2{dc, dc};
-      double2 pv;
-      pv.x = dv.x * bv.x, pv.y = dv.y * bv.y;
-      x2[i] = make_double2(0.0, 0.0);
-      r2[i] = bv;
-      p2[i] = pv;
-      acc[0] += bv.x * pv.x;
-      acc[0] += bv.y * pv.y;
-      acc[1] += bv.x * bv.x;
-      acc[1] += bv.y * bv.y;
-    }
-    if ((n & 1) && gtid == gsz - 1) {
-      const size_t i = n - 1;
-      const double bv = b[i], pv = (dinv ? dinv[i] : dc) * bv;
-      x[i] = 0.0, r[i] = bv, p[i] = pv;
-      acc[0] += bv * pv, acc[1] += bv * bv;
-    }
-  } else {
-    for (size_t i = gtid; i < n; i += gsz) {
-      const double bv = b[i], pv = (dinv ? dinv[i] : dc) * bv;
-      x[i] = 0.0, r[i] = bv, p[i] = pv;
-      acc[0] += bv * pv, acc[1] += bv * bv;
-    }
-  }
-  wg_sum<2>(acc, sred);
-  if (threadIdx.x == 0) {
-    partials2[2 * blockIdx.x + 0] = acc[0];
-    partials2[2 * blockIdx.x + 1] = acc[1];
-  }
-}
-
-__global__ __launch_bounds__(WG) void k_pcg_init_state(
-    lsb_pcg_state *__restrict__ st, const double *__restrict__ partials2,
-    unsigned nparts, double tol, int maxit) {
-  __shared__ double sred[8];
-  double v[2];
-  wg_sum_partials<2>(partials2, nparts, v, sred);
-  if (threadIdx.x == 0) {
-    st->rz[0] = v[0];
-    st->rz[1] = 0.0;
-    st->alpha[0] = st->alpha[1] = 0.0; // "no previous step" marker of k_cg1_update
-    st->bb = v[1];
-    st->thresh2 = tol * tol * v[1];
-    st->rr = v[1];
-    st->pq = 0.0;
-    st->iters = 0;
-    st->maxit = maxit;
-    st->pad = 0; // "maxit-th update done, status pending" marker of k_cg1_update / k_pcg_col_px
-    st->xpend = 0; // k_pcg_col_px: no x update pending
-    // b == 0 => x = 0 is the solution; maxit == 0 => nothing to do
-    st->status = (v[1] == 0.0) ? LSB_STATUS_CONVERGED
-                               : (maxit <= 0 ? LSB_STATUS_MAXIT : LSB_STATUS_RUNNING);
-  }
-}
-
-// 16-byte lane loads of the BLAS-1 sweeps.  NT = nontemporal: on MI355X a
-// plain read-only stream tops out near 4.6-4.8 TB/s while the same loop with
-// nontemporal loads reads 6.1-6.2 TB/s (tools/spmv_lab.hip, "read-only" probes);
-// a 5-in/2-out sweep shaped like k_pcg_update_xr gains 27 %.
-typedef double d2v __attribute__((ext_vector_type(2)));
-template <bool NT>
-__device__ __forceinline__ d2v ld2(const d2v *p) {
-  if (NT)
-    return __builtin_nontemporal_load(p);
-  return *p;
-}
-// Stores of vectors nobody reads before the NEXT sweep (x; in the single-
-// reduction form also p, s, r): nontemporal, so that they do not sit as dirty
-// lines in L2 / Infinity Cache while the SpMV that follows streams the matrix.
-// Jacobi diagonal: a vector, or -- d2 == nullptr -- ONE value for every row (an
-// operator with a constant diagonal: the preconditioner is a scaling and its
-// vector need not be read; same arithmetic, the factor comes from a register).
-template <bool NT>
-__device__ __forceinline__ d2v ldd(const d2v *d2, size_t i, double dc) {
-  if (!d2)
-    return d2v{dc, dc};
-  return ld2<NT>(d2 + i);
-}
-template <bool NT>
-__device__ __forceinline__ void st2(d2v *p, d2v v) {
-  if (NT)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
-}
-
-// alpha = rz/pq ; x += alpha p ; r -= alpha q ; partials (r.dinv.r, r.r)
-// NTX / NTPQ / NTR: which operands are loaded nontemporal -- x (also stored so), p and q (and the
-// Jacobi diagonal), r.  Which of them should bypass the caches is a matter of what the NEXT launches
-// read again (LSBENCH_HIP_BLAS1_NT is the mask: bit 0 x, 1 p and q, 2 r here; 3 r, 4 p in
-// k_pcg_update_p; 1 = all of them, the setting measured in rounds 1 and 2).
-template <bool V2, bool NTX, bool NTPQ, bool NTR>
-__global__ __launch_bounds__(WG) void k_pcg_update_xr(
-    unsigned n, const double *__restrict__ p, const double *__restrict__ q,
-    const double *__restrict__ dinv, double dc, double *__restrict__ x,
-    double *__restrict__ r, lsb_pcg_state *__restrict__ st, int parity,
-    const double *__restrict__ pq_parts, unsigned npq,
-    double *__restrict__ partials2) {
-  __shared__ double sred[8];
-  const size_t gtid = (size_t)blockIdx.x * WG + threadIdx.x;
-  const size_t gsz = (size_t)gridDim.x * WG;
-  const size_t n2 = n / 2;
-  const d2v *p2 = (const d2v *)p, *q2 = (const d2v *)q, *d2 = (const d2v *)dinv;
-  d2v *x2 = (d2v *)x, *r2 = (d2v *)r;
-  // Everything that does not depend on alpha is requested up front, so the
-  // status word, the p.q partials, r.z and this lane's first operands are ONE
-  // memory round trip, not four in a row (a small operator's sweep is nothing
-  // but these latencies).
-  const int stopped = st->status;
-  const double rz = st->rz[parity];
-  d2v pv = {0.0, 0.0}, qv = pv, dv = pv, xv = pv, rv = pv;
-  const bool first = V2 && gtid < n2;
-  if (first) {
-    pv = ld2<NTPQ>(p2 + gtid), qv = ld2<NTPQ>(q2 + gtid), dv = ldd<NTPQ>(d2, gtid, dc);
-    xv = ld2<NTX>(x2 + gtid), rv = ld2<NTR>(r2 + gtid);
-  }
-  double pqv[1];
-  wg_sum_partials<1>(pq_parts, npq, pqv, sred);
-  if (stopped)
-    return;
-  const double pq = pqv[0];
-  if (!(pq != 0.0) || !isfinite(pq)) { // same decision in every workgroup
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-      st->status = LSB_STATUS_BREAKDOWN;
-    return;
-  }
-  const double alpha = rz / pq;
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    st->pq = pq;
-  double acc[2] = {0.0, 0.0};
-  if (V2) {
-    if (first) {
-      size_t i = gtid;
-      for (;;) {
-        xv.x += alpha * pv.x, xv.y += alpha * pv.y;
-        rv.x -= alpha * qv.x, rv.y -= alpha * qv.y;
-        st2<NTX>(x2 + i, xv), r2[i] = rv;
-        acc[0] += rv.x * (dv.x * rv.x);
-        acc[0] += rv.y * (dv.y * rv.y);
-        acc[1] += rv.x * rv.x;
-        acc[1] += rv.y * rv.y;
-        i += gsz;
-        if (i >= n2)
-          break;
-        pv = ld2<NTPQ>(p2 + i), qv = ld2<NTPQ>(q2 + i), dv = ldd<NTPQ>(d2, i, dc);
-        xv = ld2<NTX>(x2 + i), rv = ld2<NTR>(r2 + i);
-      }
-    }
-    if ((n & 1) && gtid == gsz - 1) {
-      const size_t i = n - 1;
-      x[i] += alpha * p[i];
-      const double rs = r[i] - alpha * q[i];
-      r[i] = rs;
-      acc[0] += rs * ((dinv ? dinv[i] : dc) * rs), acc[1] += rs * rs;
-    }
-  } else {
-    for (size_t i = gtid; i < n; i += gsz) {
-      x[i] += alpha * p[i];
-      const double rs = r[i] - alpha * q[i];
-      r[i] = rs;
-      acc[0] += rs * ((dinv ? dinv[i] : dc) * rs), acc[1] += rs * rs;
-    }
-  }
-  wg_sum<2>(acc, sred);
-  if (threadIdx.x == 0) {
-    partials2[2 * blockIdx.x + 0] = acc[0];
-    partials2[2 * blockIdx.x + 1] = acc[1];
-  }
-}
-
-// (rz', rr) = sum partials ; stop test ; beta = rz'/rz ; p = dinv.*r + beta p
-// X2: a lane keeps TWO 16-byte pairs per operand in flight (rows i and i + grid).  With one
-// pair a lane has 32 bytes on their way (r and p; the constant diagonal is a register) --
-// 2048 workgroups x 256 lanes x 32 B = 16.8 MB, about what 8 TB/s x 2 us of latency needs, and
-// the sweep ran at 0.73 of peak where its five-operand sibling k_pcg_update_xr (64-80 B per
-// lane) reaches 0.84 (profiles/r02_trace_kernel_stats.csv).
-template <bool V2, bool NTR, bool NTP, bool X2>
-__global__ __launch_bounds__(WG) void k_pcg_update_p(
-    unsigned n, const double *__restrict__ r, const double *__restrict__ dinv, double dc,
-    const double *pin, double *p, lsb_pcg_state *__restrict__ st, int parity,
-    const double *__restrict__ parts2, unsigned nparts2) {
-  // pin: where the previous direction is read from (== p, or the other buffer
-  // of the launch-bound path that folds this update into the SpMV)
-  __shared__ double sred[8];
-  const size_t gtid = (size_t)blockIdx.x * WG + threadIdx.x;
-  const size_t gsz = (size_t)gridDim.x * WG;
-  const size_t n2 = n / 2;
-  const d2v *r2 = (const d2v *)r, *d2 = (const d2v *)dinv;
-  d2v *p2 = (d2v *)p;
-  const d2v *pi2 = (const d2v *)pin;
-  // as in k_pcg_update_xr: one round trip for status, scalars and operands
-  const int stopped = st->status;
-  const double rz_old = st->rz[parity], thresh2 = st->thresh2;
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    st->xpend = 0; // (two-launch column form: k_pcg_xfix, the launch before this one, has applied it; nobody
-                   // reads the word in this launch)
-  d2v rv = {0.0, 0.0}, dv = rv, pv = rv, rw = rv, dw = rv, pw = rv;
-  const bool first = V2 && gtid < n2;
-  bool second = X2 && V2 && gtid + gsz < n2;
-  if (first)
-    rv = ld2<NTR>(r2 + gtid), dv = ldd<NTR>(d2, gtid, dc), pv = ld2<NTP>(pi2 + gtid);
-  if (second)
-    rw = ld2<NTR>(r2 + gtid + gsz), dw = ldd<NTR>(d2, gtid + gsz, dc), pw = ld2<NTP>(pi2 + gtid + gsz);
-  double v[2];
-  wg_sum_partials<2>(parts2, nparts2, v, sred);
-  if (stopped)
-    return;
-  const double rz_new = v[0], rr = v[1];
-  const bool conv = rr <= thresh2;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    // only this thread touches iters/rr/rz[parity^1]/status in this launch
-    const int it = st->iters + 1;
-    st->iters = it;
-    st->rr = rr;
-    st->rz[parity ^ 1] = rz_new;
-    if (conv)
-      st->status = LSB_STATUS_CONVERGED;
-    else if (it >= st->maxit)
-      st->status = LSB_STATUS_MAXIT;
-  }
-  if (conv)
-    return;
-  const double beta = rz_new / rz_old;
-  if (V2) {
-    if (first) {
-      size_t i = gtid;
-      const size_t step = X2 ? 2 * gsz : gsz;
-      for (;;) {
-        pv.x = pnew_of(dv.x, rv.x, beta, pv.x); // one expression for every kernel that forms p
-        pv.y = pnew_of(dv.y, rv.y, beta, pv.y);
-        p2[i] = pv;
-        if (X2 && second) {
-          pw.x = pnew_of(dw.x, rw.x, beta, pw.x);
-          pw.y = pnew_of(dw.y, rw.y, beta, pw.y);
-          p2[i + gsz] = pw;
-        }
-        i += step;
-        if (i >= n2)
-          break;
-        rv = ld2<NTR>(r2 + i), dv = ldd<NTR>(d2, i, dc), pv = ld2<NTP>(pi2 + i);
-        if (X2) {
-          second = i + gsz < n2;
-          if (second)
-            rw = ld2<NTR>(r2 + i + gsz), dw = ldd<NTR>(d2, i + gsz, dc), pw = ld2<NTP>(pi2 + i + gsz);
-        }
-      }
-    }
-    if ((n & 1) && gtid == gsz - 1)
-      p[n - 1] = pnew_of(dinv ? dinv[n - 1] : dc, r[n - 1], beta, pin[n - 1]);
-  } else {
-    for (size_t i = gtid; i < n; i += gsz)
-      p[i] = pnew_of(dinv ? dinv[i] : dc, r[i], beta, pin[i]);
-  }
-}
-
-// --------------------------------------------------------------------------
-// Single-reduction CG (Chronopoulos & Gear 1989), LSB_KRYLOV_PCG1: the same
-// Krylov iterates as PCG in exact arithmetic, arranged so that an iteration is
-// TWO launches and ONE global reduction instead of three and two:
-//     [this kernel]  beta = g'/g ; alpha = g' / (d - beta g'/alpha)
-//                    p = u + beta p ; s = w + beta s ; x += alpha p ; r -= alpha s
-//                    u = D^-1 r ; partials (g'' = r.u, r.r)
-//     [SpMV]         w = S u ; partials d = w.u         (the fused-dot SpMV)
-// with g' = r.u and r.r taken from this kernel's own previous launch and
-// d = w.u from the SpMV in between.  For launch-latency-bound operators that is
-// 2/3 of the launches; across GPUs it is one all-reduce (3 doubles) per
-// iteration instead of two.  Costs one more vector (s) and 96 n instead of 88 n
-// bytes per iteration, so the large single-GPU case keeps the classic form.
-// --------------------------------------------------------------------------
-// UI ("implicit u"): the Jacobi diagonal is the constant dc, so u = dc r is not
-// kept at all -- r itself lives in the gather vector, the SpMV in between
-// delivers t = S r and r.t, and w = dc t, w.u = dc^2 r.t are formed here:
-// 9 vector passes per sweep instead of 11 (u neither read nor written).
-template <bool V2, bool NT, bool UI>
-__global__ __launch_bounds__(WG) void k_cg1_update(
-    unsigned n, double *__restrict__ u, const double *__restrict__ w,
-    const double *__restrict__ dinv, double dc, double *__restrict__ p, double *__restrict__ sv,
-    double *__restrict__ x, double *__restrict__ r, lsb_pcg_state *__restrict__ st,
-    int parity, const double *__restrict__ parts_gr, unsigned ngr,
-    const double *__restrict__ parts_d, unsigned nd, const lsb_ar_collect col,
-    double *__restrict__ partials2) {
-  __shared__ double sred[8];
-  const size_t gtid = (size_t)blockIdx.x * WG + threadIdx.x;
-  const size_t gsz = (size_t)gridDim.x * WG;
-  const size_t n2 = n / 2;
-  // `pend`: the previous launch was the maxit-th update.  That launch does NOT
-  // publish LSB_STATUS_MAXIT itself: its workgroups read the status word on
-  // entry, and one that started after the leader's store would skip its slice
-  // of x/r/p/s (a mix of two iterates).  It raises st->pad instead, a word
-  // nobody tests in that launch; THIS launch promotes it to the final status --
-  // every workgroup sees pad = 1 (written one launch ago) and returns, whatever
-  // it reads in the status word.
-  const int stopped = st->status, pend = st->pad;
-  const double g_old = st->rz[parity], a_old = st->alpha[parity], thresh2 = st->thresh2;
-  d2v *u2 = (d2v *)u, *p2 = (d2v *)p, *s2 = (d2v *)sv, *x2 = (d2v *)x, *r2 = (d2v *)r;
-  const d2v *w2 = (const d2v *)w, *d2 = (const d2v *)dinv;
-  d2v uv = {0.0, 0.0}, wv = uv, dv = uv, pv = uv, sw = uv, xv = uv, rv = uv;
-  const bool first = V2 && gtid < n2;
-  if (first) {
-    wv = ld2<NT>(w2 + gtid), dv = ldd<NT>(d2, gtid, dc);
-    pv = ld2<NT>(p2 + gtid), sw = ld2<NT>(s2 + gtid), xv = ld2<NT>(x2 + gtid);
-    // (the vector the SpMV gathers next -- r with the implicit u, else u -- is loaded the plain
-    // way: loaded nontemporal it is gone from the caches when the SpMV wants it, 40 instead of
-    // 25 us on the 10 M-row operator, as with p in k_pcg_update_p)
-    rv = ld2 < NT && !UI > (r2 + gtid);
-    if (UI)
-      uv = dc * rv, wv = dc * wv;
-    else
-      uv = ld2<false>(u2 + gtid);
-  }
-  double gr[2], dd[1];
-  if (col.mbox) {
-    // sharded solve over the direct xGMI path: the SpMV launch in front of this
-    // one sent this rank's sums to every rank; take w.u, r.u, r.r from the
-    // mailbox (rank order: the same bits everywhere) -- hip_ar.h
-    if (stopped)
-      return;
-    if (threadIdx.x < 64) {
-      double v[3];
-      const bool ok = ar_collect<false>(col.mbox, col.R, col.epoch, col.timeout, 3, v);
-      if (threadIdx.x == 0)
-        sred[0] = v[0], sred[1] = v[1], sred[2] = v[2], sred[3] = ok ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    dd[0] = sred[0], gr[0] = sred[1], gr[1] = sred[2];
-    if (sred[3] == 0.0) { // a peer did not arrive: every workgroup that notices says so
-      if (threadIdx.x == 0)
-        __hip_atomic_store(&st->status, (int)LSB_STATUS_COMM, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      return;
-    }
-  } else {
-    wg_sum_partials<2>(parts_gr, ngr, gr, sred);
-    wg_sum_partials<1>(parts_d, nd, dd, sred);
-    if (stopped)
-      return;
-  }
-  const double g_new = gr[0], rr = gr[1], delta = UI ? dc * dc * dd[0] : dd[0];
-  const bool leader = blockIdx.x == 0 && threadIdx.x == 0;
-  if (rr <= thresh2 || pend) { // r of the previous update meets the tolerance, or it was the last allowed
-    if (leader)
-      st->status = rr <= thresh2 ? LSB_STATUS_CONVERGED : LSB_STATUS_MAXIT, st->rr = rr;
-    return;
-  }
-  double beta = 0.0, alpha;
-  if (a_old == 0.0) { // first iteration of the solve (k_pcg_init_state zeroes alpha)
-    alpha = g_new / delta;
-  } else {
-    beta = g_new / g_old;
-    alpha = g_new / (delta - beta * g_new / a_old);
-  }
-  if (!isfinite(alpha) || alpha == 0.0) { // same decision in every workgroup
-    if (leader)
-      st->status = LSB_STATUS_BREAKDOWN;
-    return;
-  }
-  if (leader) {
-    const int it = st->iters + 1;
-    st->iters = it;
-    st->rr = rr;
-    st->pq = delta;
-    st->rz[parity ^ 1] = g_new;
-    st->alpha[parity ^ 1] = alpha;
-    if (it >= st->maxit)
-      st->pad = 1; // promoted to LSB_STATUS_MAXIT / CONVERGED by the next launch (see `pend`)
-  }
-  double acc[2] = {0.0, 0.0};
-  if (V2) {
-    if (first) {
-      size_t i = gtid;
-      for (;;) {
-        pv.x = uv.x + beta * pv.x, pv.y = uv.y + beta * pv.y;
-        sw.x = wv.x + beta * sw.x, sw.y = wv.y + beta * sw.y;
-        xv.x += alpha * pv.x, xv.y += alpha * pv.y;
-        rv.x -= alpha * sw.x, rv.y -= alpha * sw.y;
-        uv.x = dv.x * rv.x, uv.y = dv.y * rv.y;
-        st2<NT>(p2 + i, pv), st2<NT>(s2 + i, sw), st2<NT>(x2 + i, xv);
-        if (UI) {
-          r2[i] = rv; // the SpMV gathers it next: keep it cached
-        } else {
-          st2<NT>(r2 + i, rv);
-          u2[i] = uv;
-        }
-        acc[0] += rv.x * uv.x;
-        acc[0] += rv.y * uv.y;
-        acc[1] += rv.x * rv.x;
-        acc[1] += rv.y * rv.y;
-        i += gsz;
-        if (i >= n2)
-          break;
-        wv = ld2<NT>(w2 + i), dv = ldd<NT>(d2, i, dc);
-        pv = ld2<NT>(p2 + i), sw = ld2<NT>(s2 + i), xv = ld2<NT>(x2 + i);
-        rv = ld2 < NT && !UI > (r2 + i);
-        if (UI)
-          uv = dc * rv, wv = dc * wv;
-        else
-          uv = ld2<false>(u2 + i);
-      }
-    }
-    if ((n & 1) && gtid == gsz - 1) {
-      const size_t i = n - 1;
-      const double ui0 = UI ? dc * r[i] : u[i], wi = UI ? dc * w[i] : w[i];
-      const double pi = ui0 + beta * p[i], si = wi + beta * sv[i];
-      p[i] = pi, sv[i] = si;
-      x[i] += alpha * pi;
-      const double ri = r[i] - alpha * si, ui = (dinv ? dinv[i] : dc) * ri;
-      r[i] = ri;
-      if (!UI)
-        u[i] = ui;
-      acc[0] += ri * ui, acc[1] += ri * ri;
-    }
-  } else {
-    for (size_t i = gtid; i < n; i += gsz) {
-      const double ui0 = UI ? dc * r[i] : u[i], wi = UI ? dc * w[i] : w[i];
-      const double pi = ui0 + beta * p[i], si = wi + beta * sv[i];
-      p[i] = pi, sv[i] = si;
-      x[i] += alpha * pi;
-      const double ri = r[i] - alpha * si, ui = (dinv ? dinv[i] : dc) * ri;
-      r[i] = ri;
-      if (!UI)
-        u[i] = ui;
-      acc[0] += ri * ui, acc[1] += ri * ri;
-    }
-  }
-  wg_sum<2>(acc, sred);
-  if (threadIdx.x == 0) {
-    partials2[2 * blockIdx.x + 0] = acc[0];
-    partials2[2 * blockIdx.x + 1] = acc[1];
-  }
-}
-
-// Virtual-rank stand-in for the all-reduce: `nshard` shards on ONE device keep
-// their scalars at base[q*stride + off .. +cnt); sum over q in rank order and
-// hand every shard the same bits.
-__global__ void k_vreduce(double *__restrict__ base, unsigned stride,
-                          unsigned nshard, unsigned off, unsigned cnt) {
-  const unsigned t = threadIdx.x;
-  if (t < cnt) {
-    double s = 0.0;
-    for (unsigned q = 0; q < nshard; q++)
-      s += base[(size_t)q * stride + off + t];
-    for (unsigned q = 0; q < nshard; q++)
-      base[(size_t)q * stride + off + t] = s;
-  }
-}
-
-// --------------------------------------------------------------------------
-// Launchers (C ABI)
-// --------------------------------------------------------------------------
-static inline unsigned div_up(unsigned a, unsigned b) { return (a + b - 1) / b; }
-static inline unsigned round_up(unsigned a, unsigned b) { return div_up(a, b) * b; }
-static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-static __thread int g_blas1_nt = 63; /* mask, see k_pcg_update_xr; bit 5: k_cg1_update.  Per host thread =
-                                         per rank: set by the solver that enqueues (tune_blas1_nt) */
 
 // --------------------------------------------------------------------------
 // ONE ROUNDING RULE for the sliced-ELL kernels (k_spmv_sell, k_spmv_sell16, k_spmv_tmpl): a
@@ -2343,25 +1685,6 @@ __global__ __launch_bounds__(WG, 5) void k_pcg_col_r(
   }
 }
 
-// the x update a run's last k_pcg_col_r left pending (no k_pcg_col_px came behind it, or that one
-// found the solve converged): x += alpha p with p in the buffer st->xpend names.  Runs whatever the
-// status; the stand-alone k_pcg_update_p behind it clears st->xpend.
-__global__ __launch_bounds__(WG) void k_pcg_xfix(unsigned n, const double *__restrict__ p0, const double *__restrict__ p1,
-                                                 double *__restrict__ x, const lsb_pcg_state *__restrict__ st) {
-  const int pend = st->xpend;
-  if (!pend)
-    return;
-  const double alpha = st->alpha[0], alpha2 = st->alpha[1];
-  if (pend <= 2) { // one update behind: the direction is in buffer pend - 1
-    const double *__restrict__ p = pend == 1 ? p0 : p1;
-    for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG)
-      x[i] += alpha * p[i];
-  } else { // two: the last direction in buffer pend - 3, the one before it in the other
-    const double *__restrict__ p = pend == 3 ? p0 : p1, *__restrict__ pp = pend == 3 ? p1 : p0;
-    for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += (size_t)gridDim.x * WG)
-      x[i] = (x[i] + alpha2 * pp[i]) + alpha * p[i];
-  }
-}
 
 // (Round 4, measured and taken out again: k_spmv_tmpl_deep -- a wave takes 2 or 4 of its turns AT ONCE,
 // all their slice records in one batch of scalar loads, all 10 / 20 gathers, edge elements and mask
@@ -2546,10 +1869,12 @@ __global__ __launch_bounds__(WG) void k_spmv_binned(
     y[first_key] += carry_in + first_sum;
 }
 
-extern "C" {
+// (C linkage admits no templates: the launchers' pick of a binned kernel by its chunk size lives out here)
+template <int FLAGS> static decltype(&k_spmv_binned<0, 4>) binned_kern(unsigned chunk_cap) {
+  return chunk_cap == 1024 ? k_spmv_binned<FLAGS, 4> : chunk_cap == 1536 ? k_spmv_binned<FLAGS, 6> : k_spmv_binned<FLAGS, 8>;
+}
 
-void lsb_k_set_blas1_nt(int on) { g_blas1_nt = on == 1 ? 63 : on; } /* 1 = every operand (bits 0..5) */
-int lsb_k_get_blas1_nt(void) { return g_blas1_nt; }
+extern "C" {
 
 /* one bin of the binned form: chunks [c0, c0 + nchunk) */
 void lsb_k_spmv_binned(unsigned flags, unsigned chunk_cap, const unsigned *chunk_begin, unsigned c0,
@@ -2558,54 +1883,16 @@ void lsb_k_spmv_binned(unsigned flags, unsigned chunk_cap, const unsigned *chunk
   if (!nchunk)
     return;
   const unsigned g = (nchunk + NXCD - 1) / NXCD * NXCD;
-#define LSB_BINNED_U(FL, U)                                                                    \
-  k_spmv_binned<FL, U><<<g, WG, 0, (hipStream_t)stream>>>(chunk_begin + c0, nchunk, rows, cols,   \
-                                                          vals, x, y, st)
-#define LSB_BINNED(FL)                                                                         \
-  case FL:                                                                                     \
-    if (chunk_cap == 1024)                                                                     \
-      LSB_BINNED_U(FL, 4);                                                                     \
-    else if (chunk_cap == 1536)                                                                \
-      LSB_BINNED_U(FL, 6);                                                                     \
-    else                                                                                       \
-      LSB_BINNED_U(FL, 8);                                                                     \
-    break;
+  auto kern = k_spmv_binned<SP_NT, 8>;
   switch (flags & (SP_NT | 8u | 16u)) {
-    LSB_BINNED(0)
-    LSB_BINNED(2)
-    LSB_BINNED(8)
-    LSB_BINNED(10)
-    LSB_BINNED(16)
-    LSB_BINNED(18)
-  default:
-    LSB_BINNED_U(SP_NT, 8);
+  case 0: kern = binned_kern<0>(chunk_cap); break;
+  case 2: kern = binned_kern<2>(chunk_cap); break;
+  case 8: kern = binned_kern<8>(chunk_cap); break;
+  case 10: kern = binned_kern<10>(chunk_cap); break;
+  case 16: kern = binned_kern<16>(chunk_cap); break;
+  case 18: kern = binned_kern<18>(chunk_cap); break;
   }
-#undef LSB_BINNED_U
-#undef LSB_BINNED
-}
-
-unsigned lsb_k_blas1_grid(unsigned n) {
-  // 16 B/lane => WG*2 elements per workgroup per trip.  Up to 256 workgroups
-  // one trip each (small operators: all latency); beyond that four trips per
-  // lane before the grid grows -- every workgroup of the NEXT kernel re-reduces
-  // this kernel's partial sums, so a grid of 2048 on a 1 M-row shard costs more
-  // in its consumers than it gains (1.25 M rows: sweep 26.5 -> 20.8 us); cap at
-  // MAX_PARTIALS.
-  unsigned g = div_up(n, WG * 2);
-  if (g > 256) {
-    g = div_up(n, WG * 2 * 4);
-    if (g < 256)
-      g = 256;
-  }
-  // ... and at three workgroups per CU: beyond that the sweeps get SLOWER the more of them stream
-  // at once -- round 3, iteration of the 64 M-row 7-point operator (vectors of 512 MB: nothing
-  // comes out of the Infinity Cache) 1211-1238 us with 2048 workgroups, 1075-1077 us with 768
-  // (256 / 512 / 1024: 1081-1104 / 1082-1090 / 1103-1110), the 10 M-row 5-point one 140-142 ->
-  // 136-137 us; y = 4 x over 512 MB vectors: 178 us with 1024 workgroups, 204-207 us with
-  // 2048 / 4096 (profiles/r03_sweep_grid.txt).
-  if (g > LSB_STREAM_GRID_CAP)
-    g = LSB_STREAM_GRID_CAP;
-  return g ? g : 1;
+  kern<<<g, WG, 0, (hipStream_t)stream>>>(chunk_begin + c0, nchunk, rows, cols, vals, x, y, st);
 }
 
 // number of workgroups (== number of dot partials) a given SpMV launch uses
@@ -2655,6 +1942,19 @@ static lsb_ar_tail tail_for(const struct lsb_ar_tail *t, const double *partials)
   return *t;
 }
 
+static lsb_cheb_epi epi_for(const struct lsb_cheb_epi *e, bool refused, const char *why) {
+  lsb_cheb_epi none;
+  memset(&none, 0, sizeof none);
+  if (!e || !e->zout)
+    return none;
+  if (refused)
+    errx(EXIT_FAILURE, "%s", why);
+  return *e;
+}
+
+/* the sub-wavefront kernels come with 2 .. 32 lanes per row; any other count takes a whole wavefront */
+static unsigned subwave_lanes(unsigned L) { return L == 2 || L == 4 || L == 8 || L == 16 || L == 32 ? L : 64; }
+
 void lsb_k_spmv(int variant, unsigned n, const int *offs, const int *cols,
                 const double *vals, const int *rowblk,
                 const unsigned char *blklanes, unsigned nblk,
@@ -2669,61 +1969,34 @@ void lsb_k_spmv(int variant, unsigned n, const int *offs, const int *cols,
   if (tail.counter && !lsb_k_spmv_has_tail(variant))
     errx(EXIT_FAILURE, "lsb_k_spmv: SpMV form %d cannot carry the all-reduce", variant);
   const unsigned g = lsb_k_spmv_grid(variant, n, nblk, lanes_per_row, grid_cap);
-  const float *vals32 = (const float *)(const void *)vals;
-  const bool f32 = (flags & LSB_SP_F32) != 0;
   if (npartials)
     *npartials = g;
-  if (variant == LSB_SPMV_ADAPTIVE) {
-#define LSB_ADAPTIVE(FL)                                                                 \
-  case FL:                                                                               \
-    if (f32)                                                                             \
-      k_spmv_adaptive<LSB_BLOCK_NNZ, FL, float><<<g, WG, 0, s>>>(                        \
-          rowblk, blklanes, nblk, offs, cols, vals32, x, y, xdot, partials, st, rowmap,  \
-          tail);                                                                         \
-    else                                                                                 \
-      k_spmv_adaptive<LSB_BLOCK_NNZ, FL, double><<<g, WG, 0, s>>>(                       \
-          rowblk, blklanes, nblk, offs, cols, vals, x, y, xdot, partials, st, rowmap,    \
-          tail);                                                                         \
-    break;
-    switch (flags & 3u) {
-      LSB_ADAPTIVE(0)
-      LSB_ADAPTIVE(1)
-      LSB_ADAPTIVE(2)
-      LSB_ADAPTIVE(3)
+  auto launch = [&](auto *v) { /* v: the values, of the kernel's value type */
+    using VT = std::decay_t<decltype(*v)>;
+    if (variant == LSB_SPMV_ADAPTIVE) {
+      static decltype(&k_spmv_adaptive<LSB_BLOCK_NNZ, 0, VT>) const kern[4] = { /* [flags & 3] */
+          k_spmv_adaptive<LSB_BLOCK_NNZ, 0, VT>, k_spmv_adaptive<LSB_BLOCK_NNZ, 1, VT>,
+          k_spmv_adaptive<LSB_BLOCK_NNZ, 2, VT>, k_spmv_adaptive<LSB_BLOCK_NNZ, 3, VT>};
+      kern[flags & 3u]<<<g, WG, 0, s>>>(rowblk, blklanes, nblk, offs, cols, v, x, y, xdot, partials, st, rowmap, tail);
+    } else {
+      const unsigned L = subwave_lanes(lanes_per_row);
+      auto kern = k_spmv_subwave<64, VT>;
+      switch (L) {
+      case 2: kern = k_spmv_subwave<2, VT>; break;
+      case 4: kern = k_spmv_subwave<4, VT>; break;
+      case 8: kern = k_spmv_subwave<8, VT>; break;
+      case 16: kern = k_spmv_subwave<16, VT>; break;
+      case 32: kern = k_spmv_subwave<32, VT>; break;
+      }
+      kern<<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols, v, x, y, xdot, partials, st);
     }
-#undef LSB_ADAPTIVE
-  } else if (variant == LSB_SPMV_SUBWAVE) {
-    const unsigned L = lanes_per_row;
-    const unsigned slots = WG / L;
-    const unsigned rpw = round_up(div_up(n, g), slots);
-#define LSB_SUBWAVE(LL)                                                                  \
-  case LL:                                                                               \
-    if (f32)                                                                             \
-      k_spmv_subwave<LL, float><<<g, WG, 0, s>>>(n, rpw, offs, cols, vals32, x, y, xdot, \
-                                                 partials, st);                          \
-    else                                                                                 \
-      k_spmv_subwave<LL, double><<<g, WG, 0, s>>>(n, rpw, offs, cols, vals, x, y, xdot,  \
-                                                  partials, st);                         \
-    break;
-    switch (L) {
-      LSB_SUBWAVE(2)
-      LSB_SUBWAVE(4)
-      LSB_SUBWAVE(8)
-      LSB_SUBWAVE(16)
-      LSB_SUBWAVE(32)
-    default:
-      if (f32)
-        k_spmv_subwave<64, float><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), 4), offs, cols, vals32,
-                                                   x, y, xdot, partials, st);
-      else
-        k_spmv_subwave<64, double><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), 4), offs, cols, vals,
-                                                    x, y, xdot, partials, st);
-    }
-#undef LSB_SUBWAVE
-  } else {
-    const unsigned rpw = div_up(n, g);
-    k_spmv_scalar<<<g, WG, 0, s>>>(n, rpw, offs, cols, vals, x, y, xdot, partials, st);
-  }
+  };
+  if (variant != LSB_SPMV_ADAPTIVE && variant != LSB_SPMV_SUBWAVE)
+    k_spmv_scalar<<<g, WG, 0, s>>>(n, div_up(n, g), offs, cols, vals, x, y, xdot, partials, st);
+  else if (flags & LSB_SP_F32)
+    launch((const float *)(const void *)vals);
+  else
+    launch(vals);
 }
 
 /* sub-wavefront SpMV with the direction update of the previous iteration folded
@@ -2733,27 +2006,45 @@ void lsb_k_spmv_subwave_p(unsigned n, const int *offs, const int *cols, const do
                           const double *pold, double *pnew, double *y, double *partials,
                           unsigned *npartials, struct lsb_pcg_state *st, int parity,
                           const double *parts2, unsigned nparts2, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned L = lanes_per_row;
-  const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SUBWAVE, n, 0, L, 0);
+  const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SUBWAVE, n, 0, lanes_per_row, 0);
   *npartials = g;
-  const unsigned rpw = round_up(div_up(n, g), WG / L);
-#define LSB_SWP(LL)                                                                         \
-  case LL:                                                                                  \
-    k_spmv_subwave_p<LL><<<g, WG, 0, s>>>(n, rpw, offs, cols, vals, r, dinv, dc, pold, pnew, y, \
-                                          partials, st, parity, parts2, nparts2);           \
-    break;
+  const unsigned L = subwave_lanes(lanes_per_row);
+  auto kern = k_spmv_subwave_p<64>;
   switch (L) {
-    LSB_SWP(2)
-    LSB_SWP(4)
-    LSB_SWP(8)
-    LSB_SWP(16)
-    LSB_SWP(32)
-  default:
-    k_spmv_subwave_p<64><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), 4), offs, cols, vals, r, dinv,
-                                          dc, pold, pnew, y, partials, st, parity, parts2, nparts2);
+  case 2: kern = k_spmv_subwave_p<2>; break;
+  case 4: kern = k_spmv_subwave_p<4>; break;
+  case 8: kern = k_spmv_subwave_p<8>; break;
+  case 16: kern = k_spmv_subwave_p<16>; break;
+  case 32: kern = k_spmv_subwave_p<32>; break;
   }
-#undef LSB_SWP
+  kern<<<g, WG, 0, (hipStream_t)stream>>>(n, round_up(div_up(n, g), WG / L), offs, cols, vals, r, dinv, dc, pold,
+                                          pnew, y, partials, st, parity, parts2, nparts2);
+}
+
+/* What the sliced-ELL, template and z-column launchers share, over `items` slices or column items: the
+ * all-reduce tail; the grid -- grid_cap, LSB_SELL_GRID where that is 0, at most `resident` where that is
+ * given -- and *npartials; the period (a slice launch deals its slices contiguously where the period is
+ * less than a plane, a column launch keeps its plan's); the far slots per side of c's templates (0 .. 2,
+ * a column launch 1 .. 2; c == NULL: no templates). */
+struct sell_launch {
+  unsigned g, period;
+  lsb_ar_tail tail;
+};
+static sell_launch sell_prologue(const char *who, bool col, const struct lsb_sell16_dev *c, unsigned items,
+                                 unsigned n, unsigned grid_cap, unsigned resident, unsigned period,
+                                 const double *partials, unsigned *npartials, const struct lsb_ar_tail *tail_in) {
+  sell_launch L;
+  L.tail = tail_for(tail_in, partials);
+  unsigned cap = grid_cap ? grid_cap : resident ? resident : LSB_SELL_GRID;
+  if (resident && cap > resident)
+    cap = resident;
+  L.g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, items, 0, cap);
+  if (npartials)
+    *npartials = L.g;
+  L.period = !col && period && (period < NXCD || items < period) ? 0 : period;
+  if (c && (c->tmpl.nfar > 2 || (col && c->tmpl.nfar < 1)))
+    errx(EXIT_FAILURE, "%s: %u far slots per side", who, c->tmpl.nfar);
+  return L;
 }
 
 /* Sliced-ELL launch over the slices [s0, s0+ns).  flags & LSB_SP_C16: `cols` is
@@ -2768,62 +2059,28 @@ void lsb_k_spmv_sell(unsigned flags, unsigned grid_cap, unsigned period, const u
                      const struct lsb_pcg_state *st, const struct lsb_ar_tail *tail_in,
                      const struct lsb_cheb_epi *epi_in, void *stream) {
   hipStream_t s = (hipStream_t)stream;
-  const lsb_ar_tail tail = tail_for(tail_in, partials);
-  lsb_cheb_epi epi;
-  memset(&epi, 0, sizeof epi);
-  if (epi_in && epi_in->zout) {
-    if (!(flags & LSB_SP_C16) || partials || ((row_begin | s0) & 1u))
-      errx(EXIT_FAILURE, "lsb_k_spmv_sell: the Chebyshev epilogue rides in the 16-bit kernel only");
-    epi = *epi_in;
-  }
-  const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, ns, 0, grid_cap ? grid_cap : 1536);
-  if (npartials)
-    *npartials = g;
-  const int nt = (flags & SP_NT) != 0;
-  const float *vals32 = (const float *)(const void *)vals; /* flags & LSB_SP_F32 */
-  if (period && (period < NXCD || ns < period))
-    period = 0; /* less than a plane: contiguous dealing */
-#define LSB_SELL16(FL, VT, V)                                                                  \
-  k_spmv_sell16<FL, VT><<<g, WG, 0, s>>>(sptr, s0, ns, period, n, row_begin, xlen, (const short *)cols, \
-                                         sbase, V, vconst, ulen, x, y, xdot, partials, st, tail, epi)
-#define LSB_SELL32(FL, VT, V)                                                                  \
-  k_spmv_sell<FL, VT><<<g, WG, 0, s>>>(sptr, s0, ns, period, n, (const int *)cols, V, x, y, xdot, \
-                                       partials, st, tail)
-  if (epi.zout) {
-#define LSB_SELL16C(FL, VT, V)                                                                            \
-  k_spmv_sell16<FL, VT, true><<<g, WG, 0, s>>>(sptr, s0, ns, period, n, row_begin, xlen, (const short *)cols, \
-                                               sbase, V, vconst, ulen, x, y, xdot, partials, st, tail, epi)
-    if (flags & LSB_SP_F32) {
-      if (nt)
-        LSB_SELL16C(SP_NT, float, vals32);
-      else
-        LSB_SELL16C(0, float, vals32);
-    } else if (nt)
-      LSB_SELL16C(SP_NT, double, vals);
-    else
-      LSB_SELL16C(0, double, vals);
-#undef LSB_SELL16C
-  } else if (flags & LSB_SP_F32) {
+  const lsb_cheb_epi epi = epi_for(epi_in, !(flags & LSB_SP_C16) || partials || ((row_begin | s0) & 1u),
+                                   "lsb_k_spmv_sell: the Chebyshev epilogue rides in the 16-bit kernel only");
+  const sell_launch L = sell_prologue("lsb_k_spmv_sell", false, NULL, ns, n, grid_cap, 0, period, partials,
+                                      npartials, tail_in);
+  const bool nt = (flags & SP_NT) != 0;
+  auto launch = [&](auto *v) { /* v: the values, of the kernel's value type */
+    using VT = std::decay_t<decltype(*v)>;
     if (flags & LSB_SP_C16) {
-      if (nt)
-        LSB_SELL16(SP_NT, float, vals32);
-      else
-        LSB_SELL16(0, float, vals32);
-    } else if (nt)
-      LSB_SELL32(SP_NT, float, vals32);
-    else
-      LSB_SELL32(0, float, vals32);
-  } else if (flags & LSB_SP_C16) {
-    if (nt)
-      LSB_SELL16(SP_NT, double, vals);
-    else
-      LSB_SELL16(0, double, vals);
-  } else if (nt)
-    LSB_SELL32(SP_NT, double, vals);
+      auto kern = nt ? k_spmv_sell16<SP_NT, VT> : k_spmv_sell16<0, VT>;
+      if (epi.zout)
+        kern = nt ? k_spmv_sell16<SP_NT, VT, true> : k_spmv_sell16<0, VT, true>;
+      kern<<<L.g, WG, 0, s>>>(sptr, s0, ns, L.period, n, row_begin, xlen, (const short *)cols, sbase, v, vconst,
+                              ulen, x, y, xdot, partials, st, L.tail, epi);
+    } else {
+      const auto kern = nt ? k_spmv_sell<SP_NT, VT> : k_spmv_sell<0, VT>;
+      kern<<<L.g, WG, 0, s>>>(sptr, s0, ns, L.period, n, (const int *)cols, v, x, y, xdot, partials, st, L.tail);
+    }
+  };
+  if (flags & LSB_SP_F32)
+    launch((const float *)(const void *)vals);
   else
-    LSB_SELL32(0, double, vals);
-#undef LSB_SELL16
-#undef LSB_SELL32
+    launch(vals);
 }
 
 /* The constant-slot layout through slice templates (k_spmv_tmpl).  vals: the kept value slots
@@ -2832,41 +2089,19 @@ void lsb_k_spmv_tmpl(unsigned flags, unsigned grid_cap, unsigned period, const s
                      unsigned ns, unsigned n, unsigned row_begin, unsigned xlen, const double *x, double *y,
                      const double *xdot, double *partials, unsigned *npartials, const struct lsb_pcg_state *st,
                      const struct lsb_ar_tail *tail_in, const struct lsb_cheb_epi *epi_in, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const lsb_ar_tail tail = tail_for(tail_in, partials);
-  lsb_cheb_epi epi;
-  memset(&epi, 0, sizeof epi);
-  if (epi_in && epi_in->zout) {
-    if (partials || ((row_begin | s0) & 1u))
-      errx(EXIT_FAILURE, "lsb_k_spmv_tmpl: the Chebyshev epilogue takes no dot and even row offsets");
-    epi = *epi_in;
-  }
-  const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, ns, 0, grid_cap ? grid_cap : 1536);
-  if (npartials)
-    *npartials = g;
-  if (period && (period < NXCD || ns < period))
-    period = 0;
+  const lsb_cheb_epi epi = epi_for(epi_in, partials || ((row_begin | s0) & 1u),
+                                   "lsb_k_spmv_tmpl: the Chebyshev epilogue takes no dot and even row offsets");
+  const sell_launch L = sell_prologue("lsb_k_spmv_tmpl", false, c, ns, n, grid_cap, 0, period, partials, npartials,
+                                      tail_in);
   const int f32 = (flags & LSB_SP_F32) != 0, dot_is_x = xdot && xdot == x + row_begin;
-#define LSB_TMPL_ARGS                                                                                           \
-  c->sptr, s0, ns, period, n, row_begin, xlen, (const u4v *)c->tmpl.srec, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals, \
-      f32, c->vconst, x, y, xdot, dot_is_x, partials, st, tail, epi
-#define LSB_TMPL(NF)                                                                                 \
-  do {                                                                                               \
-    if (epi.zout)                                                                                    \
-      k_spmv_tmpl<NF, true><<<g, WG, 0, s>>>(LSB_TMPL_ARGS);                                         \
-    else if (flags & LSB_SP_DEFER)                                                                   \
-      k_spmv_tmpl<NF, false, true><<<g, WG, 0, s>>>(LSB_TMPL_ARGS);                                  \
-    else                                                                                             \
-      k_spmv_tmpl<NF, false><<<g, WG, 0, s>>>(LSB_TMPL_ARGS);                                        \
-  } while (0)
-  switch (c->tmpl.nfar) {
-  case 0: LSB_TMPL(0); break;
-  case 1: LSB_TMPL(1); break;
-  case 2: LSB_TMPL(2); break;
-  default: errx(EXIT_FAILURE, "lsb_k_spmv_tmpl: %u far slots per side", c->tmpl.nfar);
-  }
-#undef LSB_TMPL
-#undef LSB_TMPL_ARGS
+  static decltype(&k_spmv_tmpl<0, false>) const kern[3][3] = { /* [nfar][plain, Chebyshev epilogue, deferred store] */
+      {k_spmv_tmpl<0, false>, k_spmv_tmpl<0, true>, k_spmv_tmpl<0, false, true>},
+      {k_spmv_tmpl<1, false>, k_spmv_tmpl<1, true>, k_spmv_tmpl<1, false, true>},
+      {k_spmv_tmpl<2, false>, k_spmv_tmpl<2, true>, k_spmv_tmpl<2, false, true>}};
+  const int form = epi.zout ? 1 : (flags & LSB_SP_DEFER) ? 2 : 0;
+  kern[c->tmpl.nfar][form]<<<L.g, WG, 0, (hipStream_t)stream>>>(
+      c->sptr, s0, ns, L.period, n, row_begin, xlen, (const u4v *)c->tmpl.srec, c->tmpl.mask, c->tmpl.td, c->sbase,
+      c->vals, f32, c->vconst, x, y, xdot, dot_is_x, partials, st, L.tail, epi);
 }
 
 /* The template layout walked in z-columns (k_spmv_tmpl_col): plan = xbeg[NXCD + 1], padding to 16
@@ -2876,289 +2111,57 @@ void lsb_k_spmv_tmpl_col(unsigned flags, unsigned grid_cap, unsigned period, con
                          int centre0, unsigned n, unsigned row_begin, unsigned xlen, const struct lsb_sell16_dev *c,
                          const double *x, double *y, const double *xdot, double *partials, unsigned *npartials,
                          const struct lsb_pcg_state *st, const struct lsb_ar_tail *tail_in, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const lsb_ar_tail tail = tail_for(tail_in, partials);
-  const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, nitem, 0, grid_cap ? grid_cap : 1536);
-  if (npartials)
-    *npartials = g;
   if (period < NXCD || !plan)
     errx(EXIT_FAILURE, "lsb_k_spmv_tmpl_col: no column plan (period %u)", period);
+  const sell_launch L = sell_prologue("lsb_k_spmv_tmpl_col", true, c, nitem, n, grid_cap, 0, period, partials,
+                                      npartials, tail_in);
   const int f32 = (flags & LSB_SP_F32) != 0;
   // the centre pair is the dot's operand where the dot is with the gathered vector itself (and the
   // centre base is 0: true of every operator with a diagonal; the kernel's DOT = 1 relies on it,
   // the plan builder says so in lsb_tmpl_cols.centre0)
   const int dot = !partials || !xdot ? 0 : (xdot == x + row_begin && centre0) ? 1 : 2;
-#define LSB_COL(NF, D)                                                                                \
-  k_spmv_tmpl_col<NF, D><<<g, WG, 0, s>>>(plan, period, n, row_begin, xlen, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, \
-                                          c->vals, f32, c->vconst, x, y, xdot, partials, st, tail)
-#define LSB_COLD(NF)                                                                                  \
-  do {                                                                                                \
-    if (dot == 0)                                                                                     \
-      LSB_COL(NF, 0);                                                                                 \
-    else if (dot == 1)                                                                                \
-      LSB_COL(NF, 1);                                                                                 \
-    else                                                                                              \
-      LSB_COL(NF, 2);                                                                                 \
-  } while (0)
-  switch (c->tmpl.nfar) {
-  case 1: LSB_COLD(1); break;
-  case 2: LSB_COLD(2); break;
-  default: errx(EXIT_FAILURE, "lsb_k_spmv_tmpl_col: %u far slots per side", c->tmpl.nfar);
-  }
-#undef LSB_COLD
-#undef LSB_COL
-}
-
-void lsb_k_reduce_final(const double *partials, unsigned nparts, unsigned width,
-                        double *out, int take_sqrt,
-                        const struct lsb_pcg_state *st, void *stream) {
-  k_reduce_final<<<1, WG, 0, (hipStream_t)stream>>>(partials, nparts, width, out,
-                                                    take_sqrt, st);
-}
-
-void lsb_k_reduce_final2(const double *pa, unsigned na, unsigned wa, double *outa,
-                         const double *pb, unsigned nb, unsigned wb, double *outb,
-                         const struct lsb_pcg_state *st, void *stream) {
-  k_reduce_final2<<<1, WG, 0, (hipStream_t)stream>>>(pa, na, wa, outa, pb, nb, wb, outb, st);
-}
-
-void lsb_k_dot(unsigned n, const double *a, const double *b, double *partials,
-               unsigned *npartials, void *stream) {
-  unsigned g = div_up(n ? n : 1, WG * 4);
-  if (g > LSB_STREAM_GRID_CAP)
-    g = LSB_STREAM_GRID_CAP;
-  *npartials = g;
-  k_dot<<<g, WG, 0, (hipStream_t)stream>>>(n, a, b, partials);
-}
-
-static unsigned ew_grid(unsigned n) {
-  unsigned g = div_up(n ? n : 1, WG * 4);
-  return g > LSB_STREAM_GRID_CAP ? LSB_STREAM_GRID_CAP : g;
-}
-
-void lsb_k_axpy(unsigned n, const double *alpha, const double *x, double *y,
-                void *stream) {
-  k_axpy<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, alpha, x, y);
-}
-
-void lsb_k_xpay(unsigned n, const double *beta, const double *x, double *y,
-                void *stream) {
-  k_xpay<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, beta, x, y);
-}
-
-void lsb_k_jacobi_setup(unsigned n, unsigned row_begin, const int *offs,
-                        const int *cols, const double *vals, double *dinv,
-                        int *nzero, void *stream) {
-  k_jacobi_setup<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, row_begin, offs, cols,
-                                                             vals, dinv, nzero);
-}
-
-void lsb_k_l1_setup(unsigned n, const int *offs, const double *vals, double *dinv, int *nzero,
-                    void *stream) {
-  k_l1_setup<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, offs, vals, dinv, nzero);
-}
-
-void lsb_k_jacobi_apply(unsigned n, const double *dinv, const double *r,
-                        double *z, void *stream) {
-  k_jacobi_apply<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, dinv, r, z);
-}
-
-void lsb_k_jacobi_sweep(unsigned n, double w, const double *dinv,
-                        const double *b, const double *ax, double *x,
-                        void *stream) {
-  k_jacobi_sweep<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, w, dinv, b, ax, x);
-}
-
-void lsb_k_vreduce(double *base, unsigned stride, unsigned nshard, unsigned off,
-                   unsigned cnt, void *stream) {
-  k_vreduce<<<1, 64, 0, (hipStream_t)stream>>>(base, stride, nshard, off, cnt);
-}
-
-void lsb_k_perm_gather(unsigned n, const int *perm, const double *src, double *dst,
-                       void *stream) {
-  k_perm_gather<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, perm, src, dst);
-}
-
-void lsb_k_perm_scatter(unsigned n, const int *perm, const double *src, double *dst,
-                        void *stream) {
-  k_perm_scatter<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, perm, src, dst);
-}
-
-void lsb_k_fill_index(unsigned n, unsigned first, double *v, void *stream) {
-  k_fill_index<<<ew_grid(n), WG, 0, (hipStream_t)stream>>>(n, first, v);
-}
-
-void lsb_k_pcg_init(unsigned n, const double *b, const double *dinv, double dc, double *x,
-                    double *r, double *p, double *partials2,
-                    unsigned *npartials, void *stream) {
-  const unsigned g = lsb_k_blas1_grid(n);
-  *npartials = g;
-  if (aligned16(b) && aligned16(dinv) && aligned16(x) && aligned16(r) && aligned16(p))
-    k_pcg_init<true><<<g, WG, 0, (hipStream_t)stream>>>(n, b, dinv, dc, x, r, p, partials2);
-  else
-    k_pcg_init<false><<<g, WG, 0, (hipStream_t)stream>>>(n, b, dinv, dc, x, r, p, partials2);
-}
-
-void lsb_k_pcg_init_state(struct lsb_pcg_state *st, const double *partials2,
-                          unsigned nparts, double tol, int maxit,
-                          void *stream) {
-  k_pcg_init_state<<<1, WG, 0, (hipStream_t)stream>>>(st, partials2, nparts, tol, maxit);
-}
-
-void lsb_k_pcg_update_xr(unsigned n, const double *p, const double *q,
-                         const double *dinv, double dc, double *x, double *r,
-                         struct lsb_pcg_state *st, int parity,
-                         const double *pq_parts, unsigned npq,
-                         double *partials2, unsigned *npartials, void *stream) {
-  const unsigned g = lsb_k_blas1_grid(n);
-  *npartials = g;
-  if (aligned16(p) && aligned16(q) && aligned16(dinv) && aligned16(x) && aligned16(r)) {
-#define LSB_XR(A, B, C)                                                                           \
-  k_pcg_update_xr<true, A, B, C><<<g, WG, 0, (hipStream_t)stream>>>(n, p, q, dinv, dc, x, r, st, parity, pq_parts, \
-                                                                  npq, partials2)
-    switch (g_blas1_nt & 7) {
-    case 0: LSB_XR(false, false, false); break;
-    case 1: LSB_XR(true, false, false); break;
-    case 2: LSB_XR(false, true, false); break;
-    case 3: LSB_XR(true, true, false); break;
-    case 4: LSB_XR(false, false, true); break;
-    case 5: LSB_XR(true, false, true); break;
-    case 6: LSB_XR(false, true, true); break;
-    default: LSB_XR(true, true, true); break;
-    }
-#undef LSB_XR
-  } else {
-    k_pcg_update_xr<false, false, false, false><<<g, WG, 0, (hipStream_t)stream>>>(
-        n, p, q, dinv, dc, x, r, st, parity, pq_parts, npq, partials2);
-  }
+  static decltype(&k_spmv_tmpl_col<1, 0>) const kern[2][3] = { /* [nfar - 1][dot] */
+      {k_spmv_tmpl_col<1, 0>, k_spmv_tmpl_col<1, 1>, k_spmv_tmpl_col<1, 2>},
+      {k_spmv_tmpl_col<2, 0>, k_spmv_tmpl_col<2, 1>, k_spmv_tmpl_col<2, 2>}};
+  kern[c->tmpl.nfar - 1][dot]<<<L.g, WG, 0, (hipStream_t)stream>>>(
+      plan, L.period, n, row_begin, xlen, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals, f32, c->vconst, x, y,
+      xdot, partials, st, L.tail);
 }
 
 void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem, unsigned n,
                       const struct lsb_sell16_dev *c, const double *r, const double *pold, double *pnew, double *x,
                       int xupd, double dc, double *partials, unsigned *npartials, struct lsb_pcg_state *st, int parity,
                       const double *parts2, unsigned nparts2, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned nfar = c->tmpl.nfar;
+  if (period < NXCD || !plan || pold == pnew)
+    errx(EXIT_FAILURE, "lsb_k_pcg_col_px: no column plan (period %u) or one direction buffer", period);
   /* every workgroup resident: three per CU with two far slots per side (<= 168 VGPRs), five with one (<= 96, what
    * the kernel's launch bounds hold it to: with x it needed 102 and only four were resident, the grid's last fifth
    * ran as a second wave).  The plan's walk directions are dealt against this grid (LSB_TMPL_COL_TURN) */
-  const unsigned res = LSB_TMPL_COL_GRID(nfar);
-  const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, nitem, 0, grid_cap && grid_cap < res ? grid_cap : res);
-  if (npartials)
-    *npartials = g;
-  if (period < NXCD || !plan || pold == pnew)
-    errx(EXIT_FAILURE, "lsb_k_pcg_col_px: no column plan (period %u) or one direction buffer", period);
+  const unsigned nfar = c->tmpl.nfar;
+  const sell_launch L = sell_prologue("lsb_k_pcg_col_px", true, c, nitem, n, grid_cap, LSB_TMPL_COL_GRID(nfar), period,
+                                      partials, npartials, NULL);
   /* x, p' and q streamed nontemporally (NT = 3; measured against 0 / 1 / 2 on config 4: 950.5 / 950.3 / 905.7 /
    * 894.1 us per iteration, profiles/r04_px.txt) */
-#define LSB_PX_ARGS                                                                                   \
-  plan, period, n, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals, c->vconst, r, pold, pnew, x, dc, partials, st, \
-      parity, parts2, nparts2
-#define LSB_PX(NF)                                                                                    \
-  do {                                                                                                \
-    if (xupd)                                                                                         \
-      k_pcg_col_px<NF, 3, true><<<g, WG, 0, s>>>(LSB_PX_ARGS);                                        \
-    else                                                                                              \
-      k_pcg_col_px<NF, 3, false><<<g, WG, 0, s>>>(LSB_PX_ARGS);                                       \
-  } while (0)
-  switch (nfar) {
-  case 1: LSB_PX(1); break;
-  case 2: LSB_PX(2); break;
-  default: errx(EXIT_FAILURE, "lsb_k_pcg_col_px: %u far slots per side", nfar);
-  }
-#undef LSB_PX
-#undef LSB_PX_ARGS
+  static decltype(&k_pcg_col_px<1, 3, false>) const kern[2][2] = { /* [nfar - 1][xupd] */
+      {k_pcg_col_px<1, 3, false>, k_pcg_col_px<1, 3, true>},
+      {k_pcg_col_px<2, 3, false>, k_pcg_col_px<2, 3, true>}};
+  kern[nfar - 1][xupd != 0]<<<L.g, WG, 0, (hipStream_t)stream>>>(
+      plan, L.period, n, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals, c->vconst, r, pold, pnew, x, dc,
+      partials, st, parity, parts2, nparts2);
 }
 
 void lsb_k_pcg_col_r(unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem, unsigned n,
                      const struct lsb_sell16_dev *c, const double *p, double *r, double dc, struct lsb_pcg_state *st,
                      int parity, int pbuf, int xtwo, const double *pq_parts, unsigned npq, double *partials2,
                      unsigned *npartials, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  /* five workgroups per CU (launch bounds): the grid of lsb_k_pcg_col_px with one far slot per side */
-  const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SELL, n, nitem, 0, grid_cap && grid_cap < 1280u ? grid_cap : 1280u);
-  *npartials = g;
   if (period < NXCD || !plan)
     errx(EXIT_FAILURE, "lsb_k_pcg_col_r: no column plan (period %u)", period);
-#define LSB_R_ARGS                                                                                                \
-  plan, period, n, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals, c->vconst, p, r, dc, st, parity, pbuf, xtwo, \
-      pq_parts, npq, partials2
-  switch (c->tmpl.nfar) {
-  case 1: k_pcg_col_r<1><<<g, WG, 0, s>>>(LSB_R_ARGS); break;
-  case 2: k_pcg_col_r<2><<<g, WG, 0, s>>>(LSB_R_ARGS); break;
-  default: errx(EXIT_FAILURE, "lsb_k_pcg_col_r: %u far slots per side", c->tmpl.nfar);
-  }
-#undef LSB_R_ARGS
-}
-
-void lsb_k_pcg_xfix(unsigned n, const double *p0, const double *p1, double *x, const struct lsb_pcg_state *st,
-                    void *stream) {
-  k_pcg_xfix<<<lsb_k_blas1_grid(n), WG, 0, (hipStream_t)stream>>>(n, p0, p1, x, st);
-}
-
-void lsb_k_cg1_update(unsigned n, double *u, const double *w, const double *dinv, double dc,
-                      double *p,
-                      double *s, double *x, double *r, struct lsb_pcg_state *st, int parity,
-                      const double *parts_gr, unsigned ngr, const double *parts_d, unsigned nd,
-                      const struct lsb_ar_collect *collect, double *partials2,
-                      unsigned *npartials, void *stream) {
-  const unsigned g = lsb_k_blas1_grid(n);
-  *npartials = g;
-  hipStream_t hs = (hipStream_t)stream;
-  lsb_ar_collect col;
-  memset(&col, 0, sizeof col);
-  if (collect)
-    col = *collect;
-  const bool v2 = aligned16(u) && aligned16(w) && aligned16(dinv) && aligned16(p) &&
-                  aligned16(s) && aligned16(x) && aligned16(r);
-#define LSB_CG1(V, N, U)                                                                  \
-  k_cg1_update<V, N, U><<<g, WG, 0, hs>>>(n, u, w, dinv, dc, p, s, x, r, st, parity, parts_gr, \
-                                          ngr, parts_d, nd, col, partials2)
-  if (!u) { /* implicit u = dc r: r is the gather vector (needs the constant diagonal) */
-    if (dinv)
-      errx(EXIT_FAILURE, "lsb_k_cg1_update: implicit u needs a constant diagonal");
-    if (v2 && (g_blas1_nt & 32))
-      LSB_CG1(true, true, true);
-    else if (v2)
-      LSB_CG1(true, false, true);
-    else
-      LSB_CG1(false, false, true);
-  } else if (v2 && (g_blas1_nt & 32))
-    LSB_CG1(true, true, false);
-  else if (v2)
-    LSB_CG1(true, false, false);
-  else
-    LSB_CG1(false, false, false);
-#undef LSB_CG1
-}
-
-void lsb_k_pcg_update_p(unsigned n, const double *r, const double *dinv, double dc,
-                        const double *pin, double *p, struct lsb_pcg_state *st, int parity,
-                        const double *parts2, unsigned nparts2, void *stream) {
-  const unsigned g = lsb_k_blas1_grid(n);
-  const int x2 = 1; /* two pairs per operand in flight (one: 40.6 against 40.4 us, round 3 -- no difference) */
-  hipStream_t s = (hipStream_t)stream;
-#define LSB_UPD_P(V2, NTR, NTP, X2) \
-  k_pcg_update_p<V2, NTR, NTP, X2><<<g, WG, 0, s>>>(n, r, dinv, dc, pin, p, st, parity, parts2, nparts2)
-#define LSB_UPD_P2(NTR, NTP)          \
-  do {                                \
-    if (big)                          \
-      LSB_UPD_P(true, NTR, NTP, true); \
-    else                              \
-      LSB_UPD_P(true, NTR, NTP, false); \
-  } while (0)
-  if (aligned16(r) && aligned16(dinv) && aligned16(p) && aligned16(pin)) {
-    const bool big = x2 && (size_t)n / 2 > (size_t)g * WG; /* a second pair exists at all */
-    switch ((g_blas1_nt >> 3) & 3) {
-    case 0: LSB_UPD_P2(false, false); break;
-    case 1: LSB_UPD_P2(true, false); break;
-    case 2: LSB_UPD_P2(false, true); break;
-    default: LSB_UPD_P2(true, true); break;
-    }
-  } else {
-    LSB_UPD_P(false, false, false, false);
-  }
-#undef LSB_UPD_P2
-#undef LSB_UPD_P
+  /* five workgroups per CU (launch bounds): the grid of lsb_k_pcg_col_px with one far slot per side */
+  const sell_launch L = sell_prologue("lsb_k_pcg_col_r", true, c, nitem, n, grid_cap, LSB_TMPL_COL_GRID(1), period,
+                                      partials2, npartials, NULL);
+  const auto kern = c->tmpl.nfar == 1 ? k_pcg_col_r<1> : k_pcg_col_r<2>;
+  kern<<<L.g, WG, 0, (hipStream_t)stream>>>(plan, L.period, n, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals,
+                                            c->vconst, p, r, dc, st, parity, pbuf, xtwo, pq_parts, npq, partials2);
 }
 
 } // extern "C"

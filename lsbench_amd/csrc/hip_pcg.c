@@ -143,13 +143,13 @@ static void classic_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, in
     const size_t o = s->row_begin - sv->row_first;
     lsb_k_pcg_update_xr(s->n, s->d_pfull + s->row_begin, s->d_q, DINV(s), d_x + o, s->d_r, s->d_st, parity,
                         sv->multi ? s->d_scal : s->d_parts_pq, sv->multi ? 1u : s->npq, s->d_parts2, &s->np2,
-                        g_stream);
+                        sv->nt_mask, g_stream);
   }
   reduce_rz(sv, 1);
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
     lsb_k_pcg_update_p(s->n, s->d_r, DINV(s), s->d_pfull + s->row_begin, s->d_pfull + s->row_begin, s->d_st,
-                       parity, sv->multi ? s->d_scal + 1 : s->d_parts2, sv->multi ? 1u : s->np2, g_stream);
+                       parity, sv->multi ? s->d_scal + 1 : s->d_parts2, sv->multi ? 1u : s->np2, sv->nt_mask, g_stream);
   }
 }
 
@@ -185,7 +185,7 @@ static void gen_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sa
     const size_t o = s->row_begin - sv->row_first;
     lsb_k_pcg_update_xr(s->n, s->d_pfull + s->row_begin, s->d_q, NULL, 1.0, d_x + o, s->d_r, s->d_st,
                         parity, sv->multi ? s->d_scal : s->d_parts_pq, sv->multi ? 1u : s->npq,
-                        s->d_parts2, &s->np2, g_stream);
+                        s->d_parts2, &s->np2, sv->nt_mask, g_stream);
   }
   precond_apply(sv, 1);
   for (int i = 0; i < sv->nshard; i++) {
@@ -197,7 +197,7 @@ static void gen_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sa
     struct shard *s = &sv->sh[i];
     lsb_k_pcg_update_p(s->n, s->d_z, NULL, 1.0, s->d_pfull + s->row_begin, s->d_pfull + s->row_begin,
                        s->d_st, parity, sv->multi ? s->d_scal + 1 : s->d_parts2,
-                       sv->multi ? 1u : s->np2, g_stream);
+                       sv->multi ? 1u : s->np2, sv->nt_mask, g_stream);
   }
 }
 
@@ -227,7 +227,7 @@ static void fsai_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int p
                      rb[sv->rcur], s->d_parts2, &s->np2, s->d_st, g_stream);
   if (pos & 2) { /* last of the run */
     lsb_k_pcg_update_p(s->n, s->d_z, NULL, 1.0, pb[sv->pcur], pb[0], s->d_st, parity, s->d_parts2, s->np2,
-                       g_stream);
+                       sv->nt_mask, g_stream);
     if (sv->rcur)
       LSB_CHK_HIP(hipMemcpyAsync(s->d_r, s->d_r1, (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice,
                                  g_stream));
@@ -259,10 +259,10 @@ static void subwave_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, in
     sv->pcur ^= 1;
   }
   lsb_k_pcg_update_xr(s->n, buf[sv->pcur], s->d_q, DINV(s), d_x, s->d_r, s->d_st, parity,
-                      s->d_parts_pq, s->npq, s->d_parts2, &s->np2, g_stream);
+                      s->d_parts_pq, s->npq, s->d_parts2, &s->np2, sv->nt_mask, g_stream);
   if (pos & 2) /* last of the run */
     lsb_k_pcg_update_p(s->n, s->d_r, DINV(s), buf[sv->pcur], buf[0], s->d_st, parity, s->d_parts2,
-                       s->np2, g_stream);
+                       s->np2, sv->nt_mask, g_stream);
 }
 
 /* ---- COL: the z-column form of a 3-D stencil with a constant diagonal ----------------------------
@@ -298,7 +298,7 @@ static void col_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int po
   if (pos & 2) { /* last of the run: the pending x update, then the direction back into the gather vector */
     lsb_k_pcg_xfix(s->n, buf[0], buf[1], d_x, s->d_st, g_stream);
     lsb_k_pcg_update_p(s->n, s->d_r, DINV(s), buf[sv->pcur], buf[0], s->d_st, parity, s->d_parts2, s->np2,
-                       g_stream);
+                       sv->nt_mask, g_stream);
   }
 }
 
@@ -339,7 +339,7 @@ static void cg1_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int sa
                      sv->cg1_implicit ? s->d_pfull + s->row_begin : s->d_r, s->d_st, parity,
                      sv->multi ? s->d_scal + 1 : gr_in,
                      sv->multi ? 1u : s->np2, sv->multi ? s->d_scal : s->d_parts_pq,
-                     sv->multi ? 1u : s->npq, sv->ar_pending ? &col : NULL, gr_out, &np2, g_stream);
+                     sv->multi ? 1u : s->npq, sv->ar_pending ? &col : NULL, gr_out, &np2, sv->nt_mask, g_stream);
     /* reduced together with the SpMV's partial sums, in the all-reduce's launch
      * (direct path) or in the one reduction launch in front of it (RCCL) */
     s->ar2_parts = gr_out, s->ar2_n = np2, s->ar2_width = 2;
@@ -486,7 +486,7 @@ void drain_stream(lsb_hip_solver *sv, const char *what) {
 
 /* `reps` local iterations of the classic form on shard 0 (SpMV + the two sweeps; no exchange, no
  * all-reduce, no stop) behind 4 untimed ones: milliseconds */
-static float time_local_iters(lsb_hip_solver *sv, double *d_b, double *d_x, int reps) {
+static float time_local_iters(lsb_hip_solver *sv, double *d_b, double *d_x, int reps, unsigned nt) {
   struct shard *s = &sv->sh[0];
   const unsigned n = s->n;
   double *p = s->d_pfull + s->row_begin;
@@ -499,8 +499,8 @@ static float time_local_iters(lsb_hip_solver *sv, double *d_b, double *d_x, int 
       LSB_CHK_HIP(hipEventRecord(sv->ev_t0, g_stream));
     spmv_shard(s, s->d_pfull, s->d_q, p, s->d_parts_pq, &npq, s->d_st);
     lsb_k_pcg_update_xr(n, p, s->d_q, DINV(s), d_x, s->d_r, s->d_st, i & 1, s->d_parts_pq, npq, s->d_parts2, &np2,
-                        g_stream);
-    lsb_k_pcg_update_p(n, s->d_r, DINV(s), p, p, s->d_st, i & 1, s->d_parts2, np2, g_stream);
+                        nt, g_stream);
+    lsb_k_pcg_update_p(n, s->d_r, DINV(s), p, p, s->d_st, i & 1, s->d_parts2, np2, nt, g_stream);
   }
   LSB_CHK_HIP(hipEventRecord(sv->ev_t1, g_stream));
   LSB_CHK_HIP(hipEventSynchronize(sv->ev_t1));
@@ -562,8 +562,7 @@ void tune_blas1_nt(lsb_hip_solver *sv) {
   int bm = sv->nt_mask;
   const int reps = 20;
   for (unsigned c = 0; c < sizeof cand / sizeof cand[0] && !e; c++) {
-    lsb_k_set_blas1_nt(cand[c]);
-    const float ms = time_local_iters(sv, d_b, d_x, reps);
+    const float ms = time_local_iters(sv, d_b, d_x, reps, cand[c]);
     if (sv->o.verbose > 1)
       fprintf(stderr, "hip_cdna4: nontemporal mask %2d: %.1f us per iteration of the first shard\n", cand[c],
               ms * 1e3f / reps);
@@ -574,7 +573,6 @@ void tune_blas1_nt(lsb_hip_solver *sv) {
    * "none" won */
   if (!e)
     sv->nt_mask = bm == 0 ? 0 : (bm | 32);
-  lsb_k_set_blas1_nt(sv->nt_mask);
   /* leave the shard as the upload left it */
   LSB_CHK_HIP(hipMemsetAsync(s->d_pfull, 0, (size_t)sv->n_glob * sizeof(double), g_stream));
   LSB_CHK_HIP(hipMemsetAsync(s->d_st, 0, sizeof(struct lsb_pcg_state), g_stream));
@@ -944,7 +942,6 @@ int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
                       struct lsb_hip_result *res) {
   if (sv->o.krylov == LSB_KRYLOV_GMRES)
     return gmres_solve_dev(sv, d_b, d_x, res);
-  lsb_k_set_blas1_nt(sv->nt_mask); /* this solver's choice (the launchers read a per-thread word) */
   const double t0 = wall_seconds();
   struct lsb_hip_result r;
   /* Mixed precision: the CG runs see S~ = fp32(S) (fp64 vectors and sums) and

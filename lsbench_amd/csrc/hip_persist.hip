@@ -7,7 +7,7 @@
 // the whole solve:
 //   * workgroup g owns a contiguous row range; its rows of the CSR are copied
 //     into LDS once, and x, r, u = D^-1 r, p, s of its rows live in registers;
-//   * an iteration is the single-reduction form of hip_kernels.hip's
+//   * an iteration is the single-reduction form of hip_sweeps.hip's
 //     k_cg1_update (Chronopoulos-Gear: same iterates as PCG), so that only TWO
 //     grid-wide synchronisations are needed:
 //        [all]  copy the shared vector u into LDS; w = S u on own rows;

@@ -958,7 +958,7 @@ void sell_launch(struct shard *s, unsigned s0, unsigned ns, const double *xfull,
     /* (a z-column flavour's grid was timed for the walk -- 3-4 workgroups per CU; the launches that go through
      * k_spmv_tmpl instead -- Chebyshev epilogue, boundary parts of a split SpMV -- take that kernel's own 6 per CU:
      * config 3 with Chebyshev(16) 941 -> 811 ms per solve) */
-    lsb_k_spmv_tmpl(s->sp_flags | f32, (s->sp_flags & LSB_SP_COL) ? 1536u : s->sp_grid, s->sp_period, &s->c16, s0, ns,
+    lsb_k_spmv_tmpl(s->sp_flags | f32, (s->sp_flags & LSB_SP_COL) ? LSB_SELL_GRID : s->sp_grid, s->sp_period, &s->c16, s0, ns,
                     s->n, s->row_begin, s->n_glob, xfull, y, xdot, partials, np, st, &s->tail, &s->epi, g_stream);
   else if (s->sell_form == SELL_16)
     lsb_k_spmv_sell(s->sp_flags | f32, s->sp_grid, s->sp_period, s->c16.sptr, s0, ns, s->n, s->row_begin, s->n_glob,
@@ -1097,7 +1097,7 @@ static void time_spmv(lsb_hip_solver *sv, struct shard *s) {
       CAND(LSB_SPMV_SELL, c16 | LSB_SP_NT, grid0, 0);
       CAND(LSB_SPMV_SELL, c16, grid0, 0);
       if (o->spmv_grid <= 0)
-        CAND(LSB_SPMV_SELL, c16 | LSB_SP_NT, 1536, 0);
+        CAND(LSB_SPMV_SELL, c16 | LSB_SP_NT, LSB_SELL_GRID, 0);
       if (period) { /* every XCD an eighth of every plane */
         CAND(LSB_SPMV_SELL, c16 | LSB_SP_NT, grid0, period);
         CAND(LSB_SPMV_SELL, c16, grid0, period);
@@ -1107,16 +1107,16 @@ static void time_spmv(lsb_hip_solver *sv, struct shard *s) {
         const unsigned f = c16 | LSB_SP_NT | LSB_SP_TMPL;
         CAND(LSB_SPMV_SELL, f, grid0, 0);
         if (o->spmv_grid <= 0)
-          CAND(LSB_SPMV_SELL, f, 1536, 0);
+          CAND(LSB_SPMV_SELL, f, LSB_SELL_GRID, 0);
         if (period) {
           CAND(LSB_SPMV_SELL, f, grid0, period);
           if (o->spmv_grid <= 0)
-            CAND(LSB_SPMV_SELL, f, 1536, period);
+            CAND(LSB_SPMV_SELL, f, LSB_SELL_GRID, period);
         }
         /* the same with y parked in LDS and stored one turn later (k_spmv_tmpl<.., DEFER>): pays where
          * the vectors come out of HBM, costs ~2 us where they sit in the Infinity Cache */
         if (s->c16.tmpl.nfar >= 1 && s->nnz >= 16000000ull) {
-          const unsigned fd = f | LSB_SP_DEFER, gd = o->spmv_grid <= 0 ? 1536u : grid0;
+          const unsigned fd = f | LSB_SP_DEFER, gd = o->spmv_grid <= 0 ? LSB_SELL_GRID : grid0;
           CAND(LSB_SPMV_SELL, fd, gd, 0);
           if (period)
             CAND(LSB_SPMV_SELL, fd, gd, period);

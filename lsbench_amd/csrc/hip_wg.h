@@ -1,4 +1,4 @@
-// Workgroup-level helpers shared by the kernel files (hip_kernels.hip, hip_fsai.hip): fixed-order
+// Workgroup-level helpers shared by the kernel files (hip_kernels.hip, hip_sweeps.hip, hip_fsai.hip): fixed-order
 // reductions (every thread returns with the same bits; a result depends on the number of partial
 // records only, never on timing) and the XCD-contiguous workgroup numbering.
 #ifndef LSB_HIP_WG_H

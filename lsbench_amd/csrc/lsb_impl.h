@@ -1,7 +1,7 @@
 /*
  * Internal header of liblsbench_hip.so: the role src/lsbench-impl.h plays in
  * the reference (struct layouts + backend prototypes), plus the launcher
- * prototypes of the HIP shim (hip_kernels.hip) that hip_cdna4.c calls.
+ * prototypes of the HIP shim (hip_kernels.hip, hip_sweeps.hip) that hip_cdna4.c calls.
  */
 #ifndef LSB_IMPL_H
 #define LSB_IMPL_H
@@ -90,7 +90,7 @@ struct lsb_gmres_state {
 /* Non-zeros staged in LDS per row block of the adaptive SpMV (16 KiB). */
 #define LSB_BLOCK_NNZ 2048
 
-/* ---- HIP shim: kernel launchers (hip_kernels.hip) ------------------------
+/* ---- HIP shim: kernel launchers (hip_kernels.hip, hip_sweeps.hip) ---------
  * All take raw device pointers and a hipStream_t as void*.  `st` may be NULL
  * for the stand-alone (non-PCG) use of a kernel; when given, a non-zero
  * st->status turns the launch into a no-op on the device. */
@@ -197,7 +197,8 @@ void lsb_k_jacobi_sweep(unsigned n, double w, const double *dinv,
                         const double *b, const double *ax, double *x,
                         void *stream);
 /* PCG fused sweeps */
-/* dinv == NULL: the Jacobi diagonal is the constant dc (not read from memory) */
+/* dinv == NULL: the Jacobi diagonal is the constant dc (not read from memory).  nt: which operands
+ * the sweeps load nontemporal -- bit 0 x, 1 p and q, 2 r (update_xr); 3 r, 4 p (update_p); 5 cg1_update */
 void lsb_k_pcg_init(unsigned n, const double *b, const double *dinv, double dc, double *x,
                     double *r, double *p, double *partials2,
                     unsigned *npartials, void *stream);
@@ -208,7 +209,7 @@ void lsb_k_pcg_update_xr(unsigned n, const double *p, const double *q,
                          const double *dinv, double dc, double *x, double *r,
                          struct lsb_pcg_state *st, int parity,
                          const double *pq_parts, unsigned npq,
-                         double *partials2, unsigned *npartials, void *stream);
+                         double *partials2, unsigned *npartials, unsigned nt, void *stream);
 void lsb_k_spmv_subwave_p(unsigned n, const int *offs, const int *cols, const double *vals,
                           unsigned lanes_per_row, const double *r, const double *dinv, double dc,
                           const double *pold, double *pnew, double *y, double *partials,
@@ -216,17 +217,14 @@ void lsb_k_spmv_subwave_p(unsigned n, const int *offs, const int *cols, const do
                           const double *parts2, unsigned nparts2, void *stream);
 void lsb_k_pcg_update_p(unsigned n, const double *r, const double *dinv, double dc,
                         const double *pin, double *p, struct lsb_pcg_state *st, int parity,
-                        const double *parts2, unsigned nparts2, void *stream);
+                        const double *parts2, unsigned nparts2, unsigned nt, void *stream);
 void lsb_k_cg1_update(unsigned n, double *u, const double *w, const double *dinv, double dc,
                       double *p,
                       double *s, double *x, double *r, struct lsb_pcg_state *st, int parity,
                       const double *parts_gr, unsigned ngr, const double *parts_d, unsigned nd,
                       const struct lsb_ar_collect *collect, double *partials2, unsigned *npartials,
-                      void *stream);
+                      unsigned nt, void *stream);
 unsigned lsb_k_blas1_grid(unsigned n);
-void lsb_k_set_blas1_nt(int on); /* mask: bit 0 x, 1 p and q, 2 r (k_pcg_update_xr); 3 r, 4 p (k_pcg_update_p);
-                                    5 k_cg1_update; 1 = all; per host thread */
-int lsb_k_get_blas1_nt(void);
 void lsb_k_fill_index(unsigned n, unsigned first, double *v, void *stream);
 void lsb_k_perm_gather(unsigned n, const int *perm, const double *src, double *dst,
                        void *stream);

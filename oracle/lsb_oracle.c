@@ -633,7 +633,7 @@ done:
 
 /*
  * Single-reduction CG (Chronopoulos & Gear 1989), Jacobi-preconditioned,
- * x0 = 0 -- the recurrences of k_cg1_update in lsbench_amd/csrc/hip_kernels.hip,
+ * x0 = 0 -- the recurrences of k_cg1_update in lsbench_amd/csrc/hip_sweeps.hip,
  * stated sequentially:
  *   r = b; u = D^-1 r; w = A u; g = r.u; d = w.u
  *   repeat: stop if r.r <= tol^2 b.b

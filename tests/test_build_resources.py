@@ -19,22 +19,26 @@ CSRC = os.path.join(ROOT, "lsbench_amd", "csrc")
                     reason="hipcc not installed")
 def test_hot_kernels_have_no_spills_and_full_occupancy(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-c",
-                        os.path.join(CSRC, "hip_kernels.hip"), "-o", str(tmp_path / "k.o"),
-                        "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    info, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            info[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and name:
-            info[name][m.group(1).strip()] = int(m.group(2))
+    info = {}
+    for src in ("hip_kernels.hip", "hip_sweeps.hip"):   # the SpMV kernels; the BLAS-1 / PCG sweeps
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
+                            "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-c",
+                            os.path.join(CSRC, src), "-o", str(tmp_path / (src + ".o")),
+                            "-Rpass-analysis=kernel-resource-usage"],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        name = None
+        for line in r.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+                assert name not in info, name
+                info[name] = {}
+                continue
+            m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+            if m and name:
+                info[name][m.group(1).strip()] = int(m.group(2))
+    assert any("k_pcg_update_xr" in k for k in info) and any("k_spmv_sell" in k for k in info)
     hot = {k: v for k, v in info.items()
            if re.search(r"k_spmv_adaptive|k_pcg_update_xr|k_pcg_update_p|k_pcg_init", k)}
     assert len([k for k in hot if "k_spmv_adaptive" in k]) == 8  # four flavours x {fp64, fp32 values}

@@ -71,8 +71,10 @@ def test_two_launch_kernels_fit_their_resident_grid(tmp_path):
             assert v["ScratchSize"] == 0 and v["LDS Size"] <= 192 and v["Occupancy"] >= 5, (k, v)
 
 
-def test_launch_bounds_and_grid_caps_agree():
-    """the occupancy the kernels promise the compiler is the one their launchers cap the grid at"""
+def test_launch_bounds_and_header_grid_caps_agree():
+    """the occupancy the kernels promise the compiler is the one their launchers cap the grid at: both
+    launchers take the cap from LSB_TMPL_COL_GRID, which the header pins to GRID, and spell no grid of
+    their own"""
     with open(os.path.join(CSRC, "hip_kernels.hip")) as f:
         src = f.read()
     with open(os.path.join(ROOT, "include", "lsbench_hip.h")) as f:
@@ -84,4 +86,6 @@ def test_launch_bounds_and_grid_caps_agree():
     m = re.search(r"__launch_bounds__\(WG, (\d)\) void k_pcg_col_r\(", src)
     assert m and int(m.group(1)) * CUS == GRID[1]
     assert "LSB_TMPL_COL_GRID(nfar)" in _grid_cap(src, "lsb_k_pcg_col_px")
-    assert "1280u" in _grid_cap(src, "lsb_k_pcg_col_r")
+    assert "LSB_TMPL_COL_GRID(1)" in _grid_cap(src, "lsb_k_pcg_col_r")   # pinned to GRID[1] above
+    for launcher in ("lsb_k_pcg_col_px", "lsb_k_pcg_col_r"):
+        assert not re.search(r"\b(%d|%d)u?\b" % (GRID[1], GRID[2]), _grid_cap(src, launcher)), launcher
