@@ -11,12 +11,19 @@ C library, launched as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
+A plain run does only what `value` needs: it sets the workload up, warms up, times
+the steps, writes --dump-outputs if asked, refuses a solve whose residual recomputed
+from x misses the tolerance (one SpMV) and prints the line (its roofline from the
+SpMV launches sampled inside the timed solves).  Everything that takes runs of its
+own -- the CPU baseline, the sub-records below, the SpMV timed back to back -- comes
+with --full, where each can still be switched off by its own option (--cfg4 0, ...).
+
 Default workload = BASELINE.json configs[2], the roofline run: 5-point 2-D
-Laplacian, 3162^2 = 9,998,244 rows, 49,978,572 nnz.  Every line also carries a
+Laplacian, 3162^2 = 9,998,244 rows, 49,978,572 nnz.  A --full line also carries a
 `cfg4` sub-record: configs[3] (7-point 400^3, 64 M rows, the configuration the
 ">= 6x at 8 GPUs" target is stated on) solved on the same N GPUs right after the
 headline -- take the 1 -> 8 ratio of cfg4.value from the N = 1 and N = 8 lines.
-At N = 1 the line also carries `general_values`: the SAME 3162^2 pattern with
+At N = 1 it also carries `general_values`: the SAME 3162^2 pattern with
 general values (`lap2d:...,coef=1`, one hashed weight per grid edge), i.e. the
 thing the metric names -- an fp64 CSR SpMV whose values must be streamed -- with
 its roofline fraction on SURVEY 8(d)'s CSR byte count.  The constant-coefficient
@@ -32,13 +39,15 @@ Others:
 The JSON line also carries
   roofline      dominant kernel (SpMV): bytes the stored layout must move per launch
                 / mean launch time, HIP events on the library's stream, sampled
-                INSIDE the timed solves; peak 8000 GB/s
-  cpu_baseline  the oracle's OpenMP Jacobi-PCG (a CPU port of the same
+                INSIDE the timed solves; peak 8000 GB/s.  Where the solve samples
+                no launch (small operators: graph replay), only a --full run times
+                the SpMV after the solves; a plain line then has roofline null
+  cpu_baseline  (--full) the oracle's OpenMP Jacobi-PCG (a CPU port of the same
                 algorithm, oracle/lsb_oracle.c) on this host's cores, timed on
                 a bounded number of iterations of the SAME operator and scaled
                 to whole solves; rank 0, N = 1 only.  CHOLMOD, the reference's
                 own CPU solver, is not installable here.
-and, at N = 1, one sub-record per remaining BASELINE.json config and claim:
+and, with --full at N = 1, one sub-record per remaining BASELINE.json config and claim:
   csr_kernel    SURVEY 8(d) to the letter: on config 3's pattern with general values,
                 the kernels that stream 12 B per non-zero -- k_spmv_adaptive on the CSR
                 arrays (offs / cols / vals) and k_spmv_sell with 32-bit columns --
@@ -105,10 +114,14 @@ def parse():
     p.add_argument("--only", default="",
                    help="comma list of sub-records to run INSTEAD of the headline (csr_kernel, cfg2, cfg5): "
                         "one JSON line with just those -- what the PMC / trace passes profile")
-    p.add_argument("--csr-kernel", type=int, default=1, help="N = 1: 1 = the line carries `csr_kernel`")
-    p.add_argument("--cfg2", type=int, default=1, help="N = 1: 1 = the line carries `cfg2` (configs[1])")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline value does not need: the CPU baseline, the sub-records "
+                        "(cfg4, general_values, csr_kernel, cfg2, cfg5) and the SpMV timed back to back "
+                        "(roofline.back_to_back_launch_ms; the roofline itself where the solve samples no launch)")
+    p.add_argument("--csr-kernel", type=int, default=1, help="--full, N = 1: 1 = the line carries `csr_kernel`")
+    p.add_argument("--cfg2", type=int, default=1, help="--full, N = 1: 1 = the line carries `cfg2` (configs[1])")
     p.add_argument("--cfg2-trials", type=int, default=100)
-    p.add_argument("--cfg5", type=int, default=1, help="N = 1: 1 = the line carries `cfg5` (configs[4])")
+    p.add_argument("--cfg5", type=int, default=1, help="--full, N = 1: 1 = the line carries `cfg5` (configs[4])")
     p.add_argument("--comm", default="auto", choices=["auto", "rccl", "p2p"],
                    help="N>1: auto = direct xGMI stores where they pass the self-test and beat "
                         "RCCL; rccl / p2p force one")
@@ -121,14 +134,14 @@ def parse():
                    help="experiment mode: run exactly this many iterations per step "
                         "(tol = 0); the line is marked and is NOT a solves/s figure")
     p.add_argument("--cpu-seconds", type=float, default=12.0,
-                   help="budget of the CPU baseline leg (0 = skip)")
+                   help="--full: budget of the CPU baseline leg (0 = skip)")
     p.add_argument("--cfg4", type=int, default=1,
-                   help="1 = every line also carries a `cfg4` sub-record: BASELINE.json configs[3] "
+                   help="--full: 1 = every line also carries a `cfg4` sub-record: BASELINE.json configs[3] "
                         "(7-point 400^3, 64 M rows) solved --cfg4-steps times on the same N GPUs -- the "
                         "workload the 8-vs-1 GPU target is stated on; 0 = skip it")
     p.add_argument("--cfg4-steps", type=int, default=2)
     p.add_argument("--general-values", type=int, default=1,
-                   help="1 = at N = 1 the line also carries `general_values`: config 3's pattern with "
+                   help="--full: 1 = at N = 1 the line also carries `general_values`: config 3's pattern with "
                         "general values (lap2d:...,coef=1) -- the SpMV whose values must be streamed, "
                         "roofline fraction on SURVEY 8(d)'s CSR byte count; 0 = skip it")
     p.add_argument("--general-values-steps", type=int, default=1)
@@ -559,6 +572,7 @@ def run_workload(a, c, workload, steps, warmup, cpu_leg, dump=""):
                  % (true_relres, tol))
 
     # ---- dominant kernel: SpMV, HIP events on the library's stream ---------
+    spmv_avg_ms = None  # (a plain run times no launches of its own: no figure where the solve sampled none)
     if spmv_n:
         spmv_avg_ms = spmv_ms / spmv_n  # sampled inside the timed solves
         how = "hipEvent pairs around %d SpMV launches inside the timed solves" % spmv_n
@@ -571,12 +585,10 @@ def run_workload(a, c, workload, steps, warmup, cpu_leg, dump=""):
                                                solver.spmv_flags, solver.spmv_period)
             how = ("hipEvent pairs around %d launches of k_pcg_col_px inside the timed solves (the launch that carries "
                    "the SpMV: p' = dc r + beta p, x += alpha p, q = S p', p'.q)" % spmv_n)
-    else:
+    elif a.full:
         fused_p = False  # (what is timed below is the plain SpMV launch)
         spmv_avg_ms = solver.time_spmv(20, 200)  # graph replay: events do not fit inside
         how = "hipEvents around 200 back-to-back launches after the timed solves"
-    gbps = bytes_alg / spmv_avg_ms / 1e6
-    gbps_csr = bytes_spmv / spmv_avg_ms / 1e6
     it_basis = ("SpMV layout bytes + every vector pass of the sweeps behind it, on wall-clock "
                 "time per iteration (launch gaps, reductions and the stop test included)")
     if a.krylov == "gmres" and layout_bytes and iters:
@@ -587,7 +599,41 @@ def run_workload(a, c, workload, steps, warmup, cpu_leg, dump=""):
                     "time per inner step" % a.restart)
     # SURVEY.md section 8(d)'s protocol as well: >= 100 back-to-back launches after >= 10
     # warm-ups (warmer caches than inside the solve; reported, not used for `frac`)
-    b2b_ms = solver.time_spmv(10, 100) if spmv_n else spmv_avg_ms
+    b2b_ms = (solver.time_spmv(10, 100) if spmv_n else spmv_avg_ms) if a.full else None
+    roofline = None
+    if spmv_avg_ms is not None:
+        gbps = bytes_alg / spmv_avg_ms / 1e6
+        gbps_csr = bytes_spmv / spmv_avg_ms / 1e6
+        roofline = {"bound": "hbm", "achieved": gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": gbps / HBM_PEAK_GBPS, "traffic": traffic,
+                    # fabric-side traffic (L2 <-> Infinity Cache / HBM) of the committed profile of this
+                    # command, these kernel sources and this flavour / this run's launch time, over peak
+                    "frac_fabric": (traffic / spmv_avg_ms / 1e6 / HBM_PEAK_GBPS) if traffic else None,
+                    "traffic_source": traffic_src, "traffic_note": FABRIC_NOTE,
+                    "algorithmic_bytes": bytes_alg,
+                    "bytes_basis": ("layout: what the stored layout must move in one launch -- its index / code / "
+                                    "slot / template arrays and the values it keeps (value_slots kept / all: one "
+                                    "value per slot whose 128 entries are equal), x once, y once"
+                                    + (" -- here, averaged over a run's even and odd iterations: r, p in and p' out, every second "
+                                       "time also x and the direction before in and x out (q = S p' is not stored: the launch "
+                                       "that updates r forms it again); the direction update and the x update ride in this "
+                                       "launch (two launches and 60 instead of 88 B per row and iteration)"
+                                       if fused_p else "")
+                                    + "; SURVEY 8(d)'s CSR count is under csr_count (a CSR kernel's bytes: this "
+                                    "layout moves fewer, so that ratio is not a fraction of anything)"
+                                    if bytes_alg != bytes_spmv else
+                                    "SURVEY 8(d): 12 B per non-zero + 20 B per row + 4 (values streamed)"),
+                    "direction_update_in_this_launch": fused_p,
+                    "csr_count": {"bytes": bytes_spmv, "GBps": gbps_csr, "ratio_to_peak": gbps_csr / HBM_PEAK_GBPS},
+                    "layout_bytes": layout_bytes,
+                    "value_slots": dict(zip(("kept", "all"), vslots)),
+                    "kernel": kernel + (" (panels)" if solver.spmv_variant == la.SPMV_PANEL else "") + " (fused p.q)",
+                    "launch_ms": spmv_avg_ms, "back_to_back_launch_ms": b2b_ms,
+                    "back_to_back_kernel": (("%s (y = S x alone, %d B)" % (spmv_kernel, layout_bytes))
+                                            if fused_p else kernel) if b2b_ms is not None else None,
+                    "line_padding_rows": solver.padded,
+                    "spmv_flags": solver.spmv_flags, "xcd_period_slices": solver.spmv_period,
+                    "kernels_sha16": kernels_sha16(), "measured": how}
     n_tot_nnz = nnz_loc
     if c.dist_on:
         tt = torch.tensor([float(nnz_loc)], dtype=torch.float64, device=c.cdev)
@@ -599,13 +645,14 @@ def run_workload(a, c, workload, steps, warmup, cpu_leg, dump=""):
     if c.dist_on:
         # load balance of a sharded line: every rank's own wall-clock per iteration (before the MAX),
         # its SpMV launch inside the solve, its rows and non-zeros
-        mine = torch.tensor([dt_own / max(iters, 1) * 1e6, spmv_avg_ms * 1e3, float(nl), float(nnz_loc)],
+        mine = torch.tensor([dt_own / max(iters, 1) * 1e6, (spmv_avg_ms or 0.0) * 1e3, float(nl), float(nnz_loc)],
                             dtype=torch.float64, device=c.cdev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         allr = torch.stack(allr).cpu()
         per_rank = {"iteration_us": {"min": float(allr[:, 0].min()), "max": float(allr[:, 0].max())},
-                    "spmv_us": {"min": float(allr[:, 1].min()), "max": float(allr[:, 1].max())},
+                    "spmv_us": ({"min": float(allr[:, 1].min()), "max": float(allr[:, 1].max())}
+                                if spmv_avg_ms is not None else None),
                     "rows": [int(v) for v in allr[:, 2]], "nnz": [int(v) for v in allr[:, 3]]}
     comm.update(solver.comm_plan)  # rccl_ranks = ncclCommCount; rank 0's halo plan
     rec = {
@@ -636,37 +683,7 @@ def run_workload(a, c, workload, steps, warmup, cpu_leg, dump=""):
                        "frac": it_bytes * iters / dt / 1e9 / HBM_PEAK_GBPS,
                        "basis": it_basis}
                       if it_bytes and iters and world == 1 else None),
-        "comm": comm, "per_rank": per_rank,
-        "roofline": {"bound": "hbm", "achieved": gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": gbps / HBM_PEAK_GBPS, "traffic": traffic,
-                     # fabric-side traffic (L2 <-> Infinity Cache / HBM) of the committed profile of this
-                     # command, these kernel sources and this flavour / this run's launch time, over peak
-                     "frac_fabric": (traffic / spmv_avg_ms / 1e6 / HBM_PEAK_GBPS) if traffic else None,
-                     "traffic_source": traffic_src, "traffic_note": FABRIC_NOTE,
-                     "algorithmic_bytes": bytes_alg,
-                     "bytes_basis": ("layout: what the stored layout must move in one launch -- its index / code / "
-                                     "slot / template arrays and the values it keeps (value_slots kept / all: one "
-                                     "value per slot whose 128 entries are equal), x once, y once"
-                                     + (" -- here, averaged over a run's even and odd iterations: r, p in and p' out, every second "
-                                        "time also x and the direction before in and x out (q = S p' is not stored: the launch "
-                                        "that updates r forms it again); the direction update and the x update ride in this "
-                                        "launch (two launches and 60 instead of 88 B per row and iteration)"
-                                        if fused_p else "")
-                                     + "; SURVEY 8(d)'s CSR count is under csr_count (a CSR kernel's bytes: this "
-                                     "layout moves fewer, so that ratio is not a fraction of anything)"
-                                     if bytes_alg != bytes_spmv else
-                                     "SURVEY 8(d): 12 B per non-zero + 20 B per row + 4 (values streamed)"),
-                     "direction_update_in_this_launch": fused_p,
-                     "csr_count": {"bytes": bytes_spmv, "GBps": gbps_csr, "ratio_to_peak": gbps_csr / HBM_PEAK_GBPS},
-                     "layout_bytes": layout_bytes,
-                     "value_slots": dict(zip(("kept", "all"), vslots)),
-                     "kernel": kernel + (" (panels)" if solver.spmv_variant == la.SPMV_PANEL else "") + " (fused p.q)",
-                     "launch_ms": spmv_avg_ms, "back_to_back_launch_ms": b2b_ms,
-                     "back_to_back_kernel": ("%s (y = S x alone, %d B)" % (spmv_kernel, layout_bytes))
-                     if fused_p else kernel,
-                     "line_padding_rows": solver.padded,
-                     "spmv_flags": solver.spmv_flags, "xcd_period_slices": solver.spmv_period,
-                     "kernels_sha16": kernels_sha16(), "measured": how},
+        "comm": comm, "per_rank": per_rank, "roofline": roofline,
     }
     if a.fixed_iters > 0:
         rec["metric"] = "EXPERIMENT_fixed_%d_iterations_per_step" % a.fixed_iters
@@ -793,9 +810,9 @@ def main():
                 line[k] = f(a, c)
         print(json.dumps(line), flush=True)
         return
-    line = run_workload(a, c, a.workload, a.steps, a.warmup, cpu_leg=True, dump=a.dump_outputs)
+    line = run_workload(a, c, a.workload, a.steps, a.warmup, cpu_leg=a.full, dump=a.dump_outputs)
     spec = WORKLOADS.get(a.workload, a.workload)
-    if a.cfg4 and line["metric"] == "cg_solves_per_sec" and not spec.startswith("lap3d"):
+    if a.full and a.cfg4 and line["metric"] == "cg_solves_per_sec" and not spec.startswith("lap3d"):
         r4 = run_workload(a, c, "lap3d", a.cfg4_steps, 1, cpu_leg=False)
         line["cfg4"] = {k: r4[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup",
                                            "ms_per_step", "scaling", "iterations_per_sec",
@@ -807,7 +824,7 @@ def main():
                                                                "value_slots", "xcd_period_slices", "spmv_flags")}
         line["cfg4"]["note"] = ("BASELINE.json configs[3] on the same %d GPU(s): strong scaling of ONE 64 M-row "
                                 "operator; the >= 6x target is cfg4.value(N=8) / cfg4.value(N=1)" % c.world)
-    if (a.general_values and c.world == 1 and line["metric"] == "cg_solves_per_sec"
+    if (a.full and a.general_values and c.world == 1 and line["metric"] == "cg_solves_per_sec"
             and spec == WORKLOADS["lap2d"] and a.precision == "fp64" and a.fixed_iters == 0):
         rg = run_workload(a, c, "lap2d_coef", a.general_values_steps, 1, cpu_leg=False)
         line["general_values"] = {k: rg[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup",
@@ -825,9 +842,9 @@ def main():
             "is on the bytes the kernel's layout moves (8 B of value per entry, no column index where a slot is "
             "one diagonal); spmv.csr_count is the same launch on SURVEY 8(d)'s CSR byte count (12 B per entry), "
             "the figure a CSR kernel would have to reach.")
-    if (c.world == 1 and not c.dist_on and line["metric"] == "cg_solves_per_sec" and spec == WORKLOADS["lap2d"]
+    if (a.full and c.world == 1 and not c.dist_on and line["metric"] == "cg_solves_per_sec" and spec == WORKLOADS["lap2d"]
             and a.precision == "fp64" and a.fixed_iters == 0 and a.krylov != "gmres" and a.precond == "jacobi"):
-        # the remaining BASELINE.json configs and the SURVEY 8(d) SpMV figure, driver-run (N = 1)
+        # the remaining BASELINE.json configs and the SURVEY 8(d) SpMV figure (N = 1)
         for k, f in subs:
             if getattr(a, k):
                 line[k] = f(a, c)

@@ -91,11 +91,12 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     """bench.py's N > 1 branch end to end (gloo for torch.distributed, the test
     double for the library's collectives): same iteration count as N = 1.  Both
     lines dump x (--dump-outputs): the whole solution, in the caller's row order,
-    gathered over the ranks for N = 2."""
+    gathered over the ranks for N = 2.  --full: the solve of this small operator
+    samples no SpMV launch, so per_rank.spmv_us comes from launches timed after it."""
     import scipy.sparse as sps
     spec = "lap2d:nx=700,ny=500"
     common = ["--workload", spec, "--tol", "1e-8", "--steps", "2", "--warmup", "1",
-              "--cpu-seconds", "0", "--cfg4", "0"]
+              "--full", "--cpu-seconds", "0", "--cfg4", "0"]
     env = _env()
     env["LSB_BENCH_BACKEND"] = "gloo"
     env["LSB_BENCH_ONE_GPU"] = "1"

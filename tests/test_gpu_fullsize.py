@@ -189,7 +189,7 @@ def test_lap3d_64m_rows(hip):
 
 
 def test_bench_line_contract(tmp_path):
-    """`python bench.py` end to end at full size: ONE JSON line with the contract's keys, the
+    """`python bench.py --full` end to end at full size: ONE JSON line with the contract's keys, the
     roofline and cpu_baseline objects, a solve that is converged on the residual recomputed from
     x -- and a sub-record for every other BASELINE.json config (cfg2, cfg4, cfg5; general_values)
     plus csr_kernel, the SpMV figure that follows SURVEY 8(d) to the letter.  --dump-outputs
@@ -199,7 +199,7 @@ def test_bench_line_contract(tmp_path):
     import subprocess
     import sys
     from conftest import ROOT
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1",
                         "--cpu-seconds", "3", "--cfg4-steps", "1", "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -292,6 +292,48 @@ def test_bench_line_contract(tmp_path):
     assert c5["metric"] == "fp64_csr_spmv_GBps" and c5["config"]["rows"] == 8000000
     assert c5["spmv"]["algorithmic_bytes"] == 12 * c5["config"]["nnz_per_gpu"] + 20 * 8000000 + 4
     assert 0.1 < c5["spmv"]["frac"] <= 1.0 and abs(c5["value"] - c5["spmv"]["achieved"]) < 1e-6 * c5["value"]
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`python bench.py` without --full: the headline line with the contract's keys, its roofline
+    from the launches sampled inside the timed solves and its dump -- none of what takes runs of its
+    own (CPU baseline, sub-records, the SpMV back to back).  The whole process, start to exit, spends
+    at most 30 s outside its warm-up and timed steps.  A small operator, whose solve samples no
+    launch, gets no roofline in a plain line."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import time
+    from conftest import ROOT
+    t = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "cg_solves_per_sec" and d["unit"] == "solves/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-9 * d["value"]
+    assert d["config"]["rows"] == 9998244 and d["config"]["true_relres"] <= d["config"]["tol"] * (1 + 1e-6)
+    for k in ("cpu_baseline", "cfg4", "general_values", "csr_kernel", "cfg2", "cfg5"):
+        assert k not in d, k
+    rf = d["roofline"]
+    assert rf["kernel"].startswith("k_pcg_col_px") and 0.2 < rf["frac"] <= 1.0 and rf["launch_ms"] > 0
+    assert rf["back_to_back_launch_ms"] is None and rf["back_to_back_kernel"] is None
+    x = np.load(tmp_path / "x.npy")
+    assert sorted(os.listdir(tmp_path)) == ["x.npy"] and x.dtype == np.float64 and x.shape == (1 << 22,)
+    assert np.isfinite(x).all() and x.max() > 0
+    assert wall - (2 + 1) * d["ms_per_step"] * 1e-3 <= 30.0, (wall, d["ms_per_step"])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload",
+                        "file:tests/golden/matrices/xn3b_A_18.txt.gz", "--tol", "1e-12", "--steps", "3"],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["config"]["rows"] == 3461 and d["config"]["true_relres"] <= 1e-12 * (1 + 1e-6)
+    assert d["roofline"] is None and "cpu_baseline" not in d and "cpu_direct_baseline" not in d
 
 
 def test_powerlaw_spd_8m_rows_cg(hip):

@@ -976,3 +976,51 @@ def test_bench_dump_sample_is_fixed_and_fits_the_budget(monkeypatch):
         stratum = np.arange(K, dtype=np.int64)
         assert ((stratum * n // K <= idx) & (idx < (stratum + 1) * n // K)).all()
         assert np.array_equal(idx, bench.dump_sample(n))
+
+
+def test_bench_plain_run_leaves_the_rest_to_full(monkeypatch, capsys):
+    """bench.py without --full runs the headline alone: no CPU leg, no sub-record.  --full adds the
+    CPU leg and every sub-record of the default N = 1 line, each still switched off by its own option.
+    The runs themselves are stand-ins here: what is checked is what main() asks for."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Rec(dict):
+        def __missing__(self, k):
+            return None
+
+    calls = []
+
+    def run_workload(a, c, workload, steps, warmup, cpu_leg, dump=""):
+        calls.append((workload, steps, warmup, cpu_leg, dump))
+        return Rec(metric="cg_solves_per_sec", roofline=Rec())
+
+    def setup_ranks(a):
+        c = bench.Ctx()
+        c.rank, c.world, c.dist_on = 0, 1, False
+        return c
+
+    monkeypatch.setattr(bench, "setup_ranks", setup_ranks)
+    monkeypatch.setattr(bench, "run_workload", run_workload)
+    for k in ("csr_kernel", "cfg2", "cfg5"):
+        monkeypatch.setattr(bench, k + "_record", lambda a, c, k=k: calls.append(k) or {"value": 1.0})
+
+    def line(*argv):
+        calls.clear()
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"] + list(argv))
+        bench.main()
+        return json.loads(capsys.readouterr().out.splitlines()[-1])
+
+    subs = {"cfg4", "general_values", "csr_kernel", "cfg2", "cfg5"}
+    d = line("--dump-outputs", "out")
+    assert calls == [("lap2d", 4, 2, False, "out")] and not subs & set(d)
+    d = line("--full")
+    assert calls == [("lap2d", 4, 2, True, ""), ("lap3d", 2, 1, False, ""), ("lap2d_coef", 1, 1, False, ""),
+                     "csr_kernel", "cfg2", "cfg5"] and subs <= set(d)
+    d = line("--full", "--cfg4", "0", "--cfg2", "0")
+    assert calls == [("lap2d", 4, 2, True, ""), ("lap2d_coef", 1, 1, False, ""), "csr_kernel", "cfg5"]
+    assert set(d) & subs == {"general_values", "csr_kernel", "cfg5"}

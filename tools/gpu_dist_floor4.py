@@ -1,7 +1,7 @@
 """Config 4 (7-point 400^3, 64 M rows): what ONE rank's share -- 50 planes, 8 M rows, two
 1.28 MB halos -- costs per iteration of the sharded solve, measured on one GPU (VERDICT r2
 item 5), against the single-GPU iteration of the whole operator:
-  whole    config 4 on one shard, classic PCG (what `cfg4` of the N = 1 bench line runs)
+  whole    config 4 on one shard, classic PCG (what `cfg4` of the N = 1 `bench.py --full` line runs)
   alone    nz = 50 slab as the only rank of a communicator (LSBENCH_HIP_DIST_ALONE=1):
            single-reduction CG with its exchange / all-reduce launches in place, nobody to wait
            for, no halo (a single rank owns every column)

@@ -11,11 +11,12 @@ step() { local name=$1 secs=$2; shift 2
   if [ "$PART" != all ] && [ "$PART" != "$CUR" ]; then return 0; fi
   echo "=== $name"; timeout -k 10 "$secs" "$@" > "$OUT/$name.log" 2>&1; local rc=$?
   echo "rc=$rc"; if [ $rc -ge 124 ]; then echo "step $name killed: stopping"; exit $rc; fi; }
-Q="--cpu-seconds 0 --cfg4 0 --general-values 0 --csr-kernel 0 --cfg2 0 --cfg5 0"
+# --full: the SpMV timed back to back after the solve, whose launches the PMC passes count as well
+Q="--full --cpu-seconds 0 --cfg4 0 --general-values 0 --csr-kernel 0 --cfg2 0 --cfg5 0"
 F=file:tests/golden/matrices/xn3b_A_18.txt.gz
-step bench 600 python bench.py
-# the driver's own command line (BENCH_rNN.json): 20 timed solves after 5 warm-ups, every sub-record
-T0=$(date +%s); step bench_driver 600 python bench.py --gpus 1 --steps 20 --warmup 5; echo "bench_driver wall $(( $(date +%s) - T0 )) s"
+step bench 600 python bench.py --full
+# the driver's own command line (BENCH_rNN.json) with --full: 20 timed solves after 5 warm-ups, every sub-record
+T0=$(date +%s); step bench_driver 600 python bench.py --full --gpus 1 --steps 20 --warmup 5; echo "bench_driver wall $(( $(date +%s) - T0 )) s"
 step trace 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --steps 1 --warmup 0 $Q
 step pmc_fetch 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -- python3 bench.py --fixed-iters 60 --steps 1 --warmup 0 $Q
 step pmc_write 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write" -- python3 bench.py --fixed-iters 60 --steps 1 --warmup 0 $Q
@@ -48,7 +49,7 @@ for v in 7 6 1; do step bench_powerlaw_v$v 400 python bench.py --workload powerl
 step cfg5_spd_cg 600 python bench.py --workload "powerlaw:n=8000000,gamma=1.585350372615855,max=4096,seed=20240607,spd=1" --tol 1e-10 --steps 3 $Q
 step trace_cfg2_fsai 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_cfg2_fsai" -- python3 bench.py --workload $F --tol 1e-12 --steps 20 --warmup 2 --persistent 0 --precond fsai $Q
 step trace_cfg2 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_cfg2" -- python3 bench.py --workload $F --tol 1e-12 --steps 20 --warmup 2 --persistent 0 $Q
-C2="--workload $F --tol 1e-12 --steps 100 --warmup 5 --cfg4 0 --verify 0"
+C2="--workload $F --tol 1e-12 --steps 100 --warmup 5 --full --cfg4 0 --verify 0"
 step cfg2_launches 300 python bench.py $C2 --persistent 0
 step cfg2_persistent 300 python bench.py $C2 --persistent 1 --cpu-seconds 0
 step cfg2_dense_inverse 300 python bench.py $C2 --persistent 0 --precond bj --block-size 1000000 --cpu-seconds 0

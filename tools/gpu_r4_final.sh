@@ -6,7 +6,7 @@ timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; r
 tail -n 4 $OUT/pytest.log
 if [ $rc -ne 0 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -n 2 $OUT/smoke.log
-T0=$(date +%s); timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.log 2> $OUT/bench.err; rc=$?
+T0=$(date +%s); timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench.log 2> $OUT/bench.err; rc=$?
 echo "bench rc=$rc wall=$(( $(date +%s) - T0 )) s"
 python - "$OUT" <<'PY'
 import json, sys
