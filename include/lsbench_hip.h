@@ -647,6 +647,10 @@ int lsb_hip_solver_precond_dev(lsb_hip_solver *s, const double *d_r, double *d_z
 /* LSB_PRECOND_AMG: levels of the hierarchy, the coarsest included, and how many of them (with
  * the coarse solve) run in the one-launch tail; 2 for another preconditioner. */
 int lsb_hip_solver_amg_info(lsb_hip_solver *s, unsigned *levels, unsigned *tail_levels);
+/* LSB_PRECOND_CHEBYSHEV: the interval [lmin, lmax] of D^-1 S the polynomial was built on at creation
+ * (lmax = 1.1 x the power iteration's estimate, lmin = lmax / max(30, 16 degree^2), the degree
+ * clamped to 1 .. 32); 2 for another preconditioner. */
+int lsb_hip_solver_cheb_interval(const lsb_hip_solver *s, double *lmin, double *lmax);
 /* Time `reps` back-to-back launches of the solver's SpMV kernel with HIP
  * events on the solver's stream (after `warm` untimed ones); *ms_avg = mean
  * milliseconds per launch.  No exchange, local shard 0. */

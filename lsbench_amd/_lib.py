@@ -237,6 +237,7 @@ SIGNATURES = {
     "lsb_hip_solver_spmv_dev": (_i, [_vp, _vp, _vp]),
     "lsb_hip_solver_precond_dev": (_i, [_vp, _vp, _vp]),
     "lsb_hip_solver_amg_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u)]),
+    "lsb_hip_solver_cheb_interval": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
     "lsb_hip_solver_time_spmv": (_i, [_vp, _i, _i, C.POINTER(_d)]),
     "lsb_hip_solver_jacobi_sweep_dev": (_i, [_vp, _d, _vp, _vp]),
     "lsb_hip_solver_nrows_local": (_u, [_vp]),

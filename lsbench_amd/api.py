@@ -287,6 +287,13 @@ class Solver:
         L.check(L.load().lsb_hip_solver_amg_info(self._h, C.byref(lv), C.byref(tl)), "amg_info")
         return lv.value, tl.value
 
+    @property
+    def cheb_interval(self):
+        """(lmin, lmax) of D^-1 S the Chebyshev preconditioner's polynomial was built on."""
+        lo, hi = C.c_double(), C.c_double()
+        L.check(L.load().lsb_hip_solver_cheb_interval(self._h, C.byref(lo), C.byref(hi)), "cheb_interval")
+        return lo.value, hi.value
+
     def time_spmv(self, warm=5, reps=50):
         ms = C.c_double()
         L.check(L.load().lsb_hip_solver_time_spmv(self._h, warm, reps, C.byref(ms)),

@@ -600,3 +600,15 @@ int lsb_hip_solver_amg_info(lsb_hip_solver *sv, unsigned *levels, unsigned *tail
     *tail_levels = a->nlev - a->tail;
   return 0;
 }
+
+int lsb_hip_solver_cheb_interval(const lsb_hip_solver *sv, double *lmin, double *lmax) {
+  if (!lsb_initialized)
+    return 1;
+  if (!sv || sv->o.precond != LSB_PRECOND_CHEBYSHEV)
+    return 2;
+  if (lmin)
+    *lmin = sv->cheb_lmin;
+  if (lmax)
+    *lmax = sv->cheb_lmax;
+  return 0;
+}
