@@ -129,9 +129,15 @@ enum { LSB_KRYLOV_PCG = 0,    /* preconditioned CG (symmetric operators)    */
        LSB_KRYLOV_PCG1 = 2,   /* single-reduction CG (Chronopoulos-Gear): the
                                  same iterates with 2 launches and 1 global
                                  reduction per iteration instead of 3 and 2 */
-       LSB_KRYLOV_AUTO = 3 }; /* PCG1 when the operator is spread over several
+       LSB_KRYLOV_AUTO = 3,   /* PCG1 when the operator is spread over several
                                  shards (one collective less per iteration),
                                  PCG otherwise                              */
+       LSB_KRYLOV_BICGSTAB = 4 }; /* BiCGSTAB, right-preconditioned by a diagonal
+                                 (Jacobi, l1-Jacobi, none): the reference's Ginkgo
+                                 backend (src/ginkgo.cpp:55-64); short recurrences
+                                 for unsymmetric operators -- seven vectors, two
+                                 SpMVs and four sweeps per iteration; one shard or
+                                 several; trust it with opts.verify = 1        */
 enum { LSB_SPMV_AUTO = 0,     /* pick by mean row length                    */
        LSB_SPMV_ADAPTIVE = 1, /* row-blocked: LDS-streamed short rows +
                                  wavefront-per-row long rows                */
@@ -180,7 +186,7 @@ struct lsb_hip_opts {
   int spmv_grid;     /* workgroup cap of the SpMV launch, 0 = tuned     [0] */
   int reorder;       /* 1: solve P S P^T with P = reverse Cuthill-McKee, permute
                         b, un-permute x (single shard)                  [0] */
-  int krylov;        /* LSB_KRYLOV_*                                 [AUTO] */
+  int krylov;        /* LSB_KRYLOV_* (PCG, GMRES, PCG1, AUTO, BICGSTAB)  [AUTO] */
   int restart;       /* GMRES restart length m, 1..32                  [30] */
   int verbose;
   int ngpus;         /* hip_cdna4_bench only: row-partition the operator over
@@ -707,7 +713,8 @@ int lsb_hip_solver_overlap(const lsb_hip_solver *s, double us[2]);
 unsigned long long lsb_hip_solver_spmv_layout_bytes(const lsb_hip_solver *s);
 /* Bytes one iteration of the Krylov loop must move on this rank's first shard: the SpMV's layout
  * bytes + 8 B per row and vector pass of the sweeps (classic PCG: 9 passes, + 2 where the inverse
- * diagonal is a vector; single-reduction PCG: 9 or 11 + 1).  0 where the iteration has another
+ * diagonal is a vector; single-reduction PCG: 9 or 11 + 1; BiCGSTAB: TWO layout counts + the 18
+ * passes of its four sweeps, + 2 where the diagonal is a vector).  0 where the iteration has another
  * shape (GMRES, Chebyshev / block-Jacobi / FSAI, the fused forms of small operators, fp32 values,
  * multi-pass SpMV forms).  bench.py divides it by the measured time per iteration. */
 unsigned long long lsb_hip_solver_iteration_bytes(const lsb_hip_solver *s);

@@ -116,7 +116,8 @@ static const struct optchoice CH_PRECOND[] = {{"jacobi", LSB_PRECOND_JACOBI},   
 static const struct optchoice CH_COMM[] = {{"auto", LSB_COMM_AUTO}, {"rccl", LSB_COMM_RCCL}, {"p2p", LSB_COMM_P2P}, {NULL, 0}};
 static const struct optchoice CH_KRYLOV[] = {{"cg", LSB_KRYLOV_PCG},     {"pcg", LSB_KRYLOV_PCG}, /* (alias) */
                                              {"cg1", LSB_KRYLOV_PCG1},   {"pcg1", LSB_KRYLOV_PCG1},
-                                             {"auto", LSB_KRYLOV_AUTO},  {"gmres", LSB_KRYLOV_GMRES}, {NULL, 0}};
+                                             {"auto", LSB_KRYLOV_AUTO},  {"gmres", LSB_KRYLOV_GMRES},
+                                             {"bicgstab", LSB_KRYLOV_BICGSTAB}, {NULL, 0}};
 static const struct optchoice CH_PRECISION[] = {{"fp64", LSB_PREC_FP64}, {"fp32", LSB_PREC_MIXED},
                                                 {"mixed", LSB_PREC_MIXED}, {NULL, 0}};
 #define OPT(n, t, f, c) {n, t, offsetof(struct lsb_hip_opts, f), c}

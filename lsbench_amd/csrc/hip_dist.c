@@ -12,41 +12,47 @@
 /* communication steps: RCCL between processes, device copies between the     */
 /* virtual shards of one process                                              */
 /* ------------------------------------------------------------------------ */
-void exchange_on(lsb_hip_solver *sv, hipStream_t stream) {
+/* full: one gather vector per shard (n_glob doubles each), NULL = the shards' own d_pfull */
+#define FULL(i) (full ? full[i] : sv->sh[i].d_pfull)
+static void exchange_vec_on(lsb_hip_solver *sv, hipStream_t stream, double *const *full) {
   if (sv->dist) {
     struct shard *s = &sv->sh[0];
-    lsb_hip_comm_exchange(s->d_pfull, s->send, s->nsend, s->recv, s->nrecv, stream);
+    lsb_hip_comm_exchange(FULL(0), s->send, s->nsend, s->recv, s->nrecv, stream);
     return;
   }
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
     for (int k = 0; k < s->nrecv; k++) {
       const struct lsb_xfer *x = &s->recv[k];
-      LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + x->offset,
-                                 sv->sh[x->peer].d_pfull + x->offset,
+      LSB_CHK_HIP(hipMemcpyAsync(FULL(i) + x->offset,
+                                 FULL(x->peer) + x->offset,
                                  x->count * sizeof(double), hipMemcpyDeviceToDevice,
                                  stream));
     }
   }
 }
+void exchange_on(lsb_hip_solver *sv, hipStream_t stream) { exchange_vec_on(sv, stream, NULL); }
 
 /* gated = 1: part of a running solve (a launch no-ops once the device state has
  * left RUNNING); 0: a communication step of its own -- gated on the shard's
  * auxiliary state instead, which only ever leaves RUNNING through a time-out of
  * the direct path (the host reports that: check_aux_status). */
-void exchange_p(lsb_hip_solver *sv, int gated) {
+void exchange_p(lsb_hip_solver *sv, int gated) { exchange_vec(sv, gated, NULL); }
+
+/* the same for any gather vector of the shards (BiCGSTAB's second one); full == NULL: d_pfull */
+void exchange_vec(lsb_hip_solver *sv, int gated, double *const *full) {
   if (sv->p2p_halo && sv->dist) { /* peers are other GPUs: both roles in one launch */
-    lsb_p2p_sendrecv(sv->p2p[0], sv->sh[0].d_pfull, gated ? sv->sh[0].d_st : sv->sh[0].d_st_aux,
+    lsb_p2p_sendrecv(sv->p2p[0], FULL(0), gated ? sv->sh[0].d_st : sv->sh[0].d_st_aux,
                      g_stream);
   } else if (sv->p2p_halo) { /* all sends before any wait: virtual shards share a stream */
     for (int i = 0; i < sv->nshard; i++)
-      lsb_p2p_send(sv->p2p[i], sv->sh[i].d_pfull, gated ? sv->sh[i].d_st : sv->sh[i].d_st_aux,
+      lsb_p2p_send(sv->p2p[i], FULL(i), gated ? sv->sh[i].d_st : sv->sh[i].d_st_aux,
                    g_stream);
     for (int i = 0; i < sv->nshard; i++)
-      lsb_p2p_recv(sv->p2p[i], sv->sh[i].d_pfull, gated ? sv->sh[i].d_st : sv->sh[i].d_st_aux,
+      lsb_p2p_recv(sv->p2p[i], FULL(i), gated ? sv->sh[i].d_st : sv->sh[i].d_st_aux,
                    g_stream);
   } else {
-    exchange_on(sv, g_stream);
+    exchange_vec_on(sv, g_stream, full);
     return;
   }
   /* Mailbox regions and flags are re-used by the next exchange; inside an
@@ -156,7 +162,8 @@ int can_overlap(const lsb_hip_solver *sv) {
  * against 167 / 198 plain, profiles/r03_cfg4_share.txt). */
 void overlap_setup(lsb_hip_solver *sv) {
   sv->overlap_on = -1, sv->overlap_us[0] = sv->overlap_us[1] = 0.0;
-  if (!sv->multi || sv->o.overlap >= 0 || sv->o.krylov == LSB_KRYLOV_GMRES || getenv("LSBENCH_HIP_NO_OVERLAP_TUNE"))
+  if (!sv->multi || sv->o.overlap >= 0 || sv->o.krylov == LSB_KRYLOV_GMRES ||
+      sv->o.krylov == LSB_KRYLOV_BICGSTAB || getenv("LSBENCH_HIP_NO_OVERLAP_TUNE"))
     return;
   unsigned can = 1; /* the split needs the prefix / interior / suffix shape on every shard of every rank */
   for (int i = 0; i < sv->nshard; i++)

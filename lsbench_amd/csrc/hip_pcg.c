@@ -29,7 +29,7 @@
 enum pcg_form pcg_choose_form(const lsb_hip_solver *sv) {
   const struct shard *s = &sv->sh[0];
   const struct lsb_hip_opts *o = &sv->o;
-  if (o->krylov == LSB_KRYLOV_GMRES)
+  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_BICGSTAB)
     return PCG_NONE;
   if (o->precond == LSB_PRECOND_FSAI && !sv->multi && !s->mixed && s->variant == LSB_SPMV_SUBWAVE &&
       s->fs_g.variant == LSB_SPMV_SUBWAVE && s->fs_gt.variant == LSB_SPMV_SUBWAVE && o->sample_spmv <= 0 &&
@@ -410,13 +410,16 @@ static void pcg_enqueue_iter(lsb_hip_solver *sv, enum pcg_form form, double *d_x
  * + 2 reads of the inverse diagonal where it is a vector; the single-reduction form: 9 passes with
  * a constant diagonal (u = dc r never stored), else 11 + the diagonal.  0 where the iteration is
  * something else (GMRES, a polynomial / block / FSAI preconditioner, the one-launch and
- * two-launch forms of small operators, fp32 values, the multi-pass SpMV forms). */
+ * two-launch forms of small operators, fp32 values, the multi-pass SpMV forms).
+ * BiCGSTAB: two SpMVs + the 18 passes of its four sweeps (hip_bicgstab.hip), + 2 reads of the diagonal. */
 unsigned long long lsb_hip_solver_iteration_bytes(const lsb_hip_solver *sv) {
   const struct shard *s = &sv->sh[0];
   const unsigned long long sp = lsb_hip_solver_spmv_layout_bytes(sv), n8 = 8ull * s->n;
   const unsigned vec = s->dinv_uniform ? 0u : 1u;
   if (!sp || s->mixed || sv->ps.use)
     return 0;
+  if (sv->o.krylov == LSB_KRYLOV_BICGSTAB)
+    return 2 * sp + n8 * (18u + 2u * vec);
   switch (sv->form) {
   case PCG_CLASSIC:
     return sp + n8 * (9u + 2u * vec);
@@ -551,8 +554,9 @@ void tune_blas1_nt(lsb_hip_solver *sv) {
    * on config 3 0.971 / 1.285 / 0.399 -> 0.974 / 1.289 / 0.408 solves/s, tools/gpu_nt_generic.sh) */
   if (!e && generic_precond(sv) && s->nnz >= 4000000ull)
     sv->nt_mask = 63 & ~16;
-  if (s->nnz < 4000000ull || generic_precond(sv) || sv->o.krylov == LSB_KRYLOV_GMRES)
-    return; /* (GMRES runs none of these sweeps) */
+  if (s->nnz < 4000000ull || generic_precond(sv) || sv->o.krylov == LSB_KRYLOV_GMRES ||
+      sv->o.krylov == LSB_KRYLOV_BICGSTAB)
+    return; /* (GMRES and BiCGSTAB run none of these sweeps) */
   static const int cand[] = {63, 9, 5, 0};
   const unsigned n = s->n;
   double *d_b = (double *)lsb_hip_malloc((size_t)n * sizeof(double));
@@ -698,7 +702,7 @@ void persist_setup(lsb_hip_solver *sv) {
   unsigned nzmax, rmax, gmax;
   const unsigned nmax = lsb_k_persist_limits(&nzmax, &rmax, &gmax);
   if (sv->multi || sv->nshard != 1 || o->persistent == 0 || o->sample_spmv > 0 ||
-      o->krylov == LSB_KRYLOV_GMRES || s->n > nmax || s->n < 2 ||
+      o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_BICGSTAB || s->n > nmax || s->n < 2 ||
       (o->precond != LSB_PRECOND_JACOBI && o->precond != LSB_PRECOND_NONE &&
        o->precond != LSB_PRECOND_L1JACOBI) ||
       o->precision != LSB_PREC_FP64)
@@ -942,6 +946,8 @@ int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
                       struct lsb_hip_result *res) {
   if (sv->o.krylov == LSB_KRYLOV_GMRES)
     return gmres_solve_dev(sv, d_b, d_x, res);
+  if (sv->o.krylov == LSB_KRYLOV_BICGSTAB)
+    return bicgstab_solve_dev(sv, d_b, d_x, res);
   const double t0 = wall_seconds();
   struct lsb_hip_result r;
   /* Mixed precision: the CG runs see S~ = fp32(S) (fp64 vectors and sums) and

@@ -42,9 +42,9 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
   if (s->row_begin != 0 || s->n != s->n_glob)
     errx(EXIT_FAILURE, "hip_cdna4: --precond amg runs on one shard (the hierarchy couples all rows); use it "
                        "without --ngpus / --nvirt");
-  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_PCG1)
+  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_PCG1 || o->krylov == LSB_KRYLOV_BICGSTAB)
     errx(EXIT_FAILURE, "hip_cdna4: --precond amg runs under classic PCG (--krylov cg or auto), not %s",
-         o->krylov == LSB_KRYLOV_GMRES ? "gmres" : "cg1");
+         o->krylov == LSB_KRYLOV_GMRES ? "gmres" : o->krylov == LSB_KRYLOV_PCG1 ? "cg1" : "bicgstab");
   const double t0 = wall_seconds();
   const unsigned n = s->n;
   struct csr view = {n, 0, (unsigned *)offs, (unsigned *)cols, (double *)vals};

@@ -523,6 +523,8 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
     else if (o->precond == LSB_PRECOND_AMG)
       cnt += 3 * (size_t)n;                                    /* z, the fine level's second smoothing
                                                                   buffer and its residual */
+    if (o->krylov == LSB_KRYLOV_BICGSTAB)
+      cnt += 3 * (size_t)n + n_glob;                           /* t, p, the shadow residual; the gather vector of s^ */
     /* ... where the vectors are of the Infinity Cache's scale or below (n <= 20 M rows): that is where
      * their relative placement decides which lines fight for the same sets.  Vectors that fit no cache
      * gain nothing from it and measured 5 % SLOWER out of one allocation (64 M-row 7-point operator:
@@ -662,6 +664,15 @@ void solver_finish_setup(lsb_hip_solver *sv) {
   persist_setup(sv);
 }
 
+/* BiCGSTAB applies M^-1 inside its sweeps, as a diagonal: the preconditioners that produce z = M^-1 r as
+ * a vector are refused at creation (as AMG refuses GMRES) */
+static void bicgstab_check_precond(const struct lsb_hip_opts *o) {
+  if (o->krylov == LSB_KRYLOV_BICGSTAB && o->precond != LSB_PRECOND_JACOBI && o->precond != LSB_PRECOND_NONE &&
+      o->precond != LSB_PRECOND_L1JACOBI)
+    errx(EXIT_FAILURE, "hip_cdna4: --krylov bicgstab runs with --precond jacobi, l1 or none (Chebyshev, "
+                       "block-Jacobi, FSAI and AMG run under PCG)");
+}
+
 lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
                                       const struct lsb_hip_opts *o_in) {
   if (!lsb_initialized || !A || A->nrows == 0)
@@ -671,10 +682,12 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
     o = *o_in;
   else
     lsb_hip_get_opts(&o);
-  if (o.precision == LSB_PREC_MIXED && o.krylov == LSB_KRYLOV_GMRES) {
-    warnx("hip_cdna4: mixed precision is an iterative refinement around CG; GMRES runs in fp64");
+  if (o.precision == LSB_PREC_MIXED && (o.krylov == LSB_KRYLOV_GMRES || o.krylov == LSB_KRYLOV_BICGSTAB)) {
+    warnx("hip_cdna4: mixed precision is an iterative refinement around CG; %s runs in fp64",
+          o.krylov == LSB_KRYLOV_GMRES ? "GMRES" : "BiCGSTAB");
     o.precision = LSB_PREC_FP64;
   }
+  bicgstab_check_precond(&o);
   if (o.precision == LSB_PREC_MIXED && o.precond == LSB_PRECOND_AMG) {
     warnx("hip_cdna4: --precond amg runs in fp64");
     o.precision = LSB_PREC_FP64;
@@ -766,8 +779,10 @@ lsb_hip_solver *lsb_hip_solver_create_dist(const struct csr *A_rows,
     o = *o_in;
   else
     lsb_hip_get_opts(&o);
-  if (o.precision == LSB_PREC_MIXED && (o.krylov == LSB_KRYLOV_GMRES || o.precond == LSB_PRECOND_AMG))
+  if (o.precision == LSB_PREC_MIXED &&
+      (o.krylov == LSB_KRYLOV_GMRES || o.krylov == LSB_KRYLOV_BICGSTAB || o.precond == LSB_PRECOND_AMG))
     o.precision = LSB_PREC_FP64; /* as in lsb_hip_solver_create */
+  bicgstab_check_precond(&o);
   const int P = lsb_hip_comm_size(), me = lsb_hip_comm_rank();
   lsb_hip_solver *sv = solver_alloc(1, &o);
   sv->n_glob = n_global, sv->n_here = sv->n_user = A_rows->nrows, sv->row_first = row_begin;
@@ -844,6 +859,7 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
       lsb_p2p_destroy(sv->p2p[i]);
     free(sv->p2p);
   }
+  bicgstab_free(sv);
   for (int i = 0; i < sv->nshard; i++)
     shard_free(&sv->sh[i]);
   if (sv->have_events) {

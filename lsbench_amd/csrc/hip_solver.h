@@ -9,6 +9,7 @@
  *                    the direct xGMI path's set-up
  *   hip_pcg.c        PCG iteration forms (one chosen per solver) and the host loop
  *   hip_gmres_drv.c  GMRES(m) driver
+ *   hip_bicgstab_drv.c  BiCGSTAB driver
  * Nothing here is part of the C-ABI (include/lsbench_hip.h).
  */
 #ifndef HIP_SOLVER_H
@@ -58,7 +59,7 @@ struct halo_split {
 enum { SELL_NONE, SELL_32, SELL_16, SELL_TMPL, SELL_COL };
 /* the PCG iteration a solver runs (pcg_choose_form picks it once, at creation; hip_pcg.c) */
 enum pcg_form {
-  PCG_NONE,    /* GMRES: no PCG iteration */
+  PCG_NONE,    /* GMRES, BiCGSTAB: no PCG iteration */
   PCG_CLASSIC, /* SpMV, k_pcg_update_xr, k_pcg_update_p (one shard or many) */
   PCG_SUBWAVE, /* k_spmv_subwave_p + k_pcg_update_xr: the direction update rides in the next SpMV */
   PCG_COL,     /* k_pcg_col_px + k_pcg_col_r on the z-column plan (+ k_pcg_xfix at a run's end) */
@@ -239,6 +240,14 @@ struct lsb_hip_solver {
   double *gm_red; /* nshard x GM_RED doubles: [0] a norm, [8..) h, [48..) h2 -- all-reduced */
   struct lsb_gmres_state *gm_hst;
   int gm_m;
+  /* BiCGSTAB workspace (allocated on first use; hip_bicgstab_drv.c) */
+  struct bcg_work { /* per shard */
+    double *t, *p, *rhat, *sfull; /* t = Op s^, the direction, the shadow residual, the gather vector of s^ */
+    struct lsb_bcg_state *st;
+    unsigned nss, ntt, np2; /* partial counts of the sweeps */
+  } *bcg;
+  double *bcg_red; /* nshard x BCG_RED doubles: the all-reduced dot products */
+  struct lsb_bcg_state *bcg_hst; /* pinned, 2 slots */
   hipEvent_t ev_poll[2], ev_vec, ev_halo;
   hipEvent_t ev[4 * MAX_SAMPLES], ev_t0, ev_t1; /* per sample: e0 SpMV e1 e2 e3 */
   unsigned char samp_skip[MAX_SAMPLES];         /* the sample brackets nothing (a run's first iteration in the
@@ -315,6 +324,7 @@ LSB_INTERNAL void p2p_setup(lsb_hip_solver *sv);
 LSB_INTERNAL void overlap_setup(lsb_hip_solver *sv);
 LSB_INTERNAL void exchange_on(lsb_hip_solver *sv, hipStream_t stream);
 LSB_INTERNAL void exchange_p(lsb_hip_solver *sv, int gated);
+LSB_INTERNAL void exchange_vec(lsb_hip_solver *sv, int gated, double *const *full);
 LSB_INTERNAL void check_aux_status(lsb_hip_solver *sv, const char *where);
 LSB_INTERNAL void allreduce_scal(lsb_hip_solver *sv, unsigned off, unsigned cnt, int gated);
 LSB_INTERNAL void allreduce_pq(lsb_hip_solver *sv, unsigned cnt, int with2);
@@ -340,8 +350,13 @@ LSB_INTERNAL void precond_shard_blocks(struct shard *s, const int *offs, const i
                                        const double *vals, const struct lsb_hip_opts *o);
 LSB_INTERNAL void precond_setup(lsb_hip_solver *sv);
 LSB_INTERNAL void precond_apply(lsb_hip_solver *sv, int after_update);
-LSB_INTERNAL void precond_free_shard(struct shard *s);/* hip_gmres_drv.c */
+LSB_INTERNAL void precond_free_shard(struct shard *s);
+/* hip_gmres_drv.c */
 LSB_INTERNAL int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
                                  struct lsb_hip_result *res);
+/* hip_bicgstab_drv.c */
+LSB_INTERNAL int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
+                                    struct lsb_hip_result *res);
+LSB_INTERNAL void bicgstab_free(lsb_hip_solver *sv); /* before the shards go: its vectors may sit in their slabs */
 
 #endif

@@ -81,6 +81,19 @@ struct lsb_gmres_state {
   int iters, status, maxit, restart, jlast, cycle_open;
 };
 
+/* ---- device-side BiCGSTAB scalars (hip_bicgstab.hip) -------------------------
+ * c: the words the SpMV launchers and the reduction helpers gate on and the host polls -- status,
+ * iters, maxit, bb, thresh2 = tol^2 bb, rr (the last residual norm formed, squared); its other
+ * fields are not used.  alpha, omega and beta never leave the device. */
+struct lsb_bcg_state {
+  struct lsb_pcg_state c;
+  double rho[2];  /* r^.r, double-buffered by iteration parity */
+  double alpha, omega;
+  int half;       /* 1: k_bcg_xr took the half step; k_bcg_p behind it sets CONVERGED */
+  int nspmv;      /* products with Op of the iterations run: 2 per full one, 1 for a half step, the
+                     one or two of an iteration that ended in a breakdown */
+};
+
 /* Upper bound on per-launch partial sums any reduction kernel writes; the
  * consumer kernels re-reduce them in fixed order (deterministic). */
 #define LSB_MAX_PARTIALS 2048
@@ -251,6 +264,30 @@ void lsb_k_gm_hess(struct lsb_gmres_state *st, int j, const double *h, const dou
                    const double *partials, unsigned nparts, void *stream);
 void lsb_k_gm_finish_cycle(unsigned n, const double *V, size_t ld, const double *dinv, double *x,
                            struct lsb_gmres_state *st, void *stream);
+
+/* BiCGSTAB launchers (hip_bicgstab.hip); dinv == NULL: the constant dc */
+void lsb_k_bcg_init(unsigned n, const double *b, const double *dinv, double dc, double *x, double *r,
+                    double *rhat, double *p, double *phat, double *partials, unsigned *npartials,
+                    void *stream);
+void lsb_k_bcg_init_state(struct lsb_bcg_state *st, const double *parts, unsigned nparts, double tol,
+                          int maxit, void *stream);
+void lsb_k_bcg_restart(unsigned n, const double *b, const double *ax, const double *dinv, double dc,
+                       double *r, double *rhat, double *p, double *phat, double *partials,
+                       unsigned *npartials, void *stream);
+void lsb_k_bcg_restart_state(struct lsb_bcg_state *st, const double *parts, unsigned nparts, int more,
+                             void *stream);
+void lsb_k_bcg_s(unsigned n, double *r, const double *v, const double *dinv, double dc, double *shat,
+                 struct lsb_bcg_state *st, int parity, const double *sig_parts, unsigned nsig,
+                 double *partials, unsigned *npartials, void *stream);
+void lsb_k_bcg_tt(unsigned n, const double *t, const struct lsb_bcg_state *st, double *partials,
+                  unsigned *npartials, void *stream);
+void lsb_k_bcg_xr(unsigned n, double *x, const double *phat, const double *shat, double *r, const double *t,
+                  const double *rhat, struct lsb_bcg_state *st, const double *ss_parts, unsigned nss,
+                  const double *ts_parts, unsigned nts, const double *tt_parts, unsigned ntt,
+                  double *partials2, unsigned *npartials, void *stream);
+void lsb_k_bcg_p(unsigned n, const double *r, double *p, const double *v, const double *dinv, double dc,
+                 double *phat, struct lsb_bcg_state *st, int parity, const double *parts2, unsigned nparts2,
+                 void *stream);
 
 /* ---- preconditioners with z as a vector (hip_precond_k.hip) -------------------- */
 void lsb_k_dot2(unsigned n, const double *r, const double *z, double *partials2,

@@ -20,6 +20,11 @@
  *           0.0.  Exactly symmetric, weakly diagonally dominant with strict rows
  *           at the boundary, irreducible => SPD.  The operator the roofline line
  *           "fp64 CSR SpMV with values that must be streamed" is measured on.
+ *   lap2d / lap3d with ",conv=C": the same pattern, unsymmetric -- diffusion plus a convection term of
+ *           strength C along every axis: -1-C at column -1, -1+C at +1, -1-C/2 at -nx, -1+C/2 at +nx
+ *           (3-D: -1-C/4 at -nx*ny, -1+C/4 at +nx*ny), diagonal 4 (6).  One value per diagonal, so
+ *           constant slots, templates and the z-column walk apply as to the Laplacian; C = 0 IS the
+ *           Laplacian, bit for bit.  Not together with coef (NULL).
  *   powerlaw  n x n, row degree d_i from a truncated discrete power law
  *           P(d) ~ d^-gamma on [1,max] by inverse CDF on a 2^53-scaled integer
  *           table; the k-th entry of row i sits in column
@@ -97,8 +102,11 @@ static double ghost_w(unsigned long long cseed, unsigned long long row, unsigned
 static struct csr *gen_lap(unsigned long long nx, unsigned long long ny,
                            unsigned long long nz, int three,
                            unsigned long long r0, unsigned long long r1,
-                           unsigned long long cseed) {
+                           unsigned long long cseed, double conv) {
   const unsigned long long nxy = nx * ny;
+  /* off-diagonals by direction (k-, j-, i-, i+, j+, k+); conv = 0: all -1.0 */
+  const double wk0 = -1.0 - conv / 4, wj0 = -1.0 - conv / 2, wi0 = -1.0 - conv, wi1 = -1.0 + conv,
+               wj1 = -1.0 + conv / 2, wk1 = -1.0 + conv / 4;
   const double diag = three ? 6.0 : 4.0;
   struct csr *A = alloc_rows((unsigned)(r1 - r0));
   unsigned long long *cnt = (unsigned long long *)malloc((size_t)(r1 - r0 + 1) * sizeof *cnt);
@@ -118,18 +126,18 @@ static struct csr *gen_lap(unsigned long long nx, unsigned long long ny,
     unsigned z = A->offs[row - r0], zd;
     if (!cseed) {
       if (three && k > 0)
-        A->cols[z] = (unsigned)(row - nxy), A->vals[z++] = -1.0;
+        A->cols[z] = (unsigned)(row - nxy), A->vals[z++] = wk0;
       if (j > 0)
-        A->cols[z] = (unsigned)(row - nx), A->vals[z++] = -1.0;
+        A->cols[z] = (unsigned)(row - nx), A->vals[z++] = wj0;
       if (i > 0)
-        A->cols[z] = (unsigned)(row - 1), A->vals[z++] = -1.0;
+        A->cols[z] = (unsigned)(row - 1), A->vals[z++] = wi0;
       A->cols[z] = (unsigned)row, A->vals[z++] = diag;
       if (i + 1 < nx)
-        A->cols[z] = (unsigned)(row + 1), A->vals[z++] = -1.0;
+        A->cols[z] = (unsigned)(row + 1), A->vals[z++] = wi1;
       if (j + 1 < ny)
-        A->cols[z] = (unsigned)(row + nx), A->vals[z++] = -1.0;
+        A->cols[z] = (unsigned)(row + nx), A->vals[z++] = wj1;
       if (three && k + 1 < nz)
-        A->cols[z] = (unsigned)(row + nxy), A->vals[z++] = -1.0;
+        A->cols[z] = (unsigned)(row + nxy), A->vals[z++] = wk1;
       continue;
     }
     /* general values: one weight per edge, the diagonal = their sum in direction order */
@@ -372,5 +380,10 @@ struct csr *lsbench_matrix_synth(const char *spec, unsigned r0, unsigned r1,
   unsigned long long cseed = 0;
   if (spec_get(spec, "coef", &v) && v != 0.0)
     cseed = (unsigned long long)v;
-  return gen_lap(nx, ny, kind == 2 ? nz : 1, kind == 2, r0, r1, cseed);
+  double conv = 0.0;
+  if (spec_get(spec, "conv", &v))
+    conv = v;
+  if (conv != 0.0 && cseed)
+    return NULL; /* one or the other */
+  return gen_lap(nx, ny, kind == 2 ? nz : 1, kind == 2, r0, r1, cseed, conv);
 }
