@@ -645,6 +645,13 @@ int lsb_hip_solver_solve_dev(lsb_hip_solver *s, const double *d_b, double *d_x,
 /* y_local = Op * x: d_x holds this rank's rows (length n_local); remote
  * entries are exchanged first when the solver is distributed. */
 int lsb_hip_solver_spmv_dev(lsb_hip_solver *s, const double *d_x, double *d_y);
+/* The product the Krylov loop issues, where spmv_dev is the exact one: the same gather, exchange and
+ * status check, then the launches of an iteration's SpMV -- the solver's form, flags, grid, period
+ * and value arrays, split into interior / boundary launches where the solver overlaps its exchange.
+ * An fp64 solver: S x, the bits of spmv_dev.  LSB_PREC_MIXED: S~ x with S~ = fp32(S), what the inner
+ * CG multiplies by.  d_dot (may be NULL; one shard only, else 2): the launch's fused x.y, reduced
+ * from its own partial sums. */
+int lsb_hip_solver_spmv_inner_dev(lsb_hip_solver *s, const double *d_x, double *d_y, double *d_dot);
 /* z = M^-1 r once, the preconditioner the solver was made with (LSB_PRECOND_AMG: one V-cycle),
  * on the solver's stream; device buffers of length n_local in the caller's numbering.  2 for a
  * preconditioner that is not applied as a vector of its own (the diagonal ones: see

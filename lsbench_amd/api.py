@@ -276,6 +276,12 @@ class Solver:
     def spmv_dev(self, d_x, d_y):
         L.check(L.load().lsb_hip_solver_spmv_dev(self._h, _ptr(d_x), _ptr(d_y)), "spmv_dev")
 
+    def spmv_inner_dev(self, d_x, d_y, d_dot=None):
+        """y = the product the Krylov loop issues (fp32 matrix values under PREC_MIXED, where spmv_dev
+        stays exact); d_dot (one shard only): the launch's fused x.y."""
+        L.check(L.load().lsb_hip_solver_spmv_inner_dev(self._h, _ptr(d_x), _ptr(d_y), _ptr(d_dot)),
+                "spmv_inner_dev")
+
     def precond_dev(self, d_r, d_z):
         """z = M^-1 r once with the solver's preconditioner (device buffers, n_local each)."""
         L.check(L.load().lsb_hip_solver_precond_dev(self._h, _ptr(d_r), _ptr(d_z)), "precond_dev")

@@ -238,10 +238,10 @@ void spmv_range(struct shard *s, int part, double *y, double *partials, unsigned
     return;
   if (s->variant == LSB_SPMV_SELL)
     sell_launch(s, b0, nb, s->d_pfull, y, s->d_pfull + s->row_begin, partials, np, st);
-  else
-    lsb_k_spmv(LSB_SPMV_ADAPTIVE, s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->csr.rowblk + b0,
-               s->csr.blklanes + b0, nb, s->lanes, s->sp_flags, s->sp_grid, s->d_pfull, y,
-               s->d_pfull + s->row_begin, partials, np, st, NULL, &s->tail, g_stream);
+  else /* (the values spmv_shard streams: fp32 under mixed precision) */
+    lsb_k_spmv(LSB_SPMV_ADAPTIVE, s->n, s->csr.offs, s->csr.cols, s->mixed ? (const double *)s->csr.vals32 : s->csr.vals,
+               s->csr.rowblk + b0, s->csr.blklanes + b0, nb, s->lanes, s->sp_flags | (s->mixed ? LSB_SP_F32 : 0u),
+               s->sp_grid, s->d_pfull, y, s->d_pfull + s->row_begin, partials, np, st, NULL, &s->tail, g_stream);
 }
 
 /* The all-reduce of {w.u; the sweep's r.u, r.r} folded into neighbouring

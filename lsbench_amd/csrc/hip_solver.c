@@ -280,6 +280,10 @@ static struct lsb_sell *c16_build(struct shard *s, const struct csr *G, struct l
     lsb_sell_vc_free(V), V = NULL;
   if (V) {
     const size_t nv = ((size_t)V->nval_slots + 1) * LSB_SELL_ROWS;
+    if (s->mixed) /* fp32 matrix values: the slots' constants as well, for every kernel that reads them (k_spmv_sell16
+                     casts, the slot-by-slot paths of k_spmv_tmpl and k_spmv_tmpl_col take them as they are) */
+      for (unsigned long long q = 0; q < V->nslots; q++)
+        V->vconst[q] = (double)(float)V->vconst[q];
     c->sbase = (int *)dev_upload(V->slots, 4 * ((size_t)V->nslots + 1) * sizeof(int));
     c->vconst = (double *)dev_upload(V->vconst, ((size_t)V->nslots + 1) * sizeof(double));
     c->vals = s->mixed ? (double *)upload_f32(V->vals, nv, NULL) : (double *)dev_upload(V->vals, nv * sizeof(double));
@@ -1255,6 +1259,50 @@ int lsb_hip_solver_spmv_dev(lsb_hip_solver *sv, const double *d_x, double *d_y) 
     lsb_k_perm_scatter(sv->n_here, sv->d_perm, d_y, d_yout, g_stream);
   drain_stream(sv, "lsb_hip_solver_spmv_dev");
   check_aux_status(sv, "lsb_hip_solver_spmv_dev");
+  return 0;
+}
+
+/* y = the product the Krylov loop issues (exchange_and_spmv's launches: the solver's form, flags, grid,
+ * period and value arrays -- fp32 values under mixed precision, where spmv_dev above stays exact) */
+int lsb_hip_solver_spmv_inner_dev(lsb_hip_solver *sv, const double *d_x, double *d_y, double *d_dot) {
+  if (!lsb_initialized)
+    return 1;
+  if (!sv || !d_x || !d_y || (d_dot && sv->nshard > 1))
+    return 2;
+  double *d_yout = NULL;
+  if (sv->d_perm) { /* y = Q^T (Q S Q^T) Q x */
+    lsb_k_perm_gather(sv->n_here, sv->d_perm, d_x, sv->d_bp, g_stream);
+    d_x = sv->d_bp, d_yout = d_y, d_y = sv->d_xp;
+  }
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + s->row_begin, d_x + (s->row_begin - sv->row_first),
+                               (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice,
+                               g_stream));
+    LSB_CHK_HIP(hipMemsetAsync(&s->d_st->status, 0, sizeof(int), g_stream)); /* the launches are gated on it */
+  }
+  if (sv->multi)
+    exchange_p(sv, 0);
+  const int split = can_overlap(sv);
+  for (int i = 0; i < sv->nshard; i++) {
+    struct shard *s = &sv->sh[i];
+    double *y = d_y + (s->row_begin - sv->row_first);
+    unsigned np = 0;
+    s->npq = 0;
+    for (int part = 0; part < (split ? 3 : 1); part++) { /* interior, then the boundary parts: one stream here */
+      if (split)
+        spmv_range(s, part, y, s->d_parts_pq + s->npq, &np, s->d_st);
+      else
+        spmv_shard(s, s->d_pfull, y, s->d_pfull + s->row_begin, s->d_parts_pq, &np, s->d_st);
+      s->npq += np;
+    }
+  }
+  if (d_dot)
+    lsb_k_reduce_final(sv->sh[0].d_parts_pq, sv->sh[0].npq, 1, d_dot, 0, NULL, g_stream);
+  if (d_yout)
+    lsb_k_perm_scatter(sv->n_here, sv->d_perm, d_y, d_yout, g_stream);
+  drain_stream(sv, "lsb_hip_solver_spmv_inner_dev");
+  check_aux_status(sv, "lsb_hip_solver_spmv_inner_dev");
   return 0;
 }
 

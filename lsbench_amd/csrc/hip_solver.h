@@ -332,6 +332,9 @@ LSB_INTERNAL int can_overlap(const lsb_hip_solver *sv);
 LSB_INTERNAL int can_fold_allreduce(const lsb_hip_solver *sv);
 LSB_INTERNAL void allreduce_pq_contribute(lsb_hip_solver *sv);
 LSB_INTERNAL void exchange_and_spmv(lsb_hip_solver *sv, int sample);
+/* part 0 / 1 / 2 of the split SpMV: the units that need no halo, the ones before, the ones after them */
+LSB_INTERNAL void spmv_range(struct shard *s, int part, double *y, double *partials, unsigned *np,
+                             const struct lsb_pcg_state *st);
 LSB_INTERNAL double true_resid2(lsb_hip_solver *sv, const double *d_b, const double *d_x);
 /* hip_pcg.c */
 LSB_INTERNAL enum pcg_form pcg_choose_form(const lsb_hip_solver *sv);

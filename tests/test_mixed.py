@@ -44,11 +44,15 @@ def test_mixed_precision_on_exactly_representable_values(hip):
         ms = s.time_spmv(5, 30)
         d_y = torch.empty(L.nrows, dtype=torch.float64, device="cuda:0")
         s.spmv_dev(torch.from_numpy(b).to("cuda:0"), d_y)
-        out[prec] = (x, int(r.iters), int(r.corrections), ms, d_y.cpu().numpy())
+        d_yi = torch.full((L.nrows,), float("nan"), dtype=torch.float64, device="cuda:0")
+        s.spmv_inner_dev(torch.from_numpy(b).to("cuda:0"), d_yi)     # the product the iteration issues: fp32 values
+        out[prec] = (x, int(r.iters), int(r.corrections), ms, d_y.cpu().numpy(), d_yi.cpu().numpy())
         s.destroy()
     assert out[hip.PREC_MIXED][1] == out[hip.PREC_FP64][1] and out[hip.PREC_MIXED][2] == 0
     assert np.array_equal(out[hip.PREC_MIXED][0], out[hip.PREC_FP64][0])
     assert np.array_equal(out[hip.PREC_MIXED][4], out[hip.PREC_FP64][4])
+    assert np.array_equal(out[hip.PREC_MIXED][5], out[hip.PREC_FP64][5])
+    assert np.array_equal(out[hip.PREC_FP64][5], out[hip.PREC_FP64][4])
     # (fewer bytes only where values are streamed at all: a constant-coefficient grid keeps one
     # value per slot, or a 128-bit mask -- nothing left for fp32 to halve; no slower, that is all)
     assert out[hip.PREC_MIXED][3] < 1.15 * out[hip.PREC_FP64][3]

@@ -245,6 +245,9 @@ def test_z_column_walk_changes_no_bit_of_y(hip, monkeypatch, spec, nvirt, overla
         assert s.spmv_col_slices * 4 >= (A.nrows // nvirt // 128) * 3        # the plan exists: most slices in columns
         d_y = torch.full((A.nrows,), float("nan"), dtype=torch.float64, device="cuda:0")
         s.spmv_dev(torch.from_numpy(xs).to("cuda:0"), d_y)
+        # ... and the product the iteration issues (under MIXED spmv_dev is the fp64 CSR kernel whatever the layout)
+        d_yi = torch.full((A.nrows,), float("nan"), dtype=torch.float64, device="cuda:0")
+        s.spmv_inner_dev(torch.from_numpy(xs).to("cuda:0"), d_yi)
         x, r = s.solve(b)
         for _ in range(2):                                        # run to run: the same bits
             d_y2 = torch.empty_like(d_y)
@@ -253,8 +256,11 @@ def test_z_column_walk_changes_no_bit_of_y(hip, monkeypatch, spec, nvirt, overla
             assert torch.equal(d_y, d_y2) and np.array_equal(x, x2) and r2.iters == r.iters
         s.destroy()
         assert r.status == hip.STATUS_CONVERGED
-        out[name] = (d_y.cpu().numpy(), x, int(r.iters))
+        out[name] = (d_y.cpu().numpy(), x, int(r.iters), d_yi.cpu().numpy())
     assert np.array_equal(out["tmpl"][0], out["col"][0])          # y: bit for bit
+    assert np.array_equal(out["tmpl"][3], out["col"][3]) and not np.isnan(out["col"][3]).any()
+    if precision == "FP64":
+        assert np.array_equal(out["col"][3], out["col"][0])
     assert abs(out["tmpl"][2] - out["col"][2]) <= 2
     assert np.linalg.norm(out["tmpl"][1] - out["col"][1]) <= 1e-8 * np.linalg.norm(out["tmpl"][1])
     if precision == "FP64":
@@ -447,6 +453,9 @@ def test_constant_slots_change_no_bit(hip, monkeypatch, spec, nvirt, precision):
             assert 0 <= kept < total // 2
         d_y = torch.empty(A.nrows, dtype=torch.float64, device="cuda:0")
         s.spmv_dev(torch.from_numpy(xs).to("cuda:0"), d_y)
+        # ... and the product the iteration issues (under MIXED spmv_dev is the fp64 CSR kernel whatever the layout)
+        d_yi = torch.full((A.nrows,), float("nan"), dtype=torch.float64, device="cuda:0")
+        s.spmv_inner_dev(torch.from_numpy(xs).to("cuda:0"), d_yi)
         x, r = s.solve(b)
         for _ in range(2):                                        # run to run: the same bits
             d_y2 = torch.empty_like(d_y)
@@ -455,10 +464,13 @@ def test_constant_slots_change_no_bit(hip, monkeypatch, spec, nvirt, precision):
             assert torch.equal(d_y, d_y2) and np.array_equal(x, x2) and r2.iters == r.iters
         lb = s.spmv_layout_bytes
         s.destroy()
-        out[name] = (d_y.cpu().numpy(), x, int(r.iters), r.relres, lb)
+        out[name] = (d_y.cpu().numpy(), x, int(r.iters), r.relres, lb, d_yi.cpu().numpy())
     for name in ("const", "tmpl", "defer"):
         assert np.array_equal(out["full"][0], out[name][0]) and np.array_equal(out["full"][1], out[name][1])
         assert out["full"][2:4] == out[name][2:4]
+        assert np.array_equal(out["full"][5], out[name][5]) and not np.isnan(out[name][5]).any()
+    if precision == "FP64":
+        assert np.array_equal(out["full"][5], out["full"][0])
     if "coef" not in spec:
         # bytes a launch has to move (a small shard may not qualify for templates: then equal)
         assert out["tmpl"][4] <= out["const"][4] < out["full"][4]
