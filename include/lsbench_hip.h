@@ -678,6 +678,10 @@ unsigned lsb_hip_solver_nrows_local(const lsb_hip_solver *s);
  * a constant-coefficient grid of >= 1 M rows whose lines are not whole slices, LSBENCH_HIP_PAD_LINES=0
  * turns it off).  b and x keep the caller's numbering and length. */
 int lsb_hip_solver_padded(const lsb_hip_solver *s);
+/* Which vectors of the two-launch PCG iteration lie inside the first shard's vector slab (one allocation: their
+ * relative placement is the same in every solver): bit 0 r, 1 the gather vector (the first direction buffer),
+ * 2 the second direction buffer, 3 / 4 the x / b of a padded or re-ordered solver. */
+unsigned lsb_hip_solver_slab_mask(const lsb_hip_solver *s);
 unsigned lsb_hip_solver_nrows_global(const lsb_hip_solver *s);
 unsigned long long lsb_hip_solver_nnz_local(const lsb_hip_solver *s);
 unsigned lsb_hip_solver_nblocks(const lsb_hip_solver *s);

@@ -243,6 +243,7 @@ SIGNATURES = {
     "lsb_hip_solver_jacobi_sweep_dev": (_i, [_vp, _d, _vp, _vp]),
     "lsb_hip_solver_nrows_local": (_u, [_vp]),
     "lsb_hip_solver_padded": (_i, [_vp]),
+    "lsb_hip_solver_slab_mask": (_u, [_vp]),
     "lsb_csr_pad_lines": (_csrp, [_csrp, _u, C.POINTER(_u), C.POINTER(_u), C.POINTER(C.POINTER(C.c_int))]),
     "lsb_hip_solver_nrows_global": (_u, [_vp]),
     "lsb_hip_solver_nnz_local": (C.c_ulonglong, [_vp]),

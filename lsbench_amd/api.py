@@ -332,6 +332,12 @@ class Solver:
         return int(L.load().lsb_hip_solver_padded(self._h))
 
     @property
+    def slab_mask(self):
+        """Vectors inside the first shard's slab: bit 0 r, 1 the gather vector, 2 the second direction
+        buffer, 3 / 4 the x / b of a padded or re-ordered solver."""
+        return int(L.load().lsb_hip_solver_slab_mask(self._h))
+
+    @property
     def spmv_col_slices(self):
         """Slices shard 0's z-column plan walks in columns (k_spmv_tmpl_col); 0 = no plan."""
         return int(L.load().lsb_hip_solver_spmv_col_slices(self._h))

@@ -1549,7 +1549,7 @@ __global__ __launch_bounds__(WG, 5) void k_pcg_col_r(
     const unsigned *__restrict__ plan, unsigned period, unsigned n, const unsigned *__restrict__ sptr,
     const unsigned long long *__restrict__ mask, const lsb_sell_tmpl *__restrict__ td, const int *__restrict__ sbase,
     const double *__restrict__ vals, const double *__restrict__ vconst, const double *__restrict__ p,
-    double *__restrict__ r, double dc, lsb_pcg_state *__restrict__ st, int parity, int pbuf, int xtwo,
+    double *__restrict__ r, double dc, lsb_pcg_state *__restrict__ st, int parity, int pbuf, int xtwo, int rev,
     const double *__restrict__ pq_parts, unsigned npq, double *__restrict__ partials2) {
   static_assert(NF >= 1 && NF <= 2, "one or two far slots per side");
   __shared__ double sred[8];
@@ -1593,7 +1593,13 @@ __global__ __launch_bounds__(WG, 5) void k_pcg_col_r(
     acc[1] += rn_.x * rn_.x;                                                                   \
     acc[1] += rn_.y * rn_.y;                                                                   \
   } while (0)
-  for (unsigned g = slot; i0 + 4 * g < i1; g += gx) {
+  // rev: the turns take the band's groups of four from its END -- the launch before (k_pcg_col_px, ascending) touched
+  // those lines last, so this one starts on what is still in the Infinity Cache and the next ascending launch in turn
+  // starts where this one ended.  The groups, their lockstep bits and walk directions are the plan's either way; every
+  // row's r' is the same bits, only the order in which a thread adds its terms of (r.z', r.r) follows the turns.
+  const unsigned G = (i1 - i0 + 3u) / 4u;
+  for (unsigned j = slot; j < G; j += gx) {
+    const unsigned g = rev ? G - 1u - j : j;
     const unsigned it = __builtin_amdgcn_readfirstlane(i0 + 4 * g + wave);
     if (it >= i1)
       continue;
@@ -2141,7 +2147,9 @@ void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, 
   const sell_launch L = sell_prologue("lsb_k_pcg_col_px", true, c, nitem, n, grid_cap, LSB_TMPL_COL_GRID(nfar), period,
                                       partials, npartials, NULL);
   /* x, p' and q streamed nontemporally (NT = 3; measured against 0 / 1 / 2 on config 4: 950.5 / 950.3 / 905.7 /
-   * 894.1 us per iteration, profiles/r04_px.txt) */
+   * 894.1 us per iteration, profiles/r04_px.txt -- and on config 3's cache-scale vectors, with the vectors in one
+   * slab and k_pcg_col_r reversed: 100.1 / 96.5-96.8 / 97.4-97.5 against 95.6-95.9 us, profiles/r06_col_cache.txt:
+   * one mask for every size, so it stays a template constant) */
   static decltype(&k_pcg_col_px<1, 3, false>) const kern[2][2] = { /* [nfar - 1][xupd] */
       {k_pcg_col_px<1, 3, false>, k_pcg_col_px<1, 3, true>},
       {k_pcg_col_px<2, 3, false>, k_pcg_col_px<2, 3, true>}};
@@ -2152,7 +2160,7 @@ void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, 
 
 void lsb_k_pcg_col_r(unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem, unsigned n,
                      const struct lsb_sell16_dev *c, const double *p, double *r, double dc, struct lsb_pcg_state *st,
-                     int parity, int pbuf, int xtwo, const double *pq_parts, unsigned npq, double *partials2,
+                     int parity, int pbuf, int xtwo, int rev, const double *pq_parts, unsigned npq, double *partials2,
                      unsigned *npartials, void *stream) {
   if (period < NXCD || !plan)
     errx(EXIT_FAILURE, "lsb_k_pcg_col_r: no column plan (period %u)", period);
@@ -2161,7 +2169,8 @@ void lsb_k_pcg_col_r(unsigned grid_cap, unsigned period, const unsigned *plan, u
                                       partials2, npartials, NULL);
   const auto kern = c->tmpl.nfar == 1 ? k_pcg_col_r<1> : k_pcg_col_r<2>;
   kern<<<L.g, WG, 0, (hipStream_t)stream>>>(plan, L.period, n, c->sptr, c->tmpl.mask, c->tmpl.td, c->sbase, c->vals,
-                                            c->vconst, p, r, dc, st, parity, pbuf, xtwo, pq_parts, npq, partials2);
+                                            c->vconst, p, r, dc, st, parity, pbuf, xtwo, rev != 0, pq_parts, npq,
+                                            partials2);
 }
 
 } // extern "C"

@@ -62,7 +62,9 @@ enum pcg_form pcg_choose_form(const lsb_hip_solver *sv) {
 /* The vectors a form needs besides the shard's own, out of its slab where they fit (shard_vec): the second
  * direction buffer of SUBWAVE, COL and FSAI3, FSAI3's second residual, CG1's p and s.  Where they land sets
  * the iteration's speed (tune_blas1_nt), so they are taken when they always were: FSAI's by precond_setup
- * for every FSAI solver, whichever form it runs (the slab counts them), the others by the first init. */
+ * for every FSAI solver, whichever form it runs (the slab counts them), the others by the first init -- but
+ * for the second direction buffer of a shard that can run a fused-p form (one shard, fp64, Jacobi, classic
+ * PCG): shard_upload counts it into the slab and carves it right behind the gather vector. */
 void form_vecs(lsb_hip_solver *sv, enum pcg_form f) {
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
@@ -290,11 +292,15 @@ static void col_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity, int po
     sample_close(sv, sample);
     sv->pcur ^= 1;
   }
-  /* r -= alpha S p with S p formed again out of p (k_pcg_col_r): q never travels */
+  /* r -= alpha S p with S p formed again out of p (k_pcg_col_r): q never travels.  Its turns run through each
+   * XCD's band from the END (rev = 1): k_pcg_col_px and the z-column SpMV ascend, so every launch of the iteration
+   * starts on the lines the one before touched last -- r and the two directions are 232 MB of a 256 MB Infinity
+   * Cache on the 10 M-row grid, and with every launch ascending each line's reuse distance was a whole launch.
+   * Always, not by a timing pass: the bits of (r.z, r.r) follow the order */
   lsb_k_pcg_col_r(s->sp_grid, s->col.period, s->col.plan, s->col.items, s->n, &s->c16, buf[sv->pcur], s->d_r,
                   s->dinv_const, s->d_st,
-                  parity, sv->pcur, /* x is two updates behind after an odd iteration */ parity != 0, s->d_parts_pq, s->npq,
-                  s->d_parts2, &s->np2, g_stream);
+                  parity, sv->pcur, /* x is two updates behind after an odd iteration */ parity != 0, /* rev */ 1,
+                  s->d_parts_pq, s->npq, s->d_parts2, &s->np2, g_stream);
   if (pos & 2) { /* last of the run: the pending x update, then the direction back into the gather vector */
     lsb_k_pcg_xfix(s->n, buf[0], buf[1], d_x, s->d_st, g_stream);
     lsb_k_pcg_update_p(s->n, s->d_r, DINV(s), buf[sv->pcur], buf[0], s->d_st, parity, s->d_parts2, s->np2,
@@ -527,7 +533,14 @@ static float time_local_iters(lsb_hip_solver *sv, double *d_b, double *d_x, int 
  * from separate allocations and 136.3-137.4 with round 3's lottery (tools/gpu_r4_place.sh,
  * profiles/r04_placement.txt; general values 234.8-235.9 against 235.4-238.2).  It serves every
  * configuration (shards, Chebyshev / block-Jacobi, any vector size) and costs nothing.
- * LSBENCH_HIP_NO_SLAB=1 is the A/B switch. */
+ * LSBENCH_HIP_NO_SLAB=1 is the A/B switch.
+ * That table is the THREE-launch form's.  The two-launch form (k_pcg_col_px + k_pcg_col_r) streams r, both
+ * direction buffers and x, and until round 6 only r and the first direction were in the slab: the second was
+ * taken by the first init, did not fit and got a hipMalloc of its own, and a padded solver's x (d_xp) was one
+ * more -- round 3's draw again.  Now shard_upload counts and carves the second direction buffer, and a padded
+ * or re-ordered one-shard solver's x and b come out of shard 0's slab right behind it: r, q, p0, p1, x, b in
+ * one run of addresses (lsb_hip_solver_slab_mask says which are inside; profiles/r06_col_cache.txt has the
+ * eight-solver table of this form).  An UNPADDED solver's x is the caller's and lands where the caller put it. */
 
 /* Which operands of the two BLAS-1 sweeps should be loaded NONTEMPORAL is a matter of what the next
  * launches read again, and that depends on how the vectors compare with the 256 MB Infinity Cache:

@@ -514,6 +514,10 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
   LSB_CHK_HIP(hipStreamSynchronize(g_stream)); /* host staging is freed next */
   free(offs), free(cols);
 
+  /* can this shard run a fused-p form (pcg_choose_form: SUBWAVE, COL)?  One shard, fp64, Jacobi, classic PCG:
+   * their second direction buffer is then counted into the slab and carved here, next to the gather vector */
+  const int fused_p = n == n_glob && o->nvirt <= 1 && o->precision == LSB_PREC_FP64 &&
+                      o->precond == LSB_PRECOND_JACOBI && (o->krylov == LSB_KRYLOV_PCG || o->krylov == LSB_KRYLOV_AUTO);
   { /* the vector slab: everything this configuration's iteration streams, in one allocation */
     size_t cnt = 3 * (size_t)n + n_glob;                       /* r, q, the diagonal; the gather vector */
     if (n_glob > n || o->nvirt > 1 || o->krylov == LSB_KRYLOV_PCG1)
@@ -529,6 +533,10 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
                                                                   buffer and its residual */
     if (o->krylov == LSB_KRYLOV_BICGSTAB)
       cnt += 3 * (size_t)n + n_glob;                           /* t, p, the shadow residual; the gather vector of s^ */
+    if (fused_p)
+      cnt += (size_t)n;                                        /* the second direction buffer of the fused-p forms */
+    if (s->slab_bx)
+      cnt += 2 * (size_t)n;                                    /* a padded / re-ordered solver's x and b */
     /* ... where the vectors are of the Infinity Cache's scale or below (n <= 20 M rows): that is where
      * their relative placement decides which lines fight for the same sets.  Vectors that fit no cache
      * gain nothing from it and measured 5 % SLOWER out of one allocation (64 M-row 7-point operator:
@@ -540,11 +548,18 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
         s->d_slab = NULL, s->slab_cap = 0, (void)hipGetLastError();
     }
   }
+  /* the diagonal first (a constant one is never streamed), then what the iteration streams, in one run of
+   * addresses: r, q, the gather vector, the fused-p forms' second direction buffer -- and behind it the x and b of
+   * a padded / re-ordered solver (lsb_hip_solver_create carves them next) */
+  s->d_dinv = shard_vec(s, n);
   s->d_r = shard_vec(s, n);
   s->d_q = shard_vec(s, n);
   s->d_pfull = shard_vec(s, n_glob);
-  s->d_dinv = shard_vec(s, n);
   LSB_CHK_HIP(hipMemsetAsync(s->d_pfull, 0, (size_t)n_glob * sizeof(double), g_stream));
+  if (fused_p) {
+    s->d_p1 = shard_vec(s, n);
+    LSB_CHK_HIP(hipMemsetAsync(s->d_p1, 0, (size_t)n * sizeof(double), g_stream));
+  }
   s->d_parts_pq = (double *)lsb_hip_malloc(3 * LSB_MAX_PARTIALS * sizeof(double));
   /* two buffers: k_cg1_update reads the previous launch's partials while
    * writing its own */
@@ -729,8 +744,6 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
     sv->d_perm = (int *)dev_upload(padmap, (size_t)S->nrows * sizeof(int));
     LSB_CHK_HIP(hipStreamSynchronize(g_stream));
     free(padmap);
-    sv->d_bp = (double *)lsb_hip_malloc((size_t)S->nrows * sizeof(double));
-    sv->d_xp = (double *)lsb_hip_malloc((size_t)S->nrows * sizeof(double));
     sv->padded = 1;
   }
   if (o.reorder) {
@@ -747,18 +760,26 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
     sv->d_perm = (int *)dev_upload(perm, (size_t)S->nrows * sizeof(int));
     LSB_CHK_HIP(hipStreamSynchronize(g_stream));
     free(perm);
-    sv->d_bp = (double *)lsb_hip_malloc((size_t)S->nrows * sizeof(double));
-    sv->d_xp = (double *)lsb_hip_malloc((size_t)S->nrows * sizeof(double));
   }
   sv->n_glob = sv->n_here = S->nrows, sv->row_first = 0;
   sv->dist = 0, sv->multi = P > 1;
   unsigned *bounds = lsb_calloc(unsigned, (size_t)P + 1);
   lsb_csr_partition_rows(S, (unsigned)P, bounds);
   unsigned *hull = lsb_calloc(unsigned, 4 * (size_t)P);
+  /* b and x of a padded / re-ordered solver: with one shard out of its slab, x right behind the directions (the
+   * two-launch iteration streams r, both direction buffers and x); with several, allocations of their own */
+  sv->sh[0].slab_bx = sv->d_perm && P == 1;
   for (int q = 0; q < P; q++) {
     shard_upload(&sv->sh[q], S, bounds[q], bounds[q + 1], 0, bounds[q], S->nrows, &o);
     hull[4 * q] = bounds[q], hull[4 * q + 1] = bounds[q + 1] - bounds[q];
     hull[4 * q + 2] = sv->sh[q].col_lo, hull[4 * q + 3] = sv->sh[q].col_hi;
+  }
+  if (sv->sh[0].slab_bx) {
+    sv->d_xp = shard_vec(&sv->sh[0], S->nrows);
+    sv->d_bp = shard_vec(&sv->sh[0], S->nrows);
+  } else if (sv->d_perm) {
+    sv->d_bp = (double *)lsb_hip_malloc((size_t)S->nrows * sizeof(double));
+    sv->d_xp = (double *)lsb_hip_malloc((size_t)S->nrows * sizeof(double));
   }
   for (int q = 0; q < P; q++) {
     plan_exchange(&sv->sh[q], q, P, hull);
@@ -864,6 +885,7 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
     free(sv->p2p);
   }
   bicgstab_free(sv);
+  shard_vec_free(&sv->sh[0], sv->d_bp), shard_vec_free(&sv->sh[0], sv->d_xp); /* shard 0's slab may hold them */
   for (int i = 0; i < sv->nshard; i++)
     shard_free(&sv->sh[i]);
   if (sv->have_events) {
@@ -879,7 +901,7 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
   lsb_hip_free(sv->d_scal_all), lsb_hip_free(sv->d_tmp);
   lsb_hip_free(sv->d_vr), lsb_hip_free(sv->d_ve);
   lsb_hip_free(sv->ps.d_wgrow), lsb_hip_free(sv->ps.d_ug), lsb_hip_free(sv->ps.d_shared);
-  lsb_hip_free(sv->d_perm), lsb_hip_free(sv->d_bp), lsb_hip_free(sv->d_xp);
+  lsb_hip_free(sv->d_perm);
   for (int i = 0; sv->gm && i < sv->nshard; i++) {
     lsb_hip_free(sv->gm[i].V), lsb_hip_free(sv->gm[i].parts);
     lsb_hip_free(sv->gm[i].ax), lsb_hip_free(sv->gm[i].st);
@@ -893,6 +915,17 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
 }
 
 unsigned lsb_hip_solver_nrows_local(const lsb_hip_solver *s) { return s->n_user; } /* (n_here counts pad rows) */
+/* which of the vectors the two-launch iteration streams lie inside shard 0's slab: bit 0 r, 1 the gather vector,
+ * 2 the second direction buffer, 3 / 4 the x / b of a padded or re-ordered solver */
+unsigned lsb_hip_solver_slab_mask(const lsb_hip_solver *sv) {
+  const struct shard *s = &sv->sh[0];
+  const void *v[5] = {s->d_r, s->d_pfull, s->d_p1, sv->d_xp, sv->d_bp};
+  unsigned m = 0;
+  for (int k = 0; k < 5; k++)
+    if (v[k] && s->d_slab && (const char *)v[k] >= s->d_slab && (const char *)v[k] < s->d_slab + s->slab_cap)
+      m |= 1u << k;
+  return m;
+}
 int lsb_hip_solver_padded(const lsb_hip_solver *s) { return s->padded ? (int)(s->n_here - s->n_user) : 0; }
 unsigned lsb_hip_solver_nrows_global(const lsb_hip_solver *s) { return s->n_glob; }
 unsigned long long lsb_hip_solver_nnz_local(const lsb_hip_solver *s) {

@@ -70,7 +70,9 @@ enum pcg_form {
 
 struct shard {
   /* ONE allocation for the vectors the iteration streams (r, q, the gather vector, the Jacobi
-   * diagonal, the single-reduction form's p / s, the preconditioners' z vectors): their placement
+   * diagonal, the single-reduction form's p / s, the preconditioners' z vectors, the second direction
+   * buffer of the fused-p forms and, for a padded or re-ordered one-shard solver, its x and b -- so
+   * the two-launch form's r, p0, p1 and x are neighbours too; an unpadded solver's x is the caller's): their placement
    * relative to one another is then the same in every solver of every process -- which of their
    * lines compete for the same sets of the 256 MB Infinity Cache no longer depends on which
    * physical pages a dozen separate hipMallocs happened to get ("Where the
@@ -79,6 +81,8 @@ struct shard {
    * LSBENCH_HIP_NO_SLAB=1) is a hipMalloc of its own; shard_vec_free() tells the two apart. */
   char *d_slab;
   size_t slab_cap, slab_used;
+  int slab_bx; /* the slab also holds the solver's permuted x and b (one shard, padded or re-ordered): set by the
+                  creator before shard_upload, which counts them; carved behind the shard's own vectors */
   unsigned row_begin, n;
   unsigned long long nnz;
   unsigned n_glob; /* columns of the operator = length of the gather vector */

@@ -162,10 +162,11 @@ void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, 
                       const struct lsb_sell16_dev *c, const double *r, const double *pold, double *pnew, double *x,
                       int xupd, double dc, double *partials, unsigned *npartials, struct lsb_pcg_state *st, int parity,
                       const double *parts2, unsigned nparts2, void *stream);
-/* the r half: alpha, r -= alpha S p with S p formed again out of p (q is never stored), partials of (r.z', r.r) */
+/* the r half: alpha, r -= alpha S p with S p formed again out of p (q is never stored), partials of (r.z', r.r);
+ * rev: the turns take each XCD band's groups of four items in descending order */
 void lsb_k_pcg_col_r(unsigned grid_cap, unsigned period, const unsigned *plan, unsigned nitem, unsigned n,
                      const struct lsb_sell16_dev *c, const double *p, double *r, double dc, struct lsb_pcg_state *st,
-                     int parity, int pbuf, int xtwo, const double *pq_parts, unsigned npq, double *partials2,
+                     int parity, int pbuf, int xtwo, int rev, const double *pq_parts, unsigned npq, double *partials2,
                      unsigned *npartials, void *stream);
 void lsb_k_pcg_xfix(unsigned n, const double *p0, const double *p1, double *x, const struct lsb_pcg_state *st,
                     void *stream);
