@@ -673,6 +673,40 @@ int lsb_hip_solver_time_spmv(lsb_hip_solver *s, int warm, int reps,
 int lsb_hip_solver_jacobi_sweep_dev(lsb_hip_solver *s, double w,
                                     const double *d_b, double *d_x);
 
+/* Several right-hand sides at once (hip_mrhs.hip, hip_mrhs_drv.c): nrhs INDEPENDENT Jacobi-PCG recurrences
+ * advanced by the same launches -- every column has its own alpha, beta, residual norms, iteration count
+ * and status, a column that has stopped is frozen while the others run on, and the batch runs until every
+ * column has stopped.  Not block-CG.  The blocks are column-major with a leading dimension (ld >= n_local),
+ * like BLAS and CHOLMOD's dense matrices, in the caller's numbering.  Any nrhs >= 1: one column goes through
+ * lsb_hip_solver_solve_dev and gives its bits; 2 .. 8 run as one batch of 2, 4 or 8 columns (padded with
+ * zero columns, frozen from the start); more run in batches of 8 and a remainder.
+ * Returns 1 when the backend is not initialised; 2 for bad arguments (nrhs == 0, ld < n_local, null
+ * pointers) and for a solver this version does not serve.  Served: one shard in one process, LSB_PREC_FP64,
+ * krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE; GMRES, BiCGSTAB, PCG1, Chebyshev, block-Jacobi, FSAI,
+ * AMG, nvirt > 1, distributed and persistent solvers answer 2 -- nothing falls back to a loop of single solves.
+ * res[c] (nrhs entries) is column c's own result: iters, status, relres, corrections, true_relres are the
+ * column's; seconds is the wall-clock of the batch the column ran in and spmvs the SpMM launches of that
+ * batch, the same in all its entries; spmv_ms = 0, spmv_samples = 0 (opts.sample_spmv is ignored).
+ * Stop rules per column as in a single solve: b_c = 0 -> CONVERGED, 0 iterations, x_c = 0; r.r <= tol^2 b.b
+ * on the recurrence -> CONVERGED; iters >= maxit -> MAXIT; p.q zero or not finite -> BREAKDOWN.
+ * opts.verify = 1: after the batch stops one SpMM recomputes ||b_c - S x_c|| / ||b_c|| into true_relres
+ * (-1 without verify, and for b_c = 0); columns called converged whose recomputed residual misses tol restart
+ * in place (r = b - S x, p = D^-1 r, x kept, iterations counted on), at most 6 rounds, after which a column
+ * that still misses is MAXIT.  opts.use_graph is honoured through a graph cache of its own. */
+/* Y = Op X for nrhs columns; column c of X at d_X + c*ldx, n_local doubles, caller's numbering (as spmv_dev) */
+int lsb_hip_solver_spmm_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_X, size_t ldx,
+                            double *d_Y, size_t ldy);
+/* x_c = S^-1 b_c from x0 = 0 for c < nrhs; res[c] is column c's own result */
+int lsb_hip_solver_solve_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_B, size_t ldb,
+                                   double *d_X, size_t ldx, struct lsb_hip_result *res);
+int lsb_hip_solver_solve_multi(lsb_hip_solver *s, unsigned nrhs, const double *B, size_t ldb,
+                               double *X, size_t ldx, struct lsb_hip_result *res);   /* host buffers */
+/* bytes one iteration of the batch must move: 12 nnz + 4 (n + 1) + 8 n (11 Kp + 2 [the diagonal is a
+ * vector]) with n the internal row count and Kp the batch width -- the CSR arrays once whatever the width,
+ * 2 passes of the SpMM (x once, y once) and the 9 of the classic form's sweeps per column, the diagonal once
+ * per sweep for all columns; 0 where solve_multi does not apply */
+unsigned long long lsb_hip_solver_multi_iteration_bytes(const lsb_hip_solver *s, unsigned nrhs);
+
 unsigned lsb_hip_solver_nrows_local(const lsb_hip_solver *s);
 /* rows the solver added inside: 0, or the pad rows of a line-padded 2-D grid (lsb_csr_pad_lines;
  * a constant-coefficient grid of >= 1 M rows whose lines are not whole slices, LSBENCH_HIP_PAD_LINES=0

@@ -276,6 +276,50 @@ class Solver:
     def spmv_dev(self, d_x, d_y):
         L.check(L.load().lsb_hip_solver_spmv_dev(self._h, _ptr(d_x), _ptr(d_y)), "spmv_dev")
 
+    @staticmethod
+    def _block(t, what):
+        """(pointer, nrhs, ld) of a 2-D torch tensor of shape (nrhs, ld'): one row per column of the block"""
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError("%s: a 2-D tensor (nrhs, ld) with unit stride along its rows is needed" % what)
+        return _ptr(t), int(t.shape[0]), int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+    def spmm_dev(self, d_X, d_Y):
+        """Y = Op X for the nrhs columns held as the ROWS of two 2-D device tensors (ld = stride(0))."""
+        px, k, ldx = self._block(d_X, "spmm_dev")
+        py, ky, ldy = self._block(d_Y, "spmm_dev")
+        if k != ky:
+            raise ValueError("spmm_dev: X and Y hold different numbers of columns")
+        L.check(L.load().lsb_hip_solver_spmm_dev(self._h, k, px, ldx, py, ldy), "spmm_dev")
+
+    def solve_multi_dev(self, d_B, d_X):
+        """x_c = S^-1 b_c for the nrhs columns held as the ROWS of two 2-D device tensors; returns the list of
+        their Results."""
+        pb, k, ldb = self._block(d_B, "solve_multi_dev")
+        px, kx, ldx = self._block(d_X, "solve_multi_dev")
+        if k != kx:
+            raise ValueError("solve_multi_dev: B and X hold different numbers of columns")
+        res = (L.Result * max(k, 1))()
+        L.check(L.load().lsb_hip_solver_solve_multi_dev(self._h, k, pb, ldb, px, ldx, res), "solve_multi_dev")
+        return list(res)[:k]
+
+    def solve_multi(self, B):
+        """B: numpy (n_local, nrhs) of any order.  Returns (X of the same shape, [Result, ...])."""
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != self.n_local:
+            raise ValueError("solve_multi: B must be (n_local, nrhs)")
+        k = B.shape[1]
+        X = np.empty((self.n_local, k), np.float64, order="F")
+        res = (L.Result * max(k, 1))()
+        ld = max(self.n_local, 1)
+        L.check(L.load().lsb_hip_solver_solve_multi(self._h, k, B.ctypes.data, ld, X.ctypes.data, ld, res),
+                "solve_multi")
+        return X, list(res)[:k]
+
+    def multi_iteration_bytes(self, nrhs):
+        """Bytes one iteration of a batch of nrhs right-hand sides must move (see lsbench_hip.h); 0 where
+        solve_multi does not apply."""
+        return int(L.load().lsb_hip_solver_multi_iteration_bytes(self._h, nrhs))
+
     def spmv_inner_dev(self, d_x, d_y, d_dot=None):
         """y = the product the Krylov loop issues (fp32 matrix values under PREC_MIXED, where spmv_dev
         stays exact); d_dot (one shard only): the launch's fused x.y."""

@@ -1,5 +1,5 @@
-// What the SpMV kernels (hip_kernels.hip) and the BLAS-1 / PCG sweeps (hip_sweeps.hip) share.
-// Included by those two files only.
+// What the SpMV kernels (hip_kernels.hip), the BLAS-1 / PCG sweeps (hip_sweeps.hip) and the kernels of
+// several right-hand sides (hip_mrhs.hip) share.  Included by those files only.
 #ifndef LSB_HIP_KCOMMON_H
 #define LSB_HIP_KCOMMON_H
 #include <hip/hip_runtime.h>

@@ -1,0 +1,325 @@
+/* Several right-hand sides: host driver (kernels: hip_mrhs.hip). */
+#define _GNU_SOURCE
+#include "hip_solver.h"
+
+/*
+ * lsb_hip_solver_solve_multi[_dev]: nrhs INDEPENDENT Jacobi-PCG recurrences (x0 = 0, M^-1 = diag(dinv):
+ * Jacobi, l1-Jacobi or none) advanced by the same launches -- per iteration the SpMM Q = S P off the
+ * shard's CSR arrays with its fused per-column p.q, k_mrhs_update_xr and k_mrhs_update_p.  Every column has
+ * its own alpha, beta, norms, iteration count and status (lsb_mrhs_state); a column that has stopped is
+ * frozen while the others run on, and the batch runs until every column has stopped.  This is not block-CG.
+ *
+ * 2 .. 8 columns run as one batch of kp = 2, 4 or 8, padded with zero columns (b = 0: frozen from the
+ * start); more run in batches of 8 and a remainder; one column IS lsb_hip_solver_solve_dev.  The block
+ * vectors b, x, r, p, q are internal (interleaved, internal numbering: k_mrhs_pack / k_mrhs_unpack apply the
+ * permutation of a padded or re-ordered solver), so an iteration -- and a captured graph of iterations --
+ * does not depend on the caller's pointers.  The device decides when to stop; the host enqueues
+ * check_every iterations at a time, one chunk ahead of the poll, or the previous batch's count in one go,
+ * as pcg_run does.
+ *
+ * opts.verify: after the batch stops one SpMM recomputes b - S x of every column; the columns the recurrence
+ * called converged but whose recomputed residual misses the tolerance restart IN PLACE (r = b - S x,
+ * p = D^-1 r, x kept, bb and the threshold unchanged, iterations counted on), all others stay frozen;
+ * LSB_MAX_CORRECTIONS rounds at the most, a column that still misses is MAXIT.
+ *
+ * Served: one shard in one process, fp64 values, krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE.
+ * Every other solver answers 2: nothing falls back to a loop of single solves.
+ */
+#define DINV(s) ((s)->dinv_uniform ? NULL : (s)->d_dinv), (s)->dinv_const
+
+static int mrhs_serves(const lsb_hip_solver *sv) {
+  const struct lsb_hip_opts *o = &sv->o;
+  return !sv->multi && sv->nshard == 1 && !sv->dist && o->precision == LSB_PREC_FP64 &&
+         (o->krylov == LSB_KRYLOV_PCG || o->krylov == LSB_KRYLOV_AUTO) &&
+         (o->precond == LSB_PRECOND_JACOBI || o->precond == LSB_PRECOND_L1JACOBI ||
+          o->precond == LSB_PRECOND_NONE) &&
+         o->persistent <= 0 && !sv->ps.use && (unsigned long long)sv->sh[0].n * LSB_MRHS_MAX < (1ull << 32);
+}
+
+static unsigned batch_width(unsigned nrhs) { return nrhs <= 2 ? 2u : nrhs <= 4 ? 4u : 8u; }
+
+static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
+  struct mrhs_work *w = &sv->mr[kp == 2 ? 0 : kp == 4 ? 1 : 2];
+  if (w->kp)
+    return w;
+  const struct shard *s = &sv->sh[0];
+  if (!sv->mr_hst) {
+    LSB_CHK_HIP(hipHostMalloc((void **)&sv->mr_hst, 2 * sizeof(struct lsb_mrhs_state), 0));
+    /* lanes per row of the SpMM: the shard's (from its mean row length); LSBENCH_HIP_MRHS_LANES is the A/B switch */
+    const char *e = getenv("LSBENCH_HIP_MRHS_LANES");
+    sv->mr_lanes = e && atoi(e) > 0 ? (unsigned)atoi(e) : s->lanes;
+  }
+  /* 256-byte aligned pieces of one allocation, the blocks first: their placement relative to one another is
+   * the same in every solver */
+  const size_t blk = (((size_t)s->n * kp * sizeof(double)) + 255) & ~(size_t)255;
+  const size_t ppq = (size_t)LSB_MAX_PARTIALS * kp * sizeof(double);
+  const size_t pp2 = (size_t)LSB_STREAM_GRID_CAP * 2 * kp * sizeof(double);
+  const size_t stb = (sizeof(struct lsb_mrhs_state) + 255) & ~(size_t)255;
+  w->mem = (char *)lsb_hip_malloc(5 * blk + ppq + pp2 + stb);
+  LSB_CHK_HIP(hipMemsetAsync(w->mem, 0, 5 * blk + ppq + pp2 + stb, g_stream));
+  w->b = (double *)w->mem, w->x = (double *)(w->mem + blk), w->r = (double *)(w->mem + 2 * blk);
+  w->p = (double *)(w->mem + 3 * blk), w->q = (double *)(w->mem + 4 * blk);
+  w->parts_pq = (double *)(w->mem + 5 * blk);
+  w->parts2 = (double *)(w->mem + 5 * blk + ppq);
+  w->st = (struct lsb_mrhs_state *)(w->mem + 5 * blk + ppq + pp2);
+  w->kp = kp;
+  return w;
+}
+
+void mrhs_drop_graphs(lsb_hip_solver *sv) {
+  for (int k = 0; k < 3; k++)
+    for (int i = 0; i < LSB_NGRAPH; i++)
+      if (sv->mr[k].g[i].exec) {
+        LSB_CHK_HIP(hipGraphExecDestroy(sv->mr[k].g[i].exec));
+        sv->mr[k].g[i].exec = NULL;
+      }
+}
+
+void mrhs_free(lsb_hip_solver *sv) {
+  mrhs_drop_graphs(sv);
+  for (int k = 0; k < 3; k++) {
+    lsb_hip_free(sv->mr[k].mem);
+    memset(&sv->mr[k], 0, sizeof sv->mr[k]);
+  }
+  if (sv->mr_hst)
+    LSB_CHK_HIP(hipHostFree(sv->mr_hst));
+  sv->mr_hst = NULL;
+}
+
+/* Bytes one iteration of a batch of nrhs columns must move: the CSR arrays once whatever the width (12 B per
+ * non-zero + the row offsets), the SpMM's x in and y out and the 9 passes of the classic form's sweeps per
+ * column, the inverse diagonal once per sweep for all columns where it is a vector. */
+unsigned long long lsb_hip_solver_multi_iteration_bytes(const lsb_hip_solver *sv, unsigned nrhs) {
+  if (!sv || nrhs == 0 || !mrhs_serves(sv))
+    return 0;
+  const struct shard *s = &sv->sh[0];
+  const unsigned kp = nrhs == 1 ? 1u : batch_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs);
+  return 12ull * s->nnz + 4ull * (s->n + 1ull) + 8ull * s->n * (11ull * kp + (s->dinv_uniform ? 0u : 2u));
+}
+
+/* Iterations per host poll: pcg_run's rule (about 0.3 ms of device work at an assumed 4 TB/s) on this
+ * iteration's bytes; even, so that a chunk leaves the parity where it found it. */
+static int mrhs_chunk(const lsb_hip_solver *sv, unsigned kp) {
+  if (sv->o.check_every > 0)
+    return (sv->o.check_every + 1) & ~1;
+  double us = (double)lsb_hip_solver_multi_iteration_bytes(sv, kp) / 4.0e6;
+  if (us < 6.0)
+    us = 6.0;
+  int c = (int)(300.0 / us);
+  c = c < 8 ? 8 : c > 256 ? 256 : c;
+  return c & ~1;
+}
+
+static void spmm_shard(lsb_hip_solver *sv, struct mrhs_work *w, const double *x, double *y, const double *bres,
+                       unsigned *npq, const struct lsb_mrhs_state *st) {
+  const struct shard *s = &sv->sh[0];
+  lsb_k_spmm_csr(w->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, sv->mr_lanes, x, y, bres, w->parts_pq, npq, st,
+                 g_stream);
+}
+
+static void mrhs_enqueue_iter(lsb_hip_solver *sv, struct mrhs_work *w, int parity) {
+  const struct shard *s = &sv->sh[0];
+  unsigned npq = 0, np2 = 0;
+  spmm_shard(sv, w, w->p, w->q, NULL, &npq, w->st);
+  lsb_k_mrhs_update_xr(w->kp, s->n, w->p, w->q, DINV(s), w->x, w->r, w->st, parity, w->parts_pq, npq, w->parts2,
+                       &np2, g_stream);
+  lsb_k_mrhs_update_p(w->kp, s->n, w->r, DINV(s), w->p, w->st, parity, w->parts2, np2, g_stream);
+}
+
+/* hipGraph of `iters` (even) iterations of this width: one linear chain on internal buffers, keyed on the count */
+static hipGraphExec_t mrhs_graph(lsb_hip_solver *sv, struct mrhs_work *w, int iters) {
+  for (int i = 0; i < LSB_NGRAPH; i++)
+    if (w->g[i].exec && w->g[i].iters == iters)
+      return w->g[i].exec;
+  const int slot = w->gnext;
+  w->gnext = (w->gnext + 1) % LSB_NGRAPH;
+  if (w->g[slot].exec)
+    LSB_CHK_HIP(hipGraphExecDestroy(w->g[slot].exec));
+  hipGraph_t g;
+  LSB_CHK_HIP(hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal));
+  for (int i = 0; i < iters; i++)
+    mrhs_enqueue_iter(sv, w, i & 1);
+  LSB_CHK_HIP(hipStreamEndCapture(g_stream, &g));
+  LSB_CHK_HIP(hipGraphInstantiate(&w->g[slot].exec, g, NULL, NULL, 0));
+  LSB_CHK_HIP(hipGraphDestroy(g));
+  w->g[slot].iters = iters;
+  return w->g[slot].exec;
+}
+
+/* Enqueue iterations until no column is running; the final state lands in mr_hst[0].  *hint: the launches
+ * this stretch of the previous batch took, enqueued in one go. */
+static void mrhs_run(lsb_hip_solver *sv, struct mrhs_work *w, unsigned *hint) {
+  struct lsb_mrhs_state *hst = sv->mr_hst;
+  const int chunk = mrhs_chunk(sv, w->kp);
+  const int use_graph = sv->o.use_graph;
+  const int before = hst[0].nspmm; /* (0 for the solve proper: the caller clears it) */
+  unsigned done = 0;
+#define ENQUEUE_ITERS(count)                                                   \
+  do {                                                                         \
+    const int cnt_ = (count);                                                  \
+    if (use_graph) {                                                           \
+      LSB_CHK_HIP(hipGraphLaunch(mrhs_graph(sv, w, cnt_), g_stream));          \
+    } else {                                                                   \
+      for (int i_ = 0; i_ < cnt_; i_++)                                        \
+        mrhs_enqueue_iter(sv, w, i_ & 1);                                      \
+    }                                                                          \
+    done += (unsigned)cnt_;                                                    \
+  } while (0)
+#define ENQUEUE_POLL(slot)                                                     \
+  do {                                                                         \
+    LSB_CHK_HIP(hipMemcpyAsync(&hst[slot], w->st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream)); \
+    LSB_CHK_HIP(hipEventRecord(sv->ev_poll[slot], g_stream));                  \
+  } while (0)
+  int fin = -1;
+  if (*hint > 0) {
+    /* graphs beyond ~1k iterations cost more to build than they save */
+    int first = (int)((*hint + 1) & ~1u);
+    while (use_graph && first > 1024)
+      first = ((first / 2) + 1) & ~1;
+    int left = (int)((*hint + 1) & ~1u);
+    while (left > 0) {
+      const int c = left < first ? ((left + 1) & ~1) : first;
+      ENQUEUE_ITERS(c);
+      left -= c;
+    }
+    ENQUEUE_POLL(0);
+    wait_event(sv, sv->ev_poll[0], "poll of a hinted batch");
+    if (!hst[0].running)
+      fin = 0;
+  }
+  if (fin < 0) {
+    int cur = 0;
+    ENQUEUE_ITERS(chunk);
+    ENQUEUE_POLL(0);
+    for (;;) {
+      ENQUEUE_ITERS(chunk); /* one chunk ahead of the poll */
+      ENQUEUE_POLL(cur ^ 1);
+      wait_event(sv, sv->ev_poll[cur], "poll of the batch");
+      if (!hst[cur].running) {
+        fin = cur;
+        break;
+      }
+      cur ^= 1;
+      if (done > sv->o.maxit + *hint + 1u + 3u * (unsigned)chunk) /* cannot happen */
+        errx(EXIT_FAILURE, "hip_cdna4: a batch of right-hand sides ran past maxit without a status");
+    }
+    drain_stream(sv, "drain after the batch"); /* the speculative chunk */
+  }
+#undef ENQUEUE_ITERS
+#undef ENQUEUE_POLL
+  if (fin != 0)
+    hst[0] = hst[fin];
+  *hint = (unsigned)(hst[0].nspmm - before);
+}
+
+/* one batch: nb <= 8 columns of the caller's blocks */
+static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_t ldb, double *d_X, size_t ldx,
+                       struct lsb_hip_result *res) {
+  struct mrhs_work *w = mrhs_setup(sv, batch_width(nb));
+  const struct shard *s = &sv->sh[0];
+  struct lsb_mrhs_state *hst = sv->mr_hst;
+  const unsigned kp = w->kp, n = s->n;
+  unsigned np2 = 0, npq = 0, nverify = 0;
+  const double t0 = wall_seconds();
+  lsb_k_mrhs_pack(n, kp, nb, sv->d_perm, d_B, ldb, w->b, g_stream);
+  lsb_k_mrhs_init(kp, n, w->b, DINV(s), w->x, w->r, w->p, w->parts2, &np2, g_stream);
+  lsb_k_mrhs_init_state(kp, w->st, w->parts2, np2, sv->o.tol, (int)sv->o.maxit, g_stream);
+  hst[0].nspmm = 0;
+  for (int round = 0;; round++) {
+    mrhs_run(sv, w, &w->hint[round < LSB_MAX_CORRECTIONS ? round : LSB_MAX_CORRECTIONS]);
+    if (!(sv->o.verify && sv->o.tol > 0.0))
+      break;
+    int any = 0;
+    for (unsigned c = 0; c < nb; c++)
+      any |= hst[0].c[c].status == LSB_STATUS_CONVERGED && hst[0].c[c].bb > 0.0;
+    if (!any)
+      break;
+    /* "converged" is reported only for the residual RECOMPUTED from x */
+    const int more = round < LSB_MAX_CORRECTIONS;
+    spmm_shard(sv, w, w->x, w->q, w->b, &npq, NULL);
+    lsb_k_mrhs_restart(kp, n, w->q, DINV(s), w->r, w->p, w->st, w->parts_pq, npq, more, w->parts2, &np2, g_stream);
+    lsb_k_mrhs_restart_state(kp, w->st, w->parts_pq, npq, w->parts2, np2, more, g_stream);
+    nverify++;
+    LSB_CHK_HIP(hipMemcpyAsync(&hst[0], w->st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream));
+    drain_stream(sv, "recomputed residuals of the batch");
+    if (!hst[0].running)
+      break;
+  }
+  lsb_k_mrhs_unpack(n, kp, nb, sv->d_perm, w->x, d_X, ldx, g_stream);
+  drain_stream(sv, "un-packing the batch");
+  const double seconds = wall_seconds() - t0;
+  for (unsigned c = 0; c < nb; c++) {
+    const struct lsb_pcg_state *st = &hst[0].c[c];
+    struct lsb_hip_result r;
+    memset(&r, 0, sizeof r);
+    r.iters = (unsigned)st->iters;
+    r.status = st->status;
+    r.relres = st->bb > 0.0 ? sqrt(st->rr / st->bb) : 0.0;
+    r.true_relres = hst[0].true_relres[c];
+    if (r.true_relres >= 0.0)
+      r.relres = r.true_relres;
+    r.corrections = (unsigned)hst[0].corrections[c];
+    r.seconds = seconds;
+    r.spmvs = (unsigned)hst[0].nspmm + nverify;
+    res[c] = r;
+  }
+}
+
+static int multi_args_bad(const lsb_hip_solver *sv, unsigned nrhs, const void *a, size_t lda, const void *b,
+                          size_t ldb) {
+  return !sv || !a || !b || nrhs == 0 || lda < sv->n_user || ldb < sv->n_user;
+}
+
+int lsb_hip_solver_solve_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
+                                   size_t ldx, struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (multi_args_bad(sv, nrhs, d_B, ldb, d_X, ldx) || !mrhs_serves(sv))
+    return 2;
+  if (nrhs == 1)
+    return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
+  struct lsb_hip_result *tmp = res ? res : lsb_calloc(struct lsb_hip_result, nrhs);
+  for (unsigned c0 = 0; c0 < nrhs; c0 += LSB_MRHS_MAX) {
+    const unsigned nb = nrhs - c0 < LSB_MRHS_MAX ? nrhs - c0 : LSB_MRHS_MAX;
+    mrhs_batch(sv, nb, d_B + (size_t)c0 * ldb, ldb, d_X + (size_t)c0 * ldx, ldx, tmp + c0);
+  }
+  g_last = tmp[nrhs - 1];
+  if (!res)
+    free(tmp);
+  return 0;
+}
+
+int lsb_hip_solver_solve_multi(lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X, size_t ldx,
+                               struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (multi_args_bad(sv, nrhs, B, ldb, X, ldx) || !mrhs_serves(sv))
+    return 2;
+  const size_t n = sv->n_user, bytes = n * sizeof(double);
+  double *d_B = (double *)lsb_hip_malloc(bytes * nrhs), *d_X = (double *)lsb_hip_malloc(bytes * nrhs);
+  LSB_CHK_HIP(hipMemcpy2D(d_B, bytes, B, ldb * sizeof(double), bytes, nrhs, hipMemcpyHostToDevice));
+  const int rc = lsb_hip_solver_solve_multi_dev(sv, nrhs, d_B, n, d_X, n, res);
+  LSB_CHK_HIP(hipMemcpy2D(X, ldx * sizeof(double), d_X, bytes, bytes, nrhs, hipMemcpyDeviceToHost));
+  lsb_hip_free(d_B), lsb_hip_free(d_X);
+  return rc;
+}
+
+/* Y = Op X: the SpMM of the iteration on its own, through the same pack / unpack */
+int lsb_hip_solver_spmm_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_X, size_t ldx, double *d_Y,
+                            size_t ldy) {
+  if (!lsb_initialized)
+    return 1;
+  if (multi_args_bad(sv, nrhs, d_X, ldx, d_Y, ldy) || !mrhs_serves(sv))
+    return 2;
+  const struct shard *s = &sv->sh[0];
+  for (unsigned c0 = 0; c0 < nrhs; c0 += LSB_MRHS_MAX) {
+    const unsigned nb = nrhs - c0 < LSB_MRHS_MAX ? nrhs - c0 : LSB_MRHS_MAX;
+    struct mrhs_work *w = mrhs_setup(sv, batch_width(nb));
+    unsigned npq = 0;
+    lsb_k_mrhs_pack(s->n, w->kp, nb, sv->d_perm, d_X + (size_t)c0 * ldx, ldx, w->p, g_stream);
+    spmm_shard(sv, w, w->p, w->q, NULL, &npq, NULL);
+    lsb_k_mrhs_unpack(s->n, w->kp, nb, sv->d_perm, w->q, d_Y + (size_t)c0 * ldy, ldy, g_stream);
+  }
+  drain_stream(sv, "lsb_hip_solver_spmm_dev");
+  return 0;
+}

@@ -625,6 +625,7 @@ void drop_graphs(lsb_hip_solver *sv) {
       LSB_CHK_HIP(hipGraphExecDestroy(sv->gcache[i].exec));
       sv->gcache[i].exec = NULL;
     }
+  mrhs_drop_graphs(sv);
 }
 
 /*

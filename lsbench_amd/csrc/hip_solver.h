@@ -10,6 +10,7 @@
  *   hip_pcg.c        PCG iteration forms (one chosen per solver) and the host loop
  *   hip_gmres_drv.c  GMRES(m) driver
  *   hip_bicgstab_drv.c  BiCGSTAB driver
+ *   hip_mrhs_drv.c   several right-hand sides: multi-RHS Jacobi-PCG on a CSR SpMM
  * Nothing here is part of the C-ABI (include/lsbench_hip.h).
  */
 #ifndef HIP_SOLVER_H
@@ -252,6 +253,22 @@ struct lsb_hip_solver {
   } *bcg;
   double *bcg_red; /* nshard x BCG_RED doubles: the all-reduced dot products */
   struct lsb_bcg_state *bcg_hst; /* pinned, 2 slots */
+  /* several right-hand sides (allocated on first use, per batch width kp = 2, 4, 8; hip_mrhs_drv.c) */
+  struct mrhs_work {
+    unsigned kp;                 /* 0: not allocated */
+    char *mem;                   /* one allocation: the five interleaved blocks and the partial records */
+    double *b, *x, *r, *p, *q;   /* n kp doubles each */
+    double *parts_pq, *parts2;   /* records of the SpMM (kp wide) and of the sweeps (2 kp wide) */
+    struct lsb_mrhs_state *st;
+    unsigned hint[LSB_MAX_CORRECTIONS + 1]; /* launches the previous batch's solve and restarts took */
+    struct {
+      hipGraphExec_t exec;
+      int iters;
+    } g[LSB_NGRAPH];             /* its own graph cache: the iteration touches these buffers only */
+    int gnext;
+  } mr[3];
+  struct lsb_mrhs_state *mr_hst; /* pinned, 2 slots */
+  unsigned mr_lanes;             /* lanes per row of its SpMM */
   hipEvent_t ev_poll[2], ev_vec, ev_halo;
   hipEvent_t ev[4 * MAX_SAMPLES], ev_t0, ev_t1; /* per sample: e0 SpMV e1 e2 e3 */
   unsigned char samp_skip[MAX_SAMPLES];         /* the sample brackets nothing (a run's first iteration in the
@@ -365,5 +382,8 @@ LSB_INTERNAL int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *
 LSB_INTERNAL int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
                                     struct lsb_hip_result *res);
 LSB_INTERNAL void bicgstab_free(lsb_hip_solver *sv); /* before the shards go: its vectors may sit in their slabs */
+/* hip_mrhs_drv.c */
+LSB_INTERNAL void mrhs_free(lsb_hip_solver *sv); /* before the shards go */
+LSB_INTERNAL void mrhs_drop_graphs(lsb_hip_solver *sv);
 
 #endif

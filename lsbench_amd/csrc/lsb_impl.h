@@ -94,6 +94,19 @@ struct lsb_bcg_state {
                      one or two of an iteration that ended in a breakdown */
 };
 
+/* ---- device-side state of a batch of right-hand sides (hip_mrhs.hip) -----------
+ * One lsb_pcg_state per column (status, iters, maxit, bb, thresh2, rr, rz[2], pq are used) and the words
+ * of the batch.  A column whose status != 0 is frozen; running = some column's status is 0. */
+#define LSB_MRHS_MAX 8
+struct lsb_mrhs_state {
+  struct lsb_pcg_state c[LSB_MRHS_MAX];
+  double true_relres[LSB_MRHS_MAX]; /* opts.verify: ||b_c - S x_c|| / ||b_c|| of the last round, -1: none */
+  double tol;
+  int corrections[LSB_MRHS_MAX];    /* in-place restarts of the column */
+  int running;                      /* the SpMM's gate: cleared by the sweep that sees the last column stop */
+  int nspmm;                        /* SpMM launches of the iterations that did work */
+};
+
 /* Upper bound on per-launch partial sums any reduction kernel writes; the
  * consumer kernels re-reduce them in fixed order (deterministic). */
 #define LSB_MAX_PARTIALS 2048
@@ -289,6 +302,38 @@ void lsb_k_bcg_xr(unsigned n, double *x, const double *phat, const double *shat,
 void lsb_k_bcg_p(unsigned n, const double *r, double *p, const double *v, const double *dinv, double dc,
                  double *phat, struct lsb_bcg_state *st, int parity, const double *parts2, unsigned nparts2,
                  void *stream);
+
+/* Several right-hand sides (hip_mrhs.hip): kp = 2, 4 or 8 columns, block vectors interleaved (element
+ * (i, c) at i kp + c, 16-byte aligned); dinv == NULL: the constant dc.
+ * pack / unpack: the caller's column-major block (leading dimension ld) <-> interleaved; perm[internal row]
+ * = the caller's row, -1 on a pad row, NULL: the same numbering; columns >= nrhs are packed as zeros. */
+void lsb_k_mrhs_pack(unsigned n, unsigned kp, unsigned nrhs, const int *perm, const double *src, size_t ld,
+                     double *dst, void *stream);
+void lsb_k_mrhs_unpack(unsigned n, unsigned kp, unsigned nrhs, const int *perm, const double *src, double *dst,
+                       size_t ld, void *stream);
+/* Y = S X off any CSR (n rows, `lanes` per row), one record of kp partials per workgroup: x_c . y_c, or --
+ * bres != NULL -- y = bres - S x and y_c . y_c.  st != NULL: a no-op once st->running == 0. */
+unsigned lsb_k_spmm_grid(unsigned n, unsigned lanes);
+void lsb_k_spmm_csr(unsigned kp, unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
+                    const double *x, double *y, const double *bres, double *partials, unsigned *npartials,
+                    const struct lsb_mrhs_state *st, void *stream);
+void lsb_k_mrhs_init(unsigned kp, unsigned n, const double *b, const double *dinv, double dc, double *x, double *r,
+                     double *p, double *partials2, unsigned *npartials, void *stream);
+void lsb_k_mrhs_init_state(unsigned kp, struct lsb_mrhs_state *st, const double *partials2, unsigned nparts,
+                           double tol, int maxit, void *stream);
+void lsb_k_mrhs_update_xr(unsigned kp, unsigned n, const double *p, const double *q, const double *dinv, double dc,
+                          double *x, double *r, struct lsb_mrhs_state *st, int parity, const double *pq_parts,
+                          unsigned npq, double *partials2, unsigned *npartials, void *stream);
+void lsb_k_mrhs_update_p(unsigned kp, unsigned n, const double *r, const double *dinv, double dc, double *p,
+                         struct lsb_mrhs_state *st, int parity, const double *parts2, unsigned nparts2,
+                         void *stream);
+/* opts.verify, behind the SpMM with bres = b: the in-place restart of the columns whose recomputed residual
+ * misses the tolerance (more == 0: they become MAXIT instead) */
+void lsb_k_mrhs_restart(unsigned kp, unsigned n, const double *q, const double *dinv, double dc, double *r,
+                        double *p, const struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr, int more,
+                        double *partials, unsigned *npartials, void *stream);
+void lsb_k_mrhs_restart_state(unsigned kp, struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr,
+                              const double *rz_parts, unsigned nrz, int more, void *stream);
 
 /* ---- preconditioners with z as a vector (hip_precond_k.hip) -------------------- */
 void lsb_k_dot2(unsigned n, const double *r, const double *z, double *partials2,

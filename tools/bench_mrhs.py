@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Several right-hand sides at once against the same number of single solves, one MI355X.
+
+On ONE solver per operator, in one process, `--reps` (5) times alternating between
+  (a) nrhs calls of solve_dev -- the existing, unchanged path -- and
+  (b) one solve_multi_dev of nrhs columns,
+for nrhs in 2, 4, 8.  The columns are b_c = (c + 1) i, so every column takes the same iterations either way (to
+one or two: the scaling rounds) and (a) is a fair baseline.  Each shape is warmed up first (two untimed rounds
+each way: the second solve of a shape enqueues the first one's iteration count in one go, and under use_graph
+builds the graph of that count).  Times are a host clock around work that ends in a device synchronise.
+One JSON line on stdout: per operator and nrhs
+  rhs_per_s_single / rhs_per_s_multi   right-hand sides per second, [min, max] over the repetitions
+  us_per_iter_single / _multi          microseconds per iteration (of one solve / of the batch), [min, max]
+  multi_iteration_bytes, frac_of_8TBs  what an iteration of the batch must move, over its time, over 8 TB/s
+  gain                                 true only where (b)'s slowest repetition beats (a)'s fastest
+Progress goes to stderr.
+
+Usage: python tools/bench_mrhs.py [--operators xn3b,tj7a,coef,lap2d] [--reps 5] [--n 3162] [--nrhs 2,4,8]
+                                  [--fixed-iters N]
+"""
+import argparse
+import gzip
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def file_matrix(la, name, tmp):
+    p = os.path.join(ROOT, "tests", "golden", "matrices", name + ".txt")
+    if not os.path.exists(p):
+        out = os.path.join(tmp, name + ".txt")
+        with gzip.open(p + ".gz", "rb") as fi, open(out, "wb") as fo:
+            fo.write(fi.read())
+        p = out
+    return la.lsbench_matrix_read(p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--operators", default="xn3b,tj7a,coef,lap2d")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--n", type=int, default=3162, help="grid side of the two synthetic operators")
+    ap.add_argument("--nrhs", default="2,4,8")
+    ap.add_argument("--fixed-iters", type=int, default=0,
+                    help="cut every solve at this many iterations (tol = 0): for a kernel trace, not for rates")
+    a = ap.parse_args()
+
+    import torch
+
+    import lsbench_amd as la
+
+    assert torch.cuda.is_available(), "needs an MI355X: nothing here is measured on a CPU"
+    torch.cuda.set_device(0)
+    rc = la.hip_cdna4_init()
+    assert rc == 0 or la._lib.load().lsb_hip_stream()
+    tmp = tempfile.mkdtemp()
+    ops = {"xn3b": (lambda: file_matrix(la, "xn3b_A_18", tmp), dict(tol=1e-12), "tests/golden/matrices/xn3b_A_18"),
+           "tj7a": (lambda: file_matrix(la, "tj7a_A_18", tmp), dict(tol=1e-12), "tests/golden/matrices/tj7a_A_18"),
+           "coef": (lambda: la.lsbench_matrix_synth("lap2d:nx=%d,ny=%d,coef=1" % (a.n, a.n)),
+                    dict(tol=1e-8, op_mode=la.OP_RAW), "lap2d:nx=%d,ny=%d,coef=1" % (a.n, a.n)),
+           "lap2d": (lambda: la.lsbench_matrix_synth("lap2d:nx=%d,ny=%d" % (a.n, a.n)),
+                     dict(tol=1e-8, op_mode=la.OP_RAW), "lap2d:nx=%d,ny=%d" % (a.n, a.n))}
+    out = []
+    for key in a.operators.split(","):
+        make, kw, label = ops[key]
+        M = make()
+        t0 = time.time()
+        if a.fixed_iters:
+            kw = dict(kw, tol=0.0)
+        s = la.Solver(M, la.default_opts(maxit=a.fixed_iters or 100000, **kw))
+        n = s.n_local
+        rec = {"operator": label, "rows": n, "nnz": int(s.nnz_local), "tol": kw["tol"], "setup_s": round(time.time() - t0, 2),
+               "padded_rows": int(s.padded), "iteration_bytes_single": int(s.iteration_bytes), "reps": a.reps, "nrhs": {}}
+        for nrhs in [int(v) for v in a.nrhs.split(",")]:
+            d_B = torch.arange(n, dtype=torch.float64, device="cuda:0")[None, :] * \
+                torch.arange(1, nrhs + 1, dtype=torch.float64, device="cuda:0")[:, None]
+            d_X = torch.zeros(nrhs, n, dtype=torch.float64, device="cuda:0")
+            ts, tm, its, itm = [], [], None, None
+
+            def single():
+                t = time.perf_counter()
+                it = [int(s.solve_dev(d_B[c], d_X[c]).iters) for c in range(nrhs)]
+                torch.cuda.synchronize()
+                return time.perf_counter() - t, it
+
+            def multi():
+                t = time.perf_counter()
+                res = s.solve_multi_dev(d_B, d_X)
+                torch.cuda.synchronize()
+                want = la.STATUS_MAXIT if a.fixed_iters else la.STATUS_CONVERGED
+                assert all(r.status == want for r in res), [r.status for r in res]
+                return time.perf_counter() - t, [int(r.iters) for r in res]
+
+            for _ in range(2):  # warm-up of both shapes: the iteration hint, then the graph of that count
+                single(), multi()
+            for k in range(a.reps):
+                t, its = single()
+                ts.append(t)
+                t, itm = multi()
+                tm.append(t)
+                print("%s nrhs %d rep %d: single %.4f s, multi %.4f s" % (key, nrhs, k, ts[-1], tm[-1]),
+                      file=sys.stderr, flush=True)
+            ts, tm = np.array(ts), np.array(tm)
+            mb = s.multi_iteration_bytes(nrhs)
+            us_m = tm * 1e6 / max(itm)
+            rec["nrhs"][str(nrhs)] = {
+                "iters_single": its, "iters_multi": itm,
+                "rhs_per_s_single": [round(nrhs / ts.max(), 3), round(nrhs / ts.min(), 3)],
+                "rhs_per_s_multi": [round(nrhs / tm.max(), 3), round(nrhs / tm.min(), 3)],
+                "us_per_iter_single": [round(float(ts.min() * 1e6 / sum(its)), 3), round(float(ts.max() * 1e6 / sum(its)), 3)],
+                "us_per_iter_multi": [round(float(us_m.min()), 3), round(float(us_m.max()), 3)],
+                "multi_iteration_bytes": int(mb),
+                "frac_of_8TBs": [round(mb / (float(us_m.max()) * 1e-6) / 8e12, 4), round(mb / (float(us_m.min()) * 1e-6) / 8e12, 4)],
+                "gain": bool(tm.max() < ts.min())}
+            del d_B, d_X
+        s.destroy()
+        out.append(rec)
+        print(json.dumps(rec), file=sys.stderr, flush=True)
+    print(json.dumps({"bench": "mrhs", "operators": out}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
