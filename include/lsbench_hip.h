@@ -673,8 +673,8 @@ int lsb_hip_solver_time_spmv(lsb_hip_solver *s, int warm, int reps,
 int lsb_hip_solver_jacobi_sweep_dev(lsb_hip_solver *s, double w,
                                     const double *d_b, double *d_x);
 
-/* Several right-hand sides at once (hip_mrhs.hip, hip_mrhs_drv.c): nrhs INDEPENDENT Jacobi-PCG recurrences
- * advanced by the same launches -- every column has its own alpha, beta, residual norms, iteration count
+/* Several right-hand sides at once (hip_mrhs.hip, hip_mrhs_amg.hip, hip_mrhs_drv.c): nrhs INDEPENDENT PCG
+ * recurrences advanced by the same launches -- every column has its own alpha, beta, residual norms, iteration count
  * and status, a column that has stopped is frozen while the others run on, and the batch runs until every
  * column has stopped.  Not block-CG.  The blocks are column-major with a leading dimension (ld >= n_local),
  * like BLAS and CHOLMOD's dense matrices, in the caller's numbering.  Any nrhs >= 1: one column goes through
@@ -682,8 +682,10 @@ int lsb_hip_solver_jacobi_sweep_dev(lsb_hip_solver *s, double w,
  * zero columns, frozen from the start); more run in batches of 8 and a remainder.
  * Returns 1 when the backend is not initialised; 2 for bad arguments (nrhs == 0, ld < n_local, null
  * pointers) and for a solver this version does not serve.  Served: one shard in one process, LSB_PREC_FP64,
- * krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE; GMRES, BiCGSTAB, PCG1, Chebyshev, block-Jacobi, FSAI,
- * AMG, nvirt > 1, distributed and persistent solvers answer 2 -- nothing falls back to a loop of single solves.
+ * krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE / AMG (one V-cycle per iteration on the block of
+ * residuals: every matrix of the hierarchy is streamed once for all columns, and a column's z has the bits of
+ * the single-column cycle; opts.amg_tail_rows is ignored there); GMRES, BiCGSTAB, PCG1, Chebyshev, block-Jacobi,
+ * FSAI, nvirt > 1, distributed and persistent solvers answer 2 -- nothing falls back to a loop of single solves.
  * res[c] (nrhs entries) is column c's own result: iters, status, relres, corrections, true_relres are the
  * column's; seconds is the wall-clock of the batch the column ran in and spmvs the SpMM launches of that
  * batch, the same in all its entries; spmv_ms = 0, spmv_samples = 0 (opts.sample_spmv is ignored).
@@ -691,7 +693,7 @@ int lsb_hip_solver_jacobi_sweep_dev(lsb_hip_solver *s, double w,
  * on the recurrence -> CONVERGED; iters >= maxit -> MAXIT; p.q zero or not finite -> BREAKDOWN.
  * opts.verify = 1: after the batch stops one SpMM recomputes ||b_c - S x_c|| / ||b_c|| into true_relres
  * (-1 without verify, and for b_c = 0); columns called converged whose recomputed residual misses tol restart
- * in place (r = b - S x, p = D^-1 r, x kept, iterations counted on), at most 6 rounds, after which a column
+ * in place (r = b - S x, p = M^-1 r, x kept, iterations counted on), at most 6 rounds, after which a column
  * that still misses is MAXIT.  opts.use_graph is honoured through a graph cache of its own. */
 /* Y = Op X for nrhs columns; column c of X at d_X + c*ldx, n_local doubles, caller's numbering (as spmv_dev) */
 int lsb_hip_solver_spmm_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_X, size_t ldx,
@@ -704,8 +706,16 @@ int lsb_hip_solver_solve_multi(lsb_hip_solver *s, unsigned nrhs, const double *B
 /* bytes one iteration of the batch must move: 12 nnz + 4 (n + 1) + 8 n (11 Kp + 2 [the diagonal is a
  * vector]) with n the internal row count and Kp the batch width -- the CSR arrays once whatever the width,
  * 2 passes of the SpMM (x once, y once) and the 9 of the classic form's sweeps per column, the diagonal once
- * per sweep for all columns; 0 where solve_multi does not apply */
+ * per sweep for all columns; 0 where solve_multi does not apply, and 0 for an AMG solver: an iteration around a
+ * V-cycle has another shape, as lsb_hip_solver_iteration_bytes answers for every such preconditioner */
 unsigned long long lsb_hip_solver_multi_iteration_bytes(const lsb_hip_solver *s, unsigned nrhs);
+/* Z_c = M^-1 R_c for nrhs columns: the V-cycle of a batch's iteration on its own (blocks as above: column-major
+ * with a leading dimension, caller's numbering; any nrhs >= 1, in batches of 8 and a remainder).  Column c of Z
+ * has the bits of lsb_hip_solver_precond_dev on column c alone.  1 when the backend is not initialised; 2 for
+ * null pointers, nrhs == 0, ld < n_local and for every solver that solve_multi does not serve under AMG (Jacobi,
+ * FSAI, Chebyshev and block-Jacobi solvers among them); Z is not touched then. */
+int lsb_hip_solver_precond_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_R, size_t ldr,
+                                     double *d_Z, size_t ldz);
 
 unsigned lsb_hip_solver_nrows_local(const lsb_hip_solver *s);
 /* rows the solver added inside: 0, or the pad rows of a line-padded 2-D grid (lsb_csr_pad_lines;

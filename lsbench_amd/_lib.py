@@ -240,6 +240,7 @@ SIGNATURES = {
     "lsb_hip_solver_solve_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_solve_multi": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_multi_iteration_bytes": (C.c_ulonglong, [_vp, _u]),
+    "lsb_hip_solver_precond_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
     "lsb_hip_solver_precond_dev": (_i, [_vp, _vp, _vp]),
     "lsb_hip_solver_amg_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u)]),
     "lsb_hip_solver_cheb_interval": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),

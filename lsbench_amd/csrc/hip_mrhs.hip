@@ -19,60 +19,7 @@
 // depends on their number only (no atomics: the same bits from run to run, and a column's bits do not depend
 // on what the other columns hold).
 #include "hip_kcommon.h"
-
-typedef double d2v __attribute__((ext_vector_type(2)));
-
-// Sum `nparts` records of width W (one per workgroup of an earlier launch) per component into sout[W]: thread
-// t takes component t mod W of records t / W, t / W + WG / W, ...; butterfly over the lanes of a wave that
-// share the component, the four waves through LDS in fixed order.  sred: 4 W doubles.
-template <int W>
-__device__ __forceinline__ void wg_sum_records(const double *__restrict__ parts, unsigned nparts, double *sred,
-                                               double *sout) {
-  static_assert(W >= 2 && W <= 32 && (W & (W - 1)) == 0, "record width");
-  const unsigned t = threadIdx.x, k = t % W;
-  double v = 0.0;
-  for (unsigned i = t / W; i < nparts; i += WG / W)
-    v += parts[(size_t)i * W + k];
-#pragma unroll
-  for (int off = 32; off >= W; off >>= 1)
-    v += __shfl_xor(v, off, 64);
-  __syncthreads(); // sred / sout may still be read from a previous call
-  if ((t & 63) < W)
-    sred[(t >> 6) * W + k] = v;
-  __syncthreads();
-  if (t < W)
-    sout[t] = (sred[t] + sred[W + t]) + (sred[2 * W + t] + sred[3 * W + t]);
-  __syncthreads();
-}
-
-// Per-column sums of NV quantities over the workgroup: lane t holds, for each quantity, the sums of its two
-// columns (2 t mod KP, + 1).  sout[q KP + c]; sred: 4 NV KP doubles.
-template <int KP, int NV>
-__device__ __forceinline__ void wg_sum_cols(double (&v)[NV][2], double *sred, double *sout) {
-  constexpr int H = KP / 2;
-#pragma unroll
-  for (int q = 0; q < NV; q++) {
-#pragma unroll
-    for (int off = 32; off >= H; off >>= 1) {
-      v[q][0] += __shfl_xor(v[q][0], off, 64);
-      v[q][1] += __shfl_xor(v[q][1], off, 64);
-    }
-  }
-  const unsigned t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  constexpr int W = NV * KP;
-  __syncthreads();
-  if (lane < H) {
-#pragma unroll
-    for (int q = 0; q < NV; q++) {
-      sred[wave * W + q * KP + 2 * lane] = v[q][0];
-      sred[wave * W + q * KP + 2 * lane + 1] = v[q][1];
-    }
-  }
-  __syncthreads();
-  if (t < W)
-    sout[t] = (sred[t] + sred[W + t]) + (sred[2 * W + t] + sred[3 * W + t]);
-  __syncthreads();
-}
+#include "hip_mrhs_k.h"
 
 // --------------------------------------------------------------------------
 // caller's column-major block (leading dimension ld, caller's numbering) <-> interleaved (internal numbering)
@@ -492,13 +439,6 @@ __global__ __launch_bounds__(WG) void k_mrhs_update_p(unsigned n, const double *
 // tolerance: r = q, p = D^-1 r, x kept, bb and the threshold unchanged, iterations counted on.  Every other
 // column stays frozen.  more == 0: no round is left, such a column becomes MAXIT.
 // --------------------------------------------------------------------------
-__device__ __forceinline__ double mrhs_true_relres(const lsb_pcg_state *c, double rr) {
-  return c->bb > 0.0 ? sqrt(rr / c->bb) : -1.0;
-}
-__device__ __forceinline__ bool mrhs_misses(const lsb_pcg_state *c, double rr, double tol) {
-  return c->status == LSB_STATUS_CONVERGED && c->bb > 0.0 && !(mrhs_true_relres(c, rr) <= tol);
-}
-
 // the sweep: reads the state, writes r and p of the restarting columns and one record (r.dinv.r per column)
 template <int KP>
 __global__ __launch_bounds__(WG) void k_mrhs_restart(unsigned n, const double *__restrict__ q,
@@ -586,24 +526,7 @@ __global__ __launch_bounds__(WG) void k_mrhs_restart_state(lsb_mrhs_state *__res
 // --------------------------------------------------------------------------
 // Launchers (C ABI).  kp: 2, 4 or 8.
 // --------------------------------------------------------------------------
-static unsigned kshift_of(unsigned kp) {
-  if (kp != 2 && kp != 4 && kp != 8)
-    errx(EXIT_FAILURE, "hip_mrhs: a batch is 2, 4 or 8 columns wide, not %u", kp);
-  return kp == 2 ? 1u : kp == 4 ? 2u : 3u;
-}
 static unsigned spmm_lanes(unsigned L) { return L == 2 || L == 4 || L == 8 || L == 16 || L == 32 ? L : 64; }
-// grid of the sweeps over n rows of kp columns: 16 B per lane over n kp doubles
-static unsigned sweep_grid(unsigned n, unsigned kp) { return lsb_k_blas1_grid(n * kp); }
-
-#define KP_DISPATCH(kp, CALL)                                                  \
-  do {                                                                         \
-    switch (kshift_of(kp)) {                                                   \
-    case 1: { constexpr int KP = 2; CALL; } break;                             \
-    case 2: { constexpr int KP = 4; CALL; } break;                             \
-    default: { constexpr int KP = 8; CALL; } break;                            \
-    }                                                                          \
-  } while (0)
-
 template <int KP, bool RES>
 static void spmm_launch(unsigned L, unsigned g, unsigned n, const int *offs, const int *cols, const double *vals,
                         const double *x, double *y, const double *bres, double *partials,

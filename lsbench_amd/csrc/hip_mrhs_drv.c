@@ -1,4 +1,4 @@
-/* Several right-hand sides: host driver (kernels: hip_mrhs.hip). */
+/* Several right-hand sides: host driver (kernels: hip_mrhs.hip, hip_mrhs_amg.hip). */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
@@ -22,7 +22,13 @@
  * p = D^-1 r, x kept, bb and the threshold unchanged, iterations counted on), all others stay frozen;
  * LSB_MAX_CORRECTIONS rounds at the most, a column that still misses is MAXIT.
  *
- * Served: one shard in one process, fp64 values, krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE.
+ * LSB_PRECOND_AMG: z = M^-1 r is one V-cycle on the block r (amg_vcycle_multi: every matrix of the hierarchy is
+ * streamed once for all columns, each column with the bits of the single-column cycle), so z is a block of its
+ * own and an iteration is SpMM, k_amg_mrhs_update_xr, the cycle, k_amg_mrhs_update_p: the fine level's last
+ * sweep leaves (r.z, r.r) of every column, there is no dot-product launch.  The cycle is gated on `running`
+ * like the SpMM; the restart of opts.verify runs one un-gated cycle on r = b - S x.
+ *
+ * Served: one shard in one process, fp64 values, krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE / AMG.
  * Every other solver answers 2: nothing falls back to a loop of single solves.
  */
 #define DINV(s) ((s)->dinv_uniform ? NULL : (s)->d_dinv), (s)->dinv_const
@@ -32,9 +38,11 @@ static int mrhs_serves(const lsb_hip_solver *sv) {
   return !sv->multi && sv->nshard == 1 && !sv->dist && o->precision == LSB_PREC_FP64 &&
          (o->krylov == LSB_KRYLOV_PCG || o->krylov == LSB_KRYLOV_AUTO) &&
          (o->precond == LSB_PRECOND_JACOBI || o->precond == LSB_PRECOND_L1JACOBI ||
-          o->precond == LSB_PRECOND_NONE) &&
+          o->precond == LSB_PRECOND_NONE || (o->precond == LSB_PRECOND_AMG && sv->sh[0].amg)) &&
          o->persistent <= 0 && !sv->ps.use && (unsigned long long)sv->sh[0].n * LSB_MRHS_MAX < (1ull << 32);
 }
+
+static int mrhs_amg(const lsb_hip_solver *sv) { return sv->o.precond == LSB_PRECOND_AMG; }
 
 static unsigned batch_width(unsigned nrhs) { return nrhs <= 2 ? 2u : nrhs <= 4 ? 4u : 8u; }
 
@@ -53,7 +61,8 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
    * the same in every solver */
   const size_t blk = (((size_t)s->n * kp * sizeof(double)) + 255) & ~(size_t)255;
   const size_t ppq = (size_t)LSB_MAX_PARTIALS * kp * sizeof(double);
-  const size_t pp2 = (size_t)LSB_STREAM_GRID_CAP * 2 * kp * sizeof(double);
+  /* (an AMG solver's records of (r.z, r.r) come from a row kernel's grid, not from a sweep's) */
+  const size_t pp2 = (size_t)(mrhs_amg(sv) ? LSB_MAX_PARTIALS : LSB_STREAM_GRID_CAP) * 2 * kp * sizeof(double);
   const size_t stb = (sizeof(struct lsb_mrhs_state) + 255) & ~(size_t)255;
   w->mem = (char *)lsb_hip_malloc(5 * blk + ppq + pp2 + stb);
   LSB_CHK_HIP(hipMemsetAsync(w->mem, 0, 5 * blk + ppq + pp2 + stb, g_stream));
@@ -62,6 +71,24 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
   w->parts_pq = (double *)(w->mem + 5 * blk);
   w->parts2 = (double *)(w->mem + 5 * blk + ppq);
   w->st = (struct lsb_mrhs_state *)(w->mem + 5 * blk + ppq + pp2);
+  if (mrhs_amg(sv)) {
+    /* the blocks of the cycle: z, level 0's second smoothing buffer and residual, four vectors per coarser level */
+    const struct amg_dev *a = s->amg;
+    size_t total = 3 * blk, off = 3 * blk;
+    for (unsigned l = 1; l < a->nlev; l++)
+      total += (4 * (size_t)a->lv[l].n * kp * sizeof(double) + 255) & ~(size_t)255;
+    w->amg_mem = (char *)lsb_hip_malloc(total);
+    LSB_CHK_HIP(hipMemsetAsync(w->amg_mem, 0, total, g_stream));
+    w->av = lsb_calloc(struct amg_mvec, a->nlev);
+    w->z = (double *)w->amg_mem;
+    w->av[0].tmp = (double *)(w->amg_mem + blk), w->av[0].r = (double *)(w->amg_mem + 2 * blk);
+    for (unsigned l = 1; l < a->nlev; l++) {
+      const size_t nl = (size_t)a->lv[l].n * kp;
+      double *buf = (double *)(w->amg_mem + off);
+      w->av[l].b = buf, w->av[l].out = buf + nl, w->av[l].tmp = buf + 2 * nl, w->av[l].r = buf + 3 * nl;
+      off += (4 * nl * sizeof(double) + 255) & ~(size_t)255;
+    }
+  }
   w->kp = kp;
   return w;
 }
@@ -78,7 +105,8 @@ void mrhs_drop_graphs(lsb_hip_solver *sv) {
 void mrhs_free(lsb_hip_solver *sv) {
   mrhs_drop_graphs(sv);
   for (int k = 0; k < 3; k++) {
-    lsb_hip_free(sv->mr[k].mem);
+    lsb_hip_free(sv->mr[k].mem), lsb_hip_free(sv->mr[k].amg_mem);
+    free(sv->mr[k].av);
     memset(&sv->mr[k], 0, sizeof sv->mr[k]);
   }
   if (sv->mr_hst)
@@ -90,7 +118,7 @@ void mrhs_free(lsb_hip_solver *sv) {
  * non-zero + the row offsets), the SpMM's x in and y out and the 9 passes of the classic form's sweeps per
  * column, the inverse diagonal once per sweep for all columns where it is a vector. */
 unsigned long long lsb_hip_solver_multi_iteration_bytes(const lsb_hip_solver *sv, unsigned nrhs) {
-  if (!sv || nrhs == 0 || !mrhs_serves(sv))
+  if (!sv || nrhs == 0 || !mrhs_serves(sv) || mrhs_amg(sv)) /* (a V-cycle has another shape) */
     return 0;
   const struct shard *s = &sv->sh[0];
   const unsigned kp = nrhs == 1 ? 1u : batch_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs);
@@ -98,15 +126,25 @@ unsigned long long lsb_hip_solver_multi_iteration_bytes(const lsb_hip_solver *sv
 }
 
 /* Iterations per host poll: pcg_run's rule (about 0.3 ms of device work at an assumed 4 TB/s) on this
- * iteration's bytes; even, so that a chunk leaves the parity where it found it. */
+ * iteration's bytes; even, so that a chunk leaves the parity where it found it.  An AMG solver: the same rule
+ * on an estimate of the SpMM, the sweeps and the cycle (its matrices once per launch that streams them, its
+ * vector passes per column), at least 2 where the diagonal preconditioners keep 8 -- an AMG iteration of a
+ * large grid is milliseconds and a solve a few dozen of them, so a speculative chunk of 8 would be a
+ * noticeable part of it. */
 static int mrhs_chunk(const lsb_hip_solver *sv, unsigned kp) {
   if (sv->o.check_every > 0)
     return (sv->o.check_every + 1) & ~1;
+  const struct shard *s = &sv->sh[0];
+  const int amg = mrhs_amg(sv);
   double us = (double)lsb_hip_solver_multi_iteration_bytes(sv, kp) / 4.0e6;
+  if (amg)
+    us = (double)(12ull * s->nnz + s->amg->cycle_mat_bytes + 8ull * kp * (11ull * s->n + s->amg->cycle_vec_rows)) /
+         4.0e6;
   if (us < 6.0)
     us = 6.0;
   int c = (int)(300.0 / us);
-  c = c < 8 ? 8 : c > 256 ? 256 : c;
+  const int lo = amg ? 2 : 8;
+  c = c < lo ? lo : c > 256 ? 256 : c;
   return c & ~1;
 }
 
@@ -121,6 +159,12 @@ static void mrhs_enqueue_iter(lsb_hip_solver *sv, struct mrhs_work *w, int parit
   const struct shard *s = &sv->sh[0];
   unsigned npq = 0, np2 = 0;
   spmm_shard(sv, w, w->p, w->q, NULL, &npq, w->st);
+  if (mrhs_amg(sv)) {
+    lsb_k_amg_mrhs_update_xr(w->kp, s->n, w->p, w->q, w->x, w->r, w->st, parity, w->parts_pq, npq, g_stream);
+    amg_vcycle_multi(s, w->kp, w->av, w->r, w->z, w->parts2, &np2, w->st);
+    lsb_k_amg_mrhs_update_p(w->kp, s->n, w->z, w->p, w->st, parity, w->parts2, np2, g_stream);
+    return;
+  }
   lsb_k_mrhs_update_xr(w->kp, s->n, w->p, w->q, DINV(s), w->x, w->r, w->st, parity, w->parts_pq, npq, w->parts2,
                        &np2, g_stream);
   lsb_k_mrhs_update_p(w->kp, s->n, w->r, DINV(s), w->p, w->st, parity, w->parts2, np2, g_stream);
@@ -222,7 +266,12 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
   unsigned np2 = 0, npq = 0, nverify = 0;
   const double t0 = wall_seconds();
   lsb_k_mrhs_pack(n, kp, nb, sv->d_perm, d_B, ldb, w->b, g_stream);
-  lsb_k_mrhs_init(kp, n, w->b, DINV(s), w->x, w->r, w->p, w->parts2, &np2, g_stream);
+  if (mrhs_amg(sv)) { /* x = 0, r = b ; z = M^-1 b ; p = z and (b.z, b.b) */
+    lsb_k_amg_mrhs_init(kp, n, w->b, w->x, w->r, g_stream);
+    amg_vcycle_multi(s, kp, w->av, w->r, w->z, NULL, NULL, NULL);
+    lsb_k_amg_mrhs_init_p(kp, n, w->b, w->z, w->p, w->parts2, &np2, g_stream);
+  } else
+    lsb_k_mrhs_init(kp, n, w->b, DINV(s), w->x, w->r, w->p, w->parts2, &np2, g_stream);
   lsb_k_mrhs_init_state(kp, w->st, w->parts2, np2, sv->o.tol, (int)sv->o.maxit, g_stream);
   hst[0].nspmm = 0;
   for (int round = 0;; round++) {
@@ -237,7 +286,12 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
     /* "converged" is reported only for the residual RECOMPUTED from x */
     const int more = round < LSB_MAX_CORRECTIONS;
     spmm_shard(sv, w, w->x, w->q, w->b, &npq, NULL);
-    lsb_k_mrhs_restart(kp, n, w->q, DINV(s), w->r, w->p, w->st, w->parts_pq, npq, more, w->parts2, &np2, g_stream);
+    if (mrhs_amg(sv)) { /* r = b - S x, z = M^-1 r, p = z and r.z, for the restarting columns */
+      lsb_k_amg_mrhs_restart_r(kp, n, w->q, w->r, w->st, w->parts_pq, npq, more, g_stream);
+      amg_vcycle_multi(s, kp, w->av, w->r, w->z, NULL, NULL, NULL);
+      lsb_k_amg_mrhs_restart_p(kp, n, w->r, w->z, w->p, w->st, w->parts_pq, npq, more, w->parts2, &np2, g_stream);
+    } else
+      lsb_k_mrhs_restart(kp, n, w->q, DINV(s), w->r, w->p, w->st, w->parts_pq, npq, more, w->parts2, &np2, g_stream);
     lsb_k_mrhs_restart_state(kp, w->st, w->parts_pq, npq, w->parts2, np2, more, g_stream);
     nverify++;
     LSB_CHK_HIP(hipMemcpyAsync(&hst[0], w->st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream));
@@ -321,5 +375,25 @@ int lsb_hip_solver_spmm_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_X
     lsb_k_mrhs_unpack(s->n, w->kp, nb, sv->d_perm, w->q, d_Y + (size_t)c0 * ldy, ldy, g_stream);
   }
   drain_stream(sv, "lsb_hip_solver_spmm_dev");
+  return 0;
+}
+
+/* Z_c = M^-1 R_c, one V-cycle per column of the block, through the same pack / unpack: the cycle of an
+ * iteration on its own, un-gated.  A solver that solve_multi does not serve under AMG answers 2. */
+int lsb_hip_solver_precond_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_R, size_t ldr, double *d_Z,
+                                     size_t ldz) {
+  if (!lsb_initialized)
+    return 1;
+  if (multi_args_bad(sv, nrhs, d_R, ldr, d_Z, ldz) || !mrhs_serves(sv) || !mrhs_amg(sv))
+    return 2;
+  const struct shard *s = &sv->sh[0];
+  for (unsigned c0 = 0; c0 < nrhs; c0 += LSB_MRHS_MAX) {
+    const unsigned nb = nrhs - c0 < LSB_MRHS_MAX ? nrhs - c0 : LSB_MRHS_MAX;
+    struct mrhs_work *w = mrhs_setup(sv, batch_width(nb));
+    lsb_k_mrhs_pack(s->n, w->kp, nb, sv->d_perm, d_R + (size_t)c0 * ldr, ldr, w->r, g_stream);
+    amg_vcycle_multi(s, w->kp, w->av, w->r, w->z, NULL, NULL, NULL);
+    lsb_k_mrhs_unpack(s->n, w->kp, nb, sv->d_perm, w->z, d_Z + (size_t)c0 * ldz, ldz, g_stream);
+  }
+  drain_stream(sv, "lsb_hip_solver_precond_multi_dev");
   return 0;
 }

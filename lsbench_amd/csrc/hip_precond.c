@@ -92,7 +92,13 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
     nnzall += L->A->offs[L->n];
     if (l == 0)
       nnz0 = L->A->offs[L->n];
+    if (L->P) { /* A goes 2 nu times (nu - 1 sweeps, the residual, nu sweeps), P and R once; 6 nu + 5 vector passes */
+      a->cycle_mat_bytes += 12ull * (2ull * a->nu * L->A->offs[L->n] + L->P->offs[L->P->nrows] + L->R->offs[L->R->nrows]);
+      a->cycle_vec_rows += (6ull * a->nu + 5ull) * L->n;
+    }
   }
+  a->cycle_mat_bytes += 8ull * h->nc * h->nc;
+  a->cycle_vec_rows += 2ull * h->nc;
   a->d_cinv = (double *)amg_keep(a, dev_upload(h->coarse_inv, (size_t)h->nc * h->nc * sizeof(double)));
   {
     const unsigned L = pow2_ceil(h->nc ? h->nc : 1);
@@ -159,6 +165,47 @@ static void amg_vcycle(const struct shard *s, const double *d_r, double *d_z, co
     lsb_k_amg_csr(LSB_AMG_ADDP, &v->P, a->lv[l + 1].out, NULL, NULL, cur, st, g_stream);
     for (unsigned k = 0; k < nu; k++) { /* 2 nu - 1 out-of-place sweeps in all: the last one writes `out` */
       lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
+      double *w = cur;
+      cur = oth, oth = w;
+    }
+  }
+}
+
+/* The same cycle on a block of kp interleaved columns (hip_mrhs_amg.hip): the same step order and ping-pong
+ * parity, so a column has the bits of amg_vcycle on it.  Always a launch per step: the one-launch tail is not
+ * built for blocks (it is bitwise the same as its launches).  records: where the fine level's last sweep -- the
+ * launch that writes Z -- leaves (r_c . z_c, r_c . r_c) of every column; a one-level hierarchy has no sweep and
+ * forms them in a launch of their own. */
+void amg_vcycle_multi(const struct shard *s, unsigned kp, const struct amg_mvec *lv, const double *d_R, double *d_Z,
+                      double *records, unsigned *nrecords, const struct lsb_mrhs_state *st) {
+  const struct amg_dev *a = s->amg;
+  const unsigned nu = a->nu, top = a->nlev - 1;
+  for (unsigned l = 0; l < top; l++) {
+    const struct lsb_amg_lvdev *v = &a->lv[l];
+    const double *b = l ? lv[l].b : d_R;
+    double *out = l ? lv[l].out : d_Z, *cur = lv[l].tmp, *oth = out;
+    lsb_k_amg_first_m(kp, v->n, b, v->minv, cur, st, g_stream);
+    for (unsigned k = 1; k < nu; k++) {
+      lsb_k_amg_csr_m(kp, LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, NULL, NULL, st, g_stream);
+      double *w = cur;
+      cur = oth, oth = w;
+    }
+    lsb_k_amg_csr_m(kp, LSB_AMG_RESID, &v->A, cur, b, v->minv, lv[l].r, NULL, NULL, st, g_stream);
+    lsb_k_amg_csr_m(kp, LSB_AMG_SPMV, &v->R, lv[l].r, NULL, NULL, lv[l + 1].b, NULL, NULL, st, g_stream);
+  }
+  lsb_k_amg_dense_m(kp, a->nc, a->clanes, a->d_cinv, top ? lv[top].b : d_R, top ? lv[top].out : d_Z, st, g_stream);
+  if (!top && records)
+    lsb_k_amg_dot2_m(kp, a->lv[0].n, d_R, d_Z, records, nrecords, st, g_stream);
+  for (unsigned l = top; l-- > 0;) {
+    const struct lsb_amg_lvdev *v = &a->lv[l];
+    const double *b = l ? lv[l].b : d_R;
+    double *out = l ? lv[l].out : d_Z;
+    double *cur = (nu - 1) % 2 ? out : lv[l].tmp, *oth = (nu - 1) % 2 ? lv[l].tmp : out;
+    lsb_k_amg_csr_m(kp, LSB_AMG_ADDP, &v->P, lv[l + 1].out, NULL, NULL, cur, NULL, NULL, st, g_stream);
+    for (unsigned k = 0; k < nu; k++) { /* the last one writes `out`; on level 0 it is the one with the records */
+      const int last = l == 0 && k + 1 == nu;
+      lsb_k_amg_csr_m(kp, LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, last ? records : NULL, last ? nrecords : NULL,
+                      st, g_stream);
       double *w = cur;
       cur = oth, oth = w;
     }

@@ -10,7 +10,7 @@
  *   hip_pcg.c        PCG iteration forms (one chosen per solver) and the host loop
  *   hip_gmres_drv.c  GMRES(m) driver
  *   hip_bicgstab_drv.c  BiCGSTAB driver
- *   hip_mrhs_drv.c   several right-hand sides: multi-RHS Jacobi-PCG on a CSR SpMM
+ *   hip_mrhs_drv.c   several right-hand sides: multi-RHS Jacobi- and AMG-PCG on a CSR SpMM
  * Nothing here is part of the C-ABI (include/lsbench_hip.h).
  */
 #ifndef HIP_SOLVER_H
@@ -195,6 +195,9 @@ struct shard {
     void **mem;                          /* every allocation of the hierarchy */
     unsigned nmem;
     double setup_s;
+    /* what one cycle streams, for the poll interval of a batch of right-hand sides: the bytes of its matrices
+     * and its vector passes in rows (summed over the levels) */
+    unsigned long long cycle_mat_bytes, cycle_vec_rows;
   } *amg;
   struct lsb_xfer *recv, *send;
   int nrecv, nsend;
@@ -260,6 +263,13 @@ struct lsb_hip_solver {
     double *b, *x, *r, *p, *q;   /* n kp doubles each */
     double *parts_pq, *parts2;   /* records of the SpMM (kp wide) and of the sweeps (2 kp wide) */
     struct lsb_mrhs_state *st;
+    /* an AMG solver's: z and the cycle's vectors of every level as blocks of this width (level 0: b and out
+     * are the r and z of the call) */
+    char *amg_mem;
+    double *z;
+    struct amg_mvec {
+      double *b, *out, *tmp, *r;
+    } *av;
     unsigned hint[LSB_MAX_CORRECTIONS + 1]; /* launches the previous batch's solve and restarts took */
     struct {
       hipGraphExec_t exec;
@@ -374,6 +384,11 @@ LSB_INTERNAL void precond_shard_blocks(struct shard *s, const int *offs, const i
                                        const double *vals, const struct lsb_hip_opts *o);
 LSB_INTERNAL void precond_setup(lsb_hip_solver *sv);
 LSB_INTERNAL void precond_apply(lsb_hip_solver *sv, int after_update);
+/* Z = one V-cycle on the block R of kp interleaved columns (lv: the levels' vectors at that width); records != NULL:
+ * the records (r_c . z_c, r_c . r_c) and their number; st: the gate of the launches, NULL: always run */
+LSB_INTERNAL void amg_vcycle_multi(const struct shard *s, unsigned kp, const struct amg_mvec *lv, const double *d_R,
+                                   double *d_Z, double *records, unsigned *nrecords,
+                                   const struct lsb_mrhs_state *st);
 LSB_INTERNAL void precond_free_shard(struct shard *s);
 /* hip_gmres_drv.c */
 LSB_INTERNAL int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,

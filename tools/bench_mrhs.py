@@ -13,10 +13,14 @@ One JSON line on stdout: per operator and nrhs
   us_per_iter_single / _multi          microseconds per iteration (of one solve / of the batch), [min, max]
   multi_iteration_bytes, frac_of_8TBs  what an iteration of the batch must move, over its time, over 8 TB/s
   gain                                 true only where (b)'s slowest repetition beats (a)'s fastest
+--precond amg: the same protocol on an AMG solver (single AMG solves against batches under AMG on that solver);
+multi_iteration_bytes is 0 there (an iteration around a V-cycle has another shape) and so is frac_of_8TBs.
+--verbose: the solver's own report at creation (the AMG hierarchy level by level) on stderr, and per width the
+device memory in use behind the first batch (device_mem_mb: everything the process holds, the solver included).
 Progress goes to stderr.
 
 Usage: python tools/bench_mrhs.py [--operators xn3b,tj7a,coef,lap2d] [--reps 5] [--n 3162] [--nrhs 2,4,8]
-                                  [--fixed-iters N]
+                                  [--fixed-iters N] [--precond jacobi|amg] [--verbose]
 """
 import argparse
 import gzip
@@ -50,6 +54,8 @@ def main():
     ap.add_argument("--nrhs", default="2,4,8")
     ap.add_argument("--fixed-iters", type=int, default=0,
                     help="cut every solve at this many iterations (tol = 0): for a kernel trace, not for rates")
+    ap.add_argument("--precond", choices=("jacobi", "amg"), default="jacobi")
+    ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
 
     import torch
@@ -74,10 +80,14 @@ def main():
         t0 = time.time()
         if a.fixed_iters:
             kw = dict(kw, tol=0.0)
+        if a.precond == "amg":
+            kw = dict(kw, precond=la.PRECOND_AMG)
+        if a.verbose:
+            kw = dict(kw, verbose=1)
         s = la.Solver(M, la.default_opts(maxit=a.fixed_iters or 100000, **kw))
         n = s.n_local
         rec = {"operator": label, "rows": n, "nnz": int(s.nnz_local), "tol": kw["tol"], "setup_s": round(time.time() - t0, 2),
-               "padded_rows": int(s.padded), "iteration_bytes_single": int(s.iteration_bytes), "reps": a.reps, "nrhs": {}}
+               "padded_rows": int(s.padded), "precond": a.precond, "iteration_bytes_single": int(s.iteration_bytes), "reps": a.reps, "nrhs": {}}
         for nrhs in [int(v) for v in a.nrhs.split(",")]:
             d_B = torch.arange(n, dtype=torch.float64, device="cuda:0")[None, :] * \
                 torch.arange(1, nrhs + 1, dtype=torch.float64, device="cuda:0")[:, None]
@@ -98,8 +108,12 @@ def main():
                 assert all(r.status == want for r in res), [r.status for r in res]
                 return time.perf_counter() - t, [int(r.iters) for r in res]
 
+            mem_mb = None
             for _ in range(2):  # warm-up of both shapes: the iteration hint, then the graph of that count
                 single(), multi()
+                if a.verbose and mem_mb is None:
+                    free, total = torch.cuda.mem_get_info()
+                    mem_mb = round((total - free) / 2.0 ** 20, 1)
             for k in range(a.reps):
                 t, its = single()
                 ts.append(t)
@@ -119,6 +133,8 @@ def main():
                 "multi_iteration_bytes": int(mb),
                 "frac_of_8TBs": [round(mb / (float(us_m.max()) * 1e-6) / 8e12, 4), round(mb / (float(us_m.min()) * 1e-6) / 8e12, 4)],
                 "gain": bool(tm.max() < ts.min())}
+            if mem_mb is not None:
+                rec["nrhs"][str(nrhs)]["device_mem_mb"] = mem_mb
             del d_B, d_X
         s.destroy()
         out.append(rec)
