@@ -118,10 +118,17 @@ enum { LSB_PRECOND_JACOBI = 0, LSB_PRECOND_NONE = 1,
                                        only solves (:59-62); an application is two SpMVs,
                                        no triangular solve, no reduction        */
        LSB_PRECOND_AMG = 6 };         /* smoothed-aggregation algebraic multigrid: one
-                                       symmetric V-cycle with l1-Jacobi smoothing, the
-                                       hierarchy built on the host at solver creation
-                                       (lsb_amg_setup), applied by hip_amg.hip; one
-                                       shard, classic PCG                      */
+                                       symmetric V-cycle with l1-Jacobi smoothing (or a
+                                       Chebyshev polynomial in D^-1 A of the same cost:
+                                       opts.amg_smoother), the hierarchy built on the
+                                       host at solver creation (lsb_amg_setup), applied
+                                       by hip_amg.hip; one shard, classic PCG  */
+enum { LSB_AMG_SMOOTH_L1JACOBI = 0,   /* nu sweeps x += diag(sum_j |a_ij|)^-1 (b - A x)  */
+       LSB_AMG_SMOOTH_CHEB = 1 };     /* the Chebyshev polynomial of degree nu in D^-1 A on
+                                       [rho / opts.amg_cheb_ratio, rho], rho the level's
+                                       Gershgorin bound (lsb_amg_gershgorin): a guaranteed
+                                       bound, so the cycle stays SPD; nu row launches as nu
+                                       sweeps, one more vector (the direction d) per level */
 enum { LSB_KRYLOV_PCG = 0,    /* preconditioned CG (symmetric operators)    */
        LSB_KRYLOV_GMRES = 1,  /* restarted GMRES(m), right-preconditioned,
                                  for LSB_OP_RAW / unsymmetric operators;
@@ -232,6 +239,11 @@ struct lsb_hip_opts {
                         in ONE launch of one workgroup (k_amg_tail); 0 = off, a launch
                         per step: measured faster at every size tried (one workgroup
                         is latency-bound; profiles/r05_amg.txt)                 [0] */
+  int amg_smoother;  /* LSB_AMG_SMOOTH_*; under CHEB amg_sweeps is the polynomial's
+                        degree and amg_tail_rows is ignored (the one-launch tail is
+                        not built for it)                          [L1JACOBI] */
+  double amg_cheb_ratio; /* hi / lo of the Chebyshev smoother's interval; values below
+                        1.5 are taken as 1.5                                  [10] */
 };
 enum { LSB_PREC_FP64 = 0, LSB_PREC_MIXED = 1 };
 
@@ -422,6 +434,13 @@ struct lsb_amg_hier {
 struct lsb_amg_hier *lsb_amg_setup(const struct csr *S, double theta, unsigned coarse, unsigned max_levels);
 /* the aggregates of one level (malloc'ed, n entries; -1 = not aggregated), *naggr of them */
 int *lsb_amg_aggregate(const struct csr *A, double theta, unsigned *naggr);
+/* max_i sum_j |a_ij| / a_ii >= lambda_max(D^-1 A): the bound behind the prolongator's omega and the upper
+ * end of the Chebyshev smoother's interval.  Deterministic (no eigen-iteration). */
+double lsb_amg_gershgorin(const struct csr *A);
+/* Coefficients of the Chebyshev smoother of degree deg on [hi / ratio, hi] (ratio < 1.5 is taken as 1.5);
+ * c1, c2: deg doubles each.  Step k (0 .. deg - 1) on (x, d), s = A x:
+ *   d_i <- fma(c2[k] / a_ii, b_i - s_i, c1[k] d_i),  x_i <- x_i + d_i ;  c1[0] = 0 and step 0 does not read d. */
+void lsb_amg_cheb_coeffs(double hi, double ratio, unsigned deg, double *c1, double *c2);
 void lsb_amg_free(struct lsb_amg_hier *h);
 /* Sliced-ELL copy of a CSR for LSB_SPMV_SELL: rows in slices of LSB_SELL_ROWS,
  * every slice padded to its longest row and stored column-major (entry j of
@@ -660,6 +679,10 @@ int lsb_hip_solver_precond_dev(lsb_hip_solver *s, const double *d_r, double *d_z
 /* LSB_PRECOND_AMG: levels of the hierarchy, the coarsest included, and how many of them (with
  * the coarse solve) run in the one-launch tail; 2 for another preconditioner. */
 int lsb_hip_solver_amg_info(lsb_hip_solver *s, unsigned *levels, unsigned *tail_levels);
+/* LSB_PRECOND_AMG with LSB_AMG_SMOOTH_CHEB: the interval [lo, hi] of D^-1 A the smoother of `level` was built
+ * on (hi = lsb_amg_gershgorin of the level, lo = hi / amg_cheb_ratio); 2 for another preconditioner or
+ * smoother and for a level that is not smoothed (the coarsest, or beyond). */
+int lsb_hip_solver_amg_cheb_interval(lsb_hip_solver *s, unsigned level, double *lo, double *hi);
 /* LSB_PRECOND_CHEBYSHEV: the interval [lmin, lmax] of D^-1 S the polynomial was built on at creation
  * (lmax = 1.1 x the power iteration's estimate, lmin = lmax / max(30, 16 degree^2), the degree
  * clamped to 1 .. 32); 2 for another preconditioner. */

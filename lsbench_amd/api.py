@@ -346,6 +346,16 @@ class Solver:
         L.check(L.load().lsb_hip_solver_amg_info(self._h, C.byref(lv), C.byref(tl)), "amg_info")
         return lv.value, tl.value
 
+    def amg_cheb_interval(self, level):
+        """(lo, hi) of D^-1 A the Chebyshev smoother of an AMG level was built on; None where the level is not
+        smoothed by one (the coarsest level, an l1-Jacobi solver, another preconditioner)."""
+        lo, hi = C.c_double(), C.c_double()
+        rc = L.load().lsb_hip_solver_amg_cheb_interval(self._h, level, C.byref(lo), C.byref(hi))
+        if rc == 2:
+            return None
+        L.check(rc, "amg_cheb_interval")
+        return lo.value, hi.value
+
     @property
     def cheb_interval(self):
         """(lmin, lmax) of D^-1 S the Chebyshev preconditioner's polynomial was built on."""

@@ -18,12 +18,22 @@
 //                     walks a level's rows in passes of dependent L2 loads), so it is off by
 //                     default (opts.amg_tail_rows = 0; profiles/r05_amg.txt).
 //
+// k_amg_cheb<L>      opts.amg_smoother = LSB_AMG_SMOOTH_CHEB: one step of the Chebyshev polynomial of degree nu
+//                     in D^-1 A in the place of a sweep -- the same row product, then
+//                         d_i <- fma(c2 / a_ii, b_i - s_i, c1 d_i),  y_i = x_i + d_i
+//                     (d in place: row i reads only d_i; c1 == 0 on step 0, which does not read d).  The
+//                     coefficients come from the host in fp64 (lsb_amg_cheb_coeffs) on the interval
+//                     [rho / ratio, rho], rho the level's Gershgorin bound.  k_amg_cheb_first is step 0 from
+//                     the zero guess: d = (c2 / a_ii) b, x = d, no matrix.  The cycle has the launches and
+//                     the ping-pong parity of the l1-Jacobi one; the one-launch tail is not built for it.
+//
 // No atomics: every output row is one lane group's fixed-order reduction (amg_row), the same
 // function in both kernels, so z is bitwise repeatable and the tail on and off give the same bits.
 // Every kernel is a no-op once the solve's state has left RUNNING.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hip_amg_cheb.h"
 #include "lsb_impl.h"
 
 #define AMG_WG 256
@@ -95,6 +105,40 @@ __global__ __launch_bounds__(AMG_WG) void k_amg_first(unsigned n, const double *
     return;
   for (unsigned i = blockIdx.x * AMG_WG + threadIdx.x; i < n; i += gridDim.x * AMG_WG)
     x[i] = minv[i] * b[i];
+}
+
+// one Chebyshev step: y = xin + d', d' = c1 d + c2 D^-1 (b - A xin), d updated in place
+template <int L>
+__global__ __launch_bounds__(AMG_WG) void k_amg_cheb(unsigned n, const int *__restrict__ offs,
+                                                     const int *__restrict__ cols, const double *__restrict__ vals,
+                                                     const double *xin, const double *b, const double *dinv, double c1,
+                                                     double c2, double *d, double *y, const struct lsb_pcg_state *st) {
+  if (st && st->status)
+    return;
+  const unsigned long long stride = (unsigned long long)gridDim.x * AMG_WG; // a multiple of L: groups stay whole
+  for (unsigned long long g = (unsigned long long)blockIdx.x * AMG_WG + threadIdx.x; g / L < n; g += stride) {
+    const unsigned i = (unsigned)(g / L), lane = (unsigned)(g % L);
+    const double s = amg_row<L>(offs, cols, vals, xin, i, lane);
+    if (lane == 0) {
+      const double dn = amg_cheb_dir(c1, c2, dinv[i], b[i], s, c1 != 0.0 ? d[i] : 0.0);
+      d[i] = dn;
+      y[i] = xin[i] + dn;
+    }
+  }
+}
+
+// step 0 from the zero guess: d = (c2 D^-1) b, x = d
+__global__ __launch_bounds__(AMG_WG) void k_amg_cheb_first(unsigned n, const double *__restrict__ b,
+                                                           const double *__restrict__ dinv, double c2,
+                                                           double *__restrict__ d, double *__restrict__ x,
+                                                           const struct lsb_pcg_state *st) {
+  if (st && st->status)
+    return;
+  for (unsigned i = blockIdx.x * AMG_WG + threadIdx.x; i < n; i += gridDim.x * AMG_WG) {
+    const double v = amg_cheb_dir(0.0, c2, dinv[i], b[i], 0.0, 0.0);
+    d[i] = v;
+    x[i] = v;
+  }
 }
 
 template <int L>
@@ -237,6 +281,30 @@ void lsb_k_amg_csr(int mode, const struct lsb_amg_mat *m, const double *xin, con
     errx(EXIT_FAILURE, "lsb_k_amg_csr: no mode %d", mode);
   }
 #undef AMG_MODE
+#undef AMG_L
+}
+
+void lsb_k_amg_cheb_first(unsigned n, const double *b, const double *dinv, double c2, double *d, double *x,
+                          const struct lsb_pcg_state *st, void *stream) {
+  if (n)
+    k_amg_cheb_first<<<amg_grid(n), AMG_WG, 0, (hipStream_t)stream>>>(n, b, dinv, c2, d, x, st);
+}
+
+void lsb_k_amg_cheb(const struct lsb_amg_mat *m, const double *xin, const double *b, const double *dinv, double c1,
+                    double c2, double *d, double *y, const struct lsb_pcg_state *st, void *stream) {
+  if (!m->rows)
+    return;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned g = amg_grid((unsigned long long)m->rows * m->lanes);
+#define AMG_L(LL)                                                                                            \
+  case LL:                                                                                                   \
+    k_amg_cheb<LL><<<g, AMG_WG, 0, s>>>(m->rows, m->offs, m->cols, m->vals, xin, b, dinv, c1, c2, d, y, st); \
+    break;
+  switch (m->lanes) {
+    AMG_L(2) AMG_L(4) AMG_L(8) AMG_L(16) AMG_L(32)
+  default:
+    k_amg_cheb<64><<<g, AMG_WG, 0, s>>>(m->rows, m->offs, m->cols, m->vals, xin, b, dinv, c1, c2, d, y, st);
+  }
 #undef AMG_L
 }
 

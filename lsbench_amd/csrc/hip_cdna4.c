@@ -97,6 +97,8 @@ void lsb_hip_opts_default(struct lsb_hip_opts *o) {
   o->amg_coarse = 256;
   o->amg_max_levels = 20;
   o->amg_tail_rows = 0; /* measured: one workgroup is latency-bound, a launch per step is faster (profiles/r05_amg.txt) */
+  o->amg_smoother = LSB_AMG_SMOOTH_L1JACOBI;
+  o->amg_cheb_ratio = 10.0;
 }
 
 /* ONE typed table for everything a caller may set by name: the command line of a host
@@ -113,6 +115,7 @@ static const struct optchoice CH_PRECOND[] = {{"jacobi", LSB_PRECOND_JACOBI},   
                                               {"l1", LSB_PRECOND_L1JACOBI},     {"cheb", LSB_PRECOND_CHEBYSHEV},
                                               {"bj", LSB_PRECOND_BLOCKJACOBI},  {"fsai", LSB_PRECOND_FSAI},
                                               {"amg", LSB_PRECOND_AMG},         {NULL, 0}};
+static const struct optchoice CH_AMG_SMOOTHER[] = {{"l1", LSB_AMG_SMOOTH_L1JACOBI}, {"cheb", LSB_AMG_SMOOTH_CHEB}, {NULL, 0}};
 static const struct optchoice CH_COMM[] = {{"auto", LSB_COMM_AUTO}, {"rccl", LSB_COMM_RCCL}, {"p2p", LSB_COMM_P2P}, {NULL, 0}};
 static const struct optchoice CH_KRYLOV[] = {{"cg", LSB_KRYLOV_PCG},     {"pcg", LSB_KRYLOV_PCG}, /* (alias) */
                                              {"cg1", LSB_KRYLOV_PCG1},   {"pcg1", LSB_KRYLOV_PCG1},
@@ -157,6 +160,8 @@ static const struct optdef {
     OPT("amg-coarse", OT_INT, amg_coarse, NULL),
     OPT("amg-max-levels", OT_INT, amg_max_levels, NULL),
     OPT("amg-tail-rows", OT_INT, amg_tail_rows, NULL),
+    OPT("amg-smoother", OT_ENUM, amg_smoother, CH_AMG_SMOOTHER),
+    OPT("amg-cheb-ratio", OT_DBL, amg_cheb_ratio, NULL),
 };
 #undef OPT
 #define NOPTS (sizeof OPTS / sizeof OPTS[0])

@@ -471,20 +471,6 @@ __global__ __launch_bounds__(WG) void k_amg_mrhs_restart_p(unsigned n, const dou
 // --------------------------------------------------------------------------
 // Launchers (C ABI).  kp: 2, 4 or 8.
 // --------------------------------------------------------------------------
-static unsigned amg_lanes(unsigned L) { return L == 2 || L == 4 || L == 8 || L == 16 || L == 32 ? L : 64; }
-
-#define L_DISPATCH(lanes, CALL)                                                \
-  do {                                                                         \
-    switch (amg_lanes(lanes)) {                                                \
-    case 2: { constexpr int L = 2; CALL; } break;                              \
-    case 4: { constexpr int L = 4; CALL; } break;                              \
-    case 8: { constexpr int L = 8; CALL; } break;                              \
-    case 16: { constexpr int L = 16; CALL; } break;                            \
-    case 32: { constexpr int L = 32; CALL; } break;                            \
-    default: { constexpr int L = 64; CALL; } break;                            \
-    }                                                                          \
-  } while (0)
-
 template <int KP, int MODE, bool REC>
 static void amg_csr_launch(const struct lsb_amg_mat *m, unsigned g, const double *xin, const double *b,
                            const double *minv, double *y, double *records, const struct lsb_mrhs_state *st,

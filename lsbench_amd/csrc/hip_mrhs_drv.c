@@ -77,6 +77,9 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
     size_t total = 3 * blk, off = 3 * blk;
     for (unsigned l = 1; l < a->nlev; l++)
       total += (4 * (size_t)a->lv[l].n * kp * sizeof(double) + 255) & ~(size_t)255;
+    const size_t doff = total; /* the Chebyshev smoother's direction blocks, behind everything an l1 solver has */
+    for (unsigned l = 0; a->cheb && l + 1 < a->nlev; l++)
+      total += ((size_t)a->lv[l].n * kp * sizeof(double) + 255) & ~(size_t)255;
     w->amg_mem = (char *)lsb_hip_malloc(total);
     LSB_CHK_HIP(hipMemsetAsync(w->amg_mem, 0, total, g_stream));
     w->av = lsb_calloc(struct amg_mvec, a->nlev);
@@ -87,6 +90,11 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
       double *buf = (double *)(w->amg_mem + off);
       w->av[l].b = buf, w->av[l].out = buf + nl, w->av[l].tmp = buf + 2 * nl, w->av[l].r = buf + 3 * nl;
       off += (4 * nl * sizeof(double) + 255) & ~(size_t)255;
+    }
+    off = doff;
+    for (unsigned l = 0; a->cheb && l + 1 < a->nlev; l++) {
+      w->av[l].d = (double *)(w->amg_mem + off);
+      off += ((size_t)a->lv[l].n * kp * sizeof(double) + 255) & ~(size_t)255;
     }
   }
   w->kp = kp;

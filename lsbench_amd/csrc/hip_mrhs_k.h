@@ -1,4 +1,4 @@
-// What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_amg.hip) share: the 16-byte pair
+// What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_amg.hip, hip_amg_cheb.hip) share: the 16-byte pair
 // of the interleaved blocks, the fixed-order reductions of their per-column records, the verify round's
 // decision and the launchers' dispatch on the batch width.  Included by those files only, after
 // hip_kcommon.h.
@@ -85,6 +85,22 @@ static unsigned sweep_grid(unsigned n, unsigned kp) { return lsb_k_blas1_grid(n 
     case 1: { constexpr int KP = 2; CALL; } break;                             \
     case 2: { constexpr int KP = 4; CALL; } break;                             \
     default: { constexpr int KP = 8; CALL; } break;                            \
+    }                                                                          \
+  } while (0)
+
+
+// lanes per row of a matrix of the AMG hierarchy as the kernels are instantiated, and the dispatch on them
+static inline unsigned amg_lanes(unsigned L) { return L == 2 || L == 4 || L == 8 || L == 16 || L == 32 ? L : 64; }
+
+#define L_DISPATCH(lanes, CALL)                                                \
+  do {                                                                         \
+    switch (amg_lanes(lanes)) {                                                \
+    case 2: { constexpr int L = 2; CALL; } break;                              \
+    case 4: { constexpr int L = 4; CALL; } break;                              \
+    case 8: { constexpr int L = 8; CALL; } break;                              \
+    case 16: { constexpr int L = 16; CALL; } break;                            \
+    case 32: { constexpr int L = 32; CALL; } break;                            \
+    default: { constexpr int L = 64; CALL; } break;                            \
     }                                                                          \
   } while (0)
 

@@ -56,10 +56,16 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
   struct amg_dev *a = lsb_calloc(struct amg_dev, 1);
   a->nlev = h->nlev, a->nc = h->nc;
   a->nu = o->amg_sweeps < 1 ? 1u : (o->amg_sweeps > 16 ? 16u : (unsigned)o->amg_sweeps);
-  a->mem = lsb_calloc(void *, 12 * (size_t)h->nlev + 4);
+  a->mem = lsb_calloc(void *, 13 * (size_t)h->nlev + 4);
   a->lv = lsb_calloc(struct lsb_amg_lvdev, h->nlev);
+  const int cheb = o->amg_smoother == LSB_AMG_SMOOTH_CHEB;
+  const double ratio = o->amg_cheb_ratio >= 1.5 ? o->amg_cheb_ratio : 1.5;
+  if (o->amg_smoother != LSB_AMG_SMOOTH_L1JACOBI && !cheb)
+    errx(EXIT_FAILURE, "hip_cdna4: no AMG smoother %d (--amg-smoother l1 or cheb)", o->amg_smoother);
+  if (cheb)
+    a->cheb = lsb_calloc(struct amg_cheb, h->nlev);
   a->tail = h->nlev;
-  for (unsigned l = 0; l < h->nlev; l++)
+  for (unsigned l = 0; l < h->nlev && !cheb; l++) /* (the one-launch tail is not built for the Chebyshev smoother) */
     if (o->amg_tail_rows > 0 && h->lv[l].n <= (unsigned)o->amg_tail_rows) {
       a->tail = l;
       break;
@@ -78,8 +84,15 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
     for (unsigned i = 0; i < L->n; i++) {
       double sum = 0.0;
       for (unsigned e = L->A->offs[i]; e < L->A->offs[i + 1]; e++)
-        sum += fabs(L->A->vals[e]);
+        sum += cheb ? (L->A->cols[e] == i ? L->A->vals[e] : 0.0) : fabs(L->A->vals[e]);
       minv[i] = 1.0 / sum; /* > 0: lsb_amg_setup refused a diagonal <= 0 */
+    }
+    if (cheb && L->P) { /* the polynomial of degree nu on [rho / ratio, rho], rho the level's Gershgorin bound */
+      struct amg_cheb *c = &a->cheb[l];
+      c->hi = lsb_amg_gershgorin(L->A), c->lo = c->hi / ratio;
+      lsb_amg_cheb_coeffs(c->hi, ratio, a->nu, c->c1, c->c2);
+      c->d = (double *)amg_keep(a, lsb_hip_malloc((size_t)L->n * sizeof(double)));
+      LSB_CHK_HIP(hipMemsetAsync(c->d, 0, (size_t)L->n * sizeof(double), g_stream));
     }
     v->minv = (const double *)amg_keep(a, dev_upload(minv, (size_t)(L->n ? L->n : 1) * sizeof(double)));
     LSB_CHK_HIP(hipStreamSynchronize(g_stream));
@@ -95,6 +108,8 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
     if (L->P) { /* A goes 2 nu times (nu - 1 sweeps, the residual, nu sweeps), P and R once; 6 nu + 5 vector passes */
       a->cycle_mat_bytes += 12ull * (2ull * a->nu * L->A->offs[L->n] + L->P->offs[L->P->nrows] + L->R->offs[L->R->nrows]);
       a->cycle_vec_rows += (6ull * a->nu + 5ull) * L->n;
+      if (cheb) /* d: written by both step 0s, read and written by the 2 (nu - 1) other steps */
+        a->cycle_vec_rows += (4ull * a->nu - 2ull) * L->n;
     }
   }
   a->cycle_mat_bytes += 8ull * h->nc * h->nc;
@@ -111,14 +126,22 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
       const struct lsb_amg_level *L = &h->lv[l];
       fprintf(stderr, "hip_cdna4: AMG level %u: %u rows, %u entries, %u lanes (A)", l, L->n, L->A->offs[L->n],
               a->lv[l].A.lanes);
-      if (L->P)
+      if (L->P && cheb)
+        fprintf(stderr, ", %u / %u lanes (P / R), Chebyshev on [%.4g, %.4g]\n", a->lv[l].P.lanes, a->lv[l].R.lanes,
+                a->cheb[l].lo, a->cheb[l].hi);
+      else if (L->P)
         fprintf(stderr, ", %u / %u lanes (P / R)\n", a->lv[l].P.lanes, a->lv[l].R.lanes);
       else
         fprintf(stderr, ", dense coarse inverse, %u lanes\n", a->clanes);
     }
-    fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u of %u levels in the one-launch tail, %u sweep%s, "
-                    "set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev - a->tail, h->nlev, a->nu,
-            a->nu > 1 ? "s" : "", a->setup_s);
+    if (cheb)
+      fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u levels, Chebyshev smoother of degree %u "
+                      "(interval ratio %g), set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev, a->nu,
+              ratio, a->setup_s);
+    else
+      fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u of %u levels in the one-launch tail, %u l1-Jacobi "
+                      "sweep%s, set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev - a->tail, h->nlev,
+              a->nu, a->nu > 1 ? "s" : "", a->setup_s);
   }
   lsb_amg_free(h);
   s->amg = a;
@@ -134,7 +157,9 @@ static void amg_finish_setup(struct shard *s) {
   LSB_CHK_HIP(hipStreamSynchronize(g_stream));
 }
 
-/* z = one V-cycle on r; the launches of levels above the tail, the tail (or the coarse solve) */
+/* z = one V-cycle on r; the launches of levels above the tail, the tail (or the coarse solve).  Under the Chebyshev
+ * smoother (a->cheb) a level's first step and its sweeps are the polynomial's steps: the same launch count and
+ * ping-pong parity, d updated in place, and no tail. */
 static void amg_vcycle(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st) {
   const struct amg_dev *a = s->amg;
   const unsigned nu = a->nu, top = a->tail < a->nlev ? a->tail : a->nlev - 1;
@@ -142,9 +167,16 @@ static void amg_vcycle(const struct shard *s, const double *d_r, double *d_z, co
     const struct lsb_amg_lvdev *v = &a->lv[l];
     const double *b = l ? v->b : d_r;
     double *out = l ? v->out : d_z, *cur = v->tmp, *oth = out;
-    lsb_k_amg_first(v->n, b, v->minv, cur, st, g_stream);
+    const struct amg_cheb *c = a->cheb ? &a->cheb[l] : NULL;
+    if (c)
+      lsb_k_amg_cheb_first(v->n, b, v->minv, c->c2[0], c->d, cur, st, g_stream);
+    else
+      lsb_k_amg_first(v->n, b, v->minv, cur, st, g_stream);
     for (unsigned k = 1; k < nu; k++) {
-      lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
+      if (c)
+        lsb_k_amg_cheb(&v->A, cur, b, v->minv, c->c1[k], c->c2[k], c->d, oth, st, g_stream);
+      else
+        lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
       double *w = cur;
       cur = oth, oth = w;
     }
@@ -162,9 +194,13 @@ static void amg_vcycle(const struct shard *s, const double *d_r, double *d_z, co
     const double *b = l ? v->b : d_r;
     double *out = l ? v->out : d_z;
     double *cur = (nu - 1) % 2 ? out : v->tmp, *oth = (nu - 1) % 2 ? v->tmp : out;
+    const struct amg_cheb *c = a->cheb ? &a->cheb[l] : NULL;
     lsb_k_amg_csr(LSB_AMG_ADDP, &v->P, a->lv[l + 1].out, NULL, NULL, cur, st, g_stream);
     for (unsigned k = 0; k < nu; k++) { /* 2 nu - 1 out-of-place sweeps in all: the last one writes `out` */
-      lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
+      if (c)
+        lsb_k_amg_cheb(&v->A, cur, b, v->minv, c->c1[k], c->c2[k], c->d, oth, st, g_stream);
+      else
+        lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
       double *w = cur;
       cur = oth, oth = w;
     }
@@ -184,9 +220,16 @@ void amg_vcycle_multi(const struct shard *s, unsigned kp, const struct amg_mvec 
     const struct lsb_amg_lvdev *v = &a->lv[l];
     const double *b = l ? lv[l].b : d_R;
     double *out = l ? lv[l].out : d_Z, *cur = lv[l].tmp, *oth = out;
-    lsb_k_amg_first_m(kp, v->n, b, v->minv, cur, st, g_stream);
+    const struct amg_cheb *c = a->cheb ? &a->cheb[l] : NULL;
+    if (c)
+      lsb_k_amg_cheb_first_m(kp, v->n, b, v->minv, c->c2[0], lv[l].d, cur, st, g_stream);
+    else
+      lsb_k_amg_first_m(kp, v->n, b, v->minv, cur, st, g_stream);
     for (unsigned k = 1; k < nu; k++) {
-      lsb_k_amg_csr_m(kp, LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, NULL, NULL, st, g_stream);
+      if (c)
+        lsb_k_amg_cheb_m(kp, &v->A, cur, b, v->minv, c->c1[k], c->c2[k], lv[l].d, oth, NULL, NULL, st, g_stream);
+      else
+        lsb_k_amg_csr_m(kp, LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, NULL, NULL, st, g_stream);
       double *w = cur;
       cur = oth, oth = w;
     }
@@ -204,8 +247,12 @@ void amg_vcycle_multi(const struct shard *s, unsigned kp, const struct amg_mvec 
     lsb_k_amg_csr_m(kp, LSB_AMG_ADDP, &v->P, lv[l + 1].out, NULL, NULL, cur, NULL, NULL, st, g_stream);
     for (unsigned k = 0; k < nu; k++) { /* the last one writes `out`; on level 0 it is the one with the records */
       const int last = l == 0 && k + 1 == nu;
-      lsb_k_amg_csr_m(kp, LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, last ? records : NULL, last ? nrecords : NULL,
-                      st, g_stream);
+      if (a->cheb)
+        lsb_k_amg_cheb_m(kp, &v->A, cur, b, v->minv, a->cheb[l].c1[k], a->cheb[l].c2[k], lv[l].d, oth,
+                         last ? records : NULL, last ? nrecords : NULL, st, g_stream);
+      else
+        lsb_k_amg_csr_m(kp, LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, last ? records : NULL,
+                        last ? nrecords : NULL, st, g_stream);
       double *w = cur;
       cur = oth, oth = w;
     }
@@ -219,7 +266,7 @@ static void amg_free(struct shard *s) {
   for (unsigned k = 0; k < a->nmem; k++)
     lsb_hip_free(a->mem[k]);
   shard_vec_free(s, a->lv[0].tmp), shard_vec_free(s, a->lv[0].r);
-  free(a->mem), free(a->lv), free(a);
+  free(a->mem), free(a->lv), free(a->cheb), free(a);
   s->amg = NULL;
 }
 
@@ -645,6 +692,20 @@ int lsb_hip_solver_amg_info(lsb_hip_solver *sv, unsigned *levels, unsigned *tail
     *levels = a->nlev;
   if (tail_levels)
     *tail_levels = a->nlev - a->tail;
+  return 0;
+}
+
+int lsb_hip_solver_amg_cheb_interval(lsb_hip_solver *sv, unsigned level, double *lo, double *hi) {
+  if (!lsb_initialized)
+    return 1;
+  if (!sv || sv->o.precond != LSB_PRECOND_AMG || !sv->sh[0].amg || !sv->sh[0].amg->cheb ||
+      level + 1 >= sv->sh[0].amg->nlev)
+    return 2;
+  const struct amg_cheb *c = &sv->sh[0].amg->cheb[level];
+  if (lo)
+    *lo = c->lo;
+  if (hi)
+    *hi = c->hi;
   return 0;
 }
 

@@ -198,6 +198,12 @@ struct shard {
     /* what one cycle streams, for the poll interval of a batch of right-hand sides: the bytes of its matrices
      * and its vector passes in rows (summed over the levels) */
     unsigned long long cycle_mat_bytes, cycle_vec_rows;
+    /* opts.amg_smoother = LSB_AMG_SMOOTH_CHEB (NULL under l1-Jacobi): per smoothed level the interval of
+     * D^-1 A, the coefficients of its nu steps (lsb_amg_cheb_coeffs) and the direction vector d */
+    struct amg_cheb {
+      double lo, hi, c1[16], c2[16];
+      double *d;
+    } *cheb;
   } *amg;
   struct lsb_xfer *recv, *send;
   int nrecv, nsend;
@@ -269,6 +275,7 @@ struct lsb_hip_solver {
     double *z;
     struct amg_mvec {
       double *b, *out, *tmp, *r;
+      double *d; /* the Chebyshev smoother's direction block (NULL under l1-Jacobi) */
     } *av;
     unsigned hint[LSB_MAX_CORRECTIONS + 1]; /* launches the previous batch's solve and restarts took */
     struct {

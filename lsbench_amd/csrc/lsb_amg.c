@@ -248,6 +248,49 @@ static struct csr *amg_transpose(const struct csr *P, unsigned ncols) {
   return R;
 }
 
+/* rho = max_i sum_j |a_ij| / a_ii >= lambda_max(D^-1 A) (Gershgorin): each row's |a_ij| summed in storage
+ * order, the diagonal as amg_diag sums it.  No eigen-iteration, so the same bits for any thread count: the
+ * prolongator's omega and the upper end of the Chebyshev smoother's interval (an estimate from a power
+ * iteration fell below lambda_max on coarse Galerkin levels, and PCG then did not converge; DESIGN.md
+ * section 4). */
+double lsb_amg_gershgorin(const struct csr *A) {
+  double rho = 0.0;
+  for (unsigned i = 0; i < A->nrows; i++) {
+    double s = 0.0, d = 0.0;
+    for (unsigned e = A->offs[i]; e < A->offs[i + 1]; e++) {
+      s += fabs(A->vals[e]);
+      if (A->cols[e] - A->base == i)
+        d += A->vals[e];
+    }
+    if (!(d > 0.0))
+      errx(EXIT_FAILURE, "hip_cdna4: --precond amg needs a symmetric positive definite operator (row %u of "
+                         "a %u-row level has diagonal %g)", i, A->nrows, d);
+    if (s / d > rho)
+      rho = s / d;
+  }
+  return rho;
+}
+
+/* The Chebyshev smoother's coefficients on [hi / ratio, hi] (ratio >= 1.5), degree deg: step k is
+ *   d <- c1[k] d + c2[k] D^-1 (b - A x),  x <- x + d     (c1[0] = 0: step 0 does not read d)
+ * with theta = (hi + lo) / 2, delta = (hi - lo) / 2, sigma = theta / delta, rho_0 = 1 / sigma,
+ * rho_k = 1 / (2 sigma - rho_{k-1}), c1[k] = rho_k rho_{k-1}, c2[k] = 2 rho_k / delta, c2[0] = 1 / theta. */
+void lsb_amg_cheb_coeffs(double hi, double ratio, unsigned deg, double *c1, double *c2) {
+  if (!(ratio >= 1.5))
+    ratio = 1.5;
+  const double lo = hi / ratio, theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+  double rho = 1.0 / sigma;
+  for (unsigned k = 0; k < deg; k++) {
+    if (k == 0) {
+      c1[0] = 0.0, c2[0] = 1.0 / theta;
+      continue;
+    }
+    const double rho_new = 1.0 / (2.0 * sigma - rho);
+    c1[k] = rho_new * rho, c2[k] = 2.0 * rho_new / delta;
+    rho = rho_new;
+  }
+}
+
 /* P = (I - omega D^-1 A) P_tent; row i: for every entry (k, a_ik) of row i in ascending k with
  * agg[k] >= 0, column agg[k] gathers a_ik (summed in that order); then
  *   P_ij = [agg[i] == j] s_j - (omega / a_ii) * sum * s_j */
@@ -259,14 +302,7 @@ static struct csr *amg_prolongator(const struct csr *A, const double *d, const i
       scale[agg[i]] += 1.0;
   for (unsigned j = 0; j < na; j++)
     scale[j] = 1.0 / sqrt(scale[j]);
-  double rho = 0.0;
-  for (unsigned i = 0; i < n; i++) {
-    double s = 0.0;
-    for (unsigned e = A->offs[i]; e < A->offs[i + 1]; e++)
-      s += fabs(A->vals[e]);
-    if (s / d[i] > rho)
-      rho = s / d[i];
-  }
+  const double rho = lsb_amg_gershgorin(A);
   const double omega = 4.0 / (3.0 * rho);
   /* the pattern of row i: the aggregates of its columns (and of i itself) */
   unsigned *len = lsb_calloc(unsigned, (size_t)n + 1);

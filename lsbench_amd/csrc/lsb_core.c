@@ -89,7 +89,10 @@ static void usage(const char *prog) {
   printf("                       tril(S^k), k = --fsai-power (default 3), set up once on the device;\n");
   printf("                       amg = smoothed-aggregation AMG, one V-cycle with l1-Jacobi sweeps\n");
   printf("                       (--amg-theta T, --amg-sweeps NU, --amg-coarse ROWS, --amg-max-levels L,\n");
-  printf("                       --amg-tail-rows ROWS: levels run in one launch), one shard, cg only\n");
+  printf("                       --amg-tail-rows ROWS: levels run in one launch), one shard, cg only;\n");
+  printf("                       --amg-smoother <l1|cheb>: cheb = a Chebyshev polynomial of degree NU in\n");
+  printf("                       D^-1 A in the place of the NU sweeps, on [rho / X, rho], rho the level's\n");
+  printf("                       Gershgorin bound, X = --amg-cheb-ratio (default 10)\n");
   printf("  --ngpus <N>          (hip) row-partition the operator over N GPUs of this node\n");
   printf("                       (0 = all visible), driven from this one process\n");
   printf("  --reorder            (hip) solve the RCM-permuted operator (any --ordering\n");
@@ -113,7 +116,8 @@ struct lsbench *lsbench_init(int argc, char *argv[]) {
       {"verify", required_argument, 0, 80},
       {"amg-theta", required_argument, 0, 80}, {"amg-sweeps", required_argument, 0, 80},
       {"amg-coarse", required_argument, 0, 80}, {"amg-max-levels", required_argument, 0, 80},
-      {"amg-tail-rows", required_argument, 0, 80},
+      {"amg-tail-rows", required_argument, 0, 80}, {"amg-smoother", required_argument, 0, 80},
+      {"amg-cheb-ratio", required_argument, 0, 80},
       {0, 0, 0, 0}};
 
   /* zero-filled => solver 0 (CUSOLVER), ordering 0 (RCM), FP64: the

@@ -400,7 +400,7 @@ struct lsb_amg_mat {
 struct lsb_amg_lvdev {
   unsigned n, pad_;
   struct lsb_amg_mat A, P, R; /* P: n rows, R: the next level's n rows (none on the coarsest) */
-  const double *minv;         /* 1 / sum_j |a_ij|: the l1-Jacobi smoother */
+  const double *minv;         /* 1 / sum_j |a_ij|: the l1-Jacobi smoother (the Chebyshev smoother: 1 / a_ii) */
   double *b, *out;            /* the level's right-hand side and correction (level 0: the caller's) */
   double *tmp, *r;            /* the other smoothing buffer, the residual */
 };
@@ -414,6 +414,12 @@ void lsb_k_amg_csr(int mode, const struct lsb_amg_mat *m, const double *xin, con
                    double *y, const struct lsb_pcg_state *st, void *stream);
 void lsb_k_amg_dense(unsigned nc, unsigned lanes, const double *cinv, const double *b, double *out,
                      const struct lsb_pcg_state *st, void *stream);
+/* the Chebyshev smoother (LSB_AMG_SMOOTH_CHEB): step 0 from the zero guess, d = (c2 dinv) b, x = d ; a step
+ * with the matrix, d <- c1 d + c2 dinv (b - A xin) in place (not read when c1 == 0), y = xin + d */
+void lsb_k_amg_cheb_first(unsigned n, const double *b, const double *dinv, double c2, double *d, double *x,
+                          const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg_cheb(const struct lsb_amg_mat *m, const double *xin, const double *b, const double *dinv, double c1,
+                    double c2, double *d, double *y, const struct lsb_pcg_state *st, void *stream);
 /* levels t .. nlev - 1 of the V-cycle and the coarse solve in one launch of one 1024-thread
  * workgroup; lv = the device copy of all levels' descriptors; b0 / out0 stand in for level 0's */
 void lsb_k_amg_tail(const struct lsb_amg_lvdev *lv, unsigned t, unsigned nlev, unsigned nu, const double *cinv,
@@ -451,6 +457,14 @@ void lsb_k_amg_mrhs_restart_r(unsigned kp, unsigned n, const double *q, double *
 void lsb_k_amg_mrhs_restart_p(unsigned kp, unsigned n, const double *r, const double *z, double *p,
                               const struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr, int more,
                               double *partials, unsigned *npartials, void *stream);
+
+/* ---- the Chebyshev smoother on blocks of kp columns (hip_amg_cheb.hip): lsb_k_amg_cheb_first / lsb_k_amg_cheb
+ * per column, bit for bit; d is a block as x is.  records / nrecords as lsb_k_amg_csr_m's sweep leaves them. */
+void lsb_k_amg_cheb_first_m(unsigned kp, unsigned n, const double *b, const double *dinv, double c2, double *d,
+                            double *x, const struct lsb_mrhs_state *st, void *stream);
+void lsb_k_amg_cheb_m(unsigned kp, const struct lsb_amg_mat *m, const double *xin, const double *b,
+                      const double *dinv, double c1, double c2, double *d, double *y, double *records,
+                      unsigned *nrecords, const struct lsb_mrhs_state *st, void *stream);
 
 /* ---- backend internals shared between hip_cdna4.c and hip_comm.c -------- */
 void *lsb_hip_stream(void);

@@ -5,6 +5,8 @@
 #      per-row coefficients), xn3b_A_18 (config 2): jacobi, fsai, amg
 #   3. config 4 (64 M-row 7-point operator): AMG set-up time and solve
 #   4. rocprofv3 --kernel-trace --stats of AMG-PCG on config 3 and xn3b_A_18
+#   5. (on request) the V-cycle's smoother: l1-Jacobi nu = 1, 2 against Chebyshev nu = 1, 2, 3 (ratio 10) and
+#      nu = 2 (ratio 4) on xn3b_A_18 and config 3, two fresh processes each, the variants alternating
 # Every GPU step has its own time limit; the script stops at the first step that fails.
 # Usage: tools/gpu_amg_profile.sh OUT_DIR [steps]   (steps: a subset of "1234", default all)
 OUT=${1:?usage: tools/gpu_amg_profile.sh OUT_DIR [steps]}
@@ -61,5 +63,21 @@ if [[ $STEPS == *4* ]]; then
     echo "== $m: rocprofv3 kernel stats ($f)" | tee -a "$OUT/summary.txt"
     [ -n "$f" ] && cut -d, -f1-8 "$f" | head -n 16 | tee -a "$OUT/summary.txt"
   done
+fi
+if [[ $STEPS == *5* ]]; then
+  smoothers() { # PREFIX LIMIT_S ARGS...
+    local p=$1 lim=$2
+    shift 2
+    for rep in a b; do
+      run ${p}_l1_nu1_$rep $lim "$@" --precond amg || exit $?
+      run ${p}_cheb_nu1_$rep $lim "$@" --precond amg --amg-smoother cheb || exit $?
+      run ${p}_l1_nu2_$rep $lim "$@" --precond amg --amg-sweeps 2 || exit $?
+      run ${p}_cheb_nu2_$rep $lim "$@" --precond amg --amg-smoother cheb --amg-sweeps 2 || exit $?
+      run ${p}_cheb_nu3_$rep $lim "$@" --precond amg --amg-smoother cheb --amg-sweeps 3 || exit $?
+      run ${p}_cheb_nu2_r4_$rep $lim "$@" --precond amg --amg-smoother cheb --amg-sweeps 2 --amg-cheb-ratio 4 || exit $?
+    done
+  }
+  smoothers xn3b 120 --matrix "$XN" --trials=200
+  smoothers c3 300 --matrix $C3 --operator raw --tol 1e-8 --trials=10
 fi
 exit 0
