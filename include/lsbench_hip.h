@@ -129,6 +129,12 @@ enum { LSB_AMG_SMOOTH_L1JACOBI = 0,   /* nu sweeps x += diag(sum_j |a_ij|)^-1 (b
                                        Gershgorin bound (lsb_amg_gershgorin): a guaranteed
                                        bound, so the cycle stays SPD; nu row launches as nu
                                        sweeps, one more vector (the direction d) per level */
+enum { LSB_AMG_PREC_FP64 = 0,         /* the V-cycle in fp64 (default)                          */
+       LSB_AMG_PREC_FP32 = 1 };       /* the whole hierarchy and every level vector in fp32, inside
+                                       a Krylov loop that stays fp64 (x, r, p, q, every dot product,
+                                       the stop test): 8 B per stored entry and 4 B per vector
+                                       element where the fp64 cycle moves 12 and 8 (hip_amg_f32.hip);
+                                       no one-launch tail, no blocks of columns               */
 enum { LSB_KRYLOV_PCG = 0,    /* preconditioned CG (symmetric operators)    */
        LSB_KRYLOV_GMRES = 1,  /* restarted GMRES(m), right-preconditioned,
                                  for LSB_OP_RAW / unsymmetric operators;
@@ -239,6 +245,12 @@ struct lsb_hip_opts {
                         in ONE launch of one workgroup (k_amg_tail); 0 = off, a launch
                         per step: measured faster at every size tried (one workgroup
                         is latency-bound; profiles/r05_amg.txt)                 [0] */
+  int amg_precision; /* LSB_AMG_PREC_*: the precision of the V-cycle, whatever `precision`
+                        says; under FP32 amg_tail_rows is ignored and the solver does
+                        not serve blocks of columns; a hierarchy with an entry that does
+                        not fit a float is refused at creation.  (It sits here, in what
+                        was the alignment hole behind five ints: the size of the struct
+                        and the offset of amg_cheb_ratio hold)                [FP64] */
   int amg_smoother;  /* LSB_AMG_SMOOTH_*; under CHEB amg_sweeps is the polynomial's
                         degree and amg_tail_rows is ignored (the one-launch tail is
                         not built for it)                          [L1JACOBI] */
@@ -442,6 +454,11 @@ double lsb_amg_gershgorin(const struct csr *A);
  *   d_i <- fma(c2[k] / a_ii, b_i - s_i, c1[k] d_i),  x_i <- x_i + d_i ;  c1[0] = 0 and step 0 does not read d. */
 void lsb_amg_cheb_coeffs(double hi, double ratio, unsigned deg, double *c1, double *c2);
 void lsb_amg_free(struct lsb_amg_hier *h);
+/* The entries of a CSR as the fp32 V-cycle streams them: a malloc'ed array of offs[nrows] 8-byte words (at least
+ * one), word j = the 0-based column of entry j in the low 32 bits, the bit pattern of (float)vals[j] (round to
+ * nearest even) in the high 32.  NULL when a value is not finite or rounds to +-inf; subnormal results are kept.
+ * The caller frees with free(). */
+unsigned long long *lsb_csr_pack_f32(const struct csr *A);
 /* Sliced-ELL copy of a CSR for LSB_SPMV_SELL: rows in slices of LSB_SELL_ROWS,
  * every slice padded to its longest row and stored column-major (entry j of
  * row 128s+i at sptr[s] + 128j + i), so that a wavefront's lane l reads the
@@ -683,6 +700,13 @@ int lsb_hip_solver_amg_info(lsb_hip_solver *s, unsigned *levels, unsigned *tail_
  * on (hi = lsb_amg_gershgorin of the level, lo = hi / amg_cheb_ratio); 2 for another preconditioner or
  * smoother and for a level that is not smoothed (the coarsest, or beyond). */
 int lsb_hip_solver_amg_cheb_interval(lsb_hip_solver *s, unsigned level, double *lo, double *hi);
+/* The precision of the V-cycle: LSB_AMG_PREC_FP64 (0) or LSB_AMG_PREC_FP32 (1); 2 for a solver without AMG. */
+int lsb_hip_solver_amg_precision(lsb_hip_solver *s);
+/* Bytes one application of the V-cycle must move, 0 without AMG.  fp64: 12 per stored entry for every launch that
+ * streams a matrix (A 2 nu times per level, P and R once), 8 nc^2 for the coarse inverse, 8 per element pass of
+ * the level vectors.  fp32: 8 per stored entry, 4 nc^2, 4 per element pass; the fine level's r is read once
+ * and z written once at 8, and the fp32 copy of r is written once. */
+unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *s);
 /* LSB_PRECOND_CHEBYSHEV: the interval [lmin, lmax] of D^-1 S the polynomial was built on at creation
  * (lmax = 1.1 x the power iteration's estimate, lmin = lmax / max(30, 16 degree^2), the degree
  * clamped to 1 .. 32); 2 for another preconditioner. */

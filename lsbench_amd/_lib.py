@@ -23,6 +23,7 @@ OP_CHOLMOD_UPPER, OP_RAW = 0, 1
 PRECOND_JACOBI, PRECOND_NONE, PRECOND_L1JACOBI, PRECOND_CHEBYSHEV, PRECOND_BLOCKJACOBI, PRECOND_FSAI = 0, 1, 2, 3, 4, 5
 PRECOND_AMG = 6
 AMG_SMOOTH_L1JACOBI, AMG_SMOOTH_CHEB = 0, 1
+AMG_PREC_FP64, AMG_PREC_FP32 = 0, 1
 KRYLOV_PCG, KRYLOV_GMRES, KRYLOV_PCG1, KRYLOV_AUTO, KRYLOV_BICGSTAB = 0, 1, 2, 3, 4
 SPMV_AUTO, SPMV_ADAPTIVE, SPMV_SUBWAVE, SPMV_SCALAR, SPMV_PANEL, SPMV_SELL, SPMV_BINNED, SPMV_TWOPHASE = 0, 1, 2, 3, 4, 5, 6, 7
 SELL_ROWS = 128
@@ -66,6 +67,7 @@ class Opts(C.Structure):
                 ("comm_deadline_s", C.c_double), ("fsai_power", C.c_int), ("blas1_nt", C.c_int),
                 ("amg_theta", C.c_double), ("amg_sweeps", C.c_int), ("amg_coarse", C.c_int),
                 ("amg_max_levels", C.c_int), ("amg_tail_rows", C.c_int),
+                ("amg_precision", C.c_int),
                 ("amg_smoother", C.c_int), ("amg_cheb_ratio", C.c_double)]
 
 
@@ -218,6 +220,7 @@ SIGNATURES = {
     "lsb_amg_aggregate": (C.POINTER(C.c_int), [_csrp, _d, C.POINTER(_u)]),
     "lsb_amg_free": (None, [C.POINTER(AmgHier)]),
     "lsb_amg_gershgorin": (_d, [_csrp]),
+    "lsb_csr_pack_f32": (C.POINTER(C.c_ulonglong), [_csrp]),
     "lsb_amg_cheb_coeffs": (None, [_d, _d, _u, C.POINTER(_d), C.POINTER(_d)]),
     "lsb_sell16_templates": (C.POINTER(SellTmpls), [C.POINTER(Sell), C.POINTER(SellVc)]),
     "lsb_sell_tmpls_free": (None, [C.POINTER(SellTmpls)]),
@@ -247,6 +250,8 @@ SIGNATURES = {
     "lsb_hip_solver_precond_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
     "lsb_hip_solver_precond_dev": (_i, [_vp, _vp, _vp]),
     "lsb_hip_solver_amg_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u)]),
+    "lsb_hip_solver_amg_precision": (_i, [_vp]),
+    "lsb_hip_solver_amg_cycle_bytes": (C.c_ulonglong, [_vp]),
     "lsb_hip_solver_amg_cheb_interval": (_i, [_vp, _u, C.POINTER(_d), C.POINTER(_d)]),
     "lsb_hip_solver_cheb_interval": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
     "lsb_hip_solver_time_spmv": (_i, [_vp, _i, _i, C.POINTER(_d)]),

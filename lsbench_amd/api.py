@@ -346,6 +346,17 @@ class Solver:
         L.check(L.load().lsb_hip_solver_amg_info(self._h, C.byref(lv), C.byref(tl)), "amg_info")
         return lv.value, tl.value
 
+    @property
+    def amg_precision(self):
+        """AMG_PREC_FP64 or AMG_PREC_FP32, the precision of the V-cycle; None for a solver without AMG."""
+        rc = L.load().lsb_hip_solver_amg_precision(self._h)
+        return None if rc == 2 else rc
+
+    @property
+    def amg_cycle_bytes(self):
+        """Bytes one application of the AMG V-cycle must move (0 without AMG)."""
+        return int(L.load().lsb_hip_solver_amg_cycle_bytes(self._h))
+
     def amg_cheb_interval(self, level):
         """(lo, hi) of D^-1 A the Chebyshev smoother of an AMG level was built on; None where the level is not
         smoothed by one (the coarsest level, an l1-Jacobi solver, another preconditioner)."""

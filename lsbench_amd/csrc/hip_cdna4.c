@@ -99,6 +99,7 @@ void lsb_hip_opts_default(struct lsb_hip_opts *o) {
   o->amg_tail_rows = 0; /* measured: one workgroup is latency-bound, a launch per step is faster (profiles/r05_amg.txt) */
   o->amg_smoother = LSB_AMG_SMOOTH_L1JACOBI;
   o->amg_cheb_ratio = 10.0;
+  o->amg_precision = LSB_AMG_PREC_FP64;
 }
 
 /* ONE typed table for everything a caller may set by name: the command line of a host
@@ -116,6 +117,7 @@ static const struct optchoice CH_PRECOND[] = {{"jacobi", LSB_PRECOND_JACOBI},   
                                               {"bj", LSB_PRECOND_BLOCKJACOBI},  {"fsai", LSB_PRECOND_FSAI},
                                               {"amg", LSB_PRECOND_AMG},         {NULL, 0}};
 static const struct optchoice CH_AMG_SMOOTHER[] = {{"l1", LSB_AMG_SMOOTH_L1JACOBI}, {"cheb", LSB_AMG_SMOOTH_CHEB}, {NULL, 0}};
+static const struct optchoice CH_AMG_PRECISION[] = {{"fp64", LSB_AMG_PREC_FP64}, {"fp32", LSB_AMG_PREC_FP32}, {NULL, 0}};
 static const struct optchoice CH_COMM[] = {{"auto", LSB_COMM_AUTO}, {"rccl", LSB_COMM_RCCL}, {"p2p", LSB_COMM_P2P}, {NULL, 0}};
 static const struct optchoice CH_KRYLOV[] = {{"cg", LSB_KRYLOV_PCG},     {"pcg", LSB_KRYLOV_PCG}, /* (alias) */
                                              {"cg1", LSB_KRYLOV_PCG1},   {"pcg1", LSB_KRYLOV_PCG1},
@@ -162,6 +164,7 @@ static const struct optdef {
     OPT("amg-tail-rows", OT_INT, amg_tail_rows, NULL),
     OPT("amg-smoother", OT_ENUM, amg_smoother, CH_AMG_SMOOTHER),
     OPT("amg-cheb-ratio", OT_DBL, amg_cheb_ratio, NULL),
+    OPT("amg-precision", OT_ENUM, amg_precision, CH_AMG_PRECISION),
 };
 #undef OPT
 #define NOPTS (sizeof OPTS / sizeof OPTS[0])

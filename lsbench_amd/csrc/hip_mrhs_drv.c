@@ -38,7 +38,8 @@ static int mrhs_serves(const lsb_hip_solver *sv) {
   return !sv->multi && sv->nshard == 1 && !sv->dist && o->precision == LSB_PREC_FP64 &&
          (o->krylov == LSB_KRYLOV_PCG || o->krylov == LSB_KRYLOV_AUTO) &&
          (o->precond == LSB_PRECOND_JACOBI || o->precond == LSB_PRECOND_L1JACOBI ||
-          o->precond == LSB_PRECOND_NONE || (o->precond == LSB_PRECOND_AMG && sv->sh[0].amg)) &&
+          o->precond == LSB_PRECOND_NONE ||
+          (o->precond == LSB_PRECOND_AMG && sv->sh[0].amg && sv->sh[0].amg->prec == LSB_AMG_PREC_FP64)) &&
          o->persistent <= 0 && !sv->ps.use && (unsigned long long)sv->sh[0].n * LSB_MRHS_MAX < (1ull << 32);
 }
 

@@ -37,6 +37,72 @@ static struct lsb_amg_mat amg_upload_mat(struct amg_dev *a, const struct csr *M)
   return m;
 }
 
+/* ---- the same hierarchy in fp32 (opts.amg_precision = LSB_AMG_PREC_FP32; kernels: hip_amg_f32.hip) ---- */
+/* offsets and packed {column, float} entries; the lanes by amg_upload_mat's rule; the fp64 values stay on the host */
+static struct amg_mat32 amg_upload_mat32(struct amg_dev *a, const struct csr *M, const char *what, unsigned l) {
+  struct amg_mat32 m;
+  const unsigned n = M->nrows;
+  const unsigned long long nnz = M->offs[n];
+  if (nnz > 0x7fffffffull)
+    errx(EXIT_FAILURE, "hip_cdna4: an AMG operator has %llu entries, more than 2^31 - 1", nnz);
+  unsigned long long *w = lsb_csr_pack_f32(M);
+  if (!w)
+    errx(EXIT_FAILURE, "hip_cdna4: --amg-precision fp32: an entry of %s on level %u is not finite in fp32; use "
+                       "--amg-precision fp64", what, l);
+  m.rows = n;
+  m.offs = (const int *)amg_keep(a, dev_upload(M->offs, ((size_t)n + 1) * sizeof(unsigned)));
+  m.ent = (const unsigned long long *)amg_keep(a, dev_upload(w, (size_t)(nnz ? nnz : 1) * sizeof *w));
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  free(w);
+  const unsigned mean = n ? (unsigned)((nnz + n - 1) / n) : 1;
+  const unsigned L = pow2_ceil(mean ? mean : 1);
+  m.lanes = L < 2 ? 2 : (L > 64 ? 64 : L);
+  return m;
+}
+
+/* a float copy of cnt doubles on the device; refuses what does not fit */
+static float *amg_upload_f32(struct amg_dev *a, const double *v, size_t cnt, const char *what) {
+  float *f = (float *)malloc((cnt ? cnt : 1) * sizeof(float));
+  if (!f)
+    errx(EXIT_FAILURE, "hip_cdna4: out of host memory for the fp32 AMG hierarchy");
+  f[0] = 0.0f;
+  for (size_t i = 0; i < cnt; i++) {
+    f[i] = (float)v[i];
+    if (!isfinite(v[i]) || isinf(f[i]))
+      errx(EXIT_FAILURE, "hip_cdna4: --amg-precision fp32: an entry of %s is not finite in fp32; use "
+                         "--amg-precision fp64", what);
+  }
+  float *d = (float *)amg_keep(a, dev_upload(f, (cnt ? cnt : 1) * sizeof(float)));
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  free(f);
+  return d;
+}
+
+/* level l of the fp32 hierarchy: its matrices, minv (the Chebyshev smoother: dinv, the coefficients rounded once
+ * and the direction vector) and, below the fine level, its four vectors */
+static void amg_upload_level32(struct amg_dev *a, unsigned l, const struct lsb_amg_level *L, const double *minv,
+                               const struct amg_cheb *c) {
+  struct amg_lv32 *v = &a->lv32[l];
+  v->n = L->n;
+  v->A = amg_upload_mat32(a, L->A, "A", l);
+  if (L->P) {
+    v->P = amg_upload_mat32(a, L->P, "P", l);
+    v->R = amg_upload_mat32(a, L->R, "R", l);
+  }
+  v->minv = amg_upload_f32(a, minv, L->n, "the smoother's diagonal");
+  if (c && L->P) {
+    for (unsigned k = 0; k < a->nu; k++)
+      v->c1[k] = (float)c->c1[k], v->c2[k] = (float)c->c2[k];
+    v->d = (float *)amg_keep(a, lsb_hip_malloc((size_t)(L->n ? L->n : 1) * sizeof(float)));
+    LSB_CHK_HIP(hipMemsetAsync(v->d, 0, (size_t)(L->n ? L->n : 1) * sizeof(float), g_stream));
+  }
+  if (l > 0) {
+    float *buf = (float *)amg_keep(a, lsb_hip_malloc(4 * (size_t)L->n * sizeof(float)));
+    LSB_CHK_HIP(hipMemsetAsync(buf, 0, 4 * (size_t)L->n * sizeof(float), g_stream));
+    v->b = buf, v->out = buf + L->n, v->tmp = buf + 2 * (size_t)L->n, v->r = buf + 3 * (size_t)L->n;
+  }
+}
+
 static void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const double *vals,
                               const struct lsb_hip_opts *o) {
   if (s->row_begin != 0 || s->n != s->n_glob)
@@ -62,10 +128,17 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
   const double ratio = o->amg_cheb_ratio >= 1.5 ? o->amg_cheb_ratio : 1.5;
   if (o->amg_smoother != LSB_AMG_SMOOTH_L1JACOBI && !cheb)
     errx(EXIT_FAILURE, "hip_cdna4: no AMG smoother %d (--amg-smoother l1 or cheb)", o->amg_smoother);
+  if (o->amg_precision != LSB_AMG_PREC_FP64 && o->amg_precision != LSB_AMG_PREC_FP32)
+    errx(EXIT_FAILURE, "hip_cdna4: no AMG precision %d (--amg-precision fp64 or fp32)", o->amg_precision);
+  const int f32 = o->amg_precision == LSB_AMG_PREC_FP32;
+  a->prec = o->amg_precision;
   if (cheb)
     a->cheb = lsb_calloc(struct amg_cheb, h->nlev);
+  if (f32)
+    a->lv32 = lsb_calloc(struct amg_lv32, h->nlev);
   a->tail = h->nlev;
-  for (unsigned l = 0; l < h->nlev && !cheb; l++) /* (the one-launch tail is not built for the Chebyshev smoother) */
+  /* (the one-launch tail is not built for the Chebyshev smoother, nor for the fp32 cycle) */
+  for (unsigned l = 0; l < h->nlev && !cheb && !f32; l++)
     if (o->amg_tail_rows > 0 && h->lv[l].n <= (unsigned)o->amg_tail_rows) {
       a->tail = l;
       break;
@@ -75,10 +148,12 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
     const struct lsb_amg_level *L = &h->lv[l];
     struct lsb_amg_lvdev *v = &a->lv[l];
     v->n = L->n;
-    v->A = amg_upload_mat(a, L->A);
-    if (L->P) {
-      v->P = amg_upload_mat(a, L->P);
-      v->R = amg_upload_mat(a, L->R);
+    if (!f32) {
+      v->A = amg_upload_mat(a, L->A);
+      if (L->P) {
+        v->P = amg_upload_mat(a, L->P);
+        v->R = amg_upload_mat(a, L->R);
+      }
     }
     double *minv = (double *)malloc((size_t)(L->n ? L->n : 1) * sizeof(double));
     for (unsigned i = 0; i < L->n; i++) {
@@ -91,13 +166,18 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
       struct amg_cheb *c = &a->cheb[l];
       c->hi = lsb_amg_gershgorin(L->A), c->lo = c->hi / ratio;
       lsb_amg_cheb_coeffs(c->hi, ratio, a->nu, c->c1, c->c2);
-      c->d = (double *)amg_keep(a, lsb_hip_malloc((size_t)L->n * sizeof(double)));
-      LSB_CHK_HIP(hipMemsetAsync(c->d, 0, (size_t)L->n * sizeof(double), g_stream));
+      if (!f32) {
+        c->d = (double *)amg_keep(a, lsb_hip_malloc((size_t)L->n * sizeof(double)));
+        LSB_CHK_HIP(hipMemsetAsync(c->d, 0, (size_t)L->n * sizeof(double), g_stream));
+      }
     }
-    v->minv = (const double *)amg_keep(a, dev_upload(minv, (size_t)(L->n ? L->n : 1) * sizeof(double)));
+    if (f32)
+      amg_upload_level32(a, l, L, minv, cheb ? &a->cheb[l] : NULL);
+    else
+      v->minv = (const double *)amg_keep(a, dev_upload(minv, (size_t)(L->n ? L->n : 1) * sizeof(double)));
     LSB_CHK_HIP(hipStreamSynchronize(g_stream));
     free(minv);
-    if (l > 0) { /* level 0: the caller's r and z; its two other vectors come out of the slab (precond_setup) */
+    if (l > 0 && !f32) { /* level 0: the caller's r and z; its two other vectors come out of the slab (precond_setup) */
       double *buf = (double *)amg_keep(a, lsb_hip_malloc(4 * (size_t)L->n * sizeof(double)));
       LSB_CHK_HIP(hipMemsetAsync(buf, 0, 4 * (size_t)L->n * sizeof(double), g_stream));
       v->b = buf, v->out = buf + L->n, v->tmp = buf + 2 * (size_t)L->n, v->r = buf + 3 * (size_t)L->n;
@@ -114,7 +194,12 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
   }
   a->cycle_mat_bytes += 8ull * h->nc * h->nc;
   a->cycle_vec_rows += 2ull * h->nc;
-  a->d_cinv = (double *)amg_keep(a, dev_upload(h->coarse_inv, (size_t)h->nc * h->nc * sizeof(double)));
+  if (f32) { /* 8 B per entry, 4 nc^2, 4 B per element pass; level 0: r read and z written at 8 B, the copy of r written */
+    a->cycle_bytes32 = (a->cycle_mat_bytes - 8ull * h->nc * h->nc) / 3ull * 2ull + 4ull * h->nc * h->nc +
+                       4ull * a->cycle_vec_rows + (h->nlev > 1 ? 12ull * h->lv[0].n : 8ull * h->nc);
+    a->d_cinv32 = amg_upload_f32(a, h->coarse_inv, (size_t)h->nc * h->nc, "the coarse inverse");
+  } else
+    a->d_cinv = (double *)amg_keep(a, dev_upload(h->coarse_inv, (size_t)h->nc * h->nc * sizeof(double)));
   {
     const unsigned L = pow2_ceil(h->nc ? h->nc : 1);
     a->clanes = L < 2 ? 2 : (L > 64 ? 64 : L);
@@ -124,13 +209,14 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
   if (o->verbose) {
     for (unsigned l = 0; l < h->nlev; l++) {
       const struct lsb_amg_level *L = &h->lv[l];
-      fprintf(stderr, "hip_cdna4: AMG level %u: %u rows, %u entries, %u lanes (A)", l, L->n, L->A->offs[L->n],
-              a->lv[l].A.lanes);
+      const unsigned la = f32 ? a->lv32[l].A.lanes : a->lv[l].A.lanes;
+      const unsigned lp = f32 ? a->lv32[l].P.lanes : a->lv[l].P.lanes;
+      const unsigned lr = f32 ? a->lv32[l].R.lanes : a->lv[l].R.lanes;
+      fprintf(stderr, "hip_cdna4: AMG level %u: %u rows, %u entries, %u lanes (A)", l, L->n, L->A->offs[L->n], la);
       if (L->P && cheb)
-        fprintf(stderr, ", %u / %u lanes (P / R), Chebyshev on [%.4g, %.4g]\n", a->lv[l].P.lanes, a->lv[l].R.lanes,
-                a->cheb[l].lo, a->cheb[l].hi);
+        fprintf(stderr, ", %u / %u lanes (P / R), Chebyshev on [%.4g, %.4g]\n", lp, lr, a->cheb[l].lo, a->cheb[l].hi);
       else if (L->P)
-        fprintf(stderr, ", %u / %u lanes (P / R)\n", a->lv[l].P.lanes, a->lv[l].R.lanes);
+        fprintf(stderr, ", %u / %u lanes (P / R)\n", lp, lr);
       else
         fprintf(stderr, ", dense coarse inverse, %u lanes\n", a->clanes);
     }
@@ -142,6 +228,9 @@ static void precond_shard_amg(struct shard *s, const int *offs, const int *cols,
       fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u of %u levels in the one-launch tail, %u l1-Jacobi "
                       "sweep%s, set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev - a->tail, h->nlev,
               a->nu, a->nu > 1 ? "s" : "", a->setup_s);
+    if (f32)
+      fprintf(stderr, "hip_cdna4: AMG V-cycle in fp32 (packed entries, float vectors): %llu bytes per application, "
+                      "%llu in fp64\n", a->cycle_bytes32, a->cycle_mat_bytes + 8ull * a->cycle_vec_rows);
   }
   lsb_amg_free(h);
   s->amg = a;
@@ -153,6 +242,13 @@ static void amg_finish_setup(struct shard *s) {
   a->lv[0].tmp = shard_vec(s, s->n), a->lv[0].r = shard_vec(s, s->n);
   LSB_CHK_HIP(hipMemsetAsync(a->lv[0].tmp, 0, (size_t)s->n * sizeof(double), g_stream));
   LSB_CHK_HIP(hipMemsetAsync(a->lv[0].r, 0, (size_t)s->n * sizeof(double), g_stream));
+  if (a->lv32) { /* fp32: the same two slab vectors, split -- two ping-pong iterates, the copy of r, the residual */
+    struct amg_lv32 *v = &a->lv32[0];
+    v->tmp = (float *)a->lv[0].tmp, v->out = v->tmp + s->n;
+    v->b = (float *)a->lv[0].r, v->r = v->b + s->n;
+    LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+    return; /* (no one-launch tail: no descriptors on the device) */
+  }
   a->d_lv = (struct lsb_amg_lvdev *)amg_keep(a, dev_upload(a->lv, (size_t)a->nlev * sizeof(struct lsb_amg_lvdev)));
   LSB_CHK_HIP(hipStreamSynchronize(g_stream));
 }
@@ -202,6 +298,58 @@ static void amg_vcycle(const struct shard *s, const double *d_r, double *d_z, co
       else
         lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
       double *w = cur;
+      cur = oth, oth = w;
+    }
+  }
+}
+
+/* The cycle in fp32 (a->lv32; hip_amg_f32.hip): amg_vcycle's step order, launch count and ping-pong parity, never a
+ * tail.  The fine level's first step reads the fp64 r and leaves its fp32 copy in lv32[0].b; the fine level's last
+ * post-smoothing step writes the fp64 z.  A hierarchy of one level is the coarse solve alone, from r to z. */
+static void amg_vcycle_f32(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st) {
+  const struct amg_dev *a = s->amg;
+  const unsigned nu = a->nu, top = a->nlev - 1;
+  for (unsigned l = 0; l < top; l++) {
+    const struct amg_lv32 *v = &a->lv32[l];
+    float *cur = v->tmp, *oth = v->out;
+    const void *b0 = l ? (const void *)v->b : (const void *)d_r;
+    if (a->cheb)
+      lsb_k_amg32_cheb_first(v->n, l == 0, b0, v->minv, v->c2[0], v->d, cur, v->b, st, g_stream);
+    else
+      lsb_k_amg32_first(v->n, l == 0, b0, v->minv, cur, v->b, st, g_stream);
+    for (unsigned k = 1; k < nu; k++) {
+      if (a->cheb)
+        lsb_k_amg32_cheb(v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, v->c1[k], v->c2[k], v->d,
+                         oth, NULL, st, g_stream);
+      else
+        lsb_k_amg32_csr(LSB_AMG_SWEEP, v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, oth, NULL, st,
+                        g_stream);
+      float *w = cur;
+      cur = oth, oth = w;
+    }
+    lsb_k_amg32_csr(LSB_AMG_RESID, v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, v->r, NULL, st,
+                    g_stream);
+    lsb_k_amg32_csr(LSB_AMG_SPMV, v->R.rows, v->R.lanes, v->R.offs, v->R.ent, v->r, NULL, NULL, a->lv32[l + 1].b,
+                    NULL, st, g_stream);
+  }
+  if (top)
+    lsb_k_amg32_dense(a->nc, a->clanes, 0, a->d_cinv32, a->lv32[top].b, a->lv32[top].out, st, g_stream);
+  else
+    lsb_k_amg32_dense(a->nc, a->clanes, 1, a->d_cinv32, d_r, d_z, st, g_stream);
+  for (unsigned l = top; l-- > 0;) {
+    const struct amg_lv32 *v = &a->lv32[l];
+    float *cur = (nu - 1) % 2 ? v->out : v->tmp, *oth = (nu - 1) % 2 ? v->tmp : v->out;
+    lsb_k_amg32_csr(LSB_AMG_ADDP, v->P.rows, v->P.lanes, v->P.offs, v->P.ent, a->lv32[l + 1].out, NULL, NULL, cur,
+                    NULL, st, g_stream);
+    for (unsigned k = 0; k < nu; k++) { /* the last one writes `out` -- on the fine level z, widened */
+      double *z64 = l == 0 && k + 1 == nu ? d_z : NULL;
+      if (a->cheb)
+        lsb_k_amg32_cheb(v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, v->c1[k], v->c2[k], v->d,
+                         oth, z64, st, g_stream);
+      else
+        lsb_k_amg32_csr(LSB_AMG_SWEEP, v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, oth, z64, st,
+                        g_stream);
+      float *w = cur;
       cur = oth, oth = w;
     }
   }
@@ -266,7 +414,7 @@ static void amg_free(struct shard *s) {
   for (unsigned k = 0; k < a->nmem; k++)
     lsb_hip_free(a->mem[k]);
   shard_vec_free(s, a->lv[0].tmp), shard_vec_free(s, a->lv[0].r);
-  free(a->mem), free(a->lv), free(a->cheb), free(a);
+  free(a->mem), free(a->lv), free(a->cheb), free(a->lv32), free(a);
   s->amg = NULL;
 }
 
@@ -583,7 +731,10 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
   }
   if (sv->o.precond == LSB_PRECOND_AMG) { /* z = one V-cycle */
     struct shard *s = &sv->sh[0];
-    amg_vcycle(s, s->d_r, s->d_z, s->d_st);
+    if (s->amg->prec == LSB_AMG_PREC_FP32)
+      amg_vcycle_f32(s, s->d_r, s->d_z, s->d_st);
+    else
+      amg_vcycle(s, s->d_r, s->d_z, s->d_st);
     return;
   }
   if (sv->o.precond == LSB_PRECOND_BLOCKJACOBI) {
@@ -693,6 +844,19 @@ int lsb_hip_solver_amg_info(lsb_hip_solver *sv, unsigned *levels, unsigned *tail
   if (tail_levels)
     *tail_levels = a->nlev - a->tail;
   return 0;
+}
+
+int lsb_hip_solver_amg_precision(lsb_hip_solver *sv) {
+  if (!sv || sv->o.precond != LSB_PRECOND_AMG || !sv->sh[0].amg)
+    return 2;
+  return sv->sh[0].amg->prec;
+}
+
+unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *sv) {
+  if (!sv || sv->o.precond != LSB_PRECOND_AMG || !sv->sh[0].amg)
+    return 0;
+  const struct amg_dev *a = sv->sh[0].amg;
+  return a->prec == LSB_AMG_PREC_FP32 ? a->cycle_bytes32 : a->cycle_mat_bytes + 8ull * a->cycle_vec_rows;
 }
 
 int lsb_hip_solver_amg_cheb_interval(lsb_hip_solver *sv, unsigned level, double *lo, double *hi) {

@@ -69,6 +69,15 @@ enum pcg_form {
   PCG_FSAI3,   /* FSAI in three launches: k_spmv_subwave_p, k_fsai_xr_gr, k_fsai_gt_dots */
 };
 
+/* a matrix of the fp32 AMG hierarchy: int row offsets, one packed {column, float} word per stored entry
+ * (lsb_csr_pack_f32), `lanes` per row by amg_upload_mat's rule.  A sibling of lsb_amg_mat, whose layout
+ * k_amg_tail reads from the device. */
+struct amg_mat32 {
+  const int *offs;
+  const unsigned long long *ent;
+  unsigned rows, lanes;
+};
+
 struct shard {
   /* ONE allocation for the vectors the iteration streams (r, q, the gather vector, the Jacobi
    * diagonal, the single-reduction form's p / s, the preconditioners' z vectors, the second direction
@@ -204,6 +213,20 @@ struct shard {
       double lo, hi, c1[16], c2[16];
       double *d;
     } *cheb;
+    /* opts.amg_precision = LSB_AMG_PREC_FP32 (lv32 NULL under fp64): the hierarchy in single precision as
+     * hip_amg_f32.hip's kernels see it -- packed matrices, float minv / dinv, coarse inverse, level vectors and
+     * Chebyshev direction, the coefficients rounded once.  Level 0's four vectors are the two slab vectors
+     * lv[0].tmp and lv[0].r split in halves; lv[] then holds the row counts and nothing else of the matrices. */
+    int prec;
+    struct amg_lv32 {
+      unsigned n;
+      struct amg_mat32 A, P, R;
+      const float *minv;
+      float *b, *out, *tmp, *r; /* level 0's b: the fp32 copy of the caller's r */
+      float *d, c1[16], c2[16];
+    } *lv32;
+    float *d_cinv32;
+    unsigned long long cycle_bytes32; /* what lsb_hip_solver_amg_cycle_bytes answers under fp32 */
   } *amg;
   struct lsb_xfer *recv, *send;
   int nrecv, nsend;
@@ -397,6 +420,22 @@ LSB_INTERNAL void amg_vcycle_multi(const struct shard *s, unsigned kp, const str
                                    double *d_Z, double *records, unsigned *nrecords,
                                    const struct lsb_mrhs_state *st);
 LSB_INTERNAL void precond_free_shard(struct shard *s);
+/* ---- the fp32 V-cycle (hip_amg_f32.hip; driver: amg_vcycle_f32).  Modes, lanes, grids and the gate `st` as
+ * hip_amg.hip's launchers.  in64: b is the caller's fp64 r, rounded once, the copy stored in b32 (else b is
+ * float and b32 unused); y64 != NULL: the result goes there widened to double instead of to y (sweeps and
+ * Chebyshev steps only); ends64: a one-level hierarchy's coarse solve, fp64 r to fp64 z. */
+void lsb_k_amg32_first(unsigned n, int in64, const void *b, const float *minv, float *x, float *b32,
+                       const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_csr(int mode, unsigned rows, unsigned lanes, const int *offs, const unsigned long long *ent,
+                     const float *xin, const float *b, const float *minv, float *y, double *y64,
+                     const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_cheb_first(unsigned n, int in64, const void *b, const float *dinv, float c2, float *d, float *x,
+                            float *b32, const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_cheb(unsigned rows, unsigned lanes, const int *offs, const unsigned long long *ent,
+                      const float *xin, const float *b, const float *dinv, float c1, float c2, float *d, float *y,
+                      double *y64, const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_dense(unsigned nc, unsigned lanes, int ends64, const float *cinv, const void *b, void *out,
+                       const struct lsb_pcg_state *st, void *stream);
 /* hip_gmres_drv.c */
 LSB_INTERNAL int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
                                  struct lsb_hip_result *res);

@@ -471,3 +471,30 @@ void lsb_amg_free(struct lsb_amg_hier *h) {
   }
   free(h->lv), free(h->coarse_inv), free(h);
 }
+
+/* The entries of a CSR as hip_amg_f32.hip streams them: word j = {0-based column, bits of (float)vals[j]}.  The
+ * conversion rounds to nearest even (the default mode; nothing here changes it).  NULL: some value is not finite
+ * or rounds to +-inf -- the fp32 cycle refuses such a hierarchy. */
+unsigned long long *lsb_csr_pack_f32(const struct csr *A) {
+  if (!A)
+    return NULL;
+  const unsigned long long nnz = A->offs[A->nrows];
+  unsigned long long *w = (unsigned long long *)malloc((size_t)(nnz ? nnz : 1) * sizeof *w);
+  if (!w)
+    return NULL;
+  w[0] = 0;
+  int ok = 1;
+#pragma omp parallel for reduction(& : ok) schedule(static)
+  for (long long j = 0; j < (long long)nnz; j++) {
+    const float f = (float)A->vals[j];
+    unsigned bits;
+    memcpy(&bits, &f, sizeof bits);
+    ok &= isfinite(A->vals[j]) && !isinf(f);
+    w[j] = (unsigned long long)(A->cols[j] - A->base) | ((unsigned long long)bits << 32);
+  }
+  if (!ok) {
+    free(w);
+    return NULL;
+  }
+  return w;
+}

@@ -92,7 +92,11 @@ static void usage(const char *prog) {
   printf("                       --amg-tail-rows ROWS: levels run in one launch), one shard, cg only;\n");
   printf("                       --amg-smoother <l1|cheb>: cheb = a Chebyshev polynomial of degree NU in\n");
   printf("                       D^-1 A in the place of the NU sweeps, on [rho / X, rho], rho the level's\n");
-  printf("                       Gershgorin bound, X = --amg-cheb-ratio (default 10)\n");
+  printf("                       Gershgorin bound, X = --amg-cheb-ratio (default 10);\n");
+  printf("                       --amg-precision <fp64|fp32>: fp32 = the whole V-cycle (matrices, level\n");
+  printf("                       vectors, coarse inverse) in single precision inside the fp64 Krylov loop:\n");
+  printf("                       8 instead of 12 bytes per entry, 4 instead of 8 per vector element; no\n");
+  printf("                       one-launch tail, no blocks of right-hand sides (default fp64)\n");
   printf("  --ngpus <N>          (hip) row-partition the operator over N GPUs of this node\n");
   printf("                       (0 = all visible), driven from this one process\n");
   printf("  --reorder            (hip) solve the RCM-permuted operator (any --ordering\n");
@@ -117,7 +121,7 @@ struct lsbench *lsbench_init(int argc, char *argv[]) {
       {"amg-theta", required_argument, 0, 80}, {"amg-sweeps", required_argument, 0, 80},
       {"amg-coarse", required_argument, 0, 80}, {"amg-max-levels", required_argument, 0, 80},
       {"amg-tail-rows", required_argument, 0, 80}, {"amg-smoother", required_argument, 0, 80},
-      {"amg-cheb-ratio", required_argument, 0, 80},
+      {"amg-cheb-ratio", required_argument, 0, 80}, {"amg-precision", required_argument, 0, 80},
       {0, 0, 0, 0}};
 
   /* zero-filled => solver 0 (CUSOLVER), ordering 0 (RCM), FP64: the

@@ -7,8 +7,11 @@
 #   4. rocprofv3 --kernel-trace --stats of AMG-PCG on config 3 and xn3b_A_18
 #   5. (on request) the V-cycle's smoother: l1-Jacobi nu = 1, 2 against Chebyshev nu = 1, 2, 3 (ratio 10) and
 #      nu = 2 (ratio 4) on xn3b_A_18 and config 3, two fresh processes each, the variants alternating
+#   6. (on request) the V-cycle's precision: fp64 against fp32 (--amg-precision) at nu = 1, 2 on xn3b_A_18 and
+#      config 3, two fresh processes each, the variants alternating; then tools/gpu_amg_cycle_bw.py: the time of one
+#      application and amg_cycle_bytes over it
 # Every GPU step has its own time limit; the script stops at the first step that fails.
-# Usage: tools/gpu_amg_profile.sh OUT_DIR [steps]   (steps: a subset of "1234", default all)
+# Usage: tools/gpu_amg_profile.sh OUT_DIR [steps]   (steps: a subset of "123456", default "1234")
 OUT=${1:?usage: tools/gpu_amg_profile.sh OUT_DIR [steps]}
 STEPS=${2:-1234}
 mkdir -p "$OUT"
@@ -79,5 +82,23 @@ if [[ $STEPS == *5* ]]; then
   }
   smoothers xn3b 120 --matrix "$XN" --trials=200
   smoothers c3 300 --matrix $C3 --operator raw --tol 1e-8 --trials=10
+fi
+if [[ $STEPS == *6* ]]; then
+  precisions() { # PREFIX LIMIT_S ARGS...
+    local p=$1 lim=$2
+    shift 2
+    for rep in a b; do
+      for nu in 1 2; do
+        run ${p}_fp64_nu${nu}_$rep $lim "$@" --precond amg --amg-sweeps $nu || exit $?
+        run ${p}_fp32_nu${nu}_$rep $lim "$@" --precond amg --amg-sweeps $nu --amg-precision fp32 || exit $?
+      done
+    done
+  }
+  precisions xn3b 120 --matrix "$XN" --trials=200
+  precisions c3 300 --matrix $C3 --operator raw --tol 1e-8 --trials=10
+  for m in "$XN" $C3; do
+    timeout -k 10 300 python tools/gpu_amg_cycle_bw.py "$m" 2>&1 | tee -a "$OUT/summary.txt"
+    [ ${PIPESTATUS[0]} -eq 0 ] || exit 1
+  done
 fi
 exit 0
