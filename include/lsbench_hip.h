@@ -145,12 +145,23 @@ enum { LSB_KRYLOV_PCG = 0,    /* preconditioned CG (symmetric operators)    */
        LSB_KRYLOV_AUTO = 3,   /* PCG1 when the operator is spread over several
                                  shards (one collective less per iteration),
                                  PCG otherwise                              */
-       LSB_KRYLOV_BICGSTAB = 4 }; /* BiCGSTAB, right-preconditioned by a diagonal
+       LSB_KRYLOV_BICGSTAB = 4, /* BiCGSTAB, right-preconditioned by a diagonal
                                  (Jacobi, l1-Jacobi, none): the reference's Ginkgo
                                  backend (src/ginkgo.cpp:55-64); short recurrences
                                  for unsymmetric operators -- seven vectors, two
                                  SpMVs and four sweeps per iteration; one shard or
                                  several; trust it with opts.verify = 1        */
+       LSB_KRYLOV_RICHARDSON = 5 }; /* AMG as the solver (LSB_PRECOND_AMG only, one shard):
+                                 stationary V-cycle iterations, the way the reference's AMG
+                                 backends run (src/hypre.c:185-186, src/amgx.c:78-85 --
+                                 maxit = 2, tol = 0 is their protocol).  x = 0, r = b; cycle
+                                 k: z = M^-1 r (one V-cycle, either smoother, fp64 or fp32),
+                                 q = S z, x += z, r -= q, iters = k, then stop: r.r <=
+                                 tol^2 b.b CONVERGED, r.r not finite BREAKDOWN, k >= maxit
+                                 MAXIT.  tol = 0 never converges: exactly maxit cycles.  x
+                                 and r stay fp64 (around the fp32 cycle: iterative
+                                 refinement); iters counts cycles, relres^(1/iters) is the
+                                 convergence factor per cycle; opts.verify as in PCG       */
 enum { LSB_SPMV_AUTO = 0,     /* pick by mean row length                    */
        LSB_SPMV_ADAPTIVE = 1, /* row-blocked: LDS-streamed short rows +
                                  wavefront-per-row long rows                */
@@ -199,7 +210,8 @@ struct lsb_hip_opts {
   int spmv_grid;     /* workgroup cap of the SpMV launch, 0 = tuned     [0] */
   int reorder;       /* 1: solve P S P^T with P = reverse Cuthill-McKee, permute
                         b, un-permute x (single shard)                  [0] */
-  int krylov;        /* LSB_KRYLOV_* (PCG, GMRES, PCG1, AUTO, BICGSTAB)  [AUTO] */
+  int krylov;        /* LSB_KRYLOV_* (PCG, GMRES, PCG1, AUTO, BICGSTAB,
+                        RICHARDSON)                                  [AUTO] */
   int restart;       /* GMRES restart length m, 1..32                  [30] */
   int verbose;
   int ngpus;         /* hip_cdna4_bench only: row-partition the operator over

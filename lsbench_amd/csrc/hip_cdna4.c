@@ -122,7 +122,8 @@ static const struct optchoice CH_COMM[] = {{"auto", LSB_COMM_AUTO}, {"rccl", LSB
 static const struct optchoice CH_KRYLOV[] = {{"cg", LSB_KRYLOV_PCG},     {"pcg", LSB_KRYLOV_PCG}, /* (alias) */
                                              {"cg1", LSB_KRYLOV_PCG1},   {"pcg1", LSB_KRYLOV_PCG1},
                                              {"auto", LSB_KRYLOV_AUTO},  {"gmres", LSB_KRYLOV_GMRES},
-                                             {"bicgstab", LSB_KRYLOV_BICGSTAB}, {NULL, 0}};
+                                             {"bicgstab", LSB_KRYLOV_BICGSTAB}, {"richardson", LSB_KRYLOV_RICHARDSON},
+                                             {NULL, 0}};
 static const struct optchoice CH_PRECISION[] = {{"fp64", LSB_PREC_FP64}, {"fp32", LSB_PREC_MIXED},
                                                 {"mixed", LSB_PREC_MIXED}, {NULL, 0}};
 #define OPT(n, t, f, c) {n, t, offsetof(struct lsb_hip_opts, f), c}

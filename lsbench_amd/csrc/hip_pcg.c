@@ -29,7 +29,7 @@
 enum pcg_form pcg_choose_form(const lsb_hip_solver *sv) {
   const struct shard *s = &sv->sh[0];
   const struct lsb_hip_opts *o = &sv->o;
-  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_BICGSTAB)
+  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_BICGSTAB || o->krylov == LSB_KRYLOV_RICHARDSON)
     return PCG_NONE;
   if (o->precond == LSB_PRECOND_FSAI && !sv->multi && !s->mixed && s->variant == LSB_SPMV_SUBWAVE &&
       s->fs_g.variant == LSB_SPMV_SUBWAVE && s->fs_gt.variant == LSB_SPMV_SUBWAVE && o->sample_spmv <= 0 &&
@@ -422,7 +422,7 @@ unsigned long long lsb_hip_solver_iteration_bytes(const lsb_hip_solver *sv) {
   const struct shard *s = &sv->sh[0];
   const unsigned long long sp = lsb_hip_solver_spmv_layout_bytes(sv), n8 = 8ull * s->n;
   const unsigned vec = s->dinv_uniform ? 0u : 1u;
-  if (!sp || s->mixed || sv->ps.use)
+  if (!sp || s->mixed || sv->ps.use || sv->o.krylov == LSB_KRYLOV_RICHARDSON) /* (a cycle: amg_cycle_bytes) */
     return 0;
   if (sv->o.krylov == LSB_KRYLOV_BICGSTAB)
     return 2 * sp + n8 * (18u + 2u * vec);
@@ -626,6 +626,7 @@ void drop_graphs(lsb_hip_solver *sv) {
       sv->gcache[i].exec = NULL;
     }
   mrhs_drop_graphs(sv);
+  richardson_drop_graphs(sv);
 }
 
 /*
@@ -962,6 +963,8 @@ int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
     return gmres_solve_dev(sv, d_b, d_x, res);
   if (sv->o.krylov == LSB_KRYLOV_BICGSTAB)
     return bicgstab_solve_dev(sv, d_b, d_x, res);
+  if (sv->o.krylov == LSB_KRYLOV_RICHARDSON)
+    return richardson_solve_dev(sv, d_b, d_x, res);
   const double t0 = wall_seconds();
   struct lsb_hip_result r;
   /* Mixed precision: the CG runs see S~ = fp32(S) (fp64 vectors and sums) and

@@ -355,6 +355,14 @@ static void amg_vcycle_f32(const struct shard *s, const double *d_r, double *d_z
   }
 }
 
+/* one V-cycle in the solver's precision, z wherever the caller wants it (the Richardson driver: the gather vector) */
+void amg_cycle(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st) {
+  if (s->amg->prec == LSB_AMG_PREC_FP32)
+    amg_vcycle_f32(s, d_r, d_z, st);
+  else
+    amg_vcycle(s, d_r, d_z, st);
+}
+
 /* The same cycle on a block of kp interleaved columns (hip_mrhs_amg.hip): the same step order and ping-pong
  * parity, so a column has the bits of amg_vcycle on it.  Always a launch per step: the one-launch tail is not
  * built for blocks (it is bitwise the same as its launches).  records: where the fine level's last sweep -- the
@@ -731,10 +739,7 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
   }
   if (sv->o.precond == LSB_PRECOND_AMG) { /* z = one V-cycle */
     struct shard *s = &sv->sh[0];
-    if (s->amg->prec == LSB_AMG_PREC_FP32)
-      amg_vcycle_f32(s, s->d_r, s->d_z, s->d_st);
-    else
-      amg_vcycle(s, s->d_r, s->d_z, s->d_st);
+    amg_cycle(s, s->d_r, s->d_z, s->d_st);
     return;
   }
   if (sv->o.precond == LSB_PRECOND_BLOCKJACOBI) {

@@ -707,6 +707,7 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
     o.precision = LSB_PREC_FP64;
   }
   bicgstab_check_precond(&o);
+  richardson_check(&o, 0);
   if (o.precision == LSB_PREC_MIXED && o.precond == LSB_PRECOND_AMG) {
     warnx("hip_cdna4: --precond amg runs in fp64");
     o.precision = LSB_PREC_FP64;
@@ -808,6 +809,7 @@ lsb_hip_solver *lsb_hip_solver_create_dist(const struct csr *A_rows,
       (o.krylov == LSB_KRYLOV_GMRES || o.krylov == LSB_KRYLOV_BICGSTAB || o.precond == LSB_PRECOND_AMG))
     o.precision = LSB_PREC_FP64; /* as in lsb_hip_solver_create */
   bicgstab_check_precond(&o);
+  richardson_check(&o, 1);
   const int P = lsb_hip_comm_size(), me = lsb_hip_comm_rank();
   lsb_hip_solver *sv = solver_alloc(1, &o);
   sv->n_glob = n_global, sv->n_here = sv->n_user = A_rows->nrows, sv->row_first = row_begin;
@@ -885,6 +887,7 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
     free(sv->p2p);
   }
   bicgstab_free(sv);
+  richardson_free(sv);
   mrhs_free(sv);
   shard_vec_free(&sv->sh[0], sv->d_bp), shard_vec_free(&sv->sh[0], sv->d_xp); /* shard 0's slab may hold them */
   for (int i = 0; i < sv->nshard; i++)

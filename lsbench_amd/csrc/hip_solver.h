@@ -10,6 +10,7 @@
  *   hip_pcg.c        PCG iteration forms (one chosen per solver) and the host loop
  *   hip_gmres_drv.c  GMRES(m) driver
  *   hip_bicgstab_drv.c  BiCGSTAB driver
+ *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
  *   hip_mrhs_drv.c   several right-hand sides: multi-RHS Jacobi- and AMG-PCG on a CSR SpMM
  * Nothing here is part of the C-ABI (include/lsbench_hip.h).
  */
@@ -60,7 +61,7 @@ struct halo_split {
 enum { SELL_NONE, SELL_32, SELL_16, SELL_TMPL, SELL_COL };
 /* the PCG iteration a solver runs (pcg_choose_form picks it once, at creation; hip_pcg.c) */
 enum pcg_form {
-  PCG_NONE,    /* GMRES, BiCGSTAB: no PCG iteration */
+  PCG_NONE,    /* GMRES, BiCGSTAB, Richardson: no PCG iteration */
   PCG_CLASSIC, /* SpMV, k_pcg_update_xr, k_pcg_update_p (one shard or many) */
   PCG_SUBWAVE, /* k_spmv_subwave_p + k_pcg_update_xr: the direction update rides in the next SpMV */
   PCG_COL,     /* k_pcg_col_px + k_pcg_col_r on the z-column plan (+ k_pcg_xfix at a run's end) */
@@ -285,6 +286,17 @@ struct lsb_hip_solver {
   } *bcg;
   double *bcg_red; /* nshard x BCG_RED doubles: the all-reduced dot products */
   struct lsb_bcg_state *bcg_hst; /* pinned, 2 slots */
+  /* Richardson (allocated on first use; hip_rich_drv.c): its vectors are the shard's own (r, q, the gather vector
+   * for z) and its state the shard's d_st, polled through h_st; what it owns is its cache of captured graphs */
+  struct rich_work {
+    struct {
+      hipGraphExec_t exec;
+      int cycles;
+      double *x;
+    } g[LSB_NGRAPH]; /* keyed on the count and on x, as gcache is */
+    int gnext;
+    unsigned nrr; /* partial count of the update sweep */
+  } *rich;
   /* several right-hand sides (allocated on first use, per batch width kp = 2, 4, 8; hip_mrhs_drv.c) */
   struct mrhs_work {
     unsigned kp;                 /* 0: not allocated */
@@ -420,6 +432,8 @@ LSB_INTERNAL void amg_vcycle_multi(const struct shard *s, unsigned kp, const str
                                    double *d_Z, double *records, unsigned *nrecords,
                                    const struct lsb_mrhs_state *st);
 LSB_INTERNAL void precond_free_shard(struct shard *s);
+/* z = one V-cycle on r in the solver's precision (fp64 or fp32 cycle), z anywhere; st: the gate of its launches */
+LSB_INTERNAL void amg_cycle(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st);
 /* ---- the fp32 V-cycle (hip_amg_f32.hip; driver: amg_vcycle_f32).  Modes, lanes, grids and the gate `st` as
  * hip_amg.hip's launchers.  in64: b is the caller's fp64 r, rounded once, the copy stored in b32 (else b is
  * float and b32 unused); y64 != NULL: the result goes there widened to double instead of to y (sweeps and
@@ -443,6 +457,26 @@ LSB_INTERNAL int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *
 LSB_INTERNAL int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
                                     struct lsb_hip_result *res);
 LSB_INTERNAL void bicgstab_free(lsb_hip_solver *sv); /* before the shards go: its vectors may sit in their slabs */
+/* hip_rich_drv.c, and the launchers of hip_rich.hip (n rows; the 16-byte form where every operand is 16-byte
+ * aligned, else the 8-byte form with the same bits; partials: one per workgroup, *npartials of them) */
+LSB_INTERNAL int richardson_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
+                                      struct lsb_hip_result *res);
+LSB_INTERNAL void richardson_free(lsb_hip_solver *sv); /* before the shards go */
+LSB_INTERNAL void richardson_drop_graphs(lsb_hip_solver *sv);
+/* what --krylov richardson cannot run with, refused at creation: a preconditioner other than AMG, shards, persistent */
+LSB_INTERNAL void richardson_check(const struct lsb_hip_opts *o, int sharded);
+LSB_INTERNAL void lsb_k_rich_init(unsigned n, const double *b, double *x, double *r, double *partials,
+                                  unsigned *npartials, void *stream);
+LSB_INTERNAL void lsb_k_rich_init_state(struct lsb_pcg_state *st, const double *parts, unsigned nparts, double tol,
+                                        int maxit, void *stream);
+LSB_INTERNAL void lsb_k_rich_update(unsigned n, const double *z, const double *q, double *x, double *r,
+                                    const struct lsb_pcg_state *st, double *partials, unsigned *npartials,
+                                    void *stream);
+LSB_INTERNAL void lsb_k_rich_step(struct lsb_pcg_state *st, const double *parts, unsigned nparts, void *stream);
+LSB_INTERNAL void lsb_k_rich_restart(unsigned n, const double *b, const double *ax, double *r, double *partials,
+                                     unsigned *npartials, void *stream);
+LSB_INTERNAL void lsb_k_rich_restart_state(struct lsb_pcg_state *st, const double *parts, unsigned nparts, int more,
+                                           void *stream);
 /* hip_mrhs_drv.c */
 LSB_INTERNAL void mrhs_free(lsb_hip_solver *sv); /* before the shards go */
 LSB_INTERNAL void mrhs_drop_graphs(lsb_hip_solver *sv);
