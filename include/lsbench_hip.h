@@ -247,7 +247,7 @@ struct lsb_hip_opts {
                         -1 = timed per solver at creation (tune_blas1_nt); else a mask
                         (bit 0 x, 1 p and q, 2 r in k_pcg_update_xr; 3 r, 4 p in
                         k_pcg_update_p; 5 k_cg1_update; 1 = all)              [-1] */
-  /* LSB_PRECOND_AMG (lsb_amg.c, hip_amg.hip) */
+  /* LSB_PRECOND_AMG (lsb_amg.c, hip_amg_drv.c, hip_amg.hip) */
   double amg_theta;  /* strength threshold: j strong for i when
                         |a_ij| >= theta sqrt(|a_ii a_jj|)                 [0.08] */
   int amg_sweeps;    /* l1-Jacobi sweeps before and after the coarse correction  [1] */

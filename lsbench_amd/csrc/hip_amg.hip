@@ -4,7 +4,7 @@
 //     x = M^-1 b;  (nu - 1) x  x += M^-1 (b - A x)
 //     r = b - A x;  b_c = R r;  recurse (the coarsest level: x_c = coarse_inv b_c)
 //     x += P x_c;  nu x  x += M^-1 (b - A x)
-// The hierarchy is built on the host at solver creation (lsb_amg.c); hip_precond.c uploads it and
+// The hierarchy is built on the host at solver creation (lsb_amg.c); hip_amg_drv.c uploads it and
 // enqueues the launches below.  Everything here is a row kernel over a CSR:
 //
 // k_amg_csr<L, MODE>  L lanes per row (a sub-wavefront of the wave64, per level and per matrix from

@@ -1,6 +1,6 @@
 // The Chebyshev smoother of the AMG V-cycle (opts.amg_smoother = LSB_AMG_SMOOTH_CHEB) on interleaved blocks of
 // KP = 2, 4 or 8 columns: hip_amg.hip's k_amg_cheb / k_amg_cheb_first in the layout and on the rounding rule of
-// hip_mrhs_amg.hip (driver: amg_vcycle_multi in hip_precond.c).  The rest of the cycle on blocks -- residual,
+// hip_mrhs_amg.hip (driver: amg_cycle in hip_amg_drv.c).  The rest of the cycle on blocks -- residual,
 // restriction, prolongation, the dense coarse solve -- is hip_mrhs_amg.hip's, whatever the smoother.
 //
 // Rounding rule: per column exactly the single kernel's arithmetic -- lane l of a row's L takes entries

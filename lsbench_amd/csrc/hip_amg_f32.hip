@@ -1,5 +1,5 @@
 // The AMG V-cycle in fp32 (opts.amg_precision = LSB_AMG_PREC_FP32, --amg-precision fp32): hip_amg.hip's cycle --
-// the same steps, launch count, lane rule and ping-pong parity (driver: amg_vcycle_f32 in hip_precond.c) -- on a
+// the same steps, launch count, lane rule and ping-pong parity (driver: amg_cycle in hip_amg_drv.c) -- on a
 // hierarchy held in single precision, inside a Krylov loop that stays in fp64.  The cycle is bandwidth-bound and
 // only has to be a good approximate inverse, so it moves 8 B per stored entry and 4 B per vector element where
 // the fp64 cycle moves 12 B and 8 B.
@@ -19,8 +19,8 @@
 // one-level hierarchy) read the caller's fp64 r and round it ONCE to float -- the first step also stores that
 // copy, which every later step of the level reads -- and OUT64 kernels (the fine level's last post-smoothing
 // launch; that coarse solve) store their float result widened to double, which is exact, straight into z.  There
-// is no conversion launch at either end.  The Chebyshev coefficients are computed by the host in fp64, rounded to
-// float once at set-up and passed as kernel arguments (a captured graph keeps them).
+// is no conversion launch at either end.  The Chebyshev coefficients are computed by the host in fp64 at set-up and
+// rounded to float where they are passed as kernel arguments (a captured graph keeps them).
 //
 // Range: r is rounded to float UNSCALED.  Components beyond +-3.4e38 overflow to infinity and components below
 // about 1e-38 lose bits (subnormal) -- with b_i = i and tol 1e-12 the residual stays some 30 orders of magnitude
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(AMG32_WG) void k_amg32_dense(unsigned nc, const flo
 }
 
 // --------------------------------------------------------------------------
-// Launchers (C ABI; declared in hip_solver.h).  lanes: 2 .. 64, a power of two.
+// Launchers (C ABI; declared in lsb_impl.h).  lanes: 2 .. 64, a power of two.
 // --------------------------------------------------------------------------
 static unsigned amg32_grid(unsigned long long threads) {
   const unsigned long long g = (threads + AMG32_WG - 1) / AMG32_WG;
@@ -214,16 +214,15 @@ void lsb_k_amg32_first(unsigned n, int in64, const void *b, const float *minv, f
     k_amg32_first<false><<<amg32_grid(n), AMG32_WG, 0, s>>>(n, b, minv, x, b32, st);
 }
 
-void lsb_k_amg32_csr(int mode, unsigned rows, unsigned lanes, const int *offs, const unsigned long long *ent,
-                     const float *xin, const float *b, const float *minv, float *y, double *y64,
-                     const struct lsb_pcg_state *st, void *stream) {
-  if (!rows)
+void lsb_k_amg32_csr(int mode, const struct amg_mat32 *m, const float *xin, const float *b, const float *minv,
+                     float *y, double *y64, const struct lsb_pcg_state *st, void *stream) {
+  if (!m->rows)
     return;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned g = amg32_grid((unsigned long long)rows * lanes);
+  const unsigned g = amg32_grid((unsigned long long)m->rows * m->lanes);
   if (y64 && mode != LSB_AMG_SWEEP)
     errx(EXIT_FAILURE, "lsb_k_amg32_csr: only a sweep writes fp64");
-#define AMG32_GO(MM, O64) AMG32_LANES(lanes, (k_amg32_csr<L, MM, O64><<<g, AMG32_WG, 0, s>>>(rows, offs, ent, xin, b, minv, y, y64, st)))
+#define AMG32_GO(MM, O64) AMG32_LANES(m->lanes, (k_amg32_csr<L, MM, O64><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, minv, y, y64, st)))
   switch (mode) {
   case LSB_AMG_SWEEP:
     if (y64)
@@ -250,17 +249,16 @@ void lsb_k_amg32_cheb_first(unsigned n, int in64, const void *b, const float *di
     k_amg32_cheb_first<false><<<amg32_grid(n), AMG32_WG, 0, s>>>(n, b, dinv, c2, d, x, b32, st);
 }
 
-void lsb_k_amg32_cheb(unsigned rows, unsigned lanes, const int *offs, const unsigned long long *ent,
-                      const float *xin, const float *b, const float *dinv, float c1, float c2, float *d, float *y,
-                      double *y64, const struct lsb_pcg_state *st, void *stream) {
-  if (!rows)
+void lsb_k_amg32_cheb(const struct amg_mat32 *m, const float *xin, const float *b, const float *dinv, float c1,
+                      float c2, float *d, float *y, double *y64, const struct lsb_pcg_state *st, void *stream) {
+  if (!m->rows)
     return;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned g = amg32_grid((unsigned long long)rows * lanes);
+  const unsigned g = amg32_grid((unsigned long long)m->rows * m->lanes);
   if (y64)
-    AMG32_LANES(lanes, (k_amg32_cheb<L, true><<<g, AMG32_WG, 0, s>>>(rows, offs, ent, xin, b, dinv, c1, c2, d, y, y64, st)))
+    AMG32_LANES(m->lanes, (k_amg32_cheb<L, true><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, dinv, c1, c2, d, y, y64, st)))
   else
-    AMG32_LANES(lanes, (k_amg32_cheb<L, false><<<g, AMG32_WG, 0, s>>>(rows, offs, ent, xin, b, dinv, c1, c2, d, y, y64, st)))
+    AMG32_LANES(m->lanes, (k_amg32_cheb<L, false><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, dinv, c1, c2, d, y, y64, st)))
 }
 
 // ends64: a hierarchy of one level -- b is the caller's fp64 r, out its fp64 z; else both are float

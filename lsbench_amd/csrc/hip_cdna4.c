@@ -391,8 +391,7 @@ int lsb_hip_spmv_csr_f64(int variant, unsigned n, const int *d_offs,
     return 2;
   if (d_dot && (!d_work || !d_xdot))
     return 2;
-  unsigned L = pow2_ceil(mean_row_len ? mean_row_len : 1);
-  L = L < 2 ? 2 : (L > 64 ? 64 : L);
+  const unsigned L = row_lanes(mean_row_len);
 
   unsigned np = 0;
   if (variant == LSB_SPMV_SELL) {

@@ -1,6 +1,6 @@
 // Several right-hand sides under AMG: the V-cycle of hip_amg.hip on interleaved blocks of KP = 2, 4 or 8
-// columns, and the PCG sweeps of hip_mrhs.hip with z as a block of its own (drivers: amg_vcycle_multi in
-// hip_precond.c, hip_mrhs_drv.c).  An iteration is SpMM, k_amg_mrhs_update_xr, the cycle, k_amg_mrhs_update_p.
+// columns, and the PCG sweeps of hip_mrhs.hip with z as a block of its own (drivers: amg_cycle in
+// hip_amg_drv.c, hip_mrhs_drv.c).  An iteration is SpMM, k_amg_mrhs_update_xr, the cycle, k_amg_mrhs_update_p.
 //
 // Layout: hip_mrhs.hip's -- element (i, c) at i KP + c, 16-byte aligned -- on every level of the hierarchy.
 // Every matrix of the hierarchy (A, P, R of a level, the dense coarse inverse) is streamed once for all KP

@@ -22,7 +22,7 @@
  * p = D^-1 r, x kept, bb and the threshold unchanged, iterations counted on), all others stay frozen;
  * LSB_MAX_CORRECTIONS rounds at the most, a column that still misses is MAXIT.
  *
- * LSB_PRECOND_AMG: z = M^-1 r is one V-cycle on the block r (amg_vcycle_multi: every matrix of the hierarchy is
+ * LSB_PRECOND_AMG: z = M^-1 r is one V-cycle on the block r (amg_cycle at width kp: every matrix of the hierarchy is
  * streamed once for all columns, each column with the bits of the single-column cycle), so z is a block of its
  * own and an iteration is SpMM, k_amg_mrhs_update_xr, the cycle, k_amg_mrhs_update_p: the fine level's last
  * sweep leaves (r.z, r.r) of every column, there is no dot-product launch.  The cycle is gated on `running`
@@ -72,31 +72,10 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
   w->parts_pq = (double *)(w->mem + 5 * blk);
   w->parts2 = (double *)(w->mem + 5 * blk + ppq);
   w->st = (struct lsb_mrhs_state *)(w->mem + 5 * blk + ppq + pp2);
-  if (mrhs_amg(sv)) {
-    /* the blocks of the cycle: z, level 0's second smoothing buffer and residual, four vectors per coarser level */
-    const struct amg_dev *a = s->amg;
-    size_t total = 3 * blk, off = 3 * blk;
-    for (unsigned l = 1; l < a->nlev; l++)
-      total += (4 * (size_t)a->lv[l].n * kp * sizeof(double) + 255) & ~(size_t)255;
-    const size_t doff = total; /* the Chebyshev smoother's direction blocks, behind everything an l1 solver has */
-    for (unsigned l = 0; a->cheb && l + 1 < a->nlev; l++)
-      total += ((size_t)a->lv[l].n * kp * sizeof(double) + 255) & ~(size_t)255;
-    w->amg_mem = (char *)lsb_hip_malloc(total);
-    LSB_CHK_HIP(hipMemsetAsync(w->amg_mem, 0, total, g_stream));
-    w->av = lsb_calloc(struct amg_mvec, a->nlev);
+  if (mrhs_amg(sv)) { /* z and the blocks of the cycle's vectors */
+    w->av = lsb_calloc(struct amg_vecs, s->amg->nlev);
+    w->amg_mem = amg_block_vecs(s->amg, kp, w->av);
     w->z = (double *)w->amg_mem;
-    w->av[0].tmp = (double *)(w->amg_mem + blk), w->av[0].r = (double *)(w->amg_mem + 2 * blk);
-    for (unsigned l = 1; l < a->nlev; l++) {
-      const size_t nl = (size_t)a->lv[l].n * kp;
-      double *buf = (double *)(w->amg_mem + off);
-      w->av[l].b = buf, w->av[l].out = buf + nl, w->av[l].tmp = buf + 2 * nl, w->av[l].r = buf + 3 * nl;
-      off += (4 * nl * sizeof(double) + 255) & ~(size_t)255;
-    }
-    off = doff;
-    for (unsigned l = 0; a->cheb && l + 1 < a->nlev; l++) {
-      w->av[l].d = (double *)(w->amg_mem + off);
-      off += ((size_t)a->lv[l].n * kp * sizeof(double) + 255) & ~(size_t)255;
-    }
   }
   w->kp = kp;
   return w;
@@ -157,6 +136,14 @@ static int mrhs_chunk(const lsb_hip_solver *sv, unsigned kp) {
   return c & ~1;
 }
 
+/* Z = one V-cycle on the block R of this width (records, nrecords, st: struct amg_run's) */
+static void mrhs_cycle(const lsb_hip_solver *sv, const struct mrhs_work *w, double *records, unsigned *nrecords,
+                       const struct lsb_mrhs_state *st) {
+  const struct amg_run c = {.a = sv->sh[0].amg, .vec = w->av, .kp = w->kp, .r = w->r, .z = w->z,
+                            .records = records, .nrecords = nrecords, .mst = st};
+  amg_cycle(&c);
+}
+
 static void spmm_shard(lsb_hip_solver *sv, struct mrhs_work *w, const double *x, double *y, const double *bres,
                        unsigned *npq, const struct lsb_mrhs_state *st) {
   const struct shard *s = &sv->sh[0];
@@ -170,7 +157,7 @@ static void mrhs_enqueue_iter(lsb_hip_solver *sv, struct mrhs_work *w, int parit
   spmm_shard(sv, w, w->p, w->q, NULL, &npq, w->st);
   if (mrhs_amg(sv)) {
     lsb_k_amg_mrhs_update_xr(w->kp, s->n, w->p, w->q, w->x, w->r, w->st, parity, w->parts_pq, npq, g_stream);
-    amg_vcycle_multi(s, w->kp, w->av, w->r, w->z, w->parts2, &np2, w->st);
+    mrhs_cycle(sv, w, w->parts2, &np2, w->st);
     lsb_k_amg_mrhs_update_p(w->kp, s->n, w->z, w->p, w->st, parity, w->parts2, np2, g_stream);
     return;
   }
@@ -277,7 +264,7 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
   lsb_k_mrhs_pack(n, kp, nb, sv->d_perm, d_B, ldb, w->b, g_stream);
   if (mrhs_amg(sv)) { /* x = 0, r = b ; z = M^-1 b ; p = z and (b.z, b.b) */
     lsb_k_amg_mrhs_init(kp, n, w->b, w->x, w->r, g_stream);
-    amg_vcycle_multi(s, kp, w->av, w->r, w->z, NULL, NULL, NULL);
+    mrhs_cycle(sv, w, NULL, NULL, NULL);
     lsb_k_amg_mrhs_init_p(kp, n, w->b, w->z, w->p, w->parts2, &np2, g_stream);
   } else
     lsb_k_mrhs_init(kp, n, w->b, DINV(s), w->x, w->r, w->p, w->parts2, &np2, g_stream);
@@ -297,7 +284,7 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
     spmm_shard(sv, w, w->x, w->q, w->b, &npq, NULL);
     if (mrhs_amg(sv)) { /* r = b - S x, z = M^-1 r, p = z and r.z, for the restarting columns */
       lsb_k_amg_mrhs_restart_r(kp, n, w->q, w->r, w->st, w->parts_pq, npq, more, g_stream);
-      amg_vcycle_multi(s, kp, w->av, w->r, w->z, NULL, NULL, NULL);
+      mrhs_cycle(sv, w, NULL, NULL, NULL);
       lsb_k_amg_mrhs_restart_p(kp, n, w->r, w->z, w->p, w->st, w->parts_pq, npq, more, w->parts2, &np2, g_stream);
     } else
       lsb_k_mrhs_restart(kp, n, w->q, DINV(s), w->r, w->p, w->st, w->parts_pq, npq, more, w->parts2, &np2, g_stream);
@@ -400,7 +387,7 @@ int lsb_hip_solver_precond_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const do
     const unsigned nb = nrhs - c0 < LSB_MRHS_MAX ? nrhs - c0 : LSB_MRHS_MAX;
     struct mrhs_work *w = mrhs_setup(sv, batch_width(nb));
     lsb_k_mrhs_pack(s->n, w->kp, nb, sv->d_perm, d_R + (size_t)c0 * ldr, ldr, w->r, g_stream);
-    amg_vcycle_multi(s, w->kp, w->av, w->r, w->z, NULL, NULL, NULL);
+    mrhs_cycle(sv, w, NULL, NULL, NULL);
     lsb_k_mrhs_unpack(s->n, w->kp, nb, sv->d_perm, w->z, d_Z + (size_t)c0 * ldz, ldz, g_stream);
   }
   drain_stream(sv, "lsb_hip_solver_precond_multi_dev");

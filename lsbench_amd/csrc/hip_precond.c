@@ -1,6 +1,6 @@
 /*
  * Host side of the preconditioners that are not a diagonal scaling (kernels:
- * hip_precond_k.hip): set-up at solver creation
+ * hip_precond_k.hip; AMG: hip_amg_drv.c): set-up at solver creation
  * (untimed, like the reference's csr_init / CHOLMOD's factorisation,
  * src/cholmod-impl.h:25-26) and the launches of one application z = M^-1 r.
  */
@@ -12,418 +12,6 @@
 int generic_precond(const lsb_hip_solver *sv) {
   return sv->o.precond == LSB_PRECOND_CHEBYSHEV || sv->o.precond == LSB_PRECOND_BLOCKJACOBI ||
          sv->o.precond == LSB_PRECOND_FSAI || sv->o.precond == LSB_PRECOND_AMG;
-}
-
-/* ---- AMG: hierarchy on the host (lsb_amg.c), V-cycle on the device (hip_amg.hip) ------------ */
-static void *amg_keep(struct amg_dev *a, void *p) {
-  a->mem[a->nmem++] = p;
-  return p;
-}
-
-/* lanes per row from the mean row length, as fsai_upload_csr picks them */
-static struct lsb_amg_mat amg_upload_mat(struct amg_dev *a, const struct csr *M) {
-  struct lsb_amg_mat m;
-  const unsigned n = M->nrows;
-  const unsigned long long nnz = M->offs[n];
-  if (nnz > 0x7fffffffull)
-    errx(EXIT_FAILURE, "hip_cdna4: an AMG operator has %llu entries, more than 2^31 - 1", nnz);
-  m.rows = n;
-  m.offs = (const int *)amg_keep(a, dev_upload(M->offs, ((size_t)n + 1) * sizeof(unsigned)));
-  m.cols = (const int *)amg_keep(a, dev_upload(M->cols, (size_t)(nnz ? nnz : 1) * sizeof(unsigned)));
-  m.vals = (const double *)amg_keep(a, dev_upload(M->vals, (size_t)(nnz ? nnz : 1) * sizeof(double)));
-  const unsigned mean = n ? (unsigned)((nnz + n - 1) / n) : 1;
-  const unsigned L = pow2_ceil(mean ? mean : 1);
-  m.lanes = L < 2 ? 2 : (L > 64 ? 64 : L);
-  return m;
-}
-
-/* ---- the same hierarchy in fp32 (opts.amg_precision = LSB_AMG_PREC_FP32; kernels: hip_amg_f32.hip) ---- */
-/* offsets and packed {column, float} entries; the lanes by amg_upload_mat's rule; the fp64 values stay on the host */
-static struct amg_mat32 amg_upload_mat32(struct amg_dev *a, const struct csr *M, const char *what, unsigned l) {
-  struct amg_mat32 m;
-  const unsigned n = M->nrows;
-  const unsigned long long nnz = M->offs[n];
-  if (nnz > 0x7fffffffull)
-    errx(EXIT_FAILURE, "hip_cdna4: an AMG operator has %llu entries, more than 2^31 - 1", nnz);
-  unsigned long long *w = lsb_csr_pack_f32(M);
-  if (!w)
-    errx(EXIT_FAILURE, "hip_cdna4: --amg-precision fp32: an entry of %s on level %u is not finite in fp32; use "
-                       "--amg-precision fp64", what, l);
-  m.rows = n;
-  m.offs = (const int *)amg_keep(a, dev_upload(M->offs, ((size_t)n + 1) * sizeof(unsigned)));
-  m.ent = (const unsigned long long *)amg_keep(a, dev_upload(w, (size_t)(nnz ? nnz : 1) * sizeof *w));
-  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-  free(w);
-  const unsigned mean = n ? (unsigned)((nnz + n - 1) / n) : 1;
-  const unsigned L = pow2_ceil(mean ? mean : 1);
-  m.lanes = L < 2 ? 2 : (L > 64 ? 64 : L);
-  return m;
-}
-
-/* a float copy of cnt doubles on the device; refuses what does not fit */
-static float *amg_upload_f32(struct amg_dev *a, const double *v, size_t cnt, const char *what) {
-  float *f = (float *)malloc((cnt ? cnt : 1) * sizeof(float));
-  if (!f)
-    errx(EXIT_FAILURE, "hip_cdna4: out of host memory for the fp32 AMG hierarchy");
-  f[0] = 0.0f;
-  for (size_t i = 0; i < cnt; i++) {
-    f[i] = (float)v[i];
-    if (!isfinite(v[i]) || isinf(f[i]))
-      errx(EXIT_FAILURE, "hip_cdna4: --amg-precision fp32: an entry of %s is not finite in fp32; use "
-                         "--amg-precision fp64", what);
-  }
-  float *d = (float *)amg_keep(a, dev_upload(f, (cnt ? cnt : 1) * sizeof(float)));
-  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-  free(f);
-  return d;
-}
-
-/* level l of the fp32 hierarchy: its matrices, minv (the Chebyshev smoother: dinv, the coefficients rounded once
- * and the direction vector) and, below the fine level, its four vectors */
-static void amg_upload_level32(struct amg_dev *a, unsigned l, const struct lsb_amg_level *L, const double *minv,
-                               const struct amg_cheb *c) {
-  struct amg_lv32 *v = &a->lv32[l];
-  v->n = L->n;
-  v->A = amg_upload_mat32(a, L->A, "A", l);
-  if (L->P) {
-    v->P = amg_upload_mat32(a, L->P, "P", l);
-    v->R = amg_upload_mat32(a, L->R, "R", l);
-  }
-  v->minv = amg_upload_f32(a, minv, L->n, "the smoother's diagonal");
-  if (c && L->P) {
-    for (unsigned k = 0; k < a->nu; k++)
-      v->c1[k] = (float)c->c1[k], v->c2[k] = (float)c->c2[k];
-    v->d = (float *)amg_keep(a, lsb_hip_malloc((size_t)(L->n ? L->n : 1) * sizeof(float)));
-    LSB_CHK_HIP(hipMemsetAsync(v->d, 0, (size_t)(L->n ? L->n : 1) * sizeof(float), g_stream));
-  }
-  if (l > 0) {
-    float *buf = (float *)amg_keep(a, lsb_hip_malloc(4 * (size_t)L->n * sizeof(float)));
-    LSB_CHK_HIP(hipMemsetAsync(buf, 0, 4 * (size_t)L->n * sizeof(float), g_stream));
-    v->b = buf, v->out = buf + L->n, v->tmp = buf + 2 * (size_t)L->n, v->r = buf + 3 * (size_t)L->n;
-  }
-}
-
-static void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const double *vals,
-                              const struct lsb_hip_opts *o) {
-  if (s->row_begin != 0 || s->n != s->n_glob)
-    errx(EXIT_FAILURE, "hip_cdna4: --precond amg runs on one shard (the hierarchy couples all rows); use it "
-                       "without --ngpus / --nvirt");
-  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_PCG1 || o->krylov == LSB_KRYLOV_BICGSTAB)
-    errx(EXIT_FAILURE, "hip_cdna4: --precond amg runs under classic PCG (--krylov cg or auto), not %s",
-         o->krylov == LSB_KRYLOV_GMRES ? "gmres" : o->krylov == LSB_KRYLOV_PCG1 ? "cg1" : "bicgstab");
-  const double t0 = wall_seconds();
-  const unsigned n = s->n;
-  struct csr view = {n, 0, (unsigned *)offs, (unsigned *)cols, (double *)vals};
-  const unsigned coarse = o->amg_coarse < 1 ? 1u : (unsigned)o->amg_coarse;
-  const unsigned maxlev = o->amg_max_levels < 1 ? 1u : (o->amg_max_levels > 64 ? 64u : (unsigned)o->amg_max_levels);
-  struct lsb_amg_hier *h = lsb_amg_setup(&view, o->amg_theta, coarse, maxlev);
-  if (!h)
-    errx(EXIT_FAILURE, "hip_cdna4: cannot build the AMG hierarchy");
-  struct amg_dev *a = lsb_calloc(struct amg_dev, 1);
-  a->nlev = h->nlev, a->nc = h->nc;
-  a->nu = o->amg_sweeps < 1 ? 1u : (o->amg_sweeps > 16 ? 16u : (unsigned)o->amg_sweeps);
-  a->mem = lsb_calloc(void *, 13 * (size_t)h->nlev + 4);
-  a->lv = lsb_calloc(struct lsb_amg_lvdev, h->nlev);
-  const int cheb = o->amg_smoother == LSB_AMG_SMOOTH_CHEB;
-  const double ratio = o->amg_cheb_ratio >= 1.5 ? o->amg_cheb_ratio : 1.5;
-  if (o->amg_smoother != LSB_AMG_SMOOTH_L1JACOBI && !cheb)
-    errx(EXIT_FAILURE, "hip_cdna4: no AMG smoother %d (--amg-smoother l1 or cheb)", o->amg_smoother);
-  if (o->amg_precision != LSB_AMG_PREC_FP64 && o->amg_precision != LSB_AMG_PREC_FP32)
-    errx(EXIT_FAILURE, "hip_cdna4: no AMG precision %d (--amg-precision fp64 or fp32)", o->amg_precision);
-  const int f32 = o->amg_precision == LSB_AMG_PREC_FP32;
-  a->prec = o->amg_precision;
-  if (cheb)
-    a->cheb = lsb_calloc(struct amg_cheb, h->nlev);
-  if (f32)
-    a->lv32 = lsb_calloc(struct amg_lv32, h->nlev);
-  a->tail = h->nlev;
-  /* (the one-launch tail is not built for the Chebyshev smoother, nor for the fp32 cycle) */
-  for (unsigned l = 0; l < h->nlev && !cheb && !f32; l++)
-    if (o->amg_tail_rows > 0 && h->lv[l].n <= (unsigned)o->amg_tail_rows) {
-      a->tail = l;
-      break;
-    }
-  unsigned long long nnz0 = 0, nnzall = 0;
-  for (unsigned l = 0; l < h->nlev; l++) {
-    const struct lsb_amg_level *L = &h->lv[l];
-    struct lsb_amg_lvdev *v = &a->lv[l];
-    v->n = L->n;
-    if (!f32) {
-      v->A = amg_upload_mat(a, L->A);
-      if (L->P) {
-        v->P = amg_upload_mat(a, L->P);
-        v->R = amg_upload_mat(a, L->R);
-      }
-    }
-    double *minv = (double *)malloc((size_t)(L->n ? L->n : 1) * sizeof(double));
-    for (unsigned i = 0; i < L->n; i++) {
-      double sum = 0.0;
-      for (unsigned e = L->A->offs[i]; e < L->A->offs[i + 1]; e++)
-        sum += cheb ? (L->A->cols[e] == i ? L->A->vals[e] : 0.0) : fabs(L->A->vals[e]);
-      minv[i] = 1.0 / sum; /* > 0: lsb_amg_setup refused a diagonal <= 0 */
-    }
-    if (cheb && L->P) { /* the polynomial of degree nu on [rho / ratio, rho], rho the level's Gershgorin bound */
-      struct amg_cheb *c = &a->cheb[l];
-      c->hi = lsb_amg_gershgorin(L->A), c->lo = c->hi / ratio;
-      lsb_amg_cheb_coeffs(c->hi, ratio, a->nu, c->c1, c->c2);
-      if (!f32) {
-        c->d = (double *)amg_keep(a, lsb_hip_malloc((size_t)L->n * sizeof(double)));
-        LSB_CHK_HIP(hipMemsetAsync(c->d, 0, (size_t)L->n * sizeof(double), g_stream));
-      }
-    }
-    if (f32)
-      amg_upload_level32(a, l, L, minv, cheb ? &a->cheb[l] : NULL);
-    else
-      v->minv = (const double *)amg_keep(a, dev_upload(minv, (size_t)(L->n ? L->n : 1) * sizeof(double)));
-    LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-    free(minv);
-    if (l > 0 && !f32) { /* level 0: the caller's r and z; its two other vectors come out of the slab (precond_setup) */
-      double *buf = (double *)amg_keep(a, lsb_hip_malloc(4 * (size_t)L->n * sizeof(double)));
-      LSB_CHK_HIP(hipMemsetAsync(buf, 0, 4 * (size_t)L->n * sizeof(double), g_stream));
-      v->b = buf, v->out = buf + L->n, v->tmp = buf + 2 * (size_t)L->n, v->r = buf + 3 * (size_t)L->n;
-    }
-    nnzall += L->A->offs[L->n];
-    if (l == 0)
-      nnz0 = L->A->offs[L->n];
-    if (L->P) { /* A goes 2 nu times (nu - 1 sweeps, the residual, nu sweeps), P and R once; 6 nu + 5 vector passes */
-      a->cycle_mat_bytes += 12ull * (2ull * a->nu * L->A->offs[L->n] + L->P->offs[L->P->nrows] + L->R->offs[L->R->nrows]);
-      a->cycle_vec_rows += (6ull * a->nu + 5ull) * L->n;
-      if (cheb) /* d: written by both step 0s, read and written by the 2 (nu - 1) other steps */
-        a->cycle_vec_rows += (4ull * a->nu - 2ull) * L->n;
-    }
-  }
-  a->cycle_mat_bytes += 8ull * h->nc * h->nc;
-  a->cycle_vec_rows += 2ull * h->nc;
-  if (f32) { /* 8 B per entry, 4 nc^2, 4 B per element pass; level 0: r read and z written at 8 B, the copy of r written */
-    a->cycle_bytes32 = (a->cycle_mat_bytes - 8ull * h->nc * h->nc) / 3ull * 2ull + 4ull * h->nc * h->nc +
-                       4ull * a->cycle_vec_rows + (h->nlev > 1 ? 12ull * h->lv[0].n : 8ull * h->nc);
-    a->d_cinv32 = amg_upload_f32(a, h->coarse_inv, (size_t)h->nc * h->nc, "the coarse inverse");
-  } else
-    a->d_cinv = (double *)amg_keep(a, dev_upload(h->coarse_inv, (size_t)h->nc * h->nc * sizeof(double)));
-  {
-    const unsigned L = pow2_ceil(h->nc ? h->nc : 1);
-    a->clanes = L < 2 ? 2 : (L > 64 ? 64 : L);
-  }
-  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-  a->setup_s = wall_seconds() - t0;
-  if (o->verbose) {
-    for (unsigned l = 0; l < h->nlev; l++) {
-      const struct lsb_amg_level *L = &h->lv[l];
-      const unsigned la = f32 ? a->lv32[l].A.lanes : a->lv[l].A.lanes;
-      const unsigned lp = f32 ? a->lv32[l].P.lanes : a->lv[l].P.lanes;
-      const unsigned lr = f32 ? a->lv32[l].R.lanes : a->lv[l].R.lanes;
-      fprintf(stderr, "hip_cdna4: AMG level %u: %u rows, %u entries, %u lanes (A)", l, L->n, L->A->offs[L->n], la);
-      if (L->P && cheb)
-        fprintf(stderr, ", %u / %u lanes (P / R), Chebyshev on [%.4g, %.4g]\n", lp, lr, a->cheb[l].lo, a->cheb[l].hi);
-      else if (L->P)
-        fprintf(stderr, ", %u / %u lanes (P / R)\n", lp, lr);
-      else
-        fprintf(stderr, ", dense coarse inverse, %u lanes\n", a->clanes);
-    }
-    if (cheb)
-      fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u levels, Chebyshev smoother of degree %u "
-                      "(interval ratio %g), set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev, a->nu,
-              ratio, a->setup_s);
-    else
-      fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u of %u levels in the one-launch tail, %u l1-Jacobi "
-                      "sweep%s, set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev - a->tail, h->nlev,
-              a->nu, a->nu > 1 ? "s" : "", a->setup_s);
-    if (f32)
-      fprintf(stderr, "hip_cdna4: AMG V-cycle in fp32 (packed entries, float vectors): %llu bytes per application, "
-                      "%llu in fp64\n", a->cycle_bytes32, a->cycle_mat_bytes + 8ull * a->cycle_vec_rows);
-  }
-  lsb_amg_free(h);
-  s->amg = a;
-}
-
-/* level 0's second smoothing buffer and residual, out of the vector slab; the descriptors to the device */
-static void amg_finish_setup(struct shard *s) {
-  struct amg_dev *a = s->amg;
-  a->lv[0].tmp = shard_vec(s, s->n), a->lv[0].r = shard_vec(s, s->n);
-  LSB_CHK_HIP(hipMemsetAsync(a->lv[0].tmp, 0, (size_t)s->n * sizeof(double), g_stream));
-  LSB_CHK_HIP(hipMemsetAsync(a->lv[0].r, 0, (size_t)s->n * sizeof(double), g_stream));
-  if (a->lv32) { /* fp32: the same two slab vectors, split -- two ping-pong iterates, the copy of r, the residual */
-    struct amg_lv32 *v = &a->lv32[0];
-    v->tmp = (float *)a->lv[0].tmp, v->out = v->tmp + s->n;
-    v->b = (float *)a->lv[0].r, v->r = v->b + s->n;
-    LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-    return; /* (no one-launch tail: no descriptors on the device) */
-  }
-  a->d_lv = (struct lsb_amg_lvdev *)amg_keep(a, dev_upload(a->lv, (size_t)a->nlev * sizeof(struct lsb_amg_lvdev)));
-  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-}
-
-/* z = one V-cycle on r; the launches of levels above the tail, the tail (or the coarse solve).  Under the Chebyshev
- * smoother (a->cheb) a level's first step and its sweeps are the polynomial's steps: the same launch count and
- * ping-pong parity, d updated in place, and no tail. */
-static void amg_vcycle(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st) {
-  const struct amg_dev *a = s->amg;
-  const unsigned nu = a->nu, top = a->tail < a->nlev ? a->tail : a->nlev - 1;
-  for (unsigned l = 0; l < top; l++) {
-    const struct lsb_amg_lvdev *v = &a->lv[l];
-    const double *b = l ? v->b : d_r;
-    double *out = l ? v->out : d_z, *cur = v->tmp, *oth = out;
-    const struct amg_cheb *c = a->cheb ? &a->cheb[l] : NULL;
-    if (c)
-      lsb_k_amg_cheb_first(v->n, b, v->minv, c->c2[0], c->d, cur, st, g_stream);
-    else
-      lsb_k_amg_first(v->n, b, v->minv, cur, st, g_stream);
-    for (unsigned k = 1; k < nu; k++) {
-      if (c)
-        lsb_k_amg_cheb(&v->A, cur, b, v->minv, c->c1[k], c->c2[k], c->d, oth, st, g_stream);
-      else
-        lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
-      double *w = cur;
-      cur = oth, oth = w;
-    }
-    lsb_k_amg_csr(LSB_AMG_RESID, &v->A, cur, b, v->minv, v->r, st, g_stream);
-    lsb_k_amg_csr(LSB_AMG_SPMV, &v->R, v->r, NULL, NULL, a->lv[l + 1].b, st, g_stream);
-  }
-  if (a->tail < a->nlev)
-    lsb_k_amg_tail(a->d_lv, a->tail, a->nlev, nu, a->d_cinv, a->nc, a->clanes, d_r, d_z, st, g_stream);
-  else {
-    const unsigned c = a->nlev - 1;
-    lsb_k_amg_dense(a->nc, a->clanes, a->d_cinv, c ? a->lv[c].b : d_r, c ? a->lv[c].out : d_z, st, g_stream);
-  }
-  for (unsigned l = top; l-- > 0;) {
-    const struct lsb_amg_lvdev *v = &a->lv[l];
-    const double *b = l ? v->b : d_r;
-    double *out = l ? v->out : d_z;
-    double *cur = (nu - 1) % 2 ? out : v->tmp, *oth = (nu - 1) % 2 ? v->tmp : out;
-    const struct amg_cheb *c = a->cheb ? &a->cheb[l] : NULL;
-    lsb_k_amg_csr(LSB_AMG_ADDP, &v->P, a->lv[l + 1].out, NULL, NULL, cur, st, g_stream);
-    for (unsigned k = 0; k < nu; k++) { /* 2 nu - 1 out-of-place sweeps in all: the last one writes `out` */
-      if (c)
-        lsb_k_amg_cheb(&v->A, cur, b, v->minv, c->c1[k], c->c2[k], c->d, oth, st, g_stream);
-      else
-        lsb_k_amg_csr(LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, st, g_stream);
-      double *w = cur;
-      cur = oth, oth = w;
-    }
-  }
-}
-
-/* The cycle in fp32 (a->lv32; hip_amg_f32.hip): amg_vcycle's step order, launch count and ping-pong parity, never a
- * tail.  The fine level's first step reads the fp64 r and leaves its fp32 copy in lv32[0].b; the fine level's last
- * post-smoothing step writes the fp64 z.  A hierarchy of one level is the coarse solve alone, from r to z. */
-static void amg_vcycle_f32(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st) {
-  const struct amg_dev *a = s->amg;
-  const unsigned nu = a->nu, top = a->nlev - 1;
-  for (unsigned l = 0; l < top; l++) {
-    const struct amg_lv32 *v = &a->lv32[l];
-    float *cur = v->tmp, *oth = v->out;
-    const void *b0 = l ? (const void *)v->b : (const void *)d_r;
-    if (a->cheb)
-      lsb_k_amg32_cheb_first(v->n, l == 0, b0, v->minv, v->c2[0], v->d, cur, v->b, st, g_stream);
-    else
-      lsb_k_amg32_first(v->n, l == 0, b0, v->minv, cur, v->b, st, g_stream);
-    for (unsigned k = 1; k < nu; k++) {
-      if (a->cheb)
-        lsb_k_amg32_cheb(v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, v->c1[k], v->c2[k], v->d,
-                         oth, NULL, st, g_stream);
-      else
-        lsb_k_amg32_csr(LSB_AMG_SWEEP, v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, oth, NULL, st,
-                        g_stream);
-      float *w = cur;
-      cur = oth, oth = w;
-    }
-    lsb_k_amg32_csr(LSB_AMG_RESID, v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, v->r, NULL, st,
-                    g_stream);
-    lsb_k_amg32_csr(LSB_AMG_SPMV, v->R.rows, v->R.lanes, v->R.offs, v->R.ent, v->r, NULL, NULL, a->lv32[l + 1].b,
-                    NULL, st, g_stream);
-  }
-  if (top)
-    lsb_k_amg32_dense(a->nc, a->clanes, 0, a->d_cinv32, a->lv32[top].b, a->lv32[top].out, st, g_stream);
-  else
-    lsb_k_amg32_dense(a->nc, a->clanes, 1, a->d_cinv32, d_r, d_z, st, g_stream);
-  for (unsigned l = top; l-- > 0;) {
-    const struct amg_lv32 *v = &a->lv32[l];
-    float *cur = (nu - 1) % 2 ? v->out : v->tmp, *oth = (nu - 1) % 2 ? v->tmp : v->out;
-    lsb_k_amg32_csr(LSB_AMG_ADDP, v->P.rows, v->P.lanes, v->P.offs, v->P.ent, a->lv32[l + 1].out, NULL, NULL, cur,
-                    NULL, st, g_stream);
-    for (unsigned k = 0; k < nu; k++) { /* the last one writes `out` -- on the fine level z, widened */
-      double *z64 = l == 0 && k + 1 == nu ? d_z : NULL;
-      if (a->cheb)
-        lsb_k_amg32_cheb(v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, v->c1[k], v->c2[k], v->d,
-                         oth, z64, st, g_stream);
-      else
-        lsb_k_amg32_csr(LSB_AMG_SWEEP, v->A.rows, v->A.lanes, v->A.offs, v->A.ent, cur, v->b, v->minv, oth, z64, st,
-                        g_stream);
-      float *w = cur;
-      cur = oth, oth = w;
-    }
-  }
-}
-
-/* one V-cycle in the solver's precision, z wherever the caller wants it (the Richardson driver: the gather vector) */
-void amg_cycle(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st) {
-  if (s->amg->prec == LSB_AMG_PREC_FP32)
-    amg_vcycle_f32(s, d_r, d_z, st);
-  else
-    amg_vcycle(s, d_r, d_z, st);
-}
-
-/* The same cycle on a block of kp interleaved columns (hip_mrhs_amg.hip): the same step order and ping-pong
- * parity, so a column has the bits of amg_vcycle on it.  Always a launch per step: the one-launch tail is not
- * built for blocks (it is bitwise the same as its launches).  records: where the fine level's last sweep -- the
- * launch that writes Z -- leaves (r_c . z_c, r_c . r_c) of every column; a one-level hierarchy has no sweep and
- * forms them in a launch of their own. */
-void amg_vcycle_multi(const struct shard *s, unsigned kp, const struct amg_mvec *lv, const double *d_R, double *d_Z,
-                      double *records, unsigned *nrecords, const struct lsb_mrhs_state *st) {
-  const struct amg_dev *a = s->amg;
-  const unsigned nu = a->nu, top = a->nlev - 1;
-  for (unsigned l = 0; l < top; l++) {
-    const struct lsb_amg_lvdev *v = &a->lv[l];
-    const double *b = l ? lv[l].b : d_R;
-    double *out = l ? lv[l].out : d_Z, *cur = lv[l].tmp, *oth = out;
-    const struct amg_cheb *c = a->cheb ? &a->cheb[l] : NULL;
-    if (c)
-      lsb_k_amg_cheb_first_m(kp, v->n, b, v->minv, c->c2[0], lv[l].d, cur, st, g_stream);
-    else
-      lsb_k_amg_first_m(kp, v->n, b, v->minv, cur, st, g_stream);
-    for (unsigned k = 1; k < nu; k++) {
-      if (c)
-        lsb_k_amg_cheb_m(kp, &v->A, cur, b, v->minv, c->c1[k], c->c2[k], lv[l].d, oth, NULL, NULL, st, g_stream);
-      else
-        lsb_k_amg_csr_m(kp, LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, NULL, NULL, st, g_stream);
-      double *w = cur;
-      cur = oth, oth = w;
-    }
-    lsb_k_amg_csr_m(kp, LSB_AMG_RESID, &v->A, cur, b, v->minv, lv[l].r, NULL, NULL, st, g_stream);
-    lsb_k_amg_csr_m(kp, LSB_AMG_SPMV, &v->R, lv[l].r, NULL, NULL, lv[l + 1].b, NULL, NULL, st, g_stream);
-  }
-  lsb_k_amg_dense_m(kp, a->nc, a->clanes, a->d_cinv, top ? lv[top].b : d_R, top ? lv[top].out : d_Z, st, g_stream);
-  if (!top && records)
-    lsb_k_amg_dot2_m(kp, a->lv[0].n, d_R, d_Z, records, nrecords, st, g_stream);
-  for (unsigned l = top; l-- > 0;) {
-    const struct lsb_amg_lvdev *v = &a->lv[l];
-    const double *b = l ? lv[l].b : d_R;
-    double *out = l ? lv[l].out : d_Z;
-    double *cur = (nu - 1) % 2 ? out : lv[l].tmp, *oth = (nu - 1) % 2 ? lv[l].tmp : out;
-    lsb_k_amg_csr_m(kp, LSB_AMG_ADDP, &v->P, lv[l + 1].out, NULL, NULL, cur, NULL, NULL, st, g_stream);
-    for (unsigned k = 0; k < nu; k++) { /* the last one writes `out`; on level 0 it is the one with the records */
-      const int last = l == 0 && k + 1 == nu;
-      if (a->cheb)
-        lsb_k_amg_cheb_m(kp, &v->A, cur, b, v->minv, a->cheb[l].c1[k], a->cheb[l].c2[k], lv[l].d, oth,
-                         last ? records : NULL, last ? nrecords : NULL, st, g_stream);
-      else
-        lsb_k_amg_csr_m(kp, LSB_AMG_SWEEP, &v->A, cur, b, v->minv, oth, last ? records : NULL,
-                        last ? nrecords : NULL, st, g_stream);
-      double *w = cur;
-      cur = oth, oth = w;
-    }
-  }
-}
-
-static void amg_free(struct shard *s) {
-  struct amg_dev *a = s->amg;
-  if (!a)
-    return;
-  for (unsigned k = 0; k < a->nmem; k++)
-    lsb_hip_free(a->mem[k]);
-  shard_vec_free(s, a->lv[0].tmp), shard_vec_free(s, a->lv[0].r);
-  free(a->mem), free(a->lv), free(a->cheb), free(a->lv32), free(a);
-  s->amg = NULL;
 }
 
 /* ---- FSAI: G on the pattern of tril(S^k), rows by batched dense solves on the device ------- */
@@ -439,9 +27,7 @@ static void fsai_upload_csr(struct fsai_csr *c, unsigned n, const unsigned *offs
   c->vals = (double *)dev_upload(vals, (size_t)(nnz ? nnz : 1) * sizeof(double));
   /* launch-bound sizes: the sub-wavefront kernel; else the row-blocked one */
   struct csr view = {n, 0, (unsigned *)offs, NULL, NULL};
-  const unsigned mean = n ? (unsigned)((nnz + n - 1) / n) : 1;
-  unsigned L = pow2_ceil(mean ? mean : 1);
-  c->lanes = L < 2 ? 2 : (L > 64 ? 64 : L);
+  c->lanes = row_lanes(n ? (unsigned)((nnz + n - 1) / n) : 1);
   c->variant = nnz <= 2000000ull ? LSB_SPMV_SUBWAVE : LSB_SPMV_ADAPTIVE;
   unsigned *rb = NULL;
   c->nblk = lsb_csr_row_blocks(&view, LSB_BLOCK_NNZ, &rb);
@@ -738,8 +324,9 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
     return;
   }
   if (sv->o.precond == LSB_PRECOND_AMG) { /* z = one V-cycle */
-    struct shard *s = &sv->sh[0];
-    amg_cycle(s, s->d_r, s->d_z, s->d_st);
+    const struct shard *s = &sv->sh[0];
+    const struct amg_run c = {.a = s->amg, .vec = s->amg->vec, .r = s->d_r, .z = s->d_z, .st = s->d_st};
+    amg_cycle(&c);
     return;
   }
   if (sv->o.precond == LSB_PRECOND_BLOCKJACOBI) {
@@ -835,46 +422,6 @@ int lsb_hip_solver_precond_dev(lsb_hip_solver *sv, const double *d_r, double *d_
     lsb_k_perm_scatter(sv->n_here, sv->d_perm, sv->d_xp, d_z, g_stream);
   drain_stream(sv, "lsb_hip_solver_precond_dev");
   check_aux_status(sv, "lsb_hip_solver_precond_dev");
-  return 0;
-}
-
-int lsb_hip_solver_amg_info(lsb_hip_solver *sv, unsigned *levels, unsigned *tail_levels) {
-  if (!lsb_initialized)
-    return 1;
-  if (!sv || sv->o.precond != LSB_PRECOND_AMG || !sv->sh[0].amg)
-    return 2;
-  const struct amg_dev *a = sv->sh[0].amg;
-  if (levels)
-    *levels = a->nlev;
-  if (tail_levels)
-    *tail_levels = a->nlev - a->tail;
-  return 0;
-}
-
-int lsb_hip_solver_amg_precision(lsb_hip_solver *sv) {
-  if (!sv || sv->o.precond != LSB_PRECOND_AMG || !sv->sh[0].amg)
-    return 2;
-  return sv->sh[0].amg->prec;
-}
-
-unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *sv) {
-  if (!sv || sv->o.precond != LSB_PRECOND_AMG || !sv->sh[0].amg)
-    return 0;
-  const struct amg_dev *a = sv->sh[0].amg;
-  return a->prec == LSB_AMG_PREC_FP32 ? a->cycle_bytes32 : a->cycle_mat_bytes + 8ull * a->cycle_vec_rows;
-}
-
-int lsb_hip_solver_amg_cheb_interval(lsb_hip_solver *sv, unsigned level, double *lo, double *hi) {
-  if (!lsb_initialized)
-    return 1;
-  if (!sv || sv->o.precond != LSB_PRECOND_AMG || !sv->sh[0].amg || !sv->sh[0].amg->cheb ||
-      level + 1 >= sv->sh[0].amg->nlev)
-    return 2;
-  const struct amg_cheb *c = &sv->sh[0].amg->cheb[level];
-  if (lo)
-    *lo = c->lo;
-  if (hi)
-    *hi = c->hi;
   return 0;
 }
 

@@ -72,7 +72,8 @@ static int rich_chunk(const lsb_hip_solver *sv) {
 
 static void rich_enqueue_cycle(lsb_hip_solver *sv, double *d_x) {
   struct shard *s = &sv->sh[0];
-  amg_cycle(s, s->d_r, s->d_pfull, s->d_st);                               /* z = M^-1 r */
+  const struct amg_run c = {.a = s->amg, .vec = s->amg->vec, .r = s->d_r, .z = s->d_pfull, .st = s->d_st};
+  amg_cycle(&c);                                                           /* z = M^-1 r */
   spmv_shard(s, s->d_pfull, s->d_q, NULL, NULL, NULL, s->d_st);            /* q = S z */
   lsb_k_rich_update(s->n, s->d_pfull, s->d_q, d_x, s->d_r, s->d_st, s->d_parts2, &sv->rich->nrr, g_stream);
   lsb_k_rich_step(s->d_st, s->d_parts2, sv->rich->nrr, g_stream);

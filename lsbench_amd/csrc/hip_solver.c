@@ -7,13 +7,6 @@
 #include "hip_solver.h"
 #define NXCD_HOST 8u /* = NXCD of the kernels (hip_wg.h) */
 
-unsigned pow2_ceil(unsigned v) {
-  unsigned p = 1;
-  while (p < v)
-    p <<= 1;
-  return p;
-}
-
 /* SpMV kernel choice: rows of a few dozen non-zeros at most stream through
  * LDS (adaptive); long-row matrices go wavefront-per-row. */
 void choose_spmv(struct shard *s, const struct lsb_hip_opts *o) {
@@ -34,12 +27,7 @@ void choose_spmv(struct shard *s, const struct lsb_hip_opts *o) {
   if (v == LSB_SPMV_SELL && !s->sell.sptr)
     v = LSB_SPMV_ADAPTIVE; /* no sliced-ELL copy (32-bit offsets exceeded) */
   s->variant = v;
-  unsigned L = pow2_ceil(mean ? mean : 1);
-  if (L < 2)
-    L = 2;
-  if (L > 64)
-    L = 64;
-  s->lanes = L;
+  s->lanes = row_lanes(mean);
 }
 
 /* fp32 copy of a value array on the device; *exact &= "no value changed" */

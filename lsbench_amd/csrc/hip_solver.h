@@ -8,6 +8,8 @@
  *   hip_dist.c       what sharded solves add: exchange, all-reduce, overlap,
  *                    the direct xGMI path's set-up
  *   hip_pcg.c        PCG iteration forms (one chosen per solver) and the host loop
+ *   hip_precond.c    FSAI, block-Jacobi and the Chebyshev preconditioner: set-up and z = M^-1 r
+ *   hip_amg_drv.c    AMG: upload of the hierarchy, the V-cycle's one schedule (amg_cycle), its accessors
  *   hip_gmres_drv.c  GMRES(m) driver
  *   hip_bicgstab_drv.c  BiCGSTAB driver
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
@@ -70,13 +72,11 @@ enum pcg_form {
   PCG_FSAI3,   /* FSAI in three launches: k_spmv_subwave_p, k_fsai_xr_gr, k_fsai_gt_dots */
 };
 
-/* a matrix of the fp32 AMG hierarchy: int row offsets, one packed {column, float} word per stored entry
- * (lsb_csr_pack_f32), `lanes` per row by amg_upload_mat's rule.  A sibling of lsb_amg_mat, whose layout
- * k_amg_tail reads from the device. */
-struct amg_mat32 {
-  const int *offs;
-  const unsigned long long *ent;
-  unsigned rows, lanes;
+/* The vectors of one level of the AMG V-cycle: right-hand side, result, the other smoothing buffer, the residual, the
+ * Chebyshev smoother's direction (NULL under l1-Jacobi).  double in the fp64 cycle (one column: amg_dev.vec; blocks of
+ * kp: mrhs_work.av), float in the fp32 cycle.  Level 0 under fp64: b and out are NULL, the caller's r and z stand in */
+struct amg_vecs {
+  void *b, *out, *tmp, *r, *d;
 };
 
 struct shard {
@@ -197,36 +197,33 @@ struct shard {
   double *d_fst;     /* t = G r */
   double *d_r1;      /* the three-launch iteration's second residual buffer (form_vecs) */
   unsigned fs_maxrow; /* longest row of the pattern */
-  /* AMG (LSB_PRECOND_AMG): the hierarchy on the device, z = one V-cycle (hip_amg.hip) */
+  /* AMG (PRECOND_AMG): the hierarchy on the device, z = one V-cycle (hip_amg_drv.c; hip_amg.hip, hip_amg_f32.hip) */
   struct amg_dev {
     unsigned nlev, tail, nu, nc, clanes; /* tail: first level of the one-launch tail (nlev: none) */
-    struct lsb_amg_lvdev *lv, *d_lv;     /* descriptors: host copy, device copy */
-    double *d_cinv;                      /* nc x nc coarse inverse */
+    int prec, cheb;                      /* LSB_AMG_PREC_*; opts.amg_smoother == LSB_AMG_SMOOTH_CHEB */
+    /* a level, in the solver's precision: its matrices (.d fp64, .f fp32: packed entries), minv (double or float;
+     * the Chebyshev smoother: 1 / a_ii) and, per smoothed level under that smoother, the interval of D^-1 A and
+     * the coefficients of its nu steps (lsb_amg_cheb_coeffs; the fp32 launches round them) */
+    struct amg_lv {
+      unsigned n;
+      union amg_mat {
+        struct lsb_amg_mat d;
+        struct amg_mat32 f;
+      } A, P, R;
+      const void *minv;
+      double lo, hi, c1[16], c2[16];
+    } *lv;
+    /* the single-column cycle's vectors.  Level 0's come out of the vector slab: under fp64 tmp and r; under fp32
+     * the same two slab vectors split in halves -- tmp | out, and b (the fp32 copy of the caller's r) | r */
+    struct amg_vecs *vec;
+    struct lsb_amg_lvdev *d_lv;          /* fp64: the levels as k_amg_tail reads them */
+    void *d_cinv;                        /* nc x nc coarse inverse, double or float */
     void **mem;                          /* every allocation of the hierarchy */
     unsigned nmem;
     double setup_s;
     /* what one cycle streams, for the poll interval of a batch of right-hand sides: the bytes of its matrices
      * and its vector passes in rows (summed over the levels) */
     unsigned long long cycle_mat_bytes, cycle_vec_rows;
-    /* opts.amg_smoother = LSB_AMG_SMOOTH_CHEB (NULL under l1-Jacobi): per smoothed level the interval of
-     * D^-1 A, the coefficients of its nu steps (lsb_amg_cheb_coeffs) and the direction vector d */
-    struct amg_cheb {
-      double lo, hi, c1[16], c2[16];
-      double *d;
-    } *cheb;
-    /* opts.amg_precision = LSB_AMG_PREC_FP32 (lv32 NULL under fp64): the hierarchy in single precision as
-     * hip_amg_f32.hip's kernels see it -- packed matrices, float minv / dinv, coarse inverse, level vectors and
-     * Chebyshev direction, the coefficients rounded once.  Level 0's four vectors are the two slab vectors
-     * lv[0].tmp and lv[0].r split in halves; lv[] then holds the row counts and nothing else of the matrices. */
-    int prec;
-    struct amg_lv32 {
-      unsigned n;
-      struct amg_mat32 A, P, R;
-      const float *minv;
-      float *b, *out, *tmp, *r; /* level 0's b: the fp32 copy of the caller's r */
-      float *d, c1[16], c2[16];
-    } *lv32;
-    float *d_cinv32;
     unsigned long long cycle_bytes32; /* what lsb_hip_solver_amg_cycle_bytes answers under fp32 */
   } *amg;
   struct lsb_xfer *recv, *send;
@@ -308,10 +305,7 @@ struct lsb_hip_solver {
      * are the r and z of the call) */
     char *amg_mem;
     double *z;
-    struct amg_mvec {
-      double *b, *out, *tmp, *r;
-      double *d; /* the Chebyshev smoother's direction block (NULL under l1-Jacobi) */
-    } *av;
+    struct amg_vecs *av; /* (amg_block_vecs) */
     unsigned hint[LSB_MAX_CORRECTIONS + 1]; /* launches the previous batch's solve and restarts took */
     struct {
       hipGraphExec_t exec;
@@ -357,6 +351,14 @@ struct lsb_hip_solver {
   double p2p_us, rccl_us; /* self-test: one exchange + all-reduce, each way */
 };
 
+/* lanes per row of the row kernels from a mean row length: the next power of two, 2 .. 64 */
+static inline unsigned row_lanes(unsigned len) {
+  unsigned L = 2;
+  while (L < len && L < 64)
+    L <<= 1;
+  return L;
+}
+
 /* hip_fsai.hip */
 void lsb_k_fsai_rows(const unsigned *rows, unsigned nrows, unsigned mcap, const int *offs, const int *cols,
                      const double *vals, unsigned row_begin, const unsigned *poffs, const unsigned *pcols,
@@ -378,7 +380,6 @@ LSB_INTERNAL void drain_stream(lsb_hip_solver *sv, const char *what);
 LSB_INTERNAL void wait_event(lsb_hip_solver *sv, hipEvent_t ev, const char *what);
 LSB_INTERNAL void *dev_upload(const void *h, size_t bytes);
 /* hip_solver.c */
-LSB_INTERNAL unsigned pow2_ceil(unsigned v);
 LSB_INTERNAL double *shard_vec(struct shard *s, size_t count);
 LSB_INTERNAL void shard_vec_free(struct shard *s, void *p);
 LSB_INTERNAL void sell_launch(struct shard *s, unsigned s0, unsigned ns, const double *xfull, double *y,
@@ -426,30 +427,29 @@ LSB_INTERNAL void precond_shard_blocks(struct shard *s, const int *offs, const i
                                        const double *vals, const struct lsb_hip_opts *o);
 LSB_INTERNAL void precond_setup(lsb_hip_solver *sv);
 LSB_INTERNAL void precond_apply(lsb_hip_solver *sv, int after_update);
-/* Z = one V-cycle on the block R of kp interleaved columns (lv: the levels' vectors at that width); records != NULL:
- * the records (r_c . z_c, r_c . r_c) and their number; st: the gate of the launches, NULL: always run */
-LSB_INTERNAL void amg_vcycle_multi(const struct shard *s, unsigned kp, const struct amg_mvec *lv, const double *d_R,
-                                   double *d_Z, double *records, unsigned *nrecords,
-                                   const struct lsb_mrhs_state *st);
 LSB_INTERNAL void precond_free_shard(struct shard *s);
-/* z = one V-cycle on r in the solver's precision (fp64 or fp32 cycle), z anywhere; st: the gate of its launches */
-LSB_INTERNAL void amg_cycle(const struct shard *s, const double *d_r, double *d_z, const struct lsb_pcg_state *st);
-/* ---- the fp32 V-cycle (hip_amg_f32.hip; driver: amg_vcycle_f32).  Modes, lanes, grids and the gate `st` as
- * hip_amg.hip's launchers.  in64: b is the caller's fp64 r, rounded once, the copy stored in b32 (else b is
- * float and b32 unused); y64 != NULL: the result goes there widened to double instead of to y (sweeps and
- * Chebyshev steps only); ends64: a one-level hierarchy's coarse solve, fp64 r to fp64 z. */
-void lsb_k_amg32_first(unsigned n, int in64, const void *b, const float *minv, float *x, float *b32,
-                       const struct lsb_pcg_state *st, void *stream);
-void lsb_k_amg32_csr(int mode, unsigned rows, unsigned lanes, const int *offs, const unsigned long long *ent,
-                     const float *xin, const float *b, const float *minv, float *y, double *y64,
-                     const struct lsb_pcg_state *st, void *stream);
-void lsb_k_amg32_cheb_first(unsigned n, int in64, const void *b, const float *dinv, float c2, float *d, float *x,
-                            float *b32, const struct lsb_pcg_state *st, void *stream);
-void lsb_k_amg32_cheb(unsigned rows, unsigned lanes, const int *offs, const unsigned long long *ent,
-                      const float *xin, const float *b, const float *dinv, float c1, float c2, float *d, float *y,
-                      double *y64, const struct lsb_pcg_state *st, void *stream);
-void lsb_k_amg32_dense(unsigned nc, unsigned lanes, int ends64, const float *cinv, const void *b, void *out,
-                       const struct lsb_pcg_state *st, void *stream);
+/* hip_amg_drv.c */
+LSB_INTERNAL void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const double *vals,
+                                    const struct lsb_hip_opts *o);
+LSB_INTERNAL void amg_finish_setup(struct shard *s); /* behind d_zfull: level 0's two vectors out of the slab */
+LSB_INTERNAL void amg_free(struct shard *s);
+/* One application of the V-cycle, described on the caller's stack: z = M^-1 r in the solver's precision (kp = 0: one
+ * column, vec = a->vec) or Z = M^-1 R on interleaved blocks of kp columns (fp64; vec = the mrhs_work's).  r and z are
+ * fp64 and may be anywhere.  records != NULL (blocks): where the launch that writes Z leaves (r_c . z_c, r_c . r_c) of
+ * every column, and their number.  The gate of the launches: st (one column) or mst (blocks), NULL: always run. */
+struct amg_run {
+  const struct amg_dev *a;
+  const struct amg_vecs *vec;
+  unsigned kp, *nrecords;
+  const double *r;
+  double *z, *records;
+  const struct lsb_pcg_state *st;
+  const struct lsb_mrhs_state *mst;
+};
+LSB_INTERNAL void amg_cycle(const struct amg_run *c);
+/* the cycle's vectors at width kp, zeroed: 256-byte aligned pieces of one allocation, which it returns -- Z, level 0's
+ * tmp and r, four vectors per coarser level, then the Chebyshev smoother's direction blocks; fills v[0 .. nlev) */
+LSB_INTERNAL char *amg_block_vecs(const struct amg_dev *a, unsigned kp, struct amg_vecs *v);
 /* hip_gmres_drv.c */
 LSB_INTERNAL int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
                                  struct lsb_hip_result *res);

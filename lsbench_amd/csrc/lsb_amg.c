@@ -1,5 +1,5 @@
 /*
- * Smoothed-aggregation AMG hierarchy (LSB_PRECOND_AMG; hip_precond.c applies it through
+ * Smoothed-aggregation AMG hierarchy (LSB_PRECOND_AMG; hip_amg_drv.c applies it through
  * hip_amg.hip).  Host set-up, untimed, like FSAI's and CHOLMOD's factorisation
  * (src/cholmod-impl.h:25-26).  The rules are fixed so that a test restates them exactly:
  *

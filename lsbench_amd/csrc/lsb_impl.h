@@ -389,7 +389,7 @@ void lsb_p2p_test_setvals(double *d_v, int me, unsigned round, void *stream);
 void lsb_p2p_test_checkvals(const double *d_v, int R, unsigned round, unsigned *d_bad,
                             void *stream);
 
-/* ---- smoothed-aggregation AMG V-cycle (hip_amg.hip; set-up lsb_amg.c, hip_precond.c) ----
+/* ---- smoothed-aggregation AMG V-cycle (hip_amg.hip; set-up lsb_amg.c, hip_amg_drv.c) ----
  * One level as the kernels see it.  A CSR of the level: int offsets and columns (all < 2^31),
  * `lanes` per row (2..64, from the mean row length), `rows` of them. */
 struct lsb_amg_mat {
@@ -397,6 +397,14 @@ struct lsb_amg_mat {
   const double *vals;
   unsigned rows, lanes;
 };
+/* its sibling in the fp32 hierarchy (hip_amg_f32.hip): one packed {column, float} word per stored entry
+ * (lsb_csr_pack_f32).  A struct of its own: k_amg_tail reads lsb_amg_mat's layout from the device. */
+struct amg_mat32 {
+  const int *offs;
+  const unsigned long long *ent;
+  unsigned rows, lanes;
+};
+/* a level as k_amg_tail reads it from the device, and nothing more (the host's description: hip_solver.h) */
 struct lsb_amg_lvdev {
   unsigned n, pad_;
   struct lsb_amg_mat A, P, R; /* P: n rows, R: the next level's n rows (none on the coarsest) */
@@ -465,6 +473,21 @@ void lsb_k_amg_cheb_first_m(unsigned kp, unsigned n, const double *b, const doub
 void lsb_k_amg_cheb_m(unsigned kp, const struct lsb_amg_mat *m, const double *xin, const double *b,
                       const double *dinv, double c1, double c2, double *d, double *y, double *records,
                       unsigned *nrecords, const struct lsb_mrhs_state *st, void *stream);
+
+/* ---- the fp32 V-cycle (hip_amg_f32.hip).  Modes, lanes, grids and the gate `st` as hip_amg.hip's launchers.
+ * in64: b is the caller's fp64 r, rounded once, the copy stored in b32 (else b is float and b32 unused);
+ * y64 != NULL: the result goes there widened to double instead of to y (sweeps and Chebyshev steps only);
+ * ends64: a one-level hierarchy's coarse solve, fp64 r to fp64 z. */
+void lsb_k_amg32_first(unsigned n, int in64, const void *b, const float *minv, float *x, float *b32,
+                       const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_csr(int mode, const struct amg_mat32 *m, const float *xin, const float *b, const float *minv,
+                     float *y, double *y64, const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_cheb_first(unsigned n, int in64, const void *b, const float *dinv, float c2, float *d, float *x,
+                            float *b32, const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_cheb(const struct amg_mat32 *m, const float *xin, const float *b, const float *dinv, float c1,
+                      float c2, float *d, float *y, double *y64, const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_dense(unsigned nc, unsigned lanes, int ends64, const float *cinv, const void *b, void *out,
+                       const struct lsb_pcg_state *st, void *stream);
 
 /* ---- backend internals shared between hip_cdna4.c and hip_comm.c -------- */
 void *lsb_hip_stream(void);

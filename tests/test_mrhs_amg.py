@@ -1,5 +1,5 @@
 """Several right-hand sides under AMG: lsb_hip_solver_precond_multi_dev and solve_multi[_dev] on an AMG solver
-(hip_mrhs_amg.hip, amg_vcycle_multi in hip_precond.c, hip_mrhs_drv.c).
+(hip_mrhs_amg.hip, amg_cycle in hip_amg_drv.c, hip_mrhs_drv.c).
 
 The yardsticks: the single-column V-cycle of the same solver, byte for byte (a column of the block cycle does the
 single cycle's arithmetic); test_amg.py's numpy V-cycle and AMG-PCG with the bounds test_amg.py holds the single
