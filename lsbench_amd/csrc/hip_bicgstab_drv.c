@@ -6,9 +6,9 @@
  * Right-preconditioned BiCGSTAB, M^-1 = diag(dinv) (Jacobi, l1-Jacobi or none), x0 = 0, shadow
  * residual r^ = r0 = b (the iteration is written out at the head of
  * hip_bicgstab.hip).  Per iteration: two SpMVs with their fused dots (sigma = r^.v, ts = t.s) and four
- * sweeps.  The device decides when to stop (lsb_bcg_state); the host enqueues check_every iterations
- * at a time, one chunk ahead of the poll, as the PCG loop does.  Iterations are enqueued plainly:
- * the hipGraph helper of hip_pcg.c is keyed to the PCG forms and is not used here.
+ * sweeps.  The device decides when to stop (lsb_bcg_state); the host side is run_loop (hip_run.c) with
+ * check_every iterations per poll.  Iterations are enqueued plainly: replaying them from the graph cache
+ * (graph_launch) would be a change of behaviour that has not been measured.
  *
  * Vectors per shard: r (holds s between k_bcg_s and k_bcg_xr), v (the shard's q), t, p, r^, x, and
  * two gather vectors -- p^ = D^-1 p in the shard's own (d_pfull), s^ = D^-1 s in a second one.
@@ -19,7 +19,6 @@
  * taking the same decisions from the same all-reduced numbers.
  */
 #define BCG_RED 8 /* doubles per shard: [0] sigma [1] ss [2] ts [3] tt [4] rr (or b.b) [5] rho' */
-#define DINV(s) ((s)->dinv_uniform ? NULL : (s)->d_dinv), (s)->dinv_const
 
 #define EACH(i, s, w)                                                          \
   for (int i = 0; i < sv->nshard; i++)                                         \
@@ -27,12 +26,7 @@
       for (struct bcg_work *w = &sv->bcg[i]; w; w = NULL)
 
 static void bcg_allreduce(lsb_hip_solver *sv, unsigned off, unsigned cnt) {
-  if (!sv->multi)
-    return;
-  if (sv->dist)
-    lsb_hip_comm_allreduce_stream(sv->bcg_red + off, (int)cnt, g_stream);
-  else
-    lsb_k_vreduce(sv->bcg_red, BCG_RED, (unsigned)sv->nshard, off, cnt, g_stream);
+  red_allreduce(sv, sv->bcg_red, BCG_RED, off, cnt);
 }
 
 /* the halos of the second gather vector (s^) */
@@ -77,11 +71,9 @@ void bicgstab_free(lsb_hip_solver *sv) {
   LSB_CHK_HIP(hipHostFree(sv->bcg_hst));
 }
 
-/* Iterations per host poll, from numbers all ranks agree on.  The PCG loop's rule (auto_chunk: about 0.3 ms of
- * device work per chunk at an assumed 4 TB/s) with this iteration's bytes -- two SpMVs at 12 B per non-zero
- * and 28 vector passes counting the SpMVs' own -- and half its bounds, an iteration being two of PCG's.  An
- * estimate, not a measurement: the poll runs one chunk ahead, so the size only bounds the no-op launches
- * enqueued past the stop; opts.check_every overrides it. */
+/* Iterations per host poll, from numbers all ranks agree on: run_chunk with this iteration's bytes -- two SpMVs at
+ * 12 B per non-zero and 28 vector passes counting the SpMVs' own -- and half of PCG's bounds at twice its floor, an
+ * iteration being two of PCG's; opts.check_every overrides it. */
 static int bcg_chunk(const lsb_hip_solver *sv) {
   if (sv->o.check_every > 0)
     return sv->o.check_every;
@@ -89,11 +81,7 @@ static int bcg_chunk(const lsb_hip_solver *sv) {
   double bytes = 24.0 * (double)s->nnz + 224.0 * (double)s->n;
   if (sv->dist)
     bytes = 24.0 * (double)sv->agree_nnz + 224.0 * (double)sv->agree_n;
-  double us = bytes / 4.0e6;
-  if (us < 12.0)
-    us = 12.0;
-  const int c = (int)(300.0 / us);
-  return c < 4 ? 4 : c > 128 ? 128 : c;
+  return run_chunk(bytes, 12.0, 4, 128);
 }
 
 /* one iteration; parity = its number & 1 (which copy of rho it reads) */
@@ -143,56 +131,29 @@ static void bcg_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity) {
   }
 }
 
-/* Enqueue iterations until the device state leaves RUNNING; the final state lands in bcg_hst[0].
- * *it counts the iterations enqueued in this solve (its parity picks the copy of rho); *hint: what
- * this stretch of the previous solve took -- the benchmark protocol repeats the same solve --
- * enqueued in one go. */
-static void bcg_run(lsb_hip_solver *sv, double *d_x, unsigned *it, unsigned *hint) {
-  struct lsb_bcg_state *hst = sv->bcg_hst;
-  const int chunk = bcg_chunk(sv);
-  const int before = hst[0].c.iters; /* (0 for the solve proper: the caller clears it) */
-  unsigned done = 0;
-#define ENQUEUE_ITERS(count)                                                   \
-  do {                                                                         \
-    for (int i_ = 0; i_ < (count); i_++, (*it)++, done++)                      \
-      bcg_enqueue_iter(sv, d_x, (int)(*it & 1u));                              \
-  } while (0)
-#define ENQUEUE_POLL(slot)                                                     \
-  do {                                                                         \
-    LSB_CHK_HIP(hipMemcpyAsync(&hst[slot], sv->bcg[0].st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream)); \
-    LSB_CHK_HIP(hipEventRecord(sv->ev_poll[slot], g_stream));                  \
-  } while (0)
-  int fin = -1;
-  if (*hint > 0) {
-    ENQUEUE_ITERS((int)*hint);
-    ENQUEUE_POLL(0);
-    wait_event(sv, sv->ev_poll[0], "poll of a hinted BiCGSTAB solve");
-    if (hst[0].c.status != LSB_STATUS_RUNNING)
-      fin = 0;
-  }
-  if (fin < 0) {
-    int cur = 0;
-    ENQUEUE_ITERS(chunk);
-    ENQUEUE_POLL(0);
-    for (;;) {
-      ENQUEUE_ITERS(chunk); /* one chunk ahead of the poll */
-      ENQUEUE_POLL(cur ^ 1);
-      wait_event(sv, sv->ev_poll[cur], "poll of the BiCGSTAB solve");
-      if (hst[cur].c.status != LSB_STATUS_RUNNING) {
-        fin = cur;
-        break;
-      }
-      cur ^= 1;
-      if (done > sv->o.maxit + *hint + 3u * (unsigned)chunk) /* cannot happen */
-        errx(EXIT_FAILURE, "hip_cdna4: BiCGSTAB ran past maxit without a status");
-    }
-    drain_stream(sv, "drain after the BiCGSTAB solve"); /* the speculative chunk */
-  }
-#undef ENQUEUE_ITERS
-#undef ENQUEUE_POLL
-  if (fin != 0)
-    hst[0] = hst[fin];
-  *hint = (unsigned)(hst[0].c.iters - before);
+/* what run_loop enqueues: `it` counts the iterations enqueued in this solve (its parity picks the copy of rho) */
+struct bcg_enq {
+  lsb_hip_solver *sv;
+  double *d_x;
+  unsigned it;
+};
+static void bcg_enqueue(void *ctx, int count) {
+  struct bcg_enq *e = ctx;
+  for (int i = 0; i < count; i++, e->it++)
+    bcg_enqueue_iter(e->sv, e->d_x, (int)(e->it & 1u));
+}
+
+/* Enqueue iterations until the device state leaves RUNNING; the final state lands in bcg_hst[0] (whose c.iters
+ * the caller cleared for the solve proper).  *hint: what this stretch of the previous solve took. */
+static void bcg_run(lsb_hip_solver *sv, struct bcg_enq *e, unsigned *hint) {
+  const struct run_loop r = {.name = "BiCGSTAB", .d_state = sv->bcg[0].st, .h_state = sv->bcg_hst,
+                             .state_bytes = sizeof(struct lsb_bcg_state),
+                             .stop_off = offsetof(struct lsb_bcg_state, c.status),
+                             .progress_off = offsetof(struct lsb_bcg_state, c.iters),
+                             .enqueue = bcg_enqueue, .ctx = e, .chunk = bcg_chunk(sv), .cap = -1,
+                             .what_hinted = "poll of a hinted BiCGSTAB solve",
+                             .what_poll = "poll of the BiCGSTAB solve", .what_drain = "drain after the BiCGSTAB solve"};
+  run_loop(sv, &r, hint);
 }
 
 int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res) {
@@ -214,10 +175,11 @@ int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struc
   struct lsb_hip_result r;
   memset(&r, 0, sizeof r);
   r.true_relres = -1.0;
-  unsigned it = 0, nverify = 0;
+  struct bcg_enq enq = {.sv = sv, .d_x = d_x};
+  unsigned nverify = 0;
   hst[0].c.iters = 0;
   for (int round = 0;; round++) {
-    bcg_run(sv, d_x, &it, &sv->hint_iters[round < LSB_MAX_CORRECTIONS ? round : LSB_MAX_CORRECTIONS]);
+    bcg_run(sv, &enq, hint_slot(sv->hint_iters, round));
     if (!(sv->o.verify && hst[0].c.status == LSB_STATUS_CONVERGED && sv->o.tol > 0.0 && hst[0].c.bb > 0.0))
       break;
     /* "converged" is reported only for the residual RECOMPUTED from x; where that one misses the
@@ -251,9 +213,7 @@ int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struc
     r.corrections++;
   }
   check_aux_status(sv, "BiCGSTAB solve");
-  r.iters = (unsigned)hst[0].c.iters;
-  r.status = hst[0].c.status;
-  r.relres = hst[0].c.bb > 0.0 ? sqrt(hst[0].c.rr / hst[0].c.bb) : 0.0;
+  result_from_state(&r, &hst[0].c);
   r.spmvs = (unsigned)hst[0].nspmv + nverify;
   r.seconds = wall_seconds() - t0;
   if (res)

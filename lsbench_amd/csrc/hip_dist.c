@@ -111,6 +111,17 @@ void allreduce_scal(lsb_hip_solver *sv, unsigned off, unsigned cnt, int gated) {
     lsb_k_vreduce(sv->d_scal_all, SCAL_STRIDE, (unsigned)sv->nshard, off, cnt, g_stream);
 }
 
+/* the same over the plain path for a driver's own scalars (GMRES's gm_red, BiCGSTAB's bcg_red): one collective
+ * however many values -- the Gram-Schmidt coefficients of a step travel together */
+void red_allreduce(lsb_hip_solver *sv, double *red, unsigned stride, unsigned off, unsigned cnt) {
+  if (!sv->multi)
+    return;
+  if (sv->dist)
+    lsb_hip_comm_allreduce_stream(red + off, (int)cnt, g_stream);
+  else
+    lsb_k_vreduce(red, stride, (unsigned)sv->nshard, off, cnt, g_stream);
+}
+
 /* d_scal[0] <- all-reduced sum of the SpMV's dot partials; d_scal[1..cnt) are
  * all-reduced along with it */
 void allreduce_pq(lsb_hip_solver *sv, unsigned cnt, int with2) {

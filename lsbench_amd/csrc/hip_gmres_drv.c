@@ -10,16 +10,9 @@
  * estimate |g_{j+1}| <= tol ||b||; the host polls the state once per cycle.
  */
 #define GM_RED 96
-/* sum gm_red[q][off .. off+cnt) over the shards (of all ranks), result in every
- * shard's copy: one collective however many values -- the Gram-Schmidt
- * coefficients of a step travel together */
+/* sum gm_red[shard][off .. off+cnt) over the shards (of all ranks), result in every shard's copy */
 static void gm_allreduce(lsb_hip_solver *sv, unsigned off, unsigned cnt) {
-  if (!sv->multi)
-    return;
-  if (sv->dist)
-    lsb_hip_comm_allreduce_stream(sv->gm_red + off, (int)cnt, g_stream);
-  else
-    lsb_k_vreduce(sv->gm_red, GM_RED, (unsigned)sv->nshard, off, cnt, g_stream);
+  red_allreduce(sv, sv->gm_red, GM_RED, off, cnt);
 }
 
 int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,

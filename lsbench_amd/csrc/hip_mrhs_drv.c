@@ -13,9 +13,8 @@
  * start); more run in batches of 8 and a remainder; one column IS lsb_hip_solver_solve_dev.  The block
  * vectors b, x, r, p, q are internal (interleaved, internal numbering: k_mrhs_pack / k_mrhs_unpack apply the
  * permutation of a padded or re-ordered solver), so an iteration -- and a captured graph of iterations --
- * does not depend on the caller's pointers.  The device decides when to stop; the host enqueues
- * check_every iterations at a time, one chunk ahead of the poll, or the previous batch's count in one go,
- * as pcg_run does.
+ * does not depend on the caller's pointers.  The device decides when to stop; the host side is run_loop
+ * (hip_run.c): check_every iterations per poll, or the previous batch's count in one go.
  *
  * opts.verify: after the batch stops one SpMM recomputes b - S x of every column; the columns the recurrence
  * called converged but whose recomputed residual misses the tolerance restart IN PLACE (r = b - S x,
@@ -31,8 +30,6 @@
  * Served: one shard in one process, fp64 values, krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE / AMG.
  * Every other solver answers 2: nothing falls back to a loop of single solves.
  */
-#define DINV(s) ((s)->dinv_uniform ? NULL : (s)->d_dinv), (s)->dinv_const
-
 static int mrhs_serves(const lsb_hip_solver *sv) {
   const struct lsb_hip_opts *o = &sv->o;
   return !sv->multi && sv->nshard == 1 && !sv->dist && o->precision == LSB_PREC_FP64 &&
@@ -81,18 +78,9 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
   return w;
 }
 
-void mrhs_drop_graphs(lsb_hip_solver *sv) {
-  for (int k = 0; k < 3; k++)
-    for (int i = 0; i < LSB_NGRAPH; i++)
-      if (sv->mr[k].g[i].exec) {
-        LSB_CHK_HIP(hipGraphExecDestroy(sv->mr[k].g[i].exec));
-        sv->mr[k].g[i].exec = NULL;
-      }
-}
-
 void mrhs_free(lsb_hip_solver *sv) {
-  mrhs_drop_graphs(sv);
   for (int k = 0; k < 3; k++) {
+    graph_drop(&sv->mr[k].g);
     lsb_hip_free(sv->mr[k].mem), lsb_hip_free(sv->mr[k].amg_mem);
     free(sv->mr[k].av);
     memset(&sv->mr[k], 0, sizeof sv->mr[k]);
@@ -113,27 +101,20 @@ unsigned long long lsb_hip_solver_multi_iteration_bytes(const lsb_hip_solver *sv
   return 12ull * s->nnz + 4ull * (s->n + 1ull) + 8ull * s->n * (11ull * kp + (s->dinv_uniform ? 0u : 2u));
 }
 
-/* Iterations per host poll: pcg_run's rule (about 0.3 ms of device work at an assumed 4 TB/s) on this
- * iteration's bytes; even, so that a chunk leaves the parity where it found it.  An AMG solver: the same rule
- * on an estimate of the SpMM, the sweeps and the cycle (its matrices once per launch that streams them, its
- * vector passes per column), at least 2 where the diagonal preconditioners keep 8 -- an AMG iteration of a
- * large grid is milliseconds and a solve a few dozen of them, so a speculative chunk of 8 would be a
- * noticeable part of it. */
+/* Iterations per host poll: run_chunk on this iteration's bytes; even, so that a chunk leaves the parity where it
+ * found it.  An AMG solver: the same rule on an estimate of the SpMM, the sweeps and the cycle (its matrices once
+ * per launch that streams them, its vector passes per column), at least 2 where the diagonal preconditioners keep
+ * 8 -- an AMG iteration of a large grid is milliseconds and a solve a few dozen of them, so a speculative chunk of
+ * 8 would be a noticeable part of it. */
 static int mrhs_chunk(const lsb_hip_solver *sv, unsigned kp) {
   if (sv->o.check_every > 0)
     return (sv->o.check_every + 1) & ~1;
   const struct shard *s = &sv->sh[0];
   const int amg = mrhs_amg(sv);
-  double us = (double)lsb_hip_solver_multi_iteration_bytes(sv, kp) / 4.0e6;
+  double bytes = (double)lsb_hip_solver_multi_iteration_bytes(sv, kp);
   if (amg)
-    us = (double)(12ull * s->nnz + s->amg->cycle_mat_bytes + 8ull * kp * (11ull * s->n + s->amg->cycle_vec_rows)) /
-         4.0e6;
-  if (us < 6.0)
-    us = 6.0;
-  int c = (int)(300.0 / us);
-  const int lo = amg ? 2 : 8;
-  c = c < lo ? lo : c > 256 ? 256 : c;
-  return c & ~1;
+    bytes = (double)(12ull * s->nnz + s->amg->cycle_mat_bytes + 8ull * kp * (11ull * s->n + s->amg->cycle_vec_rows));
+  return run_chunk(bytes, 6.0, amg ? 2 : 8, 256) & ~1;
 }
 
 /* Z = one V-cycle on the block R of this width (records, nrecords, st: struct amg_run's) */
@@ -166,90 +147,37 @@ static void mrhs_enqueue_iter(lsb_hip_solver *sv, struct mrhs_work *w, int parit
   lsb_k_mrhs_update_p(w->kp, s->n, w->r, DINV(s), w->p, w->st, parity, w->parts2, np2, g_stream);
 }
 
-/* hipGraph of `iters` (even) iterations of this width: one linear chain on internal buffers, keyed on the count */
-static hipGraphExec_t mrhs_graph(lsb_hip_solver *sv, struct mrhs_work *w, int iters) {
-  for (int i = 0; i < LSB_NGRAPH; i++)
-    if (w->g[i].exec && w->g[i].iters == iters)
-      return w->g[i].exec;
-  const int slot = w->gnext;
-  w->gnext = (w->gnext + 1) % LSB_NGRAPH;
-  if (w->g[slot].exec)
-    LSB_CHK_HIP(hipGraphExecDestroy(w->g[slot].exec));
-  hipGraph_t g;
-  LSB_CHK_HIP(hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal));
+/* what run_loop enqueues: one linear chain on internal buffers, so its graphs are keyed on the count alone */
+struct mrhs_enq {
+  lsb_hip_solver *sv;
+  struct mrhs_work *w;
+};
+static void mrhs_enqueue_iters(void *ctx, int iters) {
+  const struct mrhs_enq *e = ctx;
   for (int i = 0; i < iters; i++)
-    mrhs_enqueue_iter(sv, w, i & 1);
-  LSB_CHK_HIP(hipStreamEndCapture(g_stream, &g));
-  LSB_CHK_HIP(hipGraphInstantiate(&w->g[slot].exec, g, NULL, NULL, 0));
-  LSB_CHK_HIP(hipGraphDestroy(g));
-  w->g[slot].iters = iters;
-  return w->g[slot].exec;
+    mrhs_enqueue_iter(e->sv, e->w, i & 1);
+}
+static void mrhs_enqueue(void *ctx, int iters) {
+  const struct mrhs_enq *e = ctx;
+  if (e->sv->o.use_graph)
+    graph_launch(&e->w->g, iters, NULL, mrhs_enqueue_iters, ctx);
+  else
+    mrhs_enqueue_iters(ctx, iters);
 }
 
-/* Enqueue iterations until no column is running; the final state lands in mr_hst[0].  *hint: the launches
- * this stretch of the previous batch took, enqueued in one go. */
+/* Enqueue iterations until no column is running; the final state lands in mr_hst[0] (whose nspmm the caller cleared
+ * for the solve proper).  *hint: the launches this stretch of the previous batch took. */
 static void mrhs_run(lsb_hip_solver *sv, struct mrhs_work *w, unsigned *hint) {
-  struct lsb_mrhs_state *hst = sv->mr_hst;
-  const int chunk = mrhs_chunk(sv, w->kp);
-  const int use_graph = sv->o.use_graph;
-  const int before = hst[0].nspmm; /* (0 for the solve proper: the caller clears it) */
-  unsigned done = 0;
-#define ENQUEUE_ITERS(count)                                                   \
-  do {                                                                         \
-    const int cnt_ = (count);                                                  \
-    if (use_graph) {                                                           \
-      LSB_CHK_HIP(hipGraphLaunch(mrhs_graph(sv, w, cnt_), g_stream));          \
-    } else {                                                                   \
-      for (int i_ = 0; i_ < cnt_; i_++)                                        \
-        mrhs_enqueue_iter(sv, w, i_ & 1);                                      \
-    }                                                                          \
-    done += (unsigned)cnt_;                                                    \
-  } while (0)
-#define ENQUEUE_POLL(slot)                                                     \
-  do {                                                                         \
-    LSB_CHK_HIP(hipMemcpyAsync(&hst[slot], w->st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream)); \
-    LSB_CHK_HIP(hipEventRecord(sv->ev_poll[slot], g_stream));                  \
-  } while (0)
-  int fin = -1;
-  if (*hint > 0) {
-    /* graphs beyond ~1k iterations cost more to build than they save */
-    int first = (int)((*hint + 1) & ~1u);
-    while (use_graph && first > 1024)
-      first = ((first / 2) + 1) & ~1;
-    int left = (int)((*hint + 1) & ~1u);
-    while (left > 0) {
-      const int c = left < first ? ((left + 1) & ~1) : first;
-      ENQUEUE_ITERS(c);
-      left -= c;
-    }
-    ENQUEUE_POLL(0);
-    wait_event(sv, sv->ev_poll[0], "poll of a hinted batch");
-    if (!hst[0].running)
-      fin = 0;
-  }
-  if (fin < 0) {
-    int cur = 0;
-    ENQUEUE_ITERS(chunk);
-    ENQUEUE_POLL(0);
-    for (;;) {
-      ENQUEUE_ITERS(chunk); /* one chunk ahead of the poll */
-      ENQUEUE_POLL(cur ^ 1);
-      wait_event(sv, sv->ev_poll[cur], "poll of the batch");
-      if (!hst[cur].running) {
-        fin = cur;
-        break;
-      }
-      cur ^= 1;
-      if (done > sv->o.maxit + *hint + 1u + 3u * (unsigned)chunk) /* cannot happen */
-        errx(EXIT_FAILURE, "hip_cdna4: a batch of right-hand sides ran past maxit without a status");
-    }
-    drain_stream(sv, "drain after the batch"); /* the speculative chunk */
-  }
-#undef ENQUEUE_ITERS
-#undef ENQUEUE_POLL
-  if (fin != 0)
-    hst[0] = hst[fin];
-  *hint = (unsigned)(hst[0].nspmm - before);
+  struct mrhs_enq e = {sv, w};
+  const struct run_loop r = {.name = "a batch of right-hand sides", .d_state = w->st, .h_state = sv->mr_hst,
+                             .state_bytes = sizeof(struct lsb_mrhs_state),
+                             .stop_off = offsetof(struct lsb_mrhs_state, running), .stop_is_running = 1,
+                             .progress_off = offsetof(struct lsb_mrhs_state, nspmm),
+                             .enqueue = mrhs_enqueue, .ctx = &e, .chunk = mrhs_chunk(sv, w->kp), .even = 1,
+                             .max_piece = sv->o.use_graph ? 1024 : 0, .cap = -1,
+                             .what_hinted = "poll of a hinted batch", .what_poll = "poll of the batch",
+                             .what_drain = "drain after the batch"};
+  run_loop(sv, &r, hint);
 }
 
 /* one batch: nb <= 8 columns of the caller's blocks */
@@ -271,7 +199,7 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
   lsb_k_mrhs_init_state(kp, w->st, w->parts2, np2, sv->o.tol, (int)sv->o.maxit, g_stream);
   hst[0].nspmm = 0;
   for (int round = 0;; round++) {
-    mrhs_run(sv, w, &w->hint[round < LSB_MAX_CORRECTIONS ? round : LSB_MAX_CORRECTIONS]);
+    mrhs_run(sv, w, hint_slot(w->hint, round));
     if (!(sv->o.verify && sv->o.tol > 0.0))
       break;
     int any = 0;
@@ -299,12 +227,9 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
   drain_stream(sv, "un-packing the batch");
   const double seconds = wall_seconds() - t0;
   for (unsigned c = 0; c < nb; c++) {
-    const struct lsb_pcg_state *st = &hst[0].c[c];
     struct lsb_hip_result r;
     memset(&r, 0, sizeof r);
-    r.iters = (unsigned)st->iters;
-    r.status = st->status;
-    r.relres = st->bb > 0.0 ? sqrt(st->rr / st->bb) : 0.0;
+    result_from_state(&r, &hst[0].c[c]);
     r.true_relres = hst[0].true_relres[c];
     if (r.true_relres >= 0.0)
       r.relres = r.true_relres;

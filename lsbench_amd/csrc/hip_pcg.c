@@ -1,14 +1,10 @@
 /*
  * Jacobi-PCG on the device-resident state: the iteration forms a solver may run (one is chosen at
- * creation, pcg_choose_form), what each enqueues per iteration, and the host loop around them
- * ("Host loop").
+ * creation, pcg_choose_form), what each enqueues per iteration, and the solve around them: one run through the
+ * host loop the drivers share (hip_run.c; DESIGN.md section 4, "Host loop"), then the correction runs.
  */
 #define _GNU_SOURCE
 #include "hip_solver.h"
-
-/* the Jacobi diagonal as the fused sweeps take it: the vector, or (NULL, c) when
- * every entry is the same c -- then nobody reads 8 n bytes to learn it */
-#define DINV(s) ((s)->dinv_uniform ? NULL : (s)->d_dinv), (s)->dinv_const
 
 /* ------------------------------------------------------------------------ */
 /* PCG                                                                       */
@@ -440,57 +436,14 @@ unsigned long long lsb_hip_solver_iteration_bytes(const lsb_hip_solver *sv) {
 }
 
 int lsb_hip_solver_single_reduction(const lsb_hip_solver *sv) { return sv->form == PCG_CG1; }
+/* Iterations per host poll: run_chunk on the classic iteration's bytes (the SpMV at 12 B per non-zero, the sweeps'
+ * passes and the SpMV's own), at least 8, even */
 static int auto_chunk(const lsb_hip_solver *sv) {
-  /* aim at ~0.3 ms of device work per chunk (at least 8 iterations): the poll
-   * is pipelined one chunk ahead, so small chunks cost nothing while running
-   * and bound the no-op tail enqueued past convergence */
   const struct shard *s = &sv->sh[0];
   double bytes = 12.0 * (double)s->nnz + 108.0 * (double)s->n;
   if (sv->dist) /* must not depend on this rank's own shard size */
     bytes = 12.0 * (double)sv->agree_nnz + 108.0 * (double)sv->agree_n;
-  double us = bytes / 4.0e6; /* 4 TB/s => bytes per microsecond */
-  if (us < 6.0)
-    us = 6.0;
-  int c = (int)(300.0 / us);
-  if (c < 8)
-    c = 8;
-  if (c > 256)
-    c = 256;
-  return c & ~1;
-}
-
-/* Sharded solves wait for the device with a deadline: a collective that never
- * completes (a peer process died, ranks disagreeing on the sequence of calls)
- * must end this process with a message and a non-zero exit code, not hang the
- * node until somebody's job limit (opts.comm_deadline_s,
- * LSBENCH_HIP_COMM_DEADLINE_S).  One shard alone simply blocks. */
-#include <sched.h>
-void wait_event(lsb_hip_solver *sv, hipEvent_t ev, const char *what) {
-  if (!sv->multi || !(sv->o.comm_deadline_s > 0.0)) {
-    LSB_CHK_HIP(hipEventSynchronize(ev));
-    return;
-  }
-  const double t0 = wall_seconds();
-  for (;;) {
-    const hipError_t e = hipEventQuery(ev);
-    if (e == hipSuccess)
-      return;
-    if (e != hipErrorNotReady)
-      LSB_CHK_HIP(e);
-    if (wall_seconds() - t0 > sv->o.comm_deadline_s)
-      lsb_give_up("hip_cdna4: %s: the device did not get there within %.0f s -- a collective "
-                  "of the sharded solve is hung (rank %d of %d); giving up",
-                  what, sv->o.comm_deadline_s, lsb_hip_comm_rank(), lsb_hip_comm_size());
-    sched_yield();
-  }
-}
-void drain_stream(lsb_hip_solver *sv, const char *what) {
-  if (!sv->multi) {
-    LSB_CHK_HIP(hipStreamSynchronize(g_stream));
-    return;
-  }
-  LSB_CHK_HIP(hipEventRecord(sv->ev_poll[0], g_stream));
-  wait_event(sv, sv->ev_poll[0], what);
+  return run_chunk(bytes, 6.0, 8, 256) & ~1;
 }
 
 /* `reps` local iterations of the classic form on shard 0 (SpMV + the two sweeps; no exchange, no
@@ -596,52 +549,6 @@ void tune_blas1_nt(lsb_hip_solver *sv) {
   LSB_CHK_HIP(hipStreamSynchronize(g_stream));
   lsb_hip_free(d_b), lsb_hip_free(d_x);
 }
-
-/* hipGraph of `iters` PCG iterations writing to d_x; two cached entries (the
- * hinted whole-solve graph and the small continuation chunk).  The form a run takes
- * depends on the solver and d_x alone: the key holds it. */
-static hipGraphExec_t get_graph(lsb_hip_solver *sv, enum pcg_form form, int iters, double *d_x) {
-  for (int i = 0; i < LSB_NGRAPH; i++)
-    if (sv->gcache[i].exec && sv->gcache[i].iters == iters && sv->gcache[i].x == d_x)
-      return sv->gcache[i].exec;
-  const int slot = sv->gnext;
-  sv->gnext = (sv->gnext + 1) % LSB_NGRAPH;
-  if (sv->gcache[slot].exec)
-    LSB_CHK_HIP(hipGraphExecDestroy(sv->gcache[slot].exec));
-  hipGraph_t g;
-  LSB_CHK_HIP(hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal));
-  for (int i = 0; i < iters; i++)
-    pcg_enqueue_iter(sv, form, d_x, i & 1, -1, (i == 0) | ((i == iters - 1) << 1));
-  LSB_CHK_HIP(hipStreamEndCapture(g_stream, &g));
-  LSB_CHK_HIP(hipGraphInstantiate(&sv->gcache[slot].exec, g, NULL, NULL, 0));
-  LSB_CHK_HIP(hipGraphDestroy(g));
-  sv->gcache[slot].iters = iters, sv->gcache[slot].x = d_x;
-  return sv->gcache[slot].exec;
-}
-
-void drop_graphs(lsb_hip_solver *sv) {
-  for (int i = 0; i < LSB_NGRAPH; i++)
-    if (sv->gcache[i].exec) {
-      LSB_CHK_HIP(hipGraphExecDestroy(sv->gcache[i].exec));
-      sv->gcache[i].exec = NULL;
-    }
-  mrhs_drop_graphs(sv);
-  richardson_drop_graphs(sv);
-}
-
-/*
- * Host side of one solve.  The device decides when to stop (lsb_pcg_state);
- * the host only has to enqueue enough iterations and look at the 64-byte state
- * now and then:
- *   - a solver that has solved before enqueues exactly the iteration count of
- *     its previous solve in one go (the benchmark protocol repeats the same
- *     solve `trials` times, src/cholmod-impl.h:44-63) and polls once;
- *   - otherwise, and for whatever is left, chunks of `check_every` iterations
- *     are enqueued one AHEAD of the poll, so the device never waits for the
- *     host; iterations enqueued past convergence are no-op launches.
- */
-static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res,
-                   int round);
 
 /* ||b - S x||^2 recomputed from x with the solver's operator, communicating
  * WITHOUT the direct xGMI path; overwrites the search-direction vector and
@@ -800,20 +707,46 @@ void persist_setup(lsb_hip_solver *sv) {
   lsb_hip_free(d_b), lsb_hip_free(d_x);
 }
 
+/* what run_loop enqueues: iterations of one form writing to d_x, as plain launches -- every sample_spmv-th of the
+ * run with its SpMV bracketed by events -- or replayed from a graph (the form a run takes depends on the solver and
+ * d_x alone: the cache's key holds it) */
+struct pcg_enq {
+  lsb_hip_solver *sv;
+  enum pcg_form form;
+  double *d_x;
+  int use_graph, nsamp;
+  unsigned done; /* iterations enqueued so far in this run */
+};
+static void pcg_enqueue_iters(void *ctx, int cnt) {
+  struct pcg_enq *e = ctx;
+  lsb_hip_solver *sv = e->sv;
+  for (int i = 0; i < cnt; i++) {
+    int smp = -1;
+    if (sv->o.sample_spmv > 0 && e->nsamp < MAX_SAMPLES &&
+        ((e->done + (unsigned)i) % (unsigned)sv->o.sample_spmv) == 0)
+      smp = e->nsamp++;
+    pcg_enqueue_iter(sv, e->form, e->d_x, i & 1, smp, (i == 0) | ((i == cnt - 1) << 1));
+  }
+}
+static void pcg_enqueue(void *ctx, int cnt) {
+  struct pcg_enq *e = ctx;
+  if (e->use_graph)
+    graph_launch(&e->sv->graphs, cnt, e->d_x, pcg_enqueue_iters, ctx);
+  else
+    pcg_enqueue_iters(ctx, cnt);
+  e->done += (unsigned)cnt;
+}
+
 /* One CG run from x0 = 0 to sv->tol_run; `round` = 0 for the solve proper, k for
- * its k-th correction run (each keeps its own iteration-count hint: the
- * benchmark protocol repeats the same sequence trial after trial). */
+ * its k-th correction run. */
 static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res,
                    int round) {
-  unsigned *hint = &sv->hint_iters[round < LSB_MAX_CORRECTIONS ? round : LSB_MAX_CORRECTIONS];
+  unsigned *hint = hint_slot(sv->hint_iters, round);
   const int chunk = sv->o.check_every > 0 ? (sv->o.check_every + 1) & ~1 : auto_chunk(sv);
-  const int sampling = sv->o.sample_spmv > 0;
   memset(sv->samp_skip, 0, sizeof sv->samp_skip);
-  const int use_graph = sv->o.use_graph && !sv->multi && !sampling;
-  /* k_pcg_col_px loads and stores x as 16-byte vectors: any other x runs the classic form */
-  const enum pcg_form form = sv->form == PCG_COL && ((uintptr_t)d_x & 15) ? PCG_CLASSIC : sv->form;
-  int nsamp = 0;
-  unsigned done_iters = 0;
+  struct pcg_enq enq = {.sv = sv, .d_x = d_x, .use_graph = sv->o.use_graph && !sv->multi && sv->o.sample_spmv <= 0,
+                        /* k_pcg_col_px loads and stores x as 16-byte vectors: any other x runs the classic form */
+                        .form = sv->form == PCG_COL && ((uintptr_t)d_x & 15) ? PCG_CLASSIC : sv->form};
   struct lsb_pcg_state *hst = sv->h_st; /* two pinned slots */
   double t0 = wall_seconds();
   if (sv->ps.use) {
@@ -831,8 +764,7 @@ static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct ls
     }
     struct lsb_hip_result r;
     memset(&r, 0, sizeof r);
-    r.iters = (unsigned)hst[0].iters, r.status = hst[0].status;
-    r.relres = hst[0].bb > 0.0 ? sqrt(hst[0].rr / hst[0].bb) : 0.0;
+    result_from_state(&r, &hst[0]);
     r.seconds = wall_seconds() - t0, r.true_relres = -1.0;
     *hint = r.iters;
     if (res)
@@ -840,85 +772,31 @@ static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct ls
     return 0;
   }
 
-#define ENQUEUE_ITERS(count)                                                   \
-  do {                                                                         \
-    const int cnt_ = (count);                                                  \
-    if (use_graph) {                                                           \
-      LSB_CHK_HIP(hipGraphLaunch(get_graph(sv, form, cnt_, d_x), g_stream));   \
-    } else {                                                                   \
-      for (int i_ = 0; i_ < cnt_; i_++) {                                      \
-        int smp_ = -1;                                                         \
-        if (sampling && nsamp < MAX_SAMPLES &&                                 \
-            ((done_iters + (unsigned)i_) % (unsigned)sv->o.sample_spmv) == 0)  \
-          smp_ = nsamp++;                                                      \
-        pcg_enqueue_iter(sv, form, d_x, i_ & 1, smp_, (i_ == 0) | ((i_ == cnt_ - 1) << 1)); \
-      }                                                                        \
-    }                                                                          \
-    done_iters += (unsigned)cnt_;                                              \
-  } while (0)
-#define ENQUEUE_POLL(slot)                                                     \
-  do {                                                                         \
-    LSB_CHK_HIP(hipMemcpyAsync(&hst[slot], sv->sh[0].d_st,                     \
-                               sizeof(struct lsb_pcg_state),                   \
-                               hipMemcpyDeviceToHost, g_stream));              \
-    LSB_CHK_HIP(hipEventRecord(sv->ev_poll[slot], g_stream));                  \
-  } while (0)
-
-  pcg_enqueue_init(sv, form, d_b, d_x);
-  int fin = -1; /* slot holding the final state */
-  if (*hint > 0) {
-    /* graphs beyond ~1k iterations cost more to build than they save */
-    int first = (int)((*hint + 1) & ~1u);
-    while (use_graph && first > 1024)
-      first = ((first / 2) + 1) & ~1;
-    int left = (int)((*hint + 1) & ~1u);
-    while (left > 0) {
-      const int c = left < first ? ((left + 1) & ~1) : first;
-      ENQUEUE_ITERS(c);
-      left -= c;
-    }
-    ENQUEUE_POLL(0);
-    wait_event(sv, sv->ev_poll[0], "poll of a hinted solve");
-    if (hst[0].status != LSB_STATUS_RUNNING)
-      fin = 0;
-  }
-  if (fin < 0) {
-    int cur = 0;
-    ENQUEUE_ITERS(chunk);
-    ENQUEUE_POLL(0);
-    for (;;) {
-      ENQUEUE_ITERS(chunk); /* one chunk ahead of the poll */
-      ENQUEUE_POLL(cur ^ 1);
-      wait_event(sv, sv->ev_poll[cur], "poll of the solve");
-      if (hst[cur].status != LSB_STATUS_RUNNING) {
-        fin = cur;
-        break;
-      }
-      cur ^= 1;
-      if (done_iters > sv->o.maxit + 3u * (unsigned)chunk) /* cannot happen */
-        errx(EXIT_FAILURE, "hip_cdna4: PCG ran past maxit without a status");
-    }
-    drain_stream(sv, "drain after the solve"); /* the speculative chunk */
-  }
-#undef ENQUEUE_ITERS
-#undef ENQUEUE_POLL
-  if (fin != 0)
-    hst[0] = hst[fin];
+  pcg_enqueue_init(sv, enq.form, d_b, d_x);
+  /* graphs beyond ~1k iterations cost more to build than they save: max_piece */
+  const struct run_loop loop = {.name = "PCG", .d_state = sv->sh[0].d_st, .h_state = hst,
+                                .state_bytes = sizeof(struct lsb_pcg_state),
+                                .stop_off = offsetof(struct lsb_pcg_state, status),
+                                .progress_off = offsetof(struct lsb_pcg_state, iters),
+                                .enqueue = pcg_enqueue, .ctx = &enq, .chunk = chunk, .even = 1,
+                                .max_piece = enq.use_graph ? 1024 : 0, .cap = -1,
+                                .what_hinted = "poll of a hinted solve", .what_poll = "poll of the solve",
+                                .what_drain = "drain after the solve"};
+  hst[0].iters = 0; /* every run starts from its own init: the hint is the run's whole count */
+  run_loop(sv, &loop, hint);
   if (hst[0].status == LSB_STATUS_COMM)
     lsb_give_up("hip_cdna4: a peer did not arrive within the time-out of the direct "
                 "xGMI path (LSBENCH_HIP_P2P_TIMEOUT_MS); iteration %d (rank %d of %d)", hst[0].iters,
                 lsb_hip_comm_rank(), lsb_hip_comm_size());
-  *hint = (unsigned)hst[0].iters;
   /* (single-reduction form: r.r of the maxit-th update and the final status --
    * MAXIT, or CONVERGED exactly at maxit -- are settled on the device by the
    * launch after it, k_cg1_update's `pend` branch) */
   double t1 = wall_seconds();
   struct lsb_hip_result r;
   memset(&r, 0, sizeof r);
-  r.iters = (unsigned)sv->h_st->iters;
-  r.status = sv->h_st->status;
-  r.relres = sv->h_st->bb > 0.0 ? sqrt(sv->h_st->rr / sv->h_st->bb) : 0.0;
+  result_from_state(&r, &hst[0]);
   r.seconds = t1 - t0;
+  const int nsamp = enq.nsamp;
   if (nsamp > 0) {
     double tot = 0.0;
     int used = 0;

@@ -7,8 +7,6 @@
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
-#define DINV(s) ((s)->dinv_uniform ? NULL : (s)->d_dinv), (s)->dinv_const
-
 int generic_precond(const lsb_hip_solver *sv) {
   return sv->o.precond == LSB_PRECOND_CHEBYSHEV || sv->o.precond == LSB_PRECOND_BLOCKJACOBI ||
          sv->o.precond == LSB_PRECOND_FSAI || sv->o.precond == LSB_PRECOND_AMG;

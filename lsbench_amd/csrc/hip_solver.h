@@ -7,7 +7,8 @@
  *                    timing pass, create / destroy
  *   hip_dist.c       what sharded solves add: exchange, all-reduce, overlap,
  *                    the direct xGMI path's set-up
- *   hip_pcg.c        PCG iteration forms (one chosen per solver) and the host loop
+ *   hip_run.c        what the iteration drivers share: the host loop, the cache of captured graphs, the chunk rule
+ *   hip_pcg.c        PCG iteration forms (one chosen per solver), the solve and its correction runs
  *   hip_precond.c    FSAI, block-Jacobi and the Chebyshev preconditioner: set-up and z = M^-1 r
  *   hip_amg_drv.c    AMG: upload of the hierarchy, the V-cycle's one schedule (amg_cycle), its accessors
  *   hip_gmres_drv.c  GMRES(m) driver
@@ -22,6 +23,7 @@
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 #include <strings.h>
 #include <time.h>
@@ -51,6 +53,17 @@ LSB_INTERNAL int bench_multi(double *x, struct csr *A, const double *r, const st
 #define SCAL_STRIDE 8 /* doubles per shard in the scalar slab */
 #define MAX_SAMPLES 64
 #define LSB_NGRAPH 4 /* cached hipGraphs: whole-solve + continuation chunk, solve proper + correction */
+
+/* hipGraphs of `count` iterations each, found by (count, key) and replaced round-robin (hip_run.c: graph_launch,
+ * graph_drop).  key: the caller's x where the launches hold it, NULL where they touch internal buffers only */
+struct graph_cache {
+  struct {
+    hipGraphExec_t exec;
+    int count;
+    const void *key;
+  } e[LSB_NGRAPH];
+  int next;
+};
 
 /* Rows that reference other shards' columns sit in units [0,first) and [last,count) of a layout (row
  * blocks, slices); the units in between can start before the halo has arrived (ok = 0: not separable) */
@@ -244,12 +257,8 @@ struct lsb_hip_solver {
   double *d_scal_all; /* nshard * SCAL_STRIDE doubles                        */
   struct lsb_hip_opts o;
   struct lsb_pcg_state *h_st; /* pinned, 2 slots */
-  struct {
-    hipGraphExec_t exec;
-    int iters;
-    double *x;
-  } gcache[LSB_NGRAPH];
-  int gnext;
+  struct graph_cache graphs; /* PCG's, keyed on the count and on x: the form a run takes depends on the solver and
+                                x alone */
 #define LSB_MAX_CORRECTIONS 6
 #define LSB_MIXED_INNER_TOL 1e-5 /* what an inner solve on fp32-rounded values is asked for */
   unsigned hint_iters[LSB_MAX_CORRECTIONS + 1]; /* iterations of the previous solve and of each of
@@ -283,17 +292,11 @@ struct lsb_hip_solver {
   } *bcg;
   double *bcg_red; /* nshard x BCG_RED doubles: the all-reduced dot products */
   struct lsb_bcg_state *bcg_hst; /* pinned, 2 slots */
-  /* Richardson (allocated on first use; hip_rich_drv.c): its vectors are the shard's own (r, q, the gather vector
-   * for z) and its state the shard's d_st, polled through h_st; what it owns is its cache of captured graphs */
-  struct rich_work {
-    struct {
-      hipGraphExec_t exec;
-      int cycles;
-      double *x;
-    } g[LSB_NGRAPH]; /* keyed on the count and on x, as gcache is */
-    int gnext;
-    unsigned nrr; /* partial count of the update sweep */
-  } *rich;
+  /* Richardson (hip_rich_drv.c): its vectors are the shard's own (r, q, the gather vector for z) and its state the
+   * shard's d_st, polled through h_st; what it owns is its cache of captured graphs, keyed on the count and on x,
+   * and the partial count of its update sweep */
+  struct graph_cache rich_graphs;
+  unsigned rich_nrr;
   /* several right-hand sides (allocated on first use, per batch width kp = 2, 4, 8; hip_mrhs_drv.c) */
   struct mrhs_work {
     unsigned kp;                 /* 0: not allocated */
@@ -307,11 +310,7 @@ struct lsb_hip_solver {
     double *z;
     struct amg_vecs *av; /* (amg_block_vecs) */
     unsigned hint[LSB_MAX_CORRECTIONS + 1]; /* launches the previous batch's solve and restarts took */
-    struct {
-      hipGraphExec_t exec;
-      int iters;
-    } g[LSB_NGRAPH];             /* its own graph cache: the iteration touches these buffers only */
-    int gnext;
+    struct graph_cache g;        /* its own graph cache, keyed on the count: the iteration touches these buffers only */
   } mr[3];
   struct lsb_mrhs_state *mr_hst; /* pinned, 2 slots */
   unsigned mr_lanes;             /* lanes per row of its SpMM */
@@ -351,6 +350,16 @@ struct lsb_hip_solver {
   double p2p_us, rccl_us; /* self-test: one exchange + all-reduce, each way */
 };
 
+/* the Jacobi diagonal as the fused sweeps take it: the vector, or (NULL, c) when
+ * every entry is the same c -- then nobody reads 8 n bytes to learn it */
+#define DINV(s) ((s)->dinv_uniform ? NULL : (s)->d_dinv), (s)->dinv_const
+
+/* the iteration-count hint of the solve proper (round 0) or of its k-th correction run: each keeps its own, the
+ * benchmark protocol repeats the same sequence trial after trial */
+static inline unsigned *hint_slot(unsigned *hints, int round) {
+  return &hints[round < LSB_MAX_CORRECTIONS ? round : LSB_MAX_CORRECTIONS];
+}
+
 /* lanes per row of the row kernels from a mean row length: the next power of two, 2 .. 64 */
 static inline unsigned row_lanes(unsigned len) {
   unsigned L = 2;
@@ -375,10 +384,38 @@ LSB_INTERNAL double wall_seconds(void);
  * collective, a peer that never arrived): message, flush, _exit(EXIT_FAILURE).  Never exit():
  * exit() runs the HIP runtime's teardown, which waits for exactly that stream. */
 LSB_INTERNAL void lsb_give_up(const char *fmt, ...) __attribute__((noreturn, format(printf, 1, 2)));
+LSB_INTERNAL void *dev_upload(const void *h, size_t bytes);
+/* hip_run.c */
 /* hipStreamSynchronize(g_stream) that gives up after opts.comm_deadline_s on a sharded solver */
 LSB_INTERNAL void drain_stream(lsb_hip_solver *sv, const char *what);
 LSB_INTERNAL void wait_event(lsb_hip_solver *sv, hipEvent_t ev, const char *what);
-LSB_INTERNAL void *dev_upload(const void *h, size_t bytes);
+/* One run of an iteration driver, described on the caller's stack: enqueue(ctx, count) puts count iterations on the
+ * stream -- plain launches or a cached graph, the loop does not know -- and the loop polls the device state into the
+ * two pinned slots of h_state until it has stopped; the final state ends in slot 0 (run_loop, hip_run.c). */
+typedef void run_enqueue_fn(void *ctx, int count);
+struct run_loop {
+  const char *name;              /* the driver, as the cannot-happen message names it */
+  const void *d_state;           /* the device state that is polled, */
+  void *h_state;                 /* its pinned host copy, two slots, */
+  size_t state_bytes;            /* and the size of one */
+  size_t stop_off, progress_off; /* two ints inside it: the stop word, and the count the hint is taken from */
+  int stop_is_running;           /* the stop word is a status (stopped: != RUNNING), or 1: the batch's `running` */
+  run_enqueue_fn *enqueue;
+  void *ctx;
+  int chunk;                     /* iterations per poll */
+  int even;                      /* a hinted count is rounded up to even */
+  int max_piece;                 /* a hinted count longer than this goes out in equal even pieces, halved until they
+                                    fit: graphs beyond ~1k iterations cost more to build than they save.  0: in one */
+  long cap;                      /* never more than this on the stream in the whole run; < 0: no cap */
+  const char *what_hinted, *what_poll, *what_drain; /* wait_event's and drain_stream's `what` */
+};
+LSB_INTERNAL void run_loop(lsb_hip_solver *sv, const struct run_loop *r, unsigned *hint);
+LSB_INTERNAL void graph_launch(struct graph_cache *gc, int count, const void *key, run_enqueue_fn *plain, void *ctx);
+LSB_INTERNAL void graph_drop(struct graph_cache *gc);
+LSB_INTERNAL void drop_graphs(lsb_hip_solver *sv); /* every cache of the solver */
+LSB_INTERNAL int run_chunk(double bytes, double floor_us, int lo, int hi);
+/* iters, status and relres (from rr / bb) of a result out of a polled state */
+LSB_INTERNAL void result_from_state(struct lsb_hip_result *r, const struct lsb_pcg_state *st);
 /* hip_solver.c */
 LSB_INTERNAL double *shard_vec(struct shard *s, size_t count);
 LSB_INTERNAL void shard_vec_free(struct shard *s, void *p);
@@ -401,6 +438,9 @@ LSB_INTERNAL void exchange_p(lsb_hip_solver *sv, int gated);
 LSB_INTERNAL void exchange_vec(lsb_hip_solver *sv, int gated, double *const *full);
 LSB_INTERNAL void check_aux_status(lsb_hip_solver *sv, const char *where);
 LSB_INTERNAL void allreduce_scal(lsb_hip_solver *sv, unsigned off, unsigned cnt, int gated);
+/* sum red[shard][off .. off+cnt) (stride doubles per shard) over the shards of all ranks, the result in every
+ * shard's copy: GMRES's and BiCGSTAB's scalars, not tied to a PCG state */
+LSB_INTERNAL void red_allreduce(lsb_hip_solver *sv, double *red, unsigned stride, unsigned off, unsigned cnt);
 LSB_INTERNAL void allreduce_pq(lsb_hip_solver *sv, unsigned cnt, int with2);
 LSB_INTERNAL int can_overlap(const lsb_hip_solver *sv);
 LSB_INTERNAL int can_fold_allreduce(const lsb_hip_solver *sv);
@@ -417,7 +457,6 @@ LSB_INTERNAL void form_vecs(lsb_hip_solver *sv, enum pcg_form f);
 LSB_INTERNAL void sample_open(lsb_hip_solver *sv, int k);
 LSB_INTERNAL void sample_close(lsb_hip_solver *sv, int k);
 LSB_INTERNAL void tune_blas1_nt(lsb_hip_solver *sv);
-LSB_INTERNAL void drop_graphs(lsb_hip_solver *sv);
 LSB_INTERNAL void persist_setup(lsb_hip_solver *sv);
 LSB_INTERNAL int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
                             struct lsb_hip_result *res);
@@ -461,8 +500,6 @@ LSB_INTERNAL void bicgstab_free(lsb_hip_solver *sv); /* before the shards go: it
  * aligned, else the 8-byte form with the same bits; partials: one per workgroup, *npartials of them) */
 LSB_INTERNAL int richardson_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
                                       struct lsb_hip_result *res);
-LSB_INTERNAL void richardson_free(lsb_hip_solver *sv); /* before the shards go */
-LSB_INTERNAL void richardson_drop_graphs(lsb_hip_solver *sv);
 /* what --krylov richardson cannot run with, refused at creation: a preconditioner other than AMG, shards, persistent */
 LSB_INTERNAL void richardson_check(const struct lsb_hip_opts *o, int sharded);
 LSB_INTERNAL void lsb_k_rich_init(unsigned n, const double *b, double *x, double *r, double *partials,
@@ -479,6 +516,5 @@ LSB_INTERNAL void lsb_k_rich_restart_state(struct lsb_pcg_state *st, const doubl
                                            void *stream);
 /* hip_mrhs_drv.c */
 LSB_INTERNAL void mrhs_free(lsb_hip_solver *sv); /* before the shards go */
-LSB_INTERNAL void mrhs_drop_graphs(lsb_hip_solver *sv);
 
 #endif
