@@ -34,7 +34,7 @@
 #include <stdint.h>
 
 #include "hip_amg_cheb.h"
-#include "lsb_impl.h"
+#include "hip_kcommon.h"
 
 #define AMG_WG 256
 #define AMG_TAIL 1024
@@ -263,17 +263,10 @@ void lsb_k_amg_csr(int mode, const struct lsb_amg_mat *m, const double *xin, con
     return;
   hipStream_t s = (hipStream_t)stream;
   const unsigned g = amg_grid((unsigned long long)m->rows * m->lanes);
-#define AMG_L(LL, MM)                                                                                   \
-  case LL:                                                                                              \
-    k_amg_csr<LL, MM><<<g, AMG_WG, 0, s>>>(m->rows, m->offs, m->cols, m->vals, xin, b, minv, y, st);    \
-    break;
-#define AMG_MODE(MM)                                                                                    \
-  case MM:                                                                                              \
-    switch (m->lanes) {                                                                                 \
-      AMG_L(2, MM) AMG_L(4, MM) AMG_L(8, MM) AMG_L(16, MM) AMG_L(32, MM)                                 \
-    default:                                                                                            \
-      k_amg_csr<64, MM><<<g, AMG_WG, 0, s>>>(m->rows, m->offs, m->cols, m->vals, xin, b, minv, y, st);  \
-    }                                                                                                   \
+#define AMG_MODE(MM)                                                                                            \
+  case MM:                                                                                                      \
+    LANES_DISPATCH(m->lanes, (k_amg_csr<L, MM><<<g, AMG_WG, 0, s>>>(m->rows, m->offs, m->cols, m->vals, xin, b, \
+                                                                    minv, y, st)));                             \
     break;
   switch (mode) {
     AMG_MODE(LSB_AMG_SWEEP) AMG_MODE(LSB_AMG_RESID) AMG_MODE(LSB_AMG_SPMV) AMG_MODE(LSB_AMG_ADDP)
@@ -281,7 +274,6 @@ void lsb_k_amg_csr(int mode, const struct lsb_amg_mat *m, const double *xin, con
     errx(EXIT_FAILURE, "lsb_k_amg_csr: no mode %d", mode);
   }
 #undef AMG_MODE
-#undef AMG_L
 }
 
 void lsb_k_amg_cheb_first(unsigned n, const double *b, const double *dinv, double c2, double *d, double *x,
@@ -296,30 +288,15 @@ void lsb_k_amg_cheb(const struct lsb_amg_mat *m, const double *xin, const double
     return;
   hipStream_t s = (hipStream_t)stream;
   const unsigned g = amg_grid((unsigned long long)m->rows * m->lanes);
-#define AMG_L(LL)                                                                                            \
-  case LL:                                                                                                   \
-    k_amg_cheb<LL><<<g, AMG_WG, 0, s>>>(m->rows, m->offs, m->cols, m->vals, xin, b, dinv, c1, c2, d, y, st); \
-    break;
-  switch (m->lanes) {
-    AMG_L(2) AMG_L(4) AMG_L(8) AMG_L(16) AMG_L(32)
-  default:
-    k_amg_cheb<64><<<g, AMG_WG, 0, s>>>(m->rows, m->offs, m->cols, m->vals, xin, b, dinv, c1, c2, d, y, st);
-  }
-#undef AMG_L
+  LANES_DISPATCH(m->lanes, (k_amg_cheb<L><<<g, AMG_WG, 0, s>>>(m->rows, m->offs, m->cols, m->vals, xin, b, dinv, c1, c2,
+                                                               d, y, st)));
 }
 
 void lsb_k_amg_dense(unsigned nc, unsigned lanes, const double *cinv, const double *b, double *out,
                      const struct lsb_pcg_state *st, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const unsigned g = amg_grid((unsigned long long)nc * lanes);
-  switch (lanes) {
-  case 2: k_amg_dense<2><<<g, AMG_WG, 0, s>>>(nc, cinv, b, out, st); break;
-  case 4: k_amg_dense<4><<<g, AMG_WG, 0, s>>>(nc, cinv, b, out, st); break;
-  case 8: k_amg_dense<8><<<g, AMG_WG, 0, s>>>(nc, cinv, b, out, st); break;
-  case 16: k_amg_dense<16><<<g, AMG_WG, 0, s>>>(nc, cinv, b, out, st); break;
-  case 32: k_amg_dense<32><<<g, AMG_WG, 0, s>>>(nc, cinv, b, out, st); break;
-  default: k_amg_dense<64><<<g, AMG_WG, 0, s>>>(nc, cinv, b, out, st); break;
-  }
+  LANES_DISPATCH(lanes, (k_amg_dense<L><<<g, AMG_WG, 0, s>>>(nc, cinv, b, out, st)));
 }
 
 void lsb_k_amg_tail(const struct lsb_amg_lvdev *lv, unsigned t, unsigned nlev, unsigned nu, const double *cinv,

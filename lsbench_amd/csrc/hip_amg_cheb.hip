@@ -10,7 +10,7 @@
 // only d_i) and is not read on a step with c1 == 0.
 //
 // Records: with REC the step leaves, per workgroup, one record of 2 KP doubles -- b_c . y_c per column, then
-// b_c . b_c per column -- in the format k_amg_mrhs_update_p reads (wg_sum_records<2 KP>: fixed order, no
+// b_c . b_c per column -- in the format k_mrhs_update_p reads (wg_sum_records<2 KP>: fixed order, no
 // atomics).  On the fine level's last post-smoothing step b is the residual block and y is z, so AMG-PCG on
 // blocks keeps having no dot-product launch.
 //
@@ -131,7 +131,7 @@ template <int KP, bool REC>
 static void amg_cheb_launch(const struct lsb_amg_mat *m, unsigned g, const double *xin, const double *b,
                             const double *dinv, double c1, double c2, double *d, double *y, double *records,
                             const struct lsb_mrhs_state *st, hipStream_t s) {
-  L_DISPATCH(m->lanes, (k_amg_cheb_m<L, KP, REC><<<g, WG, 0, s>>>(m->rows, round_up(div_up(m->rows, g), WG / L),
+  LANES_DISPATCH(m->lanes, (k_amg_cheb_m<L, KP, REC><<<g, WG, 0, s>>>(m->rows, round_up(div_up(m->rows, g), WG / L),
                                                                   m->offs, m->cols, m->vals, xin, b, dinv, c1, c2, d,
                                                                   y, records, st)));
 }
@@ -154,7 +154,7 @@ void lsb_k_amg_cheb_m(unsigned kp, const struct lsb_amg_mat *m, const double *xi
     return;
   }
   hipStream_t s = (hipStream_t)stream;
-  const unsigned g = lsb_k_spmm_grid(m->rows, amg_lanes(m->lanes));
+  const unsigned g = lsb_k_spmm_grid(m->rows, row_lanes(m->lanes));
   if (nrecords)
     *nrecords = g;
   if (records)

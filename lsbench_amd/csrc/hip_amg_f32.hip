@@ -29,10 +29,7 @@
 // No atomics, no allocation, no synchronisation inside an application: every output row is one lane group's
 // fixed-order reduction, so z is bitwise repeatable.  Every kernel is a no-op once the solve's state has left
 // RUNNING.  Not built: the one-launch tail, blocks of columns.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "lsb_impl.h"
+#include "hip_kcommon.h"
 
 #define AMG32_WG 256
 
@@ -191,16 +188,6 @@ static unsigned amg32_grid(unsigned long long threads) {
   return g > 16384ull ? 16384u : (g ? (unsigned)g : 1u);
 }
 
-#define AMG32_LANES(lanes, CALL)  \
-  switch (lanes) {                \
-  case 2: { constexpr int L = 2; CALL; } break;   \
-  case 4: { constexpr int L = 4; CALL; } break;   \
-  case 8: { constexpr int L = 8; CALL; } break;   \
-  case 16: { constexpr int L = 16; CALL; } break; \
-  case 32: { constexpr int L = 32; CALL; } break; \
-  default: { constexpr int L = 64; CALL; } break; \
-  }
-
 extern "C" {
 
 void lsb_k_amg32_first(unsigned n, int in64, const void *b, const float *minv, float *x, float *b32,
@@ -222,7 +209,7 @@ void lsb_k_amg32_csr(int mode, const struct amg_mat32 *m, const float *xin, cons
   const unsigned g = amg32_grid((unsigned long long)m->rows * m->lanes);
   if (y64 && mode != LSB_AMG_SWEEP)
     errx(EXIT_FAILURE, "lsb_k_amg32_csr: only a sweep writes fp64");
-#define AMG32_GO(MM, O64) AMG32_LANES(m->lanes, (k_amg32_csr<L, MM, O64><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, minv, y, y64, st)))
+#define AMG32_GO(MM, O64) LANES_DISPATCH(m->lanes, (k_amg32_csr<L, MM, O64><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, minv, y, y64, st)));
   switch (mode) {
   case LSB_AMG_SWEEP:
     if (y64)
@@ -256,9 +243,9 @@ void lsb_k_amg32_cheb(const struct amg_mat32 *m, const float *xin, const float *
   hipStream_t s = (hipStream_t)stream;
   const unsigned g = amg32_grid((unsigned long long)m->rows * m->lanes);
   if (y64)
-    AMG32_LANES(m->lanes, (k_amg32_cheb<L, true><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, dinv, c1, c2, d, y, y64, st)))
+    LANES_DISPATCH(m->lanes, (k_amg32_cheb<L, true><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, dinv, c1, c2, d, y, y64, st)));
   else
-    AMG32_LANES(m->lanes, (k_amg32_cheb<L, false><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, dinv, c1, c2, d, y, y64, st)))
+    LANES_DISPATCH(m->lanes, (k_amg32_cheb<L, false><<<g, AMG32_WG, 0, s>>>(m->rows, m->offs, m->ent, xin, b, dinv, c1, c2, d, y, y64, st)));
 }
 
 // ends64: a hierarchy of one level -- b is the caller's fp64 r, out its fp64 z; else both are float
@@ -267,9 +254,9 @@ void lsb_k_amg32_dense(unsigned nc, unsigned lanes, int ends64, const float *cin
   hipStream_t s = (hipStream_t)stream;
   const unsigned g = amg32_grid((unsigned long long)nc * lanes);
   if (ends64)
-    AMG32_LANES(lanes, (k_amg32_dense<L, true, true><<<g, AMG32_WG, 0, s>>>(nc, cinv, b, out, st)))
+    LANES_DISPATCH(lanes, (k_amg32_dense<L, true, true><<<g, AMG32_WG, 0, s>>>(nc, cinv, b, out, st)));
   else
-    AMG32_LANES(lanes, (k_amg32_dense<L, false, false><<<g, AMG32_WG, 0, s>>>(nc, cinv, b, out, st)))
+    LANES_DISPATCH(lanes, (k_amg32_dense<L, false, false><<<g, AMG32_WG, 0, s>>>(nc, cinv, b, out, st)));
 }
 
 } // extern "C"

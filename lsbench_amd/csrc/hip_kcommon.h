@@ -1,5 +1,6 @@
-// What the SpMV kernels (hip_kernels.hip), the BLAS-1 / PCG sweeps (hip_sweeps.hip) and the kernels of
-// several right-hand sides (hip_mrhs.hip) share.  Included by those files only.
+// What the SpMV kernels (hip_kernels.hip), the BLAS-1 / PCG sweeps (hip_sweeps.hip), the kernels of several
+// right-hand sides (hip_mrhs.hip) and the launchers of the AMG cycles (hip_amg*.hip, hip_mrhs_amg.hip) share.
+// Included by kernel files only.
 #ifndef LSB_HIP_KCOMMON_H
 #define LSB_HIP_KCOMMON_H
 #include <hip/hip_runtime.h>
@@ -22,5 +23,21 @@ __device__ __forceinline__ double pnew_of(double d, double r, double beta, doubl
 static inline unsigned div_up(unsigned a, unsigned b) { return (a + b - 1) / b; }
 static inline unsigned round_up(unsigned a, unsigned b) { return div_up(a, b) * b; }
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// lanes per row as the row kernels are instantiated -- 2 .. 32; any other count takes a whole wavefront -- and
+// the launchers' dispatch on them: CALL sees the count as the constant L
+static inline unsigned row_lanes(unsigned L) { return L == 2 || L == 4 || L == 8 || L == 16 || L == 32 ? L : 64; }
+
+#define LANES_DISPATCH(lanes, CALL)                                            \
+  do {                                                                         \
+    switch (row_lanes(lanes)) {                                                \
+    case 2: { constexpr int L = 2; CALL; } break;                              \
+    case 4: { constexpr int L = 4; CALL; } break;                              \
+    case 8: { constexpr int L = 8; CALL; } break;                              \
+    case 16: { constexpr int L = 16; CALL; } break;                            \
+    case 32: { constexpr int L = 32; CALL; } break;                            \
+    default: { constexpr int L = 64; CALL; } break;                            \
+    }                                                                          \
+  } while (0)
 
 #endif

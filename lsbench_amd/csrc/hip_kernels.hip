@@ -1958,9 +1958,6 @@ static lsb_cheb_epi epi_for(const struct lsb_cheb_epi *e, bool refused, const ch
   return *e;
 }
 
-/* the sub-wavefront kernels come with 2 .. 32 lanes per row; any other count takes a whole wavefront */
-static unsigned subwave_lanes(unsigned L) { return L == 2 || L == 4 || L == 8 || L == 16 || L == 32 ? L : 64; }
-
 void lsb_k_spmv(int variant, unsigned n, const int *offs, const int *cols,
                 const double *vals, const int *rowblk,
                 const unsigned char *blklanes, unsigned nblk,
@@ -1985,16 +1982,8 @@ void lsb_k_spmv(int variant, unsigned n, const int *offs, const int *cols,
           k_spmv_adaptive<LSB_BLOCK_NNZ, 2, VT>, k_spmv_adaptive<LSB_BLOCK_NNZ, 3, VT>};
       kern[flags & 3u]<<<g, WG, 0, s>>>(rowblk, blklanes, nblk, offs, cols, v, x, y, xdot, partials, st, rowmap, tail);
     } else {
-      const unsigned L = subwave_lanes(lanes_per_row);
-      auto kern = k_spmv_subwave<64, VT>;
-      switch (L) {
-      case 2: kern = k_spmv_subwave<2, VT>; break;
-      case 4: kern = k_spmv_subwave<4, VT>; break;
-      case 8: kern = k_spmv_subwave<8, VT>; break;
-      case 16: kern = k_spmv_subwave<16, VT>; break;
-      case 32: kern = k_spmv_subwave<32, VT>; break;
-      }
-      kern<<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols, v, x, y, xdot, partials, st);
+      LANES_DISPATCH(lanes_per_row, (k_spmv_subwave<L, VT><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols,
+                                                                           v, x, y, xdot, partials, st)));
     }
   };
   if (variant != LSB_SPMV_ADAPTIVE && variant != LSB_SPMV_SUBWAVE)
@@ -2014,17 +2003,9 @@ void lsb_k_spmv_subwave_p(unsigned n, const int *offs, const int *cols, const do
                           const double *parts2, unsigned nparts2, void *stream) {
   const unsigned g = lsb_k_spmv_grid(LSB_SPMV_SUBWAVE, n, 0, lanes_per_row, 0);
   *npartials = g;
-  const unsigned L = subwave_lanes(lanes_per_row);
-  auto kern = k_spmv_subwave_p<64>;
-  switch (L) {
-  case 2: kern = k_spmv_subwave_p<2>; break;
-  case 4: kern = k_spmv_subwave_p<4>; break;
-  case 8: kern = k_spmv_subwave_p<8>; break;
-  case 16: kern = k_spmv_subwave_p<16>; break;
-  case 32: kern = k_spmv_subwave_p<32>; break;
-  }
-  kern<<<g, WG, 0, (hipStream_t)stream>>>(n, round_up(div_up(n, g), WG / L), offs, cols, vals, r, dinv, dc, pold,
-                                          pnew, y, partials, st, parity, parts2, nparts2);
+  LANES_DISPATCH(lanes_per_row, (k_spmv_subwave_p<L><<<g, WG, 0, (hipStream_t)stream>>>(
+                                    n, round_up(div_up(n, g), WG / L), offs, cols, vals, r, dinv, dc, pold, pnew, y,
+                                    partials, st, parity, parts2, nparts2)));
 }
 
 /* What the sliced-ELL, template and z-column launchers share, over `items` slices or column items: the

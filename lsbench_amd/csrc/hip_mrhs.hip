@@ -1,7 +1,13 @@
 // Several right-hand sides at once: the kernels of lsb_hip_solver_solve_multi / _spmm_dev (driver:
-// hip_mrhs_drv.c).  KP = 2, 4 or 8 INDEPENDENT Jacobi-PCG recurrences advance through the same launches --
-// the classic form's three per iteration (SpMM, k_mrhs_update_xr, k_mrhs_update_p) -- each column with its
-// own alpha, beta, norms, iteration count and status.  This is not block-CG.
+// hip_mrhs_drv.c).  KP = 2, 4 or 8 INDEPENDENT PCG recurrences advance through the same launches -- the
+// classic form's three per iteration (SpMM, k_mrhs_update_xr, k_mrhs_update_p) -- each column with its own
+// alpha, beta, norms, iteration count and status.  This is not block-CG.
+//
+// Two forms of the preconditioner, ONE set of sweeps (template parameter Z): the diagonal ones, z = dinv .* r
+// formed inside the sweeps, and z as a block of its own -- the V-cycle of hip_mrhs_amg.hip runs between
+// k_mrhs_update_xr<KP, true> and k_mrhs_update_p<KP, true> and leaves the records the latter reads.  The column
+// bookkeeping (alpha and breakdown, stop test and beta, `running`, nspmm, the gated stores, the restart decision
+// of a verify round) is the same code in both.
 //
 // Layout.  The block vectors (b, x, r, p, q) are ROW-MAJOR, INTERLEAVED: element (i, c) at i KP + c,
 // 16-byte aligned.  A gather of row `col` is KP contiguous doubles (16 / 32 / 64 B) and every sweep is one
@@ -217,6 +223,45 @@ __global__ __launch_bounds__(WG) void k_mrhs_init(unsigned n, const double *__re
     partials2[(size_t)blockIdx.x * 2 * KP + threadIdx.x] = sout[threadIdx.x];
 }
 
+// z as a block of its own: x = 0, r = b; the cycle on r follows, then k_amg_dot2_m<KP, true>
+template <int KP>
+__global__ __launch_bounds__(WG) void k_amg_mrhs_init(unsigned n, const double *__restrict__ b,
+                                                      double *__restrict__ x, double *__restrict__ r) {
+  const size_t npair = (size_t)n * (KP / 2), gsz = (size_t)gridDim.x * WG;
+  const d2v *b2 = (const d2v *)b;
+  d2v *x2 = (d2v *)x, *r2 = (d2v *)r;
+  for (size_t j = (size_t)blockIdx.x * WG + threadIdx.x; j < npair; j += gsz) {
+    x2[j] = d2v{0.0, 0.0};
+    r2[j] = b2[j];
+  }
+}
+
+// one record (u.z per column, then u.u per column) per workgroup over two blocks, in k_mrhs_init's format.
+// P: also p = z -- u = b, the records k_mrhs_init_state reads.  Else u = r, the records of an iteration whose
+// cycle is a one-level hierarchy and has no sweep to leave them.  st != NULL: a no-op once st->running == 0.
+template <int KP, bool P>
+__global__ __launch_bounds__(WG) void k_amg_dot2_m(unsigned n, const double *__restrict__ u,
+                                                   const double *__restrict__ z, double *__restrict__ p,
+                                                   double *__restrict__ records, const lsb_mrhs_state *st) {
+  constexpr int H = KP / 2;
+  __shared__ double sred[8 * KP], sout[2 * KP];
+  if (st && !st->running)
+    return;
+  const size_t npair = (size_t)n * H, gsz = (size_t)gridDim.x * WG;
+  const d2v *u2 = (const d2v *)u, *z2 = (const d2v *)z;
+  double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+  for (size_t j = (size_t)blockIdx.x * WG + threadIdx.x; j < npair; j += gsz) {
+    const d2v uv = u2[j], zv = z2[j];
+    if constexpr (P)
+      ((d2v *)p)[j] = zv;
+    acc[0][0] += uv.x * zv.x, acc[0][1] += uv.y * zv.y;
+    acc[1][0] += uv.x * uv.x, acc[1][1] += uv.y * uv.y;
+  }
+  wg_sum_cols<KP, 2>(acc, sred, sout);
+  if (threadIdx.x < 2 * KP)
+    records[(size_t)blockIdx.x * 2 * KP + threadIdx.x] = sout[threadIdx.x];
+}
+
 template <int KP>
 __global__ __launch_bounds__(WG) void k_mrhs_init_state(lsb_mrhs_state *__restrict__ st,
                                                         const double *__restrict__ partials2, unsigned nparts,
@@ -261,9 +306,13 @@ __global__ __launch_bounds__(WG) void k_mrhs_init_state(lsb_mrhs_state *__restri
   }
 }
 
-// alpha_c = rz_c / pq_c ; x_c += alpha_c p_c ; r_c -= alpha_c q_c ; one record (r.dinv.r per column, then
+// Z == false: the diagonal preconditioners, z = dinv .* r formed on the fly.  Z == true: z is a block of its own,
+// written by the launches between the two sweeps (the V-cycle of hip_mrhs_amg.hip, whose last sweep leaves the
+// records); dinv, dc and partials2 are not looked at.
+//
+// alpha_c = rz_c / pq_c ; x_c += alpha_c p_c ; r_c -= alpha_c q_c ; !Z: one record (r.dinv.r per column, then
 // r.r per column) per workgroup.  p.q zero or not finite: the column is BREAKDOWN (k_pcg_update_xr's test).
-template <int KP>
+template <int KP, bool Z>
 __global__ __launch_bounds__(WG, 8) void k_mrhs_update_xr(unsigned n, const double *__restrict__ p,
                                                        const double *__restrict__ q, const double *__restrict__ dinv,
                                                        double dc, double *__restrict__ x, double *__restrict__ r,
@@ -271,7 +320,7 @@ __global__ __launch_bounds__(WG, 8) void k_mrhs_update_xr(unsigned n, const doub
                                                        const double *__restrict__ pq_parts, unsigned npq,
                                                        double *__restrict__ partials2) {
   constexpr int H = KP / 2;
-  __shared__ double sred[8 * KP], spq[KP], salpha[KP], sout[2 * KP];
+  __shared__ double sred[(Z ? 4 : 8) * KP], spq[KP], salpha[KP];
   __shared__ int sact[KP], sent[KP];
   const unsigned tid = threadIdx.x;
   const size_t gtid = (size_t)blockIdx.x * WG + tid, gsz = (size_t)gridDim.x * WG;
@@ -284,7 +333,7 @@ __global__ __launch_bounds__(WG, 8) void k_mrhs_update_xr(unsigned n, const doub
   const bool first = gtid < npair;
   if (first) {
     pv = p2[gtid], qv = q2[gtid], xv = x2[gtid], rv = r2[gtid];
-    if (dinv)
+    if (!Z && dinv)
       dv = dinv[gtid / H];
   }
   wg_sum_records<KP>(pq_parts, npq, sred, spq);
@@ -315,7 +364,7 @@ __global__ __launch_bounds__(WG, 8) void k_mrhs_update_xr(unsigned n, const doub
   if (blockIdx.x == 0 && tid == 0 && anyent) {
     st->nspmm += 1; // the SpMM in front of this launch worked
     if (!any)
-      st->running = 0; // the last columns broke down
+      st->running = 0; // the last columns broke down (Z: the cycle behind this launch is a no-op)
   }
   if (!any)
     return;
@@ -328,49 +377,50 @@ __global__ __launch_bounds__(WG, 8) void k_mrhs_update_xr(unsigned n, const doub
     for (;;) {
       xv.x += al0 * pv.x, xv.y += al1 * pv.y;
       rv.x -= al0 * qv.x, rv.y -= al1 * qv.y;
-      if (a0 & a1) {
-        x2[j] = xv, r2[j] = rv;
-      } else if (a0) { // the other column is frozen: its half is not stored
-        x[2 * j] = xv.x, r[2 * j] = rv.x;
-      } else {
-        x[2 * j + 1] = xv.y, r[2 * j + 1] = rv.y;
+      store_pairs({x, r}, {xv, rv}, j, a0, a1);
+      if constexpr (!Z) {
+        acc[0][0] += rv.x * (dv * rv.x), acc[0][1] += rv.y * (dv * rv.y);
+        acc[1][0] += rv.x * rv.x, acc[1][1] += rv.y * rv.y;
       }
-      acc[0][0] += rv.x * (dv * rv.x), acc[0][1] += rv.y * (dv * rv.y);
-      acc[1][0] += rv.x * rv.x, acc[1][1] += rv.y * rv.y;
       j += gsz;
       if (j >= npair)
         break;
       pv = p2[j], qv = q2[j], xv = x2[j], rv = r2[j];
-      if (dinv)
+      if (!Z && dinv)
         dv = dinv[j / H];
     }
   }
-  wg_sum_cols<KP, 2>(acc, sred, sout);
-  if (tid < 2 * KP)
-    partials2[(size_t)blockIdx.x * 2 * KP + tid] = sout[tid];
+  if constexpr (!Z) {
+    __shared__ double sout[2 * KP];
+    wg_sum_cols<KP, 2>(acc, sred, sout);
+    if (tid < 2 * KP)
+      partials2[(size_t)blockIdx.x * 2 * KP + tid] = sout[tid];
+  }
 }
 
-// (rz'_c, rr_c) = sum of the records ; stop test ; beta_c = rz'_c / rz_c ; p_c = dinv.*r_c + beta_c p_c
-template <int KP>
-__global__ __launch_bounds__(WG) void k_mrhs_update_p(unsigned n, const double *__restrict__ r,
-                                                      const double *__restrict__ dinv, double dc,
-                                                      double *__restrict__ p, lsb_mrhs_state *__restrict__ st,
-                                                      int parity, const double *__restrict__ parts2,
-                                                      unsigned nparts2) {
+// (rz'_c, rr_c) = sum of the records ; stop test ; beta_c = rz'_c / rz_c ; p_c = z_c + beta_c p_c, z_c = dinv .* r_c
+// or -- Z -- column c of the block zr
+template <int KP, bool Z>
+__global__ __launch_bounds__(WG, Z ? 8 : 0) void k_mrhs_update_p(unsigned n, const double *__restrict__ zr,
+                                                                 const double *__restrict__ dinv, double dc,
+                                                                 double *__restrict__ p,
+                                                                 lsb_mrhs_state *__restrict__ st, int parity,
+                                                                 const double *__restrict__ parts2,
+                                                                 unsigned nparts2) {
   constexpr int H = KP / 2;
   __shared__ double sred[8 * KP], s2[2 * KP], sbeta[KP];
   __shared__ int sact[KP], sent[KP], sleft[KP];
   const unsigned tid = threadIdx.x;
   const size_t gtid = (size_t)blockIdx.x * WG + tid, gsz = (size_t)gridDim.x * WG;
   const size_t npair = (size_t)n * H;
-  const d2v *r2 = (const d2v *)r;
+  const d2v *zr2 = (const d2v *)zr;
   d2v *p2 = (d2v *)p;
   d2v rv = {0.0, 0.0}, pv = rv;
   double dv = dc;
   const bool first = gtid < npair;
   if (first) {
-    rv = r2[gtid], pv = p2[gtid];
-    if (dinv)
+    rv = zr2[gtid], pv = p2[gtid];
+    if (!Z && dinv)
       dv = dinv[gtid / H];
   }
   wg_sum_records<2 * KP>(parts2, nparts2, sred, s2);
@@ -415,19 +465,19 @@ __global__ __launch_bounds__(WG) void k_mrhs_update_p(unsigned n, const double *
   if (first && (a0 | a1)) {
     size_t j = gtid;
     for (;;) {
-      pv.x = pnew_of(dv, rv.x, be0, pv.x); // one expression for every kernel that forms p
-      pv.y = pnew_of(dv, rv.y, be1, pv.y);
-      if (a0 & a1)
-        p2[j] = pv;
-      else if (a0)
-        p[2 * j] = pv.x;
-      else
-        p[2 * j + 1] = pv.y;
+      if constexpr (Z) { // one expression for every kernel that forms p; the literal folds d * r
+        pv.x = pnew_of(1.0, rv.x, be0, pv.x);
+        pv.y = pnew_of(1.0, rv.y, be1, pv.y);
+      } else {
+        pv.x = pnew_of(dv, rv.x, be0, pv.x);
+        pv.y = pnew_of(dv, rv.y, be1, pv.y);
+      }
+      store_pairs({p}, {pv}, j, a0, a1);
       j += gsz;
       if (j >= npair)
         break;
-      rv = r2[j], pv = p2[j];
-      if (dinv)
+      rv = zr2[j], pv = p2[j];
+      if (!Z && dinv)
         dv = dinv[j / H];
     }
   }
@@ -454,13 +504,7 @@ __global__ __launch_bounds__(WG) void k_mrhs_restart(unsigned n, const double *_
   const size_t gtid = (size_t)blockIdx.x * WG + tid, gsz = (size_t)gridDim.x * WG;
   const size_t npair = (size_t)n * H;
   const d2v *q2 = (const d2v *)q;
-  d2v *r2 = (d2v *)r, *p2 = (d2v *)p;
-  wg_sum_records<KP>(rr_parts, nrr, sred, srr);
-  if (tid < KP) {
-    const lsb_pcg_state *c = &st->c[tid];
-    sact[tid] = more && c->iters < c->maxit && mrhs_misses(c, srr[tid], st->tol);
-  }
-  __syncthreads();
+  restart_decision<KP>(st, rr_parts, nrr, more, sred, srr, sact);
   const unsigned c0 = (2u * tid) % KP;
   const int a0 = sact[c0], a1 = sact[c0 + 1];
   double acc[1][2] = {{0.0, 0.0}};
@@ -470,18 +514,62 @@ __global__ __launch_bounds__(WG) void k_mrhs_restart(unsigned n, const double *_
       const double dv = dinv ? dinv[j / H] : dc;
       d2v pv;
       pv.x = dv * rv.x, pv.y = dv * rv.y;
-      if (a0 & a1)
-        r2[j] = rv, p2[j] = pv;
-      else if (a0)
-        r[2 * j] = rv.x, p[2 * j] = pv.x;
-      else
-        r[2 * j + 1] = rv.y, p[2 * j + 1] = pv.y;
+      store_pairs({r, p}, {rv, pv}, j, a0, a1);
       acc[0][0] += rv.x * pv.x, acc[0][1] += rv.y * pv.y;
     }
   }
   wg_sum_cols<KP, 1>(acc, sred, sout);
   if (tid < KP)
     partials[(size_t)blockIdx.x * KP + tid] = sout[tid];
+}
+
+// The same round with z as a block of its own: k_amg_mrhs_restart_r stores r = q for the restarting columns, the
+// cycle (not gated: no column is running) forms z of every column, k_amg_mrhs_restart_p stores p = z for the
+// restarting columns and leaves one record (r.z per column).  Both take k_mrhs_restart's decision from the same
+// state and records; the cycle between them writes neither.
+template <int KP>
+__global__ __launch_bounds__(WG) void k_amg_mrhs_restart_r(unsigned n, const double *__restrict__ q,
+                                                           double *__restrict__ r,
+                                                           const lsb_mrhs_state *__restrict__ st,
+                                                           const double *__restrict__ rr_parts, unsigned nrr,
+                                                           int more) {
+  __shared__ double sred[4 * KP], srr[KP];
+  __shared__ int sact[KP];
+  const size_t npair = (size_t)n * (KP / 2), gsz = (size_t)gridDim.x * WG;
+  const d2v *q2 = (const d2v *)q;
+  restart_decision<KP>(st, rr_parts, nrr, more, sred, srr, sact);
+  const unsigned c0 = (2u * threadIdx.x) % KP;
+  const int a0 = sact[c0], a1 = sact[c0 + 1];
+  if (!(a0 | a1))
+    return;
+  for (size_t j = (size_t)blockIdx.x * WG + threadIdx.x; j < npair; j += gsz)
+    store_pairs({r}, {q2[j]}, j, a0, a1);
+}
+
+template <int KP>
+__global__ __launch_bounds__(WG) void k_amg_mrhs_restart_p(unsigned n, const double *__restrict__ r,
+                                                           const double *__restrict__ z, double *__restrict__ p,
+                                                           const lsb_mrhs_state *__restrict__ st,
+                                                           const double *__restrict__ rr_parts, unsigned nrr,
+                                                           int more, double *__restrict__ partials) {
+  __shared__ double sred[4 * KP], srr[KP], sout[KP];
+  __shared__ int sact[KP];
+  const size_t npair = (size_t)n * (KP / 2), gsz = (size_t)gridDim.x * WG;
+  const d2v *r2 = (const d2v *)r, *z2 = (const d2v *)z;
+  restart_decision<KP>(st, rr_parts, nrr, more, sred, srr, sact);
+  const unsigned c0 = (2u * threadIdx.x) % KP;
+  const int a0 = sact[c0], a1 = sact[c0 + 1];
+  double acc[1][2] = {{0.0, 0.0}};
+  if (a0 | a1) {
+    for (size_t j = (size_t)blockIdx.x * WG + threadIdx.x; j < npair; j += gsz) {
+      const d2v rv = r2[j], zv = z2[j];
+      store_pairs({p}, {zv}, j, a0, a1);
+      acc[0][0] += rv.x * zv.x, acc[0][1] += rv.y * zv.y;
+    }
+  }
+  wg_sum_cols<KP, 1>(acc, sred, sout);
+  if (threadIdx.x < KP)
+    partials[(size_t)blockIdx.x * KP + threadIdx.x] = sout[threadIdx.x];
 }
 
 // one workgroup, behind the sweep: the same decisions, written down
@@ -526,20 +614,12 @@ __global__ __launch_bounds__(WG) void k_mrhs_restart_state(lsb_mrhs_state *__res
 // --------------------------------------------------------------------------
 // Launchers (C ABI).  kp: 2, 4 or 8.
 // --------------------------------------------------------------------------
-static unsigned spmm_lanes(unsigned L) { return L == 2 || L == 4 || L == 8 || L == 16 || L == 32 ? L : 64; }
 template <int KP, bool RES>
-static void spmm_launch(unsigned L, unsigned g, unsigned n, const int *offs, const int *cols, const double *vals,
+static void spmm_launch(unsigned lanes, unsigned g, unsigned n, const int *offs, const int *cols, const double *vals,
                         const double *x, double *y, const double *bres, double *partials,
                         const struct lsb_mrhs_state *st, hipStream_t s) {
-  auto kern = k_spmm_csr<64, KP, RES>;
-  switch (L) {
-  case 2: kern = k_spmm_csr<2, KP, RES>; break;
-  case 4: kern = k_spmm_csr<4, KP, RES>; break;
-  case 8: kern = k_spmm_csr<8, KP, RES>; break;
-  case 16: kern = k_spmm_csr<16, KP, RES>; break;
-  case 32: kern = k_spmm_csr<32, KP, RES>; break;
-  }
-  kern<<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols, vals, x, y, bres, partials, st);
+  LANES_DISPATCH(lanes, (k_spmm_csr<L, KP, RES><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols, vals, x,
+                                                                y, bres, partials, st)));
 }
 
 extern "C" {
@@ -555,13 +635,13 @@ void lsb_k_mrhs_unpack(unsigned n, unsigned kp, unsigned nrhs, const int *perm, 
 }
 
 unsigned lsb_k_spmm_grid(unsigned n, unsigned lanes) {
-  return lsb_k_spmv_grid(LSB_SPMV_SUBWAVE, n, 0, spmm_lanes(lanes), 0);
+  return lsb_k_spmv_grid(LSB_SPMV_SUBWAVE, n, 0, row_lanes(lanes), 0);
 }
 
 void lsb_k_spmm_csr(unsigned kp, unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
                     const double *x, double *y, const double *bres, double *partials, unsigned *npartials,
                     const struct lsb_mrhs_state *st, void *stream) {
-  const unsigned L = spmm_lanes(lanes), g = lsb_k_spmm_grid(n, L);
+  const unsigned L = row_lanes(lanes), g = lsb_k_spmm_grid(n, L);
   if (npartials)
     *npartials = g;
   if (bres)
@@ -577,6 +657,24 @@ void lsb_k_mrhs_init(unsigned kp, unsigned n, const double *b, const double *din
   KP_DISPATCH(kp, (k_mrhs_init<KP><<<g, WG, 0, (hipStream_t)stream>>>(n, b, dinv, dc, x, r, p, partials2)));
 }
 
+void lsb_k_amg_mrhs_init(unsigned kp, unsigned n, const double *b, double *x, double *r, void *stream) {
+  KP_DISPATCH(kp, (k_amg_mrhs_init<KP><<<sweep_grid(n, kp), WG, 0, (hipStream_t)stream>>>(n, b, x, r)));
+}
+
+void lsb_k_amg_mrhs_init_p(unsigned kp, unsigned n, const double *b, const double *z, double *p, double *partials2,
+                           unsigned *npartials, void *stream) {
+  const unsigned g = sweep_grid(n, kp);
+  *npartials = g;
+  KP_DISPATCH(kp, (k_amg_dot2_m<KP, true><<<g, WG, 0, (hipStream_t)stream>>>(n, b, z, p, partials2, NULL)));
+}
+
+void lsb_k_amg_dot2_m(unsigned kp, unsigned n, const double *r, const double *z, double *records,
+                      unsigned *nrecords, const struct lsb_mrhs_state *st, void *stream) {
+  const unsigned g = sweep_grid(n, kp);
+  *nrecords = g;
+  KP_DISPATCH(kp, (k_amg_dot2_m<KP, false><<<g, WG, 0, (hipStream_t)stream>>>(n, r, z, NULL, records, st)));
+}
+
 void lsb_k_mrhs_init_state(unsigned kp, struct lsb_mrhs_state *st, const double *partials2, unsigned nparts,
                            double tol, int maxit, void *stream) {
   KP_DISPATCH(kp, (k_mrhs_init_state<KP><<<1, WG, 0, (hipStream_t)stream>>>(st, partials2, nparts, tol, maxit)));
@@ -587,16 +685,29 @@ void lsb_k_mrhs_update_xr(unsigned kp, unsigned n, const double *p, const double
                           unsigned npq, double *partials2, unsigned *npartials, void *stream) {
   const unsigned g = sweep_grid(n, kp);
   *npartials = g;
-  KP_DISPATCH(kp, (k_mrhs_update_xr<KP><<<g, WG, 0, (hipStream_t)stream>>>(n, p, q, dinv, dc, x, r, st, parity,
-                                                                           pq_parts, npq, partials2)));
+  KP_DISPATCH(kp, (k_mrhs_update_xr<KP, false><<<g, WG, 0, (hipStream_t)stream>>>(n, p, q, dinv, dc, x, r, st, parity,
+                                                                                  pq_parts, npq, partials2)));
+}
+
+void lsb_k_amg_mrhs_update_xr(unsigned kp, unsigned n, const double *p, const double *q, double *x, double *r,
+                              struct lsb_mrhs_state *st, int parity, const double *pq_parts, unsigned npq,
+                              void *stream) {
+  KP_DISPATCH(kp, (k_mrhs_update_xr<KP, true><<<sweep_grid(n, kp), WG, 0, (hipStream_t)stream>>>(
+                      n, p, q, NULL, 0.0, x, r, st, parity, pq_parts, npq, NULL)));
 }
 
 void lsb_k_mrhs_update_p(unsigned kp, unsigned n, const double *r, const double *dinv, double dc, double *p,
                          struct lsb_mrhs_state *st, int parity, const double *parts2, unsigned nparts2,
                          void *stream) {
   const unsigned g = sweep_grid(n, kp);
-  KP_DISPATCH(kp, (k_mrhs_update_p<KP><<<g, WG, 0, (hipStream_t)stream>>>(n, r, dinv, dc, p, st, parity, parts2,
-                                                                          nparts2)));
+  KP_DISPATCH(kp, (k_mrhs_update_p<KP, false><<<g, WG, 0, (hipStream_t)stream>>>(n, r, dinv, dc, p, st, parity, parts2,
+                                                                                 nparts2)));
+}
+
+void lsb_k_amg_mrhs_update_p(unsigned kp, unsigned n, const double *z, double *p, struct lsb_mrhs_state *st,
+                             int parity, const double *parts2, unsigned nparts2, void *stream) {
+  KP_DISPATCH(kp, (k_mrhs_update_p<KP, true><<<sweep_grid(n, kp), WG, 0, (hipStream_t)stream>>>(
+                      n, z, NULL, 0.0, p, st, parity, parts2, nparts2)));
 }
 
 void lsb_k_mrhs_restart(unsigned kp, unsigned n, const double *q, const double *dinv, double dc, double *r,
@@ -606,6 +717,21 @@ void lsb_k_mrhs_restart(unsigned kp, unsigned n, const double *q, const double *
   *npartials = g;
   KP_DISPATCH(kp, (k_mrhs_restart<KP><<<g, WG, 0, (hipStream_t)stream>>>(n, q, dinv, dc, r, p, st, rr_parts, nrr,
                                                                          more, partials)));
+}
+
+void lsb_k_amg_mrhs_restart_r(unsigned kp, unsigned n, const double *q, double *r, const struct lsb_mrhs_state *st,
+                              const double *rr_parts, unsigned nrr, int more, void *stream) {
+  KP_DISPATCH(kp, (k_amg_mrhs_restart_r<KP><<<sweep_grid(n, kp), WG, 0, (hipStream_t)stream>>>(n, q, r, st, rr_parts,
+                                                                                               nrr, more)));
+}
+
+void lsb_k_amg_mrhs_restart_p(unsigned kp, unsigned n, const double *r, const double *z, double *p,
+                              const struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr, int more,
+                              double *partials, unsigned *npartials, void *stream) {
+  const unsigned g = sweep_grid(n, kp);
+  *npartials = g;
+  KP_DISPATCH(kp, (k_amg_mrhs_restart_p<KP><<<g, WG, 0, (hipStream_t)stream>>>(n, r, z, p, st, rr_parts, nrr, more,
+                                                                               partials)));
 }
 
 void lsb_k_mrhs_restart_state(unsigned kp, struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr,

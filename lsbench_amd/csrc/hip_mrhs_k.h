@@ -1,7 +1,7 @@
 // What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_amg.hip, hip_amg_cheb.hip) share: the 16-byte pair
-// of the interleaved blocks, the fixed-order reductions of their per-column records, the verify round's
-// decision and the launchers' dispatch on the batch width.  Included by those files only, after
-// hip_kcommon.h.
+// of the interleaved blocks and its store gated per column, the fixed-order reductions of their per-column
+// records, the verify round's decision and the launchers' dispatch on the batch width.  Included by those files
+// only, after hip_kcommon.h.
 #ifndef LSB_HIP_MRHS_K_H
 #define LSB_HIP_MRHS_K_H
 #include "hip_kcommon.h"
@@ -68,6 +68,39 @@ __device__ __forceinline__ bool mrhs_misses(const lsb_pcg_state *c, double rr, d
   return c->status == LSB_STATUS_CONVERGED && c->bb > 0.0 && !(mrhs_true_relres(c, rr) <= tol);
 }
 
+// the restart decision of a verify round, per column into sact[KP]: the column was called converged, its
+// recomputed residual (the sum of the records rr_parts) misses the tolerance, and a round and iterations are left.
+// The same decision in every workgroup and in every launch of the round.  sred: 4 KP doubles, srr: KP.
+template <int KP>
+__device__ __forceinline__ void restart_decision(const lsb_mrhs_state *st, const double *rr_parts, unsigned nrr,
+                                                 int more, double *sred, double *srr, int *sact) {
+  wg_sum_records<KP>(rr_parts, nrr, sred, srr);
+  if (threadIdx.x < KP) {
+    const lsb_pcg_state *c = &st->c[threadIdx.x];
+    sact[threadIdx.x] = more && c->iters < c->maxit && mrhs_misses(c, srr[threadIdx.x], st->tol);
+  }
+  __syncthreads();
+}
+
+// Store pair j of NB blocks where at least one of the pair's two columns is active (a0 | a1): both -> one 16-byte
+// store per block, one -> its 8-byte half.  The half of a frozen column is never stored.
+template <int NB>
+__device__ __forceinline__ void store_pairs(double *const (&v)[NB], const d2v (&val)[NB], size_t j, int a0, int a1) {
+  if (a0 & a1) {
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+      ((d2v *)v[b])[j] = val[b];
+  } else if (a0) {
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+      v[b][2 * j] = val[b].x;
+  } else {
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+      v[b][2 * j + 1] = val[b].y;
+  }
+}
+
 // --------------------------------------------------------------------------
 // host helpers of the launchers.  kp: 2, 4 or 8.
 // --------------------------------------------------------------------------
@@ -85,22 +118,6 @@ static unsigned sweep_grid(unsigned n, unsigned kp) { return lsb_k_blas1_grid(n 
     case 1: { constexpr int KP = 2; CALL; } break;                             \
     case 2: { constexpr int KP = 4; CALL; } break;                             \
     default: { constexpr int KP = 8; CALL; } break;                            \
-    }                                                                          \
-  } while (0)
-
-
-// lanes per row of a matrix of the AMG hierarchy as the kernels are instantiated, and the dispatch on them
-static inline unsigned amg_lanes(unsigned L) { return L == 2 || L == 4 || L == 8 || L == 16 || L == 32 ? L : 64; }
-
-#define L_DISPATCH(lanes, CALL)                                                \
-  do {                                                                         \
-    switch (amg_lanes(lanes)) {                                                \
-    case 2: { constexpr int L = 2; CALL; } break;                              \
-    case 4: { constexpr int L = 4; CALL; } break;                              \
-    case 8: { constexpr int L = 8; CALL; } break;                              \
-    case 16: { constexpr int L = 16; CALL; } break;                            \
-    case 32: { constexpr int L = 32; CALL; } break;                            \
-    default: { constexpr int L = 64; CALL; } break;                            \
     }                                                                          \
   } while (0)
 

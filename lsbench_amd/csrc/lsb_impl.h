@@ -334,6 +334,27 @@ void lsb_k_mrhs_restart(unsigned kp, unsigned n, const double *q, const double *
                         double *partials, unsigned *npartials, void *stream);
 void lsb_k_mrhs_restart_state(unsigned kp, struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr,
                               const double *rz_parts, unsigned nrz, int more, void *stream);
+/* The same sweeps with z as a block of its own, written by a V-cycle on blocks (hip_mrhs_amg.hip) between them.
+ * records (r_c . z_c, then r_c . r_c) of a one-level hierarchy, which has no sweep to leave them; st: a no-op
+ * once st->running == 0 (NULL: always run) */
+void lsb_k_amg_dot2_m(unsigned kp, unsigned n, const double *r, const double *z, double *records,
+                      unsigned *nrecords, const struct lsb_mrhs_state *st, void *stream);
+/* x = 0, r = b ; behind the cycle on r: p = z and the records (b.z, b.b) for lsb_k_mrhs_init_state */
+void lsb_k_amg_mrhs_init(unsigned kp, unsigned n, const double *b, double *x, double *r, void *stream);
+void lsb_k_amg_mrhs_init_p(unsigned kp, unsigned n, const double *b, const double *z, double *p, double *partials2,
+                           unsigned *npartials, void *stream);
+/* lsb_k_mrhs_update_xr without dot products of its own ; p = z + beta p with the stop test on the cycle's records */
+void lsb_k_amg_mrhs_update_xr(unsigned kp, unsigned n, const double *p, const double *q, double *x, double *r,
+                              struct lsb_mrhs_state *st, int parity, const double *pq_parts, unsigned npq,
+                              void *stream);
+void lsb_k_amg_mrhs_update_p(unsigned kp, unsigned n, const double *z, double *p, struct lsb_mrhs_state *st,
+                             int parity, const double *parts2, unsigned nparts2, void *stream);
+/* opts.verify: r = q, then (behind the cycle) p = z and the records of r.z, for the restarting columns only */
+void lsb_k_amg_mrhs_restart_r(unsigned kp, unsigned n, const double *q, double *r, const struct lsb_mrhs_state *st,
+                              const double *rr_parts, unsigned nrr, int more, void *stream);
+void lsb_k_amg_mrhs_restart_p(unsigned kp, unsigned n, const double *r, const double *z, double *p,
+                              const struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr, int more,
+                              double *partials, unsigned *npartials, void *stream);
 
 /* ---- preconditioners with z as a vector (hip_precond_k.hip) -------------------- */
 void lsb_k_dot2(unsigned n, const double *r, const double *z, double *partials2,
@@ -434,7 +455,7 @@ void lsb_k_amg_tail(const struct lsb_amg_lvdev *lv, unsigned t, unsigned nlev, u
                     unsigned nc, unsigned clanes, const double *b0, double *out0, const struct lsb_pcg_state *st,
                     void *stream);
 
-/* ---- the V-cycle on blocks of kp = 2, 4 or 8 columns and the PCG sweeps around it (hip_mrhs_amg.hip) ----
+/* ---- the V-cycle on blocks of kp = 2, 4 or 8 columns (hip_mrhs_amg.hip; the PCG sweeps around it: hip_mrhs.hip) ----
  * Interleaved blocks as hip_mrhs.hip's on every level; each column's arithmetic is the single-column kernels'
  * (lsb_k_amg_first / _csr / _dense), so a column has their bits.  st: a no-op once st->running == 0 (NULL:
  * always run); never written.  records (LSB_AMG_SWEEP only, may be NULL): one record per workgroup of
@@ -446,25 +467,6 @@ void lsb_k_amg_csr_m(unsigned kp, int mode, const struct lsb_amg_mat *m, const d
                      const struct lsb_mrhs_state *st, void *stream);
 void lsb_k_amg_dense_m(unsigned kp, unsigned nc, unsigned lanes, const double *cinv, const double *b, double *out,
                        const struct lsb_mrhs_state *st, void *stream);
-/* records (r_c . z_c, then r_c . r_c) of a one-level hierarchy, which has no sweep to leave them */
-void lsb_k_amg_dot2_m(unsigned kp, unsigned n, const double *r, const double *z, double *records,
-                      unsigned *nrecords, const struct lsb_mrhs_state *st, void *stream);
-/* x = 0, r = b ; behind the cycle on r: p = z and the records (b.z, b.b) for lsb_k_mrhs_init_state */
-void lsb_k_amg_mrhs_init(unsigned kp, unsigned n, const double *b, double *x, double *r, void *stream);
-void lsb_k_amg_mrhs_init_p(unsigned kp, unsigned n, const double *b, const double *z, double *p, double *partials2,
-                           unsigned *npartials, void *stream);
-/* lsb_k_mrhs_update_xr without dot products of its own ; p = z + beta p with the stop test on the cycle's records */
-void lsb_k_amg_mrhs_update_xr(unsigned kp, unsigned n, const double *p, const double *q, double *x, double *r,
-                              struct lsb_mrhs_state *st, int parity, const double *pq_parts, unsigned npq,
-                              void *stream);
-void lsb_k_amg_mrhs_update_p(unsigned kp, unsigned n, const double *z, double *p, struct lsb_mrhs_state *st,
-                             int parity, const double *parts2, unsigned nparts2, void *stream);
-/* opts.verify: r = q, then (behind the cycle) p = z and the records of r.z, for the restarting columns only */
-void lsb_k_amg_mrhs_restart_r(unsigned kp, unsigned n, const double *q, double *r, const struct lsb_mrhs_state *st,
-                              const double *rr_parts, unsigned nrr, int more, void *stream);
-void lsb_k_amg_mrhs_restart_p(unsigned kp, unsigned n, const double *r, const double *z, double *p,
-                              const struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr, int more,
-                              double *partials, unsigned *npartials, void *stream);
 
 /* ---- the Chebyshev smoother on blocks of kp columns (hip_amg_cheb.hip): lsb_k_amg_cheb_first / lsb_k_amg_cheb
  * per column, bit for bit; d is a block as x is.  records / nrecords as lsb_k_amg_csr_m's sweep leaves them. */

@@ -1,7 +1,8 @@
 """Compile-time guard for the kernels of several right-hand sides (no GPU needed: hipcc cross-compiles gfx950),
-in the manner of test_bicgstab_resources.py: nothing in hip_mrhs.hip spills, the three sweeps of an iteration
-are within 64 VGPRs at occupancy 8 -- what the PCG sweeps are held to -- and the file holds the expected
-instantiations and nothing else."""
+in the manner of test_bicgstab_resources.py: nothing in hip_mrhs.hip spills, the sweeps of an iteration -- in
+both forms, z = dinv .* r and z as a block of its own (Lb0 / Lb1 of the two update kernels) -- and the streaming
+kernels around them are within 64 VGPRs at occupancy 8 -- what the PCG sweeps are held to -- and the file holds
+the expected instantiations and nothing else."""
 import os
 import re
 import shutil
@@ -22,6 +23,10 @@ CSRC = os.path.join(ROOT, "lsbench_amd", "csrc")
 SPMM_FOUND = {(2, 2): (28, 8), (4, 2): (30, 8), (8, 2): (30, 8), (16, 2): (32, 8), (32, 2): (32, 8), (64, 2): (34, 8),
               (2, 4): (44, 8), (4, 4): (44, 8), (8, 4): (46, 8), (16, 4): (46, 8), (32, 4): (48, 8), (64, 4): (48, 8),
               (2, 8): (76, 6), (4, 8): (76, 6), (8, 8): (78, 6), (16, 8): (78, 6), (32, 8): (80, 6), (64, 8): (80, 6)}
+# the streaming sweeps, held to 64 VGPRs at occupancy 8: those of the diagonal preconditioners and those with z as
+# a block of its own (the last four stems and the Lb1 forms of the two update kernels)
+SWEEPS = ("k_mrhs_initI", "k_mrhs_update_xrI", "k_mrhs_update_pI", "k_mrhs_restartI", "k_amg_mrhs_initI",
+          "k_amg_dot2_mI", "k_amg_mrhs_restart_rI", "k_amg_mrhs_restart_pI")
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"),
@@ -44,18 +49,24 @@ def test_mrhs_kernels_have_no_spills_and_the_sweeps_full_occupancy(tmp_path):
         m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
         if m and name:
             info[name][m.group(1).strip()] = int(m.group(2))
-    # one per batch width of the sweeps and the state kernels, 6 lane counts x 3 widths x {product, residual} of the
-    # SpMM, pack / unpack
-    for stem, count in (("k_mrhs_initI", 3), ("k_mrhs_init_stateI", 3), ("k_mrhs_update_xrI", 3),
-                        ("k_mrhs_update_pI", 3), ("k_mrhs_restartI", 3), ("k_mrhs_restart_stateI", 3),
-                        ("k_spmm_csrI", 36), ("k_mrhs_pack", 1), ("k_mrhs_unpack", 1)):
+    # one per batch width of the sweeps and the state kernels -- 3 widths x {dinv, z block} of the two update sweeps
+    # and 3 x {records, records and p = z} of the two-block record kernel --, 6 lane counts x 3 widths x {product,
+    # residual} of the SpMM, pack / unpack
+    for stem, count in (("k_mrhs_initI", 3), ("k_mrhs_init_stateI", 3), ("k_mrhs_update_xrI", 6),
+                        ("k_mrhs_update_pI", 6), ("k_mrhs_restartI", 3), ("k_mrhs_restart_stateI", 3),
+                        ("k_amg_mrhs_initI", 3), ("k_amg_dot2_mI", 6), ("k_amg_mrhs_restart_rI", 3),
+                        ("k_amg_mrhs_restart_pI", 3), ("k_spmm_csrI", 36), ("k_mrhs_pack", 1), ("k_mrhs_unpack", 1)):
         assert len([k for k in info if stem in k]) == count, (stem, sorted(info))
-    assert len(info) == 56  # nothing else lives in the file
+    for stem in ("k_mrhs_update_xrI", "k_mrhs_update_pI", "k_amg_dot2_mI"):  # both forms at every width
+        assert sorted(re.search(r"ILi(\d)ELb([01])E", k).groups() for k in info if stem in k) == \
+            sorted((str(kp), z) for kp in (2, 4, 8) for z in "01"), (stem, sorted(info))
+    assert len(info) == 77  # nothing else lives in the file
     for k, v in info.items():
         assert v["ScratchSize"] == 0, (k, v)
-    for k, v in info.items():
-        if any(stem in k for stem in ("k_mrhs_initI", "k_mrhs_update_xrI", "k_mrhs_update_pI", "k_mrhs_restartI")):
-            assert v["VGPRs"] <= 64 and v["Occupancy"] == 8, (k, v)
+    sweeps = [k for k in info if any(stem in k for stem in SWEEPS)]
+    assert len(sweeps) == 33
+    for k in sweeps:
+        assert info[k]["VGPRs"] <= 64 and info[k]["Occupancy"] == 8, (k, info[k])
     spmm = {}
     for k, v in info.items():
         m = re.search(r"k_spmm_csrILi(\d+)ELi(\d+)ELb([01])E", k)
