@@ -1376,21 +1376,25 @@ __device__ __forceinline__ void colp_single(unsigned s, unsigned n, unsigned lan
   }
 }
 
-#define COLP_ST(PTR, V, BIT)                                                                   \
-  do {                                                                                         \
-    if (NT & (BIT))                                                                            \
-      __builtin_nontemporal_store((V), (sell_d2v *)(PTR));                                     \
-    else                                                                                       \
-      *(sell_d2v *)(PTR) = (V);                                                                \
-  } while (0)
+// How the streamed results of a column leave the L2 (hip_kcommon.h: slice_store16): nothing either launch writes is
+// read again in the same launch -- neighbours form p' from r and p, never from the stored p' -- so what a store leaves
+// dirty in the L2 is only flushed at the launch's end, in front of the next launch's first load.  Measured on the
+// 10 M-row 5-point grid (profiles/r12_col_launch_cost.txt), us per iteration: p' and x nt (the form before) 95.6-96.0,
+// sc1 97.0, sc1 nt 94.3-94.5; with that, r' plain 94.3-94.5, sc1 94.1.  The same bits whatever the policy.
+constexpr int COL_ST_PX = ST_SC1_NT; // k_pcg_col_px's p' and x (where NT asks for a streaming store at all)
+constexpr int COL_ST_R = ST_SC1;     // k_pcg_col_r's r'
+// Records of the launch before that a thread of these kernels sums with its loads in flight together
+// (hip_kcommon.h: wg_sum_parts): all of a resident grid's in one batch
+constexpr int COL_PARTS_U = LSB_TMPL_COL_GRID(1) / WG;
+#define COLP_ST(PTR, V, BIT) slice_store16<(NT & (BIT)) ? COL_ST_PX : ST_KEEP>((PTR), lane, (V))
 #define COLP_STORE(OUT, LROW, WITH_Q, WITH_XP)                                                 \
   do {                                                                                         \
     if (WITH_Q)                                                                                \
-      COLP_ST(q + (LROW) + 2 * lane, (OUT).q, 2);                                              \
+      COLP_ST(q + (LROW), (OUT).q, 2);                                                         \
     if (WITH_XP) {                                                                             \
       if (XUPD)                                                                                \
-        COLP_ST(x + ((LROW) + Du) + 2 * lane, (OUT).x, 1);                                     \
-      COLP_ST(pnew + ((LROW) + Du) + 2 * lane, (OUT).p, 2);                                    \
+        COLP_ST(x + ((LROW) + Du), (OUT).x, 1);                                                \
+      COLP_ST(pnew + ((LROW) + Du), (OUT).p, 2);                                               \
     }                                                                                          \
   } while (0)
 
@@ -1420,7 +1424,7 @@ __global__ __launch_bounds__(WG, NF == 2 ? 3 : 5) void k_pcg_col_px(
   const double rz_old = st->rz[parity], thresh2 = st->thresh2, alpha = st->alpha[0], alpha2 = st->alpha[1];
   const unsigned i0 = plan[xcd], i1 = plan[xcd + 1];
   double v[2];
-  wg_sum_partials<2>(parts2, nparts2, v, sred);
+  wg_sum_parts<2, COL_PARTS_U>(parts2, nparts2, v, sred);
   if (stopped)
     return;
   const double rz_new = v[0], rr = v[1];
@@ -1559,7 +1563,7 @@ __global__ __launch_bounds__(WG, 5) void k_pcg_col_r(
   const double rz = st->rz[parity];
   const unsigned i0 = plan[xcd], i1 = plan[xcd + 1];
   double pqv[1];
-  wg_sum_partials<1>(pq_parts, npq, pqv, sred);
+  wg_sum_parts<1, COL_PARTS_U>(pq_parts, npq, pqv, sred);
   if (stopped)
     return;
   if (pad) { // the launch before counted the maxit-th iteration (and did its x update): stop here
@@ -1587,7 +1591,7 @@ __global__ __launch_bounds__(WG, 5) void k_pcg_col_r(
   do {                                                                                         \
     sell_d2v rn_;                                                                              \
     rn_.x = (RV).x - alpha * (A0), rn_.y = (RV).y - alpha * (A1);                              \
-    *(sell_d2v *)(r + (LROW) + 2 * lane) = rn_;                                                \
+    slice_store16<COL_ST_R>(r + (LROW), lane, rn_);                                            \
     acc[0] += rn_.x * (dc * rn_.x);                                                            \
     acc[0] += rn_.y * (dc * rn_.y);                                                            \
     acc[1] += rn_.x * rn_.x;                                                                   \
@@ -2130,7 +2134,8 @@ void lsb_k_pcg_col_px(unsigned grid_cap, unsigned period, const unsigned *plan, 
   /* x, p' and q streamed nontemporally (NT = 3; measured against 0 / 1 / 2 on config 4: 950.5 / 950.3 / 905.7 /
    * 894.1 us per iteration, profiles/r04_px.txt -- and on config 3's cache-scale vectors, with the vectors in one
    * slab and k_pcg_col_r reversed: 100.1 / 96.5-96.8 / 97.4-97.5 against 95.6-95.9 us, profiles/r06_col_cache.txt:
-   * one mask for every size, so it stays a template constant) */
+   * one mask for every size, so it stays a template constant).  What "nontemporal" means for the STORES is
+   * COL_ST_PX: written through the L2 (sc1 nt), not left dirty in it. */
   static decltype(&k_pcg_col_px<1, 3, false>) const kern[2][2] = { /* [nfar - 1][xupd] */
       {k_pcg_col_px<1, 3, false>, k_pcg_col_px<1, 3, true>},
       {k_pcg_col_px<2, 3, false>, k_pcg_col_px<2, 3, true>}};
