@@ -683,13 +683,42 @@ lsb_hip_solver *lsb_hip_solver_create_dist(const struct csr *A_rows,
                                            const struct lsb_hip_opts *o);
 void lsb_hip_solver_destroy(lsb_hip_solver *s);
 
-/* Jacobi-PCG from x0 = 0.  Host buffers, local rows only (length n_local);
+/* One solve from x0 = 0.  Host buffers, local rows only (length n_local);
  * H2D of b and D2H of x are outside res->seconds. */
 int lsb_hip_solver_solve(lsb_hip_solver *s, const double *b, double *x,
                          struct lsb_hip_result *res);
 /* Same with device-resident b and x (length n_local each). */
 int lsb_hip_solver_solve_dev(lsb_hip_solver *s, const double *d_b, double *d_x,
                              struct lsb_hip_result *res);
+/* The same solve from an initial guess: d_x (x) holds x0 on entry and the solution on return.  Every solver that
+ * solve[_dev] serves is served -- every Krylov method, preconditioner and PCG form, the persistent one-launch solve,
+ * mixed precision, re-numbered and line-padded solvers, shards: q = S x0 is formed the way a recomputed residual is,
+ * one sweep leaves r0 = b - q with r0.r0 and b.b, the solver's own driver solves S e = r0 from e = 0, x = x0 + e.
+ * The stop rule stays relative to ||b||, never to ||b - S x0||: the run stops at ||r|| <= tol ||b||, res->relres is
+ * relative to ||b||, res->iters counts the iterations run from x0 and opts.maxit caps them; opts.verify and the
+ * refinement of LSB_PREC_MIXED work on the recomputed b - S x as in a cold solve (under BiCGSTAB and Richardson
+ * through correction solves S e = b - S x, where their cold solve restarts in place; GMRES recomputes nothing).
+ * opts.verify here forms b - S x off the CSR arrays as in twice the working precision: true_relres is good to 1e-3
+ * of itself down to the rounding level of an fp64 product, where the cold solve's fp64 value is not.
+ *   b = 0: x = 0, CONVERGED, 0 iterations -- the cold rule, whatever x0 holds.
+ *   ||b - S x0|| <= tol ||b|| with tol > 0: CONVERGED, 0 iterations, x is x0 untouched, bit for bit.
+ *   x0 = 0: x, iters, status and relres of solve[_dev] (x compares equal; the sign of a zero may differ).  With
+ *   opts.verify the two recompute b - S x differently (below): x, iters and status are still the cold solve's as
+ *   long as neither needs a correction run, relres = true_relres differ by the rounding of the cold solve's fp64
+ *   residual, at most (len + 2) 2^-53 || |S||x| + |b| || / ||b|| with len the longest row; where a recomputed
+ *   residual sits that close to tol, one of the two may run a correction the other does not.
+ * Return codes as for solve[_dev]; 2 leaves x untouched.  res->spmvs counts the product S x0. */
+int lsb_hip_solver_solve_x0(lsb_hip_solver *s, const double *b, double *x,
+                            struct lsb_hip_result *res);
+int lsb_hip_solver_solve_x0_dev(lsb_hip_solver *s, const double *d_b, double *d_x,
+                                struct lsb_hip_result *res);
+/* ||b_c - S x0_c|| / ||b_c|| of the columns of the last solve, if that was one from an initial guess (solve_x0[_dev]:
+ * nrhs = 1; solve_multi_x0_dev: its nrhs); 0 where b_c = 0.  Accuracy: a single solve forms b - S x0 with the solver's
+ * fp64 SpMV, so its value (and the decision ||b - S x0|| <= tol ||b||) carries an absolute error of about
+ * 2^-53 || |S||x0| + |b| || / ||b|| -- a start at 1e-12 .. 1e-13 of a well-scaled system is good to a per cent or so;
+ * a batch forms it with the compensated SpMM of its verify rounds, good to about 1e-15 of itself.  struct
+ * lsb_hip_result keeps its layout: this is where the starting residual is read.  2 if the last solve was a cold one, if nrhs does not match, or on null arguments. */
+int lsb_hip_solver_start_relres(const lsb_hip_solver *s, unsigned nrhs, double *out);
 /* y_local = Op * x: d_x holds this rank's rows (length n_local); remote
  * entries are exchanged first when the solver is distributed. */
 int lsb_hip_solver_spmv_dev(lsb_hip_solver *s, const double *d_x, double *d_y);
@@ -762,6 +791,15 @@ int lsb_hip_solver_solve_multi_dev(lsb_hip_solver *s, unsigned nrhs, const doubl
                                    double *d_X, size_t ldx, struct lsb_hip_result *res);
 int lsb_hip_solver_solve_multi(lsb_hip_solver *s, unsigned nrhs, const double *B, size_t ldb,
                                double *X, size_t ldx, struct lsb_hip_result *res);   /* host buffers */
+/* solve_multi_dev from an initial guess: column c of d_X holds x0_c on entry.  Serves and refuses exactly what
+ * solve_multi_dev does (2 leaves d_X untouched); nrhs == 1 is lsb_hip_solver_solve_x0_dev.  No correction solve here:
+ * the batch starts in place on the device -- r = b - S x0 by the SpMM of a verify round, p = M^-1 r, and per column
+ * b_c = 0 -> x_c = 0, CONVERGED; r.r <= tol^2 b.b -> CONVERGED with 0 iterations, x_c the bits of x0_c; else the
+ * column runs, its iterations counted from x0, its threshold tol^2 b.b.  A column with x0_c = 0 has the bits, iters
+ * and status of the same column in solve_multi_dev.  Only n_local doubles of a column are read and written: the
+ * slack behind it stays the caller's.  lsb_hip_solver_start_relres(s, nrhs, out) reads the starting residuals. */
+int lsb_hip_solver_solve_multi_x0_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_B, size_t ldb,
+                                      double *d_X, size_t ldx, struct lsb_hip_result *res);
 /* bytes one iteration of the batch must move: 12 nnz + 4 (n + 1) + 8 n (11 Kp + 2 [the diagonal is a
  * vector]) with n the internal row count and Kp the batch width -- the CSR arrays once whatever the width,
  * 2 passes of the SpMM (x once, y once) and the 9 of the classic form's sweeps per column, the diagonal once

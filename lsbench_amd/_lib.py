@@ -241,11 +241,15 @@ SIGNATURES = {
     "lsb_hip_solver_destroy": (None, [_vp]),
     "lsb_hip_solver_solve": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
     "lsb_hip_solver_solve_dev": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
+    "lsb_hip_solver_solve_x0": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
+    "lsb_hip_solver_solve_x0_dev": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
+    "lsb_hip_solver_start_relres": (_i, [_vp, _u, C.POINTER(C.c_double)]),
     "lsb_hip_solver_spmv_dev": (_i, [_vp, _vp, _vp]),
     "lsb_hip_solver_spmv_inner_dev": (_i, [_vp, _vp, _vp, _vp]),
     "lsb_hip_solver_spmm_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
     "lsb_hip_solver_solve_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_solve_multi": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
+    "lsb_hip_solver_solve_multi_x0_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_multi_iteration_bytes": (C.c_ulonglong, [_vp, _u]),
     "lsb_hip_solver_precond_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
     "lsb_hip_solver_precond_dev": (_i, [_vp, _vp, _vp]),

@@ -259,19 +259,38 @@ class Solver:
         self.n_global = lib.lsb_hip_solver_nrows_global(h)
         self.nnz_local = lib.lsb_hip_solver_nnz_local(h)
 
-    def solve(self, b):
-        x = np.empty(self.n_local, np.float64)
+    def solve(self, b, x0=None):
+        """x0: an initial guess (n_local); None solves from zero."""
         b = np.ascontiguousarray(b, np.float64)
         res = L.Result()
-        L.check(L.load().lsb_hip_solver_solve(self._h, b.ctypes.data, x.ctypes.data,
-                                              C.byref(res)), "solve")
+        if x0 is None:
+            x = np.empty(self.n_local, np.float64)
+            L.check(L.load().lsb_hip_solver_solve(self._h, b.ctypes.data, x.ctypes.data,
+                                                  C.byref(res)), "solve")
+            return x, res
+        x = np.array(x0, dtype=np.float64, order="C")
+        if x.shape != (self.n_local,):
+            raise ValueError("solve: x0 must hold n_local values")
+        L.check(L.load().lsb_hip_solver_solve_x0(self._h, b.ctypes.data, x.ctypes.data,
+                                                 C.byref(res)), "solve_x0")
         return x, res
 
-    def solve_dev(self, d_b, d_x):
+    def solve_dev(self, d_b, d_x, warm=False):
+        """warm: d_x holds the initial guess on entry."""
         res = L.Result()
-        L.check(L.load().lsb_hip_solver_solve_dev(self._h, _ptr(d_b), _ptr(d_x),
-                                                  C.byref(res)), "solve_dev")
+        lib = L.load()
+        if warm:
+            L.check(lib.lsb_hip_solver_solve_x0_dev(self._h, _ptr(d_b), _ptr(d_x), C.byref(res)), "solve_x0_dev")
+        else:
+            L.check(lib.lsb_hip_solver_solve_dev(self._h, _ptr(d_b), _ptr(d_x), C.byref(res)), "solve_dev")
         return res
+
+    def start_relres(self, nrhs=1):
+        """||b_c - S x0_c|| / ||b_c|| of the nrhs columns of the last solve, which must have been a warm-started
+        one of that many columns (0 where b_c = 0)."""
+        out = (C.c_double * max(nrhs, 1))()
+        L.check(L.load().lsb_hip_solver_start_relres(self._h, nrhs, out), "start_relres")
+        return np.array(out[:nrhs])
 
     def spmv_dev(self, d_x, d_y):
         L.check(L.load().lsb_hip_solver_spmv_dev(self._h, _ptr(d_x), _ptr(d_y)), "spmv_dev")
@@ -291,15 +310,19 @@ class Solver:
             raise ValueError("spmm_dev: X and Y hold different numbers of columns")
         L.check(L.load().lsb_hip_solver_spmm_dev(self._h, k, px, ldx, py, ldy), "spmm_dev")
 
-    def solve_multi_dev(self, d_B, d_X):
+    def solve_multi_dev(self, d_B, d_X, warm=False):
         """x_c = S^-1 b_c for the nrhs columns held as the ROWS of two 2-D device tensors; returns the list of
-        their Results."""
+        their Results.  warm: the rows of d_X hold the columns' initial guesses on entry."""
         pb, k, ldb = self._block(d_B, "solve_multi_dev")
         px, kx, ldx = self._block(d_X, "solve_multi_dev")
         if k != kx:
             raise ValueError("solve_multi_dev: B and X hold different numbers of columns")
         res = (L.Result * max(k, 1))()
-        L.check(L.load().lsb_hip_solver_solve_multi_dev(self._h, k, pb, ldb, px, ldx, res), "solve_multi_dev")
+        lib = L.load()
+        if warm:
+            L.check(lib.lsb_hip_solver_solve_multi_x0_dev(self._h, k, pb, ldb, px, ldx, res), "solve_multi_x0_dev")
+        else:
+            L.check(lib.lsb_hip_solver_solve_multi_dev(self._h, k, pb, ldb, px, ldx, res), "solve_multi_dev")
         return list(res)[:k]
 
     def solve_multi(self, B):

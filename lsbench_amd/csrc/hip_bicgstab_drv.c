@@ -171,7 +171,7 @@ int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struc
   bcg_allreduce(sv, 4, 1);
   EACH(i, s, w)
     lsb_k_bcg_init_state(w->st, multi ? sv->bcg_red + (size_t)i * BCG_RED + 4 : s->d_parts2,
-                         multi ? 1u : w->np2, sv->o.tol, (int)sv->o.maxit, g_stream);
+                         multi ? 1u : w->np2, sv->tol_run, (int)sv->o.maxit, g_stream);
   struct lsb_hip_result r;
   memset(&r, 0, sizeof r);
   r.true_relres = -1.0;
@@ -180,7 +180,7 @@ int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struc
   hst[0].c.iters = 0;
   for (int round = 0;; round++) {
     bcg_run(sv, &enq, hint_slot(sv->hint_iters, round));
-    if (!(sv->o.verify && hst[0].c.status == LSB_STATUS_CONVERGED && sv->o.tol > 0.0 && hst[0].c.bb > 0.0))
+    if (!(sv->verify_run && hst[0].c.status == LSB_STATUS_CONVERGED && sv->tol_run > 0.0 && hst[0].c.bb > 0.0))
       break;
     /* "converged" is reported only for the residual RECOMPUTED from x; where that one misses the
      * tolerance the iteration restarts on it (r = b - Op x, r^ = p = r, x kept), LSB_MAX_CORRECTIONS

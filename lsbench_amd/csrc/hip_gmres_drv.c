@@ -81,7 +81,7 @@ int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
     EACH(i, s, w) {
       double *red = sv->gm_red + (size_t)i * GM_RED;
       lsb_k_gm_begin(w->st, sv->multi ? red : w->parts, sv->multi ? 1u : lsb_k_gm_grid(s->n),
-                     sv->o.tol, (int)sv->o.maxit, m, cycle == 0, g_stream);
+                     sv->tol_run, (int)sv->o.maxit, m, cycle == 0, g_stream);
     }
     for (int j = 0; j < m; j++) {
       /* v_j = (r or w) / norm ; z = D^-1 v_j ; w = Op z */

@@ -262,37 +262,47 @@ __global__ __launch_bounds__(WG) void k_amg_dot2_m(unsigned n, const double *__r
     records[(size_t)blockIdx.x * 2 * KP + threadIdx.x] = sout[threadIdx.x];
 }
 
+// bb_parts == NULL: a batch from x0 = 0, the records are k_mrhs_init's (r.z, b.b).  Else a batch from an initial
+// guess: the records hold (r.z, r.r) of r = b - S x0, b.b comes from k_mrhs_x0_bb's, and a column that starts
+// within the tolerance is CONVERGED with 0 iterations, its x untouched.
 template <int KP>
 __global__ __launch_bounds__(WG) void k_mrhs_init_state(lsb_mrhs_state *__restrict__ st,
                                                         const double *__restrict__ partials2, unsigned nparts,
+                                                        const double *__restrict__ bb_parts, unsigned nbb,
                                                         double tol, int maxit) {
-  __shared__ double sred[8 * KP], s2[2 * KP];
+  __shared__ double sred[8 * KP], s2[2 * KP], sbb[2 * KP];
   __shared__ int srun[KP];
   wg_sum_records<2 * KP>(partials2, nparts, sred, s2);
+  if (bb_parts)
+    wg_sum_records<2 * KP>(bb_parts, nbb, sred, sbb);
   const unsigned t = threadIdx.x;
   if (t < KP) {
     lsb_pcg_state *c = &st->c[t];
-    const double rz = s2[t], bb = s2[KP + t];
+    const double rz = s2[t], rr = s2[KP + t], bb = bb_parts ? sbb[KP + t] : rr;
     c->rz[0] = rz, c->rz[1] = 0.0;
     c->alpha[0] = c->alpha[1] = 0.0;
     c->bb = bb;
     c->thresh2 = tol * tol * bb;
-    c->rr = bb;
+    c->rr = rr;
     c->pq = 0.0;
     c->iters = 0;
     c->maxit = maxit;
     c->pad = 0, c->xpend = 0, c->pad2_ = 0;
     // b_c == 0 => x_c = 0 is the solution (the padding columns of a batch among them)
-    c->status = (bb == 0.0) ? LSB_STATUS_CONVERGED : (maxit <= 0 ? LSB_STATUS_MAXIT : LSB_STATUS_RUNNING);
+    c->status = (bb == 0.0 || (bb_parts && rr <= c->thresh2))
+                    ? LSB_STATUS_CONVERGED
+                    : (maxit <= 0 ? LSB_STATUS_MAXIT : LSB_STATUS_RUNNING);
     srun[t] = c->status == LSB_STATUS_RUNNING;
     st->true_relres[t] = -1.0;
     st->corrections[t] = 0;
+    st->start_relres[t] = bb > 0.0 ? sqrt(rr / bb) : 0.0;
   }
   if (t >= KP && t < LSB_MRHS_MAX) { // the records a narrower batch does not use
     memset(&st->c[t], 0, sizeof st->c[t]);
     st->c[t].status = LSB_STATUS_CONVERGED;
     st->true_relres[t] = -1.0;
     st->corrections[t] = 0;
+    st->start_relres[t] = 0.0;
   }
   __syncthreads();
   if (t == 0) {
@@ -676,8 +686,9 @@ void lsb_k_amg_dot2_m(unsigned kp, unsigned n, const double *r, const double *z,
 }
 
 void lsb_k_mrhs_init_state(unsigned kp, struct lsb_mrhs_state *st, const double *partials2, unsigned nparts,
-                           double tol, int maxit, void *stream) {
-  KP_DISPATCH(kp, (k_mrhs_init_state<KP><<<1, WG, 0, (hipStream_t)stream>>>(st, partials2, nparts, tol, maxit)));
+                           const double *bb_parts, unsigned nbb, double tol, int maxit, void *stream) {
+  KP_DISPATCH(kp, (k_mrhs_init_state<KP><<<1, WG, 0, (hipStream_t)stream>>>(st, partials2, nparts, bb_parts, nbb, tol,
+                                                                            maxit)));
 }
 
 void lsb_k_mrhs_update_xr(unsigned kp, unsigned n, const double *p, const double *q, const double *dinv, double dc,

@@ -1,9 +1,10 @@
-/* Several right-hand sides: host driver (kernels: hip_mrhs.hip, hip_mrhs_amg.hip). */
+/* Several right-hand sides: host driver (kernels: hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_amg.hip). */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
 /*
- * lsb_hip_solver_solve_multi[_dev]: nrhs INDEPENDENT Jacobi-PCG recurrences (x0 = 0, M^-1 = diag(dinv):
+ * lsb_hip_solver_solve_multi[_dev]: nrhs INDEPENDENT Jacobi-PCG recurrences (x0 = 0, or -- solve_multi_x0_dev -- the
+ * X0 the caller's X holds: mrhs_batch; M^-1 = diag(dinv):
  * Jacobi, l1-Jacobi or none) advanced by the same launches -- per iteration the SpMM Q = S P off the
  * shard's CSR arrays with its fused per-column p.q, k_mrhs_update_xr and k_mrhs_update_p.  Every column has
  * its own alpha, beta, norms, iteration count and status (lsb_mrhs_state); a column that has stopped is
@@ -81,7 +82,7 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
 void mrhs_free(lsb_hip_solver *sv) {
   for (int k = 0; k < 3; k++) {
     graph_drop(&sv->mr[k].g);
-    lsb_hip_free(sv->mr[k].mem), lsb_hip_free(sv->mr[k].amg_mem);
+    lsb_hip_free(sv->mr[k].mem), lsb_hip_free(sv->mr[k].amg_mem), lsb_hip_free(sv->mr[k].parts_bb);
     free(sv->mr[k].av);
     memset(&sv->mr[k], 0, sizeof sv->mr[k]);
   }
@@ -180,9 +181,10 @@ static void mrhs_run(lsb_hip_solver *sv, struct mrhs_work *w, unsigned *hint) {
   run_loop(sv, &r, hint);
 }
 
-/* one batch: nb <= 8 columns of the caller's blocks */
+/* one batch: nb <= 8 columns of the caller's blocks; start != NULL: from the X0 that d_X holds, and where the
+ * columns' starting residuals go */
 static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_t ldb, double *d_X, size_t ldx,
-                       struct lsb_hip_result *res) {
+                       struct lsb_hip_result *res, double *start) {
   struct mrhs_work *w = mrhs_setup(sv, batch_width(nb));
   const struct shard *s = &sv->sh[0];
   struct lsb_mrhs_state *hst = sv->mr_hst;
@@ -190,13 +192,33 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
   unsigned np2 = 0, npq = 0, nverify = 0;
   const double t0 = wall_seconds();
   lsb_k_mrhs_pack(n, kp, nb, sv->d_perm, d_B, ldb, w->b, g_stream);
-  if (mrhs_amg(sv)) { /* x = 0, r = b ; z = M^-1 b ; p = z and (b.z, b.b) */
-    lsb_k_amg_mrhs_init(kp, n, w->b, w->x, w->r, g_stream);
-    mrhs_cycle(sv, w, NULL, NULL, NULL);
-    lsb_k_amg_mrhs_init_p(kp, n, w->b, w->z, w->p, w->parts2, &np2, g_stream);
-  } else
-    lsb_k_mrhs_init(kp, n, w->b, DINV(s), w->x, w->r, w->p, w->parts2, &np2, g_stream);
-  lsb_k_mrhs_init_state(kp, w->st, w->parts2, np2, sv->o.tol, (int)sv->o.maxit, g_stream);
+  if (start) {
+    /* The batch's state lives on the device, with b.b and the threshold per column, so a start from X0 is no
+     * correction solve: x = X0, r = b - S x0 by the SpMM of a verify round, p = M^-1 r through the un-gated
+     * cycle or the diagonal, and a state from scratch in which the columns that start within the tolerance (or
+     * have b = 0: their x is zeroed) are frozen.  A column with x0 = 0 gets the bits of the branch below. */
+    unsigned nbb = 0;
+    if (!w->parts_bb)
+      w->parts_bb = (double *)lsb_hip_malloc((size_t)LSB_STREAM_GRID_CAP * 2 * kp * sizeof(double));
+    lsb_k_mrhs_pack(n, kp, nb, sv->d_perm, d_X, ldx, w->x, g_stream);
+    lsb_k_mrhs_x0_bb(kp, n, w->b, w->parts_bb, &nbb, g_stream);
+    spmm_shard(sv, w, w->x, w->r, w->b, &npq, NULL);
+    if (mrhs_amg(sv)) {
+      lsb_k_amg_mrhs_x0_start(kp, n, w->x, w->parts_bb, nbb, g_stream);
+      mrhs_cycle(sv, w, NULL, NULL, NULL);
+      lsb_k_amg_mrhs_init_p(kp, n, w->r, w->z, w->p, w->parts2, &np2, g_stream);
+    } else
+      lsb_k_mrhs_x0_start(kp, n, w->r, DINV(s), w->x, w->p, w->parts_bb, nbb, w->parts2, &np2, g_stream);
+    lsb_k_mrhs_init_state(kp, w->st, w->parts2, np2, w->parts_bb, nbb, sv->o.tol, (int)sv->o.maxit, g_stream);
+  } else {
+    if (mrhs_amg(sv)) { /* x = 0, r = b ; z = M^-1 b ; p = z and (b.z, b.b) */
+      lsb_k_amg_mrhs_init(kp, n, w->b, w->x, w->r, g_stream);
+      mrhs_cycle(sv, w, NULL, NULL, NULL);
+      lsb_k_amg_mrhs_init_p(kp, n, w->b, w->z, w->p, w->parts2, &np2, g_stream);
+    } else
+      lsb_k_mrhs_init(kp, n, w->b, DINV(s), w->x, w->r, w->p, w->parts2, &np2, g_stream);
+    lsb_k_mrhs_init_state(kp, w->st, w->parts2, np2, NULL, 0, sv->o.tol, (int)sv->o.maxit, g_stream);
+  }
   hst[0].nspmm = 0;
   for (int round = 0;; round++) {
     mrhs_run(sv, w, hint_slot(w->hint, round));
@@ -235,8 +257,10 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
       r.relres = r.true_relres;
     r.corrections = (unsigned)hst[0].corrections[c];
     r.seconds = seconds;
-    r.spmvs = (unsigned)hst[0].nspmm + nverify;
+    r.spmvs = (unsigned)hst[0].nspmm + nverify + (start ? 1u : 0u);
     res[c] = r;
+    if (start)
+      start[c] = hst[0].start_relres[c];
   }
 }
 
@@ -245,23 +269,36 @@ static int multi_args_bad(const lsb_hip_solver *sv, unsigned nrhs, const void *a
   return !sv || !a || !b || nrhs == 0 || lda < sv->n_user || ldb < sv->n_user;
 }
 
-int lsb_hip_solver_solve_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
-                                   size_t ldx, struct lsb_hip_result *res) {
+static int solve_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X, size_t ldx,
+                           struct lsb_hip_result *res, int warm) {
   if (!lsb_initialized)
     return 1;
   if (multi_args_bad(sv, nrhs, d_B, ldb, d_X, ldx) || !mrhs_serves(sv))
     return 2;
   if (nrhs == 1)
-    return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
+    return warm ? lsb_hip_solver_solve_x0_dev(sv, d_B, d_X, res) : lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
   struct lsb_hip_result *tmp = res ? res : lsb_calloc(struct lsb_hip_result, nrhs);
+  double *start = warm ? start_relres_slots(sv, nrhs) : NULL;
+  if (!warm)
+    sv->start_n = 0;
   for (unsigned c0 = 0; c0 < nrhs; c0 += LSB_MRHS_MAX) {
     const unsigned nb = nrhs - c0 < LSB_MRHS_MAX ? nrhs - c0 : LSB_MRHS_MAX;
-    mrhs_batch(sv, nb, d_B + (size_t)c0 * ldb, ldb, d_X + (size_t)c0 * ldx, ldx, tmp + c0);
+    mrhs_batch(sv, nb, d_B + (size_t)c0 * ldb, ldb, d_X + (size_t)c0 * ldx, ldx, tmp + c0, warm ? start + c0 : NULL);
   }
   g_last = tmp[nrhs - 1];
   if (!res)
     free(tmp);
   return 0;
+}
+
+int lsb_hip_solver_solve_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
+                                   size_t ldx, struct lsb_hip_result *res) {
+  return solve_multi_dev(sv, nrhs, d_B, ldb, d_X, ldx, res, 0);
+}
+
+int lsb_hip_solver_solve_multi_x0_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
+                                      size_t ldx, struct lsb_hip_result *res) {
+  return solve_multi_dev(sv, nrhs, d_B, ldb, d_X, ldx, res, 1);
 }
 
 int lsb_hip_solver_solve_multi(lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X, size_t ldx,

@@ -101,7 +101,7 @@ int richardson_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, str
   struct lsb_pcg_state *hst = sv->h_st;
   const double t0 = wall_seconds();
   lsb_k_rich_init(s->n, d_b, d_x, s->d_r, s->d_parts2, nrr, g_stream);
-  lsb_k_rich_init_state(s->d_st, s->d_parts2, *nrr, sv->o.tol, (int)sv->o.maxit, g_stream);
+  lsb_k_rich_init_state(s->d_st, s->d_parts2, *nrr, sv->tol_run, (int)sv->o.maxit, g_stream);
   struct lsb_hip_result r;
   memset(&r, 0, sizeof r);
   r.true_relres = -1.0;
@@ -109,7 +109,7 @@ int richardson_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, str
   hst[0].iters = 0;
   for (int round = 0;; round++) {
     rich_run(sv, d_x, hint_slot(sv->hint_iters, round));
-    if (!(sv->o.verify && hst[0].status == LSB_STATUS_CONVERGED && sv->o.tol > 0.0 && hst[0].bb > 0.0))
+    if (!(sv->verify_run && hst[0].status == LSB_STATUS_CONVERGED && sv->tol_run > 0.0 && hst[0].bb > 0.0))
       break;
     /* "converged" is reported only for the residual RECOMPUTED from x; where that one misses the tolerance the
      * cycles go on from it (r = b - S x, x kept), LSB_MAX_CORRECTIONS times at the most, inside the timed region */

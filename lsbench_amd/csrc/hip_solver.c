@@ -891,6 +891,8 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
   }
   lsb_hip_free(sv->d_scal_all), lsb_hip_free(sv->d_tmp);
   lsb_hip_free(sv->d_vr), lsb_hip_free(sv->d_ve);
+  lsb_hip_free(sv->d_x0r), lsb_hip_free(sv->d_x0e);
+  free(sv->start_rr);
   lsb_hip_free(sv->ps.d_wgrow), lsb_hip_free(sv->ps.d_ug), lsb_hip_free(sv->ps.d_shared);
   lsb_hip_free(sv->d_perm);
   for (int i = 0; sv->gm && i < sv->nshard; i++) {

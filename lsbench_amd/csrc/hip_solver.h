@@ -263,8 +263,16 @@ struct lsb_hip_solver {
 #define LSB_MIXED_INNER_TOL 1e-5 /* what an inner solve on fp32-rounded values is asked for */
   unsigned hint_iters[LSB_MAX_CORRECTIONS + 1]; /* iterations of the previous solve and of each of
                                                    its correction runs, 0 = none yet */
-  double tol_run;    /* tolerance of the CG run being enqueued (opts.tol, or a correction's) */
+  double tol_run;    /* tolerance of the run being enqueued, whichever the driver (opts.tol, a correction's, or a
+                        warm start's tol ||b|| / ||b - S x0||) */
+  int verify_run;    /* GMRES, BiCGSTAB, Richardson: the run restarts on its own recomputed residual (opts.verify;
+                        0 in a correction run and in the run of a warm start, whose caller recomputes) */
   double *d_vr, *d_ve; /* opts.verify: right-hand side and solution of a correction run */
+  /* a solve from an initial guess (solve_x0_core): r0 = b - S x0 and the correction e, n_here doubles each, taken
+   * on the first such call; ||b_c - S x0_c|| / ||b_c|| of the last one (start_n columns; 0: the last solve was cold) */
+  double *d_x0r, *d_x0e;
+  double *start_rr;
+  unsigned start_n, start_cap;
   unsigned agree_nnz, agree_n; /* distributed: largest shard, identical on all ranks */
   unsigned agree_halo;         /* largest halo (doubles) any shard receives from one peer */
   /* opts.overlap = -1: the split SpMV (interior rows while the halo travels) against the plain one,
@@ -303,6 +311,7 @@ struct lsb_hip_solver {
     char *mem;                   /* one allocation: the five interleaved blocks and the partial records */
     double *b, *x, *r, *p, *q;   /* n kp doubles each */
     double *parts_pq, *parts2;   /* records of the SpMM (kp wide) and of the sweeps (2 kp wide) */
+    double *parts_bb;            /* a batch from an initial guess: the records of b.b (2 kp wide), on first use */
     struct lsb_mrhs_state *st;
     /* an AMG solver's: z and the cycle's vectors of every level as blocks of this width (level 0: b and out
      * are the r and z of the call) */
@@ -460,6 +469,10 @@ LSB_INTERNAL void tune_blas1_nt(lsb_hip_solver *sv);
 LSB_INTERNAL void persist_setup(lsb_hip_solver *sv);
 LSB_INTERNAL int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
                             struct lsb_hip_result *res);
+/* the same from the x0 that d_x holds */
+LSB_INTERNAL int solve_x0_core(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res);
+/* where a warm-started call of nrhs columns records its starting residuals (sets start_n) */
+LSB_INTERNAL double *start_relres_slots(lsb_hip_solver *sv, unsigned nrhs);
 /* hip_precond.c */
 LSB_INTERNAL int generic_precond(const lsb_hip_solver *sv);
 LSB_INTERNAL void precond_shard_blocks(struct shard *s, const int *offs, const int *cols,

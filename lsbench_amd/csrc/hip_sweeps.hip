@@ -229,6 +229,107 @@ __global__ __launch_bounds__(WG) void k_pcg_init(
   }
 }
 
+// warm start: r0 = b - q with q = S x0 ; partials (r0.r0, b.b).  The two sums are formed by the same expression
+// in the same order: where x0 = 0 (q = 0, r0 = b) they have the same bits.
+template <bool V2>
+__global__ __launch_bounds__(WG) void k_x0_start(
+    unsigned n, const double *__restrict__ b, const double *__restrict__ q, double *__restrict__ r0,
+    double *__restrict__ partials2) {
+  __shared__ double sred[8];
+  double acc[2] = {0.0, 0.0};
+  const size_t gtid = (size_t)blockIdx.x * WG + threadIdx.x;
+  const size_t gsz = (size_t)gridDim.x * WG;
+  if (V2) {
+    const size_t n2 = n / 2;
+    const double2 *b2 = (const double2 *)b, *q2 = (const double2 *)q;
+    double2 *r2 = (double2 *)r0;
+    for (size_t i = gtid; i < n2; i += gsz) {
+      const double2 bv = b2[i], qv = q2[i];
+      double2 rv;
+      rv.x = bv.x - qv.x, rv.y = bv.y - qv.y;
+      r2[i] = rv;
+      acc[0] += rv.x * rv.x;
+      acc[0] += rv.y * rv.y;
+      acc[1] += bv.x * bv.x;
+      acc[1] += bv.y * bv.y;
+    }
+    if ((n & 1) && gtid == gsz - 1) {
+      const size_t i = n - 1;
+      const double bv = b[i], rv = bv - q[i];
+      r0[i] = rv;
+      acc[0] += rv * rv, acc[1] += bv * bv;
+    }
+  } else {
+    for (size_t i = gtid; i < n; i += gsz) {
+      const double bv = b[i], rv = bv - q[i];
+      r0[i] = rv;
+      acc[0] += rv * rv, acc[1] += bv * bv;
+    }
+  }
+  wg_sum<2>(acc, sred);
+  if (threadIdx.x == 0) {
+    partials2[2 * blockIdx.x + 0] = acc[0];
+    partials2[2 * blockIdx.x + 1] = acc[1];
+  }
+}
+
+// opts.verify behind a warm start: q = S x - b and the partials of q.q off the shard's CSR arrays (global column
+// ids into the gather vector), L lanes per row, with every product's and every addition's rounding error carried
+// along (two_prod through fma, two_sum; the butterfly folds (sum, error) pairs) -- k_spmm_csr<L, KP, true>'s scheme
+// for one column: b - S x as if formed in twice the working precision, then rounded.  Where the recurrence has
+// converged to 1e-13 an fp64 S x is mostly its own rounding (tests/xn3b_A_18.txt: 1 % of the residual).
+__device__ __forceinline__ void two_sum1(double a, double b, double &s, double &e) {
+#pragma clang fp contract(off)
+  s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+
+template <int L>
+__global__ __launch_bounds__(WG) void k_resid_csr2(unsigned n, unsigned rows_per_wg, const int *__restrict__ offs,
+                                                   const int *__restrict__ cols, const double *__restrict__ vals,
+                                                   const double *__restrict__ xfull, const double *__restrict__ b,
+                                                   double *__restrict__ q, double *__restrict__ partials) {
+  constexpr unsigned SLOTS = WG / L;
+  __shared__ double sred[4];
+  const unsigned tid = threadIdx.x, slot = tid / L, l = tid % L;
+  const unsigned ra = min(blockIdx.x * rows_per_wg, n), rb = min(ra + rows_per_wg, n);
+  double dot[1] = {0.0};
+  for (unsigned base = ra; base < rb; base += SLOTS) {
+    const unsigned r = base + slot;
+    double a = 0.0, e = 0.0;
+    if (r < rb) {
+#pragma clang fp contract(off)
+      for (int j = offs[r] + (int)l; j < offs[r + 1]; j += L) {
+        const double v = vals[j], t = xfull[cols[j]];
+        const double pr = v * t, pe = fma(v, t, -pr);
+        double se;
+        two_sum1(a, pr, a, se);
+        e += pe + se;
+      }
+    }
+#pragma unroll
+    for (int off = L >> 1; off > 0; off >>= 1) { // both partners form the same sum and the same error
+#pragma clang fp contract(off)
+      const double ao = __shfl_xor(a, off, 64), eo = __shfl_xor(e, off, 64);
+      double se;
+      two_sum1(a, ao, a, se);
+      e = (e + eo) + se;
+    }
+    if (r < rb && l == 0) {
+#pragma clang fp contract(off)
+      double t0, te;
+      two_sum1(b[r], -a, t0, te);
+      const double res = t0 + (te - e); // b - S x
+      q[r] = -res;
+      dot[0] = fma(res, res, dot[0]);
+    }
+  }
+  wg_sum<1>(dot, sred);
+  if (tid == 0)
+    partials[blockIdx.x] = dot[0];
+}
+
 __global__ __launch_bounds__(WG) void k_pcg_init_state(
     lsb_pcg_state *__restrict__ st, const double *__restrict__ partials2,
     unsigned nparts, double tol, int maxit) {
@@ -780,6 +881,29 @@ void lsb_k_pcg_init(unsigned n, const double *b, const double *dinv, double dc, 
   const bool v2 = aligned16(b) && aligned16(dinv) && aligned16(x) && aligned16(r) && aligned16(p);
   const auto kern = v2 ? k_pcg_init<true> : k_pcg_init<false>;
   kern<<<g, WG, 0, (hipStream_t)stream>>>(n, b, dinv, dc, x, r, p, partials2);
+}
+
+void lsb_k_x0_start(unsigned n, const double *b, const double *q, double *r0, double *partials2,
+                    unsigned *npartials, void *stream) {
+  const unsigned g = lsb_k_blas1_grid(n);
+  *npartials = g;
+  const bool v2 = aligned16(b) && aligned16(q) && aligned16(r0);
+  const auto kern = v2 ? k_x0_start<true> : k_x0_start<false>;
+  kern<<<g, WG, 0, (hipStream_t)stream>>>(n, b, q, r0, partials2);
+}
+
+void lsb_k_resid_csr2(unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
+                      const double *xfull, const double *b, double *q, double *partials, unsigned *npartials,
+                      void *stream) {
+  const unsigned slots = WG / row_lanes(lanes); // rows a workgroup works on at once
+  unsigned g = div_up(n ? n : 1, 4 * slots);
+  if (g > LSB_MAX_PARTIALS)
+    g = LSB_MAX_PARTIALS;
+  const unsigned rows_per_wg = round_up(div_up(n ? n : 1, g), slots);
+  g = div_up(n ? n : 1, rows_per_wg);
+  *npartials = g;
+  LANES_DISPATCH(lanes, (k_resid_csr2<L><<<g, WG, 0, (hipStream_t)stream>>>(n, rows_per_wg, offs, cols, vals, xfull, b, q,
+                                                                        partials)));
 }
 
 void lsb_k_pcg_init_state(struct lsb_pcg_state *st, const double *partials2,

@@ -105,6 +105,7 @@ struct lsb_mrhs_state {
   int corrections[LSB_MRHS_MAX];    /* in-place restarts of the column */
   int running;                      /* the SpMM's gate: cleared by the sweep that sees the last column stop */
   int nspmm;                        /* SpMM launches of the iterations that did work */
+  double start_relres[LSB_MRHS_MAX]; /* a batch from an initial guess: ||b_c - S x0_c|| / ||b_c||, 0 where b_c = 0 */
 };
 
 /* Upper bound on per-launch partial sums any reduction kernel writes; the
@@ -232,6 +233,14 @@ void lsb_k_pcg_init(unsigned n, const double *b, const double *dinv, double dc, 
 void lsb_k_pcg_init_state(struct lsb_pcg_state *st, const double *partials2,
                           unsigned nparts, double tol, int maxit,
                           void *stream);
+/* q = S x - b off a CSR with global column ids into xfull, formed as in twice the working precision and rounded;
+ * one partial of q.q per workgroup (<= LSB_MAX_PARTIALS) */
+void lsb_k_resid_csr2(unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
+                      const double *xfull, const double *b, double *q, double *partials, unsigned *npartials,
+                      void *stream);
+/* a solve from an initial guess: r0 = b - q (q = S x0), one record (r0.r0, b.b) per workgroup */
+void lsb_k_x0_start(unsigned n, const double *b, const double *q, double *r0, double *partials2,
+                    unsigned *npartials, void *stream);
 void lsb_k_pcg_update_xr(unsigned n, const double *p, const double *q,
                          const double *dinv, double dc, double *x, double *r,
                          struct lsb_pcg_state *st, int parity,
@@ -319,8 +328,21 @@ void lsb_k_spmm_csr(unsigned kp, unsigned n, const int *offs, const int *cols, c
                     const struct lsb_mrhs_state *st, void *stream);
 void lsb_k_mrhs_init(unsigned kp, unsigned n, const double *b, const double *dinv, double dc, double *x, double *r,
                      double *p, double *partials2, unsigned *npartials, void *stream);
+/* bb_parts == NULL: the state of a batch from x0 = 0, b.b from the records of lsb_k_mrhs_init.  Else the state of a
+ * batch from an initial guess: partials2 holds (r.z, r.r) of r = b - S x0 and bb_parts the records of
+ * lsb_k_mrhs_x0_bb; a column with r.r <= tol^2 b.b is CONVERGED from the start */
 void lsb_k_mrhs_init_state(unsigned kp, struct lsb_mrhs_state *st, const double *partials2, unsigned nparts,
-                           double tol, int maxit, void *stream);
+                           const double *bb_parts, unsigned nbb, double tol, int maxit, void *stream);
+/* A batch from an initial guess X0 (hip_mrhs_x0.hip), in three steps around the SpMM r = b - S x0 (bres = b):
+ * x0_bb, before it: one record (0, then b.b per column) per workgroup, in lsb_k_mrhs_init's format and order.
+ * x0_start, behind it: x_c = 0 for the columns with b_c = 0, p = dinv .* r and one record (r.z, r.r) per workgroup
+ * by lsb_k_mrhs_init's expressions -- a column with x0 = 0 gets the bits of a batch from zero.
+ * amg_mrhs_x0_start: the zeroing alone; the cycle on r and lsb_k_amg_mrhs_init_p (on r) follow. */
+void lsb_k_mrhs_x0_bb(unsigned kp, unsigned n, const double *b, double *bb_parts, unsigned *nbb, void *stream);
+void lsb_k_mrhs_x0_start(unsigned kp, unsigned n, const double *r, const double *dinv, double dc, double *x,
+                         double *p, const double *bb_parts, unsigned nbb, double *partials2, unsigned *npartials,
+                         void *stream);
+void lsb_k_amg_mrhs_x0_start(unsigned kp, unsigned n, double *x, const double *bb_parts, unsigned nbb, void *stream);
 void lsb_k_mrhs_update_xr(unsigned kp, unsigned n, const double *p, const double *q, const double *dinv, double dc,
                           double *x, double *r, struct lsb_mrhs_state *st, int parity, const double *pq_parts,
                           unsigned npq, double *partials2, unsigned *npartials, void *stream);
