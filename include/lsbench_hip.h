@@ -124,11 +124,17 @@ enum { LSB_PRECOND_JACOBI = 0, LSB_PRECOND_NONE = 1,
                                        host at solver creation (lsb_amg_setup), applied
                                        by hip_amg.hip; one shard, classic PCG  */
 enum { LSB_AMG_SMOOTH_L1JACOBI = 0,   /* nu sweeps x += diag(sum_j |a_ij|)^-1 (b - A x)  */
-       LSB_AMG_SMOOTH_CHEB = 1 };     /* the Chebyshev polynomial of degree nu in D^-1 A on
+       LSB_AMG_SMOOTH_CHEB = 1,       /* the Chebyshev polynomial of degree nu in D^-1 A on
                                        [rho / opts.amg_cheb_ratio, rho], rho the level's
                                        Gershgorin bound (lsb_amg_gershgorin): a guaranteed
                                        bound, so the cycle stays SPD; nu row launches as nu
                                        sweeps, one more vector (the direction d) per level */
+       LSB_AMG_SMOOTH_MCGS = 2 };     /* multicolour Gauss-Seidel: nu forward sweeps before and nu
+                                       backward sweeps after the coarse correction, in place, a
+                                       launch per colour of a greedy colouring (lsb_amg_colour), on
+                                       every level of at most LSB_AMG_MCGS_COLOURS colours; the other
+                                       levels keep l1-Jacobi.  No spectral bound; opt-in
+                                       (hip_amg_mcgs.hip; one column only) */
 enum { LSB_AMG_PREC_FP64 = 0,         /* the V-cycle in fp64 (default)                          */
        LSB_AMG_PREC_FP32 = 1 };       /* the whole hierarchy and every level vector in fp32, inside
                                        a Krylov loop that stays fp64 (x, r, p, q, every dot product,
@@ -265,7 +271,10 @@ struct lsb_hip_opts {
                         and the offset of amg_cheb_ratio hold)                [FP64] */
   int amg_smoother;  /* LSB_AMG_SMOOTH_*; under CHEB amg_sweeps is the polynomial's
                         degree and amg_tail_rows is ignored (the one-launch tail is
-                        not built for it)                          [L1JACOBI] */
+                        not built for it); under MCGS amg_sweeps counts the forward
+                        sweeps before and the backward sweeps after the coarse
+                        correction, amg_tail_rows is ignored and the solver does not
+                        serve blocks of columns                    [L1JACOBI] */
   double amg_cheb_ratio; /* hi / lo of the Chebyshev smoother's interval; values below
                         1.5 are taken as 1.5                                  [10] */
 };
@@ -466,6 +475,33 @@ double lsb_amg_gershgorin(const struct csr *A);
  *   d_i <- fma(c2[k] / a_ii, b_i - s_i, c1[k] d_i),  x_i <- x_i + d_i ;  c1[0] = 0 and step 0 does not read d. */
 void lsb_amg_cheb_coeffs(double hi, double ratio, unsigned deg, double *c1, double *c2);
 void lsb_amg_free(struct lsb_amg_hier *h);
+/* Multicolour Gauss-Seidel smoothing (LSB_AMG_SMOOTH_MCGS), pure host logic.
+ * lsb_amg_colour: the greedy colouring of A's stored pattern -- rows in ascending order, each takes the smallest
+ * colour that none of its stored off-diagonal neighbours already holds (a stored zero counts); serial, so the same
+ * for any thread count.  A malloc'ed int[nrows] (at least one), the number of colours in *ncolours. */
+#define LSB_AMG_MCGS_COLOURS 16 /* a level with more colours keeps l1-Jacobi; LSBENCH_HIP_AMG_MCGS_COLOURS, 1 .. 64 */
+int *lsb_amg_colour(const struct csr *A, unsigned *ncolours);
+/* The colour-sorted copy of a level's matrix: its rows regrouped colour by colour, ascending row order inside a
+ * colour (stable), so that the launch of colour c streams the contiguous rows cbeg[c] .. cbeg[c + 1) of the copy.
+ * rowid[p] is the row at position p; offs / cols / vals are the rows in that order, entry for entry, columns
+ * 0-based and in the level's numbering (the vectors are not permuted). */
+struct lsb_mcgs {
+  unsigned n, ncolours;
+  unsigned *cbeg;  /* ncolours + 1 */
+  unsigned *rowid; /* n */
+  unsigned *offs;  /* n + 1 */
+  unsigned *cols;  /* offs[n] */
+  double *vals;
+};
+/* NULL when a colour is outside 0 .. ncolours - 1 */
+struct lsb_mcgs *lsb_csr_mcgs(const struct csr *A, const int *colour, unsigned ncolours);
+void lsb_mcgs_free(struct lsb_mcgs *M);
+/* Host-side assertions of what the in-place kernels rely on, run at every upload.  0 = all hold; else the number
+ * of the violated rule and its text in why[whylen]: 2 the colour ranges cover 0 .. n and ascend; 3 rowid is a
+ * permutation; 4 every row lies in the range of its own colour (so in exactly one); 5 columns are rows of the
+ * level; 6 every stored a_ij, i != j, has colour[i] != colour[j] (looked for in every row, so an unsymmetric
+ * pattern is caught); 7 every diagonal is > 0; 8 the copy's rows are the original rows entry for entry. */
+int lsb_mcgs_check(const struct csr *A, const int *colour, const struct lsb_mcgs *M, char *why, size_t whylen);
 /* The entries of a CSR as the fp32 V-cycle streams them: a malloc'ed array of offs[nrows] 8-byte words (at least
  * one), word j = the 0-based column of entry j in the low 32 bits, the bit pattern of (float)vals[j] (round to
  * nearest even) in the high 32.  NULL when a value is not finite or rounds to +-inf; subnormal results are kept.
@@ -741,12 +777,22 @@ int lsb_hip_solver_amg_info(lsb_hip_solver *s, unsigned *levels, unsigned *tail_
  * on (hi = lsb_amg_gershgorin of the level, lo = hi / amg_cheb_ratio); 2 for another preconditioner or
  * smoother and for a level that is not smoothed (the coarsest, or beyond). */
 int lsb_hip_solver_amg_cheb_interval(lsb_hip_solver *s, unsigned level, double *lo, double *hi);
+/* LSB_PRECOND_AMG with LSB_AMG_SMOOTH_MCGS: the colours of `level`'s Gauss-Seidel sweeps; *ncolours = 0 for a level
+ * whose colouring has more than the cap and which therefore keeps l1-Jacobi.  2 for the coarsest level, a level out
+ * of range and a solver of another smoother or preconditioner. */
+int lsb_hip_solver_amg_colours(lsb_hip_solver *s, unsigned level, unsigned *ncolours);
 /* The precision of the V-cycle: LSB_AMG_PREC_FP64 (0) or LSB_AMG_PREC_FP32 (1); 2 for a solver without AMG. */
 int lsb_hip_solver_amg_precision(lsb_hip_solver *s);
 /* Bytes one application of the V-cycle must move, 0 without AMG.  fp64: 12 per stored entry for every launch that
  * streams a matrix (A 2 nu times per level, P and R once), 8 nc^2 for the coarse inverse, 8 per element pass of
  * the level vectors.  fp32: 8 per stored entry, 4 nc^2, 4 per element pass; the fine level's r is read once
- * and z written once at 8, and the fp32 copy of r is written once. */
+ * and z written once at 8, and the fp32 copy of r is written once.
+ * A level smoothed by multicolour Gauss-Seidel (LSB_AMG_SMOOTH_MCGS), M entries of which M0 in rows of colour 0,
+ * n rows of which n0 of colour 0: the colour-sorted copy once per sweep less M0 (the first forward sweep starts
+ * from zero and streams the colours >= 1 only) and A once for the residual, (2 nu + 1) M - M0 entries; per sweep
+ * b, dinv, x in and x out of every row, 8 nu n element passes, plus n - 2 n0 because the first launch writes all
+ * of x and reads b and dinv on colour 0 only; the residual, restriction and prolongation as on every level, 6 n.
+ * Row offsets and rowid are left out, as the offsets are everywhere above. */
 unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *s);
 /* LSB_PRECOND_CHEBYSHEV: the interval [lmin, lmax] of D^-1 S the polynomial was built on at creation
  * (lmax = 1.1 x the power iteration's estimate, lmin = lmax / max(30, 16 degree^2), the degree
@@ -773,7 +819,9 @@ int lsb_hip_solver_jacobi_sweep_dev(lsb_hip_solver *s, double w,
  * krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE / AMG (one V-cycle per iteration on the block of
  * residuals: every matrix of the hierarchy is streamed once for all columns, and a column's z has the bits of
  * the single-column cycle; opts.amg_tail_rows is ignored there); GMRES, BiCGSTAB, PCG1, Chebyshev, block-Jacobi,
- * FSAI, nvirt > 1, distributed and persistent solvers answer 2 -- nothing falls back to a loop of single solves.
+ * FSAI, nvirt > 1, distributed and persistent solvers answer 2, and so does an AMG solver smoothed by multicolour
+ * Gauss-Seidel (LSB_AMG_SMOOTH_MCGS: its cycle is not built on blocks; lsb_hip_solver_spmm_dev still serves it) --
+ * nothing falls back to a loop of single solves.
  * res[c] (nrhs entries) is column c's own result: iters, status, relres, corrections, true_relres are the
  * column's; seconds is the wall-clock of the batch the column ran in and spmvs the SpMM launches of that
  * batch, the same in all its entries; spmv_ms = 0, spmv_samples = 0 (opts.sample_spmv is ignored).

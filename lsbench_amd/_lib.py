@@ -22,7 +22,7 @@ SOLVER_HIP = 6
 OP_CHOLMOD_UPPER, OP_RAW = 0, 1
 PRECOND_JACOBI, PRECOND_NONE, PRECOND_L1JACOBI, PRECOND_CHEBYSHEV, PRECOND_BLOCKJACOBI, PRECOND_FSAI = 0, 1, 2, 3, 4, 5
 PRECOND_AMG = 6
-AMG_SMOOTH_L1JACOBI, AMG_SMOOTH_CHEB = 0, 1
+AMG_SMOOTH_L1JACOBI, AMG_SMOOTH_CHEB, AMG_SMOOTH_MCGS = 0, 1, 2
 AMG_PREC_FP64, AMG_PREC_FP32 = 0, 1
 KRYLOV_PCG, KRYLOV_GMRES, KRYLOV_PCG1, KRYLOV_AUTO, KRYLOV_BICGSTAB, KRYLOV_RICHARDSON = 0, 1, 2, 3, 4, 5
 SPMV_AUTO, SPMV_ADAPTIVE, SPMV_SUBWAVE, SPMV_SCALAR, SPMV_PANEL, SPMV_SELL, SPMV_BINNED, SPMV_TWOPHASE = 0, 1, 2, 3, 4, 5, 6, 7
@@ -117,6 +117,13 @@ class AmgHier(C.Structure):
     """struct lsb_amg_hier."""
     _fields_ = [("nlev", C.c_uint), ("lv", C.POINTER(AmgLevel)), ("nc", C.c_uint),
                 ("coarse_inv", C.POINTER(C.c_double))]
+
+
+class Mcgs(C.Structure):
+    """struct lsb_mcgs."""
+    _fields_ = [("n", C.c_uint), ("ncolours", C.c_uint), ("cbeg", C.POINTER(C.c_uint)),
+                ("rowid", C.POINTER(C.c_uint)), ("offs", C.POINTER(C.c_uint)), ("cols", C.POINTER(C.c_uint)),
+                ("vals", C.POINTER(C.c_double))]
 
 
 class SellTmpl(C.Structure):
@@ -222,6 +229,10 @@ SIGNATURES = {
     "lsb_amg_gershgorin": (_d, [_csrp]),
     "lsb_csr_pack_f32": (C.POINTER(C.c_ulonglong), [_csrp]),
     "lsb_amg_cheb_coeffs": (None, [_d, _d, _u, C.POINTER(_d), C.POINTER(_d)]),
+    "lsb_amg_colour": (C.POINTER(C.c_int), [_csrp, C.POINTER(_u)]),
+    "lsb_csr_mcgs": (C.POINTER(Mcgs), [_csrp, C.POINTER(C.c_int), _u]),
+    "lsb_mcgs_free": (None, [C.POINTER(Mcgs)]),
+    "lsb_mcgs_check": (_i, [_csrp, C.POINTER(C.c_int), C.POINTER(Mcgs), C.c_char_p, C.c_size_t]),
     "lsb_sell16_templates": (C.POINTER(SellTmpls), [C.POINTER(Sell), C.POINTER(SellVc)]),
     "lsb_sell_tmpls_free": (None, [C.POINTER(SellTmpls)]),
     "lsb_tmpl_check": (_i, [C.POINTER(Sell), C.POINTER(SellVc), C.POINTER(SellTmpls), _u, _u, _u, _i,
@@ -257,6 +268,7 @@ SIGNATURES = {
     "lsb_hip_solver_amg_precision": (_i, [_vp]),
     "lsb_hip_solver_amg_cycle_bytes": (C.c_ulonglong, [_vp]),
     "lsb_hip_solver_amg_cheb_interval": (_i, [_vp, _u, C.POINTER(_d), C.POINTER(_d)]),
+    "lsb_hip_solver_amg_colours": (_i, [_vp, _u, C.POINTER(_u)]),
     "lsb_hip_solver_cheb_interval": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
     "lsb_hip_solver_time_spmv": (_i, [_vp, _i, _i, C.POINTER(_d)]),
     "lsb_hip_solver_jacobi_sweep_dev": (_i, [_vp, _d, _vp, _vp]),

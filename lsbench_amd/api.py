@@ -166,6 +166,49 @@ def lsb_csr_sellize16(A, row_begin=0):
     return sptr, codes, sbase, vals
 
 
+def lsb_amg_colour(A):
+    """(colour of every row as int32, number of colours) by the greedy rule of lsb_amg_colour."""
+    nc = C.c_uint()
+    p = L.load().lsb_amg_colour(A.ptr, C.byref(nc))
+    if not p:
+        raise L.LsbenchHipError("lsb_amg_colour failed")
+    col = np.ctypeslib.as_array(p, shape=(max(A.nrows, 1),))[:A.nrows].astype(np.int32, copy=True)
+    L.libc_free(p)
+    return col, int(nc.value)
+
+
+def lsb_csr_mcgs(A, colour, ncolours):
+    """The colour-sorted copy of A (struct lsb_mcgs) as a dict of numpy arrays: cbeg, rowid, offs, cols, vals;
+    None where lsb_csr_mcgs refuses the colouring."""
+    col = np.ascontiguousarray(colour, np.int32)
+    p = L.load().lsb_csr_mcgs(A.ptr, col.ctypes.data_as(C.POINTER(C.c_int)), ncolours)
+    if not p:
+        return None
+    m = p.contents
+
+    def arr(q, cnt, dt):
+        return np.ctypeslib.as_array(q, shape=(max(cnt, 1),))[:cnt].astype(dt, copy=True)
+    offs = arr(m.offs, m.n + 1, np.uint32)
+    out = {"cbeg": arr(m.cbeg, m.ncolours + 1, np.uint32), "rowid": arr(m.rowid, m.n, np.uint32), "offs": offs,
+           "cols": arr(m.cols, int(offs[-1]), np.uint32), "vals": arr(m.vals, int(offs[-1]), np.float64)}
+    L.load().lsb_mcgs_free(p)
+    return out
+
+
+def lsb_mcgs_check(A, colour, copy):
+    """lsb_mcgs_check of a colouring and a copy given as lsb_csr_mcgs returns it: (0, "") or (rule, its text)."""
+    col = np.ascontiguousarray(colour, np.int32)
+    keep = {k: np.ascontiguousarray(copy[k], np.float64 if k == "vals" else np.uint32)
+            for k in ("cbeg", "rowid", "offs", "cols", "vals")}
+    u = C.POINTER(C.c_uint)
+    m = L.Mcgs(A.nrows, len(keep["cbeg"]) - 1, keep["cbeg"].ctypes.data_as(u), keep["rowid"].ctypes.data_as(u),
+               keep["offs"].ctypes.data_as(u), keep["cols"].ctypes.data_as(u),
+               keep["vals"].ctypes.data_as(C.POINTER(C.c_double)))
+    why = C.create_string_buffer(512)
+    rc = L.load().lsb_mcgs_check(A.ptr, col.ctypes.data_as(C.POINTER(C.c_int)), C.byref(m), why, len(why))
+    return int(rc), why.value.decode()
+
+
 def lsb_csr_rcm(A):
     perm = np.zeros(A.nrows, np.uint32)
     L.check(L.load().lsb_csr_rcm(A.ptr, perm.ctypes.data_as(C.POINTER(C.c_uint))), "rcm")
@@ -389,6 +432,17 @@ class Solver:
             return None
         L.check(rc, "amg_cheb_interval")
         return lo.value, hi.value
+
+    def amg_colours(self, level):
+        """Colours of the multicolour Gauss-Seidel sweeps of an AMG level; 0 for a level whose colouring exceeds the
+        cap and which keeps l1-Jacobi; None for the coarsest level, a level out of range and a solver of another
+        smoother or preconditioner."""
+        nc = C.c_uint()
+        rc = L.load().lsb_hip_solver_amg_colours(self._h, level, C.byref(nc))
+        if rc == 2:
+            return None
+        L.check(rc, "amg_colours")
+        return int(nc.value)
 
     @property
     def cheb_interval(self):

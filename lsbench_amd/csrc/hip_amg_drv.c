@@ -1,7 +1,7 @@
 /* AMG on the host side (LSB_PRECOND_AMG; hierarchy: lsb_amg.c; kernels: hip_amg.hip, hip_amg_cheb.hip,
- * hip_amg_f32.hip, hip_mrhs_amg.hip): the upload of the hierarchy at solver creation (untimed), the ONE schedule of
- * the V-cycle that all three flavours run -- fp64 or fp32 on one column, fp64 on blocks of columns -- and what the
- * C-ABI answers about it. */
+ * hip_amg_f32.hip, hip_amg_mcgs.hip, hip_mrhs_amg.hip): the upload of the hierarchy at solver creation (untimed), the
+ * ONE schedule of the V-cycle that all three flavours run -- fp64 or fp32 on one column, fp64 on blocks of columns --
+ * and what the C-ABI answers about it. */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
@@ -110,6 +110,50 @@ static void amg_upload_level32(struct amg_dev *a, unsigned l, const struct lsb_a
     amg_level_vecs(a, &a->vec[l], H->n, sizeof(float));
 }
 
+/* Multicolour Gauss-Seidel on level l (LSB_AMG_SMOOTH_MCGS): colour it and, where the colouring stays within the
+ * cap, sort the copy, check it and upload it in the solver's precision (the fp64 values stay on the host under
+ * fp32).  0: the level has more colours than the cap and keeps l1-Jacobi.  m0 / n0: colour 0's entries and rows. */
+static int amg_upload_mcgs(struct amg_dev *a, unsigned l, const struct lsb_amg_level *H, unsigned long long *m0,
+                           unsigned *n0) {
+  struct amg_lv *L = &a->lv[l];
+  const unsigned n = H->n;
+  unsigned nc = 0;
+  int *colour = lsb_amg_colour(H->A, &nc);
+  L->ncol_found = nc;
+  if (nc > a->mcgs_cap) {
+    free(colour);
+    return 0;
+  }
+  struct lsb_mcgs *M = lsb_csr_mcgs(H->A, colour, nc);
+  char why[256] = "no copy";
+  const int rc = M ? lsb_mcgs_check(H->A, colour, M, why, sizeof why) : 1;
+  if (rc)
+    errx(EXIT_FAILURE, "hip_cdna4: --amg-smoother mcgs: level %u (%u rows, %u colours) fails the check of its "
+                       "colour-sorted copy (%d): %s", l, n, nc, rc, why);
+  const struct csr view = {n, 0, M->offs, M->cols, M->vals};
+  const unsigned long long nnz = M->offs[n];
+  if (a->prec == LSB_AMG_PREC_FP32)
+    L->C.f = amg_upload_mat32(a, &view, "A", l);
+  else
+    L->C.d = amg_upload_mat(a, &view);
+  unsigned char *c8 = (unsigned char *)malloc(n ? n : 1);
+  if (!c8)
+    errx(EXIT_FAILURE, "hip_cdna4: out of host memory for the colours of an AMG level");
+  for (unsigned i = 0; i < n; i++)
+    c8[i] = (unsigned char)colour[i]; /* (the cap is at most 64) */
+  L->rowid = (const int *)amg_keep(a, dev_upload(M->rowid, (size_t)(n ? n : 1) * sizeof(unsigned)));
+  L->colour8 = (const unsigned char *)amg_keep(a, dev_upload(c8, n ? n : 1));
+  LSB_CHK_HIP(hipStreamSynchronize(g_stream));
+  L->cbeg = lsb_calloc(unsigned, (size_t)nc + 1);
+  memcpy(L->cbeg, M->cbeg, ((size_t)nc + 1) * sizeof(unsigned));
+  L->ncol = nc;
+  *m0 = M->offs[M->cbeg[1]], *n0 = M->cbeg[1];
+  a->mcgs_bytes += 4ull * (n + 1) + (a->prec == LSB_AMG_PREC_FP32 ? 8ull : 12ull) * nnz + 5ull * n;
+  free(c8), free(colour);
+  lsb_mcgs_free(M);
+  return 1;
+}
+
 static void amg_report(const struct amg_dev *a, const struct lsb_amg_hier *h, double ratio) {
   const int f32 = a->prec == LSB_AMG_PREC_FP32;
   unsigned long long nnz0 = h->lv[0].A->offs[h->lv[0].n], nnzall = 0;
@@ -123,6 +167,10 @@ static void amg_report(const struct amg_dev *a, const struct lsb_amg_hier *h, do
       fprintf(stderr, ", %u / %u lanes (P / R)", f32 ? L->P.f.lanes : L->P.d.lanes, f32 ? L->R.f.lanes : L->R.d.lanes);
     if (H->P && a->cheb)
       fprintf(stderr, ", Chebyshev on [%.4g, %.4g]\n", L->lo, L->hi);
+    else if (H->P && a->mcgs && L->ncol)
+      fprintf(stderr, ", Gauss-Seidel in %u colours\n", L->ncol);
+    else if (H->P && a->mcgs)
+      fprintf(stderr, ", l1-Jacobi (%u colours, more than %u)\n", L->ncol_found, a->mcgs_cap);
     else if (H->P)
       fprintf(stderr, "\n");
     else
@@ -132,6 +180,11 @@ static void amg_report(const struct amg_dev *a, const struct lsb_amg_hier *h, do
     fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u levels, Chebyshev smoother of degree %u "
                     "(interval ratio %g), set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev, a->nu,
             ratio, a->setup_s);
+  else if (a->mcgs)
+    fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u levels, %u multicolour Gauss-Seidel sweep%s forward "
+                    "and backward on levels of at most %u colours (l1-Jacobi elsewhere), colour-sorted copies %llu "
+                    "bytes on the device, set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev, a->nu,
+            a->nu > 1 ? "s" : "", a->mcgs_cap, a->mcgs_bytes, a->setup_s);
   else
     fprintf(stderr, "hip_cdna4: AMG operator complexity %.3f, %u of %u levels in the one-launch tail, %u l1-Jacobi "
                     "sweep%s, set-up %.3f s\n", nnz0 ? (double)nnzall / nnz0 : 0.0, h->nlev - a->tail, h->nlev,
@@ -151,8 +204,9 @@ void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const 
     errx(EXIT_FAILURE, "hip_cdna4: --precond amg runs under classic PCG (--krylov cg or auto), not %s",
          o->krylov == LSB_KRYLOV_GMRES ? "gmres" : o->krylov == LSB_KRYLOV_PCG1 ? "cg1" : "bicgstab");
   const int cheb = o->amg_smoother == LSB_AMG_SMOOTH_CHEB, f32 = o->amg_precision == LSB_AMG_PREC_FP32;
-  if (o->amg_smoother != LSB_AMG_SMOOTH_L1JACOBI && !cheb)
-    errx(EXIT_FAILURE, "hip_cdna4: no AMG smoother %d (--amg-smoother l1 or cheb)", o->amg_smoother);
+  const int mcgs = o->amg_smoother == LSB_AMG_SMOOTH_MCGS;
+  if (o->amg_smoother != LSB_AMG_SMOOTH_L1JACOBI && !cheb && !mcgs)
+    errx(EXIT_FAILURE, "hip_cdna4: no AMG smoother %d (--amg-smoother l1, cheb or mcgs)", o->amg_smoother);
   if (o->amg_precision != LSB_AMG_PREC_FP64 && !f32)
     errx(EXIT_FAILURE, "hip_cdna4: no AMG precision %d (--amg-precision fp64 or fp32)", o->amg_precision);
   const double ratio = o->amg_cheb_ratio >= 1.5 ? o->amg_cheb_ratio : 1.5;
@@ -165,25 +219,33 @@ void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const 
   if (!h)
     errx(EXIT_FAILURE, "hip_cdna4: cannot build the AMG hierarchy");
   struct amg_dev *a = lsb_calloc(struct amg_dev, 1);
-  a->nlev = h->nlev, a->nc = h->nc, a->prec = o->amg_precision, a->cheb = cheb;
+  a->nlev = h->nlev, a->nc = h->nc, a->prec = o->amg_precision, a->cheb = cheb, a->mcgs = mcgs;
+  if (mcgs) { /* the cap on a level's colours: LSBENCH_HIP_AMG_MCGS_COLOURS, 1 .. 64, is the A/B switch */
+    const char *e = getenv("LSBENCH_HIP_AMG_MCGS_COLOURS");
+    a->mcgs_cap = e && atoi(e) >= 1 && atoi(e) <= 64 ? (unsigned)atoi(e) : LSB_AMG_MCGS_COLOURS;
+  }
   a->nu = o->amg_sweeps < 1 ? 1u : (o->amg_sweeps > 16 ? 16u : (unsigned)o->amg_sweeps);
-  a->mem = lsb_calloc(void *, 13 * (size_t)h->nlev + 4);
+  a->mem = lsb_calloc(void *, 18 * (size_t)h->nlev + 4);
   a->lv = lsb_calloc(struct amg_lv, h->nlev);
   a->vec = lsb_calloc(struct amg_vecs, h->nlev);
-  /* the one-launch tail begins at the first level of at most amg_tail_rows rows (none under Chebyshev or fp32) */
+  /* the one-launch tail begins at the first level of at most amg_tail_rows rows (none under Chebyshev, multicolour
+   * Gauss-Seidel or fp32) */
   for (a->tail = 0; a->tail < h->nlev; a->tail++)
-    if (!cheb && !f32 && o->amg_tail_rows > 0 && h->lv[a->tail].n <= (unsigned)o->amg_tail_rows)
+    if (!cheb && !mcgs && !f32 && o->amg_tail_rows > 0 && h->lv[a->tail].n <= (unsigned)o->amg_tail_rows)
       break;
   /* per level: minv, the Chebyshev data, the upload in the solver's precision, what a cycle streams of it */
   for (unsigned l = 0; l < h->nlev; l++) {
     const struct lsb_amg_level *H = &h->lv[l];
     struct amg_lv *L = &a->lv[l];
     L->n = H->n;
+    unsigned long long m0 = 0;
+    unsigned n0 = 0;
+    const int gs = mcgs && H->P && amg_upload_mcgs(a, l, H, &m0, &n0); /* else this level keeps l1-Jacobi */
     double *minv = (double *)malloc((size_t)(H->n ? H->n : 1) * sizeof(double));
-    for (unsigned i = 0; i < H->n; i++) { /* 1 / sum_j |a_ij| (l1-Jacobi), 1 / a_ii (Chebyshev) */
+    for (unsigned i = 0; i < H->n; i++) { /* 1 / sum_j |a_ij| (l1-Jacobi), 1 / a_ii (Chebyshev, Gauss-Seidel) */
       double sum = 0.0;
       for (unsigned e = H->A->offs[i]; e < H->A->offs[i + 1]; e++)
-        sum += cheb ? (H->A->cols[e] == i ? H->A->vals[e] : 0.0) : fabs(H->A->vals[e]);
+        sum += cheb || gs ? (H->A->cols[e] == i ? H->A->vals[e] : 0.0) : fabs(H->A->vals[e]);
       minv[i] = 1.0 / sum; /* > 0: lsb_amg_setup refused a diagonal <= 0 */
     }
     if (cheb && H->P) { /* the polynomial of degree nu on [rho / ratio, rho], rho the level's Gershgorin bound */
@@ -196,7 +258,11 @@ void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const 
       amg_upload_level(a, l, H, minv);
     LSB_CHK_HIP(hipStreamSynchronize(g_stream));
     free(minv);
-    if (H->P) { /* A goes 2 nu times (nu - 1 sweeps, the residual, nu sweeps), P and R once; 6 nu + 5 vector passes */
+    if (gs) { /* lsbench_hip.h, at lsb_hip_solver_amg_cycle_bytes: the copy 2 nu times less colour 0 once, A once */
+      a->cycle_mat_bytes += 12ull * ((2ull * a->nu + 1ull) * H->A->offs[H->n] - m0 + H->P->offs[H->P->nrows] +
+                                     H->R->offs[H->R->nrows]);
+      a->cycle_vec_rows += (8ull * a->nu + 7ull) * H->n - 2ull * n0;
+    } else if (H->P) { /* A goes 2 nu times (nu - 1 sweeps, the residual, nu sweeps), P and R once; 6 nu + 5 passes */
       a->cycle_mat_bytes += 12ull * (2ull * a->nu * H->A->offs[H->n] + H->P->offs[H->P->nrows] + H->R->offs[H->R->nrows]);
       a->cycle_vec_rows += (6ull * a->nu + 5ull) * H->n;
       if (cheb) /* d: written by both step 0s, read and written by the 2 (nu - 1) other steps */
@@ -254,6 +320,8 @@ void amg_free(struct shard *s) {
     lsb_hip_free(a->mem[k]);
   /* level 0's two slab vectors (amg_finish_setup) */
   shard_vec_free(s, a->vec[0].tmp), shard_vec_free(s, a->prec == LSB_AMG_PREC_FP32 ? a->vec[0].b : a->vec[0].r);
+  for (unsigned l = 0; l < a->nlev; l++)
+    free(a->lv[l].cbeg);
   free(a->mem), free(a->lv), free(a->vec), free(a);
   s->amg = NULL;
 }
@@ -286,7 +354,9 @@ char *amg_block_vecs(const struct amg_dev *a, unsigned kp, struct amg_vecs *v) {
  *   AMG_F64  one column in fp64 (hip_amg.hip)
  *   AMG_F32  one column in fp32 (hip_amg_f32.hip): float vectors between the caller's fp64 r and z
  *   AMG_BLK  kp interleaved columns in fp64 (hip_mrhs_amg.hip, hip_amg_cheb.hip): each column with AMG_F64's bits
- * Under the Chebyshev smoother the smoothing steps are the polynomial's: the same count and parity, d in place. */
+ * Under the Chebyshev smoother the smoothing steps are the polynomial's: the same count and parity, d in place.
+ * A level smoothed by multicolour Gauss-Seidel (lv[l].ncol > 0; AMG_F64 and AMG_F32 only) is the other case: its
+ * iterate stays in ONE buffer, the level's out, and a step is a sweep of ncol launches in place (hip_amg_mcgs.hip). */
 enum amg_flavour { AMG_F64, AMG_F32, AMG_BLK };
 
 static enum amg_flavour amg_flavour(const struct amg_run *c) {
@@ -347,6 +417,32 @@ static void amg_smooth(const struct amg_run *c, unsigned l, const struct amg_vec
   }
 }
 
+/* The first launch of a multicolour Gauss-Seidel level's way down, from the zero guess, over all rows of v->out:
+ * colour 0 gets dinv b, the other colours 0.  fp32: in64 and the float copy of r as in amg_smooth */
+static void amg_mcgs_first(const struct amg_run *c, unsigned l, const struct amg_vecs *v) {
+  const struct amg_lv *L = &c->a->lv[l];
+  if (amg_flavour(c) == AMG_F64)
+    lsb_k_amg_mcgs_first(L->n, L->colour8, v->b, L->minv, v->out, c->st, g_stream);
+  else
+    lsb_k_amg32_mcgs_first(L->n, l == 0, L->colour8, l ? v->b : c->r, L->minv, v->out, v->b, c->st, g_stream);
+}
+
+/* One sweep in place on v->out, a launch per colour: forward over the colours from .. ncol - 1, or backward over
+ * ncol - 1 .. 0.  last: the level's last sweep of the cycle, which on the fine level of the fp32 cycle also stores
+ * every row widened to the caller's z (under fp64 out IS z) */
+static void amg_mcgs_sweep(const struct amg_run *c, unsigned l, const struct amg_vecs *v, int backward, unsigned from,
+                           int last) {
+  const struct amg_lv *L = &c->a->lv[l];
+  for (unsigned k = from; k < L->ncol; k++) {
+    const unsigned col = backward ? L->ncol - 1 - k : k, p0 = L->cbeg[col], p1 = L->cbeg[col + 1];
+    if (amg_flavour(c) == AMG_F64)
+      lsb_k_amg_mcgs(&L->C.d, L->rowid, p0, p1, v->out, v->b, L->minv, c->st, g_stream);
+    else
+      lsb_k_amg32_mcgs(&L->C.f, L->rowid, p0, p1, v->out, v->b, L->minv, last && l == 0 ? c->z : NULL, c->st,
+                       g_stream);
+  }
+}
+
 /* the steps that are one row kernel whatever the smoother -- residual, restriction, prolongation: y = mode(m; x, b) */
 static void amg_csr(const struct amg_run *c, int mode, const union amg_mat *m, const void *x, const void *b,
                     const void *minv, void *y) {
@@ -383,19 +479,30 @@ static void amg_coarse(const struct amg_run *c, unsigned l) {
  * the prolongation added to the iterate where the way down left it, buf[(nu - 1) % 2], then nu steps -- 2 nu - 1
  * out-of-place steps per level in all, so the last one writes out.  One column in fp64 under l1-Jacobi stops the walk
  * at a->tail and runs the levels from there in one launch (lsb_k_amg_tail: the same bits); every other flavour takes a
- * launch per step.  Allocates nothing and synchronises nothing: it may run inside a stream capture. */
+ * launch per step.  A multicolour Gauss-Seidel level has no parity: in place on out, down the first launch from zero,
+ * the colours 1 .. of the first forward sweep and nu - 1 forward sweeps, up nu backward sweeps, ncol launches each.
+ * Allocates nothing and synchronises nothing: it may run inside a stream capture. */
 void amg_cycle(const struct amg_run *c) {
   const struct amg_dev *a = c->a;
   const unsigned nu = a->nu;
+  if (a->mcgs && amg_flavour(c) == AMG_BLK)
+    errx(EXIT_FAILURE, "hip_cdna4: cannot happen: a V-cycle on blocks of columns under --amg-smoother mcgs");
   const int tail = amg_flavour(c) == AMG_F64 && a->tail < a->nlev;
   const unsigned top = tail ? a->tail : a->nlev - 1;
   for (unsigned l = 0; l < top; l++) {
     const struct amg_vecs v = amg_vecs_at(c, l);
     void *const buf[2] = {v.tmp, v.out};
     unsigned at = 0;
-    amg_smooth(c, l, &v, 0, NULL, buf[0], 0);
-    for (unsigned k = 1; k < nu; k++, at ^= 1)
-      amg_smooth(c, l, &v, k, buf[at], buf[at ^ 1], 0);
+    if (a->lv[l].ncol) { /* in place: the iterate is out */
+      at = 1;
+      amg_mcgs_first(c, l, &v);
+      for (unsigned k = 0; k < nu; k++)
+        amg_mcgs_sweep(c, l, &v, 0, k == 0, 0);
+    } else {
+      amg_smooth(c, l, &v, 0, NULL, buf[0], 0);
+      for (unsigned k = 1; k < nu; k++, at ^= 1)
+        amg_smooth(c, l, &v, k, buf[at], buf[at ^ 1], 0);
+    }
     amg_csr(c, LSB_AMG_RESID, &a->lv[l].A, buf[at], v.b, a->lv[l].minv, v.r); /* r = b - A x */
     amg_csr(c, LSB_AMG_SPMV, &a->lv[l].R, v.r, NULL, NULL, c->vec[l + 1].b);  /* the next level's b = R r */
   }
@@ -406,10 +513,15 @@ void amg_cycle(const struct amg_run *c) {
   for (unsigned l = top; l-- > 0;) {
     const struct amg_vecs v = amg_vecs_at(c, l);
     void *const buf[2] = {v.tmp, v.out};
-    unsigned at = (nu - 1) % 2;
+    unsigned at = a->lv[l].ncol ? 1 : (nu - 1) % 2;
     amg_csr(c, LSB_AMG_ADDP, &a->lv[l].P, c->vec[l + 1].out, NULL, NULL, buf[at]); /* x += P e */
-    for (unsigned k = 0; k < nu; k++, at ^= 1)
-      amg_smooth(c, l, &v, k, buf[at], buf[at ^ 1], k + 1 == nu);
+    if (a->lv[l].ncol) {
+      for (unsigned k = 0; k < nu; k++)
+        amg_mcgs_sweep(c, l, &v, 1, 0, k + 1 == nu);
+    } else {
+      for (unsigned k = 0; k < nu; k++, at ^= 1)
+        amg_smooth(c, l, &v, k, buf[at], buf[at ^ 1], k + 1 == nu);
+    }
   }
 }
 
@@ -440,6 +552,17 @@ unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *sv) {
   if (!a)
     return 0;
   return a->prec == LSB_AMG_PREC_FP32 ? a->cycle_bytes32 : a->cycle_mat_bytes + 8ull * a->cycle_vec_rows;
+}
+
+int lsb_hip_solver_amg_colours(lsb_hip_solver *sv, unsigned level, unsigned *ncolours) {
+  if (!lsb_initialized)
+    return 1;
+  const struct amg_dev *a = amg_of(sv);
+  if (!a || !a->mcgs || level + 1 >= a->nlev)
+    return 2;
+  if (ncolours)
+    *ncolours = a->lv[level].ncol;
+  return 0;
 }
 
 int lsb_hip_solver_amg_cheb_interval(lsb_hip_solver *sv, unsigned level, double *lo, double *hi) {

@@ -29,9 +29,14 @@
  * like the SpMM; the restart of opts.verify runs one un-gated cycle on r = b - S x.
  *
  * Served: one shard in one process, fp64 values, krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE / AMG.
- * Every other solver answers 2: nothing falls back to a loop of single solves.
+ * Every other solver answers 2: nothing falls back to a loop of single solves.  An AMG solver smoothed by multicolour
+ * Gauss-Seidel is not served either -- its cycle is not built on blocks -- but its SpMM is (spmm_serves).
  */
-static int mrhs_serves(const lsb_hip_solver *sv) {
+static int mrhs_mcgs(const lsb_hip_solver *sv) {
+  return sv->o.precond == LSB_PRECOND_AMG && sv->sh[0].amg && sv->sh[0].amg->mcgs;
+}
+
+static int spmm_serves(const lsb_hip_solver *sv) {
   const struct lsb_hip_opts *o = &sv->o;
   return !sv->multi && sv->nshard == 1 && !sv->dist && o->precision == LSB_PREC_FP64 &&
          (o->krylov == LSB_KRYLOV_PCG || o->krylov == LSB_KRYLOV_AUTO) &&
@@ -40,6 +45,8 @@ static int mrhs_serves(const lsb_hip_solver *sv) {
           (o->precond == LSB_PRECOND_AMG && sv->sh[0].amg && sv->sh[0].amg->prec == LSB_AMG_PREC_FP64)) &&
          o->persistent <= 0 && !sv->ps.use && (unsigned long long)sv->sh[0].n * LSB_MRHS_MAX < (1ull << 32);
 }
+
+static int mrhs_serves(const lsb_hip_solver *sv) { return spmm_serves(sv) && !mrhs_mcgs(sv); }
 
 static int mrhs_amg(const lsb_hip_solver *sv) { return sv->o.precond == LSB_PRECOND_AMG; }
 
@@ -70,7 +77,7 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
   w->parts_pq = (double *)(w->mem + 5 * blk);
   w->parts2 = (double *)(w->mem + 5 * blk + ppq);
   w->st = (struct lsb_mrhs_state *)(w->mem + 5 * blk + ppq + pp2);
-  if (mrhs_amg(sv)) { /* z and the blocks of the cycle's vectors */
+  if (mrhs_amg(sv) && !mrhs_mcgs(sv)) { /* z and the blocks of the cycle's vectors */
     w->av = lsb_calloc(struct amg_vecs, s->amg->nlev);
     w->amg_mem = amg_block_vecs(s->amg, kp, w->av);
     w->z = (double *)w->amg_mem;
@@ -321,7 +328,7 @@ int lsb_hip_solver_spmm_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_X
                             size_t ldy) {
   if (!lsb_initialized)
     return 1;
-  if (multi_args_bad(sv, nrhs, d_X, ldx, d_Y, ldy) || !mrhs_serves(sv))
+  if (multi_args_bad(sv, nrhs, d_X, ldx, d_Y, ldy) || !spmm_serves(sv))
     return 2;
   const struct shard *s = &sv->sh[0];
   for (unsigned c0 = 0; c0 < nrhs; c0 += LSB_MRHS_MAX) {

@@ -18,8 +18,8 @@
  * padded / re-ordered solver), the state the shard's d_st polled through the solver's pinned h_st.
  *
  * One shard: the hierarchy couples all rows (precond_shard_amg).  Only AMG: the V-cycle with l1-Jacobi sweeps,
- * or with the Chebyshev smoother on [rho / ratio, rho], is an SPD M with lambda(M^-1 S) <= 1, so the iteration
- * cannot diverge; FSAI, the Chebyshev polynomial and block-Jacobi give no such bound.
+ * with the Chebyshev smoother on [rho / ratio, rho], or with multicolour Gauss-Seidel forward and backward (a
+ * convergent smoother on every level), is an SPD M with lambda(M^-1 S) <= 1, so the iteration cannot diverge; FSAI, the Chebyshev polynomial and block-Jacobi give no such bound.
  */
 
 void richardson_check(const struct lsb_hip_opts *o, int sharded) {

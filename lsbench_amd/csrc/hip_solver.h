@@ -87,7 +87,8 @@ enum pcg_form {
 
 /* The vectors of one level of the AMG V-cycle: right-hand side, result, the other smoothing buffer, the residual, the
  * Chebyshev smoother's direction (NULL under l1-Jacobi).  double in the fp64 cycle (one column: amg_dev.vec; blocks of
- * kp: mrhs_work.av), float in the fp32 cycle.  Level 0 under fp64: b and out are NULL, the caller's r and z stand in */
+ * kp: mrhs_work.av), float in the fp32 cycle.  Level 0 under fp64: b and out are NULL, the caller's r and z stand in.
+ * A level smoothed by multicolour Gauss-Seidel keeps its iterate in out alone and does not touch tmp */
 struct amg_vecs {
   void *b, *out, *tmp, *r, *d;
 };
@@ -213,7 +214,9 @@ struct shard {
   /* AMG (PRECOND_AMG): the hierarchy on the device, z = one V-cycle (hip_amg_drv.c; hip_amg.hip, hip_amg_f32.hip) */
   struct amg_dev {
     unsigned nlev, tail, nu, nc, clanes; /* tail: first level of the one-launch tail (nlev: none) */
-    int prec, cheb;                      /* LSB_AMG_PREC_*; opts.amg_smoother == LSB_AMG_SMOOTH_CHEB */
+    int prec, cheb, mcgs;                /* LSB_AMG_PREC_*; opts.amg_smoother == LSB_AMG_SMOOTH_CHEB, == _MCGS */
+    unsigned mcgs_cap;                   /* mcgs: a level of more colours keeps l1-Jacobi */
+    unsigned long long mcgs_bytes;       /* mcgs: device bytes of the colour-sorted copies */
     /* a level, in the solver's precision: its matrices (.d fp64, .f fp32: packed entries), minv (double or float;
      * the Chebyshev smoother: 1 / a_ii) and, per smoothed level under that smoother, the interval of D^-1 A and
      * the coefficients of its nu steps (lsb_amg_cheb_coeffs; the fp32 launches round them) */
@@ -225,6 +228,13 @@ struct shard {
       } A, P, R;
       const void *minv;
       double lo, hi, c1[16], c2[16];
+      /* multicolour Gauss-Seidel (hip_amg_mcgs.hip): ncol > 0 on a level it smooths -- then minv holds 1 / a_ii, C is
+       * the colour-sorted copy of A (lsb_csr_mcgs), rowid its position -> row, colour8 the colour of every row and
+       * cbeg (host, ncol + 1) the colours' ranges of positions.  ncol_found: what the colouring gave, cap or not */
+      unsigned ncol, ncol_found, *cbeg;
+      union amg_mat C;
+      const int *rowid;
+      const unsigned char *colour8;
     } *lv;
     /* the single-column cycle's vectors.  Level 0's come out of the vector slab: under fp64 tmp and r; under fp32
      * the same two slab vectors split in halves -- tmp | out, and b (the fp32 copy of the caller's r) | r */

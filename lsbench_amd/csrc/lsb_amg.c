@@ -498,3 +498,150 @@ unsigned long long *lsb_csr_pack_f32(const struct csr *A) {
   }
   return w;
 }
+
+/* ---- multicolour Gauss-Seidel (LSB_AMG_SMOOTH_MCGS): colouring, the colour-sorted copy, the check ------------ */
+
+/* Greedy colouring of the stored pattern: rows in ascending order, each takes the smallest colour that none of its
+ * stored off-diagonal neighbours holds yet.  Structural (a stored zero is a neighbour) and serial: the same result
+ * for any thread count.  mark[c] == i + 1: colour c is held by a neighbour of row i. */
+int *lsb_amg_colour(const struct csr *A, unsigned *ncolours) {
+  if (!A || !ncolours)
+    return NULL;
+  const unsigned n = A->nrows, base = A->base;
+  int *colour = (int *)malloc((size_t)(n ? n : 1) * sizeof(int));
+  unsigned *mark = (unsigned *)calloc((size_t)n + 1, sizeof(unsigned));
+  if (!colour || !mark)
+    errx(EXIT_FAILURE, "hip_cdna4: out of host memory for the colouring of an AMG level (%u rows)", n);
+  unsigned nc = 0;
+  for (unsigned i = 0; i < n; i++)
+    colour[i] = -1;
+  for (unsigned i = 0; i < n; i++) {
+    for (unsigned e = A->offs[i]; e < A->offs[i + 1]; e++) {
+      const unsigned j = A->cols[e] - base;
+      if (j != i && j < n && colour[j] >= 0)
+        mark[colour[j]] = i + 1;
+    }
+    unsigned c = 0;
+    while (mark[c] == i + 1) /* (a row has fewer than n neighbours: mark[n] is never reached) */
+      c++;
+    colour[i] = (int)c;
+    if (c + 1 > nc)
+      nc = c + 1;
+  }
+  free(mark);
+  *ncolours = nc;
+  return colour;
+}
+
+/* The rows of A regrouped colour by colour, ascending row order inside a colour (a counting sort: stable); column
+ * ids stay A's, 0-based. */
+struct lsb_mcgs *lsb_csr_mcgs(const struct csr *A, const int *colour, unsigned ncolours) {
+  if (!A || !colour)
+    return NULL;
+  const unsigned n = A->nrows, base = A->base;
+  for (unsigned i = 0; i < n; i++)
+    if (colour[i] < 0 || (unsigned)colour[i] >= ncolours)
+      return NULL;
+  struct lsb_mcgs *M = lsb_calloc(struct lsb_mcgs, 1);
+  const unsigned long long nnz = A->offs[n];
+  M->n = n, M->ncolours = ncolours;
+  M->cbeg = lsb_calloc(unsigned, (size_t)ncolours + 1);
+  M->rowid = lsb_calloc(unsigned, (size_t)(n ? n : 1));
+  M->offs = lsb_calloc(unsigned, (size_t)n + 1);
+  M->cols = lsb_calloc(unsigned, (size_t)(nnz ? nnz : 1));
+  M->vals = lsb_calloc(double, (size_t)(nnz ? nnz : 1));
+  if (!M->cbeg || !M->rowid || !M->offs || !M->cols || !M->vals)
+    errx(EXIT_FAILURE, "hip_cdna4: out of host memory for the colour-sorted copy of an AMG level (%u rows)", n);
+  for (unsigned i = 0; i < n; i++)
+    M->cbeg[colour[i] + 1]++;
+  for (unsigned c = 0; c < ncolours; c++)
+    M->cbeg[c + 1] += M->cbeg[c];
+  unsigned *at = lsb_calloc(unsigned, (size_t)ncolours + 1);
+  memcpy(at, M->cbeg, ((size_t)ncolours + 1) * sizeof(unsigned));
+  for (unsigned i = 0; i < n; i++)
+    M->rowid[at[colour[i]]++] = i;
+  free(at);
+  for (unsigned p = 0; p < n; p++) {
+    const unsigned i = M->rowid[p], len = A->offs[i + 1] - A->offs[i];
+    unsigned w = M->offs[p];
+    for (unsigned e = A->offs[i]; e < A->offs[i + 1]; e++, w++)
+      M->cols[w] = A->cols[e] - base, M->vals[w] = A->vals[e];
+    M->offs[p + 1] = M->offs[p] + len;
+  }
+  return M;
+}
+
+void lsb_mcgs_free(struct lsb_mcgs *M) {
+  if (!M)
+    return;
+  free(M->cbeg), free(M->rowid), free(M->offs), free(M->cols), free(M->vals), free(M);
+}
+
+/* What k_amg_mcgs relies on to update x in place without a race, asserted on the host at every upload: 0, or the
+ * number of the violated rule and its text in why[whylen]. */
+int lsb_mcgs_check(const struct csr *A, const int *colour, const struct lsb_mcgs *M, char *why, size_t whylen) {
+#define MCGS_FAIL(code, ...)                 \
+  do {                                       \
+    if (why && whylen)                       \
+      snprintf(why, whylen, __VA_ARGS__);    \
+    free(seen);                              \
+    return code;                             \
+  } while (0)
+  unsigned char *seen = NULL;
+  if (!A || !colour || !M || !M->cbeg || !M->rowid || !M->offs || !M->cols || !M->vals)
+    MCGS_FAIL(1, "rule 1: a matrix, a colouring and a copy with all its arrays");
+  const unsigned n = A->nrows, base = A->base;
+  if (M->n != n || M->cbeg[0] != 0 || M->cbeg[M->ncolours] != n)
+    MCGS_FAIL(2, "rule 2: the colour ranges cover positions 0 .. n: cbeg[0] = 0, cbeg[ncolours] = n = %u", n);
+  for (unsigned c = 0; c < M->ncolours; c++)
+    if (M->cbeg[c] > M->cbeg[c + 1])
+      MCGS_FAIL(2, "rule 2: the colour ranges ascend (cbeg[%u] = %u > cbeg[%u] = %u)", c, M->cbeg[c], c + 1,
+                M->cbeg[c + 1]);
+  seen = (unsigned char *)calloc((size_t)n + 1, 1);
+  if (!seen)
+    MCGS_FAIL(1, "rule 1: out of host memory");
+  /* rowid is a permutation, and every row sits in the range of its own colour: in exactly one range */
+  for (unsigned c = 0; c < M->ncolours; c++)
+    for (unsigned p = M->cbeg[c]; p < M->cbeg[c + 1]; p++) {
+      const unsigned i = M->rowid[p];
+      if (i >= n || seen[i])
+        MCGS_FAIL(3, "rule 3: rowid is a permutation of the rows (position %u holds row %u %s)", p, i,
+                  i >= n ? "of no such row" : "a second time");
+      seen[i] = 1;
+      if (colour[i] != (int)c)
+        MCGS_FAIL(4, "rule 4: a row is in the range of its colour (row %u of colour %d at position %u, in the range "
+                     "of colour %u)", i, colour[i], p, c);
+    }
+  for (unsigned i = 0; i < n; i++) {
+    double d = 0.0;
+    for (unsigned e = A->offs[i]; e < A->offs[i + 1]; e++) {
+      const unsigned j = A->cols[e] - base;
+      if (j >= n)
+        MCGS_FAIL(5, "rule 5: every column is a row of the level (row %u has column %u of %u)", i, j, n);
+      if (j == i)
+        d += A->vals[e];
+      else if (colour[j] == colour[i])
+        MCGS_FAIL(6, "rule 6: rows coupled by a stored entry have different colours (a[%u][%u] is stored, both rows "
+                     "have colour %d)", i, j, colour[i]);
+    }
+    if (!(d > 0.0))
+      MCGS_FAIL(7, "rule 7: every diagonal is > 0 (row %u has %g)", i, d);
+  }
+  /* the copy's rows are the original rows, entry for entry */
+  if (M->offs[0] != 0)
+    MCGS_FAIL(8, "rule 8: the copy's offsets start at 0");
+  for (unsigned p = 0; p < n; p++) {
+    const unsigned i = M->rowid[p], len = A->offs[i + 1] - A->offs[i];
+    if (M->offs[p + 1] < M->offs[p] || M->offs[p + 1] - M->offs[p] != len || M->offs[p + 1] > A->offs[n])
+      MCGS_FAIL(8, "rule 8: position %u of the copy has the length of row %u (%u entries)", p, i, len);
+    for (unsigned k = 0; k < len; k++) {
+      const unsigned e = A->offs[i] + k, w = M->offs[p] + k;
+      if (M->cols[w] != A->cols[e] - base || memcmp(&M->vals[w], &A->vals[e], sizeof(double)) != 0)
+        MCGS_FAIL(8, "rule 8: the copy's rows are the original rows entry for entry (entry %u of row %u differs)", k,
+                  i);
+    }
+  }
+  free(seen);
+  return 0;
+#undef MCGS_FAIL
+}

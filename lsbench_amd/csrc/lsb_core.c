@@ -91,9 +91,12 @@ static void usage(const char *prog) {
   printf("                       amg = smoothed-aggregation AMG, one V-cycle with l1-Jacobi sweeps\n");
   printf("                       (--amg-theta T, --amg-sweeps NU, --amg-coarse ROWS, --amg-max-levels L,\n");
   printf("                       --amg-tail-rows ROWS: levels run in one launch), one shard, cg only;\n");
-  printf("                       --amg-smoother <l1|cheb>: cheb = a Chebyshev polynomial of degree NU in\n");
+  printf("                       --amg-smoother <l1|cheb|mcgs>: cheb = a Chebyshev polynomial of degree NU in\n");
   printf("                       D^-1 A in the place of the NU sweeps, on [rho / X, rho], rho the level's\n");
-  printf("                       Gershgorin bound, X = --amg-cheb-ratio (default 10);\n");
+  printf("                       Gershgorin bound, X = --amg-cheb-ratio (default 10); mcgs = multicolour\n");
+  printf("                       Gauss-Seidel, NU sweeps forward before and backward after the coarse\n");
+  printf("                       correction, a launch per colour, on levels of at most 16 colours (l1\n");
+  printf("                       elsewhere); one right-hand side at a time;\n");
   printf("                       --amg-precision <fp64|fp32>: fp32 = the whole V-cycle (matrices, level\n");
   printf("                       vectors, coarse inverse) in single precision inside the fp64 Krylov loop:\n");
   printf("                       8 instead of 12 bytes per entry, 4 instead of 8 per vector element; no\n");

@@ -513,6 +513,21 @@ void lsb_k_amg32_cheb(const struct amg_mat32 *m, const float *xin, const float *
 void lsb_k_amg32_dense(unsigned nc, unsigned lanes, int ends64, const float *cinv, const void *b, void *out,
                        const struct lsb_pcg_state *st, void *stream);
 
+/* ---- multicolour Gauss-Seidel smoothing (hip_amg_mcgs.hip; LSB_AMG_SMOOTH_MCGS).  m: the colour-sorted copy of the
+ * level's matrix (lsb_csr_mcgs; its lanes are the level's), rowid: position -> row, [p0, p1): one colour's range of
+ * positions.  One launch is one colour step in place: x_i <- fma(dinv_i, b_i - (row i) . x, x_i) on the rows of that
+ * colour.  _first: the first launch from the zero guess, over all n rows -- x_i = fma(dinv_i, b_i, 0) where
+ * colour[i] == 0, else 0; in64 / b32 as lsb_k_amg32_first.  z64 != NULL: the float result goes to x AND, widened, to
+ * z64.  The gate `st` as hip_amg.hip's launchers. */
+void lsb_k_amg_mcgs_first(unsigned n, const unsigned char *colour, const double *b, const double *dinv, double *x,
+                          const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg_mcgs(const struct lsb_amg_mat *m, const int *rowid, unsigned p0, unsigned p1, double *x,
+                    const double *b, const double *dinv, const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_mcgs_first(unsigned n, int in64, const unsigned char *colour, const void *b, const float *dinv,
+                            float *x, float *b32, const struct lsb_pcg_state *st, void *stream);
+void lsb_k_amg32_mcgs(const struct amg_mat32 *m, const int *rowid, unsigned p0, unsigned p1, float *x, const float *b,
+                      const float *dinv, double *z64, const struct lsb_pcg_state *st, void *stream);
+
 /* ---- backend internals shared between hip_cdna4.c and hip_comm.c -------- */
 void *lsb_hip_stream(void);
 int lsb_hip_is_initialized(void);

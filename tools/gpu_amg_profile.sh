@@ -10,8 +10,11 @@
 #   6. (on request) the V-cycle's precision: fp64 against fp32 (--amg-precision) at nu = 1, 2 on xn3b_A_18 and
 #      config 3, two fresh processes each, the variants alternating; then tools/gpu_amg_cycle_bw.py: the time of one
 #      application and amg_cycle_bytes over it
+#   7. (on request) multicolour Gauss-Seidel (--amg-smoother mcgs) at nu = 1, 2 beside l1-Jacobi nu = 1, 2 and
+#      Chebyshev nu = 2, fp64 and fp32 cycle, on xn3b_A_18 and config 3, two fresh processes each, the variants
+#      alternating; then tools/gpu_amg_cycle_bw.py with every smoother
 # Every GPU step has its own time limit; the script stops at the first step that fails.
-# Usage: tools/gpu_amg_profile.sh OUT_DIR [steps]   (steps: a subset of "123456", default "1234")
+# Usage: tools/gpu_amg_profile.sh OUT_DIR [steps]   (steps: a subset of "1234567", default "1234")
 OUT=${1:?usage: tools/gpu_amg_profile.sh OUT_DIR [steps]}
 STEPS=${2:-1234}
 mkdir -p "$OUT"
@@ -98,6 +101,27 @@ if [[ $STEPS == *6* ]]; then
   precisions c3 300 --matrix $C3 --operator raw --tol 1e-8 --trials=10
   for m in "$XN" $C3; do
     timeout -k 10 300 python tools/gpu_amg_cycle_bw.py "$m" 2>&1 | tee -a "$OUT/summary.txt"
+    [ ${PIPESTATUS[0]} -eq 0 ] || exit 1
+  done
+fi
+if [[ $STEPS == *7* ]]; then
+  mcgs_rows() { # PREFIX LIMIT_S ARGS...
+    local p=$1 lim=$2
+    shift 2
+    for rep in a b; do
+      for prec in fp64 fp32; do
+        run ${p}_l1_nu1_${prec}_$rep $lim "$@" --precond amg --amg-precision $prec || exit $?
+        run ${p}_mcgs_nu1_${prec}_$rep $lim "$@" --precond amg --amg-precision $prec --amg-smoother mcgs || exit $?
+        run ${p}_l1_nu2_${prec}_$rep $lim "$@" --precond amg --amg-precision $prec --amg-sweeps 2 || exit $?
+        run ${p}_cheb_nu2_${prec}_$rep $lim "$@" --precond amg --amg-precision $prec --amg-smoother cheb --amg-sweeps 2 || exit $?
+        run ${p}_mcgs_nu2_${prec}_$rep $lim "$@" --precond amg --amg-precision $prec --amg-smoother mcgs --amg-sweeps 2 || exit $?
+      done
+    done
+  }
+  mcgs_rows xn3b 120 --matrix "$XN" --trials=200
+  mcgs_rows c3 300 --matrix $C3 --operator raw --tol 1e-8 --trials=10
+  for m in "$XN" $C3; do
+    timeout -k 10 300 python tools/gpu_amg_cycle_bw.py "$m" all 2>&1 | tee -a "$OUT/summary.txt"
     [ ${PIPESTATUS[0]} -eq 0 ] || exit 1
   done
 fi
