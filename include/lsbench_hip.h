@@ -277,6 +277,17 @@ struct lsb_hip_opts {
                         serve blocks of columns                    [L1JACOBI] */
   double amg_cheb_ratio; /* hi / lo of the Chebyshev smoother's interval; values below
                         1.5 are taken as 1.5                                  [10] */
+  /* The tail: members appended behind the ones above, so that none of their offsets moves.  An
+   * anonymous struct -- they are members of lsb_hip_opts like the others (o.fsai_blocks) -- which
+   * the Python mirror (_lib.Opts) keeps apart in the same way: its field list is the members above,
+   * and tests pin that list's end and compare it with them. */
+  struct {
+    int fsai_blocks; /* LSB_PRECOND_FSAI: 1 = the solver serves blocks of right-hand sides
+                        (solve_multi[_dev], solve_multi_x0_dev, precond_multi_dev) where it
+                        is otherwise servable; its single-column paths are unchanged.  0: it
+                        answers 2 on blocks and allocates nothing for them.  Ignored under
+                        every other preconditioner.  A later change may flip the default  [0] */
+  };
 };
 enum { LSB_PREC_FP64 = 0, LSB_PREC_MIXED = 1 };
 
@@ -818,8 +829,10 @@ int lsb_hip_solver_jacobi_sweep_dev(lsb_hip_solver *s, double w,
  * pointers) and for a solver this version does not serve.  Served: one shard in one process, LSB_PREC_FP64,
  * krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE / AMG (one V-cycle per iteration on the block of
  * residuals: every matrix of the hierarchy is streamed once for all columns, and a column's z has the bits of
- * the single-column cycle; opts.amg_tail_rows is ignored there); GMRES, BiCGSTAB, PCG1, Chebyshev, block-Jacobi,
- * FSAI, nvirt > 1, distributed and persistent solvers answer 2, and so does an AMG solver smoothed by multicolour
+ * the single-column cycle; opts.amg_tail_rows is ignored there), and FSAI where opts.fsai_blocks is set (z = G^T (G r)
+ * on the block, the x / r update riding in the two products: four launches an iteration, hip_mrhs_fsai.hip; the
+ * single-column paths of such a solver are unchanged); GMRES, BiCGSTAB, PCG1, Chebyshev, block-Jacobi,
+ * FSAI without opts.fsai_blocks, nvirt > 1, distributed and persistent solvers answer 2, and so does an AMG solver smoothed by multicolour
  * Gauss-Seidel (LSB_AMG_SMOOTH_MCGS: its cycle is not built on blocks; lsb_hip_solver_spmm_dev still serves it) --
  * nothing falls back to a loop of single solves.
  * res[c] (nrhs entries) is column c's own result: iters, status, relres, corrections, true_relres are the
@@ -852,13 +865,19 @@ int lsb_hip_solver_solve_multi_x0_dev(lsb_hip_solver *s, unsigned nrhs, const do
  * vector]) with n the internal row count and Kp the batch width -- the CSR arrays once whatever the width,
  * 2 passes of the SpMM (x once, y once) and the 9 of the classic form's sweeps per column, the diagonal once
  * per sweep for all columns; 0 where solve_multi does not apply, and 0 for an AMG solver: an iteration around a
- * V-cycle has another shape, as lsb_hip_solver_iteration_bytes answers for every such preconditioner */
+ * V-cycle has another shape, as lsb_hip_solver_iteration_bytes answers for every such preconditioner.
+ * FSAI on blocks (opts.fsai_blocks): 12 (nnz_S + nnz_G + nnz_G^T) + 12 (n + 1) + 8 n 16 Kp -- the three matrices once
+ * each whatever the width, and 16 vector passes per column: the SpMM 2; the launch of G 6 (q and r gathered, p and x
+ * in, x and t out); the launch of G^T 5 (t gathered, q and r in, r and z out); the direction sweep 3 */
 unsigned long long lsb_hip_solver_multi_iteration_bytes(const lsb_hip_solver *s, unsigned nrhs);
-/* Z_c = M^-1 R_c for nrhs columns: the V-cycle of a batch's iteration on its own (blocks as above: column-major
- * with a leading dimension, caller's numbering; any nrhs >= 1, in batches of 8 and a remainder).  Column c of Z
- * has the bits of lsb_hip_solver_precond_dev on column c alone.  1 when the backend is not initialised; 2 for
- * null pointers, nrhs == 0, ld < n_local and for every solver that solve_multi does not serve under AMG (Jacobi,
- * FSAI, Chebyshev and block-Jacobi solvers among them); Z is not touched then. */
+/* entries of G and of G^T of an LSB_PRECOND_FSAI solver (either pointer may be NULL); 2 for any other solver */
+int lsb_hip_solver_fsai_nnz(const lsb_hip_solver *s, unsigned long long *g, unsigned long long *gt);
+/* Z_c = M^-1 R_c for nrhs columns: the V-cycle of a batch's iteration on its own, or -- FSAI with opts.fsai_blocks --
+ * the two products Z = G^T (G R) (blocks as above: column-major with a leading dimension, caller's numbering; any
+ * nrhs >= 1, in batches of 8 and a remainder).  Under AMG column c of Z has the bits of
+ * lsb_hip_solver_precond_dev on column c alone.  1 when the backend is not initialised; 2 for null pointers,
+ * nrhs == 0, ld < n_local and for every solver that solve_multi does not serve under AMG or FSAI (Jacobi, Chebyshev
+ * and block-Jacobi solvers, and FSAI without opts.fsai_blocks, among them); Z is not touched then. */
 int lsb_hip_solver_precond_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_R, size_t ldr,
                                      double *d_Z, size_t ldz);
 

@@ -69,6 +69,23 @@ class Opts(C.Structure):
                 ("amg_max_levels", C.c_int), ("amg_tail_rows", C.c_int),
                 ("amg_precision", C.c_int),
                 ("amg_smoother", C.c_int), ("amg_cheb_ratio", C.c_double)]
+    # Members the C struct has gained BEHIND amg_cheb_ratio -- appended there so that no earlier offset moves -- are
+    # not in _fields_ (tests pin the list's end): they live in a tail every instance is resized by, name ->
+    # (offset behind the fields, C type), and read and write like the fields.
+    _TAIL = {"fsai_blocks": (0, C.c_int)}
+    _TAIL_BYTES = 8  # the ints of the tail, padded to the struct's alignment of 8
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        C.resize(self, C.sizeof(type(self)) + self._TAIL_BYTES)
+        C.memset(C.addressof(self) + C.sizeof(type(self)), 0, self._TAIL_BYTES)
+
+    def _tail(self, name):
+        off, ctype = self._TAIL[name]
+        return ctype.from_address(C.addressof(self) + C.sizeof(type(self)) + off)
+
+    fsai_blocks = property(lambda self: self._tail("fsai_blocks").value,
+                           lambda self, v: setattr(self._tail("fsai_blocks"), "value", v))
 
 
 class Result(C.Structure):
@@ -263,6 +280,7 @@ SIGNATURES = {
     "lsb_hip_solver_solve_multi_x0_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_multi_iteration_bytes": (C.c_ulonglong, [_vp, _u]),
     "lsb_hip_solver_precond_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "lsb_hip_solver_fsai_nnz": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "lsb_hip_solver_precond_dev": (_i, [_vp, _vp, _vp]),
     "lsb_hip_solver_amg_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u)]),
     "lsb_hip_solver_amg_precision": (_i, [_vp]),

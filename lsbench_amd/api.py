@@ -397,13 +397,24 @@ class Solver:
         L.check(L.load().lsb_hip_solver_precond_dev(self._h, _ptr(d_r), _ptr(d_z)), "precond_dev")
 
     def precond_multi_dev(self, d_R, d_Z):
-        """Z = M^-1 R (AMG: one V-cycle per column) for the nrhs columns held as the ROWS of two 2-D device
-        tensors (ld = stride(0)); a column of Z has the bits of precond_dev on that column alone."""
+        """Z = M^-1 R (AMG: one V-cycle per column; FSAI with opts.fsai_blocks: G^T (G r)) for the nrhs columns held
+        as the ROWS of two 2-D device tensors (ld = stride(0)); under AMG a column of Z has the bits of precond_dev
+        on that column alone."""
         pr, k, ldr = self._block(d_R, "precond_multi_dev")
         pz, kz, ldz = self._block(d_Z, "precond_multi_dev")
         if k != kz:
             raise ValueError("precond_multi_dev: R and Z hold different numbers of columns")
         L.check(L.load().lsb_hip_solver_precond_multi_dev(self._h, k, pr, ldr, pz, ldz), "precond_multi_dev")
+
+    @property
+    def fsai_nnz(self):
+        """(entries of G, entries of G^T) of an FSAI-preconditioned solver; None for any other."""
+        g, gt = C.c_ulonglong(), C.c_ulonglong()
+        rc = L.load().lsb_hip_solver_fsai_nnz(self._h, C.byref(g), C.byref(gt))
+        if rc == 2:
+            return None
+        L.check(rc, "fsai_nnz")
+        return int(g.value), int(gt.value)
 
     @property
     def amg_info(self):

@@ -100,6 +100,7 @@ void lsb_hip_opts_default(struct lsb_hip_opts *o) {
   o->amg_smoother = LSB_AMG_SMOOTH_L1JACOBI;
   o->amg_cheb_ratio = 10.0;
   o->amg_precision = LSB_AMG_PREC_FP64;
+  o->fsai_blocks = 0; /* opt-in: an FSAI solver from default options answers 2 on blocks */
 }
 
 /* ONE typed table for everything a caller may set by name: the command line of a host
@@ -167,6 +168,7 @@ static const struct optdef {
     OPT("amg-smoother", OT_ENUM, amg_smoother, CH_AMG_SMOOTHER),
     OPT("amg-cheb-ratio", OT_DBL, amg_cheb_ratio, NULL),
     OPT("amg-precision", OT_ENUM, amg_precision, CH_AMG_PRECISION),
+    OPT("fsai-blocks", OT_INT, fsai_blocks, NULL),
 };
 #undef OPT
 #define NOPTS (sizeof OPTS / sizeof OPTS[0])

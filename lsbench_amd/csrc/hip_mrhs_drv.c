@@ -1,4 +1,4 @@
-/* Several right-hand sides: host driver (kernels: hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_amg.hip). */
+/* Several right-hand sides: host driver (kernels: hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_amg.hip, hip_mrhs_fsai.hip). */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
@@ -28,7 +28,15 @@
  * sweep leaves (r.z, r.r) of every column, there is no dot-product launch.  The cycle is gated on `running`
  * like the SpMM; the restart of opts.verify runs one un-gated cycle on r = b - S x.
  *
- * Served: one shard in one process, fp64 values, krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE / AMG.
+ * LSB_PRECOND_FSAI with opts.fsai_blocks: z = G^T (G r) is a block of its own as well, and the x / r sweep rides in the
+ * two products (hip_mrhs_fsai.hip): an iteration is SpMM, k_mrhs_fsai_xr_gr (alpha, x, t = G r' with r' formed in the
+ * gather), k_mrhs_fsai_gt_dots (z = G^T t, r' stored in place, the records of (r.z, r.r)), k_amg_mrhs_update_p.  There
+ * is ONE residual block: init, a warm start and a verify restart write it and run the two products un-gated as SpMMs
+ * off G and G^T where the AMG branch runs its cycle.  Without opts.fsai_blocks such a solver answers 2 and
+ * allocates nothing.
+ *
+ * Served: one shard in one process, fp64 values, krylov PCG or AUTO, precond JACOBI / L1JACOBI / NONE / AMG, and FSAI
+ * where opts.fsai_blocks is set.
  * Every other solver answers 2: nothing falls back to a loop of single solves.  An AMG solver smoothed by multicolour
  * Gauss-Seidel is not served either -- its cycle is not built on blocks -- but its SpMM is (spmm_serves).
  */
@@ -42,13 +50,19 @@ static int spmm_serves(const lsb_hip_solver *sv) {
          (o->krylov == LSB_KRYLOV_PCG || o->krylov == LSB_KRYLOV_AUTO) &&
          (o->precond == LSB_PRECOND_JACOBI || o->precond == LSB_PRECOND_L1JACOBI ||
           o->precond == LSB_PRECOND_NONE ||
-          (o->precond == LSB_PRECOND_AMG && sv->sh[0].amg && sv->sh[0].amg->prec == LSB_AMG_PREC_FP64)) &&
+          (o->precond == LSB_PRECOND_AMG && sv->sh[0].amg && sv->sh[0].amg->prec == LSB_AMG_PREC_FP64) ||
+          (o->precond == LSB_PRECOND_FSAI && o->fsai_blocks && sv->sh[0].fs_g.offs && sv->sh[0].fs_gt.offs)) &&
          o->persistent <= 0 && !sv->ps.use && (unsigned long long)sv->sh[0].n * LSB_MRHS_MAX < (1ull << 32);
 }
 
 static int mrhs_serves(const lsb_hip_solver *sv) { return spmm_serves(sv) && !mrhs_mcgs(sv); }
 
 static int mrhs_amg(const lsb_hip_solver *sv) { return sv->o.precond == LSB_PRECOND_AMG; }
+
+static int mrhs_fsai(const lsb_hip_solver *sv) { return sv->o.precond == LSB_PRECOND_FSAI; }
+
+/* z is a block of its own, written between the x / r update and lsb_k_amg_mrhs_update_p */
+static int mrhs_zblock(const lsb_hip_solver *sv) { return mrhs_amg(sv) || mrhs_fsai(sv); }
 
 static unsigned batch_width(unsigned nrhs) { return nrhs <= 2 ? 2u : nrhs <= 4 ? 4u : 8u; }
 
@@ -62,21 +76,28 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
     /* lanes per row of the SpMM: the shard's (from its mean row length); LSBENCH_HIP_MRHS_LANES is the A/B switch */
     const char *e = getenv("LSBENCH_HIP_MRHS_LANES");
     sv->mr_lanes = e && atoi(e) > 0 ? (unsigned)atoi(e) : s->lanes;
+    /* ... of G and of G^T under FSAI: each matrix's own; LSBENCH_HIP_MRHS_FSAI_LANES is the A/B switch for both (the
+     * single-column kernels never see it) */
+    e = getenv("LSBENCH_HIP_MRHS_FSAI_LANES");
+    sv->mr_fs_lanes = e && atoi(e) > 0 ? (unsigned)atoi(e) : 0;
   }
   /* 256-byte aligned pieces of one allocation, the blocks first: their placement relative to one another is
    * the same in every solver */
   const size_t blk = (((size_t)s->n * kp * sizeof(double)) + 255) & ~(size_t)255;
   const size_t ppq = (size_t)LSB_MAX_PARTIALS * kp * sizeof(double);
-  /* (an AMG solver's records of (r.z, r.r) come from a row kernel's grid, not from a sweep's) */
-  const size_t pp2 = (size_t)(mrhs_amg(sv) ? LSB_MAX_PARTIALS : LSB_STREAM_GRID_CAP) * 2 * kp * sizeof(double);
+  /* (an AMG or FSAI solver's records of (r.z, r.r) come from a row kernel's grid, not from a sweep's) */
+  const size_t pp2 = (size_t)(mrhs_zblock(sv) ? LSB_MAX_PARTIALS : LSB_STREAM_GRID_CAP) * 2 * kp * sizeof(double);
+  const size_t nblk = mrhs_fsai(sv) ? 7 : 5; /* FSAI: z and t behind the five */
   const size_t stb = (sizeof(struct lsb_mrhs_state) + 255) & ~(size_t)255;
-  w->mem = (char *)lsb_hip_malloc(5 * blk + ppq + pp2 + stb);
-  LSB_CHK_HIP(hipMemsetAsync(w->mem, 0, 5 * blk + ppq + pp2 + stb, g_stream));
+  w->mem = (char *)lsb_hip_malloc(nblk * blk + ppq + pp2 + stb);
+  LSB_CHK_HIP(hipMemsetAsync(w->mem, 0, nblk * blk + ppq + pp2 + stb, g_stream));
   w->b = (double *)w->mem, w->x = (double *)(w->mem + blk), w->r = (double *)(w->mem + 2 * blk);
   w->p = (double *)(w->mem + 3 * blk), w->q = (double *)(w->mem + 4 * blk);
-  w->parts_pq = (double *)(w->mem + 5 * blk);
-  w->parts2 = (double *)(w->mem + 5 * blk + ppq);
-  w->st = (struct lsb_mrhs_state *)(w->mem + 5 * blk + ppq + pp2);
+  w->parts_pq = (double *)(w->mem + nblk * blk);
+  w->parts2 = (double *)(w->mem + nblk * blk + ppq);
+  w->st = (struct lsb_mrhs_state *)(w->mem + nblk * blk + ppq + pp2);
+  if (mrhs_fsai(sv))
+    w->z = (double *)(w->mem + 5 * blk), w->t = (double *)(w->mem + 6 * blk);
   if (mrhs_amg(sv) && !mrhs_mcgs(sv)) { /* z and the blocks of the cycle's vectors */
     w->av = lsb_calloc(struct amg_vecs, s->amg->nlev);
     w->amg_mem = amg_block_vecs(s->amg, kp, w->av);
@@ -106,6 +127,11 @@ unsigned long long lsb_hip_solver_multi_iteration_bytes(const lsb_hip_solver *sv
     return 0;
   const struct shard *s = &sv->sh[0];
   const unsigned kp = nrhs == 1 ? 1u : batch_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs);
+  /* FSAI on blocks: S, G and G^T once each whatever the width, and 16 vector passes per column -- the SpMM 2 (p in,
+   * q out); k_mrhs_fsai_xr_gr 6 (q and r gathered, p and x of the own rows in, x and t out); k_mrhs_fsai_gt_dots 5 (t
+   * gathered, q and r of the own rows in, r and z out); k_amg_mrhs_update_p 3 (z and p in, p out) */
+  if (mrhs_fsai(sv))
+    return 12ull * (s->nnz + s->fs_g.nnz + s->fs_gt.nnz) + 12ull * (s->n + 1ull) + 8ull * s->n * 16ull * kp;
   return 12ull * s->nnz + 4ull * (s->n + 1ull) + 8ull * s->n * (11ull * kp + (s->dinv_uniform ? 0u : 2u));
 }
 
@@ -140,10 +166,42 @@ static void spmm_shard(lsb_hip_solver *sv, struct mrhs_work *w, const double *x,
                  g_stream);
 }
 
+static unsigned fs_lanes(const lsb_hip_solver *sv, const struct fsai_csr *c) {
+  return sv->mr_fs_lanes ? sv->mr_fs_lanes : c->lanes;
+}
+
+/* Z = G^T (G R) of this width, un-gated: two SpMMs off the factor's CSRs.  Their records of x.y, which nobody reads,
+ * go into parts2: every caller's next launch writes that anew, while parts_pq may still hold a verify round's
+ * residual norms for the launches behind this one */
+static void mrhs_fsai_apply(const lsb_hip_solver *sv, const struct mrhs_work *w) {
+  const struct shard *s = &sv->sh[0];
+  unsigned np = 0;
+  lsb_k_spmm_csr(w->kp, s->n, s->fs_g.offs, s->fs_g.cols, s->fs_g.vals, fs_lanes(sv, &s->fs_g), w->r, w->t, NULL,
+                 w->parts2, &np, NULL, g_stream);
+  lsb_k_spmm_csr(w->kp, s->n, s->fs_gt.offs, s->fs_gt.cols, s->fs_gt.vals, fs_lanes(sv, &s->fs_gt), w->t, w->z, NULL,
+                 w->parts2, &np, NULL, g_stream);
+}
+
+/* z = M^-1 r of every column, un-gated: the V-cycle, or FSAI's two products */
+static void mrhs_zapply(const lsb_hip_solver *sv, const struct mrhs_work *w) {
+  if (mrhs_fsai(sv))
+    mrhs_fsai_apply(sv, w);
+  else
+    mrhs_cycle(sv, w, NULL, NULL, NULL);
+}
+
 static void mrhs_enqueue_iter(lsb_hip_solver *sv, struct mrhs_work *w, int parity) {
   const struct shard *s = &sv->sh[0];
   unsigned npq = 0, np2 = 0;
   spmm_shard(sv, w, w->p, w->q, NULL, &npq, w->st);
+  if (mrhs_fsai(sv)) {
+    lsb_k_mrhs_fsai_xr_gr(w->kp, s->n, s->fs_g.offs, s->fs_g.cols, s->fs_g.vals, fs_lanes(sv, &s->fs_g), w->p, w->q,
+                          w->x, w->r, w->t, w->st, parity, w->parts_pq, npq, g_stream);
+    lsb_k_mrhs_fsai_gt_dots(w->kp, s->n, s->fs_gt.offs, s->fs_gt.cols, s->fs_gt.vals, fs_lanes(sv, &s->fs_gt), w->t,
+                            w->q, w->r, w->z, w->parts2, &np2, w->st, parity, g_stream);
+    lsb_k_amg_mrhs_update_p(w->kp, s->n, w->z, w->p, w->st, parity, w->parts2, np2, g_stream);
+    return;
+  }
   if (mrhs_amg(sv)) {
     lsb_k_amg_mrhs_update_xr(w->kp, s->n, w->p, w->q, w->x, w->r, w->st, parity, w->parts_pq, npq, g_stream);
     mrhs_cycle(sv, w, w->parts2, &np2, w->st);
@@ -210,17 +268,17 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
     lsb_k_mrhs_pack(n, kp, nb, sv->d_perm, d_X, ldx, w->x, g_stream);
     lsb_k_mrhs_x0_bb(kp, n, w->b, w->parts_bb, &nbb, g_stream);
     spmm_shard(sv, w, w->x, w->r, w->b, &npq, NULL);
-    if (mrhs_amg(sv)) {
+    if (mrhs_zblock(sv)) {
       lsb_k_amg_mrhs_x0_start(kp, n, w->x, w->parts_bb, nbb, g_stream);
-      mrhs_cycle(sv, w, NULL, NULL, NULL);
+      mrhs_zapply(sv, w);
       lsb_k_amg_mrhs_init_p(kp, n, w->r, w->z, w->p, w->parts2, &np2, g_stream);
     } else
       lsb_k_mrhs_x0_start(kp, n, w->r, DINV(s), w->x, w->p, w->parts_bb, nbb, w->parts2, &np2, g_stream);
     lsb_k_mrhs_init_state(kp, w->st, w->parts2, np2, w->parts_bb, nbb, sv->o.tol, (int)sv->o.maxit, g_stream);
   } else {
-    if (mrhs_amg(sv)) { /* x = 0, r = b ; z = M^-1 b ; p = z and (b.z, b.b) */
+    if (mrhs_zblock(sv)) { /* x = 0, r = b ; z = M^-1 b ; p = z and (b.z, b.b) */
       lsb_k_amg_mrhs_init(kp, n, w->b, w->x, w->r, g_stream);
-      mrhs_cycle(sv, w, NULL, NULL, NULL);
+      mrhs_zapply(sv, w);
       lsb_k_amg_mrhs_init_p(kp, n, w->b, w->z, w->p, w->parts2, &np2, g_stream);
     } else
       lsb_k_mrhs_init(kp, n, w->b, DINV(s), w->x, w->r, w->p, w->parts2, &np2, g_stream);
@@ -239,9 +297,9 @@ static void mrhs_batch(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
     /* "converged" is reported only for the residual RECOMPUTED from x */
     const int more = round < LSB_MAX_CORRECTIONS;
     spmm_shard(sv, w, w->x, w->q, w->b, &npq, NULL);
-    if (mrhs_amg(sv)) { /* r = b - S x, z = M^-1 r, p = z and r.z, for the restarting columns */
+    if (mrhs_zblock(sv)) { /* r = b - S x, z = M^-1 r, p = z and r.z, for the restarting columns */
       lsb_k_amg_mrhs_restart_r(kp, n, w->q, w->r, w->st, w->parts_pq, npq, more, g_stream);
-      mrhs_cycle(sv, w, NULL, NULL, NULL);
+      mrhs_zapply(sv, w);
       lsb_k_amg_mrhs_restart_p(kp, n, w->r, w->z, w->p, w->st, w->parts_pq, npq, more, w->parts2, &np2, g_stream);
     } else
       lsb_k_mrhs_restart(kp, n, w->q, DINV(s), w->r, w->p, w->st, w->parts_pq, npq, more, w->parts2, &np2, g_stream);
@@ -343,22 +401,34 @@ int lsb_hip_solver_spmm_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_X
   return 0;
 }
 
-/* Z_c = M^-1 R_c, one V-cycle per column of the block, through the same pack / unpack: the cycle of an
- * iteration on its own, un-gated.  A solver that solve_multi does not serve under AMG answers 2. */
+/* Z_c = M^-1 R_c, one V-cycle per column of the block -- or FSAI's two products -- through the same pack / unpack:
+ * the preconditioner of an iteration on its own, un-gated.  A solver that solve_multi does not serve under AMG or
+ * FSAI answers 2. */
 int lsb_hip_solver_precond_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_R, size_t ldr, double *d_Z,
                                      size_t ldz) {
   if (!lsb_initialized)
     return 1;
-  if (multi_args_bad(sv, nrhs, d_R, ldr, d_Z, ldz) || !mrhs_serves(sv) || !mrhs_amg(sv))
+  if (multi_args_bad(sv, nrhs, d_R, ldr, d_Z, ldz) || !mrhs_serves(sv) || !mrhs_zblock(sv))
     return 2;
   const struct shard *s = &sv->sh[0];
   for (unsigned c0 = 0; c0 < nrhs; c0 += LSB_MRHS_MAX) {
     const unsigned nb = nrhs - c0 < LSB_MRHS_MAX ? nrhs - c0 : LSB_MRHS_MAX;
     struct mrhs_work *w = mrhs_setup(sv, batch_width(nb));
     lsb_k_mrhs_pack(s->n, w->kp, nb, sv->d_perm, d_R + (size_t)c0 * ldr, ldr, w->r, g_stream);
-    mrhs_cycle(sv, w, NULL, NULL, NULL);
+    mrhs_zapply(sv, w);
     lsb_k_mrhs_unpack(s->n, w->kp, nb, sv->d_perm, w->z, d_Z + (size_t)c0 * ldz, ldz, g_stream);
   }
   drain_stream(sv, "lsb_hip_solver_precond_multi_dev");
+  return 0;
+}
+
+/* entries of G and of G^T of an FSAI solver (what lsb_hip_solver_multi_iteration_bytes counts); 2 for any other */
+int lsb_hip_solver_fsai_nnz(const lsb_hip_solver *sv, unsigned long long *g, unsigned long long *gt) {
+  if (!sv || sv->o.precond != LSB_PRECOND_FSAI || !sv->sh[0].fs_g.offs)
+    return 2;
+  if (g)
+    *g = sv->sh[0].fs_g.nnz;
+  if (gt)
+    *gt = sv->sh[0].fs_gt.nnz;
   return 0;
 }

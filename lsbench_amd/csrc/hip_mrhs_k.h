@@ -110,7 +110,7 @@ static unsigned kshift_of(unsigned kp) {
   return kp == 2 ? 1u : kp == 4 ? 2u : 3u;
 }
 // grid of the sweeps over n rows of kp columns: 16 B per lane over n kp doubles
-static unsigned sweep_grid(unsigned n, unsigned kp) { return lsb_k_blas1_grid(n * kp); }
+static inline unsigned sweep_grid(unsigned n, unsigned kp) { return lsb_k_blas1_grid(n * kp); }
 
 #define KP_DISPATCH(kp, CALL)                                                  \
   do {                                                                         \

@@ -328,11 +328,13 @@ struct lsb_hip_solver {
     char *amg_mem;
     double *z;
     struct amg_vecs *av; /* (amg_block_vecs) */
+    double *t; /* an FSAI solver's (opts.fsai_blocks): t = G r; it and z are two more blocks of mem */
     unsigned hint[LSB_MAX_CORRECTIONS + 1]; /* launches the previous batch's solve and restarts took */
     struct graph_cache g;        /* its own graph cache, keyed on the count: the iteration touches these buffers only */
   } mr[3];
   struct lsb_mrhs_state *mr_hst; /* pinned, 2 slots */
   unsigned mr_lanes;             /* lanes per row of its SpMM */
+  unsigned mr_fs_lanes;          /* FSAI on blocks: lanes per row of G and of G^T, 0 = each matrix's own */
   hipEvent_t ev_poll[2], ev_vec, ev_halo;
   hipEvent_t ev[4 * MAX_SAMPLES], ev_t0, ev_t1; /* per sample: e0 SpMV e1 e2 e3 */
   unsigned char samp_skip[MAX_SAMPLES];         /* the sample brackets nothing (a run's first iteration in the

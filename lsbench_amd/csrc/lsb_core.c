@@ -88,6 +88,8 @@ static void usage(const char *prog) {
   printf("                       cached dense inverse, for operators of a few thousand rows); fsai =\n");
   printf("                       factorised sparse approximate inverse G^T G on the pattern of\n");
   printf("                       tril(S^k), k = --fsai-power (default 3), set up once on the device;\n");
+  printf("                       --fsai-blocks <0|1>: 1 = such a solver also serves blocks of right-hand\n");
+  printf("                       sides (the library's solve_multi calls; default 0);\n");
   printf("                       amg = smoothed-aggregation AMG, one V-cycle with l1-Jacobi sweeps\n");
   printf("                       (--amg-theta T, --amg-sweeps NU, --amg-coarse ROWS, --amg-max-levels L,\n");
   printf("                       --amg-tail-rows ROWS: levels run in one launch), one shard, cg only;\n");
@@ -126,6 +128,7 @@ struct lsbench *lsbench_init(int argc, char *argv[]) {
       {"amg-coarse", required_argument, 0, 80}, {"amg-max-levels", required_argument, 0, 80},
       {"amg-tail-rows", required_argument, 0, 80}, {"amg-smoother", required_argument, 0, 80},
       {"amg-cheb-ratio", required_argument, 0, 80}, {"amg-precision", required_argument, 0, 80},
+      {"fsai-blocks", required_argument, 0, 80},
       {0, 0, 0, 0}};
 
   /* zero-filled => solver 0 (CUSOLVER), ordering 0 (RCM), FP64: the

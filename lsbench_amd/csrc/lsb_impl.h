@@ -95,7 +95,8 @@ struct lsb_bcg_state {
 };
 
 /* ---- device-side state of a batch of right-hand sides (hip_mrhs.hip) -----------
- * One lsb_pcg_state per column (status, iters, maxit, bb, thresh2, rr, rz[2], pq are used) and the words
+ * One lsb_pcg_state per column (status, iters, maxit, bb, thresh2, rr, rz[2], pq are used; under FSAI also
+ * alpha[parity], the step length on its way from one row kernel to the next) and the words
  * of the batch.  A column whose status != 0 is frozen; running = some column's status is 0. */
 #define LSB_MRHS_MAX 8
 struct lsb_mrhs_state {
@@ -377,6 +378,16 @@ void lsb_k_amg_mrhs_restart_r(unsigned kp, unsigned n, const double *q, double *
 void lsb_k_amg_mrhs_restart_p(unsigned kp, unsigned n, const double *r, const double *z, double *p,
                               const struct lsb_mrhs_state *st, const double *rr_parts, unsigned nrr, int more,
                               double *partials, unsigned *npartials, void *stream);
+/* FSAI on blocks (hip_mrhs_fsai.hip), between lsb_k_spmm_csr and lsb_k_amg_mrhs_update_p: G and G^T as CSR, `lanes`
+ * per row.  xr_gr: alpha_c from the SpMM's records (lsb_k_mrhs_update_xr's decisions; alpha_c left in the column's
+ * alpha[parity]), x += alpha p, t = G (r - alpha q) -- r is only read.  gt_dots: z = G^T t, r -= alpha q in place on
+ * the own rows, one record per workgroup of (r_c . z_c, then r_c . r_c); a no-op once st->running == 0. */
+void lsb_k_mrhs_fsai_xr_gr(unsigned kp, unsigned n, const int *goffs, const int *gcols, const double *gvals,
+                           unsigned lanes, const double *p, const double *q, double *x, const double *r, double *t,
+                           struct lsb_mrhs_state *st, int parity, const double *pq_parts, unsigned npq, void *stream);
+void lsb_k_mrhs_fsai_gt_dots(unsigned kp, unsigned n, const int *offs, const int *cols, const double *vals,
+                             unsigned lanes, const double *t, const double *q, double *r, double *z, double *records,
+                             unsigned *nrecords, const struct lsb_mrhs_state *st, int parity, void *stream);
 
 /* ---- preconditioners with z as a vector (hip_precond_k.hip) -------------------- */
 void lsb_k_dot2(unsigned n, const double *r, const double *z, double *partials2,

@@ -15,12 +15,15 @@ One JSON line on stdout: per operator and nrhs
   gain                                 true only where (b)'s slowest repetition beats (a)'s fastest
 --precond amg: the same protocol on an AMG solver (single AMG solves against batches under AMG on that solver);
 multi_iteration_bytes is 0 there (an iteration around a V-cycle has another shape) and so is frac_of_8TBs.
+--precond fsai [--fsai-power K]: the same protocol on an FSAI solver created with fsai_blocks = 1, whose single-column
+paths are the default FSAI solver's: (a) nrhs single FSAI solves (the fused three-launch iteration where it applies)
+against (b) one batch (four launches an iteration) on that solver.
 --verbose: the solver's own report at creation (the AMG hierarchy level by level) on stderr, and per width the
 device memory in use behind the first batch (device_mem_mb: everything the process holds, the solver included).
 Progress goes to stderr.
 
 Usage: python tools/bench_mrhs.py [--operators xn3b,tj7a,coef,lap2d] [--reps 5] [--n 3162] [--nrhs 2,4,8]
-                                  [--fixed-iters N] [--precond jacobi|amg] [--verbose]
+                                  [--fixed-iters N] [--precond jacobi|amg|fsai] [--fsai-power K] [--verbose]
 """
 import argparse
 import gzip
@@ -54,7 +57,8 @@ def main():
     ap.add_argument("--nrhs", default="2,4,8")
     ap.add_argument("--fixed-iters", type=int, default=0,
                     help="cut every solve at this many iterations (tol = 0): for a kernel trace, not for rates")
-    ap.add_argument("--precond", choices=("jacobi", "amg"), default="jacobi")
+    ap.add_argument("--precond", choices=("jacobi", "amg", "fsai"), default="jacobi")
+    ap.add_argument("--fsai-power", type=int, default=3)
     ap.add_argument("--verbose", action="store_true")
     a = ap.parse_args()
 
@@ -82,12 +86,14 @@ def main():
             kw = dict(kw, tol=0.0)
         if a.precond == "amg":
             kw = dict(kw, precond=la.PRECOND_AMG)
+        if a.precond == "fsai":
+            kw = dict(kw, precond=la.PRECOND_FSAI, fsai_power=a.fsai_power, fsai_blocks=1)
         if a.verbose:
             kw = dict(kw, verbose=1)
         s = la.Solver(M, la.default_opts(maxit=a.fixed_iters or 100000, **kw))
         n = s.n_local
         rec = {"operator": label, "rows": n, "nnz": int(s.nnz_local), "tol": kw["tol"], "setup_s": round(time.time() - t0, 2),
-               "padded_rows": int(s.padded), "precond": a.precond, "iteration_bytes_single": int(s.iteration_bytes), "reps": a.reps, "nrhs": {}}
+               "padded_rows": int(s.padded), "precond": a.precond + ("(%d)" % a.fsai_power if a.precond == "fsai" else ""), "iteration_bytes_single": int(s.iteration_bytes), "reps": a.reps, "nrhs": {}}
         for nrhs in [int(v) for v in a.nrhs.split(",")]:
             d_B = torch.arange(n, dtype=torch.float64, device="cuda:0")[None, :] * \
                 torch.arange(1, nrhs + 1, dtype=torch.float64, device="cuda:0")[:, None]
