@@ -881,6 +881,42 @@ int lsb_hip_solver_fsai_nnz(const lsb_hip_solver *s, unsigned long long *g, unsi
 int lsb_hip_solver_precond_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_R, size_t ldr,
                                      double *d_Z, size_t ldz);
 
+/* Block-CG proper (hip_bcg.hip, hip_bcg_drv.c): ONE Krylov space for a block of right-hand sides, where solve_multi
+ * runs nrhs independent recurrences.  Preconditioned BCGrQ from x0 = 0: the residual block is kept factored as
+ * R = W sigma with W^T D^-1 W = I (Cholesky-QR in the inner product of the solver's diagonal preconditioner D^-1), the
+ * search directions span the union of the columns' Krylov spaces, and the iteration count is the block's: every
+ * res[c].iters is the same number.  Blocks as for solve_multi[_dev]: column-major, ld >= n_local, the caller's
+ * numbering; res may be NULL.
+ * Returns 0: solved, or stopped with a status; 1: backend not initialised; 2: not served -- X untouched, nothing
+ * allocated; 3: the block is rank-deficient -- X untouched, res[c].status = LSB_STATUS_BREAKDOWN for every column.
+ * Served: what solve_multi serves under the diagonal preconditioners (LSB_PRECOND_JACOBI, _L1JACOBI, _NONE) with
+ * 2 <= nrhs <= 8; nrhs == 1 is lsb_hip_solver_solve_dev.  AMG, FSAI (with or without opts.fsai_blocks), Chebyshev,
+ * block-Jacobi, nvirt > 1, fp32 values, persistent solvers, nrhs > 8, nrhs == 0, null pointers and ld < n_local
+ * answer 2.  Widths 2 .. 8 run at 2, 4 or 8 columns, padded with zero columns.
+ * Stop rule: the recurrence's ||r_c|| <= tol ||b_c|| for EVERY column, or maxit; the columns are coupled, so none is
+ * frozen: all run until all meet the rule.  At maxit a column that meets its threshold is CONVERGED, the others are
+ * MAXIT.  relres = ||r_c|| / ||b_c|| of the recurrence; spmvs = SpMM launches that did work.
+ * Rank rule: at the start G = B^T D^-1 B is scaled to unit diagonal (a zero column counts as a zero pivot) and
+ * factored; a Cholesky pivot <= 1e-10 or not finite answers 3.  Inside the loop a pivot of P^T S P or of the
+ * residual block's Gram matrix that is <= 0 or not finite stops the block, every column LSB_STATUS_BREAKDOWN (0 is
+ * returned; X holds the iterate reached).
+ * opts.verify = 1: one SpMM recomputes ||b_c - S x_c|| / ||b_c|| into true_relres and relres after the stop; a
+ * column called converged that misses tol there becomes MAXIT.  There is no in-place restart in the block form.
+ * opts.use_graph and opts.check_every are honoured as by solve_multi; warm starts are not built. */
+int lsb_hip_solver_solve_block_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_B, size_t ldb,
+                                   double *d_X, size_t ldx, struct lsb_hip_result *res);
+int lsb_hip_solver_solve_block(lsb_hip_solver *s, unsigned nrhs, const double *B, size_t ldb,
+                               double *X, size_t ldx, struct lsb_hip_result *res);   /* host buffers */
+/* bytes one iteration of the block must move: 12 nnz + 4 (n + 1) + 8 n (12 Kp + 2 [the diagonal is a vector]) -- the
+ * CSR arrays once whatever the width and 12 vector passes per column: the SpMM 2 (P gathered, Q out), pass A 6 (W, Q,
+ * P, X in; W, X out), pass B 4 (W, P in; W, P out), the diagonal once in each of the two passes; 0 where the block
+ * form is not served */
+unsigned long long lsb_hip_solver_block_iteration_bytes(const lsb_hip_solver *s, unsigned nrhs);
+/* ||r_c||^2 of the recurrence and ||b_c||^2 out of the device state of the last block solved (nrhs <= 8 doubles each,
+ * either pointer may be NULL): what res[c].relres of a run without opts.verify was formed from.  2 where the solver has
+ * solved no block */
+int lsb_hip_solver_block_norms(const lsb_hip_solver *s, unsigned nrhs, double *rr, double *bb);
+
 unsigned lsb_hip_solver_nrows_local(const lsb_hip_solver *s);
 /* rows the solver added inside: 0, or the pad rows of a line-padded 2-D grid (lsb_csr_pad_lines;
  * a constant-coefficient grid of >= 1 M rows whose lines are not whole slices, LSBENCH_HIP_PAD_LINES=0

@@ -386,6 +386,47 @@ class Solver:
         solve_multi does not apply."""
         return int(L.load().lsb_hip_solver_multi_iteration_bytes(self._h, nrhs))
 
+    def solve_block_dev(self, d_B, d_X):
+        """Block-CG proper: x_c = S^-1 b_c for the 2 .. 8 columns held as the ROWS of two 2-D device tensors, searched
+        in ONE Krylov space; returns the list of their Results (the same iteration count in each).  A rank-deficient
+        block (rc 3) leaves d_X untouched and returns every status BREAKDOWN; a solver the block form does not serve
+        raises."""
+        pb, k, ldb = self._block(d_B, "solve_block_dev")
+        px, kx, ldx = self._block(d_X, "solve_block_dev")
+        if k != kx:
+            raise ValueError("solve_block_dev: B and X hold different numbers of columns")
+        res = (L.Result * max(k, 1))()
+        rc = L.load().lsb_hip_solver_solve_block_dev(self._h, k, pb, ldb, px, ldx, res)
+        if rc != 3:
+            L.check(rc, "solve_block_dev")
+        return list(res)[:k]
+
+    def solve_block(self, B):
+        """B: numpy (n_local, nrhs) of any order, 2 <= nrhs <= 8.  Returns (X of the same shape, [Result, ...]); a
+        rank-deficient block (rc 3) returns X unwritten and every status BREAKDOWN."""
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != self.n_local:
+            raise ValueError("solve_block: B must be (n_local, nrhs)")
+        k = B.shape[1]
+        X = np.empty((self.n_local, k), np.float64, order="F")
+        res = (L.Result * max(k, 1))()
+        ld = max(self.n_local, 1)
+        rc = L.load().lsb_hip_solver_solve_block(self._h, k, B.ctypes.data, ld, X.ctypes.data, ld, res)
+        if rc != 3:
+            L.check(rc, "solve_block")
+        return X, list(res)[:k]
+
+    def block_iteration_bytes(self, nrhs):
+        """Bytes one iteration of a block of nrhs right-hand sides must move (see lsbench_hip.h); 0 where the block
+        form is not served."""
+        return int(L.load().lsb_hip_solver_block_iteration_bytes(self._h, nrhs))
+
+    def block_norms(self, nrhs):
+        """(rr, bb): the recurrence's ||r_c||^2 and ||b_c||^2 out of the device state of the last block solved."""
+        rr, bb = (C.c_double * 8)(), (C.c_double * 8)()
+        L.check(L.load().lsb_hip_solver_block_norms(self._h, nrhs, rr, bb), "block_norms")
+        return np.array(rr[:nrhs]), np.array(bb[:nrhs])
+
     def spmv_inner_dev(self, d_x, d_y, d_dot=None):
         """y = the product the Krylov loop issues (fp32 matrix values under PREC_MIXED, where spmv_dev
         stays exact); d_dot (one shard only): the launch's fused x.y."""

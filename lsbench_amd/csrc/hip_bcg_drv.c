@@ -1,0 +1,213 @@
+/* Block-CG proper: host driver (kernels: hip_bcg.hip). */
+#define _GNU_SOURCE
+#include "hip_solver.h"
+
+/*
+ * lsb_hip_solver_solve_block[_dev]: ONE Krylov space for a block of 2 .. 8 right-hand sides -- preconditioned BCGrQ
+ * (the residual block kept factored as R = W sigma, W^T D^-1 W = I, by Cholesky-QR in the D^-1 inner product), x0 = 0,
+ * D^-1 the solver's diagonal preconditioner (Jacobi, l1-Jacobi or none).  Where solve_multi advances nrhs independent
+ * recurrences through shared launches, the columns here are coupled: the block searches the union of their Krylov
+ * spaces, all columns run until all meet the stop rule (||r_c|| <= tol ||b_c|| on the recurrence, every c), and every
+ * res[c] carries the block's iteration count.
+ *
+ * An iteration is five launches (hip_bcg.hip): the SpMM Q = S P with the records of P^T Q, k_bcg_small<GAMMA>,
+ * pass A (X, W~ and the records of two Gram matrices), k_bcg_small<G> (the norms, the stop test, the next factor),
+ * pass B (W, P).  The small launches have one workgroup and own the device state (lsb_blockcg_state); the device
+ * decides when to stop and the host side is run_loop (hip_run.c) exactly as for a batch of independent columns:
+ * check_every iterations per poll or the previous block's count in one go, a graph cache keyed on the count, internal
+ * buffers only (k_mrhs_pack / k_mrhs_unpack apply the permutation of a padded or re-ordered solver).
+ *
+ * The block must have full rank.  The start scales G = B^T D^-1 B to unit diagonal and factors it; a pivot <= 1e-10
+ * or not finite (a zero column among them) answers 3 with every status BREAKDOWN and X untouched -- the one host
+ * round trip before the loop.  Inside the loop a pivot of P^T S P or of W~^T D^-1 W~ that is <= 0 or not finite stops
+ * the block on the device, every column BREAKDOWN.
+ *
+ * opts.verify: one residual SpMM (k_spmm_csr<.., RES>, the verify round's of solve_multi) recomputes b - S x after the
+ * stop and fills true_relres / relres; a column called converged that misses tol on recomputation becomes MAXIT.  The
+ * in-place restart of solve_multi's verify rounds is not built for the block form.
+ *
+ * Served: what solve_multi serves under the diagonal preconditioners, 2 <= nrhs <= LSB_MRHS_MAX; one column is
+ * lsb_hip_solver_solve_dev.  Everything else answers 2 and allocates nothing.
+ */
+static int blockcg_serves(const lsb_hip_solver *sv) { return mrhs_serves_diag(sv); }
+
+static struct blockcg_work *blockcg_setup(lsb_hip_solver *sv, unsigned kp) {
+  struct blockcg_work *w = &sv->bk[kp == 2 ? 0 : kp == 4 ? 1 : 2];
+  if (w->kp)
+    return w;
+  const struct shard *s = &sv->sh[0];
+  if (!sv->bk_hst)
+    LSB_CHK_HIP(hipHostMalloc((void **)&sv->bk_hst, 2 * sizeof(struct lsb_blockcg_state), 0));
+  /* 256-byte aligned pieces of one allocation, the blocks first */
+  const unsigned tri = lsb_k_blockcg_tri(kp);
+  const size_t blk = (((size_t)s->n * kp * sizeof(double)) + 255) & ~(size_t)255;
+  const size_t rsp = (((size_t)LSB_MAX_PARTIALS * tri * sizeof(double)) + 255) & ~(size_t)255;
+  const size_t rpa = (((size_t)LSB_STREAM_GRID_CAP * 2 * tri * sizeof(double)) + 255) & ~(size_t)255;
+  const size_t stb = (sizeof(struct lsb_blockcg_state) + 255) & ~(size_t)255;
+  w->mem = (char *)lsb_hip_malloc(5 * blk + rsp + rpa + stb);
+  LSB_CHK_HIP(hipMemsetAsync(w->mem, 0, 5 * blk + rsp + rpa + stb, g_stream));
+  w->b = (double *)w->mem, w->x = (double *)(w->mem + blk), w->w = (double *)(w->mem + 2 * blk);
+  w->p = (double *)(w->mem + 3 * blk), w->q = (double *)(w->mem + 4 * blk);
+  w->rec_spmm = (double *)(w->mem + 5 * blk);
+  w->rec_pass = (double *)(w->mem + 5 * blk + rsp);
+  w->st = (struct lsb_blockcg_state *)(w->mem + 5 * blk + rsp + rpa);
+  w->kp = kp;
+  return w;
+}
+
+void blockcg_free(lsb_hip_solver *sv) {
+  for (int k = 0; k < 3; k++) {
+    graph_drop(&sv->bk[k].g);
+    lsb_hip_free(sv->bk[k].mem);
+    memset(&sv->bk[k], 0, sizeof sv->bk[k]);
+  }
+  if (sv->bk_hst)
+    LSB_CHK_HIP(hipHostFree(sv->bk_hst));
+  sv->bk_hst = NULL;
+}
+
+/* Bytes one iteration of a block of nrhs columns must move: 12 nnz + 4 (n + 1) + 8 n (12 kp + 2 [the diagonal is a
+ * vector]) -- the CSR arrays once whatever the width, and 12 vector passes per column: the SpMM 2 (P gathered, Q
+ * out), pass A 6 (W, Q, P, X in; W~, X out), pass B 4 (W~, P in; W, P out); the inverse diagonal once in each of
+ * the two passes.  0 where the block form is not served. */
+unsigned long long lsb_hip_solver_block_iteration_bytes(const lsb_hip_solver *sv, unsigned nrhs) {
+  if (!sv || nrhs == 0 || nrhs > LSB_MRHS_MAX || !blockcg_serves(sv))
+    return 0;
+  const struct shard *s = &sv->sh[0];
+  const unsigned kp = nrhs == 1 ? 1u : mrhs_batch_width(nrhs);
+  return 12ull * s->nnz + 4ull * (s->n + 1ull) + 8ull * s->n * (12ull * kp + (s->dinv_uniform ? 0u : 2u));
+}
+
+static void blockcg_enqueue_iter(lsb_hip_solver *sv, struct blockcg_work *w) {
+  const struct shard *s = &sv->sh[0];
+  unsigned nsp = 0, npa = 0;
+  lsb_k_blockcg_spmm(w->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, mrhs_spmm_lanes(sv), w->p, w->q, w->rec_spmm,
+                     &nsp, w->st, g_stream);
+  lsb_k_blockcg_small(w->kp, LSB_BLOCKCG_GAMMA, w->st, w->rec_spmm, nsp, 0, 0.0, 0, g_stream);
+  lsb_k_blockcg_pass_a(w->kp, s->n, w->w, w->q, w->p, w->x, DINV(s), w->st, w->rec_pass, &npa, g_stream);
+  lsb_k_blockcg_small(w->kp, LSB_BLOCKCG_G, w->st, w->rec_pass, npa, 0, 0.0, 0, g_stream);
+  lsb_k_blockcg_pass_b(w->kp, s->n, w->w, w->p, DINV(s), w->st, g_stream);
+}
+
+/* what run_loop enqueues: one linear chain on internal buffers, so its graphs are keyed on the count alone */
+struct blockcg_enq {
+  lsb_hip_solver *sv;
+  struct blockcg_work *w;
+};
+static void blockcg_enqueue_iters(void *ctx, int iters) {
+  const struct blockcg_enq *e = ctx;
+  for (int i = 0; i < iters; i++)
+    blockcg_enqueue_iter(e->sv, e->w);
+}
+static void blockcg_enqueue(void *ctx, int iters) {
+  const struct blockcg_enq *e = ctx;
+  if (e->sv->o.use_graph)
+    graph_launch(&e->w->g, iters, NULL, blockcg_enqueue_iters, ctx);
+  else
+    blockcg_enqueue_iters(ctx, iters);
+}
+
+static int blockcg_chunk(const lsb_hip_solver *sv, unsigned kp) {
+  if (sv->o.check_every > 0)
+    return sv->o.check_every;
+  return run_chunk((double)lsb_hip_solver_block_iteration_bytes(sv, kp), 10.0, 8, 256);
+}
+
+static int block_args_bad(const lsb_hip_solver *sv, unsigned nrhs, const void *a, size_t lda, const void *b,
+                          size_t ldb) {
+  return !sv || !a || !b || nrhs == 0 || nrhs > LSB_MRHS_MAX || lda < sv->n_user || ldb < sv->n_user;
+}
+
+int lsb_hip_solver_solve_block_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
+                                   size_t ldx, struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, d_B, ldb, d_X, ldx) || !blockcg_serves(sv))
+    return 2;
+  if (nrhs == 1)
+    return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
+  struct blockcg_work *w = blockcg_setup(sv, mrhs_batch_width(nrhs));
+  const struct shard *s = &sv->sh[0];
+  struct lsb_blockcg_state *hst = sv->bk_hst;
+  const unsigned kp = w->kp, n = s->n;
+  unsigned nrec = 0, nverify = 0;
+  int rc = 0;
+  const double t0 = wall_seconds();
+  lsb_k_mrhs_pack(n, kp, nrhs, sv->d_perm, d_B, ldb, w->b, g_stream);
+  lsb_k_blockcg_init(kp, n, w->b, DINV(s), w->rec_pass, &nrec, g_stream);
+  lsb_k_blockcg_small(kp, LSB_BLOCKCG_START, w->st, w->rec_pass, nrec, nrhs, sv->o.tol, (int)sv->o.maxit, g_stream);
+  /* the rank rule is looked at here, from one copy of the state, before anything of the caller's is written */
+  LSB_CHK_HIP(hipMemcpyAsync(&hst[0], w->st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream));
+  drain_stream(sv, "the start of the block");
+  if (hst[0].rank_bad)
+    rc = 3;
+  else {
+    lsb_k_blockcg_start(kp, n, w->b, DINV(s), w->w, w->p, w->x, w->st, g_stream);
+    struct blockcg_enq e = {sv, w};
+    const struct run_loop r = {.name = "a block of right-hand sides", .d_state = w->st, .h_state = hst,
+                               .state_bytes = sizeof(struct lsb_blockcg_state),
+                               .stop_off = offsetof(struct lsb_blockcg_state, running), .stop_is_running = 1,
+                               .progress_off = offsetof(struct lsb_blockcg_state, nspmm),
+                               .enqueue = blockcg_enqueue, .ctx = &e, .chunk = blockcg_chunk(sv, kp), .even = 0,
+                               .max_piece = sv->o.use_graph ? 512 : 0, .cap = -1,
+                               .what_hinted = "poll of a hinted block", .what_poll = "poll of the block",
+                               .what_drain = "drain after the block"};
+    run_loop(sv, &r, &w->hint);
+    if (sv->o.verify && sv->o.tol > 0.0) {
+      lsb_k_spmm_csr(kp, n, s->csr.offs, s->csr.cols, s->csr.vals, mrhs_spmm_lanes(sv), w->x, w->q, w->b, w->rec_spmm,
+                     &nrec, NULL, g_stream);
+      lsb_k_blockcg_small(kp, LSB_BLOCKCG_VERIFY, w->st, w->rec_spmm, nrec, 0, 0.0, 0, g_stream);
+      nverify = 1;
+      LSB_CHK_HIP(hipMemcpyAsync(&hst[0], w->st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream));
+    }
+    lsb_k_mrhs_unpack(n, kp, nrhs, sv->d_perm, w->x, d_X, ldx, g_stream);
+    drain_stream(sv, "un-packing the block");
+  }
+  const double seconds = wall_seconds() - t0;
+  for (unsigned c = 0; c < nrhs; c++) {
+    struct lsb_hip_result r;
+    memset(&r, 0, sizeof r);
+    r.iters = (unsigned)hst[0].iters;
+    r.status = hst[0].status[c];
+    r.relres = hst[0].bb[c] > 0.0 ? sqrt(hst[0].rr[c] / hst[0].bb[c]) : 0.0;
+    r.true_relres = hst[0].true_relres[c];
+    if (r.true_relres >= 0.0)
+      r.relres = r.true_relres;
+    r.seconds = seconds;
+    r.spmvs = (unsigned)hst[0].nspmm + nverify;
+    if (res)
+      res[c] = r;
+    g_last = r;
+  }
+  return rc;
+}
+
+int lsb_hip_solver_solve_block(lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X, size_t ldx,
+                               struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, B, ldb, X, ldx) || !blockcg_serves(sv))
+    return 2;
+  const size_t n = sv->n_user, bytes = n * sizeof(double);
+  double *d_B = (double *)lsb_hip_malloc(bytes * nrhs), *d_X = (double *)lsb_hip_malloc(bytes * nrhs);
+  LSB_CHK_HIP(hipMemcpy2D(d_B, bytes, B, ldb * sizeof(double), bytes, nrhs, hipMemcpyHostToDevice));
+  const int rc = lsb_hip_solver_solve_block_dev(sv, nrhs, d_B, n, d_X, n, res);
+  if (rc == 0)
+    LSB_CHK_HIP(hipMemcpy2D(X, ldx * sizeof(double), d_X, bytes, bytes, nrhs, hipMemcpyDeviceToHost));
+  lsb_hip_free(d_B), lsb_hip_free(d_X);
+  return rc;
+}
+
+/* ||r_c||^2 of the recurrence and ||b_c||^2 as the device state of the last block held them (nrhs <= 8 entries each,
+ * either may be NULL): what res[c].relres was formed from.  2 where no block has been solved. */
+int lsb_hip_solver_block_norms(const lsb_hip_solver *sv, unsigned nrhs, double *rr, double *bb) {
+  if (!sv || !sv->bk_hst || nrhs == 0 || nrhs > LSB_MRHS_MAX)
+    return 2;
+  for (unsigned c = 0; c < nrhs; c++) {
+    if (rr)
+      rr[c] = sv->bk_hst[0].rr[c];
+    if (bb)
+      bb[c] = sv->bk_hst[0].bb[c];
+  }
+  return 0;
+}

@@ -66,6 +66,25 @@ static int mrhs_zblock(const lsb_hip_solver *sv) { return mrhs_amg(sv) || mrhs_f
 
 static unsigned batch_width(unsigned nrhs) { return nrhs <= 2 ? 2u : nrhs <= 4 ? 4u : 8u; }
 
+static void mrhs_lanes_init(lsb_hip_solver *sv) {
+  /* lanes per row of the SpMM: the shard's (from its mean row length); LSBENCH_HIP_MRHS_LANES is the A/B switch */
+  const char *e = getenv("LSBENCH_HIP_MRHS_LANES");
+  sv->mr_lanes = e && atoi(e) > 0 ? (unsigned)atoi(e) : sv->sh[0].lanes;
+  /* ... of G and of G^T under FSAI: each matrix's own; LSBENCH_HIP_MRHS_FSAI_LANES is the A/B switch for both (the
+   * single-column kernels never see it) */
+  e = getenv("LSBENCH_HIP_MRHS_FSAI_LANES");
+  sv->mr_fs_lanes = e && atoi(e) > 0 ? (unsigned)atoi(e) : 0;
+}
+
+/* for the block-CG driver (hip_bcg_drv.c) */
+int mrhs_serves_diag(const lsb_hip_solver *sv) { return mrhs_serves(sv) && !mrhs_zblock(sv); }
+unsigned mrhs_batch_width(unsigned nrhs) { return batch_width(nrhs); }
+unsigned mrhs_spmm_lanes(lsb_hip_solver *sv) {
+  if (!sv->mr_hst) /* (mrhs_setup has not run: the same rule, nothing allocated) */
+    mrhs_lanes_init(sv);
+  return sv->mr_lanes;
+}
+
 static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
   struct mrhs_work *w = &sv->mr[kp == 2 ? 0 : kp == 4 ? 1 : 2];
   if (w->kp)
@@ -73,13 +92,7 @@ static struct mrhs_work *mrhs_setup(lsb_hip_solver *sv, unsigned kp) {
   const struct shard *s = &sv->sh[0];
   if (!sv->mr_hst) {
     LSB_CHK_HIP(hipHostMalloc((void **)&sv->mr_hst, 2 * sizeof(struct lsb_mrhs_state), 0));
-    /* lanes per row of the SpMM: the shard's (from its mean row length); LSBENCH_HIP_MRHS_LANES is the A/B switch */
-    const char *e = getenv("LSBENCH_HIP_MRHS_LANES");
-    sv->mr_lanes = e && atoi(e) > 0 ? (unsigned)atoi(e) : s->lanes;
-    /* ... of G and of G^T under FSAI: each matrix's own; LSBENCH_HIP_MRHS_FSAI_LANES is the A/B switch for both (the
-     * single-column kernels never see it) */
-    e = getenv("LSBENCH_HIP_MRHS_FSAI_LANES");
-    sv->mr_fs_lanes = e && atoi(e) > 0 ? (unsigned)atoi(e) : 0;
+    mrhs_lanes_init(sv);
   }
   /* 256-byte aligned pieces of one allocation, the blocks first: their placement relative to one another is
    * the same in every solver */

@@ -1,4 +1,5 @@
-// What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_amg.hip, hip_amg_cheb.hip) share: the 16-byte pair
+// What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_amg.hip, hip_amg_cheb.hip,
+// hip_bcg.hip) share: the 16-byte pair
 // of the interleaved blocks and its store gated per column, the fixed-order reductions of their per-column
 // records, the verify round's decision and the launchers' dispatch on the batch width.  Included by those files
 // only, after hip_kcommon.h.

@@ -15,6 +15,7 @@
  *   hip_bicgstab_drv.c  BiCGSTAB driver
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
  *   hip_mrhs_drv.c   several right-hand sides: multi-RHS Jacobi- and AMG-PCG on a CSR SpMM
+ *   hip_bcg_drv.c    block-CG proper: one Krylov space for a block of right-hand sides
  * Nothing here is part of the C-ABI (include/lsbench_hip.h).
  */
 #ifndef HIP_SOLVER_H
@@ -335,6 +336,17 @@ struct lsb_hip_solver {
   struct lsb_mrhs_state *mr_hst; /* pinned, 2 slots */
   unsigned mr_lanes;             /* lanes per row of its SpMM */
   unsigned mr_fs_lanes;          /* FSAI on blocks: lanes per row of G and of G^T, 0 = each matrix's own */
+  /* block-CG proper (allocated on first use, per width kp = 2, 4, 8; hip_bcg_drv.c) */
+  struct blockcg_work {
+    unsigned kp;               /* 0: not allocated */
+    char *mem;                 /* one allocation: the five interleaved blocks, the two record arrays, the state */
+    double *b, *x, *w, *p, *q; /* n kp doubles each */
+    double *rec_spmm, *rec_pass; /* records of the SpMM (LSB_MAX_PARTIALS) and of the passes (LSB_STREAM_GRID_CAP) */
+    struct lsb_blockcg_state *st;
+    unsigned hint;             /* SpMMs the previous block of this width took */
+    struct graph_cache g;      /* keyed on the count: the iteration touches these buffers only */
+  } bk[3];
+  struct lsb_blockcg_state *bk_hst; /* pinned, 2 slots; slot 0 keeps the last block's final state */
   hipEvent_t ev_poll[2], ev_vec, ev_halo;
   hipEvent_t ev[4 * MAX_SAMPLES], ev_t0, ev_t1; /* per sample: e0 SpMV e1 e2 e3 */
   unsigned char samp_skip[MAX_SAMPLES];         /* the sample brackets nothing (a run's first iteration in the
@@ -541,5 +553,12 @@ LSB_INTERNAL void lsb_k_rich_restart_state(struct lsb_pcg_state *st, const doubl
                                            void *stream);
 /* hip_mrhs_drv.c */
 LSB_INTERNAL void mrhs_free(lsb_hip_solver *sv); /* before the shards go */
+/* what the block-CG driver shares with it: solve_multi's service rule under the diagonal preconditioners, the width a
+ * block of nrhs <= 8 columns runs at, and the lanes per row of the SpMM (those of lsb_hip_solver_spmm_dev) */
+LSB_INTERNAL int mrhs_serves_diag(const lsb_hip_solver *sv);
+LSB_INTERNAL unsigned mrhs_batch_width(unsigned nrhs);
+LSB_INTERNAL unsigned mrhs_spmm_lanes(lsb_hip_solver *sv);
+/* hip_bcg_drv.c */
+LSB_INTERNAL void blockcg_free(lsb_hip_solver *sv); /* before the shards go */
 
 #endif

@@ -389,6 +389,54 @@ void lsb_k_mrhs_fsai_gt_dots(unsigned kp, unsigned n, const int *offs, const int
                              unsigned lanes, const double *t, const double *q, double *r, double *z, double *records,
                              unsigned *nrecords, const struct lsb_mrhs_state *st, int parity, void *stream);
 
+/* ---- block-CG proper (hip_bcg.hip; driver: hip_bcg_drv.c) ----------------------------------------------------
+ * One Krylov space for the kp = 2, 4 or 8 columns of an interleaved block (layout, pack / unpack: hip_mrhs.hip's).
+ * The device state is lsb_blockcg_state (lsb_bcg_state is BiCGSTAB's): the small matrices are row-major with stride
+ * LSB_MRHS_MAX whatever kp, the identity on the rows and columns >= nrhs.  Only the single-workgroup launches
+ * (lsb_k_blockcg_small) write it; the SpMM gates on `running`, the two passes return at once where it is 0. */
+struct lsb_blockcg_state {
+  double xi[LSB_MRHS_MAX * LSB_MRHS_MAX];    /* Gamma^-1, Gamma = P^T S P */
+  double xs[LSB_MRHS_MAX * LSB_MRHS_MAX];    /* xi sigma: X += P xs */
+  double zeta[LSB_MRHS_MAX * LSB_MRHS_MAX];  /* L^T of G = W~^T D^-1 W~ = L L^T (upper triangular) */
+  double zinv[LSB_MRHS_MAX * LSB_MRHS_MAX];  /* zeta^-1 (upper triangular); at the start: sigma^-1 */
+  double sigma[LSB_MRHS_MAX * LSB_MRHS_MAX]; /* R = W sigma (upper triangular) */
+  double rr[LSB_MRHS_MAX], bb[LSB_MRHS_MAX], thresh2[LSB_MRHS_MAX]; /* ||r_c||^2, ||b_c||^2, tol^2 ||b_c||^2 */
+  double true_relres[LSB_MRHS_MAX];          /* opts.verify: ||b_c - S x_c|| / ||b_c||, -1: none */
+  double tol;
+  double min_pivot;                          /* smallest pivot of the unit-diagonal Gram matrix of the start */
+  int status[LSB_MRHS_MAX];                  /* LSB_STATUS_*, per column; columns >= nrhs: CONVERGED */
+  int iters, maxit, nrhs;
+  int running;                               /* the SpMM's gate */
+  int nspmm;                                 /* SpMM launches that did work */
+  int rank_bad;                              /* the start found the block rank-deficient */
+};
+enum { LSB_BLOCKCG_START, LSB_BLOCKCG_GAMMA, LSB_BLOCKCG_G, LSB_BLOCKCG_VERIFY }; /* lsb_k_blockcg_small's phase */
+/* records a launch leaves, one per workgroup: the upper triangle row by row, kp (kp + 1) / 2 doubles */
+unsigned lsb_k_blockcg_tri(unsigned kp);
+/* records of (B^T D^-1 B, then b_c . b_c per column): tri + kp doubles each */
+void lsb_k_blockcg_init(unsigned kp, unsigned n, const double *b, const double *dinv, double dc, double *records,
+                        unsigned *nrecords, void *stream);
+/* one workgroup: re-reduces the records of the launch in front of it in a fixed order, does the kp x kp algebra of
+ * its phase and the stop / breakdown / maxit decision, writes the state.  START: records of lsb_k_blockcg_init (tol,
+ * maxit, nrhs are read in this phase only); GAMMA: of the SpMM; G: of pass A (G then H); VERIFY: of the residual
+ * SpMM (lsb_k_spmm_csr, kp doubles each) */
+void lsb_k_blockcg_small(unsigned kp, int phase, struct lsb_blockcg_state *st, const double *records,
+                         unsigned nrecords, unsigned nrhs, double tol, int maxit, void *stream);
+/* W = B sigma^-1, P = D^-1 W, X = 0 (not gated) */
+void lsb_k_blockcg_start(unsigned kp, unsigned n, const double *b, const double *dinv, double dc, double *w, double *p,
+                         double *x, const struct lsb_blockcg_state *st, void *stream);
+/* Q = S P with lsb_k_spmm_csr's row and rounding rule, and the records of the upper triangle of P^T Q */
+void lsb_k_blockcg_spmm(unsigned kp, unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
+                        const double *p, double *q, double *records, unsigned *nrecords,
+                        const struct lsb_blockcg_state *st, void *stream);
+/* X += P xs ; W~ = W - Q xi in place ; records of the upper triangles of W~^T D^-1 W~ and of W~^T W~ */
+void lsb_k_blockcg_pass_a(unsigned kp, unsigned n, double *w, const double *q, const double *p, double *x,
+                          const double *dinv, double dc, const struct lsb_blockcg_state *st, double *records,
+                          unsigned *nrecords, void *stream);
+/* W = W~ zeta^-1 ; P = D^-1 W + P zeta^T */
+void lsb_k_blockcg_pass_b(unsigned kp, unsigned n, double *w, double *p, const double *dinv, double dc,
+                          const struct lsb_blockcg_state *st, void *stream);
+
 /* ---- preconditioners with z as a vector (hip_precond_k.hip) -------------------- */
 void lsb_k_dot2(unsigned n, const double *r, const double *z, double *partials2,
                 unsigned *npartials, const struct lsb_pcg_state *st, void *stream);

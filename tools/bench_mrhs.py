@@ -20,10 +20,15 @@ paths are the default FSAI solver's: (a) nrhs single FSAI solves (the fused thre
 against (b) one batch (four launches an iteration) on that solver.
 --verbose: the solver's own report at creation (the AMG hierarchy level by level) on stderr, and per width the
 device memory in use behind the first batch (device_mem_mb: everything the process holds, the solver included).
+--block: block-CG proper beside the independent recurrences -- per width one solve_block_dev and one solve_multi_dev on
+the same solver and the same B (column 0 is b_i = i, the others standard normal draws of seed 7: a block must have full
+rank, which the columns (c + 1) i above have not), alternating, after the same two warm-up rounds.  Per width under
+"block": iterations of both forms (solve_multi: per column), seconds per solve (the median over the repetitions, and
+[min, max]), and bytes per iteration over the time per iteration of each form, in GB/s.  Jacobi only.
 Progress goes to stderr.
 
 Usage: python tools/bench_mrhs.py [--operators xn3b,tj7a,coef,lap2d] [--reps 5] [--n 3162] [--nrhs 2,4,8]
-                                  [--fixed-iters N] [--precond jacobi|amg|fsai] [--fsai-power K] [--verbose]
+                                  [--fixed-iters N] [--precond jacobi|amg|fsai] [--fsai-power K] [--verbose] [--block]
 """
 import argparse
 import gzip
@@ -49,6 +54,44 @@ def file_matrix(la, name, tmp):
     return la.lsbench_matrix_read(p)
 
 
+def block_leg(la, torch, s, n, nrhs, reps, key):
+    """solve_block_dev beside solve_multi_dev on one solver and one B"""
+    g = torch.Generator().manual_seed(7)
+    B = torch.randn(nrhs, n, dtype=torch.float64, generator=g)
+    B[0] = torch.arange(n, dtype=torch.float64)
+    d_B = B.to("cuda:0")
+    d_X = torch.zeros(nrhs, n, dtype=torch.float64, device="cuda:0")
+
+    def run(f):
+        t = time.perf_counter()
+        res = f(d_B, d_X)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t
+        assert all(r.status == la.STATUS_CONVERGED for r in res), [r.status for r in res]
+        return t, [int(r.iters) for r in res]
+
+    for _ in range(2):
+        run(s.solve_multi_dev), run(s.solve_block_dev)
+    tm, tb, itm, itb = [], [], None, None
+    for k in range(reps):
+        t, itm = run(s.solve_multi_dev)
+        tm.append(t)
+        t, itb = run(s.solve_block_dev)
+        tb.append(t)
+        print("%s nrhs %d rep %d: multi %.4f s, block %.4f s" % (key, nrhs, k, tm[-1], tb[-1]), file=sys.stderr,
+              flush=True)
+    tm, tb = np.array(tm), np.array(tb)
+    mb, bb = s.multi_iteration_bytes(nrhs), s.block_iteration_bytes(nrhs)
+    return {"iters_multi": itm, "iters_block": itb[0],
+            "s_per_solve_multi": round(float(np.median(tm)), 6), "s_per_solve_block": round(float(np.median(tb)), 6),
+            "s_minmax_multi": [round(float(tm.min()), 6), round(float(tm.max()), 6)],
+            "s_minmax_block": [round(float(tb.min()), 6), round(float(tb.max()), 6)],
+            "multi_iteration_bytes": int(mb), "block_iteration_bytes": int(bb),
+            "GBs_multi": round(mb * max(itm) / float(np.median(tm)) / 1e9, 1),
+            "GBs_block": round(bb * itb[0] / float(np.median(tb)) / 1e9, 1),
+            "block_over_multi_time": round(float(np.median(tb) / np.median(tm)), 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--operators", default="xn3b,tj7a,coef,lap2d")
@@ -60,6 +103,8 @@ def main():
     ap.add_argument("--precond", choices=("jacobi", "amg", "fsai"), default="jacobi")
     ap.add_argument("--fsai-power", type=int, default=3)
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--block", action="store_true", help="block-CG proper beside solve_multi (see above)")
+    ap.add_argument("--tol", type=float, default=0.0, help="override the operators' tolerances")
     a = ap.parse_args()
 
     import torch
@@ -82,6 +127,8 @@ def main():
         make, kw, label = ops[key]
         M = make()
         t0 = time.time()
+        if a.tol > 0.0:
+            kw = dict(kw, tol=a.tol)
         if a.fixed_iters:
             kw = dict(kw, tol=0.0)
         if a.precond == "amg":
@@ -94,7 +141,13 @@ def main():
         n = s.n_local
         rec = {"operator": label, "rows": n, "nnz": int(s.nnz_local), "tol": kw["tol"], "setup_s": round(time.time() - t0, 2),
                "padded_rows": int(s.padded), "precond": a.precond + ("(%d)" % a.fsai_power if a.precond == "fsai" else ""), "iteration_bytes_single": int(s.iteration_bytes), "reps": a.reps, "nrhs": {}}
+        if a.block:
+            assert a.precond == "jacobi" and not a.fixed_iters, "--block: Jacobi, to a tolerance"
+            rec["block"] = {}
         for nrhs in [int(v) for v in a.nrhs.split(",")]:
+            if a.block:
+                rec["block"][str(nrhs)] = block_leg(la, torch, s, n, nrhs, a.reps, key)
+                continue
             d_B = torch.arange(n, dtype=torch.float64, device="cuda:0")[None, :] * \
                 torch.arange(1, nrhs + 1, dtype=torch.float64, device="cuda:0")[:, None]
             d_X = torch.zeros(nrhs, n, dtype=torch.float64, device="cuda:0")
