@@ -917,6 +917,32 @@ unsigned long long lsb_hip_solver_block_iteration_bytes(const lsb_hip_solver *s,
  * solved no block */
 int lsb_hip_solver_block_norms(const lsb_hip_solver *s, unsigned nrhs, double *rr, double *bb);
 
+/* Block-CG under FSAI and AMG (hip_bcg_m.hip, the second half of hip_bcg_drv.c): the method of solve_block with D^-1
+ * replaced by the solver's preconditioner M^-1 where that is a symmetric operator, so W^T M^-1 W = I and the
+ * preconditioned block is a stored operand.  Signatures, return codes, stop rule, rank rule (on G = B^T M^-1 B),
+ * opts.verify, opts.use_graph, opts.check_every and lsb_hip_solver_block_norms: exactly solve_block[_dev]'s.
+ * Served: what solve_multi serves with z as a block of its own -- LSB_PRECOND_AMG in fp64 smoothed by l1-Jacobi or
+ * Chebyshev, LSB_PRECOND_FSAI with opts.fsai_blocks = 1 -- with 2 <= nrhs <= 8, one shard, x0 = 0.  A solver under a
+ * diagonal preconditioner is forwarded to solve_block[_dev] (the same bits); on a served solver nrhs == 1 is
+ * lsb_hip_solver_solve_dev.  Everything else answers 2, X untouched, nothing allocated: AMG smoothed by multicolour
+ * Gauss-Seidel or cycling in fp32, FSAI without opts.fsai_blocks, Chebyshev, block-Jacobi, nvirt > 1, fp32 values,
+ * BiCGSTAB / GMRES / Richardson, nrhs == 0 or > 8, null pointers, ld < n_local.  solve_block[_dev] itself keeps
+ * answering 2 on AMG and FSAI solvers.
+ * An iteration under FSAI is 7 launches (SpMM, the small algebra, X and W~, the product with G, the product with G^T
+ * carrying the Gram sums, the small algebra, W and P); under AMG 6 launches and the V-cycle.  The preconditioner's
+ * launches inside the loop are not gated on the block's stop word: after the stop they run on for the rest of a
+ * polling chunk (opts.check_every; by default at least 2 iterations under AMG) into buffers nobody reads. */
+int lsb_hip_solver_solve_block_precond_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_B, size_t ldb,
+                                           double *d_X, size_t ldx, struct lsb_hip_result *res);
+int lsb_hip_solver_solve_block_precond(lsb_hip_solver *s, unsigned nrhs, const double *B, size_t ldb,
+                                       double *X, size_t ldx, struct lsb_hip_result *res);   /* host buffers */
+/* bytes one iteration of solve_block_precond must move under FSAI: 12 (nnz + nnz_G + nnz_Gt) + 12 (n + 1) +
+ * 8 n 18 Kp -- S, G and G^T once each whatever the width and 18 vector passes per column: the SpMM 2, X and W~ 6, the
+ * product with G 2, the product with G^T and the Gram sums 3, W and P 5.  Under AMG 0, as
+ * lsb_hip_solver_multi_iteration_bytes (a V-cycle has another shape); under a diagonal preconditioner
+ * lsb_hip_solver_block_iteration_bytes; 0 where nothing is served */
+unsigned long long lsb_hip_solver_block_precond_iteration_bytes(const lsb_hip_solver *s, unsigned nrhs);
+
 unsigned lsb_hip_solver_nrows_local(const lsb_hip_solver *s);
 /* rows the solver added inside: 0, or the pad rows of a line-padded 2-D grid (lsb_csr_pad_lines;
  * a constant-coefficient grid of >= 1 M rows whose lines are not whole slices, LSBENCH_HIP_PAD_LINES=0

@@ -283,6 +283,9 @@ SIGNATURES = {
     "lsb_hip_solver_solve_block": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_block_iteration_bytes": (C.c_ulonglong, [_vp, _u]),
     "lsb_hip_solver_block_norms": (_i, [_vp, _u, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lsb_hip_solver_solve_block_precond_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
+    "lsb_hip_solver_solve_block_precond": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
+    "lsb_hip_solver_block_precond_iteration_bytes": (C.c_ulonglong, [_vp, _u]),
     "lsb_hip_solver_precond_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
     "lsb_hip_solver_fsai_nnz": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "lsb_hip_solver_precond_dev": (_i, [_vp, _vp, _vp]),

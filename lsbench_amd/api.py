@@ -386,24 +386,27 @@ class Solver:
         solve_multi does not apply."""
         return int(L.load().lsb_hip_solver_multi_iteration_bytes(self._h, nrhs))
 
-    def solve_block_dev(self, d_B, d_X):
+    def solve_block_dev(self, d_B, d_X, precond=False):
         """Block-CG proper: x_c = S^-1 b_c for the 2 .. 8 columns held as the ROWS of two 2-D device tensors, searched
         in ONE Krylov space; returns the list of their Results (the same iteration count in each).  A rank-deficient
         block (rc 3) leaves d_X untouched and returns every status BREAKDOWN; a solver the block form does not serve
-        raises."""
+        raises.  precond: lsb_hip_solver_solve_block_precond_dev, which also serves AMG and FSAI (fsai_blocks)
+        solvers and forwards a diagonal one here."""
         pb, k, ldb = self._block(d_B, "solve_block_dev")
         px, kx, ldx = self._block(d_X, "solve_block_dev")
         if k != kx:
             raise ValueError("solve_block_dev: B and X hold different numbers of columns")
         res = (L.Result * max(k, 1))()
-        rc = L.load().lsb_hip_solver_solve_block_dev(self._h, k, pb, ldb, px, ldx, res)
+        lib = L.load()
+        fn = lib.lsb_hip_solver_solve_block_precond_dev if precond else lib.lsb_hip_solver_solve_block_dev
+        rc = fn(self._h, k, pb, ldb, px, ldx, res)
         if rc != 3:
             L.check(rc, "solve_block_dev")
         return list(res)[:k]
 
-    def solve_block(self, B):
+    def solve_block(self, B, precond=False):
         """B: numpy (n_local, nrhs) of any order, 2 <= nrhs <= 8.  Returns (X of the same shape, [Result, ...]); a
-        rank-deficient block (rc 3) returns X unwritten and every status BREAKDOWN."""
+        rank-deficient block (rc 3) returns X unwritten and every status BREAKDOWN.  precond: as solve_block_dev's."""
         B = np.asfortranarray(B, dtype=np.float64)
         if B.ndim != 2 or B.shape[0] != self.n_local:
             raise ValueError("solve_block: B must be (n_local, nrhs)")
@@ -411,7 +414,9 @@ class Solver:
         X = np.empty((self.n_local, k), np.float64, order="F")
         res = (L.Result * max(k, 1))()
         ld = max(self.n_local, 1)
-        rc = L.load().lsb_hip_solver_solve_block(self._h, k, B.ctypes.data, ld, X.ctypes.data, ld, res)
+        lib = L.load()
+        fn = lib.lsb_hip_solver_solve_block_precond if precond else lib.lsb_hip_solver_solve_block
+        rc = fn(self._h, k, B.ctypes.data, ld, X.ctypes.data, ld, res)
         if rc != 3:
             L.check(rc, "solve_block")
         return X, list(res)[:k]
@@ -420,6 +425,11 @@ class Solver:
         """Bytes one iteration of a block of nrhs right-hand sides must move (see lsbench_hip.h); 0 where the block
         form is not served."""
         return int(L.load().lsb_hip_solver_block_iteration_bytes(self._h, nrhs))
+
+    def block_precond_iteration_bytes(self, nrhs):
+        """Bytes one iteration of solve_block(precond=True) must move (see lsbench_hip.h); 0 under AMG and where
+        nothing is served."""
+        return int(L.load().lsb_hip_solver_block_precond_iteration_bytes(self._h, nrhs))
 
     def block_norms(self, nrhs):
         """(rr, bb): the recurrence's ||r_c||^2 and ||b_c||^2 out of the device state of the last block solved."""

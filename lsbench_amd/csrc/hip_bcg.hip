@@ -29,60 +29,7 @@
 
 #define BS LSB_MRHS_MAX // stride of the small matrices in the state and in LDS
 #define WGS 1024        // threads of k_bcg_small: its record sums are a few hundred loads a thread otherwise
-#define BCG_PASS_GRID 512 // workgroups of a streaming pass at the most (its consumer has ONE workgroup to sum them)
-
-static_assert(BCG_PASS_GRID <= LSB_STREAM_GRID_CAP, "the driver sizes the passes' records by LSB_STREAM_GRID_CAP");
-
-// (i, j), i <= j, in the upper triangle stored row by row
-__host__ __device__ constexpr int tri_at(int KP, int i, int j) { return i * KP - i * (i - 1) / 2 + (j - i); }
-__host__ __device__ constexpr int tri_of(int KP) { return KP * (KP + 1) / 2; }
-
-// a row's KP doubles <-> KP / 2 16-byte accesses
-template <int KP> __device__ __forceinline__ void row_load(const double *__restrict__ v, size_t i, double (&o)[KP]) {
-  const d2v *v2 = (const d2v *)v + i * (KP / 2);
-#pragma unroll
-  for (int h = 0; h < KP / 2; h++) {
-    const d2v t = v2[h];
-    o[2 * h] = t.x, o[2 * h + 1] = t.y;
-  }
-}
-template <int KP> __device__ __forceinline__ void row_store(double *__restrict__ v, size_t i, const double (&o)[KP]) {
-  d2v *v2 = (d2v *)v + i * (KP / 2);
-#pragma unroll
-  for (int h = 0; h < KP / 2; h++)
-    v2[h] = d2v{o[2 * h], o[2 * h + 1]};
-}
-
-// the workgroup's sums of W per-lane values -> dst[W]: wavefront butterfly, the four waves through LDS in fixed order
-template <int W> __device__ __forceinline__ void wg_sum_store(double (&v)[W], double *sred /* 4 W */, double *dst) {
-#pragma unroll
-  for (int k = 0; k < W; k++) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-      v[k] += __shfl_xor(v[k], off, 64);
-  }
-  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < W; k++)
-      sred[wave * W + k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < W)
-    dst[threadIdx.x] = (sred[threadIdx.x] + sred[W + threadIdx.x]) + (sred[2 * W + threadIdx.x] + sred[3 * W + threadIdx.x]);
-}
-
-// rows of a streaming pass: one row per lane and trip
-static unsigned pass_grid(unsigned n) {
-  unsigned g = div_up(n ? n : 1, WG);
-  if (g > 256) {
-    g = div_up(n, WG * 4);
-    if (g < 256)
-      g = 256;
-  }
-  return g > BCG_PASS_GRID ? BCG_PASS_GRID : g;
-}
+// (tri_at, tri_of, row_load, row_store, wg_sum_store, pass_grid: hip_mrhs_k.h, shared with hip_bcg_m.hip)
 
 // --------------------------------------------------------------------------
 // Q = S P: k_spmm_csr<L, KP, false>'s row rule and rounding rule (hip_mrhs.hip) -- a lane's sum for column c is the

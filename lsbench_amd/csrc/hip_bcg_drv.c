@@ -1,4 +1,4 @@
-/* Block-CG proper: host driver (kernels: hip_bcg.hip). */
+/* Block-CG proper: host driver (kernels: hip_bcg.hip, and hip_bcg_m.hip for the preconditioned half below). */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
@@ -31,6 +31,15 @@
  */
 static int blockcg_serves(const lsb_hip_solver *sv) { return mrhs_serves_diag(sv); }
 
+/* How a block's z = M^-1 (.) is formed: by the diagonal inside the passes (solve_block), or as a block of its own by
+ * FSAI's two products or by the V-cycle (solve_block_precond, the second half of this file). */
+enum blockcg_form { BK_DIAG, BK_FSAI, BK_AMG };
+/* (the second half's, which the shared solve below calls) */
+static void blockcg_m_setup(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form);
+static void blockcg_m_zapply(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form, const double *r);
+static void blockcg_m_enqueue_iter(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form);
+static int blockcg_m_chunk(const lsb_hip_solver *sv, unsigned kp, enum blockcg_form form);
+
 static struct blockcg_work *blockcg_setup(lsb_hip_solver *sv, unsigned kp) {
   struct blockcg_work *w = &sv->bk[kp == 2 ? 0 : kp == 4 ? 1 : 2];
   if (w->kp)
@@ -58,7 +67,8 @@ static struct blockcg_work *blockcg_setup(lsb_hip_solver *sv, unsigned kp) {
 void blockcg_free(lsb_hip_solver *sv) {
   for (int k = 0; k < 3; k++) {
     graph_drop(&sv->bk[k].g);
-    lsb_hip_free(sv->bk[k].mem);
+    lsb_hip_free(sv->bk[k].mem), lsb_hip_free(sv->bk[k].pmem), lsb_hip_free(sv->bk[k].amg_mem);
+    free(sv->bk[k].av);
     memset(&sv->bk[k], 0, sizeof sv->bk[k]);
   }
   if (sv->bk_hst)
@@ -89,15 +99,21 @@ static void blockcg_enqueue_iter(lsb_hip_solver *sv, struct blockcg_work *w) {
   lsb_k_blockcg_pass_b(w->kp, s->n, w->w, w->p, DINV(s), w->st, g_stream);
 }
 
-/* what run_loop enqueues: one linear chain on internal buffers, so its graphs are keyed on the count alone */
+/* what run_loop enqueues: one linear chain on internal buffers, so its graphs are keyed on the count alone (a solver
+ * has one form: its preconditioner's) */
 struct blockcg_enq {
   lsb_hip_solver *sv;
   struct blockcg_work *w;
+  enum blockcg_form form;
 };
 static void blockcg_enqueue_iters(void *ctx, int iters) {
   const struct blockcg_enq *e = ctx;
-  for (int i = 0; i < iters; i++)
-    blockcg_enqueue_iter(e->sv, e->w);
+  for (int i = 0; i < iters; i++) {
+    if (e->form == BK_DIAG)
+      blockcg_enqueue_iter(e->sv, e->w);
+    else
+      blockcg_m_enqueue_iter(e->sv, e->w, e->form);
+  }
 }
 static void blockcg_enqueue(void *ctx, int iters) {
   const struct blockcg_enq *e = ctx;
@@ -118,15 +134,12 @@ static int block_args_bad(const lsb_hip_solver *sv, unsigned nrhs, const void *a
   return !sv || !a || !b || nrhs == 0 || nrhs > LSB_MRHS_MAX || lda < sv->n_user || ldb < sv->n_user;
 }
 
-int lsb_hip_solver_solve_block_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
-                                   size_t ldx, struct lsb_hip_result *res) {
-  if (!lsb_initialized)
-    return 1;
-  if (block_args_bad(sv, nrhs, d_B, ldb, d_X, ldx) || !blockcg_serves(sv))
-    return 2;
-  if (nrhs == 1)
-    return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
+/* one block of 2 .. 8 columns in the given form; the caller has checked the arguments and the service rule */
+static int blockcg_solve(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X, size_t ldx,
+                         struct lsb_hip_result *res, enum blockcg_form form) {
   struct blockcg_work *w = blockcg_setup(sv, mrhs_batch_width(nrhs));
+  if (form != BK_DIAG)
+    blockcg_m_setup(sv, w, form);
   const struct shard *s = &sv->sh[0];
   struct lsb_blockcg_state *hst = sv->bk_hst;
   const unsigned kp = w->kp, n = s->n;
@@ -134,7 +147,12 @@ int lsb_hip_solver_solve_block_dev(lsb_hip_solver *sv, unsigned nrhs, const doub
   int rc = 0;
   const double t0 = wall_seconds();
   lsb_k_mrhs_pack(n, kp, nrhs, sv->d_perm, d_B, ldb, w->b, g_stream);
-  lsb_k_blockcg_init(kp, n, w->b, DINV(s), w->rec_pass, &nrec, g_stream);
+  if (form == BK_DIAG)
+    lsb_k_blockcg_init(kp, n, w->b, DINV(s), w->rec_pass, &nrec, g_stream);
+  else { /* Z = M^-1 B, then the records of (B^T Z, b_c . b_c) */
+    blockcg_m_zapply(sv, w, form, w->b);
+    lsb_k_blockcg_m_gram(kp, 1, n, w->b, w->z, w->rec_pass, &nrec, w->st, g_stream);
+  }
   lsb_k_blockcg_small(kp, LSB_BLOCKCG_START, w->st, w->rec_pass, nrec, nrhs, sv->o.tol, (int)sv->o.maxit, g_stream);
   /* the rank rule is looked at here, from one copy of the state, before anything of the caller's is written */
   LSB_CHK_HIP(hipMemcpyAsync(&hst[0], w->st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream));
@@ -142,14 +160,18 @@ int lsb_hip_solver_solve_block_dev(lsb_hip_solver *sv, unsigned nrhs, const doub
   if (hst[0].rank_bad)
     rc = 3;
   else {
-    lsb_k_blockcg_start(kp, n, w->b, DINV(s), w->w, w->p, w->x, w->st, g_stream);
-    struct blockcg_enq e = {sv, w};
+    if (form == BK_DIAG)
+      lsb_k_blockcg_start(kp, n, w->b, DINV(s), w->w, w->p, w->x, w->st, g_stream);
+    else
+      lsb_k_blockcg_m_start(kp, n, w->b, w->z, w->w, w->p, w->x, w->st, g_stream);
+    struct blockcg_enq e = {sv, w, form};
     const struct run_loop r = {.name = "a block of right-hand sides", .d_state = w->st, .h_state = hst,
                                .state_bytes = sizeof(struct lsb_blockcg_state),
                                .stop_off = offsetof(struct lsb_blockcg_state, running), .stop_is_running = 1,
                                .progress_off = offsetof(struct lsb_blockcg_state, nspmm),
-                               .enqueue = blockcg_enqueue, .ctx = &e, .chunk = blockcg_chunk(sv, kp), .even = 0,
-                               .max_piece = sv->o.use_graph ? 512 : 0, .cap = -1,
+                               .enqueue = blockcg_enqueue, .ctx = &e,
+                               .chunk = form == BK_DIAG ? blockcg_chunk(sv, kp) : blockcg_m_chunk(sv, kp, form),
+                               .even = 0, .max_piece = sv->o.use_graph ? 512 : 0, .cap = -1,
                                .what_hinted = "poll of a hinted block", .what_poll = "poll of the block",
                                .what_drain = "drain after the block"};
     run_loop(sv, &r, &w->hint);
@@ -182,20 +204,38 @@ int lsb_hip_solver_solve_block_dev(lsb_hip_solver *sv, unsigned nrhs, const doub
   return rc;
 }
 
+int lsb_hip_solver_solve_block_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
+                                   size_t ldx, struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, d_B, ldb, d_X, ldx) || !blockcg_serves(sv))
+    return 2;
+  if (nrhs == 1)
+    return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
+  return blockcg_solve(sv, nrhs, d_B, ldb, d_X, ldx, res, BK_DIAG);
+}
+
+/* the host-buffer form of either entry point: the caller has checked the arguments and the service rule */
+typedef int blockcg_dev_fn(lsb_hip_solver *, unsigned, const double *, size_t, double *, size_t, struct lsb_hip_result *);
+static int blockcg_host(blockcg_dev_fn *dev, lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X,
+                        size_t ldx, struct lsb_hip_result *res) {
+  const size_t n = sv->n_user, bytes = n * sizeof(double);
+  double *d_B = (double *)lsb_hip_malloc(bytes * nrhs), *d_X = (double *)lsb_hip_malloc(bytes * nrhs);
+  LSB_CHK_HIP(hipMemcpy2D(d_B, bytes, B, ldb * sizeof(double), bytes, nrhs, hipMemcpyHostToDevice));
+  const int rc = dev(sv, nrhs, d_B, n, d_X, n, res);
+  if (rc == 0)
+    LSB_CHK_HIP(hipMemcpy2D(X, ldx * sizeof(double), d_X, bytes, bytes, nrhs, hipMemcpyDeviceToHost));
+  lsb_hip_free(d_B), lsb_hip_free(d_X);
+  return rc;
+}
+
 int lsb_hip_solver_solve_block(lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X, size_t ldx,
                                struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
   if (block_args_bad(sv, nrhs, B, ldb, X, ldx) || !blockcg_serves(sv))
     return 2;
-  const size_t n = sv->n_user, bytes = n * sizeof(double);
-  double *d_B = (double *)lsb_hip_malloc(bytes * nrhs), *d_X = (double *)lsb_hip_malloc(bytes * nrhs);
-  LSB_CHK_HIP(hipMemcpy2D(d_B, bytes, B, ldb * sizeof(double), bytes, nrhs, hipMemcpyHostToDevice));
-  const int rc = lsb_hip_solver_solve_block_dev(sv, nrhs, d_B, n, d_X, n, res);
-  if (rc == 0)
-    LSB_CHK_HIP(hipMemcpy2D(X, ldx * sizeof(double), d_X, bytes, bytes, nrhs, hipMemcpyDeviceToHost));
-  lsb_hip_free(d_B), lsb_hip_free(d_X);
-  return rc;
+  return blockcg_host(lsb_hip_solver_solve_block_dev, sv, nrhs, B, ldb, X, ldx, res);
 }
 
 /* ||r_c||^2 of the recurrence and ||b_c||^2 as the device state of the last block held them (nrhs <= 8 entries each,
@@ -210,4 +250,154 @@ int lsb_hip_solver_block_norms(const lsb_hip_solver *sv, unsigned nrhs, double *
       bb[c] = sv->bk_hst[0].bb[c];
   }
   return 0;
+}
+
+/*
+ * ---- Block-CG under FSAI and AMG -------------------------------------------------------------------------------
+ * lsb_hip_solver_solve_block_precond[_dev]: the method above with D^-1 replaced by the solver's M^-1 where that is a
+ * symmetric operator -- FSAI's G^T G, or the V-cycle smoothed by l1-Jacobi or Chebyshev -- so the preconditioned block
+ * is a stored operand Z (kernels: hip_bcg_m.hip; the SpMM, k_bcg_small, the state, run_loop, the graph cache, the
+ * hint, pack / unpack, the rank rule, opts.verify and lsb_hip_solver_block_norms are the first half's, unchanged):
+ *
+ *   start: Z = M^-1 B (un-gated: two SpMMs off G and G^T, or one cycle) ; k_bcgm_gram<START> ; k_bcg_small<START> ;
+ *          the one host round trip of the rank rule ; k_bcgm_start
+ *   FSAI, 7 launches:  k_bcg_spmm, small<GAMMA>, k_bcgm_pass_a, T = G W~ (k_spmm_csr), k_bcgm_gt_gram (Z~ = G^T T with
+ *                      the Gram sums riding in it), small<G>, k_bcgm_pass_b
+ *   AMG, 6 + a cycle:  k_bcg_spmm, small<GAMMA>, k_bcgm_pass_a, amg_cycle(r = W~, z = Z~), k_bcgm_gram, small<G>,
+ *                      k_bcgm_pass_b
+ *
+ * The gate.  The cycle's launches and lsb_k_spmm_csr gate on a lsb_mrhs_state, which a block does not have, so inside
+ * the loop they run UN-GATED (st = NULL): once the block has stopped they churn the stale W~ for the rest of the chunk
+ * into T and Z~, which nobody reads -- pass A, the Gram launches, k_bcg_small and pass B are gated on st->running and
+ * X is not touched again.  The waste is bounded by the chunk: under AMG blockcg_m_chunk takes the floor of 2 that
+ * solve_multi's chunk takes there, so at most one cycle is wasted on an un-hinted first solve; a hinted solve enqueues
+ * the previous count.
+ *
+ * Served: what solve_multi serves with a z block (mrhs_serves_zblock): AMG in fp64 smoothed by l1-Jacobi or Chebyshev,
+ * FSAI with opts.fsai_blocks; 2 <= nrhs <= LSB_MRHS_MAX, one shard, x0 = 0.  A solver under a diagonal preconditioner
+ * is forwarded to solve_block_dev (the same bits); one column is lsb_hip_solver_solve_dev.  Everything else answers 2
+ * and allocates nothing.
+ */
+static enum blockcg_form blockcg_m_form(const lsb_hip_solver *sv) {
+  return sv->o.precond == LSB_PRECOND_FSAI ? BK_FSAI : BK_AMG;
+}
+
+/* the work area grows by z -- plus t = G w and the records of k_bcgm_gt_gram's grid under FSAI; under AMG z is the
+ * head of the cycle's block vectors, as in mrhs_setup, and the Gram launch is a streaming pass (rec_pass) */
+static void blockcg_m_setup(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form) {
+  if (w->z)
+    return;
+  const struct shard *s = &sv->sh[0];
+  if (form == BK_FSAI) {
+    const size_t blk = (((size_t)s->n * w->kp * sizeof(double)) + 255) & ~(size_t)255;
+    const size_t rec = (size_t)LSB_MAX_PARTIALS * 2 * lsb_k_blockcg_tri(w->kp) * sizeof(double);
+    w->pmem = (char *)lsb_hip_malloc(2 * blk + rec);
+    LSB_CHK_HIP(hipMemsetAsync(w->pmem, 0, 2 * blk + rec, g_stream));
+    w->z = (double *)w->pmem, w->t = (double *)(w->pmem + blk), w->rec_gram = (double *)(w->pmem + 2 * blk);
+  } else {
+    w->av = lsb_calloc(struct amg_vecs, s->amg->nlev);
+    w->amg_mem = amg_block_vecs(s->amg, w->kp, w->av);
+    w->z = (double *)w->amg_mem;
+  }
+}
+
+/* T = G R by the SpMM's rule, un-gated; its records of r_c . t_c, which nobody reads, go where the next k_bcg_spmm or
+ * the verify round writes anew */
+static void blockcg_m_g(lsb_hip_solver *sv, struct blockcg_work *w, const double *r) {
+  const struct shard *s = &sv->sh[0];
+  unsigned np = 0;
+  lsb_k_spmm_csr(w->kp, s->n, s->fs_g.offs, s->fs_g.cols, s->fs_g.vals, mrhs_fsai_lanes(sv, 0), r, w->t, NULL,
+                 w->rec_spmm, &np, NULL, g_stream);
+}
+
+static void blockcg_m_cycle(lsb_hip_solver *sv, struct blockcg_work *w, const double *r) {
+  const struct amg_run c = {.a = sv->sh[0].amg, .vec = w->av, .kp = w->kp, .r = r, .z = w->z,
+                            .records = NULL, .nrecords = NULL, .mst = NULL};
+  amg_cycle(&c);
+}
+
+/* Z = M^-1 R, un-gated, no Gram sums: the start's */
+static void blockcg_m_zapply(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form, const double *r) {
+  if (form == BK_AMG) {
+    blockcg_m_cycle(sv, w, r);
+    return;
+  }
+  const struct shard *s = &sv->sh[0];
+  unsigned np = 0;
+  blockcg_m_g(sv, w, r);
+  lsb_k_spmm_csr(w->kp, s->n, s->fs_gt.offs, s->fs_gt.cols, s->fs_gt.vals, mrhs_fsai_lanes(sv, 1), w->t, w->z, NULL,
+                 w->rec_spmm, &np, NULL, g_stream);
+}
+
+static void blockcg_m_enqueue_iter(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form) {
+  const struct shard *s = &sv->sh[0];
+  unsigned nsp = 0, ngr = 0;
+  double *rec = form == BK_FSAI ? w->rec_gram : w->rec_pass;
+  lsb_k_blockcg_spmm(w->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, mrhs_spmm_lanes(sv), w->p, w->q, w->rec_spmm,
+                     &nsp, w->st, g_stream);
+  lsb_k_blockcg_small(w->kp, LSB_BLOCKCG_GAMMA, w->st, w->rec_spmm, nsp, 0, 0.0, 0, g_stream);
+  lsb_k_blockcg_m_pass_a(w->kp, s->n, w->w, w->q, w->p, w->x, w->st, g_stream);
+  if (form == BK_FSAI) {
+    blockcg_m_g(sv, w, w->w);
+    lsb_k_blockcg_m_gt_gram(w->kp, s->n, s->fs_gt.offs, s->fs_gt.cols, s->fs_gt.vals, mrhs_fsai_lanes(sv, 1), w->t,
+                            w->w, w->z, rec, &ngr, w->st, g_stream);
+  } else {
+    blockcg_m_cycle(sv, w, w->w);
+    lsb_k_blockcg_m_gram(w->kp, 0, s->n, w->w, w->z, rec, &ngr, w->st, g_stream);
+  }
+  lsb_k_blockcg_small(w->kp, LSB_BLOCKCG_G, w->st, rec, ngr, 0, 0.0, 0, g_stream);
+  lsb_k_blockcg_m_pass_b(w->kp, s->n, w->w, w->z, w->p, w->st, g_stream);
+}
+
+/* Bytes one iteration of a block of nrhs columns must move under FSAI: S, G and G^T once each whatever the width
+ * (12 B per non-zero and the three row-offset arrays), and 18 vector passes per column -- the SpMM 2 (P gathered, Q
+ * out), pass A 6 (W, Q, P, X in; W~, X out), the product with G 2 (W~ gathered, T out), k_bcgm_gt_gram 3 (T gathered,
+ * W~ in, Z~ out), pass B 5 (W~, Z~, P in; W, P out).  Under AMG 0, as lsb_hip_solver_multi_iteration_bytes (a V-cycle
+ * has another shape); a diagonal preconditioner: lsb_hip_solver_block_iteration_bytes; 0 where nothing is served. */
+unsigned long long lsb_hip_solver_block_precond_iteration_bytes(const lsb_hip_solver *sv, unsigned nrhs) {
+  if (!sv || nrhs == 0 || nrhs > LSB_MRHS_MAX)
+    return 0;
+  if (blockcg_serves(sv))
+    return lsb_hip_solver_block_iteration_bytes(sv, nrhs);
+  if (!mrhs_serves_zblock(sv) || blockcg_m_form(sv) != BK_FSAI)
+    return 0;
+  const struct shard *s = &sv->sh[0];
+  const unsigned kp = nrhs == 1 ? 1u : mrhs_batch_width(nrhs);
+  return 12ull * (s->nnz + s->fs_g.nnz + s->fs_gt.nnz) + 12ull * (s->n + 1ull) + 8ull * s->n * 18ull * kp;
+}
+
+/* iterations per host poll: blockcg_chunk's rule on this form's bytes; under AMG on solve_multi's estimate of the SpMM,
+ * the passes and the cycle, with its floor of 2 (see "The gate" above) */
+static int blockcg_m_chunk(const lsb_hip_solver *sv, unsigned kp, enum blockcg_form form) {
+  if (sv->o.check_every > 0)
+    return sv->o.check_every;
+  if (form == BK_FSAI)
+    return run_chunk((double)lsb_hip_solver_block_precond_iteration_bytes(sv, kp), 10.0, 8, 256);
+  const struct shard *s = &sv->sh[0];
+  return run_chunk((double)(12ull * s->nnz + s->amg->cycle_mat_bytes + 8ull * kp * (16ull * s->n + s->amg->cycle_vec_rows)),
+                   10.0, 2, 256);
+}
+
+int lsb_hip_solver_solve_block_precond_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb,
+                                           double *d_X, size_t ldx, struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, d_B, ldb, d_X, ldx))
+    return 2;
+  if (blockcg_serves(sv))
+    return lsb_hip_solver_solve_block_dev(sv, nrhs, d_B, ldb, d_X, ldx, res);
+  if (!mrhs_serves_zblock(sv))
+    return 2;
+  if (nrhs == 1)
+    return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
+  return blockcg_solve(sv, nrhs, d_B, ldb, d_X, ldx, res, blockcg_m_form(sv));
+}
+
+int lsb_hip_solver_solve_block_precond(lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X,
+                                       size_t ldx, struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, B, ldb, X, ldx) || !(blockcg_serves(sv) || mrhs_serves_zblock(sv)))
+    return 2;
+  return blockcg_host(lsb_hip_solver_solve_block_precond_dev, sv, nrhs, B, ldb, X, ldx, res);
 }

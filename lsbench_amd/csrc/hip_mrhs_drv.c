@@ -183,6 +183,15 @@ static unsigned fs_lanes(const lsb_hip_solver *sv, const struct fsai_csr *c) {
   return sv->mr_fs_lanes ? sv->mr_fs_lanes : c->lanes;
 }
 
+/* for the preconditioned half of the block-CG driver: solve_multi's service rule where z is a block of its own, and the
+ * lanes per row of G (gt = 0) or of G^T */
+int mrhs_serves_zblock(const lsb_hip_solver *sv) { return mrhs_serves(sv) && mrhs_zblock(sv); }
+unsigned mrhs_fsai_lanes(lsb_hip_solver *sv, int gt) {
+  if (!sv->mr_hst)
+    mrhs_lanes_init(sv);
+  return fs_lanes(sv, gt ? &sv->sh[0].fs_gt : &sv->sh[0].fs_g);
+}
+
 /* Z = G^T (G R) of this width, un-gated: two SpMMs off the factor's CSRs.  Their records of x.y, which nobody reads,
  * go into parts2: every caller's next launch writes that anew, while parts_pq may still hold a verify round's
  * residual norms for the launches behind this one */

@@ -1,5 +1,5 @@
 // What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_amg.hip, hip_amg_cheb.hip,
-// hip_bcg.hip) share: the 16-byte pair
+// hip_bcg.hip, hip_bcg_m.hip) share: the 16-byte pair
 // of the interleaved blocks and its store gated per column, the fixed-order reductions of their per-column
 // records, the verify round's decision and the launchers' dispatch on the batch width.  Included by those files
 // only, after hip_kcommon.h.
@@ -103,8 +103,67 @@ __device__ __forceinline__ void store_pairs(double *const (&v)[NB], const d2v (&
 }
 
 // --------------------------------------------------------------------------
+// What the two block-CG kernel files (hip_bcg.hip, hip_bcg_m.hip) share: a lane of their streaming launches owns whole
+// rows, and the Gram matrices leave a launch as records of their upper triangle.
+// --------------------------------------------------------------------------
+#define BCG_PASS_GRID 512 // workgroups of a streaming pass at the most (its consumer has ONE workgroup to sum them)
+
+static_assert(BCG_PASS_GRID <= LSB_STREAM_GRID_CAP, "the driver sizes the passes' records by LSB_STREAM_GRID_CAP");
+
+// (i, j), i <= j, in the upper triangle stored row by row
+__host__ __device__ constexpr int tri_at(int KP, int i, int j) { return i * KP - i * (i - 1) / 2 + (j - i); }
+__host__ __device__ constexpr int tri_of(int KP) { return KP * (KP + 1) / 2; }
+
+// a row's KP doubles <-> KP / 2 16-byte accesses
+template <int KP> __device__ __forceinline__ void row_load(const double *__restrict__ v, size_t i, double (&o)[KP]) {
+  const d2v *v2 = (const d2v *)v + i * (KP / 2);
+#pragma unroll
+  for (int h = 0; h < KP / 2; h++) {
+    const d2v t = v2[h];
+    o[2 * h] = t.x, o[2 * h + 1] = t.y;
+  }
+}
+template <int KP> __device__ __forceinline__ void row_store(double *__restrict__ v, size_t i, const double (&o)[KP]) {
+  d2v *v2 = (d2v *)v + i * (KP / 2);
+#pragma unroll
+  for (int h = 0; h < KP / 2; h++)
+    v2[h] = d2v{o[2 * h], o[2 * h + 1]};
+}
+
+// the workgroup's sums of W per-lane values -> dst[W]: wavefront butterfly, the four waves through LDS in fixed order
+template <int W> __device__ __forceinline__ void wg_sum_store(double (&v)[W], double *sred /* 4 W */, double *dst) {
+#pragma unroll
+  for (int k = 0; k < W; k++) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+      v[k] += __shfl_xor(v[k], off, 64);
+  }
+  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < W; k++)
+      sred[wave * W + k] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < W)
+    dst[threadIdx.x] = (sred[threadIdx.x] + sred[W + threadIdx.x]) + (sred[2 * W + threadIdx.x] + sred[3 * W + threadIdx.x]);
+}
+
+// --------------------------------------------------------------------------
 // host helpers of the launchers.  kp: 2, 4 or 8.
 // --------------------------------------------------------------------------
+// rows of a block-CG streaming pass: one row per lane and trip
+static inline unsigned pass_grid(unsigned n) {
+  unsigned g = div_up(n ? n : 1, WG);
+  if (g > 256) {
+    g = div_up(n, WG * 4);
+    if (g < 256)
+      g = 256;
+  }
+  return g > BCG_PASS_GRID ? BCG_PASS_GRID : g;
+}
+
 static unsigned kshift_of(unsigned kp) {
   if (kp != 2 && kp != 4 && kp != 8)
     errx(EXIT_FAILURE, "hip_mrhs: a batch is 2, 4 or 8 columns wide, not %u", kp);

@@ -15,7 +15,7 @@
  *   hip_bicgstab_drv.c  BiCGSTAB driver
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
  *   hip_mrhs_drv.c   several right-hand sides: multi-RHS Jacobi- and AMG-PCG on a CSR SpMM
- *   hip_bcg_drv.c    block-CG proper: one Krylov space for a block of right-hand sides
+ *   hip_bcg_drv.c    block-CG proper: one Krylov space for a block of right-hand sides (second half: under FSAI and AMG)
  * Nothing here is part of the C-ABI (include/lsbench_hip.h).
  */
 #ifndef HIP_SOLVER_H
@@ -343,6 +343,12 @@ struct lsb_hip_solver {
     double *b, *x, *w, *p, *q; /* n kp doubles each */
     double *rec_spmm, *rec_pass; /* records of the SpMM (LSB_MAX_PARTIALS) and of the passes (LSB_STREAM_GRID_CAP) */
     struct lsb_blockcg_state *st;
+    /* solve_block_precond under FSAI or AMG, on first use: z = M^-1 (.) as a block.  FSAI: z, t = G w and the records
+     * of the row kernel that forms the Gram sums (LSB_MAX_PARTIALS) are pmem; AMG: z and the cycle's vectors are
+     * amg_mem (amg_block_vecs, av), and the Gram sums are a streaming pass's (rec_pass) */
+    char *pmem, *amg_mem;
+    double *z, *t, *rec_gram;
+    struct amg_vecs *av;
     unsigned hint;             /* SpMMs the previous block of this width took */
     struct graph_cache g;      /* keyed on the count: the iteration touches these buffers only */
   } bk[3];
@@ -558,6 +564,10 @@ LSB_INTERNAL void mrhs_free(lsb_hip_solver *sv); /* before the shards go */
 LSB_INTERNAL int mrhs_serves_diag(const lsb_hip_solver *sv);
 LSB_INTERNAL unsigned mrhs_batch_width(unsigned nrhs);
 LSB_INTERNAL unsigned mrhs_spmm_lanes(lsb_hip_solver *sv);
+/* ... and with its preconditioned half: solve_multi's service rule where z is a block of its own (AMG in fp64 under
+ * l1-Jacobi or Chebyshev smoothing, FSAI with opts.fsai_blocks), the lanes per row of FSAI's G (gt = 0) or G^T */
+LSB_INTERNAL int mrhs_serves_zblock(const lsb_hip_solver *sv);
+LSB_INTERNAL unsigned mrhs_fsai_lanes(lsb_hip_solver *sv, int gt);
 /* hip_bcg_drv.c */
 LSB_INTERNAL void blockcg_free(lsb_hip_solver *sv); /* before the shards go */
 

@@ -436,6 +436,28 @@ void lsb_k_blockcg_pass_a(unsigned kp, unsigned n, double *w, const double *q, c
 /* W = W~ zeta^-1 ; P = D^-1 W + P zeta^T */
 void lsb_k_blockcg_pass_b(unsigned kp, unsigned n, double *w, double *p, const double *dinv, double dc,
                           const struct lsb_blockcg_state *st, void *stream);
+/* ... under a preconditioner that is an operator (hip_bcg_m.hip): Z = M^-1 (.) is a block of its own.  The state, the
+ * SpMM and lsb_k_blockcg_small are the ones above; zeta is then L^T of G = W~^T M^-1 W~.
+ * X += P xs ; W~ = W - Q xi in place ; no records */
+void lsb_k_blockcg_m_pass_a(unsigned kp, unsigned n, double *w, const double *q, const double *p, double *x,
+                            const struct lsb_blockcg_state *st, void *stream);
+/* records of two blocks of the same rows, <= LSB_STREAM_GRID_CAP of them.  start: the upper triangle of A^T Z, then
+ * a_c . a_c (lsb_k_blockcg_init's layout, tri + kp doubles; not gated, st is not read); else the upper triangles of
+ * A^T Z and of A^T A (pass A's layout, 2 tri doubles) */
+void lsb_k_blockcg_m_gram(unsigned kp, int start, unsigned n, const double *a, const double *z, double *records,
+                          unsigned *nrecords, const struct lsb_blockcg_state *st, void *stream);
+/* Z = G^T T with lsb_k_spmm_csr's row and rounding rule (offs, cols, vals: the CSR of G^T) and the records of the
+ * upper triangles of W~^T Z and of W~^T W~ in pass A's layout, one per workgroup of the SpMM's grid
+ * (<= LSB_MAX_PARTIALS) */
+void lsb_k_blockcg_m_gt_gram(unsigned kp, unsigned n, const int *offs, const int *cols, const double *vals,
+                             unsigned lanes, const double *t, const double *wt, double *z, double *records,
+                             unsigned *nrecords, const struct lsb_blockcg_state *st, void *stream);
+/* W = B sigma^-1, P = Z sigma^-1, X = 0 (not gated) */
+void lsb_k_blockcg_m_start(unsigned kp, unsigned n, const double *b, const double *z, double *w, double *p, double *x,
+                           const struct lsb_blockcg_state *st, void *stream);
+/* W = W~ zeta^-1 ; P = Z~ zeta^-1 + P zeta^T */
+void lsb_k_blockcg_m_pass_b(unsigned kp, unsigned n, double *w, const double *z, double *p,
+                            const struct lsb_blockcg_state *st, void *stream);
 
 /* ---- preconditioners with z as a vector (hip_precond_k.hip) -------------------- */
 void lsb_k_dot2(unsigned n, const double *r, const double *z, double *partials2,

@@ -24,7 +24,9 @@ device memory in use behind the first batch (device_mem_mb: everything the proce
 the same solver and the same B (column 0 is b_i = i, the others standard normal draws of seed 7: a block must have full
 rank, which the columns (c + 1) i above have not), alternating, after the same two warm-up rounds.  Per width under
 "block": iterations of both forms (solve_multi: per column), seconds per solve (the median over the repetitions, and
-[min, max]), and bytes per iteration over the time per iteration of each form, in GB/s.  Jacobi only.
+[min, max]), and bytes per iteration over the time per iteration of each form, in GB/s.  With --precond fsai|amg the
+block form is solve_block_dev(precond=True) on that solver (lsb_hip_solver_solve_block_precond_dev) and its bytes are
+block_precond_iteration_bytes: 0 under AMG, as multi_iteration_bytes, and so are the GB/s.
 Progress goes to stderr.
 
 Usage: python tools/bench_mrhs.py [--operators xn3b,tj7a,coef,lap2d] [--reps 5] [--n 3162] [--nrhs 2,4,8]
@@ -54,8 +56,8 @@ def file_matrix(la, name, tmp):
     return la.lsbench_matrix_read(p)
 
 
-def block_leg(la, torch, s, n, nrhs, reps, key):
-    """solve_block_dev beside solve_multi_dev on one solver and one B"""
+def block_leg(la, torch, s, n, nrhs, reps, key, precond):
+    """solve_block_dev (precond: its preconditioned entry point) beside solve_multi_dev on one solver and one B"""
     g = torch.Generator().manual_seed(7)
     B = torch.randn(nrhs, n, dtype=torch.float64, generator=g)
     B[0] = torch.arange(n, dtype=torch.float64)
@@ -70,18 +72,22 @@ def block_leg(la, torch, s, n, nrhs, reps, key):
         assert all(r.status == la.STATUS_CONVERGED for r in res), [r.status for r in res]
         return t, [int(r.iters) for r in res]
 
+    def block(d_B, d_X):
+        return s.solve_block_dev(d_B, d_X, precond=precond)
+
     for _ in range(2):
-        run(s.solve_multi_dev), run(s.solve_block_dev)
+        run(s.solve_multi_dev), run(block)
     tm, tb, itm, itb = [], [], None, None
     for k in range(reps):
         t, itm = run(s.solve_multi_dev)
         tm.append(t)
-        t, itb = run(s.solve_block_dev)
+        t, itb = run(block)
         tb.append(t)
         print("%s nrhs %d rep %d: multi %.4f s, block %.4f s" % (key, nrhs, k, tm[-1], tb[-1]), file=sys.stderr,
               flush=True)
     tm, tb = np.array(tm), np.array(tb)
-    mb, bb = s.multi_iteration_bytes(nrhs), s.block_iteration_bytes(nrhs)
+    mb = s.multi_iteration_bytes(nrhs)
+    bb = s.block_precond_iteration_bytes(nrhs) if precond else s.block_iteration_bytes(nrhs)
     return {"iters_multi": itm, "iters_block": itb[0],
             "s_per_solve_multi": round(float(np.median(tm)), 6), "s_per_solve_block": round(float(np.median(tb)), 6),
             "s_minmax_multi": [round(float(tm.min()), 6), round(float(tm.max()), 6)],
@@ -142,11 +148,11 @@ def main():
         rec = {"operator": label, "rows": n, "nnz": int(s.nnz_local), "tol": kw["tol"], "setup_s": round(time.time() - t0, 2),
                "padded_rows": int(s.padded), "precond": a.precond + ("(%d)" % a.fsai_power if a.precond == "fsai" else ""), "iteration_bytes_single": int(s.iteration_bytes), "reps": a.reps, "nrhs": {}}
         if a.block:
-            assert a.precond == "jacobi" and not a.fixed_iters, "--block: Jacobi, to a tolerance"
+            assert not a.fixed_iters, "--block: to a tolerance"
             rec["block"] = {}
         for nrhs in [int(v) for v in a.nrhs.split(",")]:
             if a.block:
-                rec["block"][str(nrhs)] = block_leg(la, torch, s, n, nrhs, a.reps, key)
+                rec["block"][str(nrhs)] = block_leg(la, torch, s, n, nrhs, a.reps, key, a.precond != "jacobi")
                 continue
             d_B = torch.arange(n, dtype=torch.float64, device="cuda:0")[None, :] * \
                 torch.arange(1, nrhs + 1, dtype=torch.float64, device="cuda:0")[:, None]
