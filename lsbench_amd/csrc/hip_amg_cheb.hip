@@ -3,9 +3,8 @@
 // hip_mrhs_amg.hip (driver: amg_cycle in hip_amg_drv.c).  The rest of the cycle on blocks -- residual,
 // restriction, prolongation, the dense coarse solve -- is hip_mrhs_amg.hip's, whatever the smoother.
 //
-// Rounding rule: per column exactly the single kernel's arithmetic -- lane l of a row's L takes entries
-// offs[i] + l, + L, ... in storage order through a = fma(val, x, a), the L sums are folded by the xor butterfly
-// L/2, ..., 1, and lane 0 applies amg_cheb_dir (hip_amg_cheb.h), then y = x + d.  A column of the block has the
+// Rounding rule: per column exactly the single kernel's arithmetic -- a row's sums are block_row_product's
+// (hip_mrhs_k.h), and lane 0 applies amg_cheb_dir (hip_amg_cheb.h), then y = x + d.  A column of the block has the
 // BITS of the single-column cycle; columns never mix.  The direction block d is updated in place (row i reads
 // only d_i) and is not read on a step with c1 == 0.
 //
@@ -43,28 +42,7 @@ __global__ __launch_bounds__(WG) void k_amg_cheb_m(unsigned n, unsigned rows_per
   for (unsigned base = ra; base < rb; base += SLOTS) {
     const unsigned r = base + slot;
     double a[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k++)
-      a[k] = 0.0;
-    if (r < rb) {
-      const int j1 = offs[r + 1];
-      for (int j = offs[r] + (int)l; j < j1; j += L) {
-        const double v = vals[j];
-        const size_t c = (size_t)cols[j] * H;
-#pragma unroll
-        for (int h = 0; h < H; h++) {
-          const d2v t = x2[c + h];
-          a[2 * h] = fma(v, t.x, a[2 * h]);
-          a[2 * h + 1] = fma(v, t.y, a[2 * h + 1]);
-        }
-      }
-    }
-#pragma unroll
-    for (int off = L >> 1; off > 0; off >>= 1) {
-#pragma unroll
-      for (int k = 0; k < KP; k++)
-        a[k] += __shfl_xor(a[k], off, 64);
-    }
+    block_row_product<L, KP>(offs, cols, vals, xin, r, r < rb, l, a);
     if (r < rb && l == 0) {
       const size_t o = (size_t)r * H;
       const double m = dinv[r];
@@ -131,9 +109,8 @@ template <int KP, bool REC>
 static void amg_cheb_launch(const struct lsb_amg_mat *m, unsigned g, const double *xin, const double *b,
                             const double *dinv, double c1, double c2, double *d, double *y, double *records,
                             const struct lsb_mrhs_state *st, hipStream_t s) {
-  LANES_DISPATCH(m->lanes, (k_amg_cheb_m<L, KP, REC><<<g, WG, 0, s>>>(m->rows, round_up(div_up(m->rows, g), WG / L),
-                                                                  m->offs, m->cols, m->vals, xin, b, dinv, c1, c2, d,
-                                                                  y, records, st)));
+  ROW_KERNEL_LAUNCH(m->lanes, (k_amg_cheb_m<L, KP, REC>), g, s, m->rows, m->offs, m->cols, m->vals, xin, b, dinv, c1, c2,
+                    d, y, records, st);
 }
 
 extern "C" {

@@ -29,15 +29,13 @@
 
 #define BS LSB_MRHS_MAX // stride of the small matrices in the state and in LDS
 #define WGS 1024        // threads of k_bcg_small: its record sums are a few hundred loads a thread otherwise
-// (tri_at, tri_of, row_load, row_store, wg_sum_store, pass_grid: hip_mrhs_k.h, shared with hip_bcg_m.hip)
+// (tri_at, tri_of, the dealt triangle, row_load, row_store, wg_sum_store, pass_grid: hip_mrhs_k.h, shared with
+// hip_bcg_m.hip)
 
 // --------------------------------------------------------------------------
-// Q = S P: k_spmm_csr<L, KP, false>'s row rule and rounding rule (hip_mrhs.hip) -- a lane's sum for column c is the
-// chain a = fma(val_j, p_jc, a) over its entries j0 + l, j0 + l + L, ... in that order, the L lane sums folded by the
-// xor butterfly L/2, ..., 1 -- so Q has the bits of lsb_hip_solver_spmm_dev on the same P.  After the butterfly every
-// lane of the row's group holds the row of Q; each takes the row of P and the entries t = l, l + L, ... of the upper
-// triangle of p_row^T q_row, so a lane keeps ceil(T / L) running sums, not T.  One record of T doubles per
-// workgroup, rows dealt XCD-contiguously.
+// Q = S P by the row rule (block_row_product, hip_mrhs_k.h), so Q has the bits of lsb_hip_solver_spmm_dev on the same
+// P.  Every lane of the row's group then takes the row of P and its entries of the upper triangle of p_row^T q_row
+// (the dealt triangle, hip_mrhs_k.h).  One record of T doubles per workgroup, rows dealt XCD-contiguously.
 // --------------------------------------------------------------------------
 template <int L, int KP>
 __global__ __launch_bounds__(WG) void k_bcg_spmm(unsigned n, unsigned rows_per_wg, const int *__restrict__ offs,
@@ -45,43 +43,21 @@ __global__ __launch_bounds__(WG) void k_bcg_spmm(unsigned n, unsigned rows_per_w
                                                  const double *__restrict__ x, double *__restrict__ y,
                                                  double *__restrict__ records,
                                                  const lsb_blockcg_state *__restrict__ st) {
-  constexpr int H = KP / 2, T = tri_of(KP), NA = (T + L - 1) / L;
+  constexpr int T = tri_of(KP), NA = tri_dealt(KP, L);
   constexpr unsigned SLOTS = WG / L;
   __shared__ double sred[4 * T];
   const unsigned tid = threadIdx.x, slot = tid / L, l = tid % L;
   const unsigned w = xcd_contiguous_wg();
   const unsigned ra = min(w * rows_per_wg, n), rb = min(ra + rows_per_wg, n);
   const int stopped = !st->running;
-  const d2v *x2 = (const d2v *)x;
-  double g[NA];
+  double g[1][NA]; // P^T Q, this lane's entries
 #pragma unroll
   for (int k = 0; k < NA; k++)
-    g[k] = 0.0;
+    g[0][k] = 0.0;
   for (unsigned base = ra; base < rb; base += SLOTS) {
     const unsigned r = base + slot;
     double a[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k++)
-      a[k] = 0.0;
-    if (r < rb) {
-      const int j0 = offs[r], j1 = offs[r + 1];
-      for (int j = j0 + (int)l; j < j1; j += L) {
-        const double v = vals[j];
-        const size_t c = (size_t)cols[j] * H;
-#pragma unroll
-        for (int h = 0; h < H; h++) {
-          const d2v t = x2[c + h];
-          a[2 * h] = fma(v, t.x, a[2 * h]);
-          a[2 * h + 1] = fma(v, t.y, a[2 * h + 1]);
-        }
-      }
-    }
-#pragma unroll
-    for (int off = L >> 1; off > 0; off >>= 1) {
-#pragma unroll
-      for (int k = 0; k < KP; k++)
-        a[k] += __shfl_xor(a[k], off, 64);
-    }
+    block_row_product<L, KP>(offs, cols, vals, x, r, r < rb, l, a);
     if (stopped)
       return;
     if (r < rb) {
@@ -89,36 +65,12 @@ __global__ __launch_bounds__(WG) void k_bcg_spmm(unsigned n, unsigned rows_per_w
       row_load<KP>(x, r, pr);
       if (l == 0)
         row_store<KP>(y, r, a);
-#pragma unroll
-      for (int i = 0; i < KP; i++) {
-#pragma unroll
-        for (int j = i; j < KP; j++) {
-          const int t = tri_at(KP, i, j); // a constant after unrolling
-          if ((unsigned)(t % L) == l)
-            g[t / L] = fma(pr[i], a[j], g[t / L]);
-        }
-      }
+      tri_dealt_fma<L, KP>(pr, {a}, l, g);
     }
   }
   if (stopped)
     return;
-  // lanes of a wave with the same l hold the same entries
-#pragma unroll
-  for (int k = 0; k < NA; k++) {
-#pragma unroll
-    for (int off = 32; off >= L; off >>= 1)
-      g[k] += __shfl_xor(g[k], off, 64);
-  }
-  const unsigned wave = tid >> 6, lane = tid & 63;
-  if (lane < L) {
-#pragma unroll
-    for (int k = 0; k < NA; k++)
-      if (k * L + (int)lane < T)
-        sred[wave * T + k * L + lane] = g[k];
-  }
-  __syncthreads();
-  if (tid < T)
-    records[(size_t)w * T + tid] = (sred[tid] + sred[T + tid]) + (sred[2 * T + tid] + sred[3 * T + tid]);
+  tri_dealt_store<L, KP>(g, sred, records + (size_t)w * T);
 }
 
 // --------------------------------------------------------------------------
@@ -552,8 +504,7 @@ template <int KP>
 static void bcg_spmm_launch(unsigned lanes, unsigned g, unsigned n, const int *offs, const int *cols,
                             const double *vals, const double *p, double *q, double *records,
                             const struct lsb_blockcg_state *st, hipStream_t s) {
-  LANES_DISPATCH(lanes, (k_bcg_spmm<L, KP><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols, vals, p, q,
-                                                           records, st)));
+  ROW_KERNEL_LAUNCH(lanes, (k_bcg_spmm<L, KP>), g, s, n, offs, cols, vals, p, q, records, st);
 }
 
 template <int KP>

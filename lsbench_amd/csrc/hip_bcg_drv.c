@@ -1,4 +1,5 @@
-/* Block-CG proper: host driver (kernels: hip_bcg.hip, and hip_bcg_m.hip for the preconditioned half below). */
+/* Block-CG proper: host driver (kernels: hip_bcg.hip, and hip_bcg_m.hip for the preconditioned half below; the work
+ * area, the service rules and Z = M^-1 R it shares with the driver of independent recurrences: hip_block.c). */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
@@ -29,46 +30,37 @@
  * Served: what solve_multi serves under the diagonal preconditioners, 2 <= nrhs <= LSB_MRHS_MAX; one column is
  * lsb_hip_solver_solve_dev.  Everything else answers 2 and allocates nothing.
  */
-static int blockcg_serves(const lsb_hip_solver *sv) { return mrhs_serves_diag(sv); }
+static int blockcg_serves(const lsb_hip_solver *sv) { return block_serves(sv) && !block_zblock(sv); }
 
 /* How a block's z = M^-1 (.) is formed: by the diagonal inside the passes (solve_block), or as a block of its own by
  * FSAI's two products or by the V-cycle (solve_block_precond, the second half of this file). */
 enum blockcg_form { BK_DIAG, BK_FSAI, BK_AMG };
 /* (the second half's, which the shared solve below calls) */
 static void blockcg_m_setup(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form);
-static void blockcg_m_zapply(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form, const double *r);
 static void blockcg_m_enqueue_iter(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form);
 static int blockcg_m_chunk(const lsb_hip_solver *sv, unsigned kp, enum blockcg_form form);
 
 static struct blockcg_work *blockcg_setup(lsb_hip_solver *sv, unsigned kp) {
   struct blockcg_work *w = &sv->bk[kp == 2 ? 0 : kp == 4 ? 1 : 2];
-  if (w->kp)
+  if (w->blk.kp)
     return w;
-  const struct shard *s = &sv->sh[0];
   if (!sv->bk_hst)
     LSB_CHK_HIP(hipHostMalloc((void **)&sv->bk_hst, 2 * sizeof(struct lsb_blockcg_state), 0));
-  /* 256-byte aligned pieces of one allocation, the blocks first */
+  /* behind the five blocks, 256-byte aligned: the two record arrays, then the state */
   const unsigned tri = lsb_k_blockcg_tri(kp);
-  const size_t blk = (((size_t)s->n * kp * sizeof(double)) + 255) & ~(size_t)255;
   const size_t rsp = (((size_t)LSB_MAX_PARTIALS * tri * sizeof(double)) + 255) & ~(size_t)255;
   const size_t rpa = (((size_t)LSB_STREAM_GRID_CAP * 2 * tri * sizeof(double)) + 255) & ~(size_t)255;
   const size_t stb = (sizeof(struct lsb_blockcg_state) + 255) & ~(size_t)255;
-  w->mem = (char *)lsb_hip_malloc(5 * blk + rsp + rpa + stb);
-  LSB_CHK_HIP(hipMemsetAsync(w->mem, 0, 5 * blk + rsp + rpa + stb, g_stream));
-  w->b = (double *)w->mem, w->x = (double *)(w->mem + blk), w->w = (double *)(w->mem + 2 * blk);
-  w->p = (double *)(w->mem + 3 * blk), w->q = (double *)(w->mem + 4 * blk);
-  w->rec_spmm = (double *)(w->mem + 5 * blk);
-  w->rec_pass = (double *)(w->mem + 5 * blk + rsp);
-  w->st = (struct lsb_blockcg_state *)(w->mem + 5 * blk + rsp + rpa);
-  w->kp = kp;
+  char *behind = block_work_slab(sv, &w->blk, kp, 5, rsp + rpa + stb);
+  w->rec_spmm = (double *)behind;
+  w->rec_pass = (double *)(behind + rsp);
+  w->st = (struct lsb_blockcg_state *)(behind + rsp + rpa);
   return w;
 }
 
 void blockcg_free(lsb_hip_solver *sv) {
   for (int k = 0; k < 3; k++) {
-    graph_drop(&sv->bk[k].g);
-    lsb_hip_free(sv->bk[k].mem), lsb_hip_free(sv->bk[k].pmem), lsb_hip_free(sv->bk[k].amg_mem);
-    free(sv->bk[k].av);
+    block_work_free(&sv->bk[k].blk);
     memset(&sv->bk[k], 0, sizeof sv->bk[k]);
   }
   if (sv->bk_hst)
@@ -84,23 +76,23 @@ unsigned long long lsb_hip_solver_block_iteration_bytes(const lsb_hip_solver *sv
   if (!sv || nrhs == 0 || nrhs > LSB_MRHS_MAX || !blockcg_serves(sv))
     return 0;
   const struct shard *s = &sv->sh[0];
-  const unsigned kp = nrhs == 1 ? 1u : mrhs_batch_width(nrhs);
+  const unsigned kp = nrhs == 1 ? 1u : block_width(nrhs);
   return 12ull * s->nnz + 4ull * (s->n + 1ull) + 8ull * s->n * (12ull * kp + (s->dinv_uniform ? 0u : 2u));
 }
 
 static void blockcg_enqueue_iter(lsb_hip_solver *sv, struct blockcg_work *w) {
   const struct shard *s = &sv->sh[0];
+  const struct block_work *k = &w->blk;
   unsigned nsp = 0, npa = 0;
-  lsb_k_blockcg_spmm(w->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, mrhs_spmm_lanes(sv), w->p, w->q, w->rec_spmm,
-                     &nsp, w->st, g_stream);
-  lsb_k_blockcg_small(w->kp, LSB_BLOCKCG_GAMMA, w->st, w->rec_spmm, nsp, 0, 0.0, 0, g_stream);
-  lsb_k_blockcg_pass_a(w->kp, s->n, w->w, w->q, w->p, w->x, DINV(s), w->st, w->rec_pass, &npa, g_stream);
-  lsb_k_blockcg_small(w->kp, LSB_BLOCKCG_G, w->st, w->rec_pass, npa, 0, 0.0, 0, g_stream);
-  lsb_k_blockcg_pass_b(w->kp, s->n, w->w, w->p, DINV(s), w->st, g_stream);
+  lsb_k_blockcg_spmm(k->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, sv->mr_lanes, k->p, k->q, w->rec_spmm, &nsp,
+                     w->st, g_stream);
+  lsb_k_blockcg_small(k->kp, LSB_BLOCKCG_GAMMA, w->st, w->rec_spmm, nsp, 0, 0.0, 0, g_stream);
+  lsb_k_blockcg_pass_a(k->kp, s->n, k->w, k->q, k->p, k->x, DINV(s), w->st, w->rec_pass, &npa, g_stream);
+  lsb_k_blockcg_small(k->kp, LSB_BLOCKCG_G, w->st, w->rec_pass, npa, 0, 0.0, 0, g_stream);
+  lsb_k_blockcg_pass_b(k->kp, s->n, k->w, k->p, DINV(s), w->st, g_stream);
 }
 
-/* what run_loop enqueues: one linear chain on internal buffers, so its graphs are keyed on the count alone (a solver
- * has one form: its preconditioner's) */
+/* what block_enqueue runs for run_loop (a solver has one form: its preconditioner's) */
 struct blockcg_enq {
   lsb_hip_solver *sv;
   struct blockcg_work *w;
@@ -115,13 +107,6 @@ static void blockcg_enqueue_iters(void *ctx, int iters) {
       blockcg_m_enqueue_iter(e->sv, e->w, e->form);
   }
 }
-static void blockcg_enqueue(void *ctx, int iters) {
-  const struct blockcg_enq *e = ctx;
-  if (e->sv->o.use_graph)
-    graph_launch(&e->w->g, iters, NULL, blockcg_enqueue_iters, ctx);
-  else
-    blockcg_enqueue_iters(ctx, iters);
-}
 
 static int blockcg_chunk(const lsb_hip_solver *sv, unsigned kp) {
   if (sv->o.check_every > 0)
@@ -129,29 +114,25 @@ static int blockcg_chunk(const lsb_hip_solver *sv, unsigned kp) {
   return run_chunk((double)lsb_hip_solver_block_iteration_bytes(sv, kp), 10.0, 8, 256);
 }
 
-static int block_args_bad(const lsb_hip_solver *sv, unsigned nrhs, const void *a, size_t lda, const void *b,
-                          size_t ldb) {
-  return !sv || !a || !b || nrhs == 0 || nrhs > LSB_MRHS_MAX || lda < sv->n_user || ldb < sv->n_user;
-}
-
 /* one block of 2 .. 8 columns in the given form; the caller has checked the arguments and the service rule */
 static int blockcg_solve(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X, size_t ldx,
                          struct lsb_hip_result *res, enum blockcg_form form) {
-  struct blockcg_work *w = blockcg_setup(sv, mrhs_batch_width(nrhs));
+  struct blockcg_work *w = blockcg_setup(sv, block_width(nrhs));
   if (form != BK_DIAG)
     blockcg_m_setup(sv, w, form);
   const struct shard *s = &sv->sh[0];
+  const struct block_work *k = &w->blk;
   struct lsb_blockcg_state *hst = sv->bk_hst;
-  const unsigned kp = w->kp, n = s->n;
+  const unsigned kp = k->kp, n = s->n;
   unsigned nrec = 0, nverify = 0;
   int rc = 0;
   const double t0 = wall_seconds();
-  lsb_k_mrhs_pack(n, kp, nrhs, sv->d_perm, d_B, ldb, w->b, g_stream);
+  lsb_k_mrhs_pack(n, kp, nrhs, sv->d_perm, d_B, ldb, k->b, g_stream);
   if (form == BK_DIAG)
-    lsb_k_blockcg_init(kp, n, w->b, DINV(s), w->rec_pass, &nrec, g_stream);
-  else { /* Z = M^-1 B, then the records of (B^T Z, b_c . b_c) */
-    blockcg_m_zapply(sv, w, form, w->b);
-    lsb_k_blockcg_m_gram(kp, 1, n, w->b, w->z, w->rec_pass, &nrec, w->st, g_stream);
+    lsb_k_blockcg_init(kp, n, k->b, DINV(s), w->rec_pass, &nrec, g_stream);
+  else { /* Z = M^-1 B (un-gated, no Gram sums), then the records of (B^T Z, b_c . b_c) */
+    block_zapply(sv, k, k->b, w->rec_spmm);
+    lsb_k_blockcg_m_gram(kp, 1, n, k->b, k->z, w->rec_pass, &nrec, w->st, g_stream);
   }
   lsb_k_blockcg_small(kp, LSB_BLOCKCG_START, w->st, w->rec_pass, nrec, nrhs, sv->o.tol, (int)sv->o.maxit, g_stream);
   /* the rank rule is looked at here, from one copy of the state, before anything of the caller's is written */
@@ -161,28 +142,29 @@ static int blockcg_solve(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, s
     rc = 3;
   else {
     if (form == BK_DIAG)
-      lsb_k_blockcg_start(kp, n, w->b, DINV(s), w->w, w->p, w->x, w->st, g_stream);
+      lsb_k_blockcg_start(kp, n, k->b, DINV(s), k->w, k->p, k->x, w->st, g_stream);
     else
-      lsb_k_blockcg_m_start(kp, n, w->b, w->z, w->w, w->p, w->x, w->st, g_stream);
+      lsb_k_blockcg_m_start(kp, n, k->b, k->z, k->w, k->p, k->x, w->st, g_stream);
     struct blockcg_enq e = {sv, w, form};
+    struct block_enq be = {sv, &w->blk, blockcg_enqueue_iters, &e};
     const struct run_loop r = {.name = "a block of right-hand sides", .d_state = w->st, .h_state = hst,
                                .state_bytes = sizeof(struct lsb_blockcg_state),
                                .stop_off = offsetof(struct lsb_blockcg_state, running), .stop_is_running = 1,
                                .progress_off = offsetof(struct lsb_blockcg_state, nspmm),
-                               .enqueue = blockcg_enqueue, .ctx = &e,
+                               .enqueue = block_enqueue, .ctx = &be,
                                .chunk = form == BK_DIAG ? blockcg_chunk(sv, kp) : blockcg_m_chunk(sv, kp, form),
                                .even = 0, .max_piece = sv->o.use_graph ? 512 : 0, .cap = -1,
                                .what_hinted = "poll of a hinted block", .what_poll = "poll of the block",
                                .what_drain = "drain after the block"};
     run_loop(sv, &r, &w->hint);
     if (sv->o.verify && sv->o.tol > 0.0) {
-      lsb_k_spmm_csr(kp, n, s->csr.offs, s->csr.cols, s->csr.vals, mrhs_spmm_lanes(sv), w->x, w->q, w->b, w->rec_spmm,
-                     &nrec, NULL, g_stream);
+      lsb_k_spmm_csr(kp, n, s->csr.offs, s->csr.cols, s->csr.vals, sv->mr_lanes, k->x, k->q, k->b, w->rec_spmm, &nrec,
+                     NULL, g_stream);
       lsb_k_blockcg_small(kp, LSB_BLOCKCG_VERIFY, w->st, w->rec_spmm, nrec, 0, 0.0, 0, g_stream);
       nverify = 1;
       LSB_CHK_HIP(hipMemcpyAsync(&hst[0], w->st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream));
     }
-    lsb_k_mrhs_unpack(n, kp, nrhs, sv->d_perm, w->x, d_X, ldx, g_stream);
+    lsb_k_mrhs_unpack(n, kp, nrhs, sv->d_perm, k->x, d_X, ldx, g_stream);
     drain_stream(sv, "un-packing the block");
   }
   const double seconds = wall_seconds() - t0;
@@ -208,34 +190,22 @@ int lsb_hip_solver_solve_block_dev(lsb_hip_solver *sv, unsigned nrhs, const doub
                                    size_t ldx, struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, d_B, ldb, d_X, ldx) || !blockcg_serves(sv))
+  if (block_args_bad(sv, nrhs, LSB_MRHS_MAX, d_B, ldb, d_X, ldx) || !blockcg_serves(sv))
     return 2;
   if (nrhs == 1)
     return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
   return blockcg_solve(sv, nrhs, d_B, ldb, d_X, ldx, res, BK_DIAG);
 }
 
-/* the host-buffer form of either entry point: the caller has checked the arguments and the service rule */
-typedef int blockcg_dev_fn(lsb_hip_solver *, unsigned, const double *, size_t, double *, size_t, struct lsb_hip_result *);
-static int blockcg_host(blockcg_dev_fn *dev, lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X,
-                        size_t ldx, struct lsb_hip_result *res) {
-  const size_t n = sv->n_user, bytes = n * sizeof(double);
-  double *d_B = (double *)lsb_hip_malloc(bytes * nrhs), *d_X = (double *)lsb_hip_malloc(bytes * nrhs);
-  LSB_CHK_HIP(hipMemcpy2D(d_B, bytes, B, ldb * sizeof(double), bytes, nrhs, hipMemcpyHostToDevice));
-  const int rc = dev(sv, nrhs, d_B, n, d_X, n, res);
-  if (rc == 0)
-    LSB_CHK_HIP(hipMemcpy2D(X, ldx * sizeof(double), d_X, bytes, bytes, nrhs, hipMemcpyDeviceToHost));
-  lsb_hip_free(d_B), lsb_hip_free(d_X);
-  return rc;
-}
-
+/* (the host-buffer forms: X is the caller's again only where the block was solved -- a block without full rank
+ * answers 3 with X untouched) */
 int lsb_hip_solver_solve_block(lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X, size_t ldx,
                                struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, B, ldb, X, ldx) || !blockcg_serves(sv))
+  if (block_args_bad(sv, nrhs, LSB_MRHS_MAX, B, ldb, X, ldx) || !blockcg_serves(sv))
     return 2;
-  return blockcg_host(lsb_hip_solver_solve_block_dev, sv, nrhs, B, ldb, X, ldx, res);
+  return block_solve_host(lsb_hip_solver_solve_block_dev, 0, sv, nrhs, B, ldb, X, ldx, res);
 }
 
 /* ||r_c||^2 of the recurrence and ||b_c||^2 as the device state of the last block held them (nrhs <= 8 entries each,
@@ -273,7 +243,7 @@ int lsb_hip_solver_block_norms(const lsb_hip_solver *sv, unsigned nrhs, double *
  * solve_multi's chunk takes there, so at most one cycle is wasted on an un-hinted first solve; a hinted solve enqueues
  * the previous count.
  *
- * Served: what solve_multi serves with a z block (mrhs_serves_zblock): AMG in fp64 smoothed by l1-Jacobi or Chebyshev,
+ * Served: what solve_multi serves with a z block (blockcg_m_serves): AMG in fp64 smoothed by l1-Jacobi or Chebyshev,
  * FSAI with opts.fsai_blocks; 2 <= nrhs <= LSB_MRHS_MAX, one shard, x0 = 0.  A solver under a diagonal preconditioner
  * is forwarded to solve_block_dev (the same bits); one column is lsb_hip_solver_solve_dev.  Everything else answers 2
  * and allocates nothing.
@@ -282,71 +252,38 @@ static enum blockcg_form blockcg_m_form(const lsb_hip_solver *sv) {
   return sv->o.precond == LSB_PRECOND_FSAI ? BK_FSAI : BK_AMG;
 }
 
-/* the work area grows by z -- plus t = G w and the records of k_bcgm_gt_gram's grid under FSAI; under AMG z is the
- * head of the cycle's block vectors, as in mrhs_setup, and the Gram launch is a streaming pass (rec_pass) */
+static int blockcg_m_serves(const lsb_hip_solver *sv) { return block_serves(sv) && block_zblock(sv); }
+
+/* on the first preconditioned block the work area grows by z -- plus t = G w and the records of k_bcgm_gt_gram's grid
+ * under FSAI; under AMG z is the head of the cycle's block vectors and the Gram launch is a streaming pass (rec_pass) */
 static void blockcg_m_setup(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form) {
-  if (w->z)
+  if (w->blk.z)
     return;
-  const struct shard *s = &sv->sh[0];
-  if (form == BK_FSAI) {
-    const size_t blk = (((size_t)s->n * w->kp * sizeof(double)) + 255) & ~(size_t)255;
-    const size_t rec = (size_t)LSB_MAX_PARTIALS * 2 * lsb_k_blockcg_tri(w->kp) * sizeof(double);
-    w->pmem = (char *)lsb_hip_malloc(2 * blk + rec);
-    LSB_CHK_HIP(hipMemsetAsync(w->pmem, 0, 2 * blk + rec, g_stream));
-    w->z = (double *)w->pmem, w->t = (double *)(w->pmem + blk), w->rec_gram = (double *)(w->pmem + 2 * blk);
-  } else {
-    w->av = lsb_calloc(struct amg_vecs, s->amg->nlev);
-    w->amg_mem = amg_block_vecs(s->amg, w->kp, w->av);
-    w->z = (double *)w->amg_mem;
-  }
+  const size_t rec = (size_t)LSB_MAX_PARTIALS * 2 * lsb_k_blockcg_tri(w->blk.kp) * sizeof(double);
+  w->rec_gram = (double *)block_work_z(sv, &w->blk, form == BK_FSAI ? rec : 0);
 }
 
-/* T = G R by the SpMM's rule, un-gated; its records of r_c . t_c, which nobody reads, go where the next k_bcg_spmm or
- * the verify round writes anew */
-static void blockcg_m_g(lsb_hip_solver *sv, struct blockcg_work *w, const double *r) {
-  const struct shard *s = &sv->sh[0];
-  unsigned np = 0;
-  lsb_k_spmm_csr(w->kp, s->n, s->fs_g.offs, s->fs_g.cols, s->fs_g.vals, mrhs_fsai_lanes(sv, 0), r, w->t, NULL,
-                 w->rec_spmm, &np, NULL, g_stream);
-}
-
-static void blockcg_m_cycle(lsb_hip_solver *sv, struct blockcg_work *w, const double *r) {
-  const struct amg_run c = {.a = sv->sh[0].amg, .vec = w->av, .kp = w->kp, .r = r, .z = w->z,
-                            .records = NULL, .nrecords = NULL, .mst = NULL};
-  amg_cycle(&c);
-}
-
-/* Z = M^-1 R, un-gated, no Gram sums: the start's */
-static void blockcg_m_zapply(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form, const double *r) {
-  if (form == BK_AMG) {
-    blockcg_m_cycle(sv, w, r);
-    return;
-  }
-  const struct shard *s = &sv->sh[0];
-  unsigned np = 0;
-  blockcg_m_g(sv, w, r);
-  lsb_k_spmm_csr(w->kp, s->n, s->fs_gt.offs, s->fs_gt.cols, s->fs_gt.vals, mrhs_fsai_lanes(sv, 1), w->t, w->z, NULL,
-                 w->rec_spmm, &np, NULL, g_stream);
-}
-
+/* Z = M^-1 R on a block is block_zapply and T = G R block_fsai_g (hip_block.c), both un-gated.  The records of the
+ * SpMMs off G and G^T, which nobody reads, go into rec_spmm: the next k_bcg_spmm or the verify round writes it anew. */
 static void blockcg_m_enqueue_iter(lsb_hip_solver *sv, struct blockcg_work *w, enum blockcg_form form) {
   const struct shard *s = &sv->sh[0];
+  const struct block_work *k = &w->blk;
   unsigned nsp = 0, ngr = 0;
   double *rec = form == BK_FSAI ? w->rec_gram : w->rec_pass;
-  lsb_k_blockcg_spmm(w->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, mrhs_spmm_lanes(sv), w->p, w->q, w->rec_spmm,
-                     &nsp, w->st, g_stream);
-  lsb_k_blockcg_small(w->kp, LSB_BLOCKCG_GAMMA, w->st, w->rec_spmm, nsp, 0, 0.0, 0, g_stream);
-  lsb_k_blockcg_m_pass_a(w->kp, s->n, w->w, w->q, w->p, w->x, w->st, g_stream);
+  lsb_k_blockcg_spmm(k->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, sv->mr_lanes, k->p, k->q, w->rec_spmm, &nsp,
+                     w->st, g_stream);
+  lsb_k_blockcg_small(k->kp, LSB_BLOCKCG_GAMMA, w->st, w->rec_spmm, nsp, 0, 0.0, 0, g_stream);
+  lsb_k_blockcg_m_pass_a(k->kp, s->n, k->w, k->q, k->p, k->x, w->st, g_stream);
   if (form == BK_FSAI) {
-    blockcg_m_g(sv, w, w->w);
-    lsb_k_blockcg_m_gt_gram(w->kp, s->n, s->fs_gt.offs, s->fs_gt.cols, s->fs_gt.vals, mrhs_fsai_lanes(sv, 1), w->t,
-                            w->w, w->z, rec, &ngr, w->st, g_stream);
+    block_fsai_g(sv, k, k->w, w->rec_spmm);
+    lsb_k_blockcg_m_gt_gram(k->kp, s->n, s->fs_gt.offs, s->fs_gt.cols, s->fs_gt.vals,
+                            block_fsai_lanes(sv, &s->fs_gt), k->t, k->w, k->z, rec, &ngr, w->st, g_stream);
   } else {
-    blockcg_m_cycle(sv, w, w->w);
-    lsb_k_blockcg_m_gram(w->kp, 0, s->n, w->w, w->z, rec, &ngr, w->st, g_stream);
+    block_zapply(sv, k, k->w, NULL); /* the cycle */
+    lsb_k_blockcg_m_gram(k->kp, 0, s->n, k->w, k->z, rec, &ngr, w->st, g_stream);
   }
-  lsb_k_blockcg_small(w->kp, LSB_BLOCKCG_G, w->st, rec, ngr, 0, 0.0, 0, g_stream);
-  lsb_k_blockcg_m_pass_b(w->kp, s->n, w->w, w->z, w->p, w->st, g_stream);
+  lsb_k_blockcg_small(k->kp, LSB_BLOCKCG_G, w->st, rec, ngr, 0, 0.0, 0, g_stream);
+  lsb_k_blockcg_m_pass_b(k->kp, s->n, k->w, k->z, k->p, w->st, g_stream);
 }
 
 /* Bytes one iteration of a block of nrhs columns must move under FSAI: S, G and G^T once each whatever the width
@@ -359,10 +296,10 @@ unsigned long long lsb_hip_solver_block_precond_iteration_bytes(const lsb_hip_so
     return 0;
   if (blockcg_serves(sv))
     return lsb_hip_solver_block_iteration_bytes(sv, nrhs);
-  if (!mrhs_serves_zblock(sv) || blockcg_m_form(sv) != BK_FSAI)
+  if (!blockcg_m_serves(sv) || blockcg_m_form(sv) != BK_FSAI)
     return 0;
   const struct shard *s = &sv->sh[0];
-  const unsigned kp = nrhs == 1 ? 1u : mrhs_batch_width(nrhs);
+  const unsigned kp = nrhs == 1 ? 1u : block_width(nrhs);
   return 12ull * (s->nnz + s->fs_g.nnz + s->fs_gt.nnz) + 12ull * (s->n + 1ull) + 8ull * s->n * 18ull * kp;
 }
 
@@ -382,11 +319,11 @@ int lsb_hip_solver_solve_block_precond_dev(lsb_hip_solver *sv, unsigned nrhs, co
                                            double *d_X, size_t ldx, struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, d_B, ldb, d_X, ldx))
+  if (block_args_bad(sv, nrhs, LSB_MRHS_MAX, d_B, ldb, d_X, ldx))
     return 2;
   if (blockcg_serves(sv))
     return lsb_hip_solver_solve_block_dev(sv, nrhs, d_B, ldb, d_X, ldx, res);
-  if (!mrhs_serves_zblock(sv))
+  if (!blockcg_m_serves(sv))
     return 2;
   if (nrhs == 1)
     return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
@@ -397,7 +334,7 @@ int lsb_hip_solver_solve_block_precond(lsb_hip_solver *sv, unsigned nrhs, const 
                                        size_t ldx, struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, B, ldb, X, ldx) || !(blockcg_serves(sv) || mrhs_serves_zblock(sv)))
+  if (block_args_bad(sv, nrhs, LSB_MRHS_MAX, B, ldb, X, ldx) || !(blockcg_serves(sv) || blockcg_m_serves(sv)))
     return 2;
-  return blockcg_host(lsb_hip_solver_solve_block_precond_dev, sv, nrhs, B, ldb, X, ldx, res);
+  return block_solve_host(lsb_hip_solver_solve_block_precond_dev, 0, sv, nrhs, B, ldb, X, ldx, res);
 }

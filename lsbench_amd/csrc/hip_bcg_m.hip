@@ -91,13 +91,11 @@ __global__ __launch_bounds__(WG) void k_bcgm_gram(unsigned n, const double *__re
 }
 
 // --------------------------------------------------------------------------
-// FSAI's second product with the Gram sums riding in it: Z~ = G^T T by k_spmm_csr<L, KP, false>'s row rule and
-// rounding rule (hip_mrhs.hip) -- a lane's sum for column c is the chain a = fma(val_j, t_jc, a) over its entries
-// j0 + l, j0 + l + L, ... in that order, the L lane sums folded by the xor butterfly L/2, ..., 1 -- so Z~ has the bits
-// of lsb_hip_solver_spmm_dev's rule on the same T.  After the butterfly every lane of the row's group holds the row of
-// Z~; each loads the row of W~ and takes the entries t = l, l + L, ... of the two upper triangles, k_bcg_spmm's scheme
-// for P^T Q, so a lane keeps 2 ceil(T / L) running sums.  One record of 2 T doubles per workgroup (pass A's layout),
-// rows dealt XCD-contiguously.  `offs`, `cols`, `vals`: the CSR of G^T.
+// FSAI's second product with the Gram sums riding in it: Z~ = G^T T by the row rule (block_row_product,
+// hip_mrhs_k.h), so Z~ has the bits of lsb_hip_solver_spmm_dev's rule on the same T.  Every lane of the row's group
+// then loads the row of W~ and takes its entries of the two upper triangles (the dealt triangle, hip_mrhs_k.h;
+// k_bcg_spmm's scheme for P^T Q).  One record of 2 T doubles per workgroup (pass A's layout), rows dealt
+// XCD-contiguously.  `offs`, `cols`, `vals`: the CSR of G^T.
 // --------------------------------------------------------------------------
 template <int L, int KP>
 __global__ __launch_bounds__(WG) void k_bcgm_gt_gram(unsigned n, unsigned rows_per_wg, const int *__restrict__ offs,
@@ -105,43 +103,21 @@ __global__ __launch_bounds__(WG) void k_bcgm_gt_gram(unsigned n, unsigned rows_p
                                                      const double *__restrict__ t, const double *__restrict__ wt,
                                                      double *__restrict__ z, double *__restrict__ records,
                                                      const lsb_blockcg_state *__restrict__ st) {
-  constexpr int H = KP / 2, T = tri_of(KP), NA = (T + L - 1) / L;
+  constexpr int T = tri_of(KP), NA = tri_dealt(KP, L);
   constexpr unsigned SLOTS = WG / L;
   __shared__ double sred[4 * 2 * T];
   const unsigned tid = threadIdx.x, slot = tid / L, l = tid % L;
   const unsigned w = xcd_contiguous_wg();
   const unsigned ra = min(w * rows_per_wg, n), rb = min(ra + rows_per_wg, n);
   const int stopped = !st->running;
-  const d2v *t2 = (const d2v *)t;
-  double g[NA], hh[NA]; // W~^T Z~ and W~^T W~, this lane's entries
+  double g[2][NA]; // W~^T Z~ and W~^T W~, this lane's entries
 #pragma unroll
   for (int k = 0; k < NA; k++)
-    g[k] = 0.0, hh[k] = 0.0;
+    g[0][k] = 0.0, g[1][k] = 0.0;
   for (unsigned base = ra; base < rb; base += SLOTS) {
     const unsigned r = base + slot;
     double a[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k++)
-      a[k] = 0.0;
-    if (r < rb) {
-      const int j0 = offs[r], j1 = offs[r + 1];
-      for (int j = j0 + (int)l; j < j1; j += L) {
-        const double v = vals[j];
-        const size_t c = (size_t)cols[j] * H;
-#pragma unroll
-        for (int h = 0; h < H; h++) {
-          const d2v tv = t2[c + h];
-          a[2 * h] = fma(v, tv.x, a[2 * h]);
-          a[2 * h + 1] = fma(v, tv.y, a[2 * h + 1]);
-        }
-      }
-    }
-#pragma unroll
-    for (int off = L >> 1; off > 0; off >>= 1) {
-#pragma unroll
-      for (int k = 0; k < KP; k++)
-        a[k] += __shfl_xor(a[k], off, 64);
-    }
+    block_row_product<L, KP>(offs, cols, vals, t, r, r < rb, l, a);
     if (stopped)
       return;
     if (r < rb) {
@@ -149,42 +125,12 @@ __global__ __launch_bounds__(WG) void k_bcgm_gt_gram(unsigned n, unsigned rows_p
       row_load<KP>(wt, r, wr);
       if (l == 0)
         row_store<KP>(z, r, a);
-#pragma unroll
-      for (int i = 0; i < KP; i++) {
-#pragma unroll
-        for (int j = i; j < KP; j++) {
-          const int e = tri_at(KP, i, j); // a constant after unrolling
-          if ((unsigned)(e % L) == l) {
-            g[e / L] = fma(wr[i], a[j], g[e / L]);
-            hh[e / L] = fma(wr[i], wr[j], hh[e / L]);
-          }
-        }
-      }
+      tri_dealt_fma<L, KP>(wr, {a, wr}, l, g);
     }
   }
   if (stopped)
     return;
-  // lanes of a wave with the same l hold the same entries
-#pragma unroll
-  for (int k = 0; k < NA; k++) {
-#pragma unroll
-    for (int off = 32; off >= L; off >>= 1) {
-      g[k] += __shfl_xor(g[k], off, 64);
-      hh[k] += __shfl_xor(hh[k], off, 64);
-    }
-  }
-  const unsigned wave = tid >> 6, lane = tid & 63;
-  if (lane < L) {
-#pragma unroll
-    for (int k = 0; k < NA; k++)
-      if (k * L + (int)lane < T) {
-        sred[wave * 2 * T + k * L + lane] = g[k];
-        sred[wave * 2 * T + T + k * L + lane] = hh[k];
-      }
-  }
-  __syncthreads();
-  if (tid < 2 * T)
-    records[(size_t)w * 2 * T + tid] = (sred[tid] + sred[2 * T + tid]) + (sred[4 * T + tid] + sred[6 * T + tid]);
+  tri_dealt_store<L, KP>(g, sred, records + (size_t)w * 2 * T);
 }
 
 // W = B zinv (zinv = sigma^-1, upper triangular), P = Z zinv, X = 0.  Not gated: X = 0 is the answer of a block that
@@ -254,8 +200,7 @@ template <int KP>
 static void gt_gram_launch(unsigned lanes, unsigned g, unsigned n, const int *offs, const int *cols, const double *vals,
                            const double *t, const double *wt, double *z, double *records,
                            const struct lsb_blockcg_state *st, hipStream_t s) {
-  LANES_DISPATCH(lanes, (k_bcgm_gt_gram<L, KP><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols, vals, t,
-                                                               wt, z, records, st)));
+  ROW_KERNEL_LAUNCH(lanes, (k_bcgm_gt_gram<L, KP>), g, s, n, offs, cols, vals, t, wt, z, records, st);
 }
 
 extern "C" {

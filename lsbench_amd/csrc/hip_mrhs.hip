@@ -59,10 +59,8 @@ __global__ __launch_bounds__(WG) void k_mrhs_unpack(unsigned n, unsigned kshift,
 }
 
 // --------------------------------------------------------------------------
-// Y = S X off a CSR, L lanes per row as k_spmv_subwave<L>: a lane reads (col, val) once, gathers the KP / 2
-// 16-byte pairs of row `col` and keeps KP accumulators.  One rounding rule: a lane's
-// sum for column c is the chain a = fma(val_j, x_jc, a) over its entries j0 + l, j0 + l + L, ... in that
-// order, written with explicit fma(); the L lane sums are folded by the xor butterfly L/2, ..., 1.
+// Y = S X off a CSR, L lanes per row as k_spmv_subwave<L>: a row's sums are block_row_product's (hip_mrhs_k.h),
+// the one rounding rule of DESIGN.md section 4.
 // Epilogue, lane 0 of the row: y = S x and the per-column partials of x_c . y_c (the p.q of the iteration).
 // One record of KP doubles per workgroup, rows dealt XCD-contiguously.
 // st != NULL: a no-op once st->running == 0.
@@ -110,21 +108,25 @@ __global__ __launch_bounds__(WG) void k_spmm_csr(unsigned n, unsigned rows_per_w
     const unsigned r = base + slot;
     double a[KP], e[NE]; // e: the rounding errors of a's chain (RES)
 #pragma unroll
-    for (int k = 0; k < KP; k++)
-      a[k] = 0.0;
-#pragma unroll
     for (int k = 0; k < NE; k++)
       e[k] = 0.0;
-    if (r < rb) {
-      const int j0 = offs[r], j1 = offs[r + 1];
-      for (int j = j0 + (int)l; j < j1; j += L) {
-        const double v = vals[j];
-        const size_t c = (size_t)cols[j] * H;
+    if constexpr (!RES) {
+      block_row_product<L, KP>(offs, cols, vals, x, r, r < rb, l, a);
+    } else {
+      // Another computation, not the row rule: the same entries in the same order, but every product and every
+      // addition of the loop and of the butterfly carries its rounding error along.  It stays written out here.
 #pragma unroll
-        for (int h = 0; h < H; h++) {
-          const d2v t = x2[c + h];
-          if constexpr (RES) {
+      for (int k = 0; k < KP; k++)
+        a[k] = 0.0;
+      if (r < rb) {
+        const int j0 = offs[r], j1 = offs[r + 1];
+        for (int j = j0 + (int)l; j < j1; j += L) {
+          const double v = vals[j];
+          const size_t c = (size_t)cols[j] * H;
+#pragma unroll
+          for (int h = 0; h < H; h++) {
 #pragma clang fp contract(off)
+            const d2v t = x2[c + h];
             const double tk[2] = {t.x, t.y};
 #pragma unroll
             for (int q = 0; q < 2; q++) {
@@ -133,25 +135,18 @@ __global__ __launch_bounds__(WG) void k_spmm_csr(unsigned n, unsigned rows_per_w
               two_sum(a[2 * h + q], pr, a[2 * h + q], se);
               e[2 * h + q] += pe + se;
             }
-          } else {
-            a[2 * h] = fma(v, t.x, a[2 * h]);
-            a[2 * h + 1] = fma(v, t.y, a[2 * h + 1]);
           }
         }
       }
-    }
 #pragma unroll
-    for (int off = L >> 1; off > 0; off >>= 1) {
+      for (int off = L >> 1; off > 0; off >>= 1) {
 #pragma unroll
-      for (int k = 0; k < KP; k++) {
-        if constexpr (RES) { // both partners form the same sum and the same error
+        for (int k = 0; k < KP; k++) { // both partners form the same sum and the same error
 #pragma clang fp contract(off)
           const double ao = __shfl_xor(a[k], off, 64), eo = __shfl_xor(e[k], off, 64);
           double se;
           two_sum(a[k], ao, a[k], se);
           e[k] = (e[k] + eo) + se;
-        } else {
-          a[k] += __shfl_xor(a[k], off, 64);
         }
       }
     }
@@ -628,8 +623,7 @@ template <int KP, bool RES>
 static void spmm_launch(unsigned lanes, unsigned g, unsigned n, const int *offs, const int *cols, const double *vals,
                         const double *x, double *y, const double *bres, double *partials,
                         const struct lsb_mrhs_state *st, hipStream_t s) {
-  LANES_DISPATCH(lanes, (k_spmm_csr<L, KP, RES><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols, vals, x,
-                                                                y, bres, partials, st)));
+  ROW_KERNEL_LAUNCH(lanes, (k_spmm_csr<L, KP, RES>), g, s, n, offs, cols, vals, x, y, bres, partials, st);
 }
 
 extern "C" {

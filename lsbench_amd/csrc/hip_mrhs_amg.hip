@@ -6,11 +6,10 @@
 // Every matrix of the hierarchy (A, P, R of a level, the dense coarse inverse) is streamed once for all KP
 // columns; a gather of row `col` is KP contiguous doubles.
 //
-// Rounding rule: each column's arithmetic is hip_amg.hip's amg_row<L> / amg_finish<MODE> exactly -- lane l of a
-// row's L takes entries offs[i] + l, + L, ... in storage order through the chain a = fma(val, x, a), the L sums
-// are folded by the xor butterfly L/2, ..., 1, and lane 0 applies the same finishing expression.  With the
-// level's own `lanes` a column of the block therefore has the BITS of the single-column cycle, whatever the
-// other columns hold; columns never mix, so a NaN stays in its column.
+// Rounding rule: each column's arithmetic is hip_amg.hip's amg_row<L> / amg_finish<MODE> exactly -- a row's sums are
+// block_row_product's (hip_mrhs_k.h), which per column is amg_row<L>'s chain and butterfly, and lane 0 applies the
+// same finishing expression.  With the level's own `lanes` a column of the block therefore has the BITS of the
+// single-column cycle, whatever the other columns hold; columns never mix, so a NaN stays in its column.
 //
 // Records: the SWEEP form with REC leaves, per workgroup, one record of 2 KP doubles -- b_c . y_c per column,
 // then b_c . b_c per column -- in the format k_mrhs_update_p reads (wg_sum_records<2 KP>: fixed order, no
@@ -53,28 +52,7 @@ __global__ __launch_bounds__(WG) void k_amg_csr_m(unsigned n, unsigned rows_per_
   for (unsigned base = ra; base < rb; base += SLOTS) {
     const unsigned r = base + slot;
     double a[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k++)
-      a[k] = 0.0;
-    if (r < rb) {
-      const int j1 = offs[r + 1];
-      for (int j = offs[r] + (int)l; j < j1; j += L) {
-        const double v = vals[j];
-        const size_t c = (size_t)cols[j] * H;
-#pragma unroll
-        for (int h = 0; h < H; h++) {
-          const d2v t = x2[c + h];
-          a[2 * h] = fma(v, t.x, a[2 * h]);
-          a[2 * h + 1] = fma(v, t.y, a[2 * h + 1]);
-        }
-      }
-    }
-#pragma unroll
-    for (int off = L >> 1; off > 0; off >>= 1) {
-#pragma unroll
-      for (int k = 0; k < KP; k++)
-        a[k] += __shfl_xor(a[k], off, 64);
-    }
+    block_row_product<L, KP>(offs, cols, vals, xin, r, r < rb, l, a);
     if (r < rb && l == 0) {
       const size_t o = (size_t)r * H;
 #pragma unroll
@@ -186,9 +164,8 @@ template <int KP, int MODE, bool REC>
 static void amg_csr_launch(const struct lsb_amg_mat *m, unsigned g, const double *xin, const double *b,
                            const double *minv, double *y, double *records, const struct lsb_mrhs_state *st,
                            hipStream_t s) {
-  LANES_DISPATCH(m->lanes, (k_amg_csr_m<L, KP, MODE, REC><<<g, WG, 0, s>>>(m->rows, round_up(div_up(m->rows, g), WG / L),
-                                                                       m->offs, m->cols, m->vals, xin, b, minv, y,
-                                                                       records, st)));
+  ROW_KERNEL_LAUNCH(m->lanes, (k_amg_csr_m<L, KP, MODE, REC>), g, s, m->rows, m->offs, m->cols, m->vals, xin, b, minv, y,
+                    records, st);
 }
 
 extern "C" {

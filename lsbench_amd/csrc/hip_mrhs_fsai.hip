@@ -14,9 +14,8 @@
 // its r where init, a warm start and a verify restart look for it.
 //
 // Blocks are hip_mrhs.hip's: interleaved, element (i, c) at i KP + c.  L lanes per row and one rounding rule, the
-// SpMM's: a lane's sum for column c is the chain a = fma(val_j, v_jc, a) over its entries j0 + l, j0 + l + L, ... in
-// that order, the L lane sums folded by the xor butterfly L/2, ..., 1.  A lane reads (col, val) once and gathers the
-// KP / 2 16-byte pairs of row `col`.
+// SpMM's: block_row_product (hip_mrhs_k.h).  Launch 3 calls it; launch 2 keeps the same loop and butterfly written
+// out, because what it gathers is not a stored block but r' = fma(-alpha, q, r).
 //
 // Gating as in hip_mrhs.hip: launch 2 decides per column from the status words and the records (every workgroup
 // the same decision, workgroup 0 writes) and may CLEAR `running`, which it never reads; launch 3 is a no-op once
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(WG) void k_mrhs_fsai_xr_gr(unsigned n, unsigned row
 #pragma unroll
     for (int k = 0; k < KP; k++)
       a[k] = 0.0;
-    if (row < rb) {
+    if (row < rb) { // block_row_product's loop and butterfly (hip_mrhs_k.h) with r' formed in the gather
       const int j0 = goffs[row], j1 = goffs[row + 1];
       for (int j = j0 + (int)l; j < j1; j += L) {
         const double v = gvals[j];
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(WG) void k_mrhs_fsai_gt_dots(unsigned n, unsigned r
     act[k] = st->c[k].status == LSB_STATUS_RUNNING;
     al[k] = act[k] ? st->c[k].alpha[parity] : 0.0;
   }
-  const d2v *t2 = (const d2v *)t, *q2 = (const d2v *)q;
+  const d2v *q2 = (const d2v *)q;
   double dot[2 * KP]; // r'.z per column, then r'.r'
 #pragma unroll
   for (int k = 0; k < 2 * KP; k++)
@@ -160,28 +159,7 @@ __global__ __launch_bounds__(WG) void k_mrhs_fsai_gt_dots(unsigned n, unsigned r
   for (unsigned base = ra; base < rb; base += SLOTS) {
     const unsigned row = base + slot;
     double a[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k++)
-      a[k] = 0.0;
-    if (row < rb) {
-      const int j0 = offs[row], j1 = offs[row + 1];
-      for (int j = j0 + (int)l; j < j1; j += L) {
-        const double v = vals[j];
-        const size_t c = (size_t)cols[j] * H;
-#pragma unroll
-        for (int h = 0; h < H; h++) {
-          const d2v tv = t2[c + h];
-          a[2 * h] = fma(v, tv.x, a[2 * h]);
-          a[2 * h + 1] = fma(v, tv.y, a[2 * h + 1]);
-        }
-      }
-    }
-#pragma unroll
-    for (int off = L >> 1; off > 0; off >>= 1) {
-#pragma unroll
-      for (int k = 0; k < KP; k++)
-        a[k] += __shfl_xor(a[k], off, 64);
-    }
+    block_row_product<L, KP>(offs, cols, vals, t, row, row < rb, l, a);
     if (stopped)
       return;
     if (row < rb && l == 0) {
@@ -218,16 +196,15 @@ template <int KP>
 static void xr_gr_launch(unsigned lanes, unsigned g, unsigned n, const int *goffs, const int *gcols,
                          const double *gvals, const double *p, const double *q, double *x, const double *r, double *t,
                          struct lsb_mrhs_state *st, int parity, const double *pq_parts, unsigned npq, hipStream_t s) {
-  LANES_DISPATCH(lanes, (k_mrhs_fsai_xr_gr<L, KP><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), goffs, gcols,
-                                                                   gvals, p, q, x, r, t, st, parity, pq_parts, npq)));
+  ROW_KERNEL_LAUNCH(lanes, (k_mrhs_fsai_xr_gr<L, KP>), g, s, n, goffs, gcols, gvals, p, q, x, r, t, st, parity, pq_parts,
+                    npq);
 }
 
 template <int KP>
 static void gt_dots_launch(unsigned lanes, unsigned g, unsigned n, const int *offs, const int *cols, const double *vals,
                            const double *t, const double *q, double *r, double *z, double *records,
                            const struct lsb_mrhs_state *st, int parity, hipStream_t s) {
-  LANES_DISPATCH(lanes, (k_mrhs_fsai_gt_dots<L, KP><<<g, WG, 0, s>>>(n, round_up(div_up(n, g), WG / L), offs, cols, vals,
-                                                                     t, q, r, z, records, st, parity)));
+  ROW_KERNEL_LAUNCH(lanes, (k_mrhs_fsai_gt_dots<L, KP>), g, s, n, offs, cols, vals, t, q, r, z, records, st, parity);
 }
 
 extern "C" {

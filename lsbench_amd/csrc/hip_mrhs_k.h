@@ -1,8 +1,8 @@
-// What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_amg.hip, hip_amg_cheb.hip,
-// hip_bcg.hip, hip_bcg_m.hip) share: the 16-byte pair
-// of the interleaved blocks and its store gated per column, the fixed-order reductions of their per-column
-// records, the verify round's decision and the launchers' dispatch on the batch width.  Included by those files
-// only, after hip_kcommon.h.
+// What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_fsai.hip, hip_mrhs_amg.hip,
+// hip_amg_cheb.hip, hip_bcg.hip, hip_bcg_m.hip) share: the 16-byte pair of the interleaved blocks and its store gated
+// per column, the fixed-order reductions of their per-column records, the verify round's decision, the row rule of
+// their CSR row kernels (block_row_product), the Gram triangle dealt over a row's lanes, and the launchers' dispatch
+// on the batch width and on the lanes per row.  Included by those files only, after hip_kcommon.h.
 #ifndef LSB_HIP_MRHS_K_H
 #define LSB_HIP_MRHS_K_H
 #include "hip_kcommon.h"
@@ -103,6 +103,44 @@ __device__ __forceinline__ void store_pairs(double *const (&v)[NB], const d2v (&
 }
 
 // --------------------------------------------------------------------------
+// THE ROW RULE of every CSR row kernel on blocks ("One rounding rule"): a[c] = (row `row` of the
+// matrix) . (column c of the block x), L lanes per row.  Lane l reads (col, val) of its entries j0 + l, j0 + l + L,
+// ... once each, in storage order, gathers the KP / 2 16-byte pairs of row `col` of x and runs the chain
+// a[c] = fma(val_j, x_jc, a[c]), written with explicit fma(); the L lane sums are folded by the xor butterfly
+// L/2, ..., 1, after which EVERY lane of the row's group holds the row's sums.  A lane whose row is out of range
+// (in_range == false) reads nothing, contributes zeros and takes part in the butterfly.  Whoever calls this has the
+// bits of k_spmm_csr -- of lsb_hip_solver_spmm_dev -- on the same operands.
+// --------------------------------------------------------------------------
+template <int L, int KP>
+__device__ __forceinline__ void block_row_product(const int *offs, const int *cols, const double *vals, const double *x,
+                                                  unsigned row, bool in_range, unsigned l, double (&a)[KP]) {
+  constexpr int H = KP / 2;
+  const d2v *x2 = (const d2v *)x;
+#pragma unroll
+  for (int k = 0; k < KP; k++)
+    a[k] = 0.0;
+  if (in_range) {
+    const int j0 = offs[row], j1 = offs[row + 1];
+    for (int j = j0 + (int)l; j < j1; j += L) {
+      const double v = vals[j];
+      const size_t c = (size_t)cols[j] * H;
+#pragma unroll
+      for (int h = 0; h < H; h++) {
+        const d2v t = x2[c + h];
+        a[2 * h] = fma(v, t.x, a[2 * h]);
+        a[2 * h + 1] = fma(v, t.y, a[2 * h + 1]);
+      }
+    }
+  }
+#pragma unroll
+  for (int off = L >> 1; off > 0; off >>= 1) {
+#pragma unroll
+    for (int k = 0; k < KP; k++)
+      a[k] += __shfl_xor(a[k], off, 64);
+  }
+}
+
+// --------------------------------------------------------------------------
 // What the two block-CG kernel files (hip_bcg.hip, hip_bcg_m.hip) share: a lane of their streaming launches owns whole
 // rows, and the Gram matrices leave a launch as records of their upper triangle.
 // --------------------------------------------------------------------------
@@ -150,6 +188,60 @@ template <int W> __device__ __forceinline__ void wg_sum_store(double (&v)[W], do
     dst[threadIdx.x] = (sred[threadIdx.x] + sred[W + threadIdx.x]) + (sred[2 * W + threadIdx.x] + sred[3 * W + threadIdx.x]);
 }
 
+// The DEALT TRIANGLE of the row kernels that carry Gram sums (k_bcg_spmm, k_bcgm_gt_gram).  After the row rule's
+// butterfly every lane of a row's group holds the row, so the T = tri_of(KP) entries of the upper triangle of u^T v are
+// dealt over the group's L lanes: lane l takes the entries t = l, l + L, ... and keeps ceil(T / L) running sums, not T.
+__host__ __device__ constexpr int tri_dealt(int KP, int L) { return (tri_of(KP) + L - 1) / L; }
+
+// one row's u_i v_j into this lane's entries of NT triangles, v = v[0], v[1], ... (KP doubles each)
+template <int L, int KP, int NT, int NA>
+__device__ __forceinline__ void tri_dealt_fma(const double (&u)[KP], const double *const (&v)[NT], unsigned l,
+                                              double (&g)[NT][NA]) {
+  static_assert(NA == tri_dealt(KP, L), "a lane's share of the triangle");
+#pragma unroll
+  for (int i = 0; i < KP; i++) {
+#pragma unroll
+    for (int j = i; j < KP; j++) {
+      const int t = tri_at(KP, i, j); // a constant after unrolling
+#pragma unroll
+      for (int q = 0; q < NT; q++) { // (a select, no branch: every lane forms the sum, the entry's owner keeps it)
+        const double s = fma(u[i], v[q][j], g[q][t / L]);
+        g[q][t / L] = (unsigned)(t % L) == l ? s : g[q][t / L];
+      }
+    }
+  }
+}
+
+// the workgroup's sums of NT dealt triangles -> one record of NT T doubles at dst, triangle after triangle: lanes of a
+// wave with the same l hold the same entries (butterfly 32, ..., L), the four waves through LDS in fixed order.
+// sred: 4 NT T doubles, not in use when the workgroup gets here.
+template <int L, int KP, int NT, int NA>
+__device__ __forceinline__ void tri_dealt_store(double (&g)[NT][NA], double *sred, double *dst) {
+  constexpr int T = tri_of(KP), W = NT * T;
+#pragma unroll
+  for (int k = 0; k < NA; k++) {
+#pragma unroll
+    for (int off = 32; off >= L; off >>= 1) {
+#pragma unroll
+      for (int q = 0; q < NT; q++)
+        g[q][k] += __shfl_xor(g[q][k], off, 64);
+    }
+  }
+  const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (lane < L) {
+#pragma unroll
+    for (int k = 0; k < NA; k++)
+      if (k * L + (int)lane < T) {
+#pragma unroll
+        for (int q = 0; q < NT; q++)
+          sred[wave * W + q * T + k * L + lane] = g[q][k];
+      }
+  }
+  __syncthreads();
+  if (tid < W)
+    dst[tid] = (sred[tid] + sred[W + tid]) + (sred[2 * W + tid] + sred[3 * W + tid]);
+}
+
 // --------------------------------------------------------------------------
 // host helpers of the launchers.  kp: 2, 4 or 8.
 // --------------------------------------------------------------------------
@@ -180,5 +272,11 @@ static inline unsigned sweep_grid(unsigned n, unsigned kp) { return lsb_k_blas1_
     default: { constexpr int KP = 8; CALL; } break;                            \
     }                                                                          \
   } while (0)
+
+// The launch of a CSR row kernel on blocks: g workgroups, L lanes per row (KERNEL, in parentheses, sees the count as
+// the constant L), the n rows dealt in contiguous ranges that are a multiple of the WG / L rows a workgroup takes per
+// trip.  The kernel's first two parameters are n and that range; the rest follow.
+#define ROW_KERNEL_LAUNCH(lanes, KERNEL, g, s, n, ...)                                                                 \
+  LANES_DISPATCH(lanes, (KERNEL<<<(g), WG, 0, (s)>>>((n), round_up(div_up((n), (g)), WG / L), __VA_ARGS__)))
 
 #endif

@@ -98,7 +98,7 @@ void drop_graphs(lsb_hip_solver *sv) {
   graph_drop(&sv->graphs);
   graph_drop(&sv->rich_graphs);
   for (int k = 0; k < 3; k++)
-    graph_drop(&sv->mr[k].g), graph_drop(&sv->bk[k].g);
+    graph_drop(&sv->mr[k].blk.g), graph_drop(&sv->bk[k].blk.g);
 }
 
 /* ---- the loop --------------------------------------------------------------------------------------------------

@@ -14,7 +14,9 @@
  *   hip_gmres_drv.c  GMRES(m) driver
  *   hip_bicgstab_drv.c  BiCGSTAB driver
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
- *   hip_mrhs_drv.c   several right-hand sides: multi-RHS Jacobi- and AMG-PCG on a CSR SpMM
+ *   hip_block.c      interleaved blocks of right-hand sides, what their two drivers share: the service rules, the work
+ *                    area (struct block_work), Z = M^-1 R on a block, the enqueue and host-buffer wrappers
+ *   hip_mrhs_drv.c   several right-hand sides: independent PCG recurrences (Jacobi, AMG, FSAI) on a CSR SpMM
  *   hip_bcg_drv.c    block-CG proper: one Krylov space for a block of right-hand sides (second half: under FSAI and AMG)
  * Nothing here is part of the C-ABI (include/lsbench_hip.h).
  */
@@ -66,6 +68,27 @@ struct graph_cache {
   int next;
 };
 
+/* What a work area on interleaved blocks of kp right-hand sides has in common, whichever driver owns it (hip_block.c:
+ * block_work_slab, block_work_z, block_work_free; the owners: struct mrhs_work, struct blockcg_work) */
+struct amg_vecs;
+struct block_work {
+  unsigned kp;           /* 0: not allocated */
+  char *mem;             /* the slab: the five blocks, then z and t where it holds them, then the owner's records and
+                            state */
+  double *b, *x, *p, *q; /* n kp doubles each */
+  union {
+    double *r; /* the residual block of independent recurrences */
+    double *w; /* block-CG: the factor W of R = W sigma */
+  };
+  /* z = M^-1 (.) as a block of its own, and what forming it needs.  FSAI: z and t = G (.) are two blocks, of the slab
+   * or -- block_work_z -- of zmem.  AMG: z is the head of amg_mem, the cycle's vectors of every level at this width
+   * (amg_block_vecs, av; level 0: b and out are the r and z of the call). */
+  double *z, *t;
+  char *zmem, *amg_mem;
+  struct amg_vecs *av;
+  struct graph_cache g; /* keyed on the count: the iteration touches these buffers only */
+};
+
 /* Rows that reference other shards' columns sit in units [0,first) and [last,count) of a layout (row
  * blocks, slices); the units in between can start before the halo has arrived (ok = 0: not separable) */
 struct halo_split {
@@ -88,7 +111,7 @@ enum pcg_form {
 
 /* The vectors of one level of the AMG V-cycle: right-hand side, result, the other smoothing buffer, the residual, the
  * Chebyshev smoother's direction (NULL under l1-Jacobi).  double in the fp64 cycle (one column: amg_dev.vec; blocks of
- * kp: mrhs_work.av), float in the fp32 cycle.  Level 0 under fp64: b and out are NULL, the caller's r and z stand in.
+ * kp: block_work.av), float in the fp32 cycle.  Level 0 under fp64: b and out are NULL, the caller's r and z stand in.
  * A level smoothed by multicolour Gauss-Seidel keeps its iterate in out alone and does not touch tmp */
 struct amg_vecs {
   void *b, *out, *tmp, *r, *d;
@@ -316,41 +339,29 @@ struct lsb_hip_solver {
    * and the partial count of its update sweep */
   struct graph_cache rich_graphs;
   unsigned rich_nrr;
-  /* several right-hand sides (allocated on first use, per batch width kp = 2, 4, 8; hip_mrhs_drv.c) */
+  /* Interleaved blocks of right-hand sides, per width kp = 2, 4, 8 and allocated on first use.  Two drivers run on
+   * them -- independent recurrences (hip_mrhs_drv.c) and block-CG (hip_bcg_drv.c) -- and each keeps its OWN work
+   * areas: their graph caches are keyed on the iteration count alone, and a caller may alternate the two on one
+   * solver.  What an area of either has in common is struct block_work; its records, its state and its hints lie
+   * beside it in the driver's struct. */
   struct mrhs_work {
-    unsigned kp;                 /* 0: not allocated */
-    char *mem;                   /* one allocation: the five interleaved blocks and the partial records */
-    double *b, *x, *r, *p, *q;   /* n kp doubles each */
+    struct block_work blk;
     double *parts_pq, *parts2;   /* records of the SpMM (kp wide) and of the sweeps (2 kp wide) */
     double *parts_bb;            /* a batch from an initial guess: the records of b.b (2 kp wide), on first use */
     struct lsb_mrhs_state *st;
-    /* an AMG solver's: z and the cycle's vectors of every level as blocks of this width (level 0: b and out
-     * are the r and z of the call) */
-    char *amg_mem;
-    double *z;
-    struct amg_vecs *av; /* (amg_block_vecs) */
-    double *t; /* an FSAI solver's (opts.fsai_blocks): t = G r; it and z are two more blocks of mem */
     unsigned hint[LSB_MAX_CORRECTIONS + 1]; /* launches the previous batch's solve and restarts took */
-    struct graph_cache g;        /* its own graph cache, keyed on the count: the iteration touches these buffers only */
   } mr[3];
   struct lsb_mrhs_state *mr_hst; /* pinned, 2 slots */
-  unsigned mr_lanes;             /* lanes per row of its SpMM */
-  unsigned mr_fs_lanes;          /* FSAI on blocks: lanes per row of G and of G^T, 0 = each matrix's own */
-  /* block-CG proper (allocated on first use, per width kp = 2, 4, 8; hip_bcg_drv.c) */
+  /* lanes per row of the SpMM on blocks (never 0 once read) and, FSAI on blocks, of G and of G^T (0 = each matrix's
+   * own): read when the solver first runs a block, whichever driver that is (block_work_slab) */
+  unsigned mr_lanes, mr_fs_lanes;
   struct blockcg_work {
-    unsigned kp;               /* 0: not allocated */
-    char *mem;                 /* one allocation: the five interleaved blocks, the two record arrays, the state */
-    double *b, *x, *w, *p, *q; /* n kp doubles each */
+    struct block_work blk;
     double *rec_spmm, *rec_pass; /* records of the SpMM (LSB_MAX_PARTIALS) and of the passes (LSB_STREAM_GRID_CAP) */
+    double *rec_gram; /* solve_block_precond under FSAI: the records of the row kernel that forms the Gram sums
+                         (LSB_MAX_PARTIALS), behind z and t in blk.zmem; under AMG they are a streaming pass's (rec_pass) */
     struct lsb_blockcg_state *st;
-    /* solve_block_precond under FSAI or AMG, on first use: z = M^-1 (.) as a block.  FSAI: z, t = G w and the records
-     * of the row kernel that forms the Gram sums (LSB_MAX_PARTIALS) are pmem; AMG: z and the cycle's vectors are
-     * amg_mem (amg_block_vecs, av), and the Gram sums are a streaming pass's (rec_pass) */
-    char *pmem, *amg_mem;
-    double *z, *t, *rec_gram;
-    struct amg_vecs *av;
     unsigned hint;             /* SpMMs the previous block of this width took */
-    struct graph_cache g;      /* keyed on the count: the iteration touches these buffers only */
   } bk[3];
   struct lsb_blockcg_state *bk_hst; /* pinned, 2 slots; slot 0 keeps the last block's final state */
   hipEvent_t ev_poll[2], ev_vec, ev_halo;
@@ -516,7 +527,7 @@ LSB_INTERNAL void precond_shard_amg(struct shard *s, const int *offs, const int 
 LSB_INTERNAL void amg_finish_setup(struct shard *s); /* behind d_zfull: level 0's two vectors out of the slab */
 LSB_INTERNAL void amg_free(struct shard *s);
 /* One application of the V-cycle, described on the caller's stack: z = M^-1 r in the solver's precision (kp = 0: one
- * column, vec = a->vec) or Z = M^-1 R on interleaved blocks of kp columns (fp64; vec = the mrhs_work's).  r and z are
+ * column, vec = a->vec) or Z = M^-1 R on interleaved blocks of kp columns (fp64; vec = the block_work's).  r and z are
  * fp64 and may be anywhere.  records != NULL (blocks): where the launch that writes Z leaves (r_c . z_c, r_c . r_c) of
  * every column, and their number.  The gate of the launches: st (one column) or mst (blocks), NULL: always run. */
 struct amg_run {
@@ -557,17 +568,47 @@ LSB_INTERNAL void lsb_k_rich_restart(unsigned n, const double *b, const double *
                                      unsigned *npartials, void *stream);
 LSB_INTERNAL void lsb_k_rich_restart_state(struct lsb_pcg_state *st, const double *parts, unsigned nparts, int more,
                                            void *stream);
+/* hip_block.c: what the two drivers on interleaved blocks share */
+/* the service rules: the SpMM on blocks; the solves on blocks (the SpMM's, less an AMG cycle smoothed by multicolour
+ * Gauss-Seidel); whether z = M^-1 r is a block of its own there (AMG, FSAI) or the diagonal's */
+LSB_INTERNAL int block_spmm_serves(const lsb_hip_solver *sv);
+LSB_INTERNAL int block_serves(const lsb_hip_solver *sv);
+LSB_INTERNAL int block_fsai(const lsb_hip_solver *sv);
+LSB_INTERNAL int block_zblock(const lsb_hip_solver *sv);
+LSB_INTERNAL unsigned block_width(unsigned nrhs); /* 2, 4 or 8: what nrhs <= 8 columns run at */
+LSB_INTERNAL unsigned block_fsai_lanes(const lsb_hip_solver *sv, const struct fsai_csr *c); /* of G or of G^T */
+/* 1: a call on nrhs columns (max_nrhs != 0: no more than that) with leading dimensions lda, ldb is refused */
+LSB_INTERNAL int block_args_bad(const lsb_hip_solver *sv, unsigned nrhs, unsigned max_nrhs, const void *a, size_t lda,
+                                const void *b, size_t ldb);
+/* The slab of a work area, zeroed: nblk blocks of n kp doubles (the five; 7: z and t behind them), then `behind`
+ * bytes of the owner's, whose address it returns.  The first slab of a solver reads the lanes per row. */
+LSB_INTERNAL char *block_work_slab(lsb_hip_solver *sv, struct block_work *w, unsigned kp, unsigned nblk, size_t behind);
+/* z where the slab does not hold it, zeroed.  FSAI: z, t and `behind` bytes of the owner's (returned) in zmem.
+ * AMG: the cycle's block vectors with z at their head; behind must be 0, returns NULL. */
+LSB_INTERNAL char *block_work_z(lsb_hip_solver *sv, struct block_work *w, size_t behind);
+LSB_INTERNAL void block_work_free(struct block_work *w);
+/* T = G R by the SpMM's rule, un-gated (FSAI).  Its records of r_c . t_c, which nobody reads, go into rec: kp
+ * LSB_MAX_PARTIALS doubles that no launch still in front of its next writer reads. */
+LSB_INTERNAL void block_fsai_g(const lsb_hip_solver *sv, const struct block_work *w, const double *r, double *rec);
+/* Z = M^-1 R of every column into w->z, un-gated and without records: FSAI's two products (rec: as above), or one
+ * V-cycle */
+LSB_INTERNAL void block_zapply(const lsb_hip_solver *sv, const struct block_work *w, const double *r, double *rec);
+/* What run_loop enqueues on a work area: `iters` launches a linear chain of that many iterations on internal buffers,
+ * so under opts.use_graph its graphs are keyed on the count alone (w->g) */
+struct block_enq {
+  lsb_hip_solver *sv;
+  struct block_work *w;
+  run_enqueue_fn *iters;
+  void *ctx;
+};
+LSB_INTERNAL void block_enqueue(void *block_enq, int iters);
+/* A _dev entry point on host buffers: B in, the call, X out -- whatever it answered (x_always) or only where it
+ * answered 0.  The caller has checked the arguments and the service rule. */
+typedef int block_dev_fn(lsb_hip_solver *, unsigned, const double *, size_t, double *, size_t, struct lsb_hip_result *);
+LSB_INTERNAL int block_solve_host(block_dev_fn *dev, int x_always, lsb_hip_solver *sv, unsigned nrhs, const double *B,
+                                  size_t ldb, double *X, size_t ldx, struct lsb_hip_result *res);
 /* hip_mrhs_drv.c */
 LSB_INTERNAL void mrhs_free(lsb_hip_solver *sv); /* before the shards go */
-/* what the block-CG driver shares with it: solve_multi's service rule under the diagonal preconditioners, the width a
- * block of nrhs <= 8 columns runs at, and the lanes per row of the SpMM (those of lsb_hip_solver_spmm_dev) */
-LSB_INTERNAL int mrhs_serves_diag(const lsb_hip_solver *sv);
-LSB_INTERNAL unsigned mrhs_batch_width(unsigned nrhs);
-LSB_INTERNAL unsigned mrhs_spmm_lanes(lsb_hip_solver *sv);
-/* ... and with its preconditioned half: solve_multi's service rule where z is a block of its own (AMG in fp64 under
- * l1-Jacobi or Chebyshev smoothing, FSAI with opts.fsai_blocks), the lanes per row of FSAI's G (gt = 0) or G^T */
-LSB_INTERNAL int mrhs_serves_zblock(const lsb_hip_solver *sv);
-LSB_INTERNAL unsigned mrhs_fsai_lanes(lsb_hip_solver *sv, int gt);
 /* hip_bcg_drv.c */
 LSB_INTERNAL void blockcg_free(lsb_hip_solver *sv); /* before the shards go */
 

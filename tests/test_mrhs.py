@@ -291,6 +291,89 @@ def test_spmm_every_lane_count(hip, lanes, matrix_path, monkeypatch):
     s.destroy()
 
 
+def _row_rule(offs, cols, vals, X, rows, L):
+    """The row rule of the CSR row kernels on blocks (block_row_product, hip_mrhs_k.h) restated in exact arithmetic:
+    lane l of a row's L takes the entries l, l + L, ... of the row in storage order through a = fma(val, x, a) --
+    the exact product and sum rounded once -- and the L lane sums are folded by the xor butterfly L/2, ..., 1 as
+    fp64 additions.  -> (len(rows), ncols) float64"""
+    from fractions import Fraction as F
+    offs, cols, vals = [np.asarray(a).tolist() for a in (offs, cols, vals)]
+    Xf = [[F(v) for v in row] for row in X.tolist()]
+    out = np.empty((len(rows), X.shape[1]))
+    for k, r in enumerate(rows):
+        j0, j1 = offs[r], offs[r + 1]
+        vf = {j: F(vals[j]) for j in range(j0, j1)}
+        for c in range(X.shape[1]):
+            lane = []
+            for l in range(L):
+                a = 0.0
+                for j in range(j0 + l, j1, L):
+                    a = float(vf[j] * Xf[cols[j]][c] + F(a))
+                lane.append(a)
+            off = L // 2
+            while off:
+                lane = [lane[i] + lane[i ^ off] for i in range(L)]
+                off //= 2
+            out[k, c] = lane[0]
+    return out
+
+
+def _rule_rows(S):
+    """the rows the restatement covers: the first 300, the last 300 (the ragged last workgroup), the 50 longest"""
+    n, ln = S.shape[0], np.diff(S.indptr)
+    groups = [np.arange(min(300, n)), np.arange(max(n - 300, 0), n), np.argsort(-ln, kind="stable")[:50]]
+    assert all(len(g) for g in groups)
+    return np.unique(np.concatenate(groups))
+
+
+def _check_spmm_is_the_row_rule(hip, M, kw, S, lanes, nrhs_list, seed):
+    import torch
+    # the order the shard's CSR keeps a row in (lsb_operator.c: mirrored entries by ascending row, then the row's own
+    # in the file's order) is ascending column order for these operators: the library's own operator says so
+    S = S.tocsr().copy()
+    S.sort_indices()
+    So = hip.lsb_csr_copy_base0(M) if kw else hip.lsb_csr_symmetrize_upper(M)
+    assert np.array_equal(So.offs, S.indptr) and np.array_equal(So.cols, S.indices)
+    assert So.vals.tobytes() == S.data.tobytes()
+    o = hip.default_opts(**kw)
+    s = hip.Solver(M, o)
+    assert o.reorder == 0 and s.padded == 0  # internal rows are the caller's rows
+    n, rows = S.shape[0], _rule_rows(S)
+    for nrhs in nrhs_list:
+        X = np.random.default_rng(seed + nrhs).standard_normal((n, nrhs))
+        d_X = _block(X, n + 7)
+        d_Y = torch.full((nrhs, n + 3), -7.0, dtype=torch.float64, device="cuda:0")
+        d_Y2 = torch.full((nrhs, n + 3), -7.0, dtype=torch.float64, device="cuda:0")
+        s.spmm_dev(d_X, d_Y)
+        s.spmm_dev(d_X, d_Y2)
+        assert torch.equal(d_Y, d_Y2)  # the whole of Y, run to run
+        Y = _host(d_Y, n)
+        want = _row_rule(S.indptr, S.indices, S.data, X, rows, lanes)
+        differ = int(np.count_nonzero(Y[rows] != want))
+        print("lanes", lanes, "nrhs", nrhs, "rows", len(rows), "elements that differ", differ)
+        assert Y[rows].tobytes() == want.tobytes()
+    s.destroy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nrhs", [2, 3, 8])
+@pytest.mark.parametrize("lanes", [2, 4, 8, 16, 32, 64])
+def test_spmm_has_the_bits_of_the_row_rule(hip, lanes, nrhs, matrix_path, monkeypatch):
+    """lsb_hip_solver_spmm_dev, bit for bit, against the one written rule (_row_rule) for every lanes-per-row form, on
+    rows of 2 .. 72 entries (shorter and longer than L), at widths 2, 4 (one padded column) and 8."""
+    monkeypatch.setenv("LSBENCH_HIP_MRHS_LANES", str(lanes))
+    M, kw, S = _spmm_operators(hip, matrix_path)["xn3b_A_18"]
+    _check_spmm_is_the_row_rule(hip, M, kw, S, lanes, [nrhs], 300)
+
+
+@pytest.mark.gpu
+def test_spmm_has_the_bits_of_the_row_rule_on_two_rows(hip, matrix_path, monkeypatch):
+    """... and on the smallest operator: two rows of two entries under four lanes, one workgroup with two rows in it"""
+    monkeypatch.setenv("LSBENCH_HIP_MRHS_LANES", "4")
+    M, kw, S = _spmm_operators(hip, matrix_path)["two_rows"]
+    _check_spmm_is_the_row_rule(hip, M, kw, S, 4, [2, 3, 8], 400)
+
+
 def _check_against_oracle(res, X, B, orc, tol, cols=None):
     for c in (range(B.shape[1]) if cols is None else cols):
         xo, ito, relo, sto = orc[c]
