@@ -131,9 +131,11 @@ static void bcg_enqueue_iter(lsb_hip_solver *sv, double *d_x, int parity) {
   }
 }
 
-/* what run_loop enqueues: `it` counts the iterations enqueued in this solve (its parity picks the copy of rho) */
+/* what run_loop enqueues and what a restart needs: `it` counts the iterations enqueued in this solve (its parity
+ * picks the copy of rho) */
 struct bcg_enq {
   lsb_hip_solver *sv;
+  const double *d_b;
   double *d_x;
   unsigned it;
 };
@@ -145,15 +147,35 @@ static void bcg_enqueue(void *ctx, int count) {
 
 /* Enqueue iterations until the device state leaves RUNNING; the final state lands in bcg_hst[0] (whose c.iters
  * the caller cleared for the solve proper).  *hint: what this stretch of the previous solve took. */
-static void bcg_run(lsb_hip_solver *sv, struct bcg_enq *e, unsigned *hint) {
+static void bcg_run(void *ctx, unsigned *hint) {
+  lsb_hip_solver *sv = ((struct bcg_enq *)ctx)->sv;
   const struct run_loop r = {.name = "BiCGSTAB", .d_state = sv->bcg[0].st, .h_state = sv->bcg_hst,
                              .state_bytes = sizeof(struct lsb_bcg_state),
                              .stop_off = offsetof(struct lsb_bcg_state, c.status),
                              .progress_off = offsetof(struct lsb_bcg_state, c.iters),
-                             .enqueue = bcg_enqueue, .ctx = e, .chunk = bcg_chunk(sv), .cap = -1,
+                             .enqueue = bcg_enqueue, .ctx = ctx, .chunk = bcg_chunk(sv), .cap = -1,
                              .what_hinted = "poll of a hinted BiCGSTAB solve",
                              .what_poll = "poll of the BiCGSTAB solve", .what_drain = "drain after the BiCGSTAB solve"};
   run_loop(sv, &r, hint);
+}
+
+/* the restart of run_restarting: r = b - Op x, r^ = p = r, x kept */
+static void bcg_restart(void *ctx, int more) {
+  const struct bcg_enq *e = ctx;
+  lsb_hip_solver *sv = e->sv;
+  const int multi = sv->multi;
+  gather_x(sv, e->d_x);
+  EACH(i, s, w) {
+    spmv_shard(s, s->d_pfull, s->d_q, NULL, NULL, NULL, NULL);
+    lsb_k_bcg_restart(s->n, e->d_b + (s->row_begin - sv->row_first), s->d_q, DINV(s), s->d_r, w->rhat, w->p,
+                      s->d_pfull + s->row_begin, s->d_parts2, &w->np2, g_stream);
+    if (multi)
+      lsb_k_reduce_final(s->d_parts2, w->np2, 1, sv->bcg_red + (size_t)i * BCG_RED + 4, 0, NULL, g_stream);
+  }
+  bcg_allreduce(sv, 4, 1);
+  EACH(i, s, w)
+    lsb_k_bcg_restart_state(w->st, multi ? sv->bcg_red + (size_t)i * BCG_RED + 4 : s->d_parts2,
+                            multi ? 1u : w->np2, more, g_stream);
 }
 
 int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res) {
@@ -175,43 +197,12 @@ int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struc
   struct lsb_hip_result r;
   memset(&r, 0, sizeof r);
   r.true_relres = -1.0;
-  struct bcg_enq enq = {.sv = sv, .d_x = d_x};
-  unsigned nverify = 0;
+  struct bcg_enq enq = {.sv = sv, .d_b = d_b, .d_x = d_x};
+  const struct restart_run v = {.run = bcg_run, .restart = bcg_restart, .ctx = &enq, .d_state = sv->bcg[0].st,
+                                .h_state = hst, .state_bytes = sizeof hst[0],
+                                .what_drain = "recomputed residual of the BiCGSTAB solve"};
   hst[0].c.iters = 0;
-  for (int round = 0;; round++) {
-    bcg_run(sv, &enq, hint_slot(sv->hint_iters, round));
-    if (!(sv->verify_run && hst[0].c.status == LSB_STATUS_CONVERGED && sv->tol_run > 0.0 && hst[0].c.bb > 0.0))
-      break;
-    /* "converged" is reported only for the residual RECOMPUTED from x; where that one misses the
-     * tolerance the iteration restarts on it (r = b - Op x, r^ = p = r, x kept), LSB_MAX_CORRECTIONS
-     * times at the most, inside the timed region */
-    EACH(i, s, w) {
-      (void)w;
-      LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + s->row_begin, d_x + (s->row_begin - sv->row_first),
-                                 (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice, g_stream));
-    }
-    if (multi)
-      exchange_p(sv, 0);
-    EACH(i, s, w) {
-      const size_t o = s->row_begin - sv->row_first;
-      spmv_shard(s, s->d_pfull, s->d_q, NULL, NULL, NULL, NULL);
-      lsb_k_bcg_restart(s->n, d_b + o, s->d_q, DINV(s), s->d_r, w->rhat, w->p, s->d_pfull + s->row_begin,
-                        s->d_parts2, &w->np2, g_stream);
-      if (multi)
-        lsb_k_reduce_final(s->d_parts2, w->np2, 1, sv->bcg_red + (size_t)i * BCG_RED + 4, 0, NULL, g_stream);
-    }
-    bcg_allreduce(sv, 4, 1);
-    EACH(i, s, w)
-      lsb_k_bcg_restart_state(w->st, multi ? sv->bcg_red + (size_t)i * BCG_RED + 4 : s->d_parts2,
-                              multi ? 1u : w->np2, r.corrections < LSB_MAX_CORRECTIONS, g_stream);
-    nverify++;
-    LSB_CHK_HIP(hipMemcpyAsync(&hst[0], sv->bcg[0].st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream));
-    drain_stream(sv, "recomputed residual of the BiCGSTAB solve");
-    r.true_relres = sqrt(hst[0].c.rr / hst[0].c.bb);
-    if (hst[0].c.status != LSB_STATUS_RUNNING)
-      break;
-    r.corrections++;
-  }
+  const unsigned nverify = run_restarting(sv, &v, &r);
   check_aux_status(sv, "BiCGSTAB solve");
   result_from_state(&r, &hst[0].c);
   r.spmvs = (unsigned)hst[0].nspmv + nverify;

@@ -60,14 +60,7 @@ int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
   }
   for (int cycle = 0;; cycle++) {
     if (cycle > 0) { /* ax = Op x for the restart residual */
-      EACH(i, s, w) {
-        (void)w;
-        LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + s->row_begin, d_x + (s->row_begin - sv->row_first),
-                                   (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice,
-                                   g_stream));
-      }
-      if (sv->multi)
-        exchange_p(sv, 0); /* not tied to a PCG state */
+      gather_x(sv, d_x);
       EACH(i, s, w) spmv_shard(s, s->d_pfull, w->ax, NULL, NULL, NULL, NULL);
     }
     EACH(i, s, w) {

@@ -1,7 +1,8 @@
 /*
  * Jacobi-PCG on the device-resident state: the iteration forms a solver may run (one is chosen at
- * creation, pcg_choose_form), what each enqueues per iteration, and the solve around them: one run through the
- * host loop the drivers share (hip_run.c; DESIGN.md section 4, "Host loop"), then the correction runs.
+ * creation, pcg_choose_form), what each enqueues per iteration, one run through the host loop the drivers share
+ * (hip_run.c; DESIGN.md section 4, "Host loop"), and the driver's entry point pcg_solve_dev (hip_solve.c has the
+ * solve around it).
  */
 #define _GNU_SOURCE
 #include "hip_solver.h"
@@ -51,7 +52,7 @@ enum pcg_form pcg_choose_form(const lsb_hip_solver *sv) {
       s->row_begin == 0 && s->n == s->n_glob && o->precond == LSB_PRECOND_JACOBI && !getenv("LSBENCH_HIP_NO_FUSE_PX"))
     return PCG_COL; /* (event-timed too: the sample brackets the launch that carries the SpMV) */
   /* (not while SpMV launches are being event-timed: the fused launch has no SpMV of its own to
-   * bracket, and solve_core reads the sample events) */
+   * bracket, and pcg_run reads the sample events) */
   return s->variant == LSB_SPMV_SUBWAVE && o->sample_spmv <= 0 ? PCG_SUBWAVE : PCG_CLASSIC;
 }
 
@@ -550,81 +551,6 @@ void tune_blas1_nt(lsb_hip_solver *sv) {
   lsb_hip_free(d_b), lsb_hip_free(d_x);
 }
 
-/* x into every shard's gather vector, halos exchanged: what a product with the operator starts from.  The caller
- * has switched the direct xGMI path off.  Overwrites the search-direction vector. */
-static void gather_x(lsb_hip_solver *sv, const double *d_x) {
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    const size_t o = s->row_begin - sv->row_first;
-    LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + s->row_begin, d_x + o, (size_t)s->n * sizeof(double),
-                               hipMemcpyDeviceToDevice, g_stream));
-  }
-  exchange_p(sv, 0);
-}
-
-/* q = S x in every shard, with the fp64 values whatever opts.precision says */
-static void op_exact(lsb_hip_solver *sv, const double *d_x) {
-  gather_x(sv, d_x);
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    spmv_shard_exact(s, s->d_pfull, s->d_q, s->d_pfull + s->row_begin, s->d_parts_pq, &s->npq, NULL);
-  }
-}
-
-/* ||b - S x||^2 recomputed from x with the solver's operator, communicating
- * WITHOUT the direct xGMI path; overwrites the search-direction vector and
- * leaves S x - b in every shard's q.  twice: formed off the CSR arrays as in twice the working precision
- * (k_resid_csr2) instead of by the solver's fp64 SpMV -- what opts.verify behind a warm start reports. */
-static double resid2(lsb_hip_solver *sv, const double *d_b, const double *d_x, int twice) {
-  static const double minus_one = -1.0;
-  const int on = sv->p2p_on, halo = sv->p2p_halo;
-  double rr = 0.0;
-  sv->p2p_on = sv->p2p_halo = 0;
-  for (int i = 0; i < sv->nshard; i++)
-    LSB_CHK_HIP(hipMemcpyAsync(sv->sh[i].d_scal + 5, &minus_one, sizeof(double), hipMemcpyHostToDevice,
-                               g_stream));
-  if (twice)
-    gather_x(sv, d_x);
-  else
-    op_exact(sv, d_x);
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    const size_t o = s->row_begin - sv->row_first;
-    unsigned np = 0;
-    if (twice)
-      lsb_k_resid_csr2(s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->lanes, s->d_pfull, d_b + o, s->d_q,
-                       s->d_parts_pq, &np, g_stream);
-    else {
-      lsb_k_axpy(s->n, s->d_scal + 5, d_b + o, s->d_q, g_stream); /* q = S x - b */
-      lsb_k_dot(s->n, s->d_q, s->d_q, s->d_parts_pq, &np, g_stream);
-    }
-    lsb_k_reduce_final(s->d_parts_pq, np, 1, s->d_scal + 4, 0, NULL, g_stream);
-  }
-  allreduce_scal(sv, 4, 1, 0);
-  LSB_CHK_HIP(hipMemcpyAsync(&rr, sv->sh[0].d_scal + 4, sizeof rr, hipMemcpyDeviceToHost,
-                             g_stream));
-  drain_stream(sv, "true residual");
-  sv->p2p_on = on, sv->p2p_halo = halo;
-  return rr;
-}
-double true_resid2(lsb_hip_solver *sv, const double *d_b, const double *d_x) { return resid2(sv, d_b, d_x, 0); }
-
-int lsb_hip_solver_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
-                             struct lsb_hip_result *res) {
-  if (!lsb_initialized)
-    return 1;
-  if (!sv || !d_b || !d_x)
-    return 2;
-  if (!sv->d_perm)
-    return solve_core(sv, d_b, d_x, res);
-  /* b' = Q b ; solve Q S Q^T x' = b' ; x = Q^T x'   (src/cusparse.c:177,204) */
-  lsb_k_perm_gather(sv->n_here, sv->d_perm, d_b, sv->d_bp, g_stream);
-  const int rc = solve_core(sv, sv->d_bp, sv->d_xp, res);
-  lsb_k_perm_scatter(sv->n_here, sv->d_perm, sv->d_xp, d_x, g_stream);
-  drain_stream(sv, "un-permuting x");
-  return rc;
-}
-
 /* ------------------------------------------------------------------------ */
 /* launch-bound operators: one persistent launch per solve (hip_persist.hip)   */
 /* ------------------------------------------------------------------------ */
@@ -764,8 +690,7 @@ static void pcg_enqueue(void *ctx, int cnt) {
 
 /* One CG run from x0 = 0 to sv->tol_run; `round` = 0 for the solve proper, k for
  * its k-th correction run. */
-static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res,
-                   int round) {
+int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res, int round) {
   unsigned *hint = hint_slot(sv->hint_iters, round);
   const int chunk = sv->o.check_every > 0 ? (sv->o.check_every + 1) & ~1 : auto_chunk(sv);
   memset(sv->samp_skip, 0, sizeof sv->samp_skip);
@@ -850,104 +775,17 @@ static int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct ls
   return 0;
 }
 
-/* what an inner solve on fp32-rounded values is asked for at the least (0: the values are exact) */
-static double mixed_floor_tol(const lsb_hip_solver *sv) {
-  int inexact = 0;
-  for (int i = 0; i < sv->nshard; i++)
-    inexact |= sv->sh[i].mixed && !sv->sh[i].exact32;
-  return inexact ? LSB_MIXED_INNER_TOL : 0.0;
-}
-
-/* One run of the solver's own driver from x0 = 0 to `tol` relative to ||d_b||, nothing recomputed: sv->tol_run is
- * the tolerance every driver stops on, sv->verify_run = 0 keeps GMRES, BiCGSTAB and Richardson from restarting on
- * a recomputed residual of their own.  `round`: which of PCG's iteration-count hints the run uses. */
-static void driver_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res, double tol,
-                       int round) {
-  sv->tol_run = tol, sv->verify_run = 0;
-  if (sv->o.krylov == LSB_KRYLOV_GMRES)
-    gmres_solve_dev(sv, d_b, d_x, res);
-  else if (sv->o.krylov == LSB_KRYLOV_BICGSTAB)
-    bicgstab_solve_dev(sv, d_b, d_x, res);
-  else if (sv->o.krylov == LSB_KRYLOV_RICHARDSON)
-    richardson_solve_dev(sv, d_b, d_x, res);
-  else
-    pcg_run(sv, d_b, d_x, res, round);
-}
-
-/*
- * opts.verify and the refinement of mixed precision, on the solve's own (b, x) with bb = b.b, behind a run that
- * reported CONVERGED: the residual b - S x RECOMPUTED from x (communicating over RCCL).  The recurrence residual
- * CG stops on drifts away from it over thousands of iterations (10 M-row 5-point operator, 9302 iterations:
- * recurrence 9.9e-9, recomputed 1.2e-8 at tol 1e-8), so a solve is reported converged only when the recomputed
- * residual meets the tolerance; otherwise the driver restarts on it (S e = b - S x from e = 0 to whatever is still
- * missing, x += e), at most LSB_MAX_CORRECTIONS times.  r->true_relres >= 0 on entry: a residual already recomputed.
- * twice: resid2's -- 0 in a cold solve, whose numbers stay what they were.
- */
-static void verify_correct(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *r, double bb,
-                           int twice) {
-  const int refine = sv->sh[0].mixed && sv->o.tol > 0.0;
-  if (!((sv->o.verify || refine) && r->status == LSB_STATUS_CONVERGED && sv->o.tol > 0.0 && bb > 0.0))
-    return;
-  const double floor_tol = mixed_floor_tol(sv);
-  for (int round = 1;; round++) {
-    if (r->true_relres < 0.0 || round > 1)
-      r->true_relres = sqrt(resid2(sv, d_b, d_x, twice) / bb), r->spmvs++;
-    if (r->true_relres <= sv->o.tol || round > LSB_MAX_CORRECTIONS)
-      break;
-    /* S e = S x - b (what true_resid2 left in q), then x -= e */
-    if (!sv->d_vr) {
-      sv->d_vr = (double *)lsb_hip_malloc((size_t)sv->n_here * sizeof(double));
-      sv->d_ve = (double *)lsb_hip_malloc((size_t)sv->n_here * sizeof(double));
-    }
-    for (int i = 0; i < sv->nshard; i++) {
-      struct shard *s = &sv->sh[i];
-      LSB_CHK_HIP(hipMemcpyAsync(sv->d_vr + (s->row_begin - sv->row_first), s->d_q,
-                                 (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice,
-                                 g_stream));
-    }
-    struct lsb_hip_result rc;
-    /* relative to ||S x - b|| */
-    driver_run(sv, sv->d_vr, sv->d_ve, &rc, fmax(0.7 * sv->o.tol / r->true_relres, floor_tol), round);
-    for (int i = 0; i < sv->nshard; i++) {
-      struct shard *s = &sv->sh[i];
-      const size_t o = s->row_begin - sv->row_first;
-      lsb_k_axpy(s->n, s->d_scal + 5, sv->d_ve + o, d_x + o, g_stream); /* d_scal[5] = -1 */
-    }
-    r->iters += rc.iters, r->spmvs += rc.spmvs, r->corrections++;
-    if (rc.status != LSB_STATUS_CONVERGED) {
-      r->status = rc.status;
-      r->true_relres = sqrt(resid2(sv, d_b, d_x, twice) / bb), r->spmvs++;
-      break;
-    }
-  }
-  if (r->status == LSB_STATUS_CONVERGED && !(r->true_relres <= sv->o.tol))
-    r->status = LSB_STATUS_MAXIT; /* the corrections did not get there: not converged */
-  r->relres = r->true_relres;
-  drain_stream(sv, "correction");
-}
-
 /* products with the operator of a PCG solve and its correction runs, from the counts in *r */
-static unsigned pcg_spmvs(const lsb_hip_solver *sv, const struct lsb_hip_result *r) {
+unsigned pcg_spmvs(const lsb_hip_solver *sv, const struct lsb_hip_result *r) {
   const unsigned m = sv->o.precond == LSB_PRECOND_CHEBYSHEV ? (unsigned)sv->cheb_m : 0u;
   return r->iters * (1u + m) + (1u + r->corrections) * (m + (sv->form == PCG_CG1 || sv->ps.use ? 1u : 0u)) +
          (r->true_relres >= 0.0 ? 1u + r->corrections : 0u);
 }
 
-/*
- * One solve from x0 = 0 as the caller sees it: the run of the solver's driver, then -- opts.verify, or always
- * when the direct xGMI path carried the run -- the recomputed residual and the correction runs of
- * verify_correct.
- */
-int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
-                      struct lsb_hip_result *res) {
-  sv->start_n = 0; /* a cold solve: lsb_hip_solver_start_relres has nothing to answer */
-  sv->tol_run = sv->o.tol, sv->verify_run = sv->o.verify;
-  if (sv->o.krylov == LSB_KRYLOV_GMRES)
-    return gmres_solve_dev(sv, d_b, d_x, res);
-  if (sv->o.krylov == LSB_KRYLOV_BICGSTAB)
-    return bicgstab_solve_dev(sv, d_b, d_x, res);
-  if (sv->o.krylov == LSB_KRYLOV_RICHARDSON)
-    return richardson_solve_dev(sv, d_b, d_x, res);
+/* One PCG solve from x0 = 0 as the caller sees it (the driver's entry point, hip_solve.c): the run, then -- opts.verify,
+ * or always when the direct xGMI path carried the run -- the recomputed residual and the correction runs of
+ * verify_correct. */
+int pcg_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res) {
   const double t0 = wall_seconds();
   struct lsb_hip_result r;
   /* Mixed precision: the CG runs see S~ = fp32(S) (fp64 vectors and sums) and
@@ -958,21 +796,8 @@ int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
   sv->tol_run = fmax(sv->o.tol, mixed_floor_tol(sv));
   pcg_run(sv, d_b, d_x, &r, 0);
   const double bb = sv->h_st->bb;
-  if (sv->p2p_on) {
-    /* The direct path passed its self-test, but a solve is only reported if
-     * the recomputed residual agrees with the recurrence; otherwise: say so,
-     * drop the path, solve again. */
-    const double tr = bb > 0.0 ? sqrt(true_resid2(sv, d_b, d_x) / bb) : 0.0;
-    r.true_relres = tr;
-    if (!(tr <= 100.0 * fmax(r.relres, sv->o.tol) + 1e-9)) {
-      fprintf(stderr, "hip_cdna4: WARNING: true residual %.3e after a solve over the direct xGMI "
-                      "path (recurrence: %.3e); falling back to RCCL and solving again\n",
-              tr, r.relres);
-      sv->p2p_on = sv->p2p_halo = 0;
-      memset(sv->hint_iters, 0, sizeof sv->hint_iters);
-      return solve_core(sv, d_b, d_x, res);
-    }
-  }
+  if (sv->p2p_on && !direct_path_agrees(sv, d_b, d_x, bb, &r, "solving again"))
+    return pcg_solve_dev(sv, d_b, d_x, res); /* from zero, over RCCL */
   verify_correct(sv, d_b, d_x, &r, bb, 0);
   r.seconds = wall_seconds() - t0;
   r.spmvs = pcg_spmvs(sv, &r);
@@ -980,173 +805,4 @@ int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
     *res = r;
   g_last = r;
   return 0;
-}
-
-/*
- * One solve from the x0 that d_x holds (lsb_hip_solver_solve_x0[_dev]), for every driver and every PCG form from
- * this one place: q = S x0 the way a recomputed residual forms it, k_x0_start leaves r0 = b - q and the sums
- * (r0.r0, b.b), and the solver's own driver solves S e = r0 from e = 0 to tol sqrt(b.b / r0.r0) -- relative to
- * ||r0|| what opts.tol is relative to ||b||, and exactly opts.tol when x0 = 0, where the two sums have the same
- * bits.  x = x0 + e; opts.verify and the refinement of mixed precision then see the original (b, x), as in a cold
- * solve.  b = 0: x = 0.  ||r0|| <= tol ||b||: x0 is the answer and is not touched.
- */
-int solve_x0_core(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res) {
-  static const double plus_one = 1.0;
-  const double t0 = wall_seconds(), tol = sv->o.tol;
-  const int on = sv->p2p_on, halo = sv->p2p_halo;
-  double sums[2] = {0.0, 0.0};
-  if (!sv->d_x0r) {
-    sv->d_x0r = (double *)lsb_hip_malloc((size_t)sv->n_here * sizeof(double));
-    sv->d_x0e = (double *)lsb_hip_malloc((size_t)sv->n_here * sizeof(double));
-  }
-  sv->p2p_on = sv->p2p_halo = 0;
-  op_exact(sv, d_x);
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    const size_t o = s->row_begin - sv->row_first;
-    unsigned np = 0;
-    LSB_CHK_HIP(hipMemcpyAsync(s->d_scal + 6, &plus_one, sizeof(double), hipMemcpyHostToDevice, g_stream));
-    lsb_k_x0_start(s->n, d_b + o, s->d_q, sv->d_x0r + o, s->d_parts2, &np, g_stream);
-    lsb_k_reduce_final(s->d_parts2, np, 2, s->d_scal + 3, 0, NULL, g_stream);
-  }
-  allreduce_scal(sv, 3, 2, 0);
-  LSB_CHK_HIP(hipMemcpyAsync(sums, sv->sh[0].d_scal + 3, sizeof sums, hipMemcpyDeviceToHost, g_stream));
-  drain_stream(sv, "starting residual");
-  sv->p2p_on = on, sv->p2p_halo = halo;
-  const double r0r0 = sums[0], bb = sums[1];
-  struct lsb_hip_result r;
-  memset(&r, 0, sizeof r);
-  r.true_relres = -1.0;
-  const double start = bb > 0.0 ? sqrt(r0r0 / bb) : 0.0;
-  if (bb == 0.0) { /* the cold rule, whatever x0 holds */
-    LSB_CHK_HIP(hipMemsetAsync(d_x, 0, (size_t)sv->n_here * sizeof(double), g_stream));
-    drain_stream(sv, "x = 0");
-    r.status = LSB_STATUS_CONVERGED, r.spmvs = 1;
-  } else if (tol > 0.0 && r0r0 <= tol * tol * bb) {
-    r.status = LSB_STATUS_CONVERGED, r.relres = start, r.spmvs = 1;
-    if (sv->o.verify)
-      r.true_relres = start; /* it IS the recomputed residual */
-  } else {
-    driver_run(sv, sv->d_x0r, sv->d_x0e, &r, fmax(tol * sqrt(bb / r0r0), mixed_floor_tol(sv)), 0);
-    for (int i = 0; i < sv->nshard; i++) {
-      struct shard *s = &sv->sh[i];
-      const size_t o = s->row_begin - sv->row_first;
-      lsb_k_axpy(s->n, s->d_scal + 6, sv->d_x0e + o, d_x + o, g_stream); /* d_scal[6] = 1 */
-    }
-    r.relres *= start; /* relative to ||b|| */
-    if (sv->p2p_on) { /* as in solve_core: the direct path's result must agree with a recomputed residual */
-      const double tr = sqrt(true_resid2(sv, d_b, d_x) / bb);
-      if (!(tr <= 100.0 * fmax(r.relres, tol) + 1e-9)) {
-        fprintf(stderr, "hip_cdna4: WARNING: true residual %.3e after a solve over the direct xGMI "
-                        "path (recurrence: %.3e); falling back to RCCL and solving on from this x\n",
-                tr, r.relres);
-        sv->p2p_on = sv->p2p_halo = 0;
-        memset(sv->hint_iters, 0, sizeof sv->hint_iters);
-        /* ... which is x0 + e by now; the caller is told about both runs, and about the x0 that was theirs */
-        struct lsb_hip_result again;
-        solve_x0_core(sv, d_b, d_x, &again);
-        if (sv->form != PCG_NONE)
-          r.spmvs = pcg_spmvs(sv, &r);
-        again.iters += r.iters, again.spmvs += r.spmvs + 2u; /* S x0 and the residual that failed the check */
-        again.seconds = wall_seconds() - t0;
-        start_relres_slots(sv, 1)[0] = start;
-        if (res)
-          *res = again;
-        g_last = again;
-        return 0;
-      }
-      r.true_relres = tr, r.spmvs++;
-    }
-    if (sv->o.krylov != LSB_KRYLOV_GMRES) { /* (which recomputes nothing in a cold solve either) */
-      const double tr = r.true_relres; /* the direct path's check; opts.verify recomputes in its own way */
-      r.true_relres = -1.0;
-      verify_correct(sv, d_b, d_x, &r, bb, sv->o.verify != 0); /* (the refinement alone: the cold solve's residual) */
-      if (r.true_relres < 0.0)
-        r.true_relres = tr;
-    }
-    drain_stream(sv, "x = x0 + e");
-    if (sv->form != PCG_NONE)
-      r.spmvs = pcg_spmvs(sv, &r);
-    r.spmvs++; /* S x0 */
-  }
-  r.seconds = wall_seconds() - t0;
-  start_relres_slots(sv, 1)[0] = start;
-  if (res)
-    *res = r;
-  g_last = r;
-  return 0;
-}
-
-double *start_relres_slots(lsb_hip_solver *sv, unsigned nrhs) {
-  if (nrhs > sv->start_cap) {
-    sv->start_rr = (double *)realloc(sv->start_rr, (size_t)nrhs * sizeof(double));
-    if (!sv->start_rr)
-      errx(EXIT_FAILURE, "hip_cdna4: out of memory");
-    sv->start_cap = nrhs;
-  }
-  sv->start_n = nrhs;
-  return sv->start_rr;
-}
-
-int lsb_hip_solver_start_relres(const lsb_hip_solver *sv, unsigned nrhs, double *out) {
-  if (!sv || !out || nrhs == 0 || nrhs != sv->start_n)
-    return 2;
-  memcpy(out, sv->start_rr, (size_t)nrhs * sizeof(double));
-  return 0;
-}
-
-int lsb_hip_solver_solve_x0_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res) {
-  if (!lsb_initialized)
-    return 1;
-  if (!sv || !d_b || !d_x)
-    return 2;
-  if (!sv->d_perm)
-    return solve_x0_core(sv, d_b, d_x, res);
-  /* as solve_dev, with x0' = Q x0 (a pad row starts from 0) */
-  struct lsb_hip_result r;
-  lsb_k_perm_gather(sv->n_here, sv->d_perm, d_b, sv->d_bp, g_stream);
-  lsb_k_perm_gather(sv->n_here, sv->d_perm, d_x, sv->d_xp, g_stream);
-  const int rc = solve_x0_core(sv, sv->d_bp, sv->d_xp, &r);
-  /* an x0 that already is the answer stays where it is, bit for bit */
-  if (!(r.status == LSB_STATUS_CONVERGED && r.iters == 0 && sv->start_rr[0] > 0.0)) {
-    lsb_k_perm_scatter(sv->n_here, sv->d_perm, sv->d_xp, d_x, g_stream);
-    drain_stream(sv, "un-permuting x");
-  }
-  if (res)
-    *res = r;
-  return rc;
-}
-
-int lsb_hip_solver_solve_x0(lsb_hip_solver *sv, const double *b, double *x, struct lsb_hip_result *res) {
-  if (!lsb_initialized)
-    return 1;
-  if (!sv || !b || !x)
-    return 2;
-  const size_t bytes = (size_t)sv->n_user * sizeof(double);
-  double *d_b = (double *)lsb_hip_malloc(bytes), *d_x = (double *)lsb_hip_malloc(bytes);
-  LSB_CHK_HIP(hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice));
-  LSB_CHK_HIP(hipMemcpy(d_x, x, bytes, hipMemcpyHostToDevice));
-  int rc = lsb_hip_solver_solve_x0_dev(sv, d_b, d_x, res);
-  LSB_CHK_HIP(hipMemcpy(x, d_x, bytes, hipMemcpyDeviceToHost));
-  /* cached graphs must not outlive the buffers they were captured with */
-  drop_graphs(sv);
-  lsb_hip_free(d_b), lsb_hip_free(d_x);
-  return rc;
-}
-
-int lsb_hip_solver_solve(lsb_hip_solver *sv, const double *b, double *x,
-                         struct lsb_hip_result *res) {
-  if (!lsb_initialized)
-    return 1;
-  if (!sv || !b || !x)
-    return 2;
-  const size_t bytes = (size_t)sv->n_user * sizeof(double);
-  double *d_b = (double *)lsb_hip_malloc(bytes), *d_x = (double *)lsb_hip_malloc(bytes);
-  LSB_CHK_HIP(hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice));
-  int rc = lsb_hip_solver_solve_dev(sv, d_b, d_x, res);
-  LSB_CHK_HIP(hipMemcpy(x, d_x, bytes, hipMemcpyDeviceToHost));
-  /* cached graphs must not outlive the buffers they were captured with */
-  drop_graphs(sv);
-  lsb_hip_free(d_b), lsb_hip_free(d_x);
-  return rc;
 }

@@ -45,9 +45,10 @@ static int rich_chunk(const lsb_hip_solver *sv) {
   return run_chunk((double)(12ull * s->nnz + lsb_hip_solver_amg_cycle_bytes(sv) + 64ull * s->n), 6.0, 2, 256);
 }
 
-/* what run_loop enqueues */
+/* what run_loop enqueues, and what a restart needs */
 struct rich_enq {
   lsb_hip_solver *sv;
+  const double *d_b;
   double *d_x;
 };
 
@@ -81,18 +82,29 @@ static void rich_enqueue(void *ctx, int cycles) {
 /* Enqueue cycles until the device state leaves RUNNING; the final state lands in h_st[0] (whose iters the caller
  * cleared for the solve proper).  *hint: what this stretch of the previous solve took.  Never more cycles than maxit
  * leaves: once they are all enqueued, the poll behind them finds a final status. */
-static void rich_run(lsb_hip_solver *sv, double *d_x, unsigned *hint) {
-  struct rich_enq e = {sv, d_x};
+static void rich_run(void *ctx, unsigned *hint) {
+  lsb_hip_solver *sv = ((struct rich_enq *)ctx)->sv;
   const struct run_loop r = {.name = "the Richardson iteration", .d_state = sv->sh[0].d_st, .h_state = sv->h_st,
                              .state_bytes = sizeof(struct lsb_pcg_state),
                              .stop_off = offsetof(struct lsb_pcg_state, status),
                              .progress_off = offsetof(struct lsb_pcg_state, iters),
-                             .enqueue = rich_enqueue, .ctx = &e, .chunk = rich_chunk(sv),
+                             .enqueue = rich_enqueue, .ctx = ctx, .chunk = rich_chunk(sv),
                              .cap = (long)sv->o.maxit - sv->h_st[0].iters, /* cycles the device can still run */
                              .what_hinted = "poll of a hinted Richardson solve",
                              .what_poll = "poll of the Richardson solve",
                              .what_drain = "drain after the Richardson solve"};
   run_loop(sv, &r, hint);
+}
+
+/* the restart of run_restarting: the cycles go on from r = b - S x, x kept */
+static void rich_restart(void *ctx, int more) {
+  const struct rich_enq *e = ctx;
+  struct shard *s = &e->sv->sh[0];
+  unsigned *nrr = &e->sv->rich_nrr;
+  gather_x(e->sv, e->d_x);
+  spmv_shard(s, s->d_pfull, s->d_q, NULL, NULL, NULL, NULL);
+  lsb_k_rich_restart(s->n, e->d_b, s->d_q, s->d_r, s->d_parts2, nrr, g_stream);
+  lsb_k_rich_restart_state(s->d_st, s->d_parts2, *nrr, more, g_stream);
 }
 
 int richardson_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res) {
@@ -105,26 +117,12 @@ int richardson_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x, str
   struct lsb_hip_result r;
   memset(&r, 0, sizeof r);
   r.true_relres = -1.0;
-  unsigned nverify = 0;
+  struct rich_enq e = {sv, d_b, d_x};
+  const struct restart_run v = {.run = rich_run, .restart = rich_restart, .ctx = &e, .d_state = s->d_st, .h_state = hst,
+                                .state_bytes = sizeof hst[0],
+                                .what_drain = "recomputed residual of the Richardson solve"};
   hst[0].iters = 0;
-  for (int round = 0;; round++) {
-    rich_run(sv, d_x, hint_slot(sv->hint_iters, round));
-    if (!(sv->verify_run && hst[0].status == LSB_STATUS_CONVERGED && sv->tol_run > 0.0 && hst[0].bb > 0.0))
-      break;
-    /* "converged" is reported only for the residual RECOMPUTED from x; where that one misses the tolerance the
-     * cycles go on from it (r = b - S x, x kept), LSB_MAX_CORRECTIONS times at the most, inside the timed region */
-    LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull, d_x, (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice, g_stream));
-    spmv_shard(s, s->d_pfull, s->d_q, NULL, NULL, NULL, NULL);
-    lsb_k_rich_restart(s->n, d_b, s->d_q, s->d_r, s->d_parts2, nrr, g_stream);
-    lsb_k_rich_restart_state(s->d_st, s->d_parts2, *nrr, r.corrections < LSB_MAX_CORRECTIONS, g_stream);
-    nverify++;
-    LSB_CHK_HIP(hipMemcpyAsync(&hst[0], s->d_st, sizeof hst[0], hipMemcpyDeviceToHost, g_stream));
-    drain_stream(sv, "recomputed residual of the Richardson solve");
-    r.true_relres = sqrt(hst[0].rr / hst[0].bb);
-    if (hst[0].status != LSB_STATUS_RUNNING)
-      break;
-    r.corrections++;
-  }
+  const unsigned nverify = run_restarting(sv, &v, &r);
   check_aux_status(sv, "Richardson solve");
   result_from_state(&r, &hst[0]);
   r.spmvs = r.iters + nverify; /* one product per cycle counted, one per recomputed residual */

@@ -664,6 +664,7 @@ void solver_finish_setup(lsb_hip_solver *sv) {
   }
   tune_blas1_nt(sv);
   precond_setup(sv);
+  sv->driver = solve_driver_for(sv->o.krylov);
   sv->form = pcg_choose_form(sv);
   sv->overlap_on = -1;
   p2p_setup(sv);
@@ -680,26 +681,36 @@ static void bicgstab_check_precond(const struct lsb_hip_opts *o) {
                        "block-Jacobi, FSAI and AMG run under PCG)");
 }
 
-lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
-                                      const struct lsb_hip_opts *o_in) {
-  if (!lsb_initialized || !A || A->nrows == 0)
-    return NULL;
+/* What the caller's options (NULL: the backend's current ones) become before a solver is built from them: mixed
+ * precision is an iterative refinement around CG without AMG, anything else runs in fp64 -- said aloud, but for a
+ * solver sharded over ranks --, and what the drivers cannot run with is refused */
+static struct lsb_hip_opts solver_opts(const struct lsb_hip_opts *o_in, int sharded) {
   struct lsb_hip_opts o;
   if (o_in)
     o = *o_in;
   else
     lsb_hip_get_opts(&o);
   if (o.precision == LSB_PREC_MIXED && (o.krylov == LSB_KRYLOV_GMRES || o.krylov == LSB_KRYLOV_BICGSTAB)) {
-    warnx("hip_cdna4: mixed precision is an iterative refinement around CG; %s runs in fp64",
-          o.krylov == LSB_KRYLOV_GMRES ? "GMRES" : "BiCGSTAB");
+    if (!sharded)
+      warnx("hip_cdna4: mixed precision is an iterative refinement around CG; %s runs in fp64",
+            o.krylov == LSB_KRYLOV_GMRES ? "GMRES" : "BiCGSTAB");
     o.precision = LSB_PREC_FP64;
   }
   bicgstab_check_precond(&o);
-  richardson_check(&o, 0);
+  richardson_check(&o, sharded);
   if (o.precision == LSB_PREC_MIXED && o.precond == LSB_PRECOND_AMG) {
-    warnx("hip_cdna4: --precond amg runs in fp64");
+    if (!sharded)
+      warnx("hip_cdna4: --precond amg runs in fp64");
     o.precision = LSB_PREC_FP64;
   }
+  return o;
+}
+
+lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
+                                      const struct lsb_hip_opts *o_in) {
+  if (!lsb_initialized || !A || A->nrows == 0)
+    return NULL;
+  struct lsb_hip_opts o = solver_opts(o_in, 0);
   /* the operator, 0-based, both triangles */
   struct csr *S = o.op_mode == LSB_OP_CHOLMOD_UPPER ? lsb_csr_symmetrize_upper(A)
                                                     : lsb_csr_copy_base0(A);
@@ -788,16 +799,7 @@ lsb_hip_solver *lsb_hip_solver_create_dist(const struct csr *A_rows,
                                            const struct lsb_hip_opts *o_in) {
   if (!lsb_initialized || !A_rows)
     return NULL;
-  struct lsb_hip_opts o;
-  if (o_in)
-    o = *o_in;
-  else
-    lsb_hip_get_opts(&o);
-  if (o.precision == LSB_PREC_MIXED &&
-      (o.krylov == LSB_KRYLOV_GMRES || o.krylov == LSB_KRYLOV_BICGSTAB || o.precond == LSB_PRECOND_AMG))
-    o.precision = LSB_PREC_FP64; /* as in lsb_hip_solver_create */
-  bicgstab_check_precond(&o);
-  richardson_check(&o, 1);
+  struct lsb_hip_opts o = solver_opts(o_in, 1);
   const int P = lsb_hip_comm_size(), me = lsb_hip_comm_rank();
   lsb_hip_solver *sv = solver_alloc(1, &o);
   sv->n_glob = n_global, sv->n_here = sv->n_user = A_rows->nrows, sv->row_first = row_begin;
@@ -1270,14 +1272,7 @@ int lsb_hip_solver_spmv_dev(lsb_hip_solver *sv, const double *d_x, double *d_y) 
     lsb_k_perm_gather(sv->n_here, sv->d_perm, d_x, sv->d_bp, g_stream);
     d_x = sv->d_bp, d_yout = d_y, d_y = sv->d_xp;
   }
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + s->row_begin, d_x + (s->row_begin - sv->row_first),
-                               (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice,
-                               g_stream));
-  }
-  if (sv->multi)
-    exchange_p(sv, 0);
+  gather_x(sv, d_x);
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
     spmv_shard_exact(s, s->d_pfull, d_y + (s->row_begin - sv->row_first), NULL, NULL, NULL, NULL);
@@ -1301,15 +1296,9 @@ int lsb_hip_solver_spmv_inner_dev(lsb_hip_solver *sv, const double *d_x, double 
     lsb_k_perm_gather(sv->n_here, sv->d_perm, d_x, sv->d_bp, g_stream);
     d_x = sv->d_bp, d_yout = d_y, d_y = sv->d_xp;
   }
-  for (int i = 0; i < sv->nshard; i++) {
-    struct shard *s = &sv->sh[i];
-    LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + s->row_begin, d_x + (s->row_begin - sv->row_first),
-                               (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice,
-                               g_stream));
-    LSB_CHK_HIP(hipMemsetAsync(&s->d_st->status, 0, sizeof(int), g_stream)); /* the launches are gated on it */
-  }
-  if (sv->multi)
-    exchange_p(sv, 0);
+  for (int i = 0; i < sv->nshard; i++) /* the launches are gated on it */
+    LSB_CHK_HIP(hipMemsetAsync(&sv->sh[i].d_st->status, 0, sizeof(int), g_stream));
+  gather_x(sv, d_x);
   const int split = can_overlap(sv);
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
@@ -1362,13 +1351,7 @@ int lsb_hip_solver_jacobi_sweep_dev(lsb_hip_solver *sv, double w, const double *
   if (sv->d_perm) { /* re-ordered / line-padded operator: the sweep in the solver's own numbering */
     lsb_k_perm_gather(sv->n_here, sv->d_perm, d_x, sv->d_xp, g_stream);
     lsb_k_perm_gather(sv->n_here, sv->d_perm, d_b, sv->d_bp, g_stream);
-    for (int i = 0; i < sv->nshard; i++) {
-      struct shard *s = &sv->sh[i];
-      LSB_CHK_HIP(hipMemcpyAsync(s->d_pfull + s->row_begin, sv->d_xp + (s->row_begin - sv->row_first),
-                                 (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice, g_stream));
-    }
-    if (sv->multi)
-      exchange_p(sv, 0);
+    gather_x(sv, sv->d_xp);
     for (int i = 0; i < sv->nshard; i++) {
       struct shard *s = &sv->sh[i];
       const size_t o = s->row_begin - sv->row_first;

@@ -8,7 +8,9 @@
  *   hip_dist.c       what sharded solves add: exchange, all-reduce, overlap,
  *                    the direct xGMI path's set-up
  *   hip_run.c        what the iteration drivers share: the host loop, the cache of captured graphs, the chunk rule
- *   hip_pcg.c        PCG iteration forms (one chosen per solver), the solve and its correction runs
+ *   hip_pcg.c        the PCG driver: its iteration forms (one chosen per solver), one run, the persistent launch
+ *   hip_solve.c      what a caller's solve is, whichever driver runs it (one chosen per solver): cold and from an
+ *                    initial guess, recomputed residuals and what follows from them, the single-column entry points
  *   hip_precond.c    FSAI, block-Jacobi and the Chebyshev preconditioner: set-up and z = M^-1 r
  *   hip_amg_drv.c    AMG: upload of the hierarchy, the V-cycle's one schedule (amg_cycle), its accessors
  *   hip_gmres_drv.c  GMRES(m) driver
@@ -107,6 +109,16 @@ enum pcg_form {
   PCG_CG1,     /* single reduction: k_cg1_update + SpMV */
   PCG_GENERIC, /* the classic sweeps around precond_apply (z = M^-1 r as a vector) */
   PCG_FSAI3,   /* FSAI in three launches: k_spmv_subwave_p, k_fsai_xr_gr, k_fsai_gt_dots */
+};
+
+/* An iteration driver (solve_driver_for picks it once, at creation; hip_solve.c).  solve: one solve from x0 = 0 as the
+ * caller sees it, to sv->tol_run and -- sv->verify_run -- checked against a recomputed residual.  run: one bare run
+ * of the iteration, `round` = 0 for the solve proper, k for its k-th correction run; NULL: solve, with
+ * sv->verify_run = 0, is that run */
+typedef int solve_dev_fn(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res);
+struct solve_driver {
+  solve_dev_fn *solve;
+  int (*run)(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res, int round);
 };
 
 /* The vectors of one level of the AMG V-cycle: right-hand side, result, the other smoothing buffer, the residual, the
@@ -375,6 +387,7 @@ struct lsb_hip_solver {
   /* single-reduction PCG without the vector u = D^-1 r: every shard of every
    * rank has the same constant Jacobi diagonal (k_cg1_update<UI>) */
   int cg1_implicit;
+  const struct solve_driver *driver; /* the iteration driver this solver runs (solve_driver_for) */
   enum pcg_form form; /* the PCG iteration this solver runs (pcg_choose_form) */
   int pcur, rcur; /* launch-bound fused paths: which direction / residual buffer is current */
   int nt_mask;    /* which operands of the BLAS-1 sweeps are loaded nontemporal (tune_blas1_nt) */
@@ -499,7 +512,6 @@ LSB_INTERNAL void exchange_and_spmv(lsb_hip_solver *sv, int sample);
 /* part 0 / 1 / 2 of the split SpMV: the units that need no halo, the ones before, the ones after them */
 LSB_INTERNAL void spmv_range(struct shard *s, int part, double *y, double *partials, unsigned *np,
                              const struct lsb_pcg_state *st);
-LSB_INTERNAL double true_resid2(lsb_hip_solver *sv, const double *d_b, const double *d_x);
 /* hip_pcg.c */
 LSB_INTERNAL enum pcg_form pcg_choose_form(const lsb_hip_solver *sv);
 LSB_INTERNAL void form_vecs(lsb_hip_solver *sv, enum pcg_form f);
@@ -508,10 +520,35 @@ LSB_INTERNAL void sample_open(lsb_hip_solver *sv, int k);
 LSB_INTERNAL void sample_close(lsb_hip_solver *sv, int k);
 LSB_INTERNAL void tune_blas1_nt(lsb_hip_solver *sv);
 LSB_INTERNAL void persist_setup(lsb_hip_solver *sv);
-LSB_INTERNAL int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x,
-                            struct lsb_hip_result *res);
-/* the same from the x0 that d_x holds */
-LSB_INTERNAL int solve_x0_core(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res);
+LSB_INTERNAL solve_dev_fn pcg_solve_dev;
+LSB_INTERNAL int pcg_run(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *res, int round);
+/* products with the operator of a PCG solve and its correction runs, from the counts in *r */
+LSB_INTERNAL unsigned pcg_spmvs(const lsb_hip_solver *sv, const struct lsb_hip_result *r);
+/* hip_solve.c */
+LSB_INTERNAL const struct solve_driver *solve_driver_for(int krylov);
+LSB_INTERNAL solve_dev_fn solve_core;
+LSB_INTERNAL solve_dev_fn solve_x0_core; /* the same from the x0 that d_x holds */
+LSB_INTERNAL void gather_x(lsb_hip_solver *sv, const double *d_x);
+LSB_INTERNAL double true_resid2(lsb_hip_solver *sv, const double *d_b, const double *d_x);
+LSB_INTERNAL int direct_path_agrees(lsb_hip_solver *sv, const double *d_b, const double *d_x, double bb,
+                                    struct lsb_hip_result *r, const char *then);
+LSB_INTERNAL double mixed_floor_tol(const lsb_hip_solver *sv);
+LSB_INTERNAL void verify_correct(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hip_result *r,
+                                 double bb, int twice);
+/* What a driver that restarts in place hands run_restarting: run enqueues iterations until the device state leaves
+ * RUNNING (*hint: what this stretch of the previous solve took), restart enqueues r = b - S x from the x reached
+ * and the state that goes with it (more = 0: the last one, the status is final); the state begins with a struct
+ * lsb_pcg_state and is polled into h_state */
+struct restart_run {
+  void (*run)(void *ctx, unsigned *hint);
+  void (*restart)(void *ctx, int more);
+  void *ctx;
+  const void *d_state;
+  void *h_state;
+  size_t state_bytes;
+  const char *what_drain;
+};
+LSB_INTERNAL unsigned run_restarting(lsb_hip_solver *sv, const struct restart_run *v, struct lsb_hip_result *r);
 /* where a warm-started call of nrhs columns records its starting residuals (sets start_n) */
 LSB_INTERNAL double *start_relres_slots(lsb_hip_solver *sv, unsigned nrhs);
 /* hip_precond.c */
@@ -544,16 +581,13 @@ LSB_INTERNAL void amg_cycle(const struct amg_run *c);
  * tmp and r, four vectors per coarser level, then the Chebyshev smoother's direction blocks; fills v[0 .. nlev) */
 LSB_INTERNAL char *amg_block_vecs(const struct amg_dev *a, unsigned kp, struct amg_vecs *v);
 /* hip_gmres_drv.c */
-LSB_INTERNAL int gmres_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
-                                 struct lsb_hip_result *res);
+LSB_INTERNAL solve_dev_fn gmres_solve_dev;
 /* hip_bicgstab_drv.c */
-LSB_INTERNAL int bicgstab_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
-                                    struct lsb_hip_result *res);
+LSB_INTERNAL solve_dev_fn bicgstab_solve_dev;
 LSB_INTERNAL void bicgstab_free(lsb_hip_solver *sv); /* before the shards go: its vectors may sit in their slabs */
 /* hip_rich_drv.c, and the launchers of hip_rich.hip (n rows; the 16-byte form where every operand is 16-byte
  * aligned, else the 8-byte form with the same bits; partials: one per workgroup, *npartials of them) */
-LSB_INTERNAL int richardson_solve_dev(lsb_hip_solver *sv, const double *d_b, double *d_x,
-                                      struct lsb_hip_result *res);
+LSB_INTERNAL solve_dev_fn richardson_solve_dev;
 /* what --krylov richardson cannot run with, refused at creation: a preconditioner other than AMG, shards, persistent */
 LSB_INTERNAL void richardson_check(const struct lsb_hip_opts *o, int sharded);
 LSB_INTERNAL void lsb_k_rich_init(unsigned n, const double *b, double *x, double *r, double *partials,

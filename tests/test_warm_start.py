@@ -1,5 +1,5 @@
 """Solves from an initial guess: lsb_hip_solver_solve_x0[_dev], solve_multi_x0_dev and start_relres
-(hip_pcg.c: solve_x0_core and k_x0_start; hip_mrhs_drv.c and hip_mrhs_x0.hip: the in-place start of a batch).
+(hip_solve.c: solve_x0_core and k_x0_start; hip_mrhs_drv.c and hip_mrhs_x0.hip: the in-place start of a batch).
 
 The yardsticks: the cold solve of the same solver (x0 = 0 must reproduce it), the golden solution, the
 extended-precision residual `relres_exact` of test_mrhs.py, and the numpy restatement `pcg_x0` below of the
