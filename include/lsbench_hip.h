@@ -157,7 +157,7 @@ enum { LSB_KRYLOV_PCG = 0,    /* preconditioned CG (symmetric operators)    */
                                  for unsymmetric operators -- seven vectors, two
                                  SpMVs and four sweeps per iteration; one shard or
                                  several; trust it with opts.verify = 1        */
-       LSB_KRYLOV_RICHARDSON = 5 }; /* AMG as the solver (LSB_PRECOND_AMG only, one shard):
+       LSB_KRYLOV_RICHARDSON = 5, /* AMG as the solver (LSB_PRECOND_AMG only, one shard):
                                  stationary V-cycle iterations, the way the reference's AMG
                                  backends run (src/hypre.c:185-186, src/amgx.c:78-85 --
                                  maxit = 2, tol = 0 is their protocol).  x = 0, r = b; cycle
@@ -168,6 +168,19 @@ enum { LSB_KRYLOV_PCG = 0,    /* preconditioned CG (symmetric operators)    */
                                  and r stay fp64 (around the fp32 cycle: iterative
                                  refinement); iters counts cycles, relres^(1/iters) is the
                                  convergence factor per cycle; opts.verify as in PCG       */
+       LSB_KRYLOV_DIRECT = 6 }; /* a sparse direct solve (one shard, fp64; hip_direct.hip): at creation a nested-
+                                 dissection ordering, a Cholesky factor and its explicit inverse W = L^-1 as a
+                                 skyline (lsb_csr_skyline_inverse), untimed like every set-up; a round is
+                                 x (+)= W^T (W (P r)), two launches with no dot product and no host poll between
+                                 them, then -- tol > 0 -- r = b - S x and the stop test on that RECOMPUTED residual:
+                                 r.r <= tol^2 b.b CONVERGED, not finite BREAKDOWN, rounds >= maxit MAXIT.  iters
+                                 counts rounds (rounds after the first are iterative refinement), relres and
+                                 true_relres are both the recomputed figure, spmvs counts residuals.  tol = 0: exactly
+                                 maxit rounds, the last without a residual, MAXIT, relres = -1; maxit = 1, tol = 0 is
+                                 the reference's direct protocol (src/cholmod-impl.h:59-62).  opts.precond and
+                                 opts.reorder are not consulted: the factor is the method and orders for itself.
+                                 For operators of a few thousand to a few tens of thousands of rows
+                                 (LSB_DIRECT_MAX_ENTRIES); a larger one, shards and persistent are refused */
 enum { LSB_SPMV_AUTO = 0,     /* pick by mean row length                    */
        LSB_SPMV_ADAPTIVE = 1, /* row-blocked: LDS-streamed short rows +
                                  wavefront-per-row long rows                */
@@ -360,6 +373,37 @@ void lsb_csr_block_lanes(const struct csr *A, const unsigned *rowblk,
  * the padding would exceed 1/16 of the rows.  See lsb_operator.c. */
 struct csr *lsb_csr_pad_lines(const struct csr *S, unsigned slice, unsigned *nx, unsigned *nxp, int **map);
 int lsb_csr_rcm(const struct csr *S, unsigned *perm);
+/* The direct solver's host side (lsb_direct.c, rules there; LSB_KRYLOV_DIRECT), pure host logic.
+ * lsb_csr_nd: a nested-dissection ordering of a structurally symmetric pattern, perm[new] = old, by recursive
+ * bisection along the smallest BFS level that leaves both sides 30 % of the part.  Returns 0 and a permutation for
+ * any input (disconnected graphs, rows that hold only their diagonal, n = 1), 2 on allocation failure.
+ * lsb_csr_nd_bounded: the same, but gives up with 3 as soon as the entries of W this ordering cannot avoid -- n + the
+ * sum of |side below| |separator| over its bisections, *lower -- exceed `budget`; perm is then a permutation still,
+ * only not a finished ordering. */
+int lsb_csr_nd(const struct csr *S, unsigned *perm);
+int lsb_csr_nd_bounded(const struct csr *S, unsigned *perm, unsigned long long budget, unsigned long long *lower);
+/* Entries of W = L^-1 for P S P^T = L L^T: the sum over the columns of their depth in the elimination tree (a root
+ * has depth 1), symbolic -- Liu's algorithm with path compression, no numeric work; *height (may be NULL): the
+ * deepest column.  0 when perm is no permutation or memory runs out. */
+unsigned long long lsb_csr_skyline_count(const struct csr *S, const unsigned *perm, unsigned *height);
+/* The inverse factor as a skyline.  perm is perm_in composed with a postorder of its elimination tree (perm[new] =
+ * old), in which the subtree of k is the run of indices first[k] .. k; row k of W is exactly that run of columns,
+ * dense, at vals[woff[k] .. woff[k] + k - first[k]] -- no column indices.  parent[k]: the tree (n on a root);
+ * run_end[k]: the last index of the maximal run k, k + 1, ... in which parent(i) = i + 1, so that a walk to the root
+ * is a few dozen jumps.  x = P^T W^T W P b solves S x = b.  NULL with *why (may be NULL) = 1: a pivot <= 0 or not
+ * finite (S is not symmetric positive definite), 2: more than LSB_DIRECT_MAX_ENTRIES entries, 3: out of memory or
+ * perm_in is no permutation. */
+#define LSB_DIRECT_MAX_ENTRIES (1ull << 28) /* 2 GB of doubles: operators of a few thousand to a few tens of
+                                               thousands of rows */
+struct lsb_skyinv {
+  unsigned n;
+  unsigned *perm, *first;
+  unsigned long long *woff; /* n + 1 */
+  double *vals;
+  unsigned *parent, *run_end;
+};
+struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *perm_in, int *why);
+void lsb_skyinv_free(struct lsb_skyinv *W);
 /* P S P^T for perm[new] = old, as a new 0-based CSR (src/cusparse.c:87-97). */
 struct csr *lsb_csr_permute_sym(const struct csr *S, const unsigned *perm);
 /* max |row - col| over the stored entries */
@@ -805,6 +849,11 @@ int lsb_hip_solver_amg_precision(lsb_hip_solver *s);
  * of x and reads b and dinv on colour 0 only; the residual, restriction and prolongation as on every level, 6 n.
  * Row offsets and rowid are left out, as the offsets are everywhere above. */
 unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *s);
+/* The direct solver's factor (LSB_KRYLOV_DIRECT): entries of W = L^-1, height of the elimination tree, and the bytes
+ * the two products of one round stream (16 per entry, and the index and vector traffic per row); each may be NULL.
+ * 2 for any other solver. */
+int lsb_hip_solver_direct_info(const lsb_hip_solver *s, unsigned long long *entries, unsigned *height,
+                               unsigned long long *bytes_per_round);
 /* LSB_PRECOND_CHEBYSHEV: the interval [lmin, lmax] of D^-1 S the polynomial was built on at creation
  * (lmax = 1.1 x the power iteration's estimate, lmin = lmax / max(30, 16 degree^2), the degree
  * clamped to 1 .. 32); 2 for another preconditioner. */

@@ -25,6 +25,8 @@ PRECOND_AMG = 6
 AMG_SMOOTH_L1JACOBI, AMG_SMOOTH_CHEB, AMG_SMOOTH_MCGS = 0, 1, 2
 AMG_PREC_FP64, AMG_PREC_FP32 = 0, 1
 KRYLOV_PCG, KRYLOV_GMRES, KRYLOV_PCG1, KRYLOV_AUTO, KRYLOV_BICGSTAB, KRYLOV_RICHARDSON = 0, 1, 2, 3, 4, 5
+KRYLOV_DIRECT = 6
+DIRECT_MAX_ENTRIES = 1 << 28
 SPMV_AUTO, SPMV_ADAPTIVE, SPMV_SUBWAVE, SPMV_SCALAR, SPMV_PANEL, SPMV_SELL, SPMV_BINNED, SPMV_TWOPHASE = 0, 1, 2, 3, 4, 5, 6, 7
 SELL_ROWS = 128
 BIN_CHUNK = 2048
@@ -143,6 +145,13 @@ class Mcgs(C.Structure):
                 ("vals", C.POINTER(C.c_double))]
 
 
+class Skyinv(C.Structure):
+    """struct lsb_skyinv."""
+    _fields_ = [("n", C.c_uint), ("perm", C.POINTER(C.c_uint)), ("first", C.POINTER(C.c_uint)),
+                ("woff", C.POINTER(C.c_ulonglong)), ("vals", C.POINTER(C.c_double)),
+                ("parent", C.POINTER(C.c_uint)), ("run_end", C.POINTER(C.c_uint))]
+
+
 class SellTmpl(C.Structure):
     """struct lsb_sell_tmpl (176 bytes)."""
     _fields_ = [("nslots", C.c_int), ("shaped", C.c_int), ("base", C.c_int * 8), ("kidx", C.c_int * 8),
@@ -222,6 +231,11 @@ SIGNATURES = {
     "lsb_csr_row_blocks": (_u, [_csrp, _u, C.POINTER(C.POINTER(_u))]),
     "lsb_csr_block_lanes": (None, [_csrp, C.POINTER(_u), _u, C.POINTER(C.c_ubyte)]),
     "lsb_csr_rcm": (_i, [_csrp, C.POINTER(_u)]),
+    "lsb_csr_nd": (_i, [_csrp, C.POINTER(_u)]),
+    "lsb_csr_nd_bounded": (_i, [_csrp, C.POINTER(_u), C.c_ulonglong, C.POINTER(C.c_ulonglong)]),
+    "lsb_csr_skyline_count": (C.c_ulonglong, [_csrp, C.POINTER(_u), C.POINTER(_u)]),
+    "lsb_csr_skyline_inverse": (C.POINTER(Skyinv), [_csrp, C.POINTER(_u), C.POINTER(_i)]),
+    "lsb_skyinv_free": (None, [C.POINTER(Skyinv)]),
     "lsb_csr_permute_sym": (_csrp, [_csrp, C.POINTER(_u)]),
     "lsb_csr_bandwidth": (_u, [_csrp]),
     "lsb_csr_panelize": (C.POINTER(PanelCsr), [_csrp, _u]),
@@ -292,6 +306,7 @@ SIGNATURES = {
     "lsb_hip_solver_amg_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u)]),
     "lsb_hip_solver_amg_precision": (_i, [_vp]),
     "lsb_hip_solver_amg_cycle_bytes": (C.c_ulonglong, [_vp]),
+    "lsb_hip_solver_direct_info": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(_u), C.POINTER(C.c_ulonglong)]),
     "lsb_hip_solver_amg_cheb_interval": (_i, [_vp, _u, C.POINTER(_d), C.POINTER(_d)]),
     "lsb_hip_solver_amg_colours": (_i, [_vp, _u, C.POINTER(_u)]),
     "lsb_hip_solver_cheb_interval": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),

@@ -215,6 +215,50 @@ def lsb_csr_rcm(A):
     return perm
 
 
+def lsb_csr_nd(A, budget=None):
+    """The nested-dissection ordering of lsb_csr_nd, perm[new] = old.  With a budget: (perm or None, the lower bound
+    of the entries of W this ordering cannot avoid) -- None where the bound exceeds the budget."""
+    perm = np.zeros(max(A.nrows, 1), np.uint32)
+    p = perm.ctypes.data_as(C.POINTER(C.c_uint))
+    if budget is None:
+        L.check(L.load().lsb_csr_nd(A.ptr, p), "lsb_csr_nd")
+        return perm[:A.nrows]
+    lower = C.c_ulonglong()
+    rc = L.load().lsb_csr_nd_bounded(A.ptr, p, budget, C.byref(lower))
+    if rc not in (0, 3):
+        L.check(rc, "lsb_csr_nd_bounded")
+    return (perm[:A.nrows] if rc == 0 else None), int(lower.value)
+
+
+def lsb_csr_skyline_count(A, perm):
+    """(entries of W = L^-1 under perm: the sum of the depths in the elimination tree, the tree's height)."""
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    h = C.c_uint()
+    cnt = L.load().lsb_csr_skyline_count(A.ptr, perm.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(h))
+    return int(cnt), int(h.value)
+
+
+def lsb_csr_skyline_inverse(A, perm):
+    """The skyline inverse factor (struct lsb_skyinv) as a dict of numpy arrays -- n, perm, first, woff, vals, parent,
+    run_end -- or the reason it was refused as an int: 1 not positive definite, 2 over the budget, 3 memory."""
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    why = C.c_int()
+    p = L.load().lsb_csr_skyline_inverse(A.ptr, perm.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(why))
+    if not p:
+        return int(why.value)
+    w = p.contents
+    n = int(w.n)
+
+    def arr(q, cnt, dt):
+        return np.ctypeslib.as_array(q, shape=(max(cnt, 1),))[:cnt].astype(dt, copy=True)
+    woff = arr(w.woff, n + 1, np.uint64)
+    out = {"n": n, "perm": arr(w.perm, n, np.uint32), "first": arr(w.first, n, np.uint32), "woff": woff,
+           "vals": arr(w.vals, int(woff[-1]), np.float64), "parent": arr(w.parent, n, np.uint32),
+           "run_end": arr(w.run_end, n, np.uint32)}
+    L.load().lsb_skyinv_free(p)
+    return out
+
+
 def lsb_csr_permute_sym(A, perm):
     perm = np.ascontiguousarray(perm, dtype=np.uint32)
     return Matrix(L.load().lsb_csr_permute_sym(A.ptr, perm.ctypes.data_as(C.POINTER(C.c_uint))))
@@ -484,6 +528,14 @@ class Solver:
     def amg_cycle_bytes(self):
         """Bytes one application of the AMG V-cycle must move (0 without AMG)."""
         return int(L.load().lsb_hip_solver_amg_cycle_bytes(self._h))
+
+    @property
+    def direct_info(self):
+        """(entries of W, height of the elimination tree, bytes the two products of a round stream) of a direct
+        solver (KRYLOV_DIRECT); None for any other."""
+        e, h, by = C.c_ulonglong(), C.c_uint(), C.c_ulonglong()
+        rc = L.load().lsb_hip_solver_direct_info(self._h, C.byref(e), C.byref(h), C.byref(by))
+        return None if rc == 2 else (int(e.value), int(h.value), int(by.value))
 
     def amg_cheb_interval(self, level):
         """(lo, hi) of D^-1 A the Chebyshev smoother of an AMG level was built on; None where the level is not

@@ -125,7 +125,7 @@ static const struct optchoice CH_KRYLOV[] = {{"cg", LSB_KRYLOV_PCG},     {"pcg",
                                              {"cg1", LSB_KRYLOV_PCG1},   {"pcg1", LSB_KRYLOV_PCG1},
                                              {"auto", LSB_KRYLOV_AUTO},  {"gmres", LSB_KRYLOV_GMRES},
                                              {"bicgstab", LSB_KRYLOV_BICGSTAB}, {"richardson", LSB_KRYLOV_RICHARDSON},
-                                             {NULL, 0}};
+                                             {"direct", LSB_KRYLOV_DIRECT}, {NULL, 0}};
 static const struct optchoice CH_PRECISION[] = {{"fp64", LSB_PREC_FP64}, {"fp32", LSB_PREC_MIXED},
                                                 {"mixed", LSB_PREC_MIXED}, {NULL, 0}};
 #define OPT(n, t, f, c) {n, t, offsetof(struct lsb_hip_opts, f), c}

@@ -26,7 +26,8 @@
 enum pcg_form pcg_choose_form(const lsb_hip_solver *sv) {
   const struct shard *s = &sv->sh[0];
   const struct lsb_hip_opts *o = &sv->o;
-  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_BICGSTAB || o->krylov == LSB_KRYLOV_RICHARDSON)
+  if (o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_BICGSTAB || o->krylov == LSB_KRYLOV_RICHARDSON ||
+      o->krylov == LSB_KRYLOV_DIRECT)
     return PCG_NONE;
   if (o->precond == LSB_PRECOND_FSAI && !sv->multi && !s->mixed && s->variant == LSB_SPMV_SUBWAVE &&
       s->fs_g.variant == LSB_SPMV_SUBWAVE && s->fs_gt.variant == LSB_SPMV_SUBWAVE && o->sample_spmv <= 0 &&
@@ -419,7 +420,8 @@ unsigned long long lsb_hip_solver_iteration_bytes(const lsb_hip_solver *sv) {
   const struct shard *s = &sv->sh[0];
   const unsigned long long sp = lsb_hip_solver_spmv_layout_bytes(sv), n8 = 8ull * s->n;
   const unsigned vec = s->dinv_uniform ? 0u : 1u;
-  if (!sp || s->mixed || sv->ps.use || sv->o.krylov == LSB_KRYLOV_RICHARDSON) /* (a cycle: amg_cycle_bytes) */
+  if (!sp || s->mixed || sv->ps.use || sv->o.krylov == LSB_KRYLOV_RICHARDSON || /* (a cycle: amg_cycle_bytes) */
+      sv->o.krylov == LSB_KRYLOV_DIRECT)                                        /* (a round: direct_info) */
     return 0;
   if (sv->o.krylov == LSB_KRYLOV_BICGSTAB)
     return 2 * sp + n8 * (18u + 2u * vec);
@@ -522,8 +524,8 @@ void tune_blas1_nt(lsb_hip_solver *sv) {
   if (!e && generic_precond(sv) && s->nnz >= 4000000ull)
     sv->nt_mask = 63 & ~16;
   if (s->nnz < 4000000ull || generic_precond(sv) || sv->o.krylov == LSB_KRYLOV_GMRES ||
-      sv->o.krylov == LSB_KRYLOV_BICGSTAB)
-    return; /* (GMRES and BiCGSTAB run none of these sweeps) */
+      sv->o.krylov == LSB_KRYLOV_BICGSTAB || sv->o.krylov == LSB_KRYLOV_DIRECT)
+    return; /* (GMRES, BiCGSTAB and the direct solver run none of these sweeps) */
   static const int cand[] = {63, 9, 5, 0};
   const unsigned n = s->n;
   double *d_b = (double *)lsb_hip_malloc((size_t)n * sizeof(double));
@@ -575,7 +577,8 @@ void persist_setup(lsb_hip_solver *sv) {
   unsigned nzmax, rmax, gmax;
   const unsigned nmax = lsb_k_persist_limits(&nzmax, &rmax, &gmax);
   if (sv->multi || sv->nshard != 1 || o->persistent == 0 || o->sample_spmv > 0 ||
-      o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_BICGSTAB || s->n > nmax || s->n < 2 ||
+      o->krylov == LSB_KRYLOV_GMRES || o->krylov == LSB_KRYLOV_BICGSTAB || o->krylov == LSB_KRYLOV_DIRECT ||
+      s->n > nmax || s->n < 2 ||
       (o->precond != LSB_PRECOND_JACOBI && o->precond != LSB_PRECOND_NONE &&
        o->precond != LSB_PRECOND_L1JACOBI) ||
       o->precision != LSB_PREC_FP64)

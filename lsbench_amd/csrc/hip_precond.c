@@ -396,6 +396,8 @@ void precond_free_shard(struct shard *s) {
 int lsb_hip_solver_precond_dev(lsb_hip_solver *sv, const double *d_r, double *d_z) {
   if (!lsb_initialized)
     return 1;
+  if (sv && sv->dir && d_r && d_z) /* the direct solver: z = W^T W r, its one application */
+    return direct_apply_dev(sv, d_r, d_z);
   if (!sv || !d_r || !d_z || !generic_precond(sv))
     return 2;
   const double *rin = d_r;

@@ -12,7 +12,8 @@ const struct solve_driver *solve_driver_for(int krylov) {
   static const struct solve_driver of[] = {
       [LSB_KRYLOV_PCG] = {pcg_solve_dev, pcg_run},        [LSB_KRYLOV_PCG1] = {pcg_solve_dev, pcg_run},
       [LSB_KRYLOV_AUTO] = {pcg_solve_dev, pcg_run},       [LSB_KRYLOV_GMRES] = {gmres_solve_dev, NULL},
-      [LSB_KRYLOV_BICGSTAB] = {bicgstab_solve_dev, NULL}, [LSB_KRYLOV_RICHARDSON] = {richardson_solve_dev, NULL}};
+      [LSB_KRYLOV_BICGSTAB] = {bicgstab_solve_dev, NULL}, [LSB_KRYLOV_RICHARDSON] = {richardson_solve_dev, NULL},
+      [LSB_KRYLOV_DIRECT] = {direct_solve_dev, NULL}};
   if (krylov < 0 || krylov >= (int)(sizeof of / sizeof of[0]) || !of[krylov].solve)
     errx(EXIT_FAILURE, "hip_cdna4: opts.krylov = %d names no driver", krylov);
   return &of[krylov];

@@ -698,6 +698,7 @@ static struct lsb_hip_opts solver_opts(const struct lsb_hip_opts *o_in, int shar
   }
   bicgstab_check_precond(&o);
   richardson_check(&o, sharded);
+  direct_check(&o, sharded);
   if (o.precision == LSB_PREC_MIXED && o.precond == LSB_PRECOND_AMG) {
     if (!sharded)
       warnx("hip_cdna4: --precond amg runs in fp64");
@@ -715,6 +716,10 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
   struct csr *S = o.op_mode == LSB_OP_CHOLMOD_UPPER ? lsb_csr_symmetrize_upper(A)
                                                     : lsb_csr_copy_base0(A);
   const unsigned n_user = S->nrows;
+  /* the direct solver factorises first: what it refuses, it refuses before anything is allocated on the device */
+  unsigned dir_height = 0;
+  double dir_seconds = 0.0;
+  struct lsb_skyinv *dirW = o.krylov == LSB_KRYLOV_DIRECT ? direct_factor(S, &o, &dir_height, &dir_seconds) : NULL;
   /* a constant-coefficient 2-D grid whose lines are not whole slices: pad the lines (lsb_csr_pad_lines) --
    * the +-nx diagonals become whole-slice offsets and the z-column forms apply along y.  b and x
    * travel through the same gather / scatter as a re-ordering's; the pad unknowns stay exactly 0.
@@ -723,7 +728,7 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
   {
     const char *e = getenv("LSBENCH_HIP_PAD_LINES");
     const int want = e ? atoi(e) : (S->nrows >= 1000000u ? 1 : 0);
-    if (want && !o.reorder) {
+    if (want && !o.reorder && o.krylov != LSB_KRYLOV_DIRECT) { /* (which keeps the caller's numbering) */
       unsigned nx = 0, nxp = 0;
       struct csr *Sp = lsb_csr_pad_lines(S, LSB_SELL_ROWS, &nx, &nxp, &padmap);
       if (Sp) {
@@ -790,6 +795,8 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
   free(hull), free(bounds);
   lsb_csr_free(S);
   solver_finish_setup(sv);
+  if (dirW)
+    direct_upload(sv, dirW, dir_height, dir_seconds);
   return sv;
 }
 
@@ -877,6 +884,7 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
     free(sv->p2p);
   }
   bicgstab_free(sv);
+  direct_free(sv);
   mrhs_free(sv);
   blockcg_free(sv);
   shard_vec_free(&sv->sh[0], sv->d_bp), shard_vec_free(&sv->sh[0], sv->d_xp); /* shard 0's slab may hold them */

@@ -16,6 +16,7 @@
  *   hip_gmres_drv.c  GMRES(m) driver
  *   hip_bicgstab_drv.c  BiCGSTAB driver
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
+ *   hip_direct_drv.c the direct solver: factor at creation, rounds of x (+)= W^T W r on a skyline inverse factor
  *   hip_block.c      interleaved blocks of right-hand sides, what their two drivers share: the service rules, the work
  *                    area (struct block_work), Z = M^-1 R on a block, the enqueue and host-buffer wrappers
  *   hip_mrhs_drv.c   several right-hand sides: independent PCG recurrences (Jacobi, AMG, FSAI) on a CSR SpMM
@@ -102,7 +103,7 @@ struct halo_split {
 enum { SELL_NONE, SELL_32, SELL_16, SELL_TMPL, SELL_COL };
 /* the PCG iteration a solver runs (pcg_choose_form picks it once, at creation; hip_pcg.c) */
 enum pcg_form {
-  PCG_NONE,    /* GMRES, BiCGSTAB, Richardson: no PCG iteration */
+  PCG_NONE,    /* GMRES, BiCGSTAB, Richardson, the direct solver: no PCG iteration */
   PCG_CLASSIC, /* SpMV, k_pcg_update_xr, k_pcg_update_p (one shard or many) */
   PCG_SUBWAVE, /* k_spmv_subwave_p + k_pcg_update_xr: the direction update rides in the next SpMV */
   PCG_COL,     /* k_pcg_col_px + k_pcg_col_r on the z-column plan (+ k_pcg_xfix at a run's end) */
@@ -351,6 +352,20 @@ struct lsb_hip_solver {
    * and the partial count of its update sweep */
   struct graph_cache rich_graphs;
   unsigned rich_nrr;
+  /* The direct solver (hip_direct_drv.c), NULL on every other solver: the skyline inverse factor on the device and
+   * the dealing of its rows (k), t = W P r, what the factor is (entries, tree height, set-up seconds), the record
+   * count of the residual launch, and its cache of captured graphs -- keyed on the count and on x; b is in them too,
+   * so they are dropped when a solve brings another b (graph_b) */
+  struct direct_dev {
+    struct lsb_dir_dev k;
+    void *mem[9];
+    double *d_t;
+    unsigned long long entries;
+    unsigned height, nrec;
+    double setup_s;
+    struct graph_cache graphs;
+    const double *graph_b;
+  } *dir;
   /* Interleaved blocks of right-hand sides, per width kp = 2, 4, 8 and allocated on first use.  Two drivers run on
    * them -- independent recurrences (hip_mrhs_drv.c) and block-CG (hip_bcg_drv.c) -- and each keeps its OWN work
    * areas: their graph caches are keyed on the iteration count alone, and a caller may alternate the two on one
@@ -602,6 +617,27 @@ LSB_INTERNAL void lsb_k_rich_restart(unsigned n, const double *b, const double *
                                      unsigned *npartials, void *stream);
 LSB_INTERNAL void lsb_k_rich_restart_state(struct lsb_pcg_state *st, const double *parts, unsigned nparts, int more,
                                            void *stream);
+/* hip_direct_drv.c, and the launchers of hip_direct.hip */
+LSB_INTERNAL solve_dev_fn direct_solve_dev;
+/* what --krylov direct cannot run with, refused at creation (shards, persistent); what it does not consult is set
+ * aside (precond, reorder), and mixed precision falls back to fp64, said aloud */
+LSB_INTERNAL void direct_check(struct lsb_hip_opts *o, int sharded);
+/* order, count, factorise on the host: refuses an operator over the entry budget before anything is allocated, and
+ * one that is not symmetric positive definite */
+LSB_INTERNAL struct lsb_skyinv *direct_factor(const struct csr *S, const struct lsb_hip_opts *o, unsigned *height,
+                                              double *seconds);
+LSB_INTERNAL void direct_upload(lsb_hip_solver *sv, struct lsb_skyinv *W, unsigned height, double seconds); /* frees W */
+LSB_INTERNAL void direct_free(lsb_hip_solver *sv);
+LSB_INTERNAL int direct_apply_dev(lsb_hip_solver *sv, const double *d_r, double *d_z); /* z = W^T W r, once */
+LSB_INTERNAL void lsb_k_dir_init_state(struct lsb_pcg_state *st, double tol, int maxit, void *stream);
+LSB_INTERNAL void lsb_k_dir_rows(const struct lsb_dir_dev *d, const double *b, const double *r, double *t,
+                                 const struct lsb_pcg_state *st, int src, void *stream);
+LSB_INTERNAL void lsb_k_dir_cols(const struct lsb_dir_dev *d, const double *t, double *x,
+                                 const struct lsb_pcg_state *st, int mode, void *stream);
+LSB_INTERNAL void lsb_k_dir_resid(unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
+                                  const double *b, const double *x, double *r, double *records, unsigned *nrecords,
+                                  const struct lsb_pcg_state *st, void *stream);
+LSB_INTERNAL void lsb_k_dir_step(struct lsb_pcg_state *st, const double *records, unsigned nrecords, void *stream);
 /* hip_block.c: what the two drivers on interleaved blocks share */
 /* the service rules: the SpMM on blocks; the solves on blocks (the SpMM's, less an AMG cycle smoothed by multicolour
  * Gauss-Seidel); whether z = M^-1 r is a block of its own there (AMG, FSAI) or the diagonal's */

@@ -78,8 +78,11 @@ static void usage(const char *prog) {
   printf("  --maxit <N>          (hip) iteration cap, default 20000\n");
   printf("  --operator <upper|raw> (hip) upper = CHOLMOD's triu-mirrored matrix\n");
   printf("  --nvirt <P>          (hip) P row-range shards on one device (test)\n");
-  printf("  --krylov <cg|cg1|auto|gmres|bicgstab|richardson> (hip) cg1 = single-reduction CG; gmres, bicgstab for --operator raw;\n");
-  printf("                       richardson = --precond amg as the solver: V-cycles, --maxit of them at --tol 0\n");
+  printf("  --krylov <cg|cg1|auto|gmres|bicgstab|richardson|direct> (hip) cg1 = single-reduction CG; gmres, bicgstab for\n");
+  printf("                       --operator raw; richardson = --precond amg as the solver: V-cycles, --maxit of them at --tol 0;\n");
+  printf("                       direct = a sparse direct solve: nested dissection, Cholesky, the inverse factor applied in\n");
+  printf("                       two launches per round (--tol 0 --maxit 1 is the reference's direct protocol; operators of\n");
+  printf("                       a few thousand to a few tens of thousands of rows)\n");
   printf("                       (bicgstab + Jacobi is the reference's Ginkgo backend; its stop setting is --tol 1e-4)\n");
   printf("  --restart <M>        (hip) GMRES restart length, 1..32, default 30\n");
   printf("  --precond <jacobi|l1|none|cheb|bj|fsai|amg> (hip) diag(S); diag(sum_j |S_ij|); none; Chebyshev\n");

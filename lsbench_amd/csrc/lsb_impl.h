@@ -459,6 +459,17 @@ void lsb_k_blockcg_m_start(unsigned kp, unsigned n, const double *b, const doubl
 void lsb_k_blockcg_m_pass_b(unsigned kp, unsigned n, double *w, const double *z, double *p,
                             const struct lsb_blockcg_state *st, void *stream);
 
+/* ---- the direct solver (hip_direct.hip; launchers in hip_solver.h) -------------
+ * The skyline inverse factor on the device and how k_dir_rows deals it: grp[2 g] = first row of group g, grp[2 g + 1]
+ * = rows << 8 | lanes per row; blk[w] .. blk[w + 1]: the groups of workgroup w; bwin[2 w], bwin[2 w + 1]: first
+ * column and width of the window of P r its rows read.  lds_doubles: what a launch stages at the most. */
+struct lsb_dir_dev {
+  unsigned n, nblk, ngrp, lds_doubles;
+  const double *vals;
+  const unsigned long long *woff;
+  const unsigned *first, *perm, *parent, *run_end, *grp, *blk, *bwin;
+};
+
 /* ---- preconditioners with z as a vector (hip_precond_k.hip) -------------------- */
 void lsb_k_dot2(unsigned n, const double *r, const double *z, double *partials2,
                 unsigned *npartials, const struct lsb_pcg_state *st, void *stream);
