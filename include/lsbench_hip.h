@@ -930,6 +930,39 @@ int lsb_hip_solver_fsai_nnz(const lsb_hip_solver *s, unsigned long long *g, unsi
 int lsb_hip_solver_precond_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_R, size_t ldr,
                                      double *d_Z, size_t ldz);
 
+/* The direct solver on blocks of right-hand sides (LSB_KRYLOV_DIRECT; hip_direct_m.hip, hip_direct_m_drv.c): the rounds
+ * x (+)= P^T W^T (W (P r)), r = b - S x of a single direct solve on nrhs columns at once.  A block of columns reads
+ * every entry of W once per product for all of them, walks the row records once and pays the same launches -- what a
+ * cached factor is for, and what CHOLMOD's solve takes a dense B for.  Entry points of their own: solve_multi[_dev],
+ * solve_block[_dev], spmm_dev and precond_multi_dev keep answering 2 on a direct solver.
+ * The contract: a column solved in a block is, bit for bit, that column solved alone by lsb_hip_solver_solve_dev on
+ * the same solver -- x, iters, status, relres, true_relres, spmvs.  (So no MFMA: it sums in an order of its own.)
+ * Blocks as for solve_multi: column-major, ld >= n_local, the caller's numbering; only n_local doubles of a column
+ * are read or written, the slack stays the caller's.  Any nrhs >= 1: one column is forwarded to
+ * lsb_hip_solver_solve_dev / _precond_dev; 2 .. 8 run as one block of width 2, 4 or 8, padded with zero columns that
+ * are not reported; more run in blocks of 8 and a remainder.
+ * Returns 1 when the backend is not initialised; 2 for bad arguments (nrhs == 0, ld < n_local, null pointers) and for
+ * every solver that is not a direct solver -- X is untouched and nothing is allocated.  A direct solver allocates the
+ * work area of a width when it first solves a block of that width, and nothing before.
+ * res[c] is column c's own result with the single solve's meaning field by field (under tol = 0: relres =
+ * true_relres = -1, spmvs = iters - 1); seconds is the wall clock of the block the column ran in.
+ * Columns stop on their own: a column whose status has left RUNNING is frozen, the block runs until every column has
+ * stopped.  b_c = 0 -> CONVERGED after round 1, x_c = 0, relres 0; a column with a NaN -> BREAKDOWN after round 1, and
+ * it disturbs no other column; maxit = 0 -> x = 0, MAXIT; tol = 0 -> exactly maxit rounds, no residual behind the last.
+ * opts.use_graph and opts.check_every are honoured as by the single solve.  Warm starts on blocks are not built: the
+ * columns start from x0 = 0. */
+/* x_c = S^-1 b_c for c < nrhs by the direct solver's rounds, W streamed once per product for a block of columns */
+int lsb_hip_solver_solve_direct_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_B, size_t ldb,
+                                          double *d_X, size_t ldx, struct lsb_hip_result *res);
+int lsb_hip_solver_solve_direct_multi(lsb_hip_solver *s, unsigned nrhs, const double *B, size_t ldb,
+                                      double *X, size_t ldx, struct lsb_hip_result *res);   /* host buffers */
+/* Z_c = P^T W^T W P R_c once: precond_dev's application on a block */
+int lsb_hip_solver_direct_apply_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_R, size_t ldr,
+                                          double *d_Z, size_t ldz);
+/* bytes one round of a block of width kp(nrhs) streams: 16 per entry of W and 24 per row whatever the width, 32 per
+ * row and column (lsb_hip_solver_direct_info's figure at kp = 1); 0 for any other solver or nrhs == 0 */
+unsigned long long lsb_hip_solver_direct_multi_round_bytes(const lsb_hip_solver *s, unsigned nrhs);
+
 /* Block-CG proper (hip_bcg.hip, hip_bcg_drv.c): ONE Krylov space for a block of right-hand sides, where solve_multi
  * runs nrhs independent recurrences.  Preconditioned BCGrQ from x0 = 0: the residual block is kept factored as
  * R = W sigma with W^T D^-1 W = I (Cholesky-QR in the inner product of the solver's diagonal preconditioner D^-1), the

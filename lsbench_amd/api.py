@@ -537,6 +537,46 @@ class Solver:
         rc = L.load().lsb_hip_solver_direct_info(self._h, C.byref(e), C.byref(h), C.byref(by))
         return None if rc == 2 else (int(e.value), int(h.value), int(by.value))
 
+    def solve_direct_multi_dev(self, d_B, d_X):
+        """A direct solver (KRYLOV_DIRECT) on a block: x_c = S^-1 b_c for the nrhs columns held as the ROWS of two 2-D
+        device tensors, W streamed once per product for a block of columns; returns the list of their Results.  A
+        column has the bits of solve_dev on that column alone.  Any other solver raises."""
+        pb, k, ldb = self._block(d_B, "solve_direct_multi_dev")
+        px, kx, ldx = self._block(d_X, "solve_direct_multi_dev")
+        if k != kx:
+            raise ValueError("solve_direct_multi_dev: B and X hold different numbers of columns")
+        res = (L.Result * max(k, 1))()
+        L.check(L.load().lsb_hip_solver_solve_direct_multi_dev(self._h, k, pb, ldb, px, ldx, res),
+                "solve_direct_multi_dev")
+        return list(res)[:k]
+
+    def solve_direct_multi(self, B):
+        """B: numpy (n_local, nrhs) of any order.  Returns (X of the same shape, [Result, ...])."""
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != self.n_local:
+            raise ValueError("solve_direct_multi: B must be (n_local, nrhs)")
+        k = B.shape[1]
+        X = np.empty((self.n_local, k), np.float64, order="F")
+        res = (L.Result * max(k, 1))()
+        ld = max(self.n_local, 1)
+        L.check(L.load().lsb_hip_solver_solve_direct_multi(self._h, k, B.ctypes.data, ld, X.ctypes.data, ld, res),
+                "solve_direct_multi")
+        return X, list(res)[:k]
+
+    def direct_apply_multi_dev(self, d_R, d_Z):
+        """Z_c = P^T W^T W P R_c once for the nrhs columns held as the ROWS of two 2-D device tensors: a column of Z
+        has the bits of precond_dev on that column alone."""
+        pr, k, ldr = self._block(d_R, "direct_apply_multi_dev")
+        pz, kz, ldz = self._block(d_Z, "direct_apply_multi_dev")
+        if k != kz:
+            raise ValueError("direct_apply_multi_dev: R and Z hold different numbers of columns")
+        L.check(L.load().lsb_hip_solver_direct_apply_multi_dev(self._h, k, pr, ldr, pz, ldz), "direct_apply_multi_dev")
+
+    def direct_multi_round_bytes(self, nrhs):
+        """Bytes one round of a block of nrhs right-hand sides streams on a direct solver (see lsbench_hip.h); 0 for
+        any other solver."""
+        return int(L.load().lsb_hip_solver_direct_multi_round_bytes(self._h, nrhs))
+
     def amg_cheb_interval(self, level):
         """(lo, hi) of D^-1 A the Chebyshev smoother of an AMG level was built on; None where the level is not
         smoothed by one (the coarsest level, an l1-Jacobi solver, another preconditioner)."""

@@ -64,7 +64,9 @@ char *block_work_slab(lsb_hip_solver *sv, struct block_work *w, unsigned kp, uns
   w->mem = (char *)lsb_hip_malloc(nblk * blk + behind);
   LSB_CHK_HIP(hipMemsetAsync(w->mem, 0, nblk * blk + behind, g_stream));
   w->b = (double *)w->mem, w->x = (double *)(w->mem + blk), w->r = (double *)(w->mem + 2 * blk);
-  w->p = (double *)(w->mem + 3 * blk), w->q = (double *)(w->mem + 4 * blk);
+  w->p = (double *)(w->mem + 3 * blk);
+  if (nblk >= 5)
+    w->q = (double *)(w->mem + 4 * blk);
   if (nblk == 7)
     w->z = (double *)(w->mem + 5 * blk), w->t = (double *)(w->mem + 6 * blk);
   w->kp = kp;

@@ -1,4 +1,5 @@
-/* The direct solver: the host driver (kernels: hip_direct.hip; the factor: lsb_direct.c). */
+/* The direct solver: the host driver (kernels: hip_direct.hip; the factor: lsb_direct.c; its solves on blocks of
+ * right-hand sides: hip_direct_m_drv.c). */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
@@ -131,6 +132,9 @@ void direct_upload(lsb_hip_solver *sv, struct lsb_skyinv *W, unsigned height, do
     blk[nblk] = g, bwin[2 * nblk] = wlo, bwin[2 * nblk + 1] = ww, nblk++;
     if (ww <= DIR_LDS_CAP && ww > widest)
       widest = ww;
+    for (unsigned q = 0; q < 3; q++) /* ... and of k_dir_rows_m at 2, 4, 8 columns: ww kp doubles within the same cap */
+      if (ww <= DIR_LDS_CAP / (2u << q) && ww > d->lds_m[q])
+        d->lds_m[q] = ww;
     g = g1;
   }
   blk[nblk] = ngrp;
@@ -161,6 +165,7 @@ void direct_free(lsb_hip_solver *sv) {
   if (!d)
     return;
   graph_drop(&d->graphs);
+  direct_multi_free(sv);
   for (unsigned i = 0; i < sizeof d->mem / sizeof d->mem[0]; i++)
     lsb_hip_free(d->mem[i]);
   lsb_hip_free(d->d_t);

@@ -99,8 +99,11 @@ void drop_graphs(lsb_hip_solver *sv) {
   graph_drop(&sv->rich_graphs);
   if (sv->dir)
     graph_drop(&sv->dir->graphs);
-  for (int k = 0; k < 3; k++)
+  for (int k = 0; k < 3; k++) {
     graph_drop(&sv->mr[k].blk.g), graph_drop(&sv->bk[k].blk.g);
+    if (sv->dir)
+      graph_drop(&sv->dir->m[k].blk.g);
+  }
 }
 
 /* ---- the loop --------------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@
  *   hip_bicgstab_drv.c  BiCGSTAB driver
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
  *   hip_direct_drv.c the direct solver: factor at creation, rounds of x (+)= W^T W r on a skyline inverse factor
+ *   hip_direct_m_drv.c  ... on blocks of right-hand sides: W streamed once per product for a block of columns
  *   hip_block.c      interleaved blocks of right-hand sides, what their two drivers share: the service rules, the work
  *                    area (struct block_work), Z = M^-1 R on a block, the enqueue and host-buffer wrappers
  *   hip_mrhs_drv.c   several right-hand sides: independent PCG recurrences (Jacobi, AMG, FSAI) on a CSR SpMM
@@ -355,7 +356,11 @@ struct lsb_hip_solver {
   /* The direct solver (hip_direct_drv.c), NULL on every other solver: the skyline inverse factor on the device and
    * the dealing of its rows (k), t = W P r, what the factor is (entries, tree height, set-up seconds), the record
    * count of the residual launch, and its cache of captured graphs -- keyed on the count and on x; b is in them too,
-   * so they are dropped when a solve brings another b (graph_b) */
+   * so they are dropped when a solve brings another b (graph_b).  Blocks of right-hand sides (hip_direct_m_drv.c): the
+   * widest window of P V that k_dir_rows_m stages per width kp = 2, 4, 8, in rows (lds_m), and a work area per width,
+   * made when the solver first solves a block of that width (m: blk.kp != 0) -- interleaved B, X, R and T = W P V
+   * (blk.b, .x, .r, .p), behind them the records of the residual launch and the state; its graphs are keyed on the
+   * count alone (blk.g), its hint is the rounds the previous block of this width took */
   struct direct_dev {
     struct lsb_dir_dev k;
     void *mem[9];
@@ -365,6 +370,13 @@ struct lsb_hip_solver {
     double setup_s;
     struct graph_cache graphs;
     const double *graph_b;
+    unsigned lds_m[3];
+    struct dirm_work {
+      struct block_work blk;
+      double *rec;
+      struct lsb_mrhs_state *st;
+      unsigned nrec, hint;
+    } m[3];
   } *dir;
   /* Interleaved blocks of right-hand sides, per width kp = 2, 4, 8 and allocated on first use.  Two drivers run on
    * them -- independent recurrences (hip_mrhs_drv.c) and block-CG (hip_bcg_drv.c) -- and each keeps its OWN work
@@ -638,6 +650,19 @@ LSB_INTERNAL void lsb_k_dir_resid(unsigned n, const int *offs, const int *cols, 
                                   const double *b, const double *x, double *r, double *records, unsigned *nrecords,
                                   const struct lsb_pcg_state *st, void *stream);
 LSB_INTERNAL void lsb_k_dir_step(struct lsb_pcg_state *st, const double *records, unsigned nrecords, void *stream);
+/* hip_direct_m_drv.c: the direct solver on blocks of right-hand sides, and the launchers of hip_direct_m.hip (kp: 2, 4
+ * or 8; interleaved blocks; st: the gate, NULL in rows_m / cols_m for one un-gated application that reads b and stores) */
+LSB_INTERNAL void direct_multi_free(lsb_hip_solver *sv); /* the work areas of every width */
+LSB_INTERNAL void lsb_k_dir_init_state_m(struct lsb_mrhs_state *st, unsigned kp, double tol, int maxit, void *stream);
+LSB_INTERNAL void lsb_k_dir_rows_m(unsigned kp, const struct lsb_dir_dev *d, unsigned lds_rows, const double *b,
+                                   const double *r, double *t, const struct lsb_mrhs_state *st, void *stream);
+LSB_INTERNAL void lsb_k_dir_cols_m(unsigned kp, const struct lsb_dir_dev *d, const double *t, double *x,
+                                   const struct lsb_mrhs_state *st, void *stream);
+LSB_INTERNAL void lsb_k_dir_resid_m(unsigned kp, unsigned n, const int *offs, const int *cols, const double *vals,
+                                    unsigned lanes, const double *b, const double *x, double *r, double *records,
+                                    unsigned *nrecords, const struct lsb_mrhs_state *st, void *stream);
+LSB_INTERNAL void lsb_k_dir_step_m(unsigned kp, struct lsb_mrhs_state *st, const double *records, unsigned nrecords,
+                                   void *stream);
 /* hip_block.c: what the two drivers on interleaved blocks share */
 /* the service rules: the SpMM on blocks; the solves on blocks (the SpMM's, less an AMG cycle smoothed by multicolour
  * Gauss-Seidel); whether z = M^-1 r is a block of its own there (AMG, FSAI) or the diagonal's */
@@ -650,8 +675,9 @@ LSB_INTERNAL unsigned block_fsai_lanes(const lsb_hip_solver *sv, const struct fs
 /* 1: a call on nrhs columns (max_nrhs != 0: no more than that) with leading dimensions lda, ldb is refused */
 LSB_INTERNAL int block_args_bad(const lsb_hip_solver *sv, unsigned nrhs, unsigned max_nrhs, const void *a, size_t lda,
                                 const void *b, size_t ldb);
-/* The slab of a work area, zeroed: nblk blocks of n kp doubles (the five; 7: z and t behind them), then `behind`
- * bytes of the owner's, whose address it returns.  The first slab of a solver reads the lanes per row. */
+/* The slab of a work area, zeroed: nblk blocks of n kp doubles (the five; 7: z and t behind them; 4: b, x, r, p alone,
+ * the direct solver's), then `behind` bytes of the owner's, whose address it returns.  The first slab of a solver reads
+ * the lanes per row. */
 LSB_INTERNAL char *block_work_slab(lsb_hip_solver *sv, struct block_work *w, unsigned kp, unsigned nblk, size_t behind);
 /* z where the slab does not hold it, zeroed.  FSAI: z, t and `behind` bytes of the owner's (returned) in zmem.
  * AMG: the cycle's block vectors with z at their head; behind must be 0, returns NULL. */
