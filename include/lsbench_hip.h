@@ -963,6 +963,47 @@ int lsb_hip_solver_direct_apply_multi_dev(lsb_hip_solver *s, unsigned nrhs, cons
  * row and column (lsb_hip_solver_direct_info's figure at kp = 1); 0 for any other solver or nrhs == 0 */
 unsigned long long lsb_hip_solver_direct_multi_round_bytes(const lsb_hip_solver *s, unsigned nrhs);
 
+/* AMG as the solver on blocks of right-hand sides (hip_rich_m.hip, hip_rich_m_drv.c; the fp32 cycle on blocks:
+ * hip_amg_f32_m.hip): the stationary V-cycle iteration of LSB_KRYLOV_RICHARDSON -- x = 0, r = b; per cycle z = M^-1 r,
+ * q = S z, x += z, r -= q -- on nrhs columns at once.  A cycle is streams of the hierarchy's matrices, one product
+ * with S and six vector passes; a block of columns reads each of those matrices once for all of its columns.  This
+ * is the protocol of the reference's AMG backends on a block: maxit 2, tol 0 with the fp64 cycle, maxit 1, tol 0 with
+ * the fp32 cycle.  Entry points of their own: solve_multi[_dev], solve_block[_dev], spmm_dev and precond_multi_dev keep
+ * answering 2 on such a solver.
+ * Served: krylov = LSB_KRYLOV_RICHARDSON with precond = LSB_PRECOND_AMG, one shard in one process, LSB_PREC_FP64
+ * values, smoothed by l1-Jacobi with the cycle in fp64 or in fp32 (LSB_AMG_PREC_FP32), or by the Chebyshev smoother
+ * with the cycle in fp64.  Returns 1 when the backend is not initialised; 2 for bad arguments (nrhs == 0,
+ * ld < n_local, null pointers) and for every other solver -- multicolour Gauss-Seidel, the Chebyshev smoother in fp32
+ * and AMG under PCG among them; X (or Z) is untouched then and nothing is allocated.  A served solver allocates the
+ * work area of a width when it first sees a block of that width, and nothing before.
+ * Blocks as for solve_multi: column-major, ld >= n_local, the caller's numbering (re-ordered and line-padded solvers
+ * are served); only n_local doubles of a column are read or written.  Any nrhs >= 1: one column is forwarded to
+ * lsb_hip_solver_solve_dev / _precond_dev; 2 .. 8 run as one block of width Kp = 2, 4 or 8, padded with zero columns
+ * that are not reported; more run in blocks of 8 and a remainder.
+ * opts.tol, maxit, check_every, use_graph and verify mean per column what they mean for the single solve, and res[c]
+ * is column c's own result with the single solve's meaning field by field: spmvs = iters + the residuals recomputed
+ * under opts.verify, true_relres = -1 without it; seconds is the wall clock of the block the column ran in.
+ * Columns stop on their own: a column whose status has left RUNNING is frozen -- its x is no longer written -- and
+ * the block runs until every column has stopped.  b_c = 0 -> CONVERGED, 0 cycles, x_c = 0; a column with a NaN ->
+ * BREAKDOWN at cycle 1, and it disturbs no other column; maxit = 0 -> x = 0, MAXIT; tol = 0 -> exactly maxit cycles.
+ * A column's x, iters, status and relres do not depend on the width of the block or on the other columns: its
+ * z = M^-1 r has the bits of lsb_hip_solver_precond_dev, its q = S z those of lsb_hip_solver_spmm_dev, x + z and r - q
+ * are single operations, and r.r is summed in the single solve's order.  Warm starts on blocks are not built. */
+/* x_c ~ S^-1 b_c for c < nrhs by stationary V-cycle iterations from x0 = 0; res[c] is column c's own result */
+int lsb_hip_solver_amg_solve_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_B, size_t ldb,
+                                       double *d_X, size_t ldx, struct lsb_hip_result *res);
+int lsb_hip_solver_amg_solve_multi(lsb_hip_solver *s, unsigned nrhs, const double *B, size_t ldb,
+                                   double *X, size_t ldx, struct lsb_hip_result *res);   /* host buffers */
+/* Z_c = M^-1 R_c, one V-cycle per column in the precision the solver cycles in: column c of Z has the bits of
+ * lsb_hip_solver_precond_dev on column c alone */
+int lsb_hip_solver_amg_cycle_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_R, size_t ldr,
+                                       double *d_Z, size_t ldz);
+/* bytes one cycle of a block of width Kp(nrhs) must move: the V-cycle's matrix bytes once whatever the width and its
+ * vector bytes per column (the two parts of lsb_hip_solver_amg_cycle_bytes, fp64 or fp32), 12 nnz + 16 n Kp for the
+ * SpMM, and the update's six vector passes per column, 48 n Kp; nrhs = 1: the single solve's cycle.  0 for a solver
+ * that is not served and for nrhs == 0 */
+unsigned long long lsb_hip_solver_amg_solve_multi_bytes(const lsb_hip_solver *s, unsigned nrhs);
+
 /* Block-CG proper (hip_bcg.hip, hip_bcg_drv.c): ONE Krylov space for a block of right-hand sides, where solve_multi
  * runs nrhs independent recurrences.  Preconditioned BCGrQ from x0 = 0: the residual block is kept factored as
  * R = W sigma with W^T D^-1 W = I (Cholesky-QR in the inner product of the solver's diagonal preconditioner D^-1), the

@@ -311,6 +311,10 @@ SIGNATURES = {
     "lsb_hip_solver_solve_direct_multi": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_direct_apply_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
     "lsb_hip_solver_direct_multi_round_bytes": (C.c_ulonglong, [_vp, _u]),
+    "lsb_hip_solver_amg_solve_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
+    "lsb_hip_solver_amg_solve_multi": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
+    "lsb_hip_solver_amg_cycle_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "lsb_hip_solver_amg_solve_multi_bytes": (C.c_ulonglong, [_vp, _u]),
     "lsb_hip_solver_amg_cheb_interval": (_i, [_vp, _u, C.POINTER(_d), C.POINTER(_d)]),
     "lsb_hip_solver_amg_colours": (_i, [_vp, _u, C.POINTER(_u)]),
     "lsb_hip_solver_cheb_interval": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),

@@ -577,6 +577,46 @@ class Solver:
         any other solver."""
         return int(L.load().lsb_hip_solver_direct_multi_round_bytes(self._h, nrhs))
 
+    def amg_solve_multi_dev(self, d_B, d_X):
+        """AMG as the solver (KRYLOV_RICHARDSON, PRECOND_AMG) on a block: stationary V-cycle iterations from x0 = 0 for
+        the nrhs columns held as the ROWS of two 2-D device tensors, the hierarchy streamed once per cycle for a block
+        of columns; returns the list of their Results.  A column's x, iters, status and relres do not depend on the
+        block it runs in.  A solver that is not served raises."""
+        pb, k, ldb = self._block(d_B, "amg_solve_multi_dev")
+        px, kx, ldx = self._block(d_X, "amg_solve_multi_dev")
+        if k != kx:
+            raise ValueError("amg_solve_multi_dev: B and X hold different numbers of columns")
+        res = (L.Result * max(k, 1))()
+        L.check(L.load().lsb_hip_solver_amg_solve_multi_dev(self._h, k, pb, ldb, px, ldx, res), "amg_solve_multi_dev")
+        return list(res)[:k]
+
+    def amg_solve_multi(self, B):
+        """B: numpy (n_local, nrhs) of any order.  Returns (X of the same shape, [Result, ...])."""
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != self.n_local:
+            raise ValueError("amg_solve_multi: B must be (n_local, nrhs)")
+        k = B.shape[1]
+        X = np.empty((self.n_local, k), np.float64, order="F")
+        res = (L.Result * max(k, 1))()
+        ld = max(self.n_local, 1)
+        L.check(L.load().lsb_hip_solver_amg_solve_multi(self._h, k, B.ctypes.data, ld, X.ctypes.data, ld, res),
+                "amg_solve_multi")
+        return X, list(res)[:k]
+
+    def amg_cycle_multi_dev(self, d_R, d_Z):
+        """Z = M^-1 R, one V-cycle per column in the precision the solver cycles in, for the nrhs columns held as the
+        ROWS of two 2-D device tensors: a column of Z has the bits of precond_dev on that column alone."""
+        pr, k, ldr = self._block(d_R, "amg_cycle_multi_dev")
+        pz, kz, ldz = self._block(d_Z, "amg_cycle_multi_dev")
+        if k != kz:
+            raise ValueError("amg_cycle_multi_dev: R and Z hold different numbers of columns")
+        L.check(L.load().lsb_hip_solver_amg_cycle_multi_dev(self._h, k, pr, ldr, pz, ldz), "amg_cycle_multi_dev")
+
+    def amg_solve_multi_bytes(self, nrhs):
+        """Bytes one cycle of amg_solve_multi on a block of nrhs right-hand sides must move (see lsbench_hip.h); 0 for
+        a solver that is not served."""
+        return int(L.load().lsb_hip_solver_amg_solve_multi_bytes(self._h, nrhs))
+
     def amg_cheb_interval(self, level):
         """(lo, hi) of D^-1 A the Chebyshev smoother of an AMG level was built on; None where the level is not
         smoothed by one (the coarsest level, an l1-Jacobi solver, another preconditioner)."""

@@ -1,7 +1,7 @@
 /* AMG on the host side (LSB_PRECOND_AMG; hierarchy: lsb_amg.c; kernels: hip_amg.hip, hip_amg_cheb.hip,
- * hip_amg_f32.hip, hip_amg_mcgs.hip, hip_mrhs_amg.hip): the upload of the hierarchy at solver creation (untimed), the
- * ONE schedule of the V-cycle that all three flavours run -- fp64 or fp32 on one column, fp64 on blocks of columns --
- * and what the C-ABI answers about it. */
+ * hip_amg_f32.hip, hip_amg_f32_m.hip, hip_amg_mcgs.hip, hip_mrhs_amg.hip): the upload of the hierarchy at solver
+ * creation (untimed), the ONE schedule of the V-cycle that all four flavours run -- fp64 or fp32, on one column or on
+ * blocks of columns -- and what the C-ABI answers about it. */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
@@ -194,6 +194,20 @@ static void amg_report(const struct amg_dev *a, const struct lsb_amg_hier *h, do
                     "%llu in fp64\n", a->cycle_bytes32, a->cycle_mat_bytes + 8ull * a->cycle_vec_rows);
 }
 
+/* What one cycle streams in the precision it runs in, in two parts: its matrices, and its vector passes (on blocks:
+ * per column).  fp64: cycle_mat_bytes and 8 B per element pass.  fp32: 8 B per entry, 4 nc^2, 4 B per element pass;
+ * level 0: r read, z written at 8 B, the copy of r written */
+void amg_cycle_bytes_split(const struct amg_dev *a, unsigned long long *mat, unsigned long long *vec) {
+  const unsigned long long nc2 = (unsigned long long)a->nc * a->nc;
+  if (a->prec == LSB_AMG_PREC_FP32) {
+    *mat = (a->cycle_mat_bytes - 8ull * nc2) / 3ull * 2ull + 4ull * nc2;
+    *vec = 4ull * a->cycle_vec_rows + (a->nlev > 1 ? 12ull * a->lv[0].n : 8ull * a->nc);
+  } else {
+    *mat = a->cycle_mat_bytes;
+    *vec = 8ull * a->cycle_vec_rows;
+  }
+}
+
 void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const double *vals,
                        const struct lsb_hip_opts *o) {
   /* options and refusals */
@@ -271,9 +285,11 @@ void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const 
   }
   a->cycle_mat_bytes += 8ull * h->nc * h->nc;
   a->cycle_vec_rows += 2ull * h->nc;
-  if (f32) /* 8 B per entry, 4 nc^2, 4 B per element pass; level 0: r read, z written at 8 B, the copy of r written */
-    a->cycle_bytes32 = (a->cycle_mat_bytes - 8ull * h->nc * h->nc) / 3ull * 2ull + 4ull * h->nc * h->nc +
-                       4ull * a->cycle_vec_rows + (h->nlev > 1 ? 12ull * h->lv[0].n : 8ull * h->nc);
+  if (f32) {
+    unsigned long long mat, vec;
+    amg_cycle_bytes_split(a, &mat, &vec);
+    a->cycle_bytes32 = mat + vec;
+  }
   if (f32)
     a->d_cinv = amg_upload_f32(a, h->coarse_inv, (size_t)h->nc * h->nc, "the coarse inverse");
   else
@@ -348,25 +364,48 @@ char *amg_block_vecs(const struct amg_dev *a, unsigned kp, struct amg_vecs *v) {
   return base;
 }
 
+/* its counterpart for the fp32 cycle on blocks (hip_amg_f32_m.hip): Z, an fp64 block, then four blocks of interleaved
+ * floats per level -- the fine level too, whose b is the float copy of the caller's R.  No direction blocks: the
+ * Chebyshev smoother is not built there */
+char *amg_block_vecs32(const struct amg_dev *a, unsigned kp, struct amg_vecs *v) {
+#define BLOCK_BYTES(l, cnt, elem) (((cnt) * (size_t)a->lv[l].n * kp * (elem) + 255) & ~(size_t)255)
+  const size_t zb = BLOCK_BYTES(0, 1, sizeof(double));
+  size_t total = zb;
+  for (unsigned l = 0; l < a->nlev; l++)
+    total += 4 * BLOCK_BYTES(l, 1, sizeof(float));
+  char *base = (char *)lsb_hip_malloc(total), *p = base + zb;
+  LSB_CHK_HIP(hipMemsetAsync(base, 0, total, g_stream));
+  for (unsigned l = 0; l < a->nlev; l++) {
+    const size_t nl = BLOCK_BYTES(l, 1, sizeof(float));
+    v[l].b = p, v[l].out = p + nl, v[l].tmp = p + 2 * nl, v[l].r = p + 3 * nl;
+    p += 4 * nl;
+  }
+#undef BLOCK_BYTES
+  return base;
+}
+
 /* ---- the V-cycle ------------
  * amg_cycle is the only place that knows the step order and the ping-pong parity.  The helpers above it pick the
  * launcher of the run's flavour, and each holds what is particular to a flavour at its step:
  *   AMG_F64  one column in fp64 (hip_amg.hip)
  *   AMG_F32  one column in fp32 (hip_amg_f32.hip): float vectors between the caller's fp64 r and z
  *   AMG_BLK  kp interleaved columns in fp64 (hip_mrhs_amg.hip, hip_amg_cheb.hip): each column with AMG_F64's bits
+ *   AMG_BLK32  kp interleaved columns in fp32 (hip_amg_f32_m.hip; l1-Jacobi only): each column with AMG_F32's bits,
+ *            float blocks between the fp64 blocks R and Z
  * Under the Chebyshev smoother the smoothing steps are the polynomial's: the same count and parity, d in place.
- * A level smoothed by multicolour Gauss-Seidel (lv[l].ncol > 0; AMG_F64 and AMG_F32 only) is the other case: its
+ * A level smoothed by multicolour Gauss-Seidel (lv[l].ncol > 0; one column only) is the other case: its
  * iterate stays in ONE buffer, the level's out, and a step is a sweep of ncol launches in place (hip_amg_mcgs.hip). */
-enum amg_flavour { AMG_F64, AMG_F32, AMG_BLK };
+enum amg_flavour { AMG_F64, AMG_F32, AMG_BLK, AMG_BLK32 };
 
 static enum amg_flavour amg_flavour(const struct amg_run *c) {
-  return c->kp ? AMG_BLK : c->a->prec == LSB_AMG_PREC_FP32 ? AMG_F32 : AMG_F64;
+  const int f32 = c->a->prec == LSB_AMG_PREC_FP32;
+  return c->kp ? (f32 ? AMG_BLK32 : AMG_BLK) : f32 ? AMG_F32 : AMG_F64;
 }
 
 /* level l's vectors; under fp64 level 0's b and out are the caller's r and z */
 static struct amg_vecs amg_vecs_at(const struct amg_run *c, unsigned l) {
   struct amg_vecs v = c->vec[l];
-  if (l == 0 && amg_flavour(c) != AMG_F32)
+  if (l == 0 && c->a->prec != LSB_AMG_PREC_FP32)
     v.b = (void *)c->r, v.out = c->z;
   return v;
 }
@@ -414,6 +453,12 @@ static void amg_smooth(const struct amg_run *c, unsigned l, const struct amg_vec
     else
       lsb_k_amg_csr_m(c->kp, LSB_AMG_SWEEP, &L->A.d, x, v->b, L->minv, y, rec, nrec, c->mst, g_stream);
     break;
+  case AMG_BLK32: /* (l1-Jacobi, no records: amg_cycle has checked) */
+    if (!x)
+      lsb_k_amg32_first_m(c->kp, L->n, l == 0, l ? v->b : c->r, L->minv, y, v->b, c->mst, g_stream);
+    else
+      lsb_k_amg32_csr_m(c->kp, LSB_AMG_SWEEP, &L->A.f, x, v->b, L->minv, y, y64, c->mst, g_stream);
+    break;
   }
 }
 
@@ -450,6 +495,7 @@ static void amg_csr(const struct amg_run *c, int mode, const union amg_mat *m, c
   case AMG_F64: lsb_k_amg_csr(mode, &m->d, x, b, minv, y, c->st, g_stream); break;
   case AMG_F32: lsb_k_amg32_csr(mode, &m->f, x, b, minv, y, NULL, c->st, g_stream); break;
   case AMG_BLK: lsb_k_amg_csr_m(c->kp, mode, &m->d, x, b, minv, y, NULL, NULL, c->mst, g_stream); break;
+  case AMG_BLK32: lsb_k_amg32_csr_m(c->kp, mode, &m->f, x, b, minv, y, NULL, c->mst, g_stream); break;
   }
 }
 
@@ -471,6 +517,12 @@ static void amg_coarse(const struct amg_run *c, unsigned l) {
     if (l == 0 && c->records)
       lsb_k_amg_dot2_m(c->kp, a->lv[0].n, c->r, c->z, c->records, c->nrecords, c->mst, g_stream);
     break;
+  case AMG_BLK32:
+    if (l)
+      lsb_k_amg32_dense_m(c->kp, a->nc, a->clanes, 0, a->d_cinv, v.b, v.out, c->mst, g_stream);
+    else
+      lsb_k_amg32_dense_m(c->kp, a->nc, a->clanes, 1, a->d_cinv, c->r, c->z, c->mst, g_stream);
+    break;
   }
 }
 
@@ -485,8 +537,11 @@ static void amg_coarse(const struct amg_run *c, unsigned l) {
 void amg_cycle(const struct amg_run *c) {
   const struct amg_dev *a = c->a;
   const unsigned nu = a->nu;
-  if (a->mcgs && amg_flavour(c) == AMG_BLK)
+  if (a->mcgs && c->kp)
     errx(EXIT_FAILURE, "hip_cdna4: cannot happen: a V-cycle on blocks of columns under --amg-smoother mcgs");
+  if (amg_flavour(c) == AMG_BLK32 && (a->cheb || c->records))
+    errx(EXIT_FAILURE, "hip_cdna4: cannot happen: the fp32 V-cycle on blocks of columns %s",
+         a->cheb ? "under --amg-smoother cheb" : "asked for records");
   const int tail = amg_flavour(c) == AMG_F64 && a->tail < a->nlev;
   const unsigned top = tail ? a->tail : a->nlev - 1;
   for (unsigned l = 0; l < top; l++) {

@@ -28,7 +28,8 @@
 //
 // No atomics, no allocation, no synchronisation inside an application: every output row is one lane group's
 // fixed-order reduction, so z is bitwise repeatable.  Every kernel is a no-op once the solve's state has left
-// RUNNING.  Not built: the one-launch tail, blocks of columns.
+// RUNNING.  Blocks of columns: hip_amg_f32_m.hip (l1-Jacobi; each column with this file's bits).  Not built: the
+// one-launch tail.
 #include "hip_kcommon.h"
 
 #define AMG32_WG 256

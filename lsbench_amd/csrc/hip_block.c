@@ -1,5 +1,6 @@
-/* Interleaved blocks of right-hand sides: what their two drivers -- independent recurrences (hip_mrhs_drv.c) and
- * block-CG (hip_bcg_drv.c) -- share on the host.  The contracts (what is served, the gates, verify) are the drivers'. */
+/* Interleaved blocks of right-hand sides: what their drivers -- independent recurrences (hip_mrhs_drv.c), block-CG
+ * (hip_bcg_drv.c), the direct solver (hip_direct_m_drv.c) and AMG as the solver (hip_rich_m_drv.c) -- share on the
+ * host.  The contracts (what is served, the gates, verify) are the drivers'. */
 #define _GNU_SOURCE
 #include "hip_solver.h"
 
@@ -83,7 +84,7 @@ char *block_work_z(lsb_hip_solver *sv, struct block_work *w, size_t behind) {
   }
   const struct amg_dev *a = sv->sh[0].amg;
   w->av = lsb_calloc(struct amg_vecs, a->nlev);
-  w->amg_mem = amg_block_vecs(a, w->kp, w->av);
+  w->amg_mem = a->prec == LSB_AMG_PREC_FP32 ? amg_block_vecs32(a, w->kp, w->av) : amg_block_vecs(a, w->kp, w->av);
   w->z = (double *)w->amg_mem;
   return NULL;
 }

@@ -1,5 +1,5 @@
 // What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_fsai.hip, hip_mrhs_amg.hip,
-// hip_amg_cheb.hip, hip_bcg.hip, hip_bcg_m.hip) share: the 16-byte pair of the interleaved blocks and its store gated
+// hip_amg_cheb.hip, hip_amg_f32_m.hip, hip_rich_m.hip, hip_bcg.hip, hip_bcg_m.hip) share: the 16-byte pair of the interleaved blocks and its store gated
 // per column, the fixed-order reductions of their per-column records, the verify round's decision, the row rule of
 // their CSR row kernels (block_row_product), the Gram triangle dealt over a row's lanes, and the launchers' dispatch
 // on the batch width and on the lanes per row.  Included by those files only, after hip_kcommon.h.

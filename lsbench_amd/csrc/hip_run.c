@@ -100,7 +100,7 @@ void drop_graphs(lsb_hip_solver *sv) {
   if (sv->dir)
     graph_drop(&sv->dir->graphs);
   for (int k = 0; k < 3; k++) {
-    graph_drop(&sv->mr[k].blk.g), graph_drop(&sv->bk[k].blk.g);
+    graph_drop(&sv->mr[k].blk.g), graph_drop(&sv->bk[k].blk.g), graph_drop(&sv->rm[k].blk.g);
     if (sv->dir)
       graph_drop(&sv->dir->m[k].blk.g);
   }

@@ -885,6 +885,7 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
   }
   bicgstab_free(sv);
   direct_free(sv);
+  richm_free(sv);
   mrhs_free(sv);
   blockcg_free(sv);
   shard_vec_free(&sv->sh[0], sv->d_bp), shard_vec_free(&sv->sh[0], sv->d_xp); /* shard 0's slab may hold them */

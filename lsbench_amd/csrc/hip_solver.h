@@ -18,6 +18,7 @@
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
  *   hip_direct_drv.c the direct solver: factor at creation, rounds of x (+)= W^T W r on a skyline inverse factor
  *   hip_direct_m_drv.c  ... on blocks of right-hand sides: W streamed once per product for a block of columns
+ *   hip_rich_m_drv.c ... AMG as the solver on blocks of right-hand sides: the hierarchy streamed once per cycle
  *   hip_block.c      interleaved blocks of right-hand sides, what their two drivers share: the service rules, the work
  *                    area (struct block_work), Z = M^-1 R on a block, the enqueue and host-buffer wrappers
  *   hip_mrhs_drv.c   several right-hand sides: independent PCG recurrences (Jacobi, AMG, FSAI) on a CSR SpMM
@@ -86,7 +87,8 @@ struct block_work {
   };
   /* z = M^-1 (.) as a block of its own, and what forming it needs.  FSAI: z and t = G (.) are two blocks, of the slab
    * or -- block_work_z -- of zmem.  AMG: z is the head of amg_mem, the cycle's vectors of every level at this width
-   * (amg_block_vecs, av; level 0: b and out are the r and z of the call). */
+   * (amg_block_vecs, av; level 0: b and out are the r and z of the call; the fp32 cycle: amg_block_vecs32, float
+   * blocks on every level behind the fp64 z). */
   double *z, *t;
   char *zmem, *amg_mem;
   struct amg_vecs *av;
@@ -403,6 +405,18 @@ struct lsb_hip_solver {
     unsigned hint;             /* SpMMs the previous block of this width took */
   } bk[3];
   struct lsb_blockcg_state *bk_hst; /* pinned, 2 slots; slot 0 keeps the last block's final state */
+  /* AMG as the solver on blocks (hip_rich_m_drv.c): a work area per width, made when the solver first sees a block of
+   * that width -- interleaved B, X, R and Q = S Z (blk.b, .x, .r, .p), Z at the head of the cycle's block vectors
+   * (blk.z, blk.amg_mem, blk.av: fp64 or fp32 as the solver cycles); behind the four blocks the records of the SpMM,
+   * which nobody reads, those of the sweeps, and the state, polled through mr_hst.  Its graphs are keyed on the count
+   * alone (blk.g); hint: the cycles the previous block of this width and each of its restarts took */
+  struct richm_work {
+    struct block_work blk;
+    double *rec_spmm, *rec;
+    struct lsb_mrhs_state *st;
+    unsigned nrec;
+    unsigned hint[LSB_MAX_CORRECTIONS + 1];
+  } rm[3];
   hipEvent_t ev_poll[2], ev_vec, ev_halo;
   hipEvent_t ev[4 * MAX_SAMPLES], ev_t0, ev_t1; /* per sample: e0 SpMV e1 e2 e3 */
   unsigned char samp_skip[MAX_SAMPLES];         /* the sample brackets nothing (a run's first iteration in the
@@ -590,10 +604,13 @@ LSB_INTERNAL void precond_shard_amg(struct shard *s, const int *offs, const int 
                                     const struct lsb_hip_opts *o);
 LSB_INTERNAL void amg_finish_setup(struct shard *s); /* behind d_zfull: level 0's two vectors out of the slab */
 LSB_INTERNAL void amg_free(struct shard *s);
+/* bytes one cycle streams in the solver's precision: its matrices, its vector passes (lsb_hip_solver_amg_cycle_bytes is
+ * their sum; a block of kp columns streams mat + kp vec) */
+LSB_INTERNAL void amg_cycle_bytes_split(const struct amg_dev *a, unsigned long long *mat, unsigned long long *vec);
 /* One application of the V-cycle, described on the caller's stack: z = M^-1 r in the solver's precision (kp = 0: one
- * column, vec = a->vec) or Z = M^-1 R on interleaved blocks of kp columns (fp64; vec = the block_work's).  r and z are
- * fp64 and may be anywhere.  records != NULL (blocks): where the launch that writes Z leaves (r_c . z_c, r_c . r_c) of
- * every column, and their number.  The gate of the launches: st (one column) or mst (blocks), NULL: always run. */
+ * column, vec = a->vec) or Z = M^-1 R on interleaved blocks of kp columns (vec = the block_work's; the cycle in fp32
+ * takes no records and has no Chebyshev smoother there).  r and z are fp64 and may be anywhere.  records != NULL
+ * (blocks): where the launch that writes Z leaves (r_c . z_c, r_c . r_c) of every column, and their number.  The gate of the launches: st (one column) or mst (blocks), NULL: always run. */
 struct amg_run {
   const struct amg_dev *a;
   const struct amg_vecs *vec;
@@ -607,6 +624,18 @@ LSB_INTERNAL void amg_cycle(const struct amg_run *c);
 /* the cycle's vectors at width kp, zeroed: 256-byte aligned pieces of one allocation, which it returns -- Z, level 0's
  * tmp and r, four vectors per coarser level, then the Chebyshev smoother's direction blocks; fills v[0 .. nlev) */
 LSB_INTERNAL char *amg_block_vecs(const struct amg_dev *a, unsigned kp, struct amg_vecs *v);
+/* the same for the fp32 cycle on blocks: Z (fp64), then b, out, tmp, r as blocks of interleaved floats per level */
+LSB_INTERNAL char *amg_block_vecs32(const struct amg_dev *a, unsigned kp, struct amg_vecs *v);
+/* the launchers of hip_amg_f32_m.hip: lsb_k_amg32_first / _csr / _dense on blocks of kp = 2, 4 or 8 interleaved float
+ * columns, per column bit for bit; in64 / b32, y64, ends64 as theirs, on fp64 blocks in hip_mrhs.hip's layout; st: a
+ * no-op once st->running == 0 (NULL: always run) */
+LSB_INTERNAL void lsb_k_amg32_first_m(unsigned kp, unsigned n, int in64, const void *b, const float *minv, float *x,
+                                      float *b32, const struct lsb_mrhs_state *st, void *stream);
+LSB_INTERNAL void lsb_k_amg32_csr_m(unsigned kp, int mode, const struct amg_mat32 *m, const float *xin, const float *b,
+                                    const float *minv, float *y, double *y64, const struct lsb_mrhs_state *st,
+                                    void *stream);
+LSB_INTERNAL void lsb_k_amg32_dense_m(unsigned kp, unsigned nc, unsigned lanes, int ends64, const float *cinv,
+                                      const void *b, void *out, const struct lsb_mrhs_state *st, void *stream);
 /* hip_gmres_drv.c */
 LSB_INTERNAL solve_dev_fn gmres_solve_dev;
 /* hip_bicgstab_drv.c */
@@ -629,6 +658,26 @@ LSB_INTERNAL void lsb_k_rich_restart(unsigned n, const double *b, const double *
                                      unsigned *npartials, void *stream);
 LSB_INTERNAL void lsb_k_rich_restart_state(struct lsb_pcg_state *st, const double *parts, unsigned nparts, int more,
                                            void *stream);
+/* hip_rich_m_drv.c: the iteration on blocks of right-hand sides, and the launchers of hip_rich_m.hip (kp: 2, 4 or 8;
+ * interleaved blocks; records: kp doubles per workgroup of a sweep, *nrecords of them; per column the bits of the
+ * launchers above on that column alone) */
+LSB_INTERNAL void richm_free(lsb_hip_solver *sv); /* the work areas of every width */
+LSB_INTERNAL void lsb_k_richm_init(unsigned kp, unsigned n, const double *b, double *x, double *r, double *records,
+                                   unsigned *nrecords, void *stream);
+LSB_INTERNAL void lsb_k_richm_init_state(unsigned kp, struct lsb_mrhs_state *st, const double *records,
+                                         unsigned nrecords, double tol, int maxit, void *stream);
+LSB_INTERNAL void lsb_k_richm_update(unsigned kp, unsigned n, const double *z, const double *q, double *x, double *r,
+                                     const struct lsb_mrhs_state *st, double *records, unsigned *nrecords,
+                                     void *stream);
+LSB_INTERNAL void lsb_k_richm_step(unsigned kp, struct lsb_mrhs_state *st, const double *records, unsigned nrecords,
+                                   void *stream);
+/* the verify round: r = b - ax for the columns called converged; then their recomputed norms decide, a column with
+ * fewer than max_restarts restarts behind it may cycle on */
+LSB_INTERNAL void lsb_k_richm_restart(unsigned kp, unsigned n, const double *b, const double *ax, double *r,
+                                      const struct lsb_mrhs_state *st, double *records, unsigned *nrecords,
+                                      void *stream);
+LSB_INTERNAL void lsb_k_richm_restart_state(unsigned kp, struct lsb_mrhs_state *st, const double *records,
+                                            unsigned nrecords, int max_restarts, void *stream);
 /* hip_direct_drv.c, and the launchers of hip_direct.hip */
 LSB_INTERNAL solve_dev_fn direct_solve_dev;
 /* what --krylov direct cannot run with, refused at creation (shards, persistent); what it does not consult is set
