@@ -810,6 +810,43 @@ int lsb_hip_solver_solve_x0_dev(lsb_hip_solver *s, const double *d_b, double *d_
  * a batch forms it with the compensated SpMM of its verify rounds, good to about 1e-15 of itself.  struct
  * lsb_hip_result keeps its layout: this is where the starting residual is read.  2 if the last solve was a cold one, if nrhs does not match, or on null arguments. */
 int lsb_hip_solver_start_relres(const lsb_hip_solver *s, unsigned nrhs, double *out);
+/* Successive right-hand sides (time stepping, a Newton loop): the solver keeps an S-orthonormal basis X~ of up to
+ * `depth` earlier solutions on the device -- pairs (x~_k, S x~_k) of n_local doubles, X~^T S X~ = I -- and starts each
+ * solve of the sequence from x0 = X~ (X~^T b), the S-norm best approximation of the solution in their span (Fischer,
+ * CMAME 163, 1998).  Opt-in: nothing else reads or disturbs the basis, a solver that never asks for one allocates
+ * nothing.
+ *   seq_begin: depth = 1 .. LSB_SEQ_MAX_DEPTH allocates the pairs and empties the basis; again: empties it, and
+ *   re-allocates if depth changed; depth = 0 frees everything.  2, and nothing allocated, for depth > LSB_SEQ_MAX_DEPTH
+ *   and on a solver this does not serve: more than one shard (virtual shards included), ranks, and the unsymmetric
+ *   drivers GMRES and BiCGSTAB -- the projection needs a symmetric positive definite operator.  Every other solver that
+ *   solve_x0 serves on one shard is served.
+ *   solve_seq[_dev]: b and x in the caller's numbering as in solve[_dev]; x need not be initialised.  With an empty
+ *   basis it IS solve[_dev], bit for bit.  Otherwise x0 = X~ (X~^T b) and solve_x0's rules from there: the stop rule
+ *   relative to ||b||, ||b - S x0|| <= tol ||b|| returns x0 with 0 iterations, b = 0 gives x = 0, res->iters counts
+ *   from x0 and lsb_hip_solver_start_relres(s, 1, .) reports ||b - S x0|| / ||b||.  2 before seq_begin and on null
+ *   arguments; 2 leaves x untouched.
+ *   Behind a solve that ended CONVERGED after at least one iteration (opts.tol > 0) the basis takes the correction
+ *   d = x - x0 (the first solve: d = x): w = S d by the fp64 product of a recomputed residual, two Gram-Schmidt passes
+ *   against the held pairs (d -= sum beta_k x~_k, w -= sum beta_k S x~_k with beta_k = x~_k . w), nu = d . w, and
+ *   (d, w) / sqrt(nu) becomes the next pair -- unless nu is not finite or not > 0, then the basis stays as it was.  A
+ *   full basis restarts first: it is emptied and d = x, the whole current solution (restarts counts these).  Under
+ *   opts.verify or mixed precision, where correction runs moved x on, x0 is formed again and d = x - x0.
+ *   One host read of three doubles ends the update; it is the only one the feature adds to a solve.
+ *   seq_info: depth (0: none), pairs held, restarts since seq_begin, device bytes the feature holds; any may be NULL.
+ *   seq_basis_dev: pair k < held in the caller's numbering into d_xk, d_sxk (n_local doubles each, either may be
+ *   NULL); 2 for k >= held.  For tests. */
+#define LSB_SEQ_MAX_DEPTH 16
+int lsb_hip_solver_seq_begin(lsb_hip_solver *s, unsigned depth);
+int lsb_hip_solver_solve_seq_dev(lsb_hip_solver *s, const double *d_b, double *d_x, struct lsb_hip_result *res);
+int lsb_hip_solver_solve_seq(lsb_hip_solver *s, const double *b, double *x, struct lsb_hip_result *res);
+int lsb_hip_solver_seq_info(const lsb_hip_solver *s, unsigned *depth, unsigned *held, unsigned *restarts,
+                            unsigned long long *bytes);
+int lsb_hip_solver_seq_basis_dev(lsb_hip_solver *s, unsigned k, double *d_xk, double *d_sxk);
+/* Device time of the last solve_seq[_dev]'s projection (0: the basis was empty) and update (0: there was none), in
+ * microseconds between events on the solver's stream; 2 before seq_begin.  For tools/bench_seq.py.  The events are
+ * recorded on request only: the first call behind a seq_begin that (re-)allocated the basis answers 0, 0 and turns the
+ * recording on -- four event records per solve from then on; a sequence that never asks records none. */
+int lsb_hip_solver_seq_last_us(lsb_hip_solver *s, double *project_us, double *update_us);
 /* y_local = Op * x: d_x holds this rank's rows (length n_local); remote
  * entries are exchanged first when the solver is distributed. */
 int lsb_hip_solver_spmv_dev(lsb_hip_solver *s, const double *d_x, double *d_y);

@@ -27,6 +27,7 @@ AMG_PREC_FP64, AMG_PREC_FP32 = 0, 1
 KRYLOV_PCG, KRYLOV_GMRES, KRYLOV_PCG1, KRYLOV_AUTO, KRYLOV_BICGSTAB, KRYLOV_RICHARDSON = 0, 1, 2, 3, 4, 5
 KRYLOV_DIRECT = 6
 DIRECT_MAX_ENTRIES = 1 << 28
+SEQ_MAX_DEPTH = 16  # LSB_SEQ_MAX_DEPTH
 SPMV_AUTO, SPMV_ADAPTIVE, SPMV_SUBWAVE, SPMV_SCALAR, SPMV_PANEL, SPMV_SELL, SPMV_BINNED, SPMV_TWOPHASE = 0, 1, 2, 3, 4, 5, 6, 7
 SELL_ROWS = 128
 BIN_CHUNK = 2048
@@ -286,6 +287,12 @@ SIGNATURES = {
     "lsb_hip_solver_solve_x0": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
     "lsb_hip_solver_solve_x0_dev": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
     "lsb_hip_solver_start_relres": (_i, [_vp, _u, C.POINTER(C.c_double)]),
+    "lsb_hip_solver_seq_begin": (_i, [_vp, _u]),
+    "lsb_hip_solver_solve_seq_dev": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
+    "lsb_hip_solver_solve_seq": (_i, [_vp, _vp, _vp, C.POINTER(Result)]),
+    "lsb_hip_solver_seq_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u), C.POINTER(_u), C.POINTER(C.c_ulonglong)]),
+    "lsb_hip_solver_seq_basis_dev": (_i, [_vp, _u, _vp, _vp]),
+    "lsb_hip_solver_seq_last_us": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
     "lsb_hip_solver_spmv_dev": (_i, [_vp, _vp, _vp]),
     "lsb_hip_solver_spmv_inner_dev": (_i, [_vp, _vp, _vp, _vp]),
     "lsb_hip_solver_spmm_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),

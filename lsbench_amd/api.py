@@ -379,6 +379,48 @@ class Solver:
         L.check(L.load().lsb_hip_solver_start_relres(self._h, nrhs, out), "start_relres")
         return np.array(out[:nrhs])
 
+    def seq_begin(self, depth):
+        """Successive right-hand sides: keep a basis of up to `depth` (1 .. SEQ_MAX_DEPTH) earlier solutions on the
+        device and empty it; 0 frees it.  Raises on a solver the projection does not serve (shards, GMRES,
+        BiCGSTAB)."""
+        L.check(L.load().lsb_hip_solver_seq_begin(self._h, depth), "seq_begin")
+
+    def solve_seq(self, b):
+        """One solve of a sequence, from the projection of b on the basis (an empty basis: solve(b)).  Returns
+        (x, result); the basis takes what was solved for."""
+        b = np.ascontiguousarray(b, np.float64)
+        if b.shape != (self.n_local,):
+            raise ValueError("solve_seq: b must hold n_local values")
+        x = np.empty(self.n_local, np.float64)
+        res = L.Result()
+        L.check(L.load().lsb_hip_solver_solve_seq(self._h, b.ctypes.data, x.ctypes.data, C.byref(res)), "solve_seq")
+        return x, res
+
+    def solve_seq_dev(self, d_b, d_x):
+        res = L.Result()
+        L.check(L.load().lsb_hip_solver_solve_seq_dev(self._h, _ptr(d_b), _ptr(d_x), C.byref(res)), "solve_seq_dev")
+        return res
+
+    @property
+    def seq_info(self):
+        """(depth, pairs held, restarts since seq_begin, device bytes held); all 0 without a basis."""
+        d, h, r, by = C.c_uint(), C.c_uint(), C.c_uint(), C.c_ulonglong()
+        L.check(L.load().lsb_hip_solver_seq_info(self._h, C.byref(d), C.byref(h), C.byref(r), C.byref(by)),
+                "seq_info")
+        return d.value, h.value, r.value, int(by.value)
+
+    def seq_basis_dev(self, k, d_xk, d_sxk):
+        """Pair k < held, (x~_k, S x~_k), into two device vectors of n_local doubles in the caller's numbering."""
+        L.check(L.load().lsb_hip_solver_seq_basis_dev(self._h, k, _ptr(d_xk), _ptr(d_sxk)), "seq_basis_dev")
+
+    @property
+    def seq_last_us(self):
+        """(projection, update): device microseconds of the last solve_seq's two parts, 0 where it had none.  The
+        events are recorded only once this was asked: the first look behind a seq_begin turns them on, answers 0, 0."""
+        p, u = C.c_double(), C.c_double()
+        L.check(L.load().lsb_hip_solver_seq_last_us(self._h, C.byref(p), C.byref(u)), "seq_last_us")
+        return p.value, u.value
+
     def spmv_dev(self, d_x, d_y):
         L.check(L.load().lsb_hip_solver_spmv_dev(self._h, _ptr(d_x), _ptr(d_y)), "spmv_dev")
 

@@ -31,7 +31,7 @@ void gather_x(lsb_hip_solver *sv, const double *d_x) {
 }
 
 /* q = S x in every shard, with the fp64 values whatever opts.precision says */
-static void op_exact(lsb_hip_solver *sv, const double *d_x) {
+void op_exact(lsb_hip_solver *sv, const double *d_x) {
   gather_x(sv, d_x);
   for (int i = 0; i < sv->nshard; i++) {
     struct shard *s = &sv->sh[i];
@@ -197,6 +197,13 @@ int solve_core(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb_hi
   return sv->driver->solve(sv, d_b, d_x, res);
 }
 
+void x0_vecs(lsb_hip_solver *sv) {
+  if (!sv->d_x0r) {
+    sv->d_x0r = (double *)lsb_hip_malloc((size_t)sv->n_here * sizeof(double));
+    sv->d_x0e = (double *)lsb_hip_malloc((size_t)sv->n_here * sizeof(double));
+  }
+}
+
 /*
  * One solve from the x0 that d_x holds (lsb_hip_solver_solve_x0[_dev]), for every driver and every PCG form from
  * this one place: q = S x0 the way a recomputed residual forms it, k_x0_start leaves r0 = b - q and the sums
@@ -210,10 +217,7 @@ int solve_x0_core(lsb_hip_solver *sv, const double *d_b, double *d_x, struct lsb
   const double t0 = wall_seconds(), tol = sv->o.tol;
   const int on = sv->p2p_on, halo = sv->p2p_halo;
   double sums[2] = {0.0, 0.0};
-  if (!sv->d_x0r) {
-    sv->d_x0r = (double *)lsb_hip_malloc((size_t)sv->n_here * sizeof(double));
-    sv->d_x0e = (double *)lsb_hip_malloc((size_t)sv->n_here * sizeof(double));
-  }
+  x0_vecs(sv);
   sv->p2p_on = sv->p2p_halo = 0;
   op_exact(sv, d_x);
   for (int i = 0; i < sv->nshard; i++) {

@@ -888,6 +888,7 @@ void lsb_hip_solver_destroy(lsb_hip_solver *sv) {
   richm_free(sv);
   mrhs_free(sv);
   blockcg_free(sv);
+  seq_free(sv);
   shard_vec_free(&sv->sh[0], sv->d_bp), shard_vec_free(&sv->sh[0], sv->d_xp); /* shard 0's slab may hold them */
   for (int i = 0; i < sv->nshard; i++)
     shard_free(&sv->sh[i]);

@@ -11,6 +11,8 @@
  *   hip_pcg.c        the PCG driver: its iteration forms (one chosen per solver), one run, the persistent launch
  *   hip_solve.c      what a caller's solve is, whichever driver runs it (one chosen per solver): cold and from an
  *                    initial guess, recomputed residuals and what follows from them, the single-column entry points
+ *   hip_seq_drv.c    successive right-hand sides: the basis of earlier solutions a solver keeps when asked, the
+ *                    projection in front of a solve and the update behind it
  *   hip_precond.c    FSAI, block-Jacobi and the Chebyshev preconditioner: set-up and z = M^-1 r
  *   hip_amg_drv.c    AMG: upload of the hierarchy, the V-cycle's one schedule (amg_cycle), its accessors
  *   hip_gmres_drv.c  GMRES(m) driver
@@ -323,6 +325,19 @@ struct lsb_hip_solver {
   double *d_x0r, *d_x0e;
   double *start_rr;
   unsigned start_n, start_cap;
+  /* Successive right-hand sides (hip_seq_drv.c), NULL until lsb_hip_solver_seq_begin: ONE allocation of `bytes` -- the
+   * pairs x~_k (X) and S x~_k (SX), depth columns of ld doubles each (ld even, the rows behind n_here zero), the
+   * records of the sweeps (parts) and the scalars (scal: the coefficients of the projection and of the two
+   * Gram-Schmidt passes, the record of the store) -- in the solver's internal numbering; events around the last
+   * projection and the last update, made and recorded only once asked for */
+  struct seq_basis {
+    unsigned depth, held, restarts;
+    size_t ld;
+    double *X, *SX, *parts, *scal;
+    unsigned long long bytes;
+    hipEvent_t ev[4];
+    int timing, timed_project, timed_update; /* timing: lsb_hip_solver_seq_last_us was called, the events exist */
+  } *seq;
   unsigned agree_nnz, agree_n; /* distributed: largest shard, identical on all ranks */
   unsigned agree_halo;         /* largest halo (doubles) any shard receives from one peer */
   /* opts.overlap = -1: the split SpMV (interior rows while the halo travels) against the plain one,
@@ -570,6 +585,8 @@ LSB_INTERNAL const struct solve_driver *solve_driver_for(int krylov);
 LSB_INTERNAL solve_dev_fn solve_core;
 LSB_INTERNAL solve_dev_fn solve_x0_core; /* the same from the x0 that d_x holds */
 LSB_INTERNAL void gather_x(lsb_hip_solver *sv, const double *d_x);
+LSB_INTERNAL void op_exact(lsb_hip_solver *sv, const double *d_x); /* q = S x in every shard, with the fp64 values */
+LSB_INTERNAL void x0_vecs(lsb_hip_solver *sv); /* d_x0r and d_x0e, taken on first use */
 LSB_INTERNAL double true_resid2(lsb_hip_solver *sv, const double *d_b, const double *d_x);
 LSB_INTERNAL int direct_path_agrees(lsb_hip_solver *sv, const double *d_b, const double *d_x, double bb,
                                     struct lsb_hip_result *r, const char *then);
@@ -592,6 +609,8 @@ struct restart_run {
 LSB_INTERNAL unsigned run_restarting(lsb_hip_solver *sv, const struct restart_run *v, struct lsb_hip_result *r);
 /* where a warm-started call of nrhs columns records its starting residuals (sets start_n) */
 LSB_INTERNAL double *start_relres_slots(lsb_hip_solver *sv, unsigned nrhs);
+/* hip_seq_drv.c */
+LSB_INTERNAL void seq_free(lsb_hip_solver *sv);
 /* hip_precond.c */
 LSB_INTERNAL int generic_precond(const lsb_hip_solver *sv);
 LSB_INTERNAL void precond_shard_blocks(struct shard *s, const int *offs, const int *cols,

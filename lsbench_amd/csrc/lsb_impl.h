@@ -289,6 +289,26 @@ void lsb_k_gm_hess(struct lsb_gmres_state *st, int j, const double *h, const dou
 void lsb_k_gm_finish_cycle(unsigned n, const double *V, size_t ld, const double *dinv, double *x,
                            struct lsb_gmres_state *st, void *stream);
 
+/* Successive right-hand sides (hip_seq.hip): the projection onto m = 1 .. LSB_SEQ_MAX_DEPTH earlier solutions.  X, SX:
+ * the pairs (x~_k, S x~_k), vector-major, column k at k ld with ld even.  partials: room for lsb_k_seq_grid(n) records
+ * of m + 2 doubles.  A lane takes two neighbouring rows per turn and all of a turn's loads are issued before the first
+ * is waited for; the operands need 8-byte alignment only, and the bits do not depend on it; the scalars are read from
+ * device memory.
+ * dots: alpha_k = sum_i X[k][i] v[i], reduced on the device.  combine: x0_i = sum_k alpha_k X[k][i], an fma chain in
+ * ascending k from 0.0.  orth: d -= sum_k beta_k X[k], w -= sum_k beta_k SX[k] in place; out[0 .. m) = X[k] . w',
+ * out[m] = d' . w', out[m + 1] = d . w from before the update -- dots' sums on the vectors just written, bit for bit.
+ * store: xs = d / sqrt(*nu), sxs = w / sqrt(*nu) and rec = (*nu0, *nu, 1); *nu not finite or not > 0: rec = (*nu0, *nu,
+ * 0) and nothing else. */
+unsigned lsb_k_seq_grid(unsigned n);
+void lsb_k_seq_dots(unsigned n, unsigned m, const double *X, size_t ld, const double *v, double *partials,
+                    double *alpha, void *stream);
+void lsb_k_seq_combine(unsigned n, unsigned m, const double *X, size_t ld, const double *alpha, double *x0,
+                       void *stream);
+void lsb_k_seq_orth(unsigned n, unsigned m, const double *X, const double *SX, size_t ld, const double *beta,
+                    double *d, double *w, double *partials, double *out, void *stream);
+void lsb_k_seq_store(unsigned n, const double *d, const double *w, double *xs, double *sxs, const double *nu,
+                     const double *nu0, double *rec, void *stream);
+
 /* BiCGSTAB launchers (hip_bicgstab.hip); dinv == NULL: the constant dc */
 void lsb_k_bcg_init(unsigned n, const double *b, const double *dinv, double dc, double *x, double *r,
                     double *rhat, double *p, double *phat, double *partials, unsigned *npartials,
