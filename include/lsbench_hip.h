@@ -404,6 +404,41 @@ struct lsb_skyinv {
 };
 struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *perm_in, int *why);
 void lsb_skyinv_free(struct lsb_skyinv *W);
+/* The inverse factor in tiers, for operators whose single skyline is over the budget (lsb_direct.c).  With the
+ * thresholds T_1 < ... < T_(m-1), T_i the smallest integer with T_i^m >= n^i, tier(k) is the number of thresholds the
+ * subtree of k is larger than; tiers never decrease towards the root, tiers nobody is in are dropped (ntier <= m), and
+ * the rows are numbered tier by tier, in postorder inside a tier: tier t is lo[t] .. lo[t + 1] - 1, lo[ntier] = n.  L
+ * is then block lower triangular.  W_tt = (L_tt)^-1 are skylines as in struct lsb_skyinv, one after another in the
+ * same arrays: row k is the run of columns first[k] .. k >= lo[tier(k)], parent[k] = n on the root of a tier's tree,
+ * run_end[k] stays inside k's tier.  The blocks below the diagonal are the rows of L themselves, twice: C by rows --
+ * row i >= lo[1] at coffs[i - lo[1]] .. coffs[i - lo[1] + 1], columns < lo[tier(i)] ascending -- and C^T by tier and
+ * column -- for t = 1 .. ntier - 1 the columns j < lo[t], lo[t] + 1 offsets each, tier t's at toffs[sum over
+ * 1 <= s < t of (lo[s] + 1)], the rows of tier t ascending.  Both hold the same values bit for bit.  A solve is
+ *   forward   y_t = W_tt ((P b)_t - C_t y_<t)                 t = 0 .. ntier - 1
+ *   backward  x_t = W_tt^T (y_t - sum over s > t of (C_s^T x_s)_t)   t = ntier - 1 .. 0, then x = P^T x.
+ * The budget: w_entries + 3 coupling_entries <= LSB_DIRECT_MAX_ENTRIES (a coupling entry is kept twice at 12 B).
+ * lsb_csr_tiered_count: symbolic, O(nnz(L)): the entries of the W_tt, of C, and the height of the whole tree, for
+ * tiers = 1 .. LSB_DIRECT_MAX_TIERS; returns 0, 2 for tiers out of range or a perm that is none, 3 out of memory.
+ * lsb_csr_tiered_inverse: tiers = 1 is lsb_csr_skyline_inverse's factor byte for byte with nothing coupled; tiers = 0
+ * takes the fewest tiers that fit the budget by the symbolic count (LSB_DIRECT_MAX_TIERS if none does, which is then
+ * refused with 2); *why as for lsb_csr_skyline_inverse, 3 also for tiers > LSB_DIRECT_MAX_TIERS. */
+#define LSB_DIRECT_MAX_TIERS 6
+struct lsb_tierinv {
+  unsigned n, ntier;
+  unsigned lo[LSB_DIRECT_MAX_TIERS + 1];
+  unsigned *perm, *first;
+  unsigned long long *woff; /* n + 1 */
+  double *vals;
+  unsigned *parent, *run_end;
+  unsigned *coffs, *ccols; /* C: n - lo[1] + 1 offsets (1 when ntier = 1) */
+  double *cvals;
+  unsigned *toffs, *tcols; /* C^T, tier by tier */
+  double *tvals;
+};
+struct lsb_tierinv *lsb_csr_tiered_inverse(const struct csr *S, const unsigned *perm_in, unsigned tiers, int *why);
+void lsb_tierinv_free(struct lsb_tierinv *W);
+int lsb_csr_tiered_count(const struct csr *S, const unsigned *perm, unsigned tiers, unsigned long long *w_entries,
+                         unsigned long long *coupling_entries, unsigned *height);
 /* P S P^T for perm[new] = old, as a new 0-based CSR (src/cusparse.c:87-97). */
 struct csr *lsb_csr_permute_sym(const struct csr *S, const unsigned *perm);
 /* max |row - col| over the stored entries */
@@ -891,6 +926,25 @@ unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *s);
  * 2 for any other solver. */
 int lsb_hip_solver_direct_info(const lsb_hip_solver *s, unsigned long long *entries, unsigned *height,
                                unsigned long long *bytes_per_round);
+/* A direct solver (o->krylov must be LSB_KRYLOV_DIRECT; o = NULL: the backend's current options) whose inverse factor
+ * is kept in tiers (struct lsb_tierinv; hip_direct_t.hip, hip_direct_t_drv.c): for operators whose single skyline is
+ * over LSB_DIRECT_MAX_ENTRIES.  tiers = 1 is lsb_hip_solver_create itself; 2 .. LSB_DIRECT_MAX_TIERS asks for that
+ * many (the factor may have fewer: tiers nobody is in are dropped); 0 takes the fewest that fit the budget
+ * w_entries + 3 coupling_entries <= LSB_DIRECT_MAX_ENTRIES by the symbolic count.  NULL for another krylov or tiers
+ * out of range; what lsb_hip_solver_create refuses for a direct solver is refused in the same way, and so is a factor
+ * over the budget in the tiers asked for.  A round is 4 m - 2 launches for m tiers instead of 2, then the residual
+ * and the stop test as before.  Every solve entry point of a direct solver works on it (solve[_dev], solve_x0[_dev],
+ * solve_seq[_dev], precond_dev, opts.verify) but the blocks of right-hand sides, which answer 2.
+ * On such a solver lsb_hip_solver_direct_info reports the entries of the W_tt, the height of the whole tree, and as
+ * bytes per round 16 per entry of the W_tt, 24 per coupling entry (C and C^T once each: a value and a 32-bit column),
+ * and 104 per row (first / woff twice, the offsets of C and C^T, P r, y, z and x). */
+lsb_hip_solver *lsb_hip_solver_create_direct(const struct csr *A, const struct lsb_hip_opts *o, int tiers);
+/* Tiers of a direct solver's factor: how many, the entries of the W_tt and of the coupling C, the rows of each tier
+ * (LSB_DIRECT_MAX_TIERS slots, 0 behind the last tier) and the launches of one application (4 m - 2); each may be
+ * NULL.  A solver of lsb_hip_solver_create reports one tier and no coupling.  2 for a solver that is not direct. */
+int lsb_hip_solver_direct_tier_info(const lsb_hip_solver *s, unsigned *ntiers, unsigned long long *w_entries,
+                                    unsigned long long *coupling_entries, unsigned *tier_rows,
+                                    unsigned *launches_per_round);
 /* LSB_PRECOND_CHEBYSHEV: the interval [lmin, lmax] of D^-1 S the polynomial was built on at creation
  * (lmax = 1.1 x the power iteration's estimate, lmin = lmax / max(30, 16 degree^2), the degree
  * clamped to 1 .. 32); 2 for another preconditioner. */

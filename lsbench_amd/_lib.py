@@ -27,6 +27,7 @@ AMG_PREC_FP64, AMG_PREC_FP32 = 0, 1
 KRYLOV_PCG, KRYLOV_GMRES, KRYLOV_PCG1, KRYLOV_AUTO, KRYLOV_BICGSTAB, KRYLOV_RICHARDSON = 0, 1, 2, 3, 4, 5
 KRYLOV_DIRECT = 6
 DIRECT_MAX_ENTRIES = 1 << 28
+DIRECT_MAX_TIERS = 6
 SEQ_MAX_DEPTH = 16  # LSB_SEQ_MAX_DEPTH
 SPMV_AUTO, SPMV_ADAPTIVE, SPMV_SUBWAVE, SPMV_SCALAR, SPMV_PANEL, SPMV_SELL, SPMV_BINNED, SPMV_TWOPHASE = 0, 1, 2, 3, 4, 5, 6, 7
 SELL_ROWS = 128
@@ -153,6 +154,16 @@ class Skyinv(C.Structure):
                 ("parent", C.POINTER(C.c_uint)), ("run_end", C.POINTER(C.c_uint))]
 
 
+class Tierinv(C.Structure):
+    """struct lsb_tierinv."""
+    _fields_ = [("n", C.c_uint), ("ntier", C.c_uint), ("lo", C.c_uint * (DIRECT_MAX_TIERS + 1)),
+                ("perm", C.POINTER(C.c_uint)), ("first", C.POINTER(C.c_uint)),
+                ("woff", C.POINTER(C.c_ulonglong)), ("vals", C.POINTER(C.c_double)),
+                ("parent", C.POINTER(C.c_uint)), ("run_end", C.POINTER(C.c_uint)),
+                ("coffs", C.POINTER(C.c_uint)), ("ccols", C.POINTER(C.c_uint)), ("cvals", C.POINTER(C.c_double)),
+                ("toffs", C.POINTER(C.c_uint)), ("tcols", C.POINTER(C.c_uint)), ("tvals", C.POINTER(C.c_double))]
+
+
 class SellTmpl(C.Structure):
     """struct lsb_sell_tmpl (176 bytes)."""
     _fields_ = [("nslots", C.c_int), ("shaped", C.c_int), ("base", C.c_int * 8), ("kidx", C.c_int * 8),
@@ -237,6 +248,10 @@ SIGNATURES = {
     "lsb_csr_skyline_count": (C.c_ulonglong, [_csrp, C.POINTER(_u), C.POINTER(_u)]),
     "lsb_csr_skyline_inverse": (C.POINTER(Skyinv), [_csrp, C.POINTER(_u), C.POINTER(_i)]),
     "lsb_skyinv_free": (None, [C.POINTER(Skyinv)]),
+    "lsb_csr_tiered_inverse": (C.POINTER(Tierinv), [_csrp, C.POINTER(_u), _u, C.POINTER(_i)]),
+    "lsb_tierinv_free": (None, [C.POINTER(Tierinv)]),
+    "lsb_csr_tiered_count": (_i, [_csrp, C.POINTER(_u), _u, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                  C.POINTER(_u)]),
     "lsb_csr_permute_sym": (_csrp, [_csrp, C.POINTER(_u)]),
     "lsb_csr_bandwidth": (_u, [_csrp]),
     "lsb_csr_panelize": (C.POINTER(PanelCsr), [_csrp, _u]),
@@ -314,6 +329,9 @@ SIGNATURES = {
     "lsb_hip_solver_amg_precision": (_i, [_vp]),
     "lsb_hip_solver_amg_cycle_bytes": (C.c_ulonglong, [_vp]),
     "lsb_hip_solver_direct_info": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(_u), C.POINTER(C.c_ulonglong)]),
+    "lsb_hip_solver_create_direct": (_vp, [_csrp, C.POINTER(Opts), _i]),
+    "lsb_hip_solver_direct_tier_info": (_i, [_vp, C.POINTER(_u), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                             C.POINTER(_u), C.POINTER(_u)]),
     "lsb_hip_solver_solve_direct_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_solve_direct_multi": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_direct_apply_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),

@@ -259,6 +259,45 @@ def lsb_csr_skyline_inverse(A, perm):
     return out
 
 
+def lsb_csr_tiered_count(A, perm, tiers):
+    """(entries of the W_tt, entries of the coupling C, height of the whole tree) under perm in `tiers` tiers
+    (1 .. DIRECT_MAX_TIERS), symbolic; None where the library refuses the arguments."""
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    w, c, h = C.c_ulonglong(), C.c_ulonglong(), C.c_uint()
+    rc = L.load().lsb_csr_tiered_count(A.ptr, perm.ctypes.data_as(C.POINTER(C.c_uint)), tiers, C.byref(w), C.byref(c),
+                                       C.byref(h))
+    return (int(w.value), int(c.value), int(h.value)) if rc == 0 else None
+
+
+def lsb_csr_tiered_inverse(A, perm, tiers):
+    """The tiered inverse factor (struct lsb_tierinv) as a dict of numpy arrays -- n, ntier, lo (ntier + 1), the
+    skyline arrays of lsb_csr_skyline_inverse, C as coffs / ccols / cvals (row i of the new numbering at
+    coffs[i - lo[1]]) and C^T as toffs / tcols / tvals (tier t's lo[t] + 1 offsets one after another) -- or the reason
+    it was refused as an int.  tiers = 0: the fewest that fit the budget."""
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    why = C.c_int()
+    p = L.load().lsb_csr_tiered_inverse(A.ptr, perm.ctypes.data_as(C.POINTER(C.c_uint)), tiers, C.byref(why))
+    if not p:
+        return int(why.value)
+    w = p.contents
+    n, ntier = int(w.n), int(w.ntier)
+
+    def arr(q, cnt, dt):
+        return np.ctypeslib.as_array(q, shape=(max(cnt, 1),))[:cnt].astype(dt, copy=True)
+    lo = np.array(list(w.lo)[:ntier + 1], np.int64)
+    woff = arr(w.woff, n + 1, np.uint64)
+    coffs = arr(w.coffs, n - int(lo[min(1, ntier)]) + 1, np.uint32)
+    toffs = arr(w.toffs, int((lo[1:ntier] + 1).sum()), np.uint32)
+    nc = int(coffs[-1])
+    out = {"n": n, "ntier": ntier, "lo": lo, "perm": arr(w.perm, n, np.uint32), "first": arr(w.first, n, np.uint32),
+           "woff": woff, "vals": arr(w.vals, int(woff[-1]), np.float64), "parent": arr(w.parent, n, np.uint32),
+           "run_end": arr(w.run_end, n, np.uint32), "coffs": coffs, "ccols": arr(w.ccols, nc, np.uint32),
+           "cvals": arr(w.cvals, nc, np.float64), "toffs": toffs, "tcols": arr(w.tcols, nc, np.uint32),
+           "tvals": arr(w.tvals, nc, np.float64)}
+    L.load().lsb_tierinv_free(p)
+    return out
+
+
 def lsb_csr_permute_sym(A, perm):
     perm = np.ascontiguousarray(perm, dtype=np.uint32)
     return Matrix(L.load().lsb_csr_permute_sym(A.ptr, perm.ctypes.data_as(C.POINTER(C.c_uint))))
@@ -341,10 +380,36 @@ class Solver:
         if not h:
             raise L.LsbenchHipError("lsb_hip_solver_create failed: backend not "
                                     "initialised (no GPU?) -- there is no CPU path")
+        self._adopt(h)
+
+    def _adopt(self, h):
+        lib = L.load()
         self._h = h
         self.n_local = lib.lsb_hip_solver_nrows_local(h)
         self.n_global = lib.lsb_hip_solver_nrows_global(h)
         self.nnz_local = lib.lsb_hip_solver_nnz_local(h)
+
+    @classmethod
+    def create_direct(cls, A, opts, tiers=0):
+        """A direct solver (opts.krylov = KRYLOV_DIRECT) whose inverse factor is kept in `tiers` tiers: 1 is
+        Solver(A, opts), 0 takes the fewest tiers that fit the entry budget.  See lsb_hip_solver_create_direct."""
+        self = cls.__new__(cls)
+        self.opts = opts
+        h = L.load().lsb_hip_solver_create_direct(A.ptr, C.byref(opts), tiers)
+        if not h:
+            raise L.LsbenchHipError("lsb_hip_solver_create_direct failed: backend not initialised (no GPU?), "
+                                    "opts.krylov is not KRYLOV_DIRECT, or tiers is out of 0 .. %d"
+                                    % L.DIRECT_MAX_TIERS)
+        self._adopt(h)
+        return self
+
+    def direct_tier_info(self):
+        """(tiers, entries of the W_tt, entries of the coupling, rows per tier, launches per round) of a direct solver;
+        None for any other."""
+        nt, w, c, lp = C.c_uint(), C.c_ulonglong(), C.c_ulonglong(), C.c_uint()
+        rows = (C.c_uint * L.DIRECT_MAX_TIERS)()
+        rc = L.load().lsb_hip_solver_direct_tier_info(self._h, C.byref(nt), C.byref(w), C.byref(c), rows, C.byref(lp))
+        return (int(nt.value), int(w.value), int(c.value), list(rows)[:nt.value], int(lp.value)) if rc == 0 else None
 
     def solve(self, b, x0=None):
         """x0: an initial guess (n_local); None solves from zero."""

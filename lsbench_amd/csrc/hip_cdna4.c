@@ -172,6 +172,30 @@ static const struct optdef {
 };
 #undef OPT
 #define NOPTS (sizeof OPTS / sizeof OPTS[0])
+/* --direct-tiers K (LSBENCH_HIP_DIRECT_TIERS): not a member of struct lsb_hip_opts, whose layout stays; the tiers of
+ * the direct solver's inverse factor that hip_cdna4_bench asks lsb_hip_solver_create_direct for under --krylov direct:
+ * 1 (the default) = the single skyline of lsb_hip_solver_create, 0 = the fewest that fit the entry budget */
+static int g_direct_tiers = 1, g_direct_tiers_set;
+
+static int direct_tiers_assign(const char *value) {
+  char *end = NULL;
+  const long v = value && *value ? strtol(value, &end, 10) : -1;
+  if (!end || *end || v < 0 || v > LSB_DIRECT_MAX_TIERS)
+    return 1;
+  g_direct_tiers = (int)v, g_direct_tiers_set = 1;
+  return 0;
+}
+
+static int direct_tiers(void) {
+  const char *e;
+  if (!g_direct_tiers_set) {
+    g_direct_tiers_set = 1;
+    if ((e = getenv("LSBENCH_HIP_DIRECT_TIERS")) && direct_tiers_assign(e))
+      warnx("hip_cdna4: LSBENCH_HIP_DIRECT_TIERS=%s is not a value of option `direct-tiers' (0 .. %d); ignored", e,
+            LSB_DIRECT_MAX_TIERS);
+  }
+  return g_direct_tiers;
+}
 
 static int opt_name_eq(const char *a, const char *b) { /* case-blind, '-' == '_' */
   for (; *a && *b; a++, b++) {
@@ -241,6 +265,14 @@ int hip_cdna4_set_option(const char *name, const char *value) {
   if (!name)
     return 1;
   lsb_hip_get_opts(&o);
+  if (opt_name_eq(name, "direct-tiers")) {
+    if (direct_tiers_assign(value)) {
+      warnx("hip_cdna4: `%s' is not a value of option `direct-tiers' (0 .. %d)", value ? value : "(null)",
+            LSB_DIRECT_MAX_TIERS);
+      return 1;
+    }
+    return 0;
+  }
   for (size_t k = 0; k < NOPTS; k++)
     if (opt_name_eq(name, OPTS[k].name)) {
       if (opt_assign(&o, &OPTS[k], value)) {
@@ -481,7 +513,9 @@ int hip_cdna4_bench(double *x, struct csr *A, const double *r,
 
   /* untimed setup: operator build, upload, Jacobi, row blocks
    * (counterpart of csr_init, src/cusparse.c:47-125) */
-  lsb_hip_solver *sv = lsb_hip_solver_create(A, &o);
+  lsb_hip_solver *sv = o.krylov == LSB_KRYLOV_DIRECT && direct_tiers() != 1
+                           ? lsb_hip_solver_create_direct(A, &o, direct_tiers())
+                           : lsb_hip_solver_create(A, &o);
   if (!sv)
     errx(EXIT_FAILURE, "hip_cdna4: cannot set up the solver");
   double *d_r = (double *)lsb_hip_malloc(bytes), *d_x = (double *)lsb_hip_malloc(bytes);

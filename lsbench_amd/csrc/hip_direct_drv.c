@@ -92,6 +92,51 @@ static unsigned dir_lanes(unsigned len) {
   return L;
 }
 
+unsigned direct_row_lanes(unsigned len) { return dir_lanes(len); }
+
+unsigned long long direct_block_target(unsigned long long entries) {
+  return entries / 1024 < DIR_BLOCK_MIN ? DIR_BLOCK_MIN : entries / 1024;
+}
+
+/* groups: consecutive rows of one lane count, a wavefront's worth; workgroups: groups of about equal entry count */
+void direct_deal_rows(const unsigned *first, const unsigned long long *woff, unsigned r0, unsigned r1,
+                      unsigned long long target, unsigned cap, unsigned *grp, unsigned *ngrp_io, unsigned *blk,
+                      unsigned *bwin, unsigned *nblk_io, unsigned *widest_io, unsigned *lds_m) {
+  const unsigned gfirst = *ngrp_io;
+  if (cap == 0 || cap > DIR_LDS_CAP)
+    cap = DIR_LDS_CAP;
+  unsigned ngrp = gfirst, nblk = *nblk_io, widest = *widest_io;
+  for (unsigned k = r0; k < r1;) {
+    const unsigned L = dir_lanes(k - first[k] + 1);
+    unsigned nr = 1;
+    while (k + nr < r1 && nr < 64 / L && dir_lanes(k + nr - first[k + nr] + 1) == L)
+      nr++;
+    grp[2 * ngrp] = k, grp[2 * ngrp + 1] = nr << 8 | L, ngrp++;
+    k += nr;
+  }
+  for (unsigned g = gfirst; g < ngrp;) {
+    unsigned long long have = 0;
+    unsigned wlo = r1, g1 = g;
+    while (g1 < ngrp && (g1 == g || have < target)) {
+      const unsigned q0 = grp[2 * g1], q1 = q0 + (grp[2 * g1 + 1] >> 8);
+      for (unsigned k = q0; k < q1; k++)
+        if (first[k] < wlo)
+          wlo = first[k];
+      have += woff[q1] - woff[q0];
+      g1++;
+    }
+    const unsigned khi = grp[2 * (g1 - 1)] + (grp[2 * (g1 - 1) + 1] >> 8) - 1, ww = khi - wlo + 1;
+    blk[nblk] = g, bwin[2 * nblk] = wlo, bwin[2 * nblk + 1] = ww, nblk++;
+    if (ww <= cap && ww > widest)
+      widest = ww;
+    for (unsigned q = 0; lds_m && q < 3; q++) /* ... and of k_dir_rows_m at 2, 4, 8 columns: ww kp doubles within the same cap */
+      if (ww <= DIR_LDS_CAP / (2u << q) && ww > lds_m[q])
+        lds_m[q] = ww;
+    g = g1;
+  }
+  *ngrp_io = ngrp, *nblk_io = nblk, *widest_io = widest;
+}
+
 void direct_upload(lsb_hip_solver *sv, struct lsb_skyinv *W, unsigned height, double seconds) {
   const unsigned n = W->n;
   struct direct_dev *d = lsb_calloc(struct direct_dev, 1);
@@ -102,41 +147,10 @@ void direct_upload(lsb_hip_solver *sv, struct lsb_skyinv *W, unsigned height, do
         !(W->parent[k] > k && W->parent[k] <= n) || W->run_end[k] < k || W->run_end[k] >= n ||
         (k > 0 && W->first[k] < k && W->first[k] > W->first[k - 1]))
       errx(EXIT_FAILURE, "hip_cdna4: --krylov direct: the inverse factor is malformed at row %u", k);
-  /* groups: consecutive rows of one lane count, a wavefront's worth; workgroups: groups of about equal entry count */
-  unsigned *grp = lsb_calloc(unsigned, 2 * (size_t)n), ngrp = 0;
-  for (unsigned k = 0; k < n;) {
-    const unsigned L = dir_lanes(k - W->first[k] + 1);
-    unsigned nr = 1;
-    while (k + nr < n && nr < 64 / L && dir_lanes(k + nr - W->first[k + nr] + 1) == L)
-      nr++;
-    grp[2 * ngrp] = k, grp[2 * ngrp + 1] = nr << 8 | L, ngrp++;
-    k += nr;
-  }
-  unsigned long long target = entries / 1024;
-  if (target < DIR_BLOCK_MIN)
-    target = DIR_BLOCK_MIN;
-  unsigned *blk = lsb_calloc(unsigned, (size_t)ngrp + 1), *bwin = lsb_calloc(unsigned, 2 * (size_t)ngrp), nblk = 0;
-  unsigned widest = 0;
-  for (unsigned g = 0; g < ngrp;) {
-    unsigned long long have = 0;
-    unsigned wlo = n, g1 = g;
-    while (g1 < ngrp && (g1 == g || have < target)) {
-      const unsigned r0 = grp[2 * g1], r1 = r0 + (grp[2 * g1 + 1] >> 8);
-      for (unsigned k = r0; k < r1; k++)
-        if (W->first[k] < wlo)
-          wlo = W->first[k];
-      have += W->woff[r1] - W->woff[r0];
-      g1++;
-    }
-    const unsigned khi = grp[2 * (g1 - 1)] + (grp[2 * (g1 - 1) + 1] >> 8) - 1, ww = khi - wlo + 1;
-    blk[nblk] = g, bwin[2 * nblk] = wlo, bwin[2 * nblk + 1] = ww, nblk++;
-    if (ww <= DIR_LDS_CAP && ww > widest)
-      widest = ww;
-    for (unsigned q = 0; q < 3; q++) /* ... and of k_dir_rows_m at 2, 4, 8 columns: ww kp doubles within the same cap */
-      if (ww <= DIR_LDS_CAP / (2u << q) && ww > d->lds_m[q])
-        d->lds_m[q] = ww;
-    g = g1;
-  }
+  unsigned *grp = lsb_calloc(unsigned, 2 * (size_t)n), *blk = lsb_calloc(unsigned, (size_t)n + 1);
+  unsigned *bwin = lsb_calloc(unsigned, 2 * (size_t)n), ngrp = 0, nblk = 0, widest = 0;
+  direct_deal_rows(W->first, W->woff, 0, n, direct_block_target(entries), 0, grp, &ngrp, blk, bwin, &nblk, &widest,
+                   d->lds_m);
   blk[nblk] = ngrp;
   d->k.n = n, d->k.nblk = nblk, d->k.ngrp = ngrp, d->k.lds_doubles = widest;
   d->k.vals = d->mem[0] = dev_upload(W->vals, (size_t)(entries ? entries : 1) * sizeof(double));
@@ -166,6 +180,7 @@ void direct_free(lsb_hip_solver *sv) {
     return;
   graph_drop(&d->graphs);
   direct_multi_free(sv);
+  direct_tier_free(sv);
   for (unsigned i = 0; i < sizeof d->mem / sizeof d->mem[0]; i++)
     lsb_hip_free(d->mem[i]);
   lsb_hip_free(d->d_t);
@@ -186,8 +201,12 @@ static void dir_enqueue_rounds(void *ctx, int rounds) {
   struct direct_dev *d = e->sv->dir;
   const int no_resid = !(e->sv->tol_run > 0.0) && e->sv->o.maxit <= 1; /* the reference's protocol: two launches */
   for (int i = 0; i < rounds; i++) {
-    lsb_k_dir_rows(&d->k, e->d_b, s->d_r, d->d_t, s->d_st, 0, g_stream);
-    lsb_k_dir_cols(&d->k, d->d_t, e->d_x, s->d_st, 0, g_stream);
+    if (d->tier)
+      direct_tier_enqueue(e->sv, e->d_b, s->d_r, e->d_x, 0);
+    else {
+      lsb_k_dir_rows(&d->k, e->d_b, s->d_r, d->d_t, s->d_st, 0, g_stream);
+      lsb_k_dir_cols(&d->k, d->d_t, e->d_x, s->d_st, 0, g_stream);
+    }
     if (!no_resid)
       lsb_k_dir_resid(s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->lanes, e->d_b, e->d_x, s->d_r, s->d_parts2,
                       &d->nrec, s->d_st, g_stream);
@@ -247,8 +266,12 @@ int direct_apply_dev(lsb_hip_solver *sv, const double *d_r, double *d_z) {
   struct shard *s = &sv->sh[0];
   struct direct_dev *d = sv->dir;
   LSB_CHK_HIP(hipMemsetAsync(&s->d_st->status, 0, sizeof(int), g_stream)); /* the launches are gated on it */
-  lsb_k_dir_rows(&d->k, d_r, d_r, d->d_t, s->d_st, 1, g_stream);
-  lsb_k_dir_cols(&d->k, d->d_t, d_z, s->d_st, 1, g_stream);
+  if (d->tier)
+    direct_tier_enqueue(sv, d_r, d_r, d_z, 1);
+  else {
+    lsb_k_dir_rows(&d->k, d_r, d_r, d->d_t, s->d_st, 1, g_stream);
+    lsb_k_dir_cols(&d->k, d->d_t, d_z, s->d_st, 1, g_stream);
+  }
   drain_stream(sv, "lsb_hip_solver_precond_dev");
   return 0;
 }
@@ -263,6 +286,6 @@ int lsb_hip_solver_direct_info(const lsb_hip_solver *sv, unsigned long long *ent
   if (height)
     *height = d->height;
   if (bytes_per_round) /* the two products: W twice, first / woff per row twice, P r in, t out and in, x out */
-    *bytes_per_round = 16ull * d->entries + (24ull + 32ull) * d->k.n;
+    *bytes_per_round = d->tier ? direct_tier_round_bytes(sv) : 16ull * d->entries + (24ull + 32ull) * d->k.n;
   return 0;
 }

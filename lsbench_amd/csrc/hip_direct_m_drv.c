@@ -54,7 +54,7 @@ static unsigned dirm_lds(const lsb_hip_solver *sv, unsigned kp) { return sv->dir
 /* Bytes one round of a block of width kp(nrhs) streams: W twice and first / woff per row twice whatever the width
  * (lsb_hip_solver_direct_info's figure at one column), and per column P V in, T out and in, X out */
 unsigned long long lsb_hip_solver_direct_multi_round_bytes(const lsb_hip_solver *sv, unsigned nrhs) {
-  if (!sv || !sv->dir || nrhs == 0)
+  if (!sv || !sv->dir || sv->dir->tier || nrhs == 0)
     return 0;
   const struct direct_dev *d = sv->dir;
   const unsigned kp = nrhs == 1 ? 1u : block_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs);
@@ -133,7 +133,7 @@ int lsb_hip_solver_solve_direct_multi_dev(lsb_hip_solver *sv, unsigned nrhs, con
                                           size_t ldx, struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, 0, d_B, ldb, d_X, ldx) || !sv->dir)
+  if (block_args_bad(sv, nrhs, 0, d_B, ldb, d_X, ldx) || !sv->dir || sv->dir->tier)
     return 2;
   if (nrhs == 1)
     return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
@@ -153,7 +153,7 @@ int lsb_hip_solver_solve_direct_multi(lsb_hip_solver *sv, unsigned nrhs, const d
                                       size_t ldx, struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, 0, B, ldb, X, ldx) || !sv->dir)
+  if (block_args_bad(sv, nrhs, 0, B, ldb, X, ldx) || !sv->dir || sv->dir->tier)
     return 2;
   return block_solve_host(lsb_hip_solver_solve_direct_multi_dev, 0, sv, nrhs, B, ldb, X, ldx, res);
 }
@@ -163,7 +163,7 @@ int lsb_hip_solver_direct_apply_multi_dev(lsb_hip_solver *sv, unsigned nrhs, con
                                           size_t ldz) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, 0, d_R, ldr, d_Z, ldz) || !sv->dir)
+  if (block_args_bad(sv, nrhs, 0, d_R, ldr, d_Z, ldz) || !sv->dir || sv->dir->tier)
     return 2;
   if (nrhs == 1)
     return lsb_hip_solver_precond_dev(sv, d_R, d_Z);

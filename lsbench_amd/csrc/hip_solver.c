@@ -707,8 +707,8 @@ static struct lsb_hip_opts solver_opts(const struct lsb_hip_opts *o_in, int shar
   return o;
 }
 
-lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
-                                      const struct lsb_hip_opts *o_in) {
+/* tiers: 1 = the direct solver's single skyline (and every other solver), else lsb_hip_solver_create_direct's */
+static lsb_hip_solver *solver_create(const struct csr *A, const struct lsb_hip_opts *o_in, int tiers) {
   if (!lsb_initialized || !A || A->nrows == 0)
     return NULL;
   struct lsb_hip_opts o = solver_opts(o_in, 0);
@@ -719,7 +719,12 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
   /* the direct solver factorises first: what it refuses, it refuses before anything is allocated on the device */
   unsigned dir_height = 0;
   double dir_seconds = 0.0;
-  struct lsb_skyinv *dirW = o.krylov == LSB_KRYLOV_DIRECT ? direct_factor(S, &o, &dir_height, &dir_seconds) : NULL;
+  struct lsb_skyinv *dirW = NULL;
+  struct lsb_tierinv *dirT = NULL;
+  if (o.krylov == LSB_KRYLOV_DIRECT && tiers == 1)
+    dirW = direct_factor(S, &o, &dir_height, &dir_seconds);
+  else if (o.krylov == LSB_KRYLOV_DIRECT)
+    dirT = direct_tier_factor(S, &o, tiers, &dir_height, &dir_seconds);
   /* a constant-coefficient 2-D grid whose lines are not whole slices: pad the lines (lsb_csr_pad_lines) --
    * the +-nx diagonals become whole-slice offsets and the z-column forms apply along y.  b and x
    * travel through the same gather / scatter as a re-ordering's; the pad unknowns stay exactly 0.
@@ -797,7 +802,24 @@ lsb_hip_solver *lsb_hip_solver_create(const struct csr *A,
   solver_finish_setup(sv);
   if (dirW)
     direct_upload(sv, dirW, dir_height, dir_seconds);
+  if (dirT)
+    direct_tier_upload(sv, dirT, dir_height, dir_seconds);
   return sv;
+}
+
+lsb_hip_solver *lsb_hip_solver_create(const struct csr *A, const struct lsb_hip_opts *o_in) {
+  return solver_create(A, o_in, 1);
+}
+
+lsb_hip_solver *lsb_hip_solver_create_direct(const struct csr *A, const struct lsb_hip_opts *o_in, int tiers) {
+  struct lsb_hip_opts o;
+  if (o_in)
+    o = *o_in;
+  else
+    lsb_hip_get_opts(&o);
+  if (o.krylov != LSB_KRYLOV_DIRECT || tiers < 0 || tiers > LSB_DIRECT_MAX_TIERS)
+    return NULL;
+  return solver_create(A, o_in, tiers);
 }
 
 lsb_hip_solver *lsb_hip_solver_create_dist(const struct csr *A_rows,

@@ -20,6 +20,7 @@
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
  *   hip_direct_drv.c the direct solver: factor at creation, rounds of x (+)= W^T W r on a skyline inverse factor
  *   hip_direct_m_drv.c  ... on blocks of right-hand sides: W streamed once per product for a block of columns
+ *   hip_direct_t_drv.c  ... on a tiered factor, for operators whose single skyline is over the entry budget
  *   hip_rich_m_drv.c ... AMG as the solver on blocks of right-hand sides: the hierarchy streamed once per cycle
  *   hip_block.c      interleaved blocks of right-hand sides, what their two drivers share: the service rules, the work
  *                    area (struct block_work), Z = M^-1 R on a block, the enqueue and host-buffer wrappers
@@ -388,6 +389,14 @@ struct lsb_hip_solver {
     struct graph_cache graphs;
     const double *graph_b;
     unsigned lds_m[3];
+    /* a tiered factor (hip_direct_t_drv.c), NULL on a single skyline: k is then unused but for k.n, d_t is y, and
+     * the blocks of right-hand sides are refused */
+    struct direct_tier_dev {
+      struct lsb_dirt_dev k;
+      void *mem[17];
+      double *d_z;
+      unsigned long long coupling;
+    } *tier;
     struct dirm_work {
       struct block_work blk;
       double *rec;
@@ -718,6 +727,31 @@ LSB_INTERNAL void lsb_k_dir_resid(unsigned n, const int *offs, const int *cols, 
                                   const double *b, const double *x, double *r, double *records, unsigned *nrecords,
                                   const struct lsb_pcg_state *st, void *stream);
 LSB_INTERNAL void lsb_k_dir_step(struct lsb_pcg_state *st, const double *records, unsigned nrecords, void *stream);
+/* the dealing of the skyline rows r0 .. r1 - 1 to k_dir_rows, appended to grp (at *ngrp), blk and bwin (at *nblk):
+ * groups of consecutive rows with one lane count, workgroups of about `target` entries; *widest: the widest window
+ * within `cap` doubles (0 or more than DIR_LDS_CAP: DIR_LDS_CAP), lds_m (may be NULL): the same per width of hip_direct_m.hip.  The caller closes blk[*nblk] */
+LSB_INTERNAL void direct_deal_rows(const unsigned *first, const unsigned long long *woff, unsigned r0, unsigned r1,
+                                   unsigned long long target, unsigned cap, unsigned *grp, unsigned *ngrp,
+                                   unsigned *blk, unsigned *bwin, unsigned *nblk, unsigned *widest, unsigned *lds_m);
+LSB_INTERNAL unsigned direct_row_lanes(unsigned len); /* lanes per row from its length alone: 1 .. 64 */
+LSB_INTERNAL unsigned long long direct_block_target(unsigned long long entries);
+/* hip_direct_t_drv.c: the direct solver on a tiered factor (lsb_hip_solver_create_direct), and the launchers of
+ * hip_direct_t.hip (t: the tier) */
+LSB_INTERNAL struct lsb_tierinv *direct_tier_factor(const struct csr *S, const struct lsb_hip_opts *o, int tiers,
+                                                    unsigned *height, double *seconds);
+LSB_INTERNAL void direct_tier_upload(lsb_hip_solver *sv, struct lsb_tierinv *T, unsigned height, double seconds);
+LSB_INTERNAL void direct_tier_free(lsb_hip_solver *sv);
+LSB_INTERNAL unsigned long long direct_tier_round_bytes(const lsb_hip_solver *sv);
+/* one application x (+)= P^T L^-T L^-1 P r: 4 m - 2 launches; src, mode: as in k_dir_rows, k_dir_cols */
+LSB_INTERNAL void direct_tier_enqueue(lsb_hip_solver *sv, const double *d_b, const double *d_r, double *d_x, int fixed);
+LSB_INTERNAL void lsb_k_dirt_rows(const struct lsb_dirt_dev *d, unsigned t, const double *b, const double *r,
+                                  const double *v, double *y, const struct lsb_pcg_state *st, int src, void *stream);
+LSB_INTERNAL void lsb_k_dirt_cols(const struct lsb_dirt_dev *d, unsigned t, const double *y, double *z, double *x,
+                                  const struct lsb_pcg_state *st, int mode, void *stream);
+LSB_INTERNAL void lsb_k_dirt_fwd(const struct lsb_dirt_dev *d, unsigned t, const double *b, const double *r,
+                                 const double *y, double *z, const struct lsb_pcg_state *st, int src, void *stream);
+LSB_INTERNAL void lsb_k_dirt_bwd(const struct lsb_dirt_dev *d, unsigned t, const double *z, double *y,
+                                 const struct lsb_pcg_state *st, void *stream);
 /* hip_direct_m_drv.c: the direct solver on blocks of right-hand sides, and the launchers of hip_direct_m.hip (kp: 2, 4
  * or 8; interleaved blocks; st: the gate, NULL in rows_m / cols_m for one un-gated application that reads b and stores) */
 LSB_INTERNAL void direct_multi_free(lsb_hip_solver *sv); /* the work areas of every width */

@@ -83,6 +83,9 @@ static void usage(const char *prog) {
   printf("                       direct = a sparse direct solve: nested dissection, Cholesky, the inverse factor applied in\n");
   printf("                       two launches per round (--tol 0 --maxit 1 is the reference's direct protocol; operators of\n");
   printf("                       a few thousand to a few tens of thousands of rows)\n");
+  printf("                       --direct-tiers <K>: the inverse factor of --krylov direct in K tiers, for larger\n");
+  printf("                       operators: only the diagonal blocks are inverted, 4 K - 2 launches per round;\n");
+  printf("                       0 = the fewest that fit, 1 = the single skyline (default), at most 6\n");
   printf("                       (bicgstab + Jacobi is the reference's Ginkgo backend; its stop setting is --tol 1e-4)\n");
   printf("  --restart <M>        (hip) GMRES restart length, 1..32, default 30\n");
   printf("  --precond <jacobi|l1|none|cheb|bj|fsai|amg> (hip) diag(S); diag(sum_j |S_ij|); none; Chebyshev\n");
@@ -131,7 +134,7 @@ struct lsbench *lsbench_init(int argc, char *argv[]) {
       {"amg-coarse", required_argument, 0, 80}, {"amg-max-levels", required_argument, 0, 80},
       {"amg-tail-rows", required_argument, 0, 80}, {"amg-smoother", required_argument, 0, 80},
       {"amg-cheb-ratio", required_argument, 0, 80}, {"amg-precision", required_argument, 0, 80},
-      {"fsai-blocks", required_argument, 0, 80},
+      {"fsai-blocks", required_argument, 0, 80}, {"direct-tiers", required_argument, 0, 80},
       {0, 0, 0, 0}};
 
   /* zero-filled => solver 0 (CUSOLVER), ordering 0 (RCM), FP64: the

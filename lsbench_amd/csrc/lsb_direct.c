@@ -23,6 +23,9 @@
  *   W          column j of L^-1 lives on the path j -> root: solve L w = e_j along it, column-oriented; OpenMP over
  *              columns, each of which writes its own slots.  Row k of W is the run of columns [first_k, k] (its
  *              subtree), dense: (L^-1)_kj != 0 exactly when k is an ancestor of j.
+ *   tiers      for operators whose single skyline is over the budget: the tree cut by subtree size into tiers, the
+ *              rows numbered tier by tier; W is kept for the diagonal blocks alone and the blocks below them are the
+ *              sparse rows of L (tier_build; one tier is the single skyline, computed by the same code).
  */
 #define _GNU_SOURCE
 #include <math.h>
@@ -265,6 +268,129 @@ unsigned long long lsb_csr_skyline_count(const struct csr *S, const unsigned *pe
   return total;
 }
 
+/* ---- tiers ---------------------------------------------------------------------------------------------------- */
+/* The thresholds of m tiers: T_i, i = 1 .. m - 1, the smallest integer with T_i^m >= n^i.  In integers, so that a
+ * model in another language reproduces them: eight limbs of 32 bits hold n^5 and T^6 for every 32-bit n */
+struct big {
+  unsigned w[8];
+};
+
+static void big_pow(struct big *r, unsigned base, unsigned e) {
+  memset(r, 0, sizeof *r);
+  r->w[0] = 1;
+  while (e-- > 0) {
+    unsigned long long c = 0;
+    for (unsigned l = 0; l < 8; l++)
+      c += (unsigned long long)r->w[l] * base, r->w[l] = (unsigned)c, c >>= 32;
+  }
+}
+
+static int big_ge(const struct big *a, const struct big *b) {
+  for (unsigned l = 8; l-- > 0;)
+    if (a->w[l] != b->w[l])
+      return a->w[l] > b->w[l];
+  return 1;
+}
+
+static void tier_thresholds(unsigned n, unsigned m, unsigned *T) {
+  for (unsigned i = 1; i < m; i++) {
+    struct big want, have;
+    big_pow(&want, n, i);
+    unsigned lo = 1, hi = n ? n : 1; /* n^m >= n^i */
+    while (lo < hi) {
+      const unsigned mid = lo + (hi - lo) / 2;
+      big_pow(&have, mid, m);
+      if (big_ge(&have, &want))
+        hi = mid;
+      else
+        lo = mid + 1;
+    }
+    T[i - 1] = lo;
+  }
+}
+
+/* tier[v] = how many of the thresholds size[v] exceeds, then the tiers nobody is in dropped; lo[t]: vertices in the
+ * tiers below t (lo[ntier] = n).  A subtree is no smaller than its children's: tiers never decrease towards the root.
+ * Returns ntier */
+static unsigned tier_assign(unsigned n, unsigned m, const unsigned *size, unsigned *tier, unsigned *lo) {
+  unsigned T[LSB_DIRECT_MAX_TIERS], cnt[LSB_DIRECT_MAX_TIERS] = {0}, map[LSB_DIRECT_MAX_TIERS] = {0}, ntier = 0;
+  tier_thresholds(n, m, T);
+  for (unsigned v = 0; v < n; v++) {
+    unsigned t = 0;
+    while (t + 1 < m && size[v] > T[t])
+      t++;
+    tier[v] = t, cnt[t]++;
+  }
+  lo[0] = 0;
+  for (unsigned t = 0; t < m; t++)
+    if (cnt[t])
+      map[t] = ntier, lo[ntier + 1] = lo[ntier] + cnt[t], ntier++;
+  if (!ntier) /* n = 0 */
+    ntier = 1, lo[1] = 0;
+  for (unsigned v = 0; v < n; v++)
+    tier[v] = map[tier[v]];
+  return ntier;
+}
+
+int lsb_csr_tiered_count(const struct csr *S, const unsigned *perm, unsigned tiers, unsigned long long *w_entries,
+                         unsigned long long *coupling_entries, unsigned *height) {
+  const unsigned n = S->nrows, n1 = n ? n : 1;
+  unsigned long long w = 0, c = 0;
+  unsigned h = 0, lo[LSB_DIRECT_MAX_TIERS + 1];
+  int rc = tiers >= 1 && tiers <= LSB_DIRECT_MAX_TIERS ? 0 : 2;
+  unsigned *inv = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
+  unsigned *parent = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
+  unsigned *work = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
+  unsigned *size = (unsigned *)calloc(n1, sizeof(unsigned));
+  unsigned *tier = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
+  if (!rc && !(inv && parent && work && size && tier))
+    rc = 3;
+  if (!rc && invert_perm(n, perm, inv))
+    rc = 2;
+  if (!rc) {
+    etree(S, perm, inv, parent, work);
+    for (unsigned k = 0; k < n; k++) { /* parent > child: sizes bottom-up in index order */
+      size[k] += 1;
+      if (parent[k] != NONE)
+        size[parent[k]] += size[k];
+    }
+    tier_assign(n, tiers, size, tier, lo);
+    /* W_tt: a column's depth inside its tier; the height is the whole tree's.  size[] becomes the depth, work[] the
+     * depth inside the tier */
+    for (unsigned k = n; k-- > 0;) {
+      const unsigned p = parent[k];
+      size[k] = p == NONE ? 1u : size[p] + 1u;
+      work[k] = p == NONE || tier[p] != tier[k] ? 1u : work[p] + 1u;
+      w += work[k];
+      if (size[k] > h)
+        h = size[k];
+    }
+    /* the entries of L from the row subtrees: those that leave the row's tier are the coupling */
+    unsigned *mark = work;
+    for (unsigned k = 0; k < n; k++)
+      mark[k] = NONE;
+    for (unsigned k = 0; k < n; k++) {
+      mark[k] = k;
+      const unsigned row = perm[k];
+      for (unsigned j = S->offs[row]; j < S->offs[row + 1]; j++) {
+        const unsigned col = S->cols[j] - S->base;
+        if (col >= n || inv[col] >= k)
+          continue;
+        for (unsigned i = inv[col]; mark[i] != k; i = parent[i])
+          mark[i] = k, c += tier[i] != tier[k];
+      }
+    }
+  }
+  if (w_entries)
+    *w_entries = w;
+  if (coupling_entries)
+    *coupling_entries = c;
+  if (height)
+    *height = h;
+  free(inv), free(parent), free(work), free(size), free(tier);
+  return rc;
+}
+
 /* ---- the factor ----------------------------------------------------------------------------------------------- */
 void lsb_skyinv_free(struct lsb_skyinv *W) {
   if (!W)
@@ -273,10 +399,23 @@ void lsb_skyinv_free(struct lsb_skyinv *W) {
   free(W);
 }
 
-struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *perm_in, int *why) {
+void lsb_tierinv_free(struct lsb_tierinv *W) {
+  if (!W)
+    return;
+  free(W->perm), free(W->first), free(W->woff), free(W->vals), free(W->parent), free(W->run_end);
+  free(W->coffs), free(W->ccols), free(W->cvals), free(W->toffs), free(W->tcols), free(W->tvals);
+  free(W);
+}
+
+/* The factor in `tiers` tiers (>= 1; one tier: the single skyline, nothing coupled).  Tier-major numbering: sorted by
+ * (tier, postorder index), still an elimination order with the same fill, and the part of a subtree that lies in
+ * tier t is a run of indices inside tier t's range.  L is then block lower triangular: W_tt = (L_tt)^-1 is a skyline
+ * like the single one (first clipped at the tier's start, parent = n on the root of a tier's tree), and the blocks
+ * below the diagonal are the rows of L itself, kept twice: C by rows, C^T by tier and lower-tier column */
+static struct lsb_tierinv *tier_build(const struct csr *S, const unsigned *perm_in, unsigned tiers, int *why) {
   const unsigned n = S->nrows, n1 = n ? n : 1;
   int bad = 0;
-  struct lsb_skyinv *W = lsb_calloc(struct lsb_skyinv, 1);
+  struct lsb_tierinv *W = lsb_calloc(struct lsb_tierinv, 1);
   unsigned *inv = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
   unsigned *par0 = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
   unsigned *tmp = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
@@ -284,6 +423,9 @@ struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *
   unsigned *head = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
   unsigned *next = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
   unsigned *post = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
+  unsigned *tier0 = (unsigned *)malloc((size_t)n1 * sizeof(unsigned)); /* by the index of the given ordering */
+  unsigned *tier = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));  /* by the tier-major index */
+  unsigned *ord = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));   /* tier-major index -> given index */
   unsigned *cc = NULL, *lrow = NULL;
   unsigned long long *lp = NULL;
   double *lval = NULL, *x = NULL;
@@ -296,8 +438,8 @@ struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *
     W->run_end = (unsigned *)malloc((size_t)n1 * sizeof(unsigned));
     W->woff = (unsigned long long *)calloc((size_t)n + 1, sizeof(unsigned long long));
   }
-  if (!W || !inv || !par0 || !tmp || !size || !head || !next || !post || !W->perm || !W->first || !W->parent ||
-      !W->run_end || !W->woff || invert_perm(n, perm_in, inv)) {
+  if (!W || !inv || !par0 || !tmp || !size || !head || !next || !post || !tier0 || !tier || !ord || !W->perm ||
+      !W->first || !W->parent || !W->run_end || !W->woff || invert_perm(n, perm_in, inv)) {
     bad = 3;
     goto out;
   }
@@ -347,11 +489,28 @@ struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *
       goto out;
     }
   }
+  /* the tiers, and the postorder sorted by them (stable: inside a tier the postorder stays) */
+  W->ntier = tier_assign(n, tiers, size, tier0, W->lo);
+  {
+    unsigned at[LSB_DIRECT_MAX_TIERS];
+    memcpy(at, W->lo, sizeof at);
+    for (unsigned k = 0; k < n; k++)
+      ord[at[tier0[post[k]]]++] = post[k];
+  }
+  unsigned *full = next; /* the whole tree in the new numbering (n on a root): what the factorisation climbs */
   for (unsigned k = 0; k < n; k++)
-    W->perm[k] = perm_in[post[k]], tmp[post[k]] = k; /* tmp: old tree index -> new */
+    W->perm[k] = perm_in[ord[k]], tmp[ord[k]] = k, tier[k] = tier0[ord[k]]; /* tmp: given index -> new */
   for (unsigned k = 0; k < n; k++) {
-    W->parent[k] = par0[post[k]] == NONE ? n : tmp[par0[post[k]]];
-    W->first[k] = k + 1 - size[post[k]];
+    full[k] = par0[ord[k]] == NONE ? n : tmp[par0[ord[k]]];
+    W->parent[k] = full[k] < n && tier[full[k]] == tier[k] ? full[k] : n;
+  }
+  unsigned *tsize = post; /* the part of k's subtree in k's own tier */
+  memset(tsize, 0, (size_t)n1 * sizeof(unsigned));
+  for (unsigned k = 0; k < n; k++) {
+    tsize[k] += 1;
+    if (W->parent[k] < n)
+      tsize[W->parent[k]] += tsize[k];
+    W->first[k] = k + 1 - tsize[k];
   }
   for (unsigned k = n; k-- > 0;)
     W->run_end[k] = (k + 1 < n && W->parent[k] == k + 1) ? W->run_end[k + 1] : k;
@@ -371,13 +530,18 @@ struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *
     goto out;
   }
   unsigned *mark = inv, *pat = head;
+  unsigned long long coupling = 0;
   for (unsigned k = 0; k < n; k++)
     mark[k] = NONE;
   for (unsigned k = 0; k < n; k++) {
     mark[k] = k;
     for (unsigned j = B->offs[k]; j < B->offs[k + 1] && B->cols[j] < k; j++)
-      for (unsigned i = B->cols[j]; mark[i] != k; i = W->parent[i])
-        mark[i] = k, cc[i]++;
+      for (unsigned i = B->cols[j]; mark[i] != k; i = full[i])
+        mark[i] = k, cc[i]++, coupling += tier[i] != tier[k];
+  }
+  if (W->woff[n] + 3 * coupling > LSB_DIRECT_MAX_ENTRIES) { /* C and C^T: 12 B an entry each */
+    bad = 2;
+    goto out;
   }
   for (unsigned k = 0; k < n; k++)
     lp[k + 1] = lp[k] + cc[k];
@@ -407,7 +571,7 @@ struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *
         continue;
       }
       x[c] = B->vals[j];
-      for (unsigned i = c; mark[i] != k; i = W->parent[i])
+      for (unsigned i = c; mark[i] != k; i = full[i])
         mark[i] = k, pat[np++] = i;
     }
     qsort(pat, np, sizeof(unsigned), cmp_unsigned);
@@ -425,8 +589,9 @@ struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *
     diag[k] = sqrt(d);
   }
   if (!bad) {
-    /* column j of W = L^-1 on the path j -> root: w_j = 1 / l_jj; ascending m on the path, w_m final, then
-     * w_i -= l_im w_m for the rows i of column m (ancestors of m: on the path), and w_i /= l_ii when its turn comes */
+    /* column j of W_tt = (L_tt)^-1 on the path j -> the root of its tier's tree: w_j = 1 / l_jj; ascending m on the
+     * path, w_m final, then w_i -= l_im w_m for the rows i of column m in this tier (ancestors of m: on the path; the
+     * rows of a column ascend, so they come first in its list), and w_i /= l_ii when its turn comes */
     int oom = 0;
 #pragma omp parallel
     {
@@ -439,13 +604,13 @@ struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *
       for (long long jj = 0; jj < (long long)n; jj++) {
         if (!w)
           continue;
-        const unsigned j = (unsigned)jj;
+        const unsigned j = (unsigned)jj, hi = W->lo[tier[j] + 1];
         w[j] = 1.0;
         for (unsigned m = j; m < n; m = W->parent[m]) {
           const double wm = w[m] / diag[m];
           w[m] = 0.0;
           W->vals[W->woff[m] + (j - W->first[m])] = wm;
-          for (unsigned long long p = lp[m]; p < lp[m + 1]; p++)
+          for (unsigned long long p = lp[m]; p < lp[m + 1] && lrow[p] < hi; p++)
             w[lrow[p]] -= lval[p] * wm;
         }
       }
@@ -455,15 +620,99 @@ struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *
       bad = 3;
   }
   free(diag);
+  if (!bad) {
+    /* C: the rows of tiers >= 1, row i at coffs[i - lo[1]], columns ascending (filled column by column).  C^T: for
+     * t = 1 .. ntier - 1 the columns j < lo[t] with their rows in tier t, lo[t] + 1 offsets each, one after another
+     * (tier t's begin at the sum of lo[s] + 1 over 1 <= s < t); cc[j] walks column j's list, whose rows ascend through the tiers */
+    const unsigned lo1 = W->lo[1 < W->ntier ? 1 : W->ntier], nc = n - lo1;
+    size_t nt = 1;
+    for (unsigned t = 1; t < W->ntier; t++)
+      nt += (size_t)W->lo[t] + 1;
+    W->coffs = (unsigned *)calloc((size_t)nc + 1, sizeof(unsigned));
+    W->ccols = (unsigned *)malloc((size_t)(coupling ? coupling : 1) * sizeof(unsigned));
+    W->cvals = (double *)malloc((size_t)(coupling ? coupling : 1) * sizeof(double));
+    W->toffs = (unsigned *)calloc(nt, sizeof(unsigned));
+    W->tcols = (unsigned *)malloc((size_t)(coupling ? coupling : 1) * sizeof(unsigned));
+    W->tvals = (double *)malloc((size_t)(coupling ? coupling : 1) * sizeof(double));
+    if (!W->coffs || !W->ccols || !W->cvals || !W->toffs || !W->tcols || !W->tvals) {
+      bad = 3;
+      goto out;
+    }
+    for (unsigned j = 0; j < n; j++) {
+      unsigned long long p = lp[j];
+      while (p < lp[j + 1] && lrow[p] < W->lo[tier[j] + 1])
+        p++;
+      cc[j] = (unsigned)(p - lp[j]); /* where column j leaves its own tier */
+      for (; p < lp[j + 1]; p++)
+        W->coffs[lrow[p] - lo1 + 1]++;
+    }
+    for (unsigned i = 0; i < nc; i++)
+      W->coffs[i + 1] += W->coffs[i];
+    unsigned *fill = mark;
+    memcpy(fill, W->coffs, (size_t)nc * sizeof(unsigned));
+    for (unsigned j = 0; j < n; j++)
+      for (unsigned long long p = lp[j] + cc[j]; p < lp[j + 1]; p++) {
+        const unsigned e = fill[lrow[p] - lo1]++;
+        W->ccols[e] = j, W->cvals[e] = lval[p];
+      }
+    unsigned e = 0;
+    size_t at = 0;
+    for (unsigned t = 1; t < W->ntier; t++) {
+      for (unsigned j = 0; j < W->lo[t]; j++) {
+        W->toffs[at++] = e;
+        for (; lp[j] + cc[j] < lp[j + 1] && lrow[lp[j] + cc[j]] < W->lo[t + 1]; cc[j]++)
+          W->tcols[e] = lrow[lp[j] + cc[j]], W->tvals[e] = lval[lp[j] + cc[j]], e++;
+      }
+      W->toffs[at++] = e;
+    }
+  }
 out:
-  free(inv), free(par0), free(tmp), free(size), free(head), free(next), free(post);
+  free(inv), free(par0), free(tmp), free(size), free(head), free(next), free(post), free(tier0), free(tier), free(ord);
   free(cc), free(lp), free(lrow), free(lval), free(x);
   lsb_csr_free(B);
   if (why)
     *why = bad;
   if (bad) {
-    lsb_skyinv_free(W);
+    lsb_tierinv_free(W);
     return NULL;
   }
   return W;
+}
+
+struct lsb_skyinv *lsb_csr_skyline_inverse(const struct csr *S, const unsigned *perm_in, int *why) {
+  struct lsb_tierinv *T = tier_build(S, perm_in, 1, why);
+  struct lsb_skyinv *W = T ? lsb_calloc(struct lsb_skyinv, 1) : NULL;
+  if (!W) {
+    if (T && why)
+      *why = 3;
+    lsb_tierinv_free(T);
+    return NULL;
+  }
+  W->n = T->n, W->perm = T->perm, W->first = T->first, W->woff = T->woff, W->vals = T->vals;
+  W->parent = T->parent, W->run_end = T->run_end;
+  T->perm = T->first = T->parent = T->run_end = NULL, T->woff = NULL, T->vals = NULL;
+  lsb_tierinv_free(T);
+  return W;
+}
+
+struct lsb_tierinv *lsb_csr_tiered_inverse(const struct csr *S, const unsigned *perm_in, unsigned tiers, int *why) {
+  if (tiers > LSB_DIRECT_MAX_TIERS) {
+    if (why)
+      *why = 3;
+    return NULL;
+  }
+  if (tiers == 0) { /* the fewest tiers that fit, by the symbolic count alone */
+    for (tiers = 1; tiers < LSB_DIRECT_MAX_TIERS; tiers++) {
+      unsigned long long w = 0, c = 0;
+      const int rc = lsb_csr_tiered_count(S, perm_in, tiers, &w, &c, NULL);
+      if (rc) {
+        if (why)
+          *why = 3;
+        return NULL;
+      }
+      if (w + 3 * c <= LSB_DIRECT_MAX_ENTRIES)
+        break;
+    }
+  }
+  return tier_build(S, perm_in, tiers, why);
 }

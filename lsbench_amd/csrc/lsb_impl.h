@@ -490,6 +490,23 @@ struct lsb_dir_dev {
   const unsigned *first, *perm, *parent, *run_end, *grp, *blk, *bwin;
 };
 
+/* ---- the direct solver on a tiered factor (hip_direct_t.hip; launchers in hip_solver.h) ----
+ * struct lsb_tierinv on the device.  grp / blk / bwin as in struct lsb_dir_dev, dealt tier by tier: tier t's
+ * workgroups are blk0 .. blk0 + nblk - 1 and stage lds_doubles at the most.  cgrp / tgrp: the rows of C and of C^T in
+ * groups of the same shape (first row, rows << 8 | lanes per row), tier t's at cg0 .. cg1 - 1 and tg0 .. tg1 - 1;
+ * tbase: where tier t's offsets begin in toffs. */
+struct lsb_dirt_tier {
+  unsigned lo, hi, blk0, nblk, lds_doubles, cg0, cg1, tg0, tg1, tbase;
+};
+struct lsb_dirt_dev {
+  unsigned n, ntier;
+  const double *vals, *cvals, *tvals;
+  const unsigned long long *woff;
+  const unsigned *first, *perm, *parent, *run_end, *grp, *blk, *bwin;
+  const unsigned *coffs, *ccols, *toffs, *tcols, *cgrp, *tgrp;
+  struct lsb_dirt_tier t[LSB_DIRECT_MAX_TIERS];
+};
+
 /* ---- preconditioners with z as a vector (hip_precond_k.hip) -------------------- */
 void lsb_k_dot2(unsigned n, const double *r, const double *z, double *partials2,
                 unsigned *npartials, const struct lsb_pcg_state *st, void *stream);
