@@ -934,7 +934,8 @@ int lsb_hip_solver_direct_info(const lsb_hip_solver *s, unsigned long long *entr
  * out of range; what lsb_hip_solver_create refuses for a direct solver is refused in the same way, and so is a factor
  * over the budget in the tiers asked for.  A round is 4 m - 2 launches for m tiers instead of 2, then the residual
  * and the stop test as before.  Every solve entry point of a direct solver works on it (solve[_dev], solve_x0[_dev],
- * solve_seq[_dev], precond_dev, opts.verify) but the blocks of right-hand sides, which answer 2.
+ * solve_seq[_dev], precond_dev, opts.verify) but the blocks of right-hand sides, which answer 2: blocks on a tiered
+ * factor have entry points of their own, lsb_hip_solver_solve_direct_tier_multi[_dev] below.
  * On such a solver lsb_hip_solver_direct_info reports the entries of the W_tt, the height of the whole tree, and as
  * bytes per round 16 per entry of the W_tt, 24 per coupling entry (C and C^T once each: a value and a 32-bit column),
  * and 104 per row (first / woff twice, the offsets of C and C^T, P r, y, z and x). */
@@ -1053,6 +1054,28 @@ int lsb_hip_solver_direct_apply_multi_dev(lsb_hip_solver *s, unsigned nrhs, cons
 /* bytes one round of a block of width kp(nrhs) streams: 16 per entry of W and 24 per row whatever the width, 32 per
  * row and column (lsb_hip_solver_direct_info's figure at kp = 1); 0 for any other solver or nrhs == 0 */
 unsigned long long lsb_hip_solver_direct_multi_round_bytes(const lsb_hip_solver *s, unsigned nrhs);
+/* The same on every direct solver, one with a tiered factor (lsb_hip_solver_create_direct) included: there a round on
+ * a block is the 4 m - 2 launches of the tiers in their block form (hip_direct_tm.hip), every entry of the W_tt, of C
+ * and of C^T loaded once per product for all columns, then the residual and the stop test of the blocks above.  The
+ * three entry points above keep answering 2 on a tiered solver; these forward to them on a single skyline (tiers = 1
+ * included).  Arguments, layout, block cutting, return values, results and the stop rules are theirs, and so is the
+ * contract: a column of a block has the bits of that column solved alone by lsb_hip_solver_solve_dev (applied alone by
+ * lsb_hip_solver_precond_dev) on the same solver; nrhs == 1 is forwarded to those.  1 when the backend is not
+ * initialised; 2 for bad arguments and for a solver that is not direct: nothing is written.  The work area of a width
+ * (five block vectors on a tiered solver) is made when the solver first sees a block of that width.
+ * Not built on these blocks: warm starts, sequences and opts.verify; more than 8 columns per block; fp32 storage. */
+int lsb_hip_solver_solve_direct_tier_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_B, size_t ldb,
+                                               double *d_X, size_t ldx, struct lsb_hip_result *res);
+int lsb_hip_solver_solve_direct_tier_multi(lsb_hip_solver *s, unsigned nrhs, const double *B, size_t ldb,
+                                           double *X, size_t ldx, struct lsb_hip_result *res);   /* host buffers */
+/* Z_c = P^T L^-T L^-1 P R_c once, un-gated: precond_dev's application on a block */
+int lsb_hip_solver_direct_tier_apply_multi_dev(lsb_hip_solver *s, unsigned nrhs, const double *d_R, size_t ldr,
+                                               double *d_Z, size_t ldz);
+/* bytes one round of a block of width kp(nrhs) streams.  A tiered factor: fixed + kp per_column with fixed = 16 per
+ * entry of the W_tt, 24 per coupling entry and 32 per row (first / woff twice, the offsets of C and C^T), per_column =
+ * 72 per row (nine passes over P V, Y, Z and X); at nrhs = 1 lsb_hip_solver_direct_info's figure.  A single skyline:
+ * lsb_hip_solver_direct_multi_round_bytes.  0 for any other solver or nrhs == 0 */
+unsigned long long lsb_hip_solver_direct_tier_multi_round_bytes(const lsb_hip_solver *s, unsigned nrhs);
 
 /* AMG as the solver on blocks of right-hand sides (hip_rich_m.hip, hip_rich_m_drv.c; the fp32 cycle on blocks:
  * hip_amg_f32_m.hip): the stationary V-cycle iteration of LSB_KRYLOV_RICHARDSON -- x = 0, r = b; per cycle z = M^-1 r,

@@ -336,6 +336,11 @@ SIGNATURES = {
     "lsb_hip_solver_solve_direct_multi": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_direct_apply_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
     "lsb_hip_solver_direct_multi_round_bytes": (C.c_ulonglong, [_vp, _u]),
+    "lsb_hip_solver_solve_direct_tier_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t,
+                                                        C.POINTER(Result)]),
+    "lsb_hip_solver_solve_direct_tier_multi": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
+    "lsb_hip_solver_direct_tier_apply_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "lsb_hip_solver_direct_tier_multi_round_bytes": (C.c_ulonglong, [_vp, _u]),
     "lsb_hip_solver_amg_solve_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_amg_solve_multi": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(Result)]),
     "lsb_hip_solver_amg_cycle_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),

@@ -684,6 +684,48 @@ class Solver:
         any other solver."""
         return int(L.load().lsb_hip_solver_direct_multi_round_bytes(self._h, nrhs))
 
+    def solve_direct_tier_multi_dev(self, d_B, d_X):
+        """solve_direct_multi_dev on every direct solver, one with a tiered factor (create_direct) included: the
+        tiers' launches run on the block, every entry of the factor and of its coupling loaded once per product for
+        all columns.  A column has the bits of solve_dev on that column alone on the same solver.  A single skyline is
+        forwarded to solve_direct_multi_dev.  Any solver that is not direct raises."""
+        pb, k, ldb = self._block(d_B, "solve_direct_tier_multi_dev")
+        px, kx, ldx = self._block(d_X, "solve_direct_tier_multi_dev")
+        if k != kx:
+            raise ValueError("solve_direct_tier_multi_dev: B and X hold different numbers of columns")
+        res = (L.Result * max(k, 1))()
+        L.check(L.load().lsb_hip_solver_solve_direct_tier_multi_dev(self._h, k, pb, ldb, px, ldx, res),
+                "solve_direct_tier_multi_dev")
+        return list(res)[:k]
+
+    def solve_direct_tier_multi(self, B):
+        """B: numpy (n_local, nrhs) of any order.  Returns (X of the same shape, [Result, ...])."""
+        B = np.asfortranarray(B, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != self.n_local:
+            raise ValueError("solve_direct_tier_multi: B must be (n_local, nrhs)")
+        k = B.shape[1]
+        X = np.empty((self.n_local, k), np.float64, order="F")
+        res = (L.Result * max(k, 1))()
+        ld = max(self.n_local, 1)
+        L.check(L.load().lsb_hip_solver_solve_direct_tier_multi(self._h, k, B.ctypes.data, ld, X.ctypes.data, ld, res),
+                "solve_direct_tier_multi")
+        return X, list(res)[:k]
+
+    def direct_tier_apply_multi_dev(self, d_R, d_Z):
+        """One application of the factor, tiered or not, to the nrhs columns held as the ROWS of two 2-D device
+        tensors: a column of Z has the bits of precond_dev on that column alone."""
+        pr, k, ldr = self._block(d_R, "direct_tier_apply_multi_dev")
+        pz, kz, ldz = self._block(d_Z, "direct_tier_apply_multi_dev")
+        if k != kz:
+            raise ValueError("direct_tier_apply_multi_dev: R and Z hold different numbers of columns")
+        L.check(L.load().lsb_hip_solver_direct_tier_apply_multi_dev(self._h, k, pr, ldr, pz, ldz),
+                "direct_tier_apply_multi_dev")
+
+    def direct_tier_multi_round_bytes(self, nrhs):
+        """Bytes one round of a block of nrhs right-hand sides streams on a direct solver, tiered or not (see
+        lsbench_hip.h); at nrhs = 1 direct_info's figure; 0 for any other solver."""
+        return int(L.load().lsb_hip_solver_direct_tier_multi_round_bytes(self._h, nrhs))
+
     def amg_solve_multi_dev(self, d_B, d_X):
         """AMG as the solver (KRYLOV_RICHARDSON, PRECOND_AMG) on a block: stationary V-cycle iterations from x0 = 0 for
         the nrhs columns held as the ROWS of two 2-D device tensors, the hierarchy streamed once per cycle for a block

@@ -129,8 +129,8 @@ void direct_deal_rows(const unsigned *first, const unsigned long long *woff, uns
     blk[nblk] = g, bwin[2 * nblk] = wlo, bwin[2 * nblk + 1] = ww, nblk++;
     if (ww <= cap && ww > widest)
       widest = ww;
-    for (unsigned q = 0; lds_m && q < 3; q++) /* ... and of k_dir_rows_m at 2, 4, 8 columns: ww kp doubles within the same cap */
-      if (ww <= DIR_LDS_CAP / (2u << q) && ww > lds_m[q])
+    for (unsigned q = 0; lds_m && q < 3; q++) /* ... and of the block kernels at 2, 4, 8 columns: ww kp doubles within the same cap */
+      if (ww <= cap / (2u << q) && ww > lds_m[q])
         lds_m[q] = ww;
     g = g1;
   }

@@ -30,15 +30,6 @@
 
 typedef unsigned long long dir_u64;
 
-// rounds the running columns have completed (0: round 1 is next)
-template <int KP> __device__ __forceinline__ int dirm_round(const lsb_mrhs_state *__restrict__ st) {
-  int it = 0;
-#pragma unroll
-  for (int c = KP - 1; c >= 0; c--)
-    it = st->c[c].status == LSB_STATUS_RUNNING ? st->c[c].iters : it;
-  return it;
-}
-
 // not gated: the state still holds the previous block's.  Columns >= kp are no columns: never running
 __global__ void k_dir_init_state_m(lsb_mrhs_state *__restrict__ st, unsigned kp, double tol, int maxit) {
   if (threadIdx.x != 0 || blockIdx.x != 0)

@@ -26,6 +26,11 @@
  *
  * Every solver that is not a direct solver answers 2, as the direct solver does from solve_multi, solve_block, spmm_dev
  * and precond_multi_dev.
+ *
+ * A tiered factor (hip_direct_t_drv.c) is not served by these three entry points, which answer 2 on it, but by
+ * lsb_hip_solver_solve_direct_tier_multi[_dev] and _direct_tier_apply_multi_dev below, which serve every direct solver
+ * (a single skyline through the entry points above).  Everything here is shared: the work area holds a fifth block there
+ * (Z; Y is p), and the products of a round are direct_tier_enqueue_m's 4 m - 2 launches instead of two.
  */
 static struct dirm_work *dirm_setup(lsb_hip_solver *sv, unsigned kp) {
   struct dirm_work *w = &sv->dir->m[kp == 2 ? 0 : kp == 4 ? 1 : 2];
@@ -33,10 +38,11 @@ static struct dirm_work *dirm_setup(lsb_hip_solver *sv, unsigned kp) {
     return w;
   if (!sv->mr_hst) /* (mrhs_free's) */
     LSB_CHK_HIP(hipHostMalloc((void **)&sv->mr_hst, 2 * sizeof(struct lsb_mrhs_state), 0));
-  /* behind the four blocks: the records of the residual launch (r.r, b.b per column), then the state */
+  /* behind the blocks: the records of the residual launch (r.r, b.b per column), then the state */
   const size_t recb = (size_t)LSB_MAX_PARTIALS * 2 * kp * sizeof(double);
   const size_t stb = (sizeof(struct lsb_mrhs_state) + 255) & ~(size_t)255;
-  char *behind = block_work_slab(sv, &w->blk, kp, 4, recb + stb); /* b, x, r and p = T */
+  /* b, x, r and p = T; a tiered factor: p = Y and q = Z */
+  char *behind = block_work_slab(sv, &w->blk, kp, sv->dir->tier ? 5 : 4, recb + stb);
   w->rec = (double *)behind;
   w->st = (struct lsb_mrhs_state *)(behind + recb);
   return w;
@@ -61,6 +67,17 @@ unsigned long long lsb_hip_solver_direct_multi_round_bytes(const lsb_hip_solver 
   return 16ull * d->entries + (24ull + 32ull * kp) * d->k.n;
 }
 
+/* X (+)= (the factor's application to B or R): st == NULL once, un-gated, from B */
+static void dirm_products(lsb_hip_solver *sv, const struct block_work *k, const struct lsb_mrhs_state *st) {
+  const struct direct_dev *d = sv->dir;
+  if (d->tier) {
+    direct_tier_enqueue_m(sv, k, st);
+    return;
+  }
+  lsb_k_dir_rows_m(k->kp, &d->k, dirm_lds(sv, k->kp), k->b, st ? k->r : k->b, k->p, st, g_stream);
+  lsb_k_dir_cols_m(k->kp, &d->k, k->p, k->x, st, g_stream);
+}
+
 /* what block_enqueue runs for run_loop */
 struct dirm_enq {
   lsb_hip_solver *sv;
@@ -70,13 +87,11 @@ struct dirm_enq {
 static void dirm_enqueue_rounds(void *ctx, int rounds) {
   const struct dirm_enq *e = ctx;
   const struct shard *s = &e->sv->sh[0];
-  const struct direct_dev *d = e->sv->dir;
   struct dirm_work *w = e->w;
   const struct block_work *k = &w->blk;
   const int no_resid = !(e->sv->o.tol > 0.0) && e->sv->o.maxit <= 1; /* the reference's protocol: two launches */
   for (int i = 0; i < rounds; i++) {
-    lsb_k_dir_rows_m(k->kp, &d->k, dirm_lds(e->sv, k->kp), k->b, k->r, k->p, w->st, g_stream);
-    lsb_k_dir_cols_m(k->kp, &d->k, k->p, k->x, w->st, g_stream);
+    dirm_products(e->sv, k, w->st);
     if (!no_resid)
       lsb_k_dir_resid_m(k->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->lanes, k->b, k->x, k->r, w->rec,
                         &w->nrec, w->st, g_stream);
@@ -129,12 +144,9 @@ static void dirm_block(lsb_hip_solver *sv, unsigned nb, const double *d_B, size_
   }
 }
 
-int lsb_hip_solver_solve_direct_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
-                                          size_t ldx, struct lsb_hip_result *res) {
-  if (!lsb_initialized)
-    return 1;
-  if (block_args_bad(sv, nrhs, 0, d_B, ldb, d_X, ldx) || !sv->dir || sv->dir->tier)
-    return 2;
+/* the arguments are checked and sv is a direct solver, tiered or not */
+static int dirm_solve_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X, size_t ldx,
+                          struct lsb_hip_result *res) {
   if (nrhs == 1)
     return lsb_hip_solver_solve_dev(sv, d_B, d_X, res);
   struct lsb_hip_result *tmp = res ? res : lsb_calloc(struct lsb_hip_result, nrhs);
@@ -149,6 +161,15 @@ int lsb_hip_solver_solve_direct_multi_dev(lsb_hip_solver *sv, unsigned nrhs, con
   return 0;
 }
 
+int lsb_hip_solver_solve_direct_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb, double *d_X,
+                                          size_t ldx, struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, 0, d_B, ldb, d_X, ldx) || !sv->dir || sv->dir->tier)
+    return 2;
+  return dirm_solve_dev(sv, nrhs, d_B, ldb, d_X, ldx, res);
+}
+
 int lsb_hip_solver_solve_direct_multi(lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X,
                                       size_t ldx, struct lsb_hip_result *res) {
   if (!lsb_initialized)
@@ -159,12 +180,7 @@ int lsb_hip_solver_solve_direct_multi(lsb_hip_solver *sv, unsigned nrhs, const d
 }
 
 /* Z_c = P^T W^T W P R_c once, un-gated: direct_apply_dev on a block, through the same pack / unpack */
-int lsb_hip_solver_direct_apply_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_R, size_t ldr, double *d_Z,
-                                          size_t ldz) {
-  if (!lsb_initialized)
-    return 1;
-  if (block_args_bad(sv, nrhs, 0, d_R, ldr, d_Z, ldz) || !sv->dir || sv->dir->tier)
-    return 2;
+static int dirm_apply_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_R, size_t ldr, double *d_Z, size_t ldz) {
   if (nrhs == 1)
     return lsb_hip_solver_precond_dev(sv, d_R, d_Z);
   const unsigned n = sv->sh[0].n;
@@ -173,10 +189,56 @@ int lsb_hip_solver_direct_apply_multi_dev(lsb_hip_solver *sv, unsigned nrhs, con
     struct dirm_work *w = dirm_setup(sv, block_width(nb));
     const struct block_work *k = &w->blk;
     lsb_k_mrhs_pack(n, k->kp, nb, NULL, d_R + (size_t)c0 * ldr, ldr, k->b, g_stream);
-    lsb_k_dir_rows_m(k->kp, &sv->dir->k, dirm_lds(sv, k->kp), k->b, k->b, k->p, NULL, g_stream);
-    lsb_k_dir_cols_m(k->kp, &sv->dir->k, k->p, k->x, NULL, g_stream);
+    dirm_products(sv, k, NULL);
     lsb_k_mrhs_unpack(n, k->kp, nb, NULL, k->x, d_Z + (size_t)c0 * ldz, ldz, g_stream);
   }
   drain_stream(sv, "lsb_hip_solver_direct_apply_multi_dev");
   return 0;
+}
+
+int lsb_hip_solver_direct_apply_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_R, size_t ldr, double *d_Z,
+                                          size_t ldz) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, 0, d_R, ldr, d_Z, ldz) || !sv->dir || sv->dir->tier)
+    return 2;
+  return dirm_apply_dev(sv, nrhs, d_R, ldr, d_Z, ldz);
+}
+
+/* ---- every direct solver, a tiered one included ----------------------------------------------------------------- */
+int lsb_hip_solver_solve_direct_tier_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_B, size_t ldb,
+                                               double *d_X, size_t ldx, struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, 0, d_B, ldb, d_X, ldx) || !sv->dir)
+    return 2;
+  return dirm_solve_dev(sv, nrhs, d_B, ldb, d_X, ldx, res);
+}
+
+int lsb_hip_solver_solve_direct_tier_multi(lsb_hip_solver *sv, unsigned nrhs, const double *B, size_t ldb, double *X,
+                                           size_t ldx, struct lsb_hip_result *res) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, 0, B, ldb, X, ldx) || !sv->dir)
+    return 2;
+  return block_solve_host(lsb_hip_solver_solve_direct_tier_multi_dev, 0, sv, nrhs, B, ldb, X, ldx, res);
+}
+
+int lsb_hip_solver_direct_tier_apply_multi_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_R, size_t ldr,
+                                               double *d_Z, size_t ldz) {
+  if (!lsb_initialized)
+    return 1;
+  if (block_args_bad(sv, nrhs, 0, d_R, ldr, d_Z, ldz) || !sv->dir)
+    return 2;
+  return dirm_apply_dev(sv, nrhs, d_R, ldr, d_Z, ldz);
+}
+
+/* a single skyline: lsb_hip_solver_direct_multi_round_bytes; a tiered factor: fixed + kp per_column, derived above
+ * direct_tier_multi_round_bytes */
+unsigned long long lsb_hip_solver_direct_tier_multi_round_bytes(const lsb_hip_solver *sv, unsigned nrhs) {
+  if (!sv || !sv->dir || nrhs == 0)
+    return 0;
+  if (!sv->dir->tier)
+    return lsb_hip_solver_direct_multi_round_bytes(sv, nrhs);
+  return direct_tier_multi_round_bytes(sv, nrhs == 1 ? 1u : block_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs));
 }

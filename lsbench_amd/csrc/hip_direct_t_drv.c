@@ -15,7 +15,9 @@
  * (lsb_csr_tiered_count; tiers = 0 takes the fewest that fit) and factorised on the host before anything is
  * allocated on the device.  tiers = 1 is lsb_hip_solver_create itself.  The solves, the warm starts, the sequences
  * and opts.verify are hip_direct_drv.c's: a round there calls direct_tier_enqueue instead of its two launches.
- * Blocks of right-hand sides are refused on a tiered solver (the entry points answer 2).
+ * Blocks of right-hand sides: lsb_hip_solver_solve_direct_multi[_dev] and its companions keep answering 2 on a tiered
+ * solver; lsb_hip_solver_solve_direct_tier_multi[_dev] (hip_direct_m_drv.c) serve it, a round of theirs calls
+ * direct_tier_enqueue_m, the same launches in their block form (hip_direct_tm.hip).
  *
  * Two vectors of its own: y (direct_dev.d_t) and z, in the tier-major numbering.
  */
@@ -123,7 +125,7 @@ void direct_tier_upload(lsb_hip_solver *sv, struct lsb_tierinv *T, unsigned heig
     struct lsb_dirt_tier *k = &q->k.t[t];
     k->lo = T->lo[t], k->hi = T->lo[t + 1], k->blk0 = nblk, k->tbase = tbase[t];
     direct_deal_rows(T->first, T->woff, k->lo, k->hi, direct_block_target(entries), cap, grp, &ngrp, blk, bwin, &nblk,
-                     &k->lds_doubles, NULL);
+                     &k->lds_doubles, k->lds_m);
     k->nblk = nblk - k->blk0;
     if (k->lds_doubles > widest_all)
       widest_all = k->lds_doubles;
@@ -205,6 +207,35 @@ void direct_tier_enqueue(lsb_hip_solver *sv, const double *d_b, const double *d_
 unsigned long long direct_tier_round_bytes(const lsb_hip_solver *sv) {
   const struct direct_dev *d = sv->dir;
   return 16ull * d->entries + 24ull * d->tier->coupling + (24ull + 32ull + 8ull + 40ull) * d->k.n;
+}
+
+/* the same launches on a block of k->kp interleaved columns: Y = k->p, Z = k->q */
+void direct_tier_enqueue_m(lsb_hip_solver *sv, const struct block_work *k, const struct lsb_mrhs_state *st) {
+  const struct lsb_dirt_dev *d = &sv->dir->tier->k;
+  double *y = k->p, *z = k->q;
+  lsb_k_dirt_rows_m(k->kp, d, 0, k->b, k->r, NULL, y, st, g_stream);
+  for (unsigned t = 1; t < d->ntier; t++) {
+    lsb_k_dirt_fwd_m(k->kp, d, t, k->b, k->r, y, z, st, g_stream);
+    lsb_k_dirt_rows_m(k->kp, d, t, NULL, NULL, z, y, st, g_stream);
+  }
+  for (unsigned t = d->ntier; t-- > 0;) {
+    lsb_k_dirt_cols_m(k->kp, d, t, y, z, k->x, st, g_stream);
+    if (t > 0)
+      lsb_k_dirt_bwd_m(k->kp, d, t, z, y, st, g_stream);
+  }
+}
+
+/* A round on a block of width kp: fixed + kp per_column.
+ *   fixed      what is loaded once for all columns: the W_tt twice (16 per entry) with first / woff per row twice
+ *              (24 n), C and C^T once each at 12 B an entry (24 per coupling entry), their offsets (8 n)
+ *   per_column the block vectors, 8 B per row and pass, every row in one tier: k_dirt_fwd_m reads P V and writes Z
+ *              (tier 0: k_dirt_rows_m reads P V), k_dirt_rows_m reads Z and writes Y, k_dirt_cols_m reads Y and writes
+ *              Z and X, k_dirt_bwd_m reads and writes Y -- nine passes, 72 n.  The gathers of Y by C and of Z by C^T
+ *              are left out, as they are at one column
+ * kp = 1 is direct_tier_round_bytes: 32 n + 72 n = 104 n. */
+unsigned long long direct_tier_multi_round_bytes(const lsb_hip_solver *sv, unsigned kp) {
+  const struct direct_dev *d = sv->dir;
+  return 16ull * d->entries + 24ull * d->tier->coupling + (24ull + 8ull) * d->k.n + 72ull * kp * d->k.n;
 }
 
 int lsb_hip_solver_direct_tier_info(const lsb_hip_solver *sv, unsigned *ntiers, unsigned long long *w_entries,

@@ -1,5 +1,5 @@
 // What the kernel files of several right-hand sides (hip_mrhs.hip, hip_mrhs_x0.hip, hip_mrhs_fsai.hip, hip_mrhs_amg.hip,
-// hip_amg_cheb.hip, hip_amg_f32_m.hip, hip_rich_m.hip, hip_bcg.hip, hip_bcg_m.hip) share: the 16-byte pair of the interleaved blocks and its store gated
+// hip_amg_cheb.hip, hip_amg_f32_m.hip, hip_rich_m.hip, hip_bcg.hip, hip_bcg_m.hip, hip_direct_m.hip, hip_direct_tm.hip) share: the 16-byte pair of the interleaved blocks and its store gated
 // per column, the fixed-order reductions of their per-column records, the verify round's decision, the row rule of
 // their CSR row kernels (block_row_product), the Gram triangle dealt over a row's lanes, and the launchers' dispatch
 // on the batch width and on the lanes per row.  Included by those files only, after hip_kcommon.h.
@@ -240,6 +240,19 @@ __device__ __forceinline__ void tri_dealt_store(double (&g)[NT][NA], double *sre
   __syncthreads();
   if (tid < W)
     dst[tid] = (sred[tid] + sred[W + tid]) + (sred[2 * W + tid] + sred[3 * W + tid]);
+}
+
+// --------------------------------------------------------------------------
+// What the two kernel files of the direct solver on blocks (hip_direct_m.hip, hip_direct_tm.hip) share: all running
+// columns of a block have run the same number of rounds, so which round it is comes from any of them.
+// --------------------------------------------------------------------------
+// rounds the running columns have completed (0: round 1 is next)
+template <int KP> __device__ __forceinline__ int dirm_round(const lsb_mrhs_state *__restrict__ st) {
+  int it = 0;
+#pragma unroll
+  for (int c = KP - 1; c >= 0; c--)
+    it = st->c[c].status == LSB_STATUS_RUNNING ? st->c[c].iters : it;
+  return it;
 }
 
 // --------------------------------------------------------------------------

@@ -389,8 +389,9 @@ struct lsb_hip_solver {
     struct graph_cache graphs;
     const double *graph_b;
     unsigned lds_m[3];
-    /* a tiered factor (hip_direct_t_drv.c), NULL on a single skyline: k is then unused but for k.n, d_t is y, and
-     * the blocks of right-hand sides are refused */
+    /* a tiered factor (hip_direct_t_drv.c), NULL on a single skyline: k is then unused but for k.n, d_t is y.  Blocks
+     * of right-hand sides on it have entry points of their own (lsb_hip_solver_solve_direct_tier_multi[_dev]): the
+     * work area m[] of a width then holds a fifth block, Z (blk.q), and Y is blk.p */
     struct direct_tier_dev {
       struct lsb_dirt_dev k;
       void *mem[17];
@@ -729,7 +730,8 @@ LSB_INTERNAL void lsb_k_dir_resid(unsigned n, const int *offs, const int *cols, 
 LSB_INTERNAL void lsb_k_dir_step(struct lsb_pcg_state *st, const double *records, unsigned nrecords, void *stream);
 /* the dealing of the skyline rows r0 .. r1 - 1 to k_dir_rows, appended to grp (at *ngrp), blk and bwin (at *nblk):
  * groups of consecutive rows with one lane count, workgroups of about `target` entries; *widest: the widest window
- * within `cap` doubles (0 or more than DIR_LDS_CAP: DIR_LDS_CAP), lds_m (may be NULL): the same per width of hip_direct_m.hip.  The caller closes blk[*nblk] */
+ * within `cap` doubles (0 or more than DIR_LDS_CAP: DIR_LDS_CAP), lds_m (may be NULL): the widest of at most cap / kp
+ * rows per width kp = 2, 4, 8 of the block kernels.  The caller closes blk[*nblk] */
 LSB_INTERNAL void direct_deal_rows(const unsigned *first, const unsigned long long *woff, unsigned r0, unsigned r1,
                                    unsigned long long target, unsigned cap, unsigned *grp, unsigned *ngrp,
                                    unsigned *blk, unsigned *bwin, unsigned *nblk, unsigned *widest, unsigned *lds_m);
@@ -752,6 +754,23 @@ LSB_INTERNAL void lsb_k_dirt_fwd(const struct lsb_dirt_dev *d, unsigned t, const
                                  const double *y, double *z, const struct lsb_pcg_state *st, int src, void *stream);
 LSB_INTERNAL void lsb_k_dirt_bwd(const struct lsb_dirt_dev *d, unsigned t, const double *z, double *y,
                                  const struct lsb_pcg_state *st, void *stream);
+/* the same on a block of kp = 2, 4 or 8 interleaved right-hand sides (hip_direct_tm.hip): B, R, X of the work area in
+ * the caller's numbering, Y = k->p and Z = k->q in the tier-major one; st: the gate, NULL for one un-gated application
+ * that reads k->b and stores k->x.  direct_tier_multi_round_bytes: what a round of that width streams (kp = 1:
+ * direct_tier_round_bytes) */
+LSB_INTERNAL void direct_tier_enqueue_m(lsb_hip_solver *sv, const struct block_work *k,
+                                        const struct lsb_mrhs_state *st);
+LSB_INTERNAL unsigned long long direct_tier_multi_round_bytes(const lsb_hip_solver *sv, unsigned kp);
+LSB_INTERNAL void lsb_k_dirt_rows_m(unsigned kp, const struct lsb_dirt_dev *d, unsigned t, const double *b,
+                                    const double *r, const double *v, double *y, const struct lsb_mrhs_state *st,
+                                    void *stream);
+LSB_INTERNAL void lsb_k_dirt_cols_m(unsigned kp, const struct lsb_dirt_dev *d, unsigned t, const double *y, double *z,
+                                    double *x, const struct lsb_mrhs_state *st, void *stream);
+LSB_INTERNAL void lsb_k_dirt_fwd_m(unsigned kp, const struct lsb_dirt_dev *d, unsigned t, const double *b,
+                                   const double *r, const double *y, double *z, const struct lsb_mrhs_state *st,
+                                   void *stream);
+LSB_INTERNAL void lsb_k_dirt_bwd_m(unsigned kp, const struct lsb_dirt_dev *d, unsigned t, const double *z, double *y,
+                                   const struct lsb_mrhs_state *st, void *stream);
 /* hip_direct_m_drv.c: the direct solver on blocks of right-hand sides, and the launchers of hip_direct_m.hip (kp: 2, 4
  * or 8; interleaved blocks; st: the gate, NULL in rows_m / cols_m for one un-gated application that reads b and stores) */
 LSB_INTERNAL void direct_multi_free(lsb_hip_solver *sv); /* the work areas of every width */

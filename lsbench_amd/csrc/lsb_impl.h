@@ -494,9 +494,10 @@ struct lsb_dir_dev {
  * struct lsb_tierinv on the device.  grp / blk / bwin as in struct lsb_dir_dev, dealt tier by tier: tier t's
  * workgroups are blk0 .. blk0 + nblk - 1 and stage lds_doubles at the most.  cgrp / tgrp: the rows of C and of C^T in
  * groups of the same shape (first row, rows << 8 | lanes per row), tier t's at cg0 .. cg1 - 1 and tg0 .. tg1 - 1;
- * tbase: where tier t's offsets begin in toffs. */
+ * tbase: where tier t's offsets begin in toffs.  lds_m: the widest window, in rows, that the tier's launch on a block
+ * of 2, 4, 8 right-hand sides stages (hip_direct_tm.hip). */
 struct lsb_dirt_tier {
-  unsigned lo, hi, blk0, nblk, lds_doubles, cg0, cg1, tg0, tg1, tbase;
+  unsigned lo, hi, blk0, nblk, lds_doubles, cg0, cg1, tg0, tg1, tbase, lds_m[3];
 };
 struct lsb_dirt_dev {
   unsigned n, ntier;
