@@ -927,16 +927,18 @@ unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *s);
 int lsb_hip_solver_direct_info(const lsb_hip_solver *s, unsigned long long *entries, unsigned *height,
                                unsigned long long *bytes_per_round);
 /* A direct solver (o->krylov must be LSB_KRYLOV_DIRECT; o = NULL: the backend's current options) whose inverse factor
- * is kept in tiers (struct lsb_tierinv; hip_direct_t.hip, hip_direct_t_drv.c): for operators whose single skyline is
+ * is kept in tiers (struct lsb_tierinv; hip_direct_t.hip, hip_direct_drv.c): for operators whose single skyline is
  * over LSB_DIRECT_MAX_ENTRIES.  tiers = 1 is lsb_hip_solver_create itself; 2 .. LSB_DIRECT_MAX_TIERS asks for that
  * many (the factor may have fewer: tiers nobody is in are dropped); 0 takes the fewest that fit the budget
- * w_entries + 3 coupling_entries <= LSB_DIRECT_MAX_ENTRIES by the symbolic count.  NULL for another krylov or tiers
+ * w_entries + 3 coupling_entries <= LSB_DIRECT_MAX_ENTRIES by the symbolic count -- where that is one, the solver IS
+ * lsb_hip_solver_create's.  A factor of one tier is the single skyline however it was asked for: two launches, 56
+ * bytes per row and round, served by the block entry points of the single skyline.  NULL for another krylov or tiers
  * out of range; what lsb_hip_solver_create refuses for a direct solver is refused in the same way, and so is a factor
  * over the budget in the tiers asked for.  A round is 4 m - 2 launches for m tiers instead of 2, then the residual
  * and the stop test as before.  Every solve entry point of a direct solver works on it (solve[_dev], solve_x0[_dev],
- * solve_seq[_dev], precond_dev, opts.verify) but the blocks of right-hand sides, which answer 2: blocks on a tiered
- * factor have entry points of their own, lsb_hip_solver_solve_direct_tier_multi[_dev] below.
- * On such a solver lsb_hip_solver_direct_info reports the entries of the W_tt, the height of the whole tree, and as
+ * solve_seq[_dev], precond_dev, opts.verify) but, on more than one tier, the blocks of right-hand sides, which answer
+ * 2: blocks on a tiered factor have entry points of their own, lsb_hip_solver_solve_direct_tier_multi[_dev] below.
+ * On a solver of more than one tier lsb_hip_solver_direct_info reports the entries of the W_tt, the height of the whole tree, and as
  * bytes per round 16 per entry of the W_tt, 24 per coupling entry (C and C^T once each: a value and a 32-bit column),
  * and 104 per row (first / woff twice, the offsets of C and C^T, P r, y, z and x). */
 lsb_hip_solver *lsb_hip_solver_create_direct(const struct csr *A, const struct lsb_hip_opts *o, int tiers);
@@ -1057,8 +1059,8 @@ unsigned long long lsb_hip_solver_direct_multi_round_bytes(const lsb_hip_solver 
 /* The same on every direct solver, one with a tiered factor (lsb_hip_solver_create_direct) included: there a round on
  * a block is the 4 m - 2 launches of the tiers in their block form (hip_direct_tm.hip), every entry of the W_tt, of C
  * and of C^T loaded once per product for all columns, then the residual and the stop test of the blocks above.  The
- * three entry points above keep answering 2 on a tiered solver; these forward to them on a single skyline (tiers = 1
- * included).  Arguments, layout, block cutting, return values, results and the stop rules are theirs, and so is the
+ * three entry points above keep answering 2 on a solver of more than one tier; on a single skyline (one tier, however
+ * it was created) these are the three above.  Arguments, layout, block cutting, return values, results and the stop rules are theirs, and so is the
  * contract: a column of a block has the bits of that column solved alone by lsb_hip_solver_solve_dev (applied alone by
  * lsb_hip_solver_precond_dev) on the same solver; nrhs == 1 is forwarded to those.  1 when the backend is not
  * initialised; 2 for bad arguments and for a solver that is not direct: nothing is written.  The work area of a width

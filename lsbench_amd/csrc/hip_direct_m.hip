@@ -1,18 +1,17 @@
-// The direct solver on blocks of right-hand sides (lsb_hip_solver_solve_direct_multi[_dev], _direct_apply_multi_dev;
-// the host side: hip_direct_m_drv.c): the rounds of hip_direct.hip on KP = 2, 4 or 8 columns at once, every entry of W
-// loaded ONCE per product for all of them.
+// The direct solver on blocks of right-hand sides (lsb_hip_solver_solve_direct_multi[_dev] and its companions; the
+// host side: hip_direct_m_drv.c): the rounds of hip_direct.hip on KP = 2, 4 or 8 columns at once.  This file holds what
+// every round of a block shares, whatever the number of tiers; the products are hip_direct_tm.hip's.
 //
 //   state                                           k_dir_init_state_m (one thread)
-//   round k:  T = W (P V)       V = B in round 1     k_dir_rows_m<KP>
-//             X (+)= P^T W^T T  stored in round 1    k_dir_cols_m<KP>
+//   round k:  X (+)= P^T L^-T L^-1 P V               the products: hip_direct_tm.hip (V = B, X stored in round 1)
 //             R = B - S X ; records of r.r, b.b      k_dir_resid_m<L, KP>   (tol = 0: not in the last round)
 //             iters = k ; the stop test per column   k_dir_step_m<KP>       (one workgroup)
 //
 // The rule of every block here: a column of a block has the bits of the same column solved alone.  So each kernel
-// keeps the summation order of its single-column twin per column -- the same lanes per row, the same fma chain, the
-// same butterfly, the same order of the partial sums -- and only shares what has no rounding: the loads of W, of
-// first / woff, of the CSR.  That rules out MFMA (v_mfma_f64_* sums in an order of its own); at <= 8 columns the
-// products are nowhere near the fp64 vector rate anyway.
+// keeps the summation order of the single-column kernel per column -- the same lanes per row, the same fma chain, the
+// same butterfly, the same order of the partial sums -- and only shares what has no rounding: the loads of the
+// factor, of first / woff, of the CSR.  That rules out MFMA (v_mfma_f64_* sums in an order of its own); at <= 8
+// columns the products are nowhere near the fp64 vector rate anyway.
 //
 // Block vectors are interleaved as in hip_mrhs.hip: element (i, c) at i KP + c, read and written as 16-byte pairs, in
 // the caller's numbering (perm is applied inside the kernels, as by the single-column ones).  The state is a
@@ -25,10 +24,6 @@
 #include "hip_mrhs_k.h"
 
 #define DIR_HIDDEN __attribute__((visibility("hidden")))
-#define DIR_COLS 64  // columns per workgroup of k_dir_cols_m: one wavefront's width, as in k_dir_cols
-#define DIR_CWG 1024 // ... and its threads: sixteen wavefronts share the rows that reach the window
-
-typedef unsigned long long dir_u64;
 
 // not gated: the state still holds the previous block's.  Columns >= kp are no columns: never running
 __global__ void k_dir_init_state_m(lsb_mrhs_state *__restrict__ st, unsigned kp, double tol, int maxit) {
@@ -48,170 +43,6 @@ __global__ void k_dir_init_state_m(lsb_mrhs_state *__restrict__ st, unsigned kp,
   st->tol = tol;
   st->running = maxit > 0;
   st->nspmm = 0; // rounds that did work: what the host's hint is taken from
-}
-
-// T = W (P V).  k_dir_rows' groups, workgroups and windows (the dealing does not depend on the width) and its lane
-// rule per column: L lanes per row from the row's length alone, lane l takes entries l, l + L, ... with fma in ascending
-// order into KP accumulators from ONE load of w[e], the lanes folded by the xor butterfly.  A window of at most cap
-// rows of P V is staged in LDS (ww KP doubles), a wider one gathered from global memory: the same numbers either way
-template <int KP>
-__global__ __launch_bounds__(WG) void k_dir_rows_m(const double *__restrict__ vals, const dir_u64 *__restrict__ woff,
-                                                   const unsigned *__restrict__ first,
-                                                   const unsigned *__restrict__ perm, const unsigned *__restrict__ grp,
-                                                   const unsigned *__restrict__ blk, const unsigned *__restrict__ bwin,
-                                                   unsigned cap, const double *__restrict__ b,
-                                                   const double *__restrict__ r, double *__restrict__ t,
-                                                   const lsb_mrhs_state *__restrict__ st) {
-  constexpr int H = KP / 2;
-  extern __shared__ __attribute__((aligned(16))) double win_m[];
-  if (st && !st->running)
-    return;
-  const d2v *__restrict__ v2 = (const d2v *)(!st || dirm_round<KP>(st) == 0 ? b : r);
-  d2v *win2 = (d2v *)win_m;
-  const unsigned g0 = blk[blockIdx.x], g1 = blk[blockIdx.x + 1];
-  const unsigned wlo = bwin[2 * blockIdx.x], ww = bwin[2 * blockIdx.x + 1];
-  const bool staged = ww <= cap;
-  if (staged) {
-    for (unsigned i = threadIdx.x; i < ww * H; i += WG)
-      win2[i] = v2[(size_t)perm[wlo + i / H] * H + i % H];
-    __syncthreads();
-  }
-  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (unsigned g = g0 + wave; g < g1; g += WG / 64) {
-    const unsigned row0 = grp[2 * g], meta = grp[2 * g + 1];
-    const unsigned L = meta & 0xffu, nr = meta >> 8; // L: a power of two, 1 .. 64; nr <= 64 / L rows
-    const unsigned sub = lane / L, l = lane & (L - 1);
-    const bool mine = sub < nr;
-    double acc[KP];
-#pragma unroll
-    for (int c = 0; c < KP; c++)
-      acc[c] = 0.0;
-    if (mine) {
-      const unsigned k = row0 + sub, f = first[k], len = k - f + 1;
-      const double *__restrict__ w = vals + woff[k];
-      if (staged) {
-        const d2v *a = win2 + (size_t)(f - wlo) * H;
-#pragma unroll 2
-        for (unsigned e = l; e < len; e += L) {
-          const double we = w[e];
-#pragma unroll
-          for (int h = 0; h < H; h++) {
-            const d2v p = a[(size_t)e * H + h];
-            acc[2 * h] = fma(we, p.x, acc[2 * h]), acc[2 * h + 1] = fma(we, p.y, acc[2 * h + 1]);
-          }
-        }
-      } else {
-        for (unsigned e = l; e < len; e += L) {
-          const double we = w[e];
-          const d2v *a = v2 + (size_t)perm[f + e] * H; // one run of 8 KP bytes per entry
-#pragma unroll
-          for (int h = 0; h < H; h++) {
-            const d2v p = a[h];
-            acc[2 * h] = fma(we, p.x, acc[2 * h]), acc[2 * h + 1] = fma(we, p.y, acc[2 * h + 1]);
-          }
-        }
-      }
-    }
-    for (unsigned m = 32; m >= 1; m >>= 1)
-      if (m < L) { // (the same L in the whole wavefront)
-#pragma unroll
-        for (int c = 0; c < KP; c++)
-          acc[c] += __shfl_xor(acc[c], m, 64);
-      }
-    if (mine && l == 0)
-      row_store<KP>(t, row0 + sub, acc);
-  }
-}
-
-// X (+)= P^T W^T T.  k_dir_cols' shape: 64 columns per workgroup, one lane per column in each of sixteen wavefronts,
-// the window's own rows and then the ancestors of its last column run by run, dealt round-robin to the wavefronts in
-// visiting order; each wavefront adds its own rows in ascending k into KP accumulators per lane -- ONE load of W for
-// KP fma -- and the sixteen partial sums are added in ascending order.  Everything about a row (its first column, its
-// offset, the KP values of t_k) is wave-uniform and fetched by uniform loads.  A masked term is fma(0, 0, acc), both
-// factors masked: it leaves acc's bits alone and keeps a NaN of one row or one column out of the others, so the
-// number of rows in flight (FL) is free.  The store is gated per column: a frozen column is not written
-template <int KP, int FL>
-__global__ __launch_bounds__(DIR_CWG) void k_dir_cols_m(unsigned n, const double *__restrict__ vals,
-                                                        const dir_u64 *__restrict__ woff,
-                                                        const unsigned *__restrict__ first,
-                                                        const unsigned *__restrict__ perm,
-                                                        const unsigned *__restrict__ parent,
-                                                        const unsigned *__restrict__ run_end,
-                                                        const double *__restrict__ t, double *__restrict__ x,
-                                                        const lsb_mrhs_state *__restrict__ st) {
-  constexpr unsigned NW = DIR_CWG / 64;
-  constexpr int H = KP / 2;
-  __shared__ double part[NW][KP][DIR_COLS];
-  if (st && !st->running)
-    return;
-  const bool add = st && dirm_round<KP>(st) > 0;
-  const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const unsigned j0 = blockIdx.x * DIR_COLS, j1 = (j0 + DIR_COLS < n ? j0 + DIR_COLS : n) - 1;
-  const unsigned j = j0 + lane;
-  const bool active = j <= j1;
-  double acc[KP];
-#pragma unroll
-  for (int c = 0; c < KP; c++)
-    acc[c] = 0.0;
-  // this wavefront's rows k0, k0 + NW, ... <= kend, FL at a time: their loads of W are independent of one another
-  // and go out together
-  auto visit = [&](unsigned k0, unsigned kend) {
-    for (unsigned kb = k0; kb <= kend; kb += FL * NW) {
-      double w[FL];
-      unsigned kk[FL];
-      bool in[FL];
-#pragma unroll
-      for (int u = 0; u < FL; u++) {
-        const unsigned k = kb + u * NW;
-        kk[u] = k <= kend ? k : kend; // (past the run: its last row again, not added)
-        const unsigned f = first[kk[u]];
-        in[u] = active && j >= f && j <= kk[u] && k <= kend;
-        w[u] = vals[woff[kk[u]] + (in[u] ? j - f : 0u)]; // (every lane loads: no branch between the loads)
-      }
-#pragma unroll
-      for (int u = 0; u < FL; u++) {
-        const double *__restrict__ tk = t + (size_t)kk[u] * KP;
-        const double wu = in[u] ? w[u] : 0.0;
-#pragma unroll
-        for (int c = 0; c < KP; c++)
-          acc[c] = fma(in[u] ? tk[c] : 0.0, wu, acc[c]);
-      }
-    }
-  };
-  visit(j0 + wave, j1); // the window's own rows
-  unsigned pos = j1 - j0 + 1; // rows visited so far
-  for (unsigned p = parent[j1]; p < n;) { // the ancestors of j1, run by run
-    const unsigned re = run_end[p];
-    visit(p + ((wave + NW - (pos & (NW - 1))) & (NW - 1)), re);
-    pos += re - p + 1;
-    p = parent[re];
-  }
-#pragma unroll
-  for (int c = 0; c < KP; c++)
-    part[wave][c][lane] = acc[c];
-  __syncthreads();
-  if (wave < (unsigned)H && active) { // wavefront h: the pair of columns 2 h, 2 h + 1
-    double z[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      z[q] = part[0][2 * wave + q][lane];
-#pragma unroll
-      for (unsigned w = 1; w < NW; w++)
-        z[q] += part[w][2 * wave + q][lane];
-    }
-    const int a0 = !st || st->c[2 * wave].status == LSB_STATUS_RUNNING;
-    const int a1 = !st || st->c[2 * wave + 1].status == LSB_STATUS_RUNNING;
-    if (a0 | a1) {
-      const size_t i = (size_t)perm[j] * H + wave;
-      double *const xs[1] = {x};
-      d2v val[1] = {d2v{z[0], z[1]}};
-      if (add) {
-        const d2v old = ((const d2v *)x)[i];
-        val[0] = d2v{old.x + z[0], old.y + z[1]};
-      }
-      store_pairs<1>(xs, val, i, a0, a1);
-    }
-  }
 }
 
 // R = B - S X off the plain CSR by k_dir_resid's rule: L lanes per row (the row rule of the blocks is that kernel's:
@@ -304,9 +135,6 @@ __global__ __launch_bounds__(WG) void k_dir_step_m(lsb_mrhs_state *__restrict__ 
   st->running = any;
 }
 
-// rows in flight per wavefront of k_dir_cols_m: fewer at the wider blocks, so that nothing spills
-template <int KP> struct dirm_flight { static constexpr int value = KP == 2 ? 8 : 4; };
-
 template <int KP>
 static void resid_m_launch(unsigned g, unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
                            const double *b, const double *x, double *r, double *records,
@@ -318,23 +146,6 @@ extern "C" {
 
 DIR_HIDDEN void lsb_k_dir_init_state_m(struct lsb_mrhs_state *st, unsigned kp, double tol, int maxit, void *stream) {
   k_dir_init_state_m<<<1, 64, 0, (hipStream_t)stream>>>(st, kp, tol, maxit);
-}
-
-// lds_rows: the widest window the launch stages, in rows (<= DIR_LDS_CAP / kp: the host's)
-DIR_HIDDEN void lsb_k_dir_rows_m(unsigned kp, const struct lsb_dir_dev *d, unsigned lds_rows, const double *b, const double *r, double *t, const struct lsb_mrhs_state *st,
-                                 void *stream) {
-  if (!d->nblk)
-    return;
-  KP_DISPATCH(kp, (k_dir_rows_m<KP><<<d->nblk, WG, (size_t)lds_rows * KP * sizeof(double), (hipStream_t)stream>>>(
-                      d->vals, d->woff, d->first, d->perm, d->grp, d->blk, d->bwin, lds_rows, b, r, t, st)));
-}
-
-DIR_HIDDEN void lsb_k_dir_cols_m(unsigned kp, const struct lsb_dir_dev *d, const double *t, double *x,
-                                 const struct lsb_mrhs_state *st, void *stream) {
-  if (!d->n)
-    return;
-  KP_DISPATCH(kp, (k_dir_cols_m<KP, dirm_flight<KP>::value><<<div_up(d->n, DIR_COLS), DIR_CWG, 0, (hipStream_t)stream>>>(
-                      d->n, d->vals, d->woff, d->first, d->perm, d->parent, d->run_end, t, x, st)));
 }
 
 DIR_HIDDEN void lsb_k_dir_resid_m(unsigned kp, unsigned n, const int *offs, const int *cols, const double *vals,

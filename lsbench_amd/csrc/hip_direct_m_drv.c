@@ -16,7 +16,8 @@
  * is the caller's, the factor's permutation is applied inside the kernels), so a round -- and a captured graph of
  * rounds -- does not depend on the caller's pointers: the graphs of a work area are keyed on the count alone.
  *
- * A round: k_dir_rows_m, k_dir_cols_m, k_dir_resid_m (not where tol = 0 and maxit <= 1), k_dir_step_m.  Every column
+ * A round: the products (direct_tier_enqueue_m: two launches at one tier, 4 m - 2 on m tiers), k_dir_resid_m (not
+ * where tol = 0 and maxit <= 1), k_dir_step_m.  Every column
  * has its own lsb_pcg_state inside the block's lsb_mrhs_state and stops on its own; a stopped column is frozen, the
  * block runs until every column has stopped (`running`, the gate of every launch).  The host side is run_loop on
  * `running`: 2 rounds per poll or opts.check_every, the previous block's count in one go, never more than maxit rounds.
@@ -27,10 +28,9 @@
  * Every solver that is not a direct solver answers 2, as the direct solver does from solve_multi, solve_block, spmm_dev
  * and precond_multi_dev.
  *
- * A tiered factor (hip_direct_t_drv.c) is not served by these three entry points, which answer 2 on it, but by
- * lsb_hip_solver_solve_direct_tier_multi[_dev] and _direct_tier_apply_multi_dev below, which serve every direct solver
- * (a single skyline through the entry points above).  Everything here is shared: the work area holds a fifth block there
- * (Z; Y is p), and the products of a round are direct_tier_enqueue_m's 4 m - 2 launches instead of two.
+ * A tiered factor (direct_tiered: more than one tier) is not served by these three entry points, which answer 2 on it,
+ * but by lsb_hip_solver_solve_direct_tier_multi[_dev] and _direct_tier_apply_multi_dev below, which serve every direct
+ * solver.  Everything here is shared: the work area holds a fifth block there (Z; Y is p).
  */
 static struct dirm_work *dirm_setup(lsb_hip_solver *sv, unsigned kp) {
   struct dirm_work *w = &sv->dir->m[kp == 2 ? 0 : kp == 4 ? 1 : 2];
@@ -42,7 +42,7 @@ static struct dirm_work *dirm_setup(lsb_hip_solver *sv, unsigned kp) {
   const size_t recb = (size_t)LSB_MAX_PARTIALS * 2 * kp * sizeof(double);
   const size_t stb = (sizeof(struct lsb_mrhs_state) + 255) & ~(size_t)255;
   /* b, x, r and p = T; a tiered factor: p = Y and q = Z */
-  char *behind = block_work_slab(sv, &w->blk, kp, sv->dir->tier ? 5 : 4, recb + stb);
+  char *behind = block_work_slab(sv, &w->blk, kp, direct_tiered(sv) ? 5 : 4, recb + stb);
   w->rec = (double *)behind;
   w->st = (struct lsb_mrhs_state *)(behind + recb);
   return w;
@@ -55,27 +55,11 @@ void direct_multi_free(lsb_hip_solver *sv) {
   }
 }
 
-static unsigned dirm_lds(const lsb_hip_solver *sv, unsigned kp) { return sv->dir->lds_m[kp == 2 ? 0 : kp == 4 ? 1 : 2]; }
-
-/* Bytes one round of a block of width kp(nrhs) streams: W twice and first / woff per row twice whatever the width
- * (lsb_hip_solver_direct_info's figure at one column), and per column P V in, T out and in, X out */
+/* Bytes one round of a block of width kp(nrhs) streams (direct_round_bytes); 0 on a tiered solver */
 unsigned long long lsb_hip_solver_direct_multi_round_bytes(const lsb_hip_solver *sv, unsigned nrhs) {
-  if (!sv || !sv->dir || sv->dir->tier || nrhs == 0)
+  if (!sv || !sv->dir || direct_tiered(sv) || nrhs == 0)
     return 0;
-  const struct direct_dev *d = sv->dir;
-  const unsigned kp = nrhs == 1 ? 1u : block_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs);
-  return 16ull * d->entries + (24ull + 32ull * kp) * d->k.n;
-}
-
-/* X (+)= (the factor's application to B or R): st == NULL once, un-gated, from B */
-static void dirm_products(lsb_hip_solver *sv, const struct block_work *k, const struct lsb_mrhs_state *st) {
-  const struct direct_dev *d = sv->dir;
-  if (d->tier) {
-    direct_tier_enqueue_m(sv, k, st);
-    return;
-  }
-  lsb_k_dir_rows_m(k->kp, &d->k, dirm_lds(sv, k->kp), k->b, st ? k->r : k->b, k->p, st, g_stream);
-  lsb_k_dir_cols_m(k->kp, &d->k, k->p, k->x, st, g_stream);
+  return direct_round_bytes(sv, nrhs == 1 ? 1u : block_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs));
 }
 
 /* what block_enqueue runs for run_loop */
@@ -91,7 +75,7 @@ static void dirm_enqueue_rounds(void *ctx, int rounds) {
   const struct block_work *k = &w->blk;
   const int no_resid = !(e->sv->o.tol > 0.0) && e->sv->o.maxit <= 1; /* the reference's protocol: two launches */
   for (int i = 0; i < rounds; i++) {
-    dirm_products(e->sv, k, w->st);
+    direct_tier_enqueue_m(e->sv, k, w->st);
     if (!no_resid)
       lsb_k_dir_resid_m(k->kp, s->n, s->csr.offs, s->csr.cols, s->csr.vals, s->lanes, k->b, k->x, k->r, w->rec,
                         &w->nrec, w->st, g_stream);
@@ -165,7 +149,7 @@ int lsb_hip_solver_solve_direct_multi_dev(lsb_hip_solver *sv, unsigned nrhs, con
                                           size_t ldx, struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, 0, d_B, ldb, d_X, ldx) || !sv->dir || sv->dir->tier)
+  if (block_args_bad(sv, nrhs, 0, d_B, ldb, d_X, ldx) || !sv->dir || direct_tiered(sv))
     return 2;
   return dirm_solve_dev(sv, nrhs, d_B, ldb, d_X, ldx, res);
 }
@@ -174,7 +158,7 @@ int lsb_hip_solver_solve_direct_multi(lsb_hip_solver *sv, unsigned nrhs, const d
                                       size_t ldx, struct lsb_hip_result *res) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, 0, B, ldb, X, ldx) || !sv->dir || sv->dir->tier)
+  if (block_args_bad(sv, nrhs, 0, B, ldb, X, ldx) || !sv->dir || direct_tiered(sv))
     return 2;
   return block_solve_host(lsb_hip_solver_solve_direct_multi_dev, 0, sv, nrhs, B, ldb, X, ldx, res);
 }
@@ -189,7 +173,7 @@ static int dirm_apply_dev(lsb_hip_solver *sv, unsigned nrhs, const double *d_R, 
     struct dirm_work *w = dirm_setup(sv, block_width(nb));
     const struct block_work *k = &w->blk;
     lsb_k_mrhs_pack(n, k->kp, nb, NULL, d_R + (size_t)c0 * ldr, ldr, k->b, g_stream);
-    dirm_products(sv, k, NULL);
+    direct_tier_enqueue_m(sv, k, NULL); /* once, un-gated, from B */
     lsb_k_mrhs_unpack(n, k->kp, nb, NULL, k->x, d_Z + (size_t)c0 * ldz, ldz, g_stream);
   }
   drain_stream(sv, "lsb_hip_solver_direct_apply_multi_dev");
@@ -200,7 +184,7 @@ int lsb_hip_solver_direct_apply_multi_dev(lsb_hip_solver *sv, unsigned nrhs, con
                                           size_t ldz) {
   if (!lsb_initialized)
     return 1;
-  if (block_args_bad(sv, nrhs, 0, d_R, ldr, d_Z, ldz) || !sv->dir || sv->dir->tier)
+  if (block_args_bad(sv, nrhs, 0, d_R, ldr, d_Z, ldz) || !sv->dir || direct_tiered(sv))
     return 2;
   return dirm_apply_dev(sv, nrhs, d_R, ldr, d_Z, ldz);
 }
@@ -233,12 +217,9 @@ int lsb_hip_solver_direct_tier_apply_multi_dev(lsb_hip_solver *sv, unsigned nrhs
   return dirm_apply_dev(sv, nrhs, d_R, ldr, d_Z, ldz);
 }
 
-/* a single skyline: lsb_hip_solver_direct_multi_round_bytes; a tiered factor: fixed + kp per_column, derived above
- * direct_tier_multi_round_bytes */
+/* direct_round_bytes at the width of the block, one tier or more */
 unsigned long long lsb_hip_solver_direct_tier_multi_round_bytes(const lsb_hip_solver *sv, unsigned nrhs) {
   if (!sv || !sv->dir || nrhs == 0)
     return 0;
-  if (!sv->dir->tier)
-    return lsb_hip_solver_direct_multi_round_bytes(sv, nrhs);
-  return direct_tier_multi_round_bytes(sv, nrhs == 1 ? 1u : block_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs));
+  return direct_round_bytes(sv, nrhs == 1 ? 1u : block_width(nrhs > LSB_MRHS_MAX ? LSB_MRHS_MAX : nrhs));
 }

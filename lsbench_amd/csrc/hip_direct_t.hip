@@ -1,8 +1,11 @@
-// The direct solver on a tiered inverse factor (lsb_hip_solver_create_direct; the factor: lsb_direct.c, struct
-// lsb_tierinv; the driver: hip_direct_t_drv.c).  The rows are numbered tier by tier, L is block lower triangular, and
-// only the diagonal blocks are inverted: W_tt = (L_tt)^-1 are skylines like hip_direct.hip's single one, the blocks
-// below the diagonal are the sparse rows of L, by rows (C) and by columns (C^T).  Two work vectors in the tier-major
-// numbering: y (the forward result, then the backward operand u, in place) and z.
+// The direct solver's products x (+)= P^T L^-T L^-1 P r on the inverse factor in m tiers (the factor: lsb_direct.c,
+// struct lsb_tierinv; the driver: hip_direct_drv.c).  The rows are numbered tier by tier, L is block lower triangular,
+// and only the diagonal blocks are inverted: W_tt = (L_tt)^-1 are skylines -- row k is the dense run of columns
+// first[k] .. k at vals[woff[k] ..], 8 B per entry, no column indices and no transposed copy --, the blocks below the
+// diagonal are the sparse rows of L, by rows (C) and by columns (C^T).  One tier (lsb_hip_solver_create, tiers = 1) is
+// the single skyline W = L^-1: no coupling, x = P^T W^T (W (P r)), k_dirt_rows<true> and k_dirt_cols and nothing else,
+// z == NULL and not stored.  Two work vectors in the tier-major numbering otherwise: y (the forward result, then the
+// backward operand u, in place) and z.
 //
 //   round k:  y_0 = W_00 (P r)_0                      k_dirt_rows<true>   r = b in round 1, read through perm
 //             t = 1 .. m - 1:
@@ -12,23 +15,37 @@
 //             t = m - 1 .. 1:
 //               y_j -= sum_i C_t[i, j] z_i, j < lo_t  k_dirt_bwd          rows of C^T: one owner per y_j
 //               z_(t-1) = W^T y_(t-1) ; x[perm] (+)=  k_dirt_cols
-//   then k_dir_resid and k_dir_step of hip_direct.hip, as they are: 4 m - 2 launches in front of them.
+//   then k_dir_resid and k_dir_step of hip_direct.hip: 4 m - 2 launches in front of them, two at one tier.
 //
 // The rules are hip_direct.hip's: every launch is gated on the status, the round is read from the state (iters), all
 // sums run in a fixed order without atomics, and no workgroup waits on another -- the launches are the only ordering.
 //
-// k_dirt_rows / k_dirt_cols are k_dir_rows / k_dir_cols on one tier's row range: the groups, the workgroups and the
-// windows of the first never straddle a tier (the host deals tier by tier), the 64-column windows of the second start
-// at the tier's first row, and a walk to the root ends at the root of the tier's tree (parent = n).  The coupling
-// kernels take a wavefront per group of consecutive rows with the same lane count L, a function of the row's length
-// alone (about four entries per lane, 1 .. 64): lane l of a row takes entries l, l + L, ... with fma in ascending
-// order, the lanes are folded by the xor butterfly; a row of thousands of entries is one wavefront's.
+// k_dirt_rows, on one tier's row range.  The host deals the rows into groups -- consecutive rows that take the same
+// number of lanes L, 64 / L of them: one wavefront's work -- and the groups into workgroups of about equal entry
+// count; no group, workgroup or window straddles a tier.  The column runs of consecutive rows nest or abut
+// (postorder), so a workgroup reads one contiguous window of its operand; it stages the window in LDS once where it
+// fits the launch's LDS (cap doubles), else it gathers from global memory -- the same numbers either way.  Lane rule,
+// a function of the row's length alone, so the bits do not depend on the dealing: L lanes per row (about four entries
+// per lane, 1 .. 64), lane l takes entries l, l + L, ... with fma in ascending order, the lanes are folded by the xor
+// butterfly.
+//
+// k_dirt_cols, on one tier's columns.  A workgroup owns 64 consecutive columns [j0, j1] from the tier's first row on,
+// one lane per column in each of its sixteen wavefronts, and visits the rows that reach them: first the rows
+// j0 .. j1, then the ancestors of j1 beyond it, run by run from run_end / parent (every ancestor of a window column
+// above j1 is an ancestor of j1), up to the root of the tier's tree (parent = n).  Lane j takes part in row k where
+// first[k] <= j <= k; a row is one coalesced run of the window's width.  The visited rows are dealt round-robin to
+// the sixteen wavefronts in visiting order; each adds its own in ascending k and the sixteen sums are added in
+// ascending order.  Nobody walks parent[] vertex by vertex: the largest subtree is numbered last (lsb_direct.c), so a
+// walk to the root is a handful of runs.
+//
+// The coupling kernels take a wavefront per group of consecutive rows with the same lane count L, by the lane rule
+// above; a row of thousands of entries is one wavefront's.
 #include "hip_kcommon.h"
 
 #define DIRT_HIDDEN __attribute__((visibility("hidden")))
-#define DIRT_COLS 64
+#define DIRT_COLS 64 // columns per workgroup of k_dirt_cols: one wavefront's width
 #define DIRT_FLIGHT 8
-#define DIRT_CWG 1024
+#define DIRT_CWG 1024 // ... and its threads: sixteen wavefronts share the rows that reach the window
 
 typedef unsigned long long dirt_u64;
 
@@ -69,10 +86,13 @@ __global__ __launch_bounds__(WG) void k_dirt_rows(const double *__restrict__ val
 #pragma unroll 4
         for (unsigned e = l; e < len; e += L)
           acc = fma(w[e], a[e], acc);
+      } else if (PERM) { // (no unroll hint: two dependent loads per entry; measured slower with one on one tier)
+        for (unsigned e = l; e < len; e += L)
+          acc = fma(w[e], v[perm[f + e]], acc);
       } else {
 #pragma unroll 4
         for (unsigned e = l; e < len; e += L)
-          acc = fma(w[e], PERM ? v[perm[f + e]] : v[f + e], acc);
+          acc = fma(w[e], v[f + e], acc);
       }
     }
     for (unsigned m = 32; m >= 1; m >>= 1)
@@ -83,8 +103,8 @@ __global__ __launch_bounds__(WG) void k_dirt_rows(const double *__restrict__ val
   }
 }
 
-// the columns lo .. hi - 1 of one tier: z_j = (W_tt^T t)_j, stored, and x[perm[j]] = or += z_j (mode: 0 = by the
-// state -- round 1 stores x, the others add to it --, 1 = store whatever the state says)
+// the columns lo .. hi - 1 of one tier: z_j = (W_tt^T t)_j, stored where z != NULL, and x[perm[j]] = or += z_j (mode:
+// 0 = by the state -- round 1 stores x, the others add to it --, 1 = store whatever the state says)
 __global__ __launch_bounds__(DIRT_CWG) void k_dirt_cols(unsigned n, unsigned lo, unsigned hi,
                                                         const double *__restrict__ vals,
                                                         const dirt_u64 *__restrict__ woff,
@@ -105,8 +125,9 @@ __global__ __launch_bounds__(DIRT_CWG) void k_dirt_cols(unsigned n, unsigned lo,
   const unsigned j = j0 + lane;
   const bool active = j <= j1;
   double acc = 0.0;
-  // this wavefront's rows k0, k0 + NW, ... <= kend, 64 at a time: lane m fetches what row m of the batch needs, then
-  // every lane walks the batch with those broadcast, DIRT_FLIGHT rows' loads of W in flight together
+  // this wavefront's rows k0, k0 + NW, ... <= kend, 64 at a time: lane m fetches what row m of the batch needs (its
+  // first column, its offset, t_k), then every lane walks the batch with those broadcast -- the loads of W are
+  // independent of one another, DIRT_FLIGHT rows' go out together
   auto visit = [&](unsigned k0, unsigned kend) {
     for (unsigned kb = k0; kb <= kend; kb += 64 * NW) {
       const unsigned km = kb + lane * NW;
@@ -145,12 +166,13 @@ __global__ __launch_bounds__(DIRT_CWG) void k_dirt_cols(unsigned n, unsigned lo,
   part[wave][lane] = acc;
   __syncthreads();
   if (wave == 0 && active) {
+    const unsigned i = perm[j]; // (asked for ahead of the sums and of the branch on z: its latency hides behind them)
     double s = part[0][lane];
 #pragma unroll
     for (unsigned w = 1; w < NW; w++)
       s += part[w][lane];
-    z[j] = s;
-    const unsigned i = perm[j];
+    if (z) // (uniform over the launch: NULL at one tier, where nobody reads z)
+      z[j] = s;
     x[i] = add ? x[i] + s : s;
   }
 }

@@ -1,7 +1,8 @@
-// The direct solver on a tiered inverse factor, on blocks of right-hand sides (lsb_hip_solver_solve_direct_tier_multi
-// [_dev], _direct_tier_apply_multi_dev; the host side: direct_tier_enqueue_m in hip_direct_t_drv.c, the work area and
-// the entry points in hip_direct_m_drv.c): the 4 m - 2 launches of hip_direct_t.hip on KP = 2, 4 or 8 columns at once,
-// every entry of the W_tt, of C and of C^T loaded ONCE per product for all of them.
+// The direct solver's products on blocks of right-hand sides (lsb_hip_solver_solve_direct_multi[_dev],
+// _solve_direct_tier_multi[_dev] and their _apply_multi_dev; the host side: direct_tier_enqueue_m in hip_direct_drv.c,
+// the work area and the entry points in hip_direct_m_drv.c): the 4 m - 2 launches of hip_direct_t.hip on KP = 2, 4 or 8
+// columns at once, every entry of the W_tt, of C and of C^T loaded ONCE per product for all of them.  One tier (the
+// single skyline): k_dirt_rows_m<KP, true> and k_dirt_cols_m and nothing else, Z == NULL and not stored.
 //
 //   round k:  Y_0 = W_00 (P V)_0                      k_dirt_rows_m<KP, true>   V = B in round 1, read through perm
 //             t = 1 .. m - 1:
@@ -14,7 +15,7 @@
 //   then k_dir_resid_m and k_dir_step_m of hip_direct_m.hip, as they are.
 //
 // The rule of the block: a column has the bits of the same column solved alone on the same solver.  Every kernel here
-// is its twin of hip_direct_t.hip per column -- the same lanes per row, the same fma chain in ascending order, the same
+// is its namesake of hip_direct_t.hip per column -- the same lanes per row, the same fma chain in ascending order, the same
 // xor butterfly, the same ascending sum of the sixteen partial sums -- and shares only what does not round: the loads
 // of vals / cvals / tvals, of first / woff, of the offsets and the column indices.  No MFMA, no atomics, nobody waits
 // on another workgroup: the launches are the only ordering.
@@ -104,8 +105,8 @@ __global__ __launch_bounds__(WG) void k_dirt_rows_m(const double *__restrict__ v
   }
 }
 
-// the columns lo .. hi - 1 of one tier: Z_j = (W_tt^T Y)_j, stored for every column of the block, and X[perm[j]] = or
-// += Z_j, gated per column.  k_dirt_cols' shape: 64 columns per workgroup from the tier's first row, the window's own
+// the columns lo .. hi - 1 of one tier: Z_j = (W_tt^T Y)_j, stored for every column of the block where z != NULL, and
+// X[perm[j]] = or += Z_j, gated per column.  k_dirt_cols' shape: 64 columns per workgroup from the tier's first row, the window's own
 // rows and then the ancestors of its last column inside the tier (parent == n ends the walk), run by run, dealt
 // round-robin to the sixteen wavefronts in visiting order; each wavefront adds its rows in ascending k into KP
 // accumulators per lane -- ONE load of W for KP fma -- and the sixteen partial sums are added in ascending order.  A
@@ -182,7 +183,8 @@ __global__ __launch_bounds__(DIRT_CWG) void k_dirt_cols_m(unsigned n, unsigned l
       for (unsigned w = 1; w < NW; w++)
         s[q] += part[w][2 * wave + q][lane];
     }
-    ((d2v *)z)[(size_t)j * H + wave] = d2v{s[0], s[1]};
+    if (z) // (uniform over the launch: NULL at one tier, where nobody reads Z)
+      ((d2v *)z)[(size_t)j * H + wave] = d2v{s[0], s[1]};
     const int a0 = !st || st->c[2 * wave].status == LSB_STATUS_RUNNING;
     const int a1 = !st || st->c[2 * wave + 1].status == LSB_STATUS_RUNNING;
     if (a0 | a1) {
@@ -296,8 +298,7 @@ __global__ __launch_bounds__(WG) void k_dirt_bwd_m(const unsigned *__restrict__ 
   }
 }
 
-// rows in flight per wavefront of k_dirt_cols_m: fewer at the wider blocks, so that nothing spills (dirm_flight's
-// values: the kernel is k_dir_cols_m with one more store)
+// rows in flight per wavefront of k_dirt_cols_m: fewer at the wider blocks, so that nothing spills
 template <int KP> struct dirtm_flight { static constexpr int value = KP == 2 ? 8 : 4; };
 
 extern "C" {

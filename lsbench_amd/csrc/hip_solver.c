@@ -719,12 +719,9 @@ static lsb_hip_solver *solver_create(const struct csr *A, const struct lsb_hip_o
   /* the direct solver factorises first: what it refuses, it refuses before anything is allocated on the device */
   unsigned dir_height = 0;
   double dir_seconds = 0.0;
-  struct lsb_skyinv *dirW = NULL;
   struct lsb_tierinv *dirT = NULL;
-  if (o.krylov == LSB_KRYLOV_DIRECT && tiers == 1)
-    dirW = direct_factor(S, &o, &dir_height, &dir_seconds);
-  else if (o.krylov == LSB_KRYLOV_DIRECT)
-    dirT = direct_tier_factor(S, &o, tiers, &dir_height, &dir_seconds);
+  if (o.krylov == LSB_KRYLOV_DIRECT)
+    dirT = direct_factor(S, &o, tiers, &dir_height, &dir_seconds);
   /* a constant-coefficient 2-D grid whose lines are not whole slices: pad the lines (lsb_csr_pad_lines) --
    * the +-nx diagonals become whole-slice offsets and the z-column forms apply along y.  b and x
    * travel through the same gather / scatter as a re-ordering's; the pad unknowns stay exactly 0.
@@ -800,8 +797,6 @@ static lsb_hip_solver *solver_create(const struct csr *A, const struct lsb_hip_o
   free(hull), free(bounds);
   lsb_csr_free(S);
   solver_finish_setup(sv);
-  if (dirW)
-    direct_upload(sv, dirW, dir_height, dir_seconds);
   if (dirT)
     direct_tier_upload(sv, dirT, dir_height, dir_seconds);
   return sv;

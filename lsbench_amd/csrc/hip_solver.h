@@ -18,9 +18,9 @@
  *   hip_gmres_drv.c  GMRES(m) driver
  *   hip_bicgstab_drv.c  BiCGSTAB driver
  *   hip_rich_drv.c   AMG as the solver: stationary V-cycle iterations (Richardson)
- *   hip_direct_drv.c the direct solver: factor at creation, rounds of x (+)= W^T W r on a skyline inverse factor
- *   hip_direct_m_drv.c  ... on blocks of right-hand sides: W streamed once per product for a block of columns
- *   hip_direct_t_drv.c  ... on a tiered factor, for operators whose single skyline is over the entry budget
+ *   hip_direct_drv.c the direct solver: factor at creation, rounds of x (+)= L^-T L^-1 r on an inverse factor in tiers
+ *                    (one tier: the single skyline W = L^-1; more for operators whose single skyline is over the budget)
+ *   hip_direct_m_drv.c  ... on blocks of right-hand sides: the factor streamed once per product for a block of columns
  *   hip_rich_m_drv.c ... AMG as the solver on blocks of right-hand sides: the hierarchy streamed once per cycle
  *   hip_block.c      interleaved blocks of right-hand sides, what their two drivers share: the service rules, the work
  *                    area (struct block_work), Z = M^-1 R on a block, the enqueue and host-buffer wrappers
@@ -371,33 +371,24 @@ struct lsb_hip_solver {
    * and the partial count of its update sweep */
   struct graph_cache rich_graphs;
   unsigned rich_nrr;
-  /* The direct solver (hip_direct_drv.c), NULL on every other solver: the skyline inverse factor on the device and
-   * the dealing of its rows (k), t = W P r, what the factor is (entries, tree height, set-up seconds), the record
-   * count of the residual launch, and its cache of captured graphs -- keyed on the count and on x; b is in them too,
-   * so they are dropped when a solve brings another b (graph_b).  Blocks of right-hand sides (hip_direct_m_drv.c): the
-   * widest window of P V that k_dir_rows_m stages per width kp = 2, 4, 8, in rows (lds_m), and a work area per width,
-   * made when the solver first solves a block of that width (m: blk.kp != 0) -- interleaved B, X, R and T = W P V
-   * (blk.b, .x, .r, .p), behind them the records of the residual launch and the state; its graphs are keyed on the
-   * count alone (blk.g), its hint is the rounds the previous block of this width took */
+  /* The direct solver (hip_direct_drv.c), NULL on every other solver: the inverse factor in tiers on the device and
+   * the dealing of its rows (k; one tier: the single skyline), y (d_t; at one tier t = W P r) and z (NULL at one tier),
+   * what the factor is (entries of the W_tt, of the coupling, tree height, set-up seconds), the record count of the
+   * residual launch, and its cache of captured graphs -- keyed on the count and on x; b is in them too, so they are
+   * dropped when a solve brings another b (graph_b).  Blocks of right-hand sides (hip_direct_m_drv.c): a work area per
+   * width, made when the solver first solves a block of that width (m: blk.kp != 0) -- interleaved B, X, R and Y
+   * (blk.b, .x, .r, .p; at one tier Y is T = W P V), tiered a fifth block, Z (blk.q), behind them the records of the
+   * residual launch and the state; its graphs are keyed on the count alone (blk.g), its hint is the rounds the previous
+   * block of this width took */
   struct direct_dev {
-    struct lsb_dir_dev k;
-    void *mem[9];
-    double *d_t;
-    unsigned long long entries;
+    struct lsb_dirt_dev k;
+    void *mem[17];
+    double *d_t, *d_z;
+    unsigned long long entries, coupling;
     unsigned height, nrec;
     double setup_s;
     struct graph_cache graphs;
     const double *graph_b;
-    unsigned lds_m[3];
-    /* a tiered factor (hip_direct_t_drv.c), NULL on a single skyline: k is then unused but for k.n, d_t is y.  Blocks
-     * of right-hand sides on it have entry points of their own (lsb_hip_solver_solve_direct_tier_multi[_dev]): the
-     * work area m[] of a width then holds a fifth block, Z (blk.q), and Y is blk.p */
-    struct direct_tier_dev {
-      struct lsb_dirt_dev k;
-      void *mem[17];
-      double *d_z;
-      unsigned long long coupling;
-    } *tier;
     struct dirm_work {
       struct block_work blk;
       double *rec;
@@ -712,40 +703,26 @@ LSB_INTERNAL solve_dev_fn direct_solve_dev;
 /* what --krylov direct cannot run with, refused at creation (shards, persistent); what it does not consult is set
  * aside (precond, reorder), and mixed precision falls back to fp64, said aloud */
 LSB_INTERNAL void direct_check(struct lsb_hip_opts *o, int sharded);
-/* order, count, factorise on the host: refuses an operator over the entry budget before anything is allocated, and
- * one that is not symmetric positive definite */
-LSB_INTERNAL struct lsb_skyinv *direct_factor(const struct csr *S, const struct lsb_hip_opts *o, unsigned *height,
-                                              double *seconds);
-LSB_INTERNAL void direct_upload(lsb_hip_solver *sv, struct lsb_skyinv *W, unsigned height, double seconds); /* frees W */
+/* order, count, factorise on the host in `tiers` tiers (1: the single skyline; 0: the fewest that fit): refuses an
+ * operator over the entry budget before anything is allocated, and one that is not symmetric positive definite */
+LSB_INTERNAL struct lsb_tierinv *direct_factor(const struct csr *S, const struct lsb_hip_opts *o, int tiers,
+                                               unsigned *height, double *seconds);
+LSB_INTERNAL void direct_tier_upload(lsb_hip_solver *sv, struct lsb_tierinv *T, unsigned height, double seconds); /* frees T */
 LSB_INTERNAL void direct_free(lsb_hip_solver *sv);
-LSB_INTERNAL int direct_apply_dev(lsb_hip_solver *sv, const double *d_r, double *d_z); /* z = W^T W r, once */
+LSB_INTERNAL int direct_apply_dev(lsb_hip_solver *sv, const double *d_r, double *d_z); /* z = L^-T L^-1 r, once */
+/* a direct solver whose factor has more than one tier: coupling, z, 4 m - 2 launches per round, blocks of right-hand
+ * sides through lsb_hip_solver_solve_direct_tier_multi[_dev] alone */
+static inline int direct_tiered(const lsb_hip_solver *sv) { return sv->dir->k.ntier > 1; }
+/* what a round on a block of width kp streams (kp = 1: a single solve) */
+LSB_INTERNAL unsigned long long direct_round_bytes(const lsb_hip_solver *sv, unsigned kp);
 LSB_INTERNAL void lsb_k_dir_init_state(struct lsb_pcg_state *st, double tol, int maxit, void *stream);
-LSB_INTERNAL void lsb_k_dir_rows(const struct lsb_dir_dev *d, const double *b, const double *r, double *t,
-                                 const struct lsb_pcg_state *st, int src, void *stream);
-LSB_INTERNAL void lsb_k_dir_cols(const struct lsb_dir_dev *d, const double *t, double *x,
-                                 const struct lsb_pcg_state *st, int mode, void *stream);
 LSB_INTERNAL void lsb_k_dir_resid(unsigned n, const int *offs, const int *cols, const double *vals, unsigned lanes,
                                   const double *b, const double *x, double *r, double *records, unsigned *nrecords,
                                   const struct lsb_pcg_state *st, void *stream);
 LSB_INTERNAL void lsb_k_dir_step(struct lsb_pcg_state *st, const double *records, unsigned nrecords, void *stream);
-/* the dealing of the skyline rows r0 .. r1 - 1 to k_dir_rows, appended to grp (at *ngrp), blk and bwin (at *nblk):
- * groups of consecutive rows with one lane count, workgroups of about `target` entries; *widest: the widest window
- * within `cap` doubles (0 or more than DIR_LDS_CAP: DIR_LDS_CAP), lds_m (may be NULL): the widest of at most cap / kp
- * rows per width kp = 2, 4, 8 of the block kernels.  The caller closes blk[*nblk] */
-LSB_INTERNAL void direct_deal_rows(const unsigned *first, const unsigned long long *woff, unsigned r0, unsigned r1,
-                                   unsigned long long target, unsigned cap, unsigned *grp, unsigned *ngrp,
-                                   unsigned *blk, unsigned *bwin, unsigned *nblk, unsigned *widest, unsigned *lds_m);
-LSB_INTERNAL unsigned direct_row_lanes(unsigned len); /* lanes per row from its length alone: 1 .. 64 */
-LSB_INTERNAL unsigned long long direct_block_target(unsigned long long entries);
-/* hip_direct_t_drv.c: the direct solver on a tiered factor (lsb_hip_solver_create_direct), and the launchers of
- * hip_direct_t.hip (t: the tier) */
-LSB_INTERNAL struct lsb_tierinv *direct_tier_factor(const struct csr *S, const struct lsb_hip_opts *o, int tiers,
-                                                    unsigned *height, double *seconds);
-LSB_INTERNAL void direct_tier_upload(lsb_hip_solver *sv, struct lsb_tierinv *T, unsigned height, double seconds);
-LSB_INTERNAL void direct_tier_free(lsb_hip_solver *sv);
-LSB_INTERNAL unsigned long long direct_tier_round_bytes(const lsb_hip_solver *sv);
-/* one application x (+)= P^T L^-T L^-1 P r: 4 m - 2 launches; src, mode: as in k_dir_rows, k_dir_cols */
-LSB_INTERNAL void direct_tier_enqueue(lsb_hip_solver *sv, const double *d_b, const double *d_r, double *d_x, int fixed);
+/* the launchers of hip_direct_t.hip, the products on tier t: src 0 = the operand by the state (b in round 1, r
+ * afterwards), 1 = b whatever the state says; mode 0 = x by the state (stored in round 1, added to afterwards), 1 =
+ * stored; z may be NULL in lsb_k_dirt_cols (one tier) */
 LSB_INTERNAL void lsb_k_dirt_rows(const struct lsb_dirt_dev *d, unsigned t, const double *b, const double *r,
                                   const double *v, double *y, const struct lsb_pcg_state *st, int src, void *stream);
 LSB_INTERNAL void lsb_k_dirt_cols(const struct lsb_dirt_dev *d, unsigned t, const double *y, double *z, double *x,
@@ -755,12 +732,10 @@ LSB_INTERNAL void lsb_k_dirt_fwd(const struct lsb_dirt_dev *d, unsigned t, const
 LSB_INTERNAL void lsb_k_dirt_bwd(const struct lsb_dirt_dev *d, unsigned t, const double *z, double *y,
                                  const struct lsb_pcg_state *st, void *stream);
 /* the same on a block of kp = 2, 4 or 8 interleaved right-hand sides (hip_direct_tm.hip): B, R, X of the work area in
- * the caller's numbering, Y = k->p and Z = k->q in the tier-major one; st: the gate, NULL for one un-gated application
- * that reads k->b and stores k->x.  direct_tier_multi_round_bytes: what a round of that width streams (kp = 1:
- * direct_tier_round_bytes) */
+ * the caller's numbering, Y = k->p and Z = k->q (NULL at one tier) in the factor's; st: the gate, NULL for one
+ * un-gated application that reads k->b and stores k->x */
 LSB_INTERNAL void direct_tier_enqueue_m(lsb_hip_solver *sv, const struct block_work *k,
                                         const struct lsb_mrhs_state *st);
-LSB_INTERNAL unsigned long long direct_tier_multi_round_bytes(const lsb_hip_solver *sv, unsigned kp);
 LSB_INTERNAL void lsb_k_dirt_rows_m(unsigned kp, const struct lsb_dirt_dev *d, unsigned t, const double *b,
                                     const double *r, const double *v, double *y, const struct lsb_mrhs_state *st,
                                     void *stream);
@@ -772,13 +747,9 @@ LSB_INTERNAL void lsb_k_dirt_fwd_m(unsigned kp, const struct lsb_dirt_dev *d, un
 LSB_INTERNAL void lsb_k_dirt_bwd_m(unsigned kp, const struct lsb_dirt_dev *d, unsigned t, const double *z, double *y,
                                    const struct lsb_mrhs_state *st, void *stream);
 /* hip_direct_m_drv.c: the direct solver on blocks of right-hand sides, and the launchers of hip_direct_m.hip (kp: 2, 4
- * or 8; interleaved blocks; st: the gate, NULL in rows_m / cols_m for one un-gated application that reads b and stores) */
+ * or 8; interleaved blocks; st: the gate) */
 LSB_INTERNAL void direct_multi_free(lsb_hip_solver *sv); /* the work areas of every width */
 LSB_INTERNAL void lsb_k_dir_init_state_m(struct lsb_mrhs_state *st, unsigned kp, double tol, int maxit, void *stream);
-LSB_INTERNAL void lsb_k_dir_rows_m(unsigned kp, const struct lsb_dir_dev *d, unsigned lds_rows, const double *b,
-                                   const double *r, double *t, const struct lsb_mrhs_state *st, void *stream);
-LSB_INTERNAL void lsb_k_dir_cols_m(unsigned kp, const struct lsb_dir_dev *d, const double *t, double *x,
-                                   const struct lsb_mrhs_state *st, void *stream);
 LSB_INTERNAL void lsb_k_dir_resid_m(unsigned kp, unsigned n, const int *offs, const int *cols, const double *vals,
                                     unsigned lanes, const double *b, const double *x, double *r, double *records,
                                     unsigned *nrecords, const struct lsb_mrhs_state *st, void *stream);

@@ -1,5 +1,5 @@
 /*
- * Host side of the direct solver (LSB_KRYLOV_DIRECT; hip_direct_drv.c applies the factor through hip_direct.hip):
+ * Host side of the direct solver (LSB_KRYLOV_DIRECT; hip_direct_drv.c applies the factor through hip_direct_t.hip):
  * a nested-dissection ordering, the symbolic count, and the explicit inverse factor W = L^-1 of P S P^T = L L^T as a
  * skyline.  Set-up, untimed, like FSAI's, AMG's and CHOLMOD's factorisation (src/cholmod-impl.h:25-26).  Plain C
  * with OpenMP; nothing here touches the device.

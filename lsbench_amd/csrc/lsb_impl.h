@@ -479,20 +479,12 @@ void lsb_k_blockcg_m_start(unsigned kp, unsigned n, const double *b, const doubl
 void lsb_k_blockcg_m_pass_b(unsigned kp, unsigned n, double *w, const double *z, double *p,
                             const struct lsb_blockcg_state *st, void *stream);
 
-/* ---- the direct solver (hip_direct.hip; launchers in hip_solver.h) -------------
- * The skyline inverse factor on the device and how k_dir_rows deals it: grp[2 g] = first row of group g, grp[2 g + 1]
- * = rows << 8 | lanes per row; blk[w] .. blk[w + 1]: the groups of workgroup w; bwin[2 w], bwin[2 w + 1]: first
- * column and width of the window of P r its rows read.  lds_doubles: what a launch stages at the most. */
-struct lsb_dir_dev {
-  unsigned n, nblk, ngrp, lds_doubles;
-  const double *vals;
-  const unsigned long long *woff;
-  const unsigned *first, *perm, *parent, *run_end, *grp, *blk, *bwin;
-};
-
-/* ---- the direct solver on a tiered factor (hip_direct_t.hip; launchers in hip_solver.h) ----
- * struct lsb_tierinv on the device.  grp / blk / bwin as in struct lsb_dir_dev, dealt tier by tier: tier t's
- * workgroups are blk0 .. blk0 + nblk - 1 and stage lds_doubles at the most.  cgrp / tgrp: the rows of C and of C^T in
+/* ---- the direct solver's factor on the device (hip_direct_t.hip, hip_direct_tm.hip; launchers in hip_solver.h) ----
+ * struct lsb_tierinv on the device; one tier is the single skyline, and the coupling's pointers are then NULL.  How
+ * k_dirt_rows deals the skyline rows: grp[2 g] = first row of group g, grp[2 g + 1] = rows << 8 | lanes per row;
+ * blk[w] .. blk[w + 1]: the groups of workgroup w; bwin[2 w], bwin[2 w + 1]: first column and width of the window
+ * of its operand its rows read.  Dealt tier by tier: tier t's workgroups are blk0 .. blk0 + nblk - 1 and stage
+ * lds_doubles at the most.  cgrp / tgrp: the rows of C and of C^T in
  * groups of the same shape (first row, rows << 8 | lanes per row), tier t's at cg0 .. cg1 - 1 and tg0 .. tg1 - 1;
  * tbase: where tier t's offsets begin in toffs.  lds_m: the widest window, in rows, that the tier's launch on a block
  * of 2, 4, 8 right-hand sides stages (hip_direct_tm.hip). */

@@ -31,7 +31,7 @@ from test_mrhs import columns
 
 XN3B, TJ7A, ONE, TRI, FOREST, DIAG, SINGLE = "xn3b_A_18", "tj7a_A_12", "lap2d:nx=12,ny=9", "tri300", "forest", \
     "I1_05x05", "n1"
-WIDE = "lap2d:nx=100,ny=90"  # 9000 rows: the top rows' windows of P r are wider than k_dir_rows stages in LDS
+WIDE = "lap2d:nx=100,ny=90"  # 9000 rows: the top rows' windows of P r are wider than k_dirt_rows stages in LDS
 # the entries of W under the throw-away ordering the method was proposed with (BFS level sets, leaf size 32)
 PROPOSED = {XN3B: 2.46e6, TJ7A: 4.27e6}
 EPS = 2.0 ** -52

@@ -4,7 +4,7 @@ _direct_multi_round_bytes; hip_direct_m.hip, hip_direct_m_drv.c): W streamed onc
 The contract makes the tests exact: a column solved in a block is, bit for bit, that column solved alone by solve_dev
 (or applied alone by precond_dev) on the same solver -- x, iters, status, relres, true_relres, spmvs.
 
-CPU: the surface.  GPU: one application at every width on every path of k_dir_rows_m (every window staged; the
+CPU: the surface.  GPU: one application at every width on every path of k_dirt_rows_m (every window staged; the
 gathered path at width 8 only; the gathered path at every width); the solves; columns that stop on their own; the
 layout of the caller's blocks; the refusals."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """The direct solver on a tiered factor on blocks of right-hand sides (lsb_hip_solver_solve_direct_tier_multi[_dev],
-_direct_tier_apply_multi_dev, _direct_tier_multi_round_bytes; hip_direct_tm.hip, hip_direct_t_drv.c,
+_direct_tier_apply_multi_dev, _direct_tier_multi_round_bytes; hip_direct_tm.hip, hip_direct_drv.c,
 hip_direct_m_drv.c): the 4 m - 2 launches of the tiers on 2, 4 or 8 columns at once, the factor and its coupling loaded
 once per product for all of them.
 

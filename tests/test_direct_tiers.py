@@ -1,5 +1,5 @@
 """The direct solver on a tiered inverse factor (lsb_hip_solver_create_direct; lsb_direct.c, hip_direct_t.hip,
-hip_direct_t_drv.c), for operators whose single skyline W = L^-1 is over the entry budget.
+hip_direct_drv.c), for operators whose single skyline W = L^-1 is over the entry budget.
 
     tiers      the elimination tree cut by subtree size: tier(k) = how many of the thresholds T_i (the smallest integer
                with T_i^m >= n^i) the subtree of k exceeds; rows numbered tier by tier, postorder inside a tier
@@ -526,6 +526,100 @@ def test_cross_checks(hip, matrix_path, golden_x):
     j = hip.Solver(as_matrix(S), hip.default_opts(op_mode=hip.OP_RAW))
     assert j.direct_tier_info() is None
     j.destroy()
+
+
+ONE_TIER = ["lap2d:nx=12,ny=9", XN3B]  # 108 rows and 3461: one tier fits both
+
+
+def _one_tier_opts(hip, **kw):
+    return hip.default_opts(op_mode=hip.OP_RAW, krylov=hip.KRYLOV_DIRECT, **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ONE_TIER)
+def test_one_tier_is_one_solver(hip, name, matrix_path):
+    """lsb_hip_solver_create, create_direct(.., 1) and create_direct(.., 0) on an operator that fits one tier are the
+    same solver: the same figures, the same bytes of x and of one application, served alike by the block entry points
+    of the single skyline."""
+    import torch
+    from lsbench_amd.api import _ptr
+    lib = _lib.load()
+    S = operator(name, matrix_path)
+    n = S.shape[0]
+    b = rhs(n)
+    B = np.stack([b, b + 1.0])
+    r = np.sin(np.arange(n, dtype=np.float64)) + 0.5
+    got = []
+    for how in ("create", 1, 0):
+        rec = {}
+        for key, kw in (("tol", dict(tol=1e-12, maxit=10)), ("one", dict(tol=0.0, maxit=1))):
+            o = _one_tier_opts(hip, **kw)
+            s = hip.Solver(as_matrix(S), o) if how == "create" else hip.Solver.create_direct(as_matrix(S), o, how)
+            rec["info"] = s.direct_info
+            assert s.direct_tier_info() == (1, rec["info"][0], 0, [n], 2)
+            assert rec["info"][2] == 16 * rec["info"][0] + 56 * n
+            rec["bytes"] = [s.direct_multi_round_bytes(k) for k in (2, 4, 8)]
+            assert rec["bytes"] == [16 * rec["info"][0] + (24 + 32 * k) * n for k in (2, 4, 8)]
+            x, res = _solve_dev(s, b)
+            rec[key] = [x.tobytes()]
+            d_X = torch.full((2, n), float("nan"), dtype=torch.float64, device="cuda:0")
+            res2 = (_lib.Result * 2)()
+            assert lib.lsb_hip_solver_solve_direct_multi_dev(s._h, 2, _ptr(_dev(B)), n, _ptr(d_X), n, res2) == 0
+            X = d_X.cpu().numpy()
+            assert X[0].tobytes() == x.tobytes()
+            x1, _ = _solve_dev(s, B[1])
+            assert X[1].tobytes() == x1.tobytes()
+            rec[key].append(X.tobytes())
+            if key == "tol":
+                assert res.status == hip.STATUS_CONVERGED and res2[0].status == res2[1].status == hip.STATUS_CONVERGED
+                z = _nan(n)
+                s.precond_dev(_dev(r), z)
+                rec["z"] = z.cpu().numpy().tobytes()
+                assert np.isfinite(z.cpu().numpy()).all()
+            s.destroy()
+        got.append(rec)
+    for rec in got[1:]:
+        assert rec == got[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ONE_TIER)
+def test_one_tier_gathered_is_staged(hip, name, matrix_path, monkeypatch, capfd):
+    """The gathered windows of the one-tier solver on small shapes: with at most 16 doubles of a window staged
+    (LSBENCH_HIP_DIRECT_TIER_LDS at creation), one application has the bytes it has with every window staged -- at one
+    column and through lsb_hip_solver_direct_apply_multi_dev at widths 2 and 8.  That the knob took hold is read off the
+    verbose line of the upload ("windows of up to %u doubles in LDS"): without it a window wider than 16 doubles is staged,
+    with it none is."""
+    import re
+    import torch
+    S = operator(name, matrix_path)
+    n = S.shape[0]
+    i = np.arange(n, dtype=np.float64)
+    R = np.stack([np.sin(i + 0.37 * c) + 0.5 for c in range(8)])
+    out, staged = [], []
+    monkeypatch.delenv("LSBENCH_HIP_DIRECT_TIER_LDS", raising=False)
+    for cap in (None, 16):
+        if cap:
+            monkeypatch.setenv("LSBENCH_HIP_DIRECT_TIER_LDS", str(cap))
+        capfd.readouterr()
+        s = hip.Solver(as_matrix(S), _one_tier_opts(hip, verbose=1))
+        staged.append(int(re.search(r"windows of up to (\d+) doubles in LDS", capfd.readouterr().err).group(1)))
+        assert s.direct_tier_info()[0] == 1
+        z = _nan(n)
+        s.precond_dev(_dev(R[0]), z)
+        rec = [z.cpu().numpy()]
+        for k in (2, 8):
+            d_Z = torch.full((k, n), float("nan"), dtype=torch.float64, device="cuda:0")
+            s.direct_apply_multi_dev(_dev(R[:k]), d_Z)
+            rec.append(d_Z.cpu().numpy())
+            assert rec[-1][0].tobytes() == rec[0].tobytes()  # a column of a block: that column alone
+        s.destroy()
+        assert all(np.isfinite(a).all() for a in rec)
+        out.append([a.tobytes() for a in rec])
+    print(name, "n", n, "widest staged window without / with the knob:", staged)
+    assert 16 < staged[0] <= n  # without the knob a window wider than 16 doubles is staged
+    assert staged[1] <= 16      # ... with it none is: those windows are gathered
+    assert out[0] == out[1]
 
 
 @pytest.mark.gpu
