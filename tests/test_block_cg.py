@@ -30,8 +30,10 @@ PIVOT_FLOOR = 1e-10
 
 
 # ------------------------------------------------------------------------------------ the restatement
-def block_pcg(S, B, tol, maxit=20000):
-    """-> dict(rc, X, iters, status[k], rr[k], bb[k], relres[k], nspmm).  rc 3: rank-deficient at the start."""
+def block_pcg(S, B, tol, maxit=20000, trace=None):
+    """-> dict(rc, X, iters, status[k], rr[k], bb[k], relres[k], nspmm).  rc 3: rank-deficient at the start.
+    trace: a list that receives what the method holds -- the start's dict(G, sigma, W, P), then one dict per completed
+    iteration (Gam, xi, G, H, rr, zeta, sigma, W, P, X), copies -- for tests/test_block_cg_kernels.py."""
     n, k = B.shape
     dinv = 1.0 / S.diagonal()
     G = B.T @ (dinv[:, None] * B)
@@ -53,6 +55,8 @@ def block_pcg(S, B, tol, maxit=20000):
     W = sl.solve_triangular(L, B.T, lower=True).T  # B L^-T
     P = dinv[:, None] * W
     X = np.zeros((n, k))
+    if trace is not None:
+        trace.append(dict(G=G.copy(), sigma=sigma.copy(), W=W.copy(), P=P.copy()))
     thr = tol * tol * bb
     status = [RUNNING] * k
     it = nspmm = 0
@@ -92,6 +96,9 @@ def block_pcg(S, B, tol, maxit=20000):
         W = sl.solve_triangular(L, Wt.T, lower=True).T  # Wt zeta^-1
         P = dinv[:, None] * W + P @ zeta.T
         sigma = zeta @ sigma
+        if trace is not None:
+            trace.append(dict(Gam=Gam.copy(), xi=xi.copy(), G=G.copy(), H=H.copy(), rr=rr.copy(), zeta=zeta.copy(),
+                              sigma=sigma.copy(), W=W.copy(), P=P.copy(), X=X.copy()))
     out.update(X=X, iters=it, status=status, rr=rr, relres=np.sqrt(rr / bb), nspmm=nspmm)
     return out
 
@@ -260,8 +267,9 @@ def test_parity_with_the_restatement(hip, name, k, matrix_path):
 @pytest.mark.parametrize("k", WIDTHS)
 @pytest.mark.parametrize("name", OPERATORS)
 def test_maxit_cuts(hip, name, k, matrix_path):
-    """No getter exposes Q, so the cuts at 1, 2 and 3 iterations against the restatement stand in for the comparison
-    of the first Q with spmm_dev (seen: 2e-16 .. 3e-14 at every cut).  One iteration: 1e-13 relative.  Two and three: 1e-11 -- a step's k x k inverses
+    """The cuts at 1, 2 and 3 iterations against the restatement (seen: 2e-16 .. 3e-14 at every cut); Q against
+    spmm_dev and the small matrices are compared directly, launch by launch, in test_block_cg_kernels.py.  One
+    iteration: 1e-13 relative.  Two and three: 1e-11 -- a step's k x k inverses
     amplify what the step before left (an fp64 rounding, 1e-16 to 1e-15 relative) by at most the reciprocal of the Gram
     matrices' eigenvalue ratio, 1 / 0.09 = 11, once for Gamma and once for G."""
     path = _path(name, matrix_path)
