@@ -117,12 +117,20 @@ enum { LSB_PRECOND_JACOBI = 0, LSB_PRECOND_NONE = 1,
                                        in csr_init (src/cholmod-impl.h:25-26) and times
                                        only solves (:59-62); an application is two SpMVs,
                                        no triangular solve, no reduction        */
-       LSB_PRECOND_AMG = 6 };         /* smoothed-aggregation algebraic multigrid: one
+       LSB_PRECOND_AMG = 6,           /* smoothed-aggregation algebraic multigrid: one
                                        symmetric V-cycle with l1-Jacobi smoothing (or a
                                        Chebyshev polynomial in D^-1 A of the same cost:
                                        opts.amg_smoother), the hierarchy built on the
                                        host at solver creation (lsb_amg_setup), applied
                                        by hip_amg.hip; one shard, classic PCG  */
+       LSB_PRECOND_GMG = 7 };         /* geometric multigrid on a constant-coefficient 5- or
+                                       7-point grid operator (lsb_gmg_detect; anything else is
+                                       refused at creation): one symmetric V-cycle with damped
+                                       Jacobi smoothing, no matrix on any level -- every level
+                                       is the stencil, the kernels stream vectors only
+                                       (lsb_gmg.c, hip_gmg_drv.c, hip_gmg.hip).  Reads the
+                                       multigrid members amg_sweeps, amg_coarse and
+                                       amg_max_levels; one shard, fp64, classic PCG; opt-in */
 enum { LSB_AMG_SMOOTH_L1JACOBI = 0,   /* nu sweeps x += diag(sum_j |a_ij|)^-1 (b - A x)  */
        LSB_AMG_SMOOTH_CHEB = 1,       /* the Chebyshev polynomial of degree nu in D^-1 A on
                                        [rho / opts.amg_cheb_ratio, rho], rho the level's
@@ -266,7 +274,9 @@ struct lsb_hip_opts {
                         -1 = timed per solver at creation (tune_blas1_nt); else a mask
                         (bit 0 x, 1 p and q, 2 r in k_pcg_update_xr; 3 r, 4 p in
                         k_pcg_update_p; 5 k_cg1_update; 1 = all)              [-1] */
-  /* LSB_PRECOND_AMG (lsb_amg.c, hip_amg_drv.c, hip_amg.hip) */
+  /* LSB_PRECOND_AMG (lsb_amg.c, hip_amg_drv.c, hip_amg.hip).  amg_sweeps, amg_coarse and amg_max_levels are the
+   * multigrid members: LSB_PRECOND_GMG reads these three too (nu, the row count at which coarsening stops, the level
+   * cap) and ignores every other amg_* member */
   double amg_theta;  /* strength threshold: j strong for i when
                         |a_ij| >= theta sqrt(|a_ii a_jj|)                 [0.08] */
   int amg_sweeps;    /* l1-Jacobi sweeps before and after the coarse correction  [1] */
@@ -565,6 +575,28 @@ double lsb_amg_gershgorin(const struct csr *A);
  *   d_i <- fma(c2[k] / a_ii, b_i - s_i, c1[k] d_i),  x_i <- x_i + d_i ;  c1[0] = 0 and step 0 does not read d. */
 void lsb_amg_cheb_coeffs(double hi, double ratio, unsigned deg, double *c1, double *c2);
 void lsb_amg_free(struct lsb_amg_hier *h);
+/* Geometric multigrid on grids (LSB_PRECOND_GMG), pure host logic (lsb_gmg.c, rules there).
+ * lsb_gmg_detect: 0 when S (any base) is a constant-coefficient grid operator -- row (k ny + j) nx + i holds exactly a
+ * diagonal a and -c at each grid neighbour that exists, c > 0, a == 2 dim c, nx, ny [, nz] >= 2 -- and then *g is the
+ * grid (n[d] = 1 beyond dim); else the number of the rule it breaks: 1 fewer than 4 rows, 2 the pattern, 3 the
+ * off-diagonal value, 4 the diagonal.
+ * lsb_gmg_plan: the levels, lv[0] the grid itself with delta = 1; coarse points at the fine indices 2 j + 1, so
+ * n' = n / 2, delta' = delta / 2 (n even) or (1 + delta) / 2 (n odd), all dimensions together; stops at <= coarse
+ * rows, when some n_d < 4, or at max_levels (at most cap, the length of lv).  Returns the number of levels, -1 when the
+ * coarsest level would have more than LSB_GMG_COARSE_MAX rows (a very thin grid), -2 for a bad argument. */
+#define LSB_GMG_MAX_LEVELS 32
+#define LSB_GMG_COARSE_MAX 4096
+struct lsb_gmg_grid {
+  unsigned dim, n[3];
+  double c;
+};
+struct lsb_gmg_level {
+  unsigned n[3];
+  double delta[3]; /* distance from the last point to the far boundary, in the level's spacing */
+};
+int lsb_gmg_detect(const struct csr *S, struct lsb_gmg_grid *g);
+int lsb_gmg_plan(const struct lsb_gmg_grid *g, unsigned coarse, unsigned max_levels, struct lsb_gmg_level *lv,
+                 unsigned cap);
 /* Multicolour Gauss-Seidel smoothing (LSB_AMG_SMOOTH_MCGS), pure host logic.
  * lsb_amg_colour: the greedy colouring of A's stored pattern -- rows in ascending order, each takes the smallest
  * colour that none of its stored off-diagonal neighbours already holds (a stored zero counts); serial, so the same
@@ -897,6 +929,10 @@ int lsb_hip_solver_spmv_inner_dev(lsb_hip_solver *s, const double *d_x, double *
  * preconditioner that is not applied as a vector of its own (the diagonal ones: see
  * lsb_hip_solver_jacobi_sweep_dev). */
 int lsb_hip_solver_precond_dev(lsb_hip_solver *s, const double *d_r, double *d_z);
+/* For tests, LSB_PRECOND_GMG only (2 for every other solver): the same application in the solver's own numbering --
+ * buffers of n_local + lsb_hip_solver_padded rows, row (j, i) of a line-padded grid at j pitch + i, the pad rows of r
+ * to be 0 -- which is what the launches themselves read and write: tests look at the pad rows of z there. */
+int lsb_hip_solver_precond_padded_dev(lsb_hip_solver *s, const double *d_r, double *d_z);
 /* LSB_PRECOND_AMG: levels of the hierarchy, the coarsest included, and how many of them (with
  * the coarse solve) run in the one-launch tail; 2 for another preconditioner. */
 int lsb_hip_solver_amg_info(lsb_hip_solver *s, unsigned *levels, unsigned *tail_levels);
@@ -921,6 +957,17 @@ int lsb_hip_solver_amg_precision(lsb_hip_solver *s);
  * of x and reads b and dinv on colour 0 only; the residual, restriction and prolongation as on every level, 6 n.
  * Row offsets and rowid are left out, as the offsets are everywhere above. */
 unsigned long long lsb_hip_solver_amg_cycle_bytes(const lsb_hip_solver *s);
+/* LSB_PRECOND_GMG: the levels of the cycle, the coarsest included, the grid (dims[d] = 1 beyond its dimension) and the
+ * pitch of the fine level's grid lines in the solver's numbering (dims[0], or more under line padding); each may be
+ * NULL.  2 for another preconditioner. */
+int lsb_hip_solver_gmg_info(lsb_hip_solver *s, unsigned *levels, unsigned dims[3], unsigned *pitch);
+/* ... level l's points and delta per dimension (lsb_gmg_plan's); 2 for a level out of range */
+int lsb_hip_solver_gmg_level(lsb_hip_solver *s, unsigned level, unsigned n[3], double delta[3]);
+/* Bytes one application of the geometric V-cycle must move, 0 without it: vectors only.  Per level of n rows and n'
+ * coarse rows, 8 B per element pass -- fused (nu = 1): the way down reads b and writes x and b', 16 n + 8 n', the way
+ * up reads x, b and x' and writes the result, 24 n + 8 n'; plain steps: x = w b 16 n, each of the 2 nu - 1 sweeps
+ * 24 n, the restriction 16 n + 8 n', the prolongation 16 n + 8 n'.  The coarsest level: 8 nc^2 + 16 nc. */
+unsigned long long lsb_hip_solver_gmg_cycle_bytes(const lsb_hip_solver *s);
 /* The direct solver's factor (LSB_KRYLOV_DIRECT): entries of W = L^-1, height of the elimination tree, and the bytes
  * the two products of one round stream (16 per entry, and the index and vector traffic per row); each may be NULL.
  * 2 for any other solver. */

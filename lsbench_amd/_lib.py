@@ -22,6 +22,8 @@ SOLVER_HIP = 6
 OP_CHOLMOD_UPPER, OP_RAW = 0, 1
 PRECOND_JACOBI, PRECOND_NONE, PRECOND_L1JACOBI, PRECOND_CHEBYSHEV, PRECOND_BLOCKJACOBI, PRECOND_FSAI = 0, 1, 2, 3, 4, 5
 PRECOND_AMG = 6
+PRECOND_GMG = 7
+GMG_MAX_LEVELS, GMG_COARSE_MAX = 32, 4096
 AMG_SMOOTH_L1JACOBI, AMG_SMOOTH_CHEB, AMG_SMOOTH_MCGS = 0, 1, 2
 AMG_PREC_FP64, AMG_PREC_FP32 = 0, 1
 KRYLOV_PCG, KRYLOV_GMRES, KRYLOV_PCG1, KRYLOV_AUTO, KRYLOV_BICGSTAB, KRYLOV_RICHARDSON = 0, 1, 2, 3, 4, 5
@@ -138,6 +140,16 @@ class AmgHier(C.Structure):
     """struct lsb_amg_hier."""
     _fields_ = [("nlev", C.c_uint), ("lv", C.POINTER(AmgLevel)), ("nc", C.c_uint),
                 ("coarse_inv", C.POINTER(C.c_double))]
+
+
+class GmgGrid(C.Structure):
+    """struct lsb_gmg_grid."""
+    _fields_ = [("dim", C.c_uint), ("n", C.c_uint * 3), ("c", C.c_double)]
+
+
+class GmgLevel(C.Structure):
+    """struct lsb_gmg_level."""
+    _fields_ = [("n", C.c_uint * 3), ("delta", C.c_double * 3)]
 
 
 class Mcgs(C.Structure):
@@ -276,6 +288,8 @@ SIGNATURES = {
     "lsb_amg_gershgorin": (_d, [_csrp]),
     "lsb_csr_pack_f32": (C.POINTER(C.c_ulonglong), [_csrp]),
     "lsb_amg_cheb_coeffs": (None, [_d, _d, _u, C.POINTER(_d), C.POINTER(_d)]),
+    "lsb_gmg_detect": (_i, [_csrp, C.POINTER(GmgGrid)]),
+    "lsb_gmg_plan": (_i, [C.POINTER(GmgGrid), _u, _u, C.POINTER(GmgLevel), _u]),
     "lsb_amg_colour": (C.POINTER(C.c_int), [_csrp, C.POINTER(_u)]),
     "lsb_csr_mcgs": (C.POINTER(Mcgs), [_csrp, C.POINTER(C.c_int), _u]),
     "lsb_mcgs_free": (None, [C.POINTER(Mcgs)]),
@@ -325,9 +339,13 @@ SIGNATURES = {
     "lsb_hip_solver_precond_multi_dev": (_i, [_vp, _u, _vp, C.c_size_t, _vp, C.c_size_t]),
     "lsb_hip_solver_fsai_nnz": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "lsb_hip_solver_precond_dev": (_i, [_vp, _vp, _vp]),
+    "lsb_hip_solver_precond_padded_dev": (_i, [_vp, _vp, _vp]),
     "lsb_hip_solver_amg_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u)]),
     "lsb_hip_solver_amg_precision": (_i, [_vp]),
     "lsb_hip_solver_amg_cycle_bytes": (C.c_ulonglong, [_vp]),
+    "lsb_hip_solver_gmg_info": (_i, [_vp, C.POINTER(_u), C.POINTER(_u), C.POINTER(_u)]),
+    "lsb_hip_solver_gmg_level": (_i, [_vp, _u, C.POINTER(_u), C.POINTER(_d)]),
+    "lsb_hip_solver_gmg_cycle_bytes": (C.c_ulonglong, [_vp]),
     "lsb_hip_solver_direct_info": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(_u), C.POINTER(C.c_ulonglong)]),
     "lsb_hip_solver_create_direct": (_vp, [_csrp, C.POINTER(Opts), _i]),
     "lsb_hip_solver_direct_tier_info": (_i, [_vp, C.POINTER(_u), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),

@@ -166,6 +166,28 @@ def lsb_csr_sellize16(A, row_begin=0):
     return sptr, codes, sbase, vals
 
 
+def lsb_gmg_detect(A):
+    """lsb_gmg_detect: (0, {"dim", "n": (nx, ny, nz), "c"}) for a constant-coefficient grid operator, else (the number
+    of the rule it breaks, None)."""
+    g = L.GmgGrid()
+    rc = int(L.load().lsb_gmg_detect(A.ptr, C.byref(g)))
+    return (rc, None) if rc else (0, {"dim": int(g.dim), "n": tuple(int(v) for v in g.n), "c": float(g.c)})
+
+
+def lsb_gmg_plan(dims, coarse=256, max_levels=20, c=1.0):
+    """lsb_gmg_plan for the grid dims = (nx, ny[, nz]): the levels as a list of ((n_d), (delta_d)), each of len(dims)
+    entries; None where the coarsest level would be too large (-1)."""
+    dim = len(dims)
+    g = L.GmgGrid(dim, (C.c_uint * 3)(*(list(dims) + [1] * (3 - dim))), c)
+    lv = (L.GmgLevel * L.GMG_MAX_LEVELS)()
+    rc = int(L.load().lsb_gmg_plan(C.byref(g), coarse, max_levels, lv, L.GMG_MAX_LEVELS))
+    if rc == -1:
+        return None
+    if rc < 1:
+        raise L.LsbenchHipError("lsb_gmg_plan: bad argument (rc=%d)" % rc)
+    return [(tuple(int(v) for v in lv[l].n[:dim]), tuple(float(v) for v in lv[l].delta[:dim])) for l in range(rc)]
+
+
 def lsb_amg_colour(A):
     """(colour of every row as int32, number of colours) by the greedy rule of lsb_amg_colour."""
     nc = C.c_uint()
@@ -598,6 +620,11 @@ class Solver:
         """z = M^-1 r once with the solver's preconditioner (device buffers, n_local each)."""
         L.check(L.load().lsb_hip_solver_precond_dev(self._h, _ptr(d_r), _ptr(d_z)), "precond_dev")
 
+    def precond_padded_dev(self, d_r, d_z):
+        """For tests, GMG solvers only: z = M^-1 r in the solver's own numbering (n_local + padded rows each; the pad
+        rows of r are 0)."""
+        L.check(L.load().lsb_hip_solver_precond_padded_dev(self._h, _ptr(d_r), _ptr(d_z)), "precond_padded_dev")
+
     def precond_multi_dev(self, d_R, d_Z):
         """Z = M^-1 R (AMG: one V-cycle per column; FSAI with opts.fsai_blocks: G^T (G r)) for the nrhs columns held
         as the ROWS of two 2-D device tensors (ld = stride(0)); under AMG a column of Z has the bits of precond_dev
@@ -635,6 +662,32 @@ class Solver:
     def amg_cycle_bytes(self):
         """Bytes one application of the AMG V-cycle must move (0 without AMG)."""
         return int(L.load().lsb_hip_solver_amg_cycle_bytes(self._h))
+
+    @property
+    def gmg_info(self):
+        """(levels, (nx, ny, nz), pitch of the fine level's lines) of a GMG-preconditioned solver; None for any
+        other."""
+        lv, dims, pitch = C.c_uint(), (C.c_uint * 3)(), C.c_uint()
+        rc = L.load().lsb_hip_solver_gmg_info(self._h, C.byref(lv), dims, C.byref(pitch))
+        if rc == 2:
+            return None
+        L.check(rc, "gmg_info")
+        return int(lv.value), tuple(int(v) for v in dims), int(pitch.value)
+
+    def gmg_level(self, level):
+        """((n_d), (delta_d)), three entries each, of one level of a GMG-preconditioned solver; None for a level out
+        of range or another preconditioner."""
+        n, delta = (C.c_uint * 3)(), (C.c_double * 3)()
+        rc = L.load().lsb_hip_solver_gmg_level(self._h, level, n, delta)
+        if rc == 2:
+            return None
+        L.check(rc, "gmg_level")
+        return tuple(int(v) for v in n), tuple(float(v) for v in delta)
+
+    @property
+    def gmg_cycle_bytes(self):
+        """Bytes one application of the geometric V-cycle must move (0 without it)."""
+        return int(L.load().lsb_hip_solver_gmg_cycle_bytes(self._h))
 
     @property
     def direct_info(self):

@@ -116,7 +116,8 @@ static const struct optchoice CH_OPERATOR[] = {{"upper", LSB_OP_CHOLMOD_UPPER}, 
 static const struct optchoice CH_PRECOND[] = {{"jacobi", LSB_PRECOND_JACOBI},   {"none", LSB_PRECOND_NONE},
                                               {"l1", LSB_PRECOND_L1JACOBI},     {"cheb", LSB_PRECOND_CHEBYSHEV},
                                               {"bj", LSB_PRECOND_BLOCKJACOBI},  {"fsai", LSB_PRECOND_FSAI},
-                                              {"amg", LSB_PRECOND_AMG},         {NULL, 0}};
+                                              {"amg", LSB_PRECOND_AMG},         {"gmg", LSB_PRECOND_GMG},
+                                              {NULL, 0}};
 static const struct optchoice CH_AMG_SMOOTHER[] = {{"l1", LSB_AMG_SMOOTH_L1JACOBI}, {"cheb", LSB_AMG_SMOOTH_CHEB},
                                                   {"mcgs", LSB_AMG_SMOOTH_MCGS}, {NULL, 0}};
 static const struct optchoice CH_AMG_PRECISION[] = {{"fp64", LSB_AMG_PREC_FP64}, {"fp32", LSB_AMG_PREC_FP32}, {NULL, 0}};

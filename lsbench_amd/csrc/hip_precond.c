@@ -1,6 +1,6 @@
 /*
  * Host side of the preconditioners that are not a diagonal scaling (kernels:
- * hip_precond_k.hip; AMG: hip_amg_drv.c): set-up at solver creation
+ * hip_precond_k.hip; AMG: hip_amg_drv.c; GMG: hip_gmg_drv.c): set-up at solver creation
  * (untimed, like the reference's csr_init / CHOLMOD's factorisation,
  * src/cholmod-impl.h:25-26) and the launches of one application z = M^-1 r.
  */
@@ -9,7 +9,7 @@
 
 int generic_precond(const lsb_hip_solver *sv) {
   return sv->o.precond == LSB_PRECOND_CHEBYSHEV || sv->o.precond == LSB_PRECOND_BLOCKJACOBI ||
-         sv->o.precond == LSB_PRECOND_FSAI || sv->o.precond == LSB_PRECOND_AMG;
+         sv->o.precond == LSB_PRECOND_FSAI || sv->o.precond == LSB_PRECOND_AMG || sv->o.precond == LSB_PRECOND_GMG;
 }
 
 /* ---- FSAI: G on the pattern of tril(S^k), rows by batched dense solves on the device ------- */
@@ -131,6 +131,8 @@ void precond_shard_blocks(struct shard *s, const int *offs, const int *cols, con
     precond_shard_fsai(s, offs, cols, vals, o);
   if (o->precond == LSB_PRECOND_AMG)
     precond_shard_amg(s, offs, cols, vals, o);
+  if (o->precond == LSB_PRECOND_GMG)
+    precond_shard_gmg(s, o);
   if (o->precond != LSB_PRECOND_BLOCKJACOBI)
     return;
   unsigned bs = o->block_size < 1 ? 1u : (unsigned)o->block_size;
@@ -233,6 +235,8 @@ void precond_setup(lsb_hip_solver *sv) {
       s->d_chd = shard_vec(s, s->n);
     if (sv->o.precond == LSB_PRECOND_AMG)
       amg_finish_setup(s);
+    if (sv->o.precond == LSB_PRECOND_GMG)
+      gmg_finish_setup(s);
   }
   if (sv->o.precond != LSB_PRECOND_CHEBYSHEV)
     return;
@@ -327,6 +331,11 @@ void precond_apply(lsb_hip_solver *sv, int after_update) {
     amg_cycle(&c);
     return;
   }
+  if (sv->o.precond == LSB_PRECOND_GMG) { /* z = one geometric V-cycle */
+    const struct shard *s = &sv->sh[0];
+    gmg_cycle(s, s->d_r, s->d_z, s->d_st);
+    return;
+  }
   if (sv->o.precond == LSB_PRECOND_BLOCKJACOBI) {
     for (int i = 0; i < sv->nshard; i++) {
       struct shard *s = &sv->sh[i];
@@ -389,6 +398,7 @@ void precond_free_shard(struct shard *s) {
   shard_vec_free(s, s->d_zfull2);
   fsai_free_csr(&s->fs_g), fsai_free_csr(&s->fs_gt), shard_vec_free(s, s->d_fst);
   amg_free(s);
+  gmg_free(s);
 }
 
 /* z = M^-1 r once, outside a solve: r goes where the solve keeps it, the state is set running (the
@@ -422,6 +432,23 @@ int lsb_hip_solver_precond_dev(lsb_hip_solver *sv, const double *d_r, double *d_
     lsb_k_perm_scatter(sv->n_here, sv->d_perm, sv->d_xp, d_z, g_stream);
   drain_stream(sv, "lsb_hip_solver_precond_dev");
   check_aux_status(sv, "lsb_hip_solver_precond_dev");
+  return 0;
+}
+
+/* ... of a GMG solver in its own numbering: what the launches read and write, the pad rows of a line-padded grid
+ * included (for tests) */
+int lsb_hip_solver_precond_padded_dev(lsb_hip_solver *sv, const double *d_r, double *d_z) {
+  if (!lsb_initialized)
+    return 1;
+  if (!sv || !d_r || !d_z || sv->o.precond != LSB_PRECOND_GMG || sv->nshard != 1 || sv->dist)
+    return 2;
+  struct shard *s = &sv->sh[0];
+  LSB_CHK_HIP(hipMemcpyAsync(s->d_r, d_r, (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice, g_stream));
+  LSB_CHK_HIP(hipMemsetAsync(&s->d_st->status, 0, sizeof(int), g_stream));
+  precond_apply(sv, 0);
+  LSB_CHK_HIP(hipMemcpyAsync(d_z, s->d_z, (size_t)s->n * sizeof(double), hipMemcpyDeviceToDevice, g_stream));
+  drain_stream(sv, "lsb_hip_solver_precond_padded_dev");
+  check_aux_status(sv, "lsb_hip_solver_precond_padded_dev");
   return 0;
 }
 

@@ -519,6 +519,8 @@ void shard_upload(struct shard *s, const struct csr *S, unsigned r0,
     else if (o->precond == LSB_PRECOND_AMG)
       cnt += 3 * (size_t)n;                                    /* z, the fine level's second smoothing
                                                                   buffer and its residual */
+    else if (o->precond == LSB_PRECOND_GMG)
+      cnt += 2 * (size_t)n;                                    /* z, the fine level's other smoothing buffer */
     if (o->krylov == LSB_KRYLOV_BICGSTAB)
       cnt += 3 * (size_t)n + n_glob;                           /* t, p, the shadow residual; the gather vector of s^ */
     if (fused_p)
@@ -696,6 +698,7 @@ static struct lsb_hip_opts solver_opts(const struct lsb_hip_opts *o_in, int shar
             o.krylov == LSB_KRYLOV_GMRES ? "GMRES" : "BiCGSTAB");
     o.precision = LSB_PREC_FP64;
   }
+  gmg_check(&o, sharded);
   bicgstab_check_precond(&o);
   richardson_check(&o, sharded);
   direct_check(&o, sharded);
@@ -722,6 +725,15 @@ static lsb_hip_solver *solver_create(const struct csr *A, const struct lsb_hip_o
   struct lsb_tierinv *dirT = NULL;
   if (o.krylov == LSB_KRYLOV_DIRECT)
     dirT = direct_factor(S, &o, tiers, &dir_height, &dir_seconds);
+  /* geometric multigrid: the grid is read off the operator as the caller numbers it, before any padding */
+  struct lsb_gmg_grid gmg_grid = {0, {0, 0, 0}, 0.0};
+  unsigned gmg_pitch = 0;
+  if (o.precond == LSB_PRECOND_GMG) {
+    const int why = lsb_gmg_detect(S, &gmg_grid);
+    if (why)
+      errx(EXIT_FAILURE, "hip_cdna4: --precond gmg needs a constant-coefficient grid operator (the 5- or 7-point "
+                         "Laplacian, diagonal 2 dim c, off-diagonals -c); this one is refused: %s", lsb_gmg_why(why));
+  }
   /* a constant-coefficient 2-D grid whose lines are not whole slices: pad the lines (lsb_csr_pad_lines) --
    * the +-nx diagonals become whole-slice offsets and the z-column forms apply along y.  b and x
    * travel through the same gather / scatter as a re-ordering's; the pad unknowns stay exactly 0.
@@ -739,6 +751,7 @@ static lsb_hip_solver *solver_create(const struct csr *A, const struct lsb_hip_o
                   Sp->nrows);
         lsb_csr_free(S);
         S = Sp;
+        gmg_pitch = nxp;
       }
     }
   }
@@ -776,6 +789,7 @@ static lsb_hip_solver *solver_create(const struct csr *A, const struct lsb_hip_o
   /* b and x of a padded / re-ordered solver: with one shard out of its slab, x right behind the directions (the
    * two-launch iteration streams r, both direction buffers and x); with several, allocations of their own */
   sv->sh[0].slab_bx = sv->d_perm && P == 1;
+  sv->sh[0].gmg_grid = gmg_grid, sv->sh[0].gmg_pitch = gmg_pitch;
   for (int q = 0; q < P; q++) {
     shard_upload(&sv->sh[q], S, bounds[q], bounds[q + 1], 0, bounds[q], S->nrows, &o);
     hull[4 * q] = bounds[q], hull[4 * q + 1] = bounds[q + 1] - bounds[q];

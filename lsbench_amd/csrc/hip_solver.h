@@ -292,6 +292,23 @@ struct shard {
     unsigned long long cycle_mat_bytes, cycle_vec_rows;
     unsigned long long cycle_bytes32; /* what lsb_hip_solver_amg_cycle_bytes answers under fp32 */
   } *amg;
+  /* Geometric multigrid (PRECOND_GMG; hip_gmg_drv.c, hip_gmg.hip).  gmg_grid / gmg_pitch: what the creator detected on
+   * the operator before line padding and the pitch of its lines after it, handed over before shard_upload (dim = 0:
+   * nothing was handed over -- a shard of a sharded solver).  gmg: the levels as the kernels take them, their vectors
+   * (level 0: b and buf[1] are the caller's r and z, buf[0] comes out of the slab; below it one allocation, mem), the
+   * coarsest level's dense inverse, and what a cycle streams */
+  struct lsb_gmg_grid gmg_grid;
+  unsigned gmg_pitch;
+  struct gmg_dev {
+    unsigned dim, nlev, nu, nc, clanes;
+    int fused; /* nu == 1 and not LSBENCH_HIP_GMG_FUSE=0: k_gmg_down / k_gmg_up in the place of the plain steps */
+    struct lsb_gmg_level plan[LSB_GMG_MAX_LEVELS];
+    struct lsb_gmg_lv lv[LSB_GMG_MAX_LEVELS];
+    double *b[LSB_GMG_MAX_LEVELS], *buf[LSB_GMG_MAX_LEVELS][2];
+    double *mem, *d_cinv;
+    unsigned long long cycle_bytes;
+    double setup_s;
+  } *gmg;
   struct lsb_xfer *recv, *send;
   int nrecv, nsend;
 };
@@ -619,6 +636,14 @@ LSB_INTERNAL void precond_shard_blocks(struct shard *s, const int *offs, const i
 LSB_INTERNAL void precond_setup(lsb_hip_solver *sv);
 LSB_INTERNAL void precond_apply(lsb_hip_solver *sv, int after_update);
 LSB_INTERNAL void precond_free_shard(struct shard *s);
+/* hip_gmg_drv.c: what LSB_PRECOND_GMG cannot run with is refused (gmg_check, before anything is built); the levels of
+ * a shard that was handed its grid; level 0's buffer out of the slab, behind d_zfull; z = one V-cycle of r, on the
+ * solver's stream, nothing allocated and nothing synchronised; free */
+LSB_INTERNAL void gmg_check(const struct lsb_hip_opts *o, int sharded);
+LSB_INTERNAL void precond_shard_gmg(struct shard *s, const struct lsb_hip_opts *o);
+LSB_INTERNAL void gmg_finish_setup(struct shard *s);
+LSB_INTERNAL void gmg_cycle(const struct shard *s, const double *r, double *z, const struct lsb_pcg_state *st);
+LSB_INTERNAL void gmg_free(struct shard *s);
 /* hip_amg_drv.c */
 LSB_INTERNAL void precond_shard_amg(struct shard *s, const int *offs, const int *cols, const double *vals,
                                     const struct lsb_hip_opts *o);

@@ -368,12 +368,14 @@ static struct csr *amg_prolongator(const struct csr *A, const double *d, const i
   return P;
 }
 
-/* dense inverse of the SPD coarsest operator: Cholesky A = L L^T, then A^-1 column by column */
-static double *amg_coarse_inverse(const struct csr *A) {
+/* dense inverse of the SPD coarsest operator: Cholesky A = L L^T, then A^-1 column by column (the geometric
+ * cycle's coarsest level comes here too: who = the option the messages name, what = the inverse as the out-of-memory
+ * message calls it) */
+double *lsb_amg_coarse_inverse(const struct csr *A, const char *who, const char *what) {
   const unsigned n = A->nrows;
   double *L = lsb_calloc(double, (size_t)n * n), *X = lsb_calloc(double, (size_t)n * n);
   if (!L || !X)
-    errx(EXIT_FAILURE, "hip_cdna4: out of host memory for the AMG coarse inverse (%u rows)", n);
+    errx(EXIT_FAILURE, "hip_cdna4: out of host memory for %s (%u rows)", what, n);
   for (unsigned i = 0; i < n; i++)
     for (unsigned e = A->offs[i]; e < A->offs[i + 1]; e++)
       L[(size_t)i * n + A->cols[e]] = A->vals[e];
@@ -382,8 +384,8 @@ static double *amg_coarse_inverse(const struct csr *A) {
     for (unsigned t = 0; t < k; t++)
       p -= L[(size_t)k * n + t] * L[(size_t)k * n + t];
     if (!(p > 0.0))
-      errx(EXIT_FAILURE, "hip_cdna4: --precond amg needs a symmetric positive definite operator (the "
-                         "coarsest level's Cholesky met a pivot <= 0 in row %u of %u)", k, n);
+      errx(EXIT_FAILURE, "hip_cdna4: %s needs a symmetric positive definite operator (the "
+                         "coarsest level's Cholesky met a pivot <= 0 in row %u of %u)", who, k, n);
     const double lkk = sqrt(p);
     L[(size_t)k * n + k] = lkk;
 #pragma omp parallel for schedule(static)
@@ -457,7 +459,7 @@ struct lsb_amg_hier *lsb_amg_setup(const struct csr *S, double theta, unsigned c
     errx(EXIT_FAILURE, "hip_cdna4: AMG coarsening stopped at %u rows (level %u), more than the %d a dense "
                        "coarse solve takes; raise --amg-max-levels or --amg-theta", h->nc, h->nlev,
          AMG_MAX_COARSE_DENSE);
-  h->coarse_inv = amg_coarse_inverse(h->lv[h->nlev - 1].A);
+  h->coarse_inv = lsb_amg_coarse_inverse(h->lv[h->nlev - 1].A, "--precond amg", "the AMG coarse inverse");
   return h;
 }
 

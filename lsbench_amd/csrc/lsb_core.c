@@ -88,7 +88,7 @@ static void usage(const char *prog) {
   printf("                       0 = the fewest that fit, 1 = the single skyline (default), at most 6\n");
   printf("                       (bicgstab + Jacobi is the reference's Ginkgo backend; its stop setting is --tol 1e-4)\n");
   printf("  --restart <M>        (hip) GMRES restart length, 1..32, default 30\n");
-  printf("  --precond <jacobi|l1|none|cheb|bj|fsai|amg> (hip) diag(S); diag(sum_j |S_ij|); none; Chebyshev\n");
+  printf("  --precond <jacobi|l1|none|cheb|bj|fsai|amg|gmg> (hip) diag(S); diag(sum_j |S_ij|); none; Chebyshev\n");
   printf("                       polynomial in D^-1 S (--cheb-degree M, default 4); block-Jacobi with\n");
   printf("                       dense inverted blocks of --block-size B rows (default 8; B >= n = a\n");
   printf("                       cached dense inverse, for operators of a few thousand rows); fsai =\n");
@@ -108,7 +108,11 @@ static void usage(const char *prog) {
   printf("                       --amg-precision <fp64|fp32>: fp32 = the whole V-cycle (matrices, level\n");
   printf("                       vectors, coarse inverse) in single precision inside the fp64 Krylov loop:\n");
   printf("                       8 instead of 12 bytes per entry, 4 instead of 8 per vector element; no\n");
-  printf("                       one-launch tail, no blocks of right-hand sides (default fp64)\n");
+  printf("                       one-launch tail, no blocks of right-hand sides (default fp64);\n");
+  printf("                       gmg = geometric multigrid for the constant-coefficient 5- / 7-point grid\n");
+  printf("                       Laplacians (lap2d, lap3d; anything else is refused): one V-cycle with NU\n");
+  printf("                       damped Jacobi sweeps, no matrix on any level; reads --amg-sweeps NU,\n");
+  printf("                       --amg-coarse ROWS and --amg-max-levels L; one shard, fp64, cg only\n");
   printf("  --ngpus <N>          (hip) row-partition the operator over N GPUs of this node\n");
   printf("                       (0 = all visible), driven from this one process\n");
   printf("  --reorder            (hip) solve the RCM-permuted operator (any --ordering\n");

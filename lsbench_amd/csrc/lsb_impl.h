@@ -650,6 +650,44 @@ void lsb_k_amg32_mcgs_first(unsigned n, int in64, const unsigned char *colour, c
 void lsb_k_amg32_mcgs(const struct amg_mat32 *m, const int *rowid, unsigned p0, unsigned p1, float *x, const float *b,
                       const float *dinv, double *z64, const struct lsb_pcg_state *st, void *stream);
 
+/* ---- geometric multigrid on grids (lsb_gmg.c, hip_gmg.hip; LSB_PRECOND_GMG) ----
+ * the rest of the host logic: why lsb_gmg_detect refused; the 2^dim diagonals D and smoothing weights w = omega / D of
+ * a level, indexed by the mask of far faces a point lies on (bit d: i_d == n_d - 1); the level's operator as a CSR;
+ * AMG's dense inverse of a coarsest operator (lsb_amg.c), who = the option its messages name, what = the inverse
+ * as its out-of-memory message calls it */
+const char *lsb_gmg_why(int rc);
+void lsb_gmg_diagonals(unsigned dim, double c, const double delta[3], double D[8], double w[8]);
+struct csr *lsb_gmg_level_csr(unsigned dim, double c, const struct lsb_gmg_level *lv);
+double *lsb_amg_coarse_inverse(const struct csr *A, const char *who, const char *what);
+/* A level as the kernels take it, by value: its points n and the next level's nc per dimension (1 beyond the grid's),
+ * the doubles between grid lines (n[0], or more on a line-padded fine level: the lanes i >= n[0] of a line write 0),
+ * c, sigma, per dimension what the last fine point of an odd n takes of the last coarse one, delta / (1 + delta), and
+ * the diagonals and weights by far-face mask.  Point (i, j, k) is element (k n[1] + j) pitch + i. */
+struct lsb_gmg_lv {
+  unsigned n[3], pitch;
+  unsigned nc[3], pad_;
+  double c, sigma, wlast[3];
+  double D[8], w[8];
+};
+/* The steps of the cycle on one level, dim = 2 or 3.  first: x = w b.  sweep: y = x + w (b - A x), out of place.
+ * restrict: bc = sigma P^T (b - A x), a coarse point forms the 3^dim fine residuals it needs.  prolong: x += P xc.
+ * down = first and restrict in one launch (the residual of x = w b needs only b): writes x and bc.  up = prolong and
+ * one sweep: y = u + w (b - A u), u = x + P xc on a tile with a one-point halo in LDS.  Each step's arithmetic is one
+ * device function shared by the plain and the fused kernel: the two paths give the same bits.  The gate `st` as
+ * hip_amg.hip's launchers. */
+void lsb_k_gmg_first(unsigned dim, const struct lsb_gmg_lv *lv, const double *b, double *x,
+                     const struct lsb_pcg_state *st, void *stream);
+void lsb_k_gmg_sweep(unsigned dim, const struct lsb_gmg_lv *lv, const double *xin, const double *b, double *y,
+                     const struct lsb_pcg_state *st, void *stream);
+void lsb_k_gmg_restrict(unsigned dim, const struct lsb_gmg_lv *lv, const double *x, const double *b, double *bc,
+                        const struct lsb_pcg_state *st, void *stream);
+void lsb_k_gmg_prolong(unsigned dim, const struct lsb_gmg_lv *lv, double *x, const double *xc,
+                       const struct lsb_pcg_state *st, void *stream);
+void lsb_k_gmg_down(unsigned dim, const struct lsb_gmg_lv *lv, const double *b, double *x, double *bc,
+                    const struct lsb_pcg_state *st, void *stream);
+void lsb_k_gmg_up(unsigned dim, const struct lsb_gmg_lv *lv, const double *x, const double *b, const double *xc,
+                  double *y, const struct lsb_pcg_state *st, void *stream);
+
 /* ---- backend internals shared between hip_cdna4.c and hip_comm.c -------- */
 void *lsb_hip_stream(void);
 int lsb_hip_is_initialized(void);
